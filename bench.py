@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: audio-sec/s training throughput, Conformer-CTC-Large (BASELINE.json), MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 One "step" = one full optimizer step of the drop-in EncDecCTCModel on a synthetic batch resident in HBM:
@@ -9,9 +9,12 @@ log-mel front-end -> conv sub-sampling -> 18 Conformer blocks -> decoder -> CTC 
 gradient all-reduce (N > 1, overlapped on a side stream) -> fused AdamW + Noam step; train mode (dropout, dither,
 batch-statistics BatchNorm with SyncBN across ranks), bf16 compute with fp32 master weights.  Per-GPU batch is fixed
 (weak scaling): 32 x 20 s clips of 16 kHz audio, 60 target tokens each, vocab 128 + blank.
-Prints ONE JSON line (rank 0) -- see the README/DESIGN.md for the fields; `roofline` is measured live with HIP events
-around every launch of the dominant GEMM kernel in one extra step, `cpu_baseline` times the CPU oracle (oracle/) on the
-host cores on a bounded sample of the same workload.
+Prints ONE JSON line (rank 0) -- see the README/DESIGN.md for the fields.  A plain run sets up, warms up, times the K steps
+and prints the line.  --full adds the measurements that take work of their own: `roofline` (HIP events around every launch
+of the dominant GEMM kernel in one extra step, the HBM-bound kernels and the vendor library timed on their own),
+`cpu_baseline` (the CPU oracle, oracle/, timed on the host cores on a bounded sample of the same workload) and, for N > 1,
+the instrumented exchange steps behind `distributed`.  --dump-outputs DIR writes what the last timed step computed
+(dump_outputs below).
 """
 import argparse
 import json
@@ -60,6 +63,12 @@ def parse():
                          "recorded launch sequences replayed per padded length, auto = both timed on the device, the faster kept")
     ap.add_argument("--cpu-batch", type=int, default=2)
     ap.add_argument("--cpu-steps", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline number does not need: roofline (unless --no-roofline), cpu_baseline (unless "
+                         "--no-cpu-baseline) and, with --gpus > 1, the instrumented gradient / SyncBN exchange steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the loss and the "
+                         "parameters the step left in every flat buffer (a fixed seeded sample of the large ones)")
     return ap.parse_args()
 
 
@@ -126,6 +135,27 @@ def var_len_batches(a, rank, world, vocab, dev):
     pad = 1.0 - sum(valid) / sum(float(durs[ib].max()) * len(ib) for ib in idx_batches)
     return batches, valid, {"durations": f"uniform {lo:g}-{hi:g} s", "sampler": a.sampler + (f" ({a.buckets} buckets)" if a.sampler == "bucket" else ""),
                             "padded_sample_fraction": round(pad, 4), "distinct_padded_lengths": len({b[0].shape[1] for b in batches})}
+
+
+def dump_outputs(out_dir, model, loss, budget_bytes=64 << 20):
+    """--dump-outputs: what a caller of the timed step holds after the last one, as float32 .npy files -- the loss (`loss`) and,
+    per module that owns a flat parameter buffer, the parameters the optimizer step left (`params_<module>`).  A buffer larger
+    than its equal share of `budget_bytes` is written as a fixed sample: the sorted unique indices of numpy RandomState(0) draws,
+    the same in every run and every build.  (The step's gradients are not written: on the headline workload two runs of one
+    build leave gradients ~5 % apart in relative L2 norm, parameters ~1e-5, the loss ~3e-4.)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    names = {id(m): n for n, m in model.named_children()}
+    arrays = [("loss", loss.detach())]
+    for m in model.trainable_modules():
+        arrays.append((f"params_{names[id(m)]}", m.flat_parameters().flat))
+    share = budget_bytes // 4 // len(arrays)
+    for name, t in arrays:
+        t = t.detach().reshape(-1)
+        if t.numel() > share:
+            idx = np.unique(np.random.RandomState(0).randint(0, t.numel(), size=share))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline(size, secs, vocab, batch, steps, budget_s=40.0):
@@ -359,6 +389,8 @@ def self_launch(a):
 
 def main():
     a = parse()
+    if not a.full:
+        a.no_roofline = a.no_cpu_baseline = True
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         raise SystemExit(self_launch(a))
     rank = int(os.environ.get("RANK", "0"))
@@ -555,6 +587,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = t.item()
     ms = dt / a.steps * 1e3
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, loss)
     if a.var_len:
         tv = torch.tensor([timed_valid], device=dev, dtype=torch.float64)
         if world > 1:
@@ -584,6 +618,19 @@ def main():
         dist_info["rccl_version"] = f"unavailable ({type(e).__name__})"
     if world > 1:
         syncs = model._grad_syncs()
+        dist_info.update({
+            "grad_allreduce_launches_per_step": sum(gs.launches_last_step for gs in syncs),
+            "grad_bytes_per_step": int(sum(gs.grad.numel() * 4 for gs in syncs)),
+            "bucket_bytes": int(syncs[0].bucket_elems * 4),
+            "tail_bytes": int(syncs[0].tail_elems * 4),
+            "grad_wire_dtype": "bf16" if syncs[0].wire_dtype is not None else "fp32",
+            "syncbn_own_process_group": os.environ.get("MI355X_SYNCBN_OWN_GROUP", "0") == "1",
+            # how the statistics travel: "mailbox" = one kernel launch per exchange over peer-mapped memory (csrc/mailbox.hip),
+            # "process group" = torch.distributed.all_reduce
+            "syncbn_exchange": ("mailbox" if getattr(model.encoder, "_syncbn_mailbox", None) is not None else "process group"),
+        })
+    if world > 1 and a.full:
+        # two instrumented steps: exposed exchange time, SyncBN exchanges and per-bucket all-reduce times
         for gs in syncs:
             gs.profile = True
         enc = model.encoder
@@ -603,22 +650,13 @@ def main():
         t = torch.tensor([exposed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dist_info.update({
-            "grad_allreduce_launches_per_step": sum(gs.launches_last_step for gs in syncs),
-            "grad_bytes_per_step": int(sum(gs.grad.numel() * 4 for gs in syncs)),
-            "bucket_bytes": int(syncs[0].bucket_elems * 4),
             "exposed_exchange_ms_max_over_ranks": round(float(t.item()), 3),
             "syncbn_allreduces_per_step": n_syncbn,
             "syncbn_exposed_ms_this_rank": round(syncbn_ms, 3),
-            "grad_wire_dtype": "bf16" if syncs[0].wire_dtype is not None else "fp32",
             # every all-reduce of the last instrumented step on this rank, in issue order: [MiB, ms on the exchange stream from its
             # enqueue to its completion]; the last entry of the encoder's list is the tail bucket (cut to <= tail_bytes)
             "buckets_mib_ms_this_rank": [[round(n_ * 4 / 2 ** 20, 2), round(e0.elapsed_time(e1), 3)]
                                          for gs in syncs for (n_, e0, e1) in gs.bucket_events_last_step],
-            "tail_bytes": int(syncs[0].tail_elems * 4),
-            "syncbn_own_process_group": os.environ.get("MI355X_SYNCBN_OWN_GROUP", "0") == "1",
-            # how the statistics travel: "mailbox" = one kernel launch per exchange over peer-mapped memory (csrc/mailbox.hip),
-            # "process group" = torch.distributed.all_reduce
-            "syncbn_exchange": ("mailbox" if getattr(model.encoder, "_syncbn_mailbox", None) is not None else "process group"),
         })
 
     roof = None

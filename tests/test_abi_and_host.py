@@ -524,6 +524,28 @@ def test_bench_refuses_a_multi_gpu_job_it_cannot_place():
     assert r.returncode != 0 and "{" not in r.stdout and "WORLD_SIZE=2" in r.stderr, (r.returncode, r.stdout[-200:], r.stderr[-300:])
 
 
+def test_bench_dump_outputs_writes_float32_arrays_under_the_cap(tmp_path):
+    """`bench.py --dump-outputs DIR`: the loss and every flat buffer's parameters as float32 .npy, within the size cap; a buffer
+    above its share is a sample at fixed seeded indices, so two dumps of one state are identical"""
+    import bench
+    from nemo_amd.models import EncDecCTCModel, conformer_ctc_config
+    torch.manual_seed(0)
+    m = EncDecCTCModel(conformer_ctc_config("small", vocab_size=20, d_model=64, n_heads=4, n_layers=2))
+    cap = 200_000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), m, torch.tensor(3.5), budget_bytes=cap)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["loss.npy", "params_decoder.npy", "params_encoder.npy"]
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert got[n[:-4]].dtype == np.float32 and np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n))
+    assert sum(x.nbytes for x in got.values()) <= cap
+    assert got["loss"].tolist() == [3.5]
+    dec, enc = m.decoder.flat_parameters().flat.numpy(), m.encoder.flat_parameters().flat.numpy()
+    assert np.array_equal(got["params_decoder"], dec)
+    assert 0 < got["params_encoder"].size < enc.size and np.isin(got["params_encoder"], enc).all()
+
+
 def test_step_scoped_arena_bookkeeping():
     """nemo_amd.arena.Arena on host tensors: the first cycle only measures (everything comes from torch.empty), the next rewind
     sizes the buffer to 1.25 x the demand, tensors are 256-byte aligned views handed out front to back, a cycle that outgrows the

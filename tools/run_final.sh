@@ -14,7 +14,7 @@ for part in $PARTS; do
 case $part in
 suite) timeout 1200 python -m pytest tests -x -q -m gpu --durations=8 > $O/gpu_suite.log 2>&1; echo "gpu tests rc=$?"; tail -14 $O/gpu_suite.log ;;
 smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $O/smoke.log ;;
-bench) timeout 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; line $O/bench_default.json ;;
+bench) timeout 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; line $O/bench_default.json ;;
 models)
   timeout 300 python bench.py --model squeezeformer --size medium --no-cpu-baseline --no-roofline > $O/bench_squeezeformer_medium.json 2>/dev/null; line $O/bench_squeezeformer_medium.json
   timeout 300 python bench.py --model transducer --no-cpu-baseline --no-roofline > $O/bench_transducer.json 2>/dev/null; line $O/bench_transducer.json
@@ -25,7 +25,7 @@ models)
   timeout 300 python bench.py --model squeezeformer --size medium --var-len 5:30 --sampler semisort --steps 16 --warmup 4 > $O/bench_squeezeformer_varlen_semisort.json 2>/dev/null; line $O/bench_squeezeformer_varlen_semisort.json ;;
 gloo2)
   for mb in 1 0; do
-    MI355X_SYNCBN_MAILBOX=$mb BENCH_DEVICE=0 BENCH_DIST_BACKEND=gloo timeout 300 python bench.py --gpus 2 --steps 6 --warmup 3 --no-cpu-baseline --no-roofline > $O/bench_gloo2_mailbox$mb.json 2> $O/bench_gloo2_mailbox$mb.err; echo "gloo2 mailbox=$mb rc=$?"
+    MI355X_SYNCBN_MAILBOX=$mb BENCH_DEVICE=0 BENCH_DIST_BACKEND=gloo timeout 300 python bench.py --gpus 2 --steps 6 --warmup 3 --full --no-cpu-baseline --no-roofline > $O/bench_gloo2_mailbox$mb.json 2> $O/bench_gloo2_mailbox$mb.err; echo "gloo2 mailbox=$mb rc=$?"
     python -c "
 import json
 try:

@@ -615,6 +615,30 @@ int mi355x_rnnt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, 
                               int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out,
                               void* c_out, void* stream);
 
+/* ---- Token-and-Duration Transducer (TDT) loss: the objective of the reference's TDTLossNumba (rnnt_pytorch.py -> GPUTDT,
+ * gpu_rnnt.py).  acts f32 [B,T,U1,V1+D] = joint LOGITS with row pitch ld_acts >= V1+D: V1 label logits (blank among them), then D
+ * duration logits for durations[] (host array: integers, strictly ascending, durations[0] = 0, durations[D-1] <= 8, 2 <= D <= 8).
+ * Blank arcs of duration d >= 1 move (t,u) -> (t+d,u), label arcs (t,u) -> (t+d,u+1) (d = 0 allowed); arc weight = label
+ * log-prob + duration log-prob - sigma (sigma >= 0); a path ends with a blank arc landing on (T_b, U_b).  costs f32 [B] =
+ * -log P(y|x); grads (NULL = loss only) = grad_scale * d cost / d acts in grads_dtype with row pitch ld_grads >= V1+D (bf16:
+ * ld_grads % 8 == 0, columns [V1+D, ld_grads) zero-filled); cells beyond an utterance's (T_b, U_b+1) are zeros.  workspace f32,
+ * at least mi355x_tdt_workspace_elems(B,T,U1,D) elements.  U1 <= 1024. */
+int mi355x_tdt_workspace_elems(int B, int T, int U1, int D, long long* elems);
+int mi355x_tdt_loss_ex(const void* acts, long long ld_acts, const void* labels, const void* act_lens, const void* label_lens, int B,
+                       int T, int U1, int V1, int D, const int* durations, int blank, float sigma, float grad_scale, void* costs,
+                       void* grads, int grads_dtype, long long ld_grads, void* workspace, long long workspace_elems, void* stream);
+
+/* ---- greedy TDT decoding on the device: mi355x_rnnt_greedy_decode's arguments plus the duration set; w_out [V1+D, J], b_out
+ * [V1+D].  Per utterance: t = 0; while t < enc_len[b]: k = argmax of the V1 label logits, d = durations[argmax of the D duration
+ * logits] (first maximum wins for both); blank -> t += max(d, 1); else emit (k, t), commit the state, t += d, where the
+ * max_symbols-th consecutive label of duration 0 (max_symbols > 0) is moved on by one frame.  At most max_out labels. */
+int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                             const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                             const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out,
+                             long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D,
+                             const int* durations, int blank, int max_symbols, void* tokens, void* times, void* out_len,
+                             void* score, int max_out, void* h_out, void* c_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

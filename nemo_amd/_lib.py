@@ -182,6 +182,10 @@ SIGNATURES = {
     "mi355x_mailbox_poll": [vp, vp, vp],
     "mi355x_mailbox_destroy": [vp],
     "mi355x_rnnt_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
+    "mi355x_tdt_workspace_elems": [i32, i32, i32, i32, vp],
+    "mi355x_tdt_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
+    "mi355x_tdt_greedy_decode": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32,
+                                 i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp],
 }
 
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["mi355x_asr_version"])

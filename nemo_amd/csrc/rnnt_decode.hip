@@ -14,8 +14,13 @@
 // products -- an HBM / L2-bandwidth-bound loop by nature (no reuse across the 1-row "batch" of a workgroup: not MFMA work).
 // Outputs are integer token ids and frame indices: bit-exact against the oracle restatement (oracle/transducer_ref.py
 // greedy_decode) and the reference-run fixture (tests/golden/ref_rnnt_greedy.json).
+//
+// Token-and-Duration Transducer (mi355x_tdt_greedy_decode, the TDT instance of the same kernel): the output layer has V1 + D rows,
+// label arg-max over the first V1 logits, duration arg-max over the last D, and the frame index advances by the predicted
+// duration (a blank by at least one frame; a run of max_symbols labels predicted with duration 0 is moved on by one frame).
 #include "common.h"
 #include "mi355x_asr.h"
+#include "tdt.h"
 
 #define RD_THREADS 512
 #define RD_WAVES 8
@@ -54,9 +59,10 @@ struct RnntDecP {
   int* tokens; int* times; int* out_len; float* score;
   float* h_out; float* c_out;                // optional final state [B, H]
   int B, T, J, H, V1, blank, max_symbols, max_out;
+  TdtDur dur;                                // TDT: duration set (dur.D = 0 for the RNN-T search)
 };
 
-template <typename WT>
+template <typename WT, bool TDT>
 __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
   extern __shared__ __attribute__((aligned(16))) float rd_smem[];
   const int H = p.H, J = p.J, V1 = p.V1;
@@ -68,10 +74,10 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
   float* z = cn + H;             // [4H] gate pre-activations
   float* gp = z + 4 * H;         // [J] prediction projection of hn
   float* a = gp + J;             // [J] relu(f_t + gp)
-  float* lg = a + J;             // [V1] logits
+  float* lg = a + J;             // [V1] logits (TDT: [V1 + D], the duration logits behind the label logits)
   __shared__ float red_v[RD_WAVES];
   __shared__ int red_i[RD_WAVES];
-  __shared__ int s_k;
+  __shared__ int s_k, s_d;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int len = (int)min((long long)p.T, max(0LL, p.enc_len ? p.enc_len[b] : (long long)p.T));
   for (int i = tid; i < H; i += RD_THREADS) { h[i] = 0.f; c[i] = 0.f; x[i] = 0.f; }
@@ -99,53 +105,91 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
 
   int n = 0;
   float score = 0.f;
-  for (int t = 0; t < len; ++t) {
+  // joint on frame t and the current prediction projection: label arg-max -> s_k (TDT: duration index arg-max -> s_d), returns
+  // sum_v exp(lg[v] - max) over the label logits
+  auto joint_step = [&](int t) -> float {
     const char* frow = (const char*)p.f + ((long long)b * p.T + t) * p.ldf * (p.f_dt == MI_DT_F32 ? 4 : 2);
-    // max_symbols <= 0 (the reference's `max_symbols_per_step=None`: unbounded inner loop, rnnt_greedy_decoding.py:620-700) is
-    // bounded HERE by the output budget: a model that never emits blank would otherwise keep this workgroup -- and the GPU --
-    // busy for ever.  Once max_out labels are out the search stops (out_len == max_out tells the caller it was cut short).
-    for (int sym = 0; p.max_symbols > 0 ? sym < p.max_symbols : n < p.max_out; ++sym) {
-      for (int j = tid; j < J; j += RD_THREADS) {
-        const float fv = p.f_dt == MI_DT_F32 ? ((const float*)frow)[j] : bf2f(((const bf16_t*)frow)[j]);
-        a[j] = fmaxf(fv + gp[j], 0.f);
-      }
-      __syncthreads();
-      rd_gemv<WT, false>((const WT*)p.w_out, p.ld_out, a, V1, J, p.b_out, lg);
-      __syncthreads();
-      // arg-max (lowest index among equal maxima, like torch.max) and log-sum-exp (score = sum of the emitted labels' log-probs)
-      float bv = -INFINITY; int bi = 0x7fffffff;
-      for (int v = tid; v < V1; v += RD_THREADS) { const float q = lg[v]; if (q > bv) { bv = q; bi = v; } }
+    for (int j = tid; j < J; j += RD_THREADS) {
+      const float fv = p.f_dt == MI_DT_F32 ? ((const float*)frow)[j] : bf2f(((const bf16_t*)frow)[j]);
+      a[j] = fmaxf(fv + gp[j], 0.f);
+    }
+    __syncthreads();
+    rd_gemv<WT, false>((const WT*)p.w_out, p.ld_out, a, TDT ? V1 + p.dur.D : V1, J, p.b_out, lg);
+    __syncthreads();
+    // arg-max (lowest index among equal maxima, like torch.max) and log-sum-exp (score = sum of the emitted labels' log-probs)
+    float bv = -INFINITY; int bi = 0x7fffffff;
+    for (int v = tid; v < V1; v += RD_THREADS) { const float q = lg[v]; if (q > bv) { bv = q; bi = v; } }
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-      }
-      if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
-      __syncthreads();
-      float mv = red_v[0]; int mi = red_i[0];
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
+    __syncthreads();
+    float mv = red_v[0]; int mi = red_i[0];
 #pragma unroll
-      for (int w = 1; w < RD_WAVES; ++w) if (red_v[w] > mv || (red_v[w] == mv && red_i[w] < mi)) { mv = red_v[w]; mi = red_i[w]; }
-      float se = 0.f;
-      for (int v = tid; v < V1; v += RD_THREADS) se += expf(lg[v] - mv);
-      __syncthreads();   // (red_v is re-used by block_sum)
-      se = block_sum(se, red_v);
-      if (tid == 0) s_k = mi;
-      __syncthreads();
+    for (int w = 1; w < RD_WAVES; ++w) if (red_v[w] > mv || (red_v[w] == mv && red_i[w] < mi)) { mv = red_v[w]; mi = red_i[w]; }
+    float se = 0.f;
+    for (int v = tid; v < V1; v += RD_THREADS) se += expf(lg[v] - mv);
+    __syncthreads();   // (red_v is re-used by block_sum)
+    se = block_sum(se, red_v);
+    if (tid == 0) {
+      s_k = mi;
+      if (TDT) {   // first maximum wins, as for the labels
+        int di = 0;
+        for (int i = 1; i < p.dur.D; ++i) if (lg[V1 + i] > lg[V1 + di]) di = i;
+        s_d = di;
+      }
+    }
+    __syncthreads();
+    return se;
+  };
+  // commit the state that consumed the previous label, consume the new one
+  auto emit = [&](int k, int t, float se) {
+    if (n < p.max_out) {
+      if (tid == 0) { p.tokens[(long long)b * p.max_out + n] = k; if (p.times) p.times[(long long)b * p.max_out + n] = t; }
+    }
+    ++n;
+    // Score semantics: the sum of the emitted labels' LOG-PROBABILITIES (log-softmax of the joint's logits) -- what the
+    // reference's search computes on CPU tensors.  On CUDA tensors its `_joint_step(log_normalize=None)` skips the
+    // log-softmax and sums raw maximum logits instead (rnnt_greedy_decoding.py:257-259, 965): scores then differ by the
+    // summed log-partition terms; the token ids, time stamps and lengths are the same either way.
+    score += -logf(se);   // log-prob of the arg-max label = mv - (mv + log se)
+    for (int i = tid; i < H; i += RD_THREADS) { h[i] = hn[i]; c[i] = cn[i]; x[i] = p.emb[(long long)k * H + i]; }
+    __syncthreads();
+    pred_step(false);
+  };
+  if constexpr (TDT) {
+    // t advances by the predicted duration; the output budget bounds the search like max_symbols <= 0 below
+    int t = 0, same = 0;
+    while (t < len && n < p.max_out) {
+      const float se = joint_step(t);
       const int k = s_k;
-      if (k == p.blank) break;
-      if (n < p.max_out) {
-        if (tid == 0) { p.tokens[(long long)b * p.max_out + n] = k; if (p.times) p.times[(long long)b * p.max_out + n] = t; }
+      const int di = s_d;
+      int d = 0;
+#pragma unroll
+      for (int i = 0; i < TDT_MAXD; ++i) d = (i == di) ? p.dur.d[i] : d;
+      if (k == p.blank) {   // a blank never stays on its frame
+        t += max(d, 1);
+        same = 0;
+      } else {
+        emit(k, t, se);
+        same = d == 0 ? same + 1 : 0;
+        if (d == 0 && p.max_symbols > 0 && same >= p.max_symbols) { d = 1; same = 0; }
+        t += d;
       }
-      ++n;
-      // Score semantics: the sum of the emitted labels' LOG-PROBABILITIES (log-softmax of the joint's logits) -- what the
-      // reference's search computes on CPU tensors.  On CUDA tensors its `_joint_step(log_normalize=None)` skips the
-      // log-softmax and sums raw maximum logits instead (rnnt_greedy_decoding.py:257-259, 965): scores then differ by the
-      // summed log-partition terms; the token ids, time stamps and lengths are the same either way.
-      score += -logf(se);   // log-prob of the arg-max label = mv - (mv + log se)
-      // commit the state that consumed the previous label, consume the new one
-      for (int i = tid; i < H; i += RD_THREADS) { h[i] = hn[i]; c[i] = cn[i]; x[i] = p.emb[(long long)k * H + i]; }
-      __syncthreads();
-      pred_step(false);
+    }
+  } else {
+    for (int t = 0; t < len; ++t) {
+      // max_symbols <= 0 (the reference's `max_symbols_per_step=None`: unbounded inner loop, rnnt_greedy_decoding.py:620-700) is
+      // bounded HERE by the output budget: a model that never emits blank would otherwise keep this workgroup -- and the GPU --
+      // busy for ever.  Once max_out labels are out the search stops (out_len == max_out tells the caller it was cut short).
+      for (int sym = 0; p.max_symbols > 0 ? sym < p.max_symbols : n < p.max_out; ++sym) {
+        const float se = joint_step(t);
+        const int k = s_k;
+        if (k == p.blank) break;
+        emit(k, t, se);
+      }
     }
   }
   if (tid == 0) { p.out_len[b] = n < p.max_out ? n : p.max_out; if (p.score) p.score[b] = score; }
@@ -156,13 +200,12 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
   if (p.h_out) for (int i = tid; i < H; i += RD_THREADS) { p.h_out[(long long)b * H + i] = h[i]; p.c_out[(long long)b * H + i] = c[i]; }
 }
 
-extern "C" int mi355x_rnnt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                         const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                         const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-                                         const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
-                                         int H, int V1, int blank, int max_symbols, void* tokens, void* times, void* out_len,
-                                         void* score, int max_out, void* h_out, void* c_out, void* stream) {
-  mi_clear_errors();
+static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                              const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh,
+                              const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out, long long ld_out,
+                              const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, const TdtDur* dur, int blank,
+                              int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out,
+                              void* c_out, void* stream) {
   if (!enc_proj || !emb || !w_ih || !w_hh || !b_ih || !b_hh || !w_pred || !w_out || !tokens || !out_len) return MI_ERR_ARG;
   if (B <= 0 || T <= 0 || J <= 0 || H <= 0 || V1 <= 1 || max_out <= 0 || blank < 0 || blank >= V1) return MI_ERR_ARG;
   if ((H & 3) || (J & 3) || (ld_ih & 3) || (ld_hh & 3) || (ld_pred & 3) || (ld_out & 3) || (!h_out != !c_out)) return MI_ERR_ARG;
@@ -175,14 +218,47 @@ extern "C" int mi355x_rnnt_greedy_decode(const void* enc_proj, int f_dtype, long
   p.tokens = (int*)tokens; p.times = (int*)times; p.out_len = (int*)out_len; p.score = (float*)score;
   p.h_out = (float*)h_out; p.c_out = (float*)c_out;
   p.B = B; p.T = T; p.J = J; p.H = H; p.V1 = V1; p.blank = blank; p.max_symbols = max_symbols; p.max_out = max_out;
-  const size_t shm = (size_t)(9 * H + 2 * J + V1 + 4) * sizeof(float);
+  p.dur = {};
+  if (dur) p.dur = *dur;
+  const int D = p.dur.D;
+  const size_t shm = (size_t)(9 * H + 2 * J + V1 + D + 4) * sizeof(float);
   if (shm > 160 * 1024 - 256) return MI_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+#define RD_LAUNCH(WT, TDT)                                                                                                  \
+  hipFuncSetAttribute((const void*)rnnt_greedy_kernel<WT, TDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);    \
+  MI_LAUNCH((rnnt_greedy_kernel<WT, TDT>), dim3(B), dim3(RD_THREADS), shm, s, p)
   if (w_dtype == MI_DT_F32) {
-    hipFuncSetAttribute((const void*)rnnt_greedy_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    MI_LAUNCH(rnnt_greedy_kernel<float>, dim3(B), dim3(RD_THREADS), shm, (hipStream_t)stream, p);
+    if (dur) { RD_LAUNCH(float, true); } else { RD_LAUNCH(float, false); }
   } else {
-    hipFuncSetAttribute((const void*)rnnt_greedy_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    MI_LAUNCH(rnnt_greedy_kernel<bf16_t>, dim3(B), dim3(RD_THREADS), shm, (hipStream_t)stream, p);
+    if (dur) { RD_LAUNCH(bf16_t, true); } else { RD_LAUNCH(bf16_t, false); }
   }
+#undef RD_LAUNCH
   return mi_check_launch();
+}
+
+extern "C" int mi355x_rnnt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                         const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                                         const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+                                         const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
+                                         int H, int V1, int blank, int max_symbols, void* tokens, void* times, void* out_len,
+                                         void* score, int max_out, void* h_out, void* c_out, void* stream) {
+  mi_clear_errors();
+  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len, score,
+                            max_out, h_out, c_out, stream);
+}
+
+extern "C" int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                        const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                                        const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+                                        const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
+                                        int H, int V1, int D, const int* durations, int blank, int max_symbols, void* tokens,
+                                        void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out,
+                                        void* stream) {
+  mi_clear_errors();
+  TdtDur dur;
+  if (tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
+  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len, score,
+                            max_out, h_out, c_out, stream);
 }

@@ -13,7 +13,7 @@ from typing import Any, Dict
 
 import torch
 
-from ..modules import RNNTLoss
+from ..modules import RNNTLoss, TDTLoss
 from .ctc_models import EncDecCTCModel, _build as _build_ctc
 
 _DEFAULT_TARGETS = {"decoder": "nemo.collections.asr.modules.RNNTDecoder", "joint": "nemo.collections.asr.modules.RNNTJoint"}
@@ -50,26 +50,39 @@ class EncDecRNNTModel(EncDecCTCModel):
         n_cls = len(vocab) if vocab is not None else int(cfg["joint"].get("num_classes", cfg["decoder"].get("vocab_size", -1)))
         if n_cls < 1:
             raise ValueError("the vocabulary size must be given (`labels`, `joint.num_classes` or `decoder.vocab_size`)")
+        lc = dict(cfg.get("loss") or {})
+        loss_name = lc.get("loss_name", "default")
+        if loss_name not in ("default", "warprnnt_numba", "tdt"):
+            # losses/rnnt.py:41-100 RNNT_LOSS_RESOLVER: multiblank / pytorch / graph losses are different objectives
+            raise NotImplementedError(f"transducer loss '{loss_name}' (implemented: default = warprnnt_numba semantics, tdt)")
         dec = dict(cfg["decoder"]); dec["vocab_size"] = n_cls
         jnt = dict(cfg["joint"]); jnt["num_classes"] = n_cls
+        tdt_kw = None
+        if loss_name == "tdt":
+            # Token-and-Duration Transducer: the joint appends one logit per duration (num_extra_outputs), blank = vocabulary size
+            tdt_kw = dict(lc.get("tdt_kwargs") or {})
+            if not tdt_kw.get("durations"):
+                raise ValueError("loss_name 'tdt' needs loss.tdt_kwargs.durations")
+            jnt["num_extra_outputs"] = len(tdt_kw["durations"])
         jnt["jointnet"] = dict(jnt["jointnet"])
         jnt["jointnet"].setdefault("encoder_hidden", cfg.get("model_defaults", {}).get("enc_hidden", self.encoder._feat_out))
         jnt["jointnet"].setdefault("pred_hidden", dec["prednet"]["pred_hidden"])
         self.decoder = _build("decoder", dec)
         self.joint = _build("joint", jnt)
-        lc = dict(cfg.get("loss") or {})
-        if lc.get("loss_name", "default") not in ("default", "warprnnt_numba"):
-            # losses/rnnt.py:41-100 RNNT_LOSS_RESOLVER: tdt / multiblank / pytorch / graph losses are different objectives
-            raise NotImplementedError(f"transducer loss '{lc.get('loss_name')}' (implemented: default = warprnnt_numba semantics)")
         if cfg.get("aux_ctc"):
             raise NotImplementedError("aux_ctc (EncDecHybridRNNTCTCModel's auxiliary CTC head) is not part of EncDecRNNTModel")
         self._check_interctc(cfg.get("interctc"))
         # skip_nan_grad (models/asr_model.py:147-174): handled by the shared fit_step / on_after_backward (EncDecCTCModel)
         self._skip_nan_grad = bool(cfg.get("skip_nan_grad"))
         self.skipped_steps = 0
-        kw = dict(lc.get("warprnnt_numba_kwargs") or {})
-        self.loss = RNNTLoss(blank=n_cls, reduction=cfg.get("rnnt_reduction", "mean_batch"),
-                             fastemit_lambda=kw.get("fastemit_lambda", 0.0), clamp=kw.get("clamp", -1.0))
+        if tdt_kw is not None:
+            self.loss = TDTLoss(blank=n_cls, durations=list(tdt_kw["durations"]), reduction=cfg.get("rnnt_reduction", "mean_batch"),
+                                fastemit_lambda=tdt_kw.get("fastemit_lambda", 0.0), clamp=tdt_kw.get("clamp", -1.0),
+                                sigma=tdt_kw.get("sigma", 0.0), omega=tdt_kw.get("omega", 0.0))
+        else:
+            kw = dict(lc.get("warprnnt_numba_kwargs") or {})
+            self.loss = RNNTLoss(blank=n_cls, reduction=cfg.get("rnnt_reduction", "mean_batch"),
+                                 fastemit_lambda=kw.get("fastemit_lambda", 0.0), clamp=kw.get("clamp", -1.0))
         if self.joint.fuse_loss_wer:
             self.joint.set_loss(self.loss)
         sa = cfg.get("spec_augment")
@@ -109,8 +122,14 @@ class EncDecRNNTModel(EncDecCTCModel):
             if strategy not in ("greedy", "greedy_batch"):
                 raise NotImplementedError(f"transducer decoding strategy '{strategy}' (implemented: greedy, greedy_batch)")
             ms = dict(dcfg.get("greedy") or {}).get("max_symbols", 10)
+            # TDT: `decoding.model_type: tdt` with `decoding.durations`; a joint with duration outputs decodes as TDT with the
+            # loss's durations when the decoding section does not say otherwise
+            tdt_loss = isinstance(self.loss, TDTLoss)
+            model_type = dcfg.get("model_type", "tdt" if tdt_loss else "rnnt")
+            durations = dcfg.get("durations") or (self.loss.durations if tdt_loss else None)
             self._decoding = RNNTDecoding(self.decoder, self.joint, vocabulary=list(vocab) if vocab is not None else None,
-                                          max_symbols=ms, tokenizer=self.tokenizer if vocab is None else None)
+                                          max_symbols=ms, tokenizer=self.tokenizer if vocab is None else None,
+                                          model_type=model_type, durations=list(durations) if durations else None)
         return self._decoding
 
     @property
@@ -293,3 +312,19 @@ def fastconformer_transducer_config(size: str = "large", vocab_size: int = 1024,
         "optim": dict(name="adamw", lr=5.0, betas=[0.9, 0.98], weight_decay=1e-3,
                       sched=dict(name="NoamAnnealing", d_model=d_model, warmup_steps=10000, warmup_ratio=None, min_lr=1e-6)),
     }
+
+
+def fastconformer_tdt_config(size: str = "large", vocab_size: int = 1024, durations=(0, 1, 2, 3, 4), sigma: float = 0.02,
+                             omega: float = 0.1, spec_augment: bool = False, **encoder_overrides) -> Dict[str, Any]:
+    """model section of examples/asr/conf/fastconformer/fast-conformer_tdt_bpe.yaml (the Parakeet-TDT recipe): the
+    FastConformer-Transducer model with the Token-and-Duration Transducer objective -- the joint appends one logit per duration
+    (joint.num_extra_outputs), loss_name tdt with tdt_kwargs {durations, sigma, omega}, greedy TDT decoding."""
+    cfg = fastconformer_transducer_config(size, vocab_size=vocab_size, spec_augment=spec_augment, **encoder_overrides)
+    durations = [int(d) for d in durations]
+    cfg["model_defaults"]["tdt_durations"] = list(durations)
+    cfg["model_defaults"]["num_tdt_durations"] = len(durations)
+    cfg["joint"]["num_extra_outputs"] = len(durations)
+    cfg["loss"] = dict(loss_name="tdt", tdt_kwargs=dict(fastemit_lambda=0.0, clamp=-1.0, durations=list(durations), sigma=sigma,
+                                                        omega=omega))
+    cfg["decoding"] = dict(strategy="greedy_batch", model_type="tdt", durations=list(durations), greedy=dict(max_symbols=10))
+    return cfg

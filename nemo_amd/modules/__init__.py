@@ -6,5 +6,6 @@ from .conv_asr import ConvASRDecoder  # noqa: F401
 from .ctc import CTCLoss  # noqa: F401
 from .ctc_decoding import GreedyCTCDecoder, WER, word_error_rate  # noqa: F401
 from .rnnt_loss import RNNTLoss, RNNTLossNumba  # noqa: F401
+from .tdt_loss import TDTLoss, TDTLossNumba  # noqa: F401
 from .rnnt import RNNTDecoder, RNNTJoint  # noqa: F401
-from .rnnt_decoding import GreedyBatchedRNNTInfer, RNNTDecoding, RNNTWER, Hypothesis  # noqa: F401
+from .rnnt_decoding import GreedyBatchedRNNTInfer, GreedyBatchedTDTInfer, RNNTDecoding, RNNTWER, Hypothesis  # noqa: F401

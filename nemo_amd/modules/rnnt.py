@@ -29,6 +29,7 @@ from ..core import (AcousticEncodedRepresentation, ElementType, EmbeddedTextType
                     LossType, NeuralModule, NeuralType, typecheck)
 from ..flat import FlatParams
 from ..packing import PackPlan
+from .tdt_loss import TDTLoss, draw_rnnt_call
 
 
 def _pad8(n):
@@ -348,14 +349,16 @@ class RNNTJoint(_ModuleBase):
         bad = []
         if jointnet.get("activation", "relu").lower() != "relu": bad.append(f"activation={jointnet.get('activation')}")
         if masking_prob > 0.0: bad.append("masking_prob")
-        if num_extra_outputs: bad.append("num_extra_outputs")
         if log_softmax: bad.append("log_softmax=True (the MI355X loss fuses the log-softmax, as the reference's GPU loss does)")
         if bad:
             raise NotImplementedError("MI355X RNNTJoint does not implement: " + ", ".join(bad))
         self.vocabulary = vocabulary
         self._vocab_size = num_classes
-        self._num_extra_outputs = 0
-        self._num_classes = num_classes + 1
+        if num_extra_outputs < 0 or num_extra_outputs > 8:
+            raise ValueError(f"num_extra_outputs (TDT durations) must lie in [0, 8], got {num_extra_outputs}")
+        # TDT (num_extra_outputs = number of durations): the output layer appends the duration logits behind the V+1 label logits
+        self._num_extra_outputs = int(num_extra_outputs)
+        self._num_classes = num_classes + 1 + self._num_extra_outputs
         self._fuse_loss_wer, self._fused_batch_size = fuse_loss_wer, fused_batch_size
         # fused joint + loss: cut every sub-batch to its own longest encoder / target length, as the reference does
         # (rnnt.py:1559-1600); costs one host read of the lengths per step.  MI355X_RNNT_TRUNCATE=0 keeps the padded grid.
@@ -589,6 +592,19 @@ class RNNTJoint(_ModuleBase):
             return gtmp[off: off + p.numel()].view(p.shape)
 
         out = self.joint_net[-1]
+        # TDT: the loss of every sub-batch is the TDT loss, or -- one draw per call, with probability omega -- the RNN-T loss of
+        # the label logits (duration gradients zero); the label logits are the first V+1 columns of the pitched rows either way
+        tdt = isinstance(loss_mod, TDTLoss)
+        tdt_as_rnnt = tdt and draw_rnnt_call(loss_mod.omega)
+        Vl = self._vocab_size + 1   # label logits (= the whole row without TDT)
+
+        def pitched_loss(logits, ld, nb, Ts, Us, lab, el_, tl_, grads, ldg, gscale):
+            if tdt and not tdt_as_rnnt:
+                return ops.tdt_loss_pitched(logits, ld, nb, Ts, Us, Vl, loss_mod.durations, lab, el_, tl_, self._vocab_size,
+                                            grads=grads, ld_grads=ldg, sigma=loss_mod.sigma, grad_scale=gscale)
+            return ops.rnnt_loss_pitched(logits, ld, nb, Ts, Us, Vl, lab, el_, tl_, self._vocab_size, grads, ldg,
+                                         grad_scale=gscale)
+
         xe, xd, f, g = self._project(enc, dec, W, cdt)
         df = torch.empty(B * T, J, dtype=cdt, device=dev) if need_grad else None
         dg32 = torch.zeros(B * U1, J, dtype=torch.float32, device=dev) if need_grad else None
@@ -629,8 +645,12 @@ class RNNTJoint(_ModuleBase):
             sub_bwd_kw = dict(df_rows=dfs, dg_pitch=U1) if cut else {}
             if not need_grad:
                 h, logits = self._sub_fwd(fs, gs, fb0, nb, Ts, Us, W, cdt, drop)
-                costs[b0:b0 + nb] = ops.rnnt_loss(logits, lab, el[b0:b0 + nb], tl[b0:b0 + nb], self._vocab_size,
-                                                  fastemit_lambda=fe, clamp=cl, grad_scale=scale)
+                if tdt:
+                    V1 = self._num_classes
+                    costs[b0:b0 + nb] = pitched_loss(logits, V1, nb, Ts, Us, lab, el[b0:b0 + nb], tl[b0:b0 + nb], None, V1, scale)
+                else:
+                    costs[b0:b0 + nb] = ops.rnnt_loss(logits, lab, el[b0:b0 + nb], tl[b0:b0 + nb], self._vocab_size,
+                                                      fastemit_lambda=fe, clamp=cl, grad_scale=scale)
                 del h, logits
                 continue
             if cdt == torch.bfloat16:
@@ -640,17 +660,24 @@ class RNNTJoint(_ModuleBase):
                 V1p = _pad8(V1)
                 h, logits = self._sub_fwd(fs, gs, fb0, nb, Ts, Us, W, cdt, drop, ld=V1p)
                 dlog = torch.empty(nb * Ts * Us, V1p, dtype=cdt, device=dev)
-                c = ops.rnnt_loss_pitched(logits, V1p, nb, Ts, Us, V1, lab, el[b0:b0 + nb], tl[b0:b0 + nb],
-                                          self._vocab_size, dlog, V1p, fastemit_lambda=fe, clamp=cl,
-                                          grad_scale=scale / self.temperature if self.temperature != 1.0 else scale)
+                gscale = scale / self.temperature if self.temperature != 1.0 else scale
+                if tdt:
+                    c = pitched_loss(logits, V1p, nb, Ts, Us, lab, el[b0:b0 + nb], tl[b0:b0 + nb], dlog, V1p, gscale)
+                else:
+                    c = ops.rnnt_loss_pitched(logits, V1p, nb, Ts, Us, V1, lab, el[b0:b0 + nb], tl[b0:b0 + nb],
+                                              self._vocab_size, dlog, V1p, fastemit_lambda=fe, clamp=cl, grad_scale=gscale)
                 costs[b0:b0 + nb] = c
                 self._sub_bwd(None, h, b0, nb, Ts, Us, W, cdt, drop, df, dg32, gview(out.weight), gview(out.bias), dlog=dlog,
                               **sub_bwd_kw)
             else:
                 h, logits = self._sub_fwd(fs, gs, fb0, nb, Ts, Us, W, cdt, drop)
                 grads = torch.empty_like(logits)
-                c = ops.rnnt_loss(logits, lab, el[b0:b0 + nb], tl[b0:b0 + nb], self._vocab_size, grads=grads,
-                                  fastemit_lambda=fe, clamp=cl, grad_scale=scale)
+                if tdt:
+                    V1 = self._num_classes
+                    c = pitched_loss(logits, V1, nb, Ts, Us, lab, el[b0:b0 + nb], tl[b0:b0 + nb], grads, V1, scale)
+                else:
+                    c = ops.rnnt_loss(logits, lab, el[b0:b0 + nb], tl[b0:b0 + nb], self._vocab_size, grads=grads,
+                                      fastemit_lambda=fe, clamp=cl, grad_scale=scale)
                 costs[b0:b0 + nb] = c
                 self._sub_bwd(grads, h, b0, nb, Ts, Us, W, cdt, drop, df, dg32, gview(out.weight), gview(out.bias), **sub_bwd_kw)
                 del grads

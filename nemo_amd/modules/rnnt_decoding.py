@@ -78,10 +78,11 @@ class GreedyBatchedRNNTInfer:
             H = dec.pred_hidden
             w = (lstm.weight_ih_l0, H, lstm.weight_hh_l0, H, jnt.pred.weight, H, out.weight, J)
         lens = encoded_lengths.to(device=dev, dtype=torch.int64).contiguous()
-        res = ops.rnnt_greedy_decode(f.view(B, T, J), lens, emb, w[0], w[1], w[2], w[3], lstm.bias_ih_l0, lstm.bias_hh_l0, w[4], w[5],
-                                     jnt.pred.bias, w[6], w[7], out.bias, self._blank_index, self.max_symbols or 0,
-                                     with_state=with_state)
+        res = self._search(f.view(B, T, J), lens, emb, w[0], w[1], w[2], w[3], lstm.bias_ih_l0, lstm.bias_hh_l0, w[4], w[5],
+                           jnt.pred.bias, w[6], w[7], out.bias, self._blank_index, self.max_symbols or 0, with_state=with_state)
         return res
+
+    _search = staticmethod(ops.rnnt_greedy_decode)
 
     def forward(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, partial_hypotheses=None):
         if partial_hypotheses is not None:
@@ -98,16 +99,42 @@ class GreedyBatchedRNNTInfer:
     __call__ = forward
 
 
+class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
+    """`GreedyBatchedTDTInfer` (parts/submodules/tdt_loop_labels_computer.py and rnnt_greedy_decoding.py): greedy search of a
+    Token-and-Duration Transducer, whose joint appends one logit per duration behind the V+1 label logits.  Per utterance the
+    label is the arg-max of the label logits, the duration the arg-max of the duration logits; a blank moves on by
+    max(duration, 1) frames, a label by its duration, and the `max_symbols`-th consecutive label of duration 0 by one frame.
+    One launch for the batch (`mi355x_tdt_greedy_decode`)."""
+
+    def __init__(self, decoder_model, joint_model, blank_index: int, durations, max_symbols_per_step: Optional[int] = None,
+                 **kw):
+        super().__init__(decoder_model, joint_model, blank_index, max_symbols_per_step=max_symbols_per_step, **kw)
+        from .tdt_loss import check_durations
+        self.durations = check_durations(list(durations))
+        if getattr(joint_model, "_num_extra_outputs", len(self.durations)) != len(self.durations):
+            raise ValueError(f"the joint has {joint_model._num_extra_outputs} extra outputs for {len(self.durations)} durations")
+
+    def _search(self, *args, with_state=False):
+        return ops.tdt_greedy_decode(*args[:16], self.durations, args[16], with_state=with_state)
+
+
 class RNNTDecoding:
     """`strategy: greedy_batch` of AbstractRNNTDecoding (rnnt_decoding.py:216-330) for a character / word-piece vocabulary;
     blank id = len(vocabulary) (rnnt_decoding.py:1170)."""
 
     def __init__(self, decoder, joint, vocabulary: Optional[Sequence[str]] = None, max_symbols: Optional[int] = 10,
-                 tokenizer=None):
+                 tokenizer=None, model_type: str = "rnnt", durations: Optional[Sequence[int]] = None):
         self.vocabulary = list(vocabulary) if vocabulary is not None else None
         self.tokenizer = tokenizer
         self.blank_id = decoder.blank_idx
-        self.decoding = GreedyBatchedRNNTInfer(decoder, joint, self.blank_id, max_symbols_per_step=max_symbols)
+        if model_type == "tdt":   # rnnt_decoding.py: `model_type: tdt` with the duration set of the joint's extra outputs
+            if not durations:
+                raise ValueError("decoding with model_type 'tdt' needs `durations`")
+            self.decoding = GreedyBatchedTDTInfer(decoder, joint, self.blank_id, durations, max_symbols_per_step=max_symbols)
+        elif model_type == "rnnt":
+            self.decoding = GreedyBatchedRNNTInfer(decoder, joint, self.blank_id, max_symbols_per_step=max_symbols)
+        else:
+            raise NotImplementedError(f"transducer decoding model_type '{model_type}' (implemented: rnnt, tdt)")
 
     def ids_to_text(self, ids: Sequence[int]) -> str:
         ids = [int(i) for i in ids if int(i) != self.blank_id]

@@ -655,12 +655,14 @@ def rnnt_loss(acts, labels, act_lens, label_lens, blank, grads=None, fastemit_la
 
 def rnnt_loss_pitched(acts, ld_acts, B, T, U1, V1, labels, act_lens, label_lens, blank, grads, ld_grads, fastemit_lambda=0.0,
                       clamp=0.0, grad_scale=1.0):
-    """acts f32, rows of pitch ld_acts; grads (f32 or bf16) rows of pitch ld_grads, pad columns zero-filled -> costs f32 [B]"""
+    """acts f32, rows of pitch ld_acts; grads (f32 or bf16, or None: loss only) rows of pitch ld_grads, pad columns zero-filled
+    -> costs f32 [B]"""
     n = 5 * B * T * U1 + 2 * B
     ws = torch.empty(n, device=acts.device, dtype=torch.float32)
     costs = torch.empty(B, device=acts.device, dtype=torch.float32)
     check(lib.mi355x_rnnt_loss_ex(_ptr(acts), ld_acts, _ptr(labels), _ptr(act_lens), _ptr(label_lens), B, T, U1, V1, blank,
-                                  fastemit_lambda, clamp, grad_scale, _ptr(costs), _ptr(grads), dt(grads), ld_grads, _ptr(ws), n,
+                                  fastemit_lambda, clamp, grad_scale, _ptr(costs), _ptr(grads), dt(grads) if grads is not None else F32,
+                                  ld_grads if grads is not None else 0, _ptr(ws), n,
                                   _stream()), "rnnt_loss_ex")
     return costs
 
@@ -686,6 +688,57 @@ def rnnt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b
                                         ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1, blank, max_symbols, _ptr(tokens),
                                         _ptr(times), _ptr(out_len), _ptr(score), max_out, _ptr(h), _ptr(c), _stream()),
           "rnnt_greedy_decode")
+    return (tokens, times, out_len, score) + (((h, c),) if with_state else ())
+
+
+def _tdt_durations(durations):
+    d = [int(x) for x in durations]
+    return len(d), (C.c_int * len(d))(*d)
+
+
+def tdt_loss_pitched(acts, ld_acts, B, T, U1, V1, durations, labels, act_lens, label_lens, blank, grads=None, ld_grads=0,
+                     sigma=0.0, grad_scale=1.0):
+    """Token-and-Duration Transducer loss (mi355x_tdt_loss_ex): acts f32 logits [.., V1 + D] in rows of pitch ld_acts (V1 label
+    logits, then one per duration); grads (f32 or bf16, optional) rows of pitch ld_grads, pad columns zero-filled -> costs f32 [B]"""
+    D, dur = _tdt_durations(durations)
+    n = (4 + 2 * D) * B * T * U1 + 2 * B
+    ws = torch.empty(n, device=acts.device, dtype=torch.float32)
+    costs = torch.empty(B, device=acts.device, dtype=torch.float32)
+    check(lib.mi355x_tdt_loss_ex(_ptr(acts), ld_acts, _ptr(labels), _ptr(act_lens), _ptr(label_lens), B, T, U1, V1, D, dur, blank,
+                                 sigma, grad_scale, _ptr(costs), _ptr(grads), dt(grads) if grads is not None else F32,
+                                 ld_grads if grads is not None else 0, _ptr(ws), n, _stream()), "tdt_loss_ex")
+    return costs
+
+
+def tdt_loss(acts, labels, act_lens, label_lens, blank, durations, grads=None, sigma=0.0, grad_scale=1.0):
+    """acts f32 [B,T,U1,V1+D] logits (contiguous); labels i64 [B,U1-1]; returns costs f32 [B]; fills `grads` (f32, same shape)"""
+    B, T, U1, W = acts.shape
+    V1 = W - len(durations)
+    return tdt_loss_pitched(acts, W, B, T, U1, V1, durations, labels, act_lens, label_lens, blank, grads=grads, ld_grads=W,
+                            sigma=sigma, grad_scale=grad_scale)
+
+
+def tdt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
+                      blank, durations, max_symbols, max_out=None, with_state=False):
+    """greedy TDT search of a whole batch in one launch (mi355x_tdt_greedy_decode): as rnnt_greedy_decode, with w_out / b_out
+    holding V1 + len(durations) rows (label logits, then duration logits); frames advance by the predicted duration"""
+    B, T, J = enc_proj.shape
+    V1, H = emb.shape
+    D, dur = _tdt_durations(durations)
+    if max_out is None:
+        max_out = T * max_symbols if max_symbols > 0 else 4 * T
+    dev = enc_proj.device
+    tokens = torch.empty(B, max_out, dtype=torch.int32, device=dev)
+    times = torch.empty(B, max_out, dtype=torch.int32, device=dev)
+    out_len = torch.empty(B, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    h = torch.empty(B, H, dtype=torch.float32, device=dev) if with_state else None
+    c = torch.empty(B, H, dtype=torch.float32, device=dev) if with_state else None
+    check(lib.mi355x_tdt_greedy_decode(_ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih,
+                                       _ptr(w_hh), ld_hh, _ptr(b_ih), _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out),
+                                       ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1, D, dur, blank, max_symbols, _ptr(tokens),
+                                       _ptr(times), _ptr(out_len), _ptr(score), max_out, _ptr(h), _ptr(c), _stream()),
+          "tdt_greedy_decode")
     return (tokens, times, out_len, score) + (((h, c),) if with_state else ())
 
 

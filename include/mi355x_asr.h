@@ -639,6 +639,27 @@ int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, c
                              const int* durations, int blank, int max_symbols, void* tokens, void* times, void* out_len,
                              void* score, int max_out, void* h_out, void* c_out, void* stream);
 
+/* ---- cache-aware streaming inference (ConformerEncoder.cache_aware_stream_step; the `update_cache` paths of
+ * RelPositionMultiHeadAttention and CausalConv1D).  Caches are f32 in the reference's layouts; in bf16 compute they hold the
+ * bf16-rounded operands widened to f32, so a streamed chunk reads the same operand values as the offline forward.
+ * mi355x_stream_cache_assemble: kv_in [B*(C+Tq), d] (dtype) = cat(cache [B,C,d] f32, y [B*Tq,d] dtype) along time; cache_next
+ * [B,C,d] f32 = its last C rows (d % 4 == 0; C may be 0).
+ * mi355x_stream_attn: q [B*Tq, ldq] (head h at column h*dk), kv [B*Tk, ldkv] (k of head h at h*dk, v at v_off + h*dk),
+ * pos [2Tk-1, ldp] = linear_pos of the Tk table (row r <-> relative position Tk-1-r), bias_u / bias_v f32 [H*dk];
+ * cache_len / chunk_len i64 [B].  Query i sits at key position C + i (C = Tk - Tq); score(i,j) = ((q_i+u).k_j + (q_i+v).p_{j+Tq-1-i})
+ * * scale; key j is visible when C - cache_len[b] <= j < C + chunk_len[b] and, for chunk > 0, 0 <= (C+i)/chunk - j/chunk <=
+ * left_chunks (< 0: unlimited).  ctx [B*Tq, ldo] (dtype); a row with no visible key is zero.  dk <= 128.
+ * mi355x_stream_dwconv: x [B*Tq, d] (dtype), cache [B, d, K-1] f32 (left taps), w [d, K], bias [d] f32 -> y [B*Tq, d] (dtype),
+ * cache_next [B, d, K-1] f32 = the last K-1 frames of cat(cache, x); K in {3, 5, 9, 31}; cache_next must not alias cache. */
+int mi355x_stream_cache_assemble(const void* cache, const void* y, void* kv_in, void* cache_next, int dtype, int B, int C, int Tq,
+                                 int d, void* stream);
+int mi355x_stream_attn(const void* q, long long ldq, const void* kv, long long ldkv, long long v_off, const void* pos,
+                       long long ldp, const void* bias_u, const void* bias_v, const void* cache_len, const void* chunk_len,
+                       void* ctx, long long ldo, int dtype, int B, int H, int Tq, int Tk, int dk, int chunk, int left_chunks,
+                       float scale, void* stream);
+int mi355x_stream_dwconv(const void* x, const void* cache, const void* w, const void* bias, void* y, void* cache_next, int dtype,
+                         int B, int Tq, int d, int ksize, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

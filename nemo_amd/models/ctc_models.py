@@ -302,6 +302,45 @@ class EncDecCTCModel(nn.Module):
             self.train(was_training)
         return out
 
+    # ------------------------------------------------------------------ cache-aware streaming (asr_model.py ASRModuleMixin)
+    @torch.no_grad()
+    def conformer_stream_step(self, processed_signal, processed_signal_length=None, cache_last_channel=None, cache_last_time=None,
+                              cache_last_channel_len=None, keep_all_outputs=True, previous_hypotheses=None,
+                              previous_pred_out=None, drop_extra_pre_encoded=None, return_transcription=True,
+                              return_log_probs=False):
+        """`ASRModuleMixin.conformer_stream_step` for CTC models: one chunk through the encoder with caches
+        (ConformerEncoder.cache_aware_stream_step), the decoder's log-softmax, and the per-frame arg-max of every utterance's valid
+        frames appended to `previous_pred_out`.  -> (greedy_predictions: list of i64 [n_b] per utterance, texts (None unless
+        return_transcription), cache_last_channel_next, cache_last_time_next, cache_last_channel_next_len, best_hyp = None)
+        [+ (log_probs, encoded_len) with return_log_probs; encoded_len counts the frames of all chunks so far]."""
+        if not hasattr(self.encoder, "cache_aware_stream_step"):
+            raise NotImplementedError(f"{type(self.encoder).__name__} has no cache-aware streaming")
+        if return_transcription and self.wer is None:
+            raise RuntimeError("conformer_stream_step(return_transcription=True) needs a vocabulary (decoder.vocabulary or a tokenizer)")
+        encoded, encoded_len, ch_next, t_next, len_next = self.encoder.cache_aware_stream_step(
+            processed_signal=processed_signal, processed_signal_length=processed_signal_length,
+            cache_last_channel=cache_last_channel, cache_last_time=cache_last_time, cache_last_channel_len=cache_last_channel_len,
+            keep_all_outputs=keep_all_outputs, drop_extra_pre_encoded=drop_extra_pre_encoded)
+        log_probs = self.decoder(encoder_output=encoded)
+        preds = log_probs.argmax(dim=-1).cpu()
+        enc_len = encoded_len.cpu().clone()
+        blank = self.decoder.num_classes_with_blank - 1
+        greedy, texts = [], ([] if return_transcription else None)
+        for b in range(preds.shape[0]):
+            cur = preds[b, : int(enc_len[b])]
+            if previous_pred_out is not None:
+                prev = previous_pred_out[b].to(cur.device)
+                cur = torch.cat((prev, cur), dim=-1)
+                enc_len[b] += prev.numel()
+            greedy.append(cur)
+            if return_transcription:   # ctc_decoder_predictions_tensor: merge repeats, drop blanks
+                ids = [int(t) for t in torch.unique_consecutive(cur).tolist() if int(t) != blank]
+                texts.append(self.wer.decoding.ids_to_text(ids))
+        result = [greedy, texts, ch_next, t_next, len_next, None]
+        if return_log_probs:
+            result += [log_probs, enc_len.to(log_probs.device)]
+        return tuple(result)
+
     # ------------------------------------------------------------------ fine-tuning on another alphabet (ctc_models.py:190-262)
     def change_vocabulary(self, new_vocabulary, decoding_cfg=None):
         """replaces the decoder by a freshly initialised one over `new_vocabulary` (the encoder is kept), rebuilds the

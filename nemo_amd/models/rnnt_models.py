@@ -244,6 +244,11 @@ class EncDecRNNTModel(EncDecCTCModel):
             sample_id = sample_id.cpu().numpy()
         return list(zip(sample_id, texts))
 
+    def conformer_stream_step(self, *args, **kwargs):
+        """the reference streams transducers with greedy decoding from `partial_hypotheses`, which the greedy transducer decoders
+        here do not take yet (the encoder step itself, ConformerEncoder.cache_aware_stream_step, works for transducer encoders)"""
+        raise NotImplementedError("conformer_stream_step for transducer models: greedy decoding with partial_hypotheses")
+
     @torch.no_grad()
     def transcribe(self, audio, batch_size: int = 4, return_hypotheses: bool = False, num_workers: int = 0,
                    channel_selector=None, verbose: bool = False):

@@ -201,6 +201,10 @@ class ConformerEncoder(NeuralModule):
         return OrderedDict({
             "audio_signal": NeuralType(("B", "D", "T"), SpectrogramType()),
             "length": NeuralType(tuple("B"), LengthsType()),
+            # streaming caches (conformer_encoder.py:226-230; modules/conformer_streaming.py)
+            "cache_last_channel": NeuralType(("D", "B", "T", "D"), ChannelType(), optional=True),
+            "cache_last_time": NeuralType(("D", "B", "D", "T"), ChannelType(), optional=True),
+            "cache_last_channel_len": NeuralType(tuple("B"), LengthsType(), optional=True),
             "bypass_pre_encode": NeuralType(tuple(), BoolType(), optional=True),   # conformer_encoder.py:231
         })
 
@@ -209,6 +213,9 @@ class ConformerEncoder(NeuralModule):
         return OrderedDict({
             "outputs": NeuralType(("B", "D", "T"), AcousticEncodedRepresentation()),
             "encoded_lengths": NeuralType(tuple("B"), LengthsType()),
+            "cache_last_channel_next": NeuralType(("D", "B", "T", "D"), ChannelType(), optional=True),
+            "cache_last_time_next": NeuralType(("D", "B", "D", "T"), ChannelType(), optional=True),
+            "cache_last_channel_next_len": NeuralType(tuple("B"), LengthsType(), optional=True),
         })
 
     def __init__(self, feat_in, n_layers, d_model, feat_out=-1, causal_downsampling=False, subsampling="striding",
@@ -305,6 +312,7 @@ class ConformerEncoder(NeuralModule):
         self.capture_layers = []
         self.captured = {}
         self.max_audio_length = pos_emb_max_len
+        self.streaming_cfg = None   # CacheAwareStreamingConfig, filled by setup_streaming_params (lazily by the first stream step)
         self._init_engine(compute_dtype, tail=lambda n: n.endswith("self_attn.linear_pos.weight"))
 
     def _init_engine(self, compute_dtype, tail=None):
@@ -533,8 +541,22 @@ class ConformerEncoder(NeuralModule):
     @typecheck()
     def forward(self, audio_signal, length, cache_last_channel=None, cache_last_time=None, cache_last_channel_len=None,
                 bypass_pre_encode=False):
-        if cache_last_channel is not None:
-            raise NotImplementedError("streaming caches are not on the training hot path")
+        if cache_last_channel is not None or cache_last_time is not None:
+            if cache_last_channel is None or cache_last_time is None or cache_last_channel_len is None:
+                raise ValueError("cache-aware streaming needs cache_last_channel, cache_last_time and cache_last_channel_len")
+            if bypass_pre_encode:
+                raise NotImplementedError("cache-aware streaming with bypass_pre_encode=True")
+            if audio_signal.shape[-2] != self._feat_in:
+                raise ValueError(f"audio_signal should have shape (batch, {self._feat_in}, n_frame), got {tuple(audio_signal.shape)}")
+            if getattr(self, "streaming_cfg", None) is None:
+                self.setup_streaming_params()
+            if length is None:
+                length = audio_signal.new_full((audio_signal.size(0),), audio_signal.size(-1), dtype=torch.int64)
+            self._flatp.ensure(audio_signal.device)
+            from .conformer_streaming import stream_step
+            with torch.no_grad():
+                return stream_step(self, audio_signal, length, cache_last_channel, cache_last_time, cache_last_channel_len,
+                                   self.streaming_cfg.drop_extra_pre_encoded)
         if bypass_pre_encode and audio_signal.shape[-1] != self.d_model:
             raise ValueError(f"If bypass_pre_encode is True, audio_signal should have shape (batch, n_frame, {self.d_model}) "
                              f"but got last dimension {audio_signal.shape[-1]}.")  # conformer_encoder.py:563-568
@@ -556,6 +578,73 @@ class ConformerEncoder(NeuralModule):
         out, enc_len, S_ = self._forward_impl(audio_signal, length, save=bool(self.capture_layers))
         self.captured = dict(zip(self.capture_layers, getattr(S_, "cap_out", ()))) if S_ is not None else {}
         return out, enc_len
+
+    # ------------------------------------------------------------------ cache-aware streaming (modules/conformer_streaming.py)
+    def setup_streaming_params(self, chunk_size=None, shift_size=None, left_chunks=None, att_context_size=None, max_context=10000):
+        """conformer_encoder.py `setup_streaming_params`: fills `self.streaming_cfg` for `att_context_size` (default: the encoder's
+        default context; any entry of att_context_size_all).  Implemented for chunked_limited attention, causal depthwise conv
+        and causal down-sampling; explicit chunk_size / shift_size / left_chunks are refused."""
+        from .conformer_streaming import streaming_config
+        for name, v in (("chunk_size", chunk_size), ("shift_size", shift_size), ("left_chunks", left_chunks)):
+            if v is not None:
+                raise NotImplementedError(f"setup_streaming_params({name}=...): the chunking follows att_context_size here")
+        cs = list(self.att_context_size if att_context_size is None else att_context_size)
+        if [int(v) for v in cs] not in [[int(v) for v in a] for a in self.att_context_size_all]:
+            raise ValueError(f"att_context_size={cs} is not one of the trained contexts {self.att_context_size_all}")
+        self.streaming_cfg = streaming_config(self, cs)
+        self._stream_ctx = (int(cs[0]), int(cs[1]))
+        return self.streaming_cfg
+
+    def get_initial_cache_state(self, batch_size=1, dtype=torch.float32, device=None, max_dim=0):
+        """zero caches in the reference's layouts: cache_last_channel [n_layers, B, C, d_model], cache_last_time
+        [n_layers, B, d_model, K-1], cache_last_channel_len i64 [B]"""
+        if getattr(self, "streaming_cfg", None) is None:
+            self.setup_streaming_params()
+        if device is None:
+            device = next(self.parameters()).device
+        C = self.streaming_cfg.last_channel_cache_size
+        ch = torch.zeros(self.n_layers, batch_size, C, self.d_model, dtype=dtype, device=device)
+        tm = torch.zeros(self.n_layers, batch_size, self.d_model, self.conv_kernel_size - 1, dtype=dtype, device=device)
+        return ch, tm, torch.zeros(batch_size, dtype=torch.int64, device=device)
+
+    def streaming_post_process(self, rets, keep_all_outputs=True):
+        """conformer_encoder.py `streaming_post_process`: trims the channel caches to their size and, with keep_all_outputs=False,
+        the outputs to valid_out_len (a no-op for chunked_limited, where a chunk yields exactly valid_out_len frames)"""
+        if len(rets) == 2:
+            return rets[0], rets[1], None, None, None
+        encoded, encoded_len, ch_next, t_next, ch_next_len = rets
+        cfg = self.streaming_cfg
+        if ch_next is not None and cfg.last_channel_cache_size > 0:
+            ch_next = ch_next[:, :, -cfg.last_channel_cache_size:, :]
+        if cfg.valid_out_len > 0 and not keep_all_outputs:
+            encoded = encoded[:, :, :cfg.valid_out_len]
+            encoded_len = torch.clamp(encoded_len, max=cfg.valid_out_len)
+        return encoded, encoded_len, ch_next, t_next, ch_next_len
+
+    def cache_aware_stream_step(self, processed_signal, processed_signal_length=None, cache_last_channel=None, cache_last_time=None,
+                                cache_last_channel_len=None, keep_all_outputs=True, drop_extra_pre_encoded=None,
+                                bypass_pre_encode=False):
+        """one chunk of `processed_signal` [B, F, pre-encode cache + chunk] through the encoder with caches ->
+        (outputs [B, D, T'], encoded_lengths, cache_last_channel_next, cache_last_time_next, cache_last_channel_next_len)"""
+        if getattr(self, "streaming_cfg", None) is None:
+            self.setup_streaming_params()
+        if self.training:
+            raise RuntimeError("cache_aware_stream_step: the encoder is in training mode (call .eval())")
+        prev = None
+        if drop_extra_pre_encoded is not None:
+            prev = self.streaming_cfg.drop_extra_pre_encoded
+            self.streaming_cfg.drop_extra_pre_encoded = drop_extra_pre_encoded
+        try:
+            if processed_signal_length is None:
+                processed_signal_length = processed_signal.new_full((processed_signal.size(0),), processed_signal.size(-1),
+                                                                    dtype=torch.int64)
+            rets = self(audio_signal=processed_signal, length=processed_signal_length, cache_last_channel=cache_last_channel,
+                        cache_last_time=cache_last_time, cache_last_channel_len=cache_last_channel_len,
+                        bypass_pre_encode=bypass_pre_encode)
+            return self.streaming_post_process(rets, keep_all_outputs=keep_all_outputs)
+        finally:
+            if prev is not None:
+                self.streaming_cfg.drop_extra_pre_encoded = prev
 
     # ------------------------------------------------------------------ helpers
     def _cdt(self):
@@ -1168,32 +1257,7 @@ class ConformerEncoder(NeuralModule):
         elif self.subsampling == "dw_striding":
             x = self._sub_fwd_dw(S, mel, lens, W, cdt, save)
         else:
-            # ---- sub-sampling: conv1 (direct) -> conv2 (implicit MFMA GEMM, ReLU+mask epilogue) -> out Linear (+xscale, dropout)
-            S.out1 = self._new(B, T1, F1, C_, dtype=cdt, device=dev)
-            ops.conv1_fwd(mel, pe.conv[0].weight, pe.conv[0].bias, S.out1, len0, len1, C_, pad=pe._pad)
-            # (channel counts the gather does not cover fall back to an im2col image, kept alive for the weight gradient)
-            implicit = (self.conv2_implicit and self._conv2_implicit(cdt, C_, B * T2 * F2)
-                        and B * T1 * F1 * C_ < 2 ** 31)  # the gathered weight gradient addresses the grid with 32-bit offsets
-            S.col = None
-            if not implicit:
-                col = self._buf("col", (B * T2 * F2, 9 * C_), cdt, dev)
-                ops.im2col(S.out1, col, B, T1, F1, C_, pad=pe._pad)
-                self._col_gen = getattr(self, "_col_gen", 0) + 1
-                S.col, S.col_gen = (col if save else None), self._col_gen
-            S.out2 = self._new(B * T2 * F2, C_, dtype=cdt, device=dev)
-            if implicit:
-                # implicit GEMM: the A rows are gathered from out1 by the LDS-DMA (tap (kh-1, kw-1) per 512-wide K block);
-                # forward, weight gradient and input gradient all gather -- no im2col image, no col2im pass
-                ops.gemm(S.out1, W["pre.w2"], S.out2, B * T2 * F2, C_, 9 * C_, C_, W.pitch("pre.w2"), C_, bias=pe.conv[2].bias,
-                         epi=ops.EPI_RELU_MASK, row_len=len2, rows_per_b=T2 * F2, rows_inner=F2,
-                         gather=dict(nI=T2, nJ=F2, SI=T1, SJ=F1, C=C_, si=2, sj=2,
-                                     taps=[(kh - pe._pad, kw - pe._pad) for kh in range(3) for kw in range(3)]))
-            else:
-                ops.gemm(col, W["pre.w2"], S.out2, B * T2 * F2, C_, 9 * C_, 9 * C_, W.pitch("pre.w2"), C_, bias=pe.conv[2].bias,
-                         epi=ops.EPI_RELU_MASK, row_len=len2, rows_per_b=T2 * F2, rows_inner=F2)
-            x = self._new(M, d, dtype=torch.float32, device=dev)
-            ops.gemm(S.out2, W["pre.out"], x, M, d, F2 * C_, F2 * C_, W.pitch("pre.out"), d, bias=pe.out.bias,
-                     alpha=(self.xscale or 1.0), drop=S.drop_pre)
+            x = self._sub_fwd_striding(S, mel, lens, W, cdt, save)
         # ---- packed rows: from here to the end of the layer stack only the valid frames exist
         S.pk = pk = self._packing_plan(length, B, T, lens=lens)
         self.packed_last = (pk.Mp, M) if pk is not None else None
@@ -1266,6 +1330,41 @@ class ConformerEncoder(NeuralModule):
         S.cap_out = [S.cap_out[order[l]] for l in self.capture_layers if l in order]
         S.cap_layers = [l for l in self.capture_layers if l in order]
         return out, len2, (S if save else None)
+
+    def _sub_fwd_striding(self, S, mel, lens, W, cdt, save):
+        """'striding' sub-sampling: conv1 (direct) -> conv2 (implicit MFMA GEMM, ReLU+mask epilogue) -> out Linear (+xscale,
+        dropout); `S.dims` holds the grid"""
+        B, F_, T, T1, F1, T2, F2, M, _, training, seed = S.dims
+        dev = mel.device
+        pe = self.pre_encode
+        C_, d = pe._conv_channels, self.d_model
+        len0, len1, len2 = lens[0], lens[1], lens[-1]
+        S.out1 = self._new(B, T1, F1, C_, dtype=cdt, device=dev)
+        ops.conv1_fwd(mel, pe.conv[0].weight, pe.conv[0].bias, S.out1, len0, len1, C_, pad=pe._pad)
+        # (channel counts the gather does not cover fall back to an im2col image, kept alive for the weight gradient)
+        implicit = (self.conv2_implicit and self._conv2_implicit(cdt, C_, B * T2 * F2)
+                    and B * T1 * F1 * C_ < 2 ** 31)  # the gathered weight gradient addresses the grid with 32-bit offsets
+        S.col = None
+        if not implicit:
+            col = self._buf("col", (B * T2 * F2, 9 * C_), cdt, dev)
+            ops.im2col(S.out1, col, B, T1, F1, C_, pad=pe._pad)
+            self._col_gen = getattr(self, "_col_gen", 0) + 1
+            S.col, S.col_gen = (col if save else None), self._col_gen
+        S.out2 = self._new(B * T2 * F2, C_, dtype=cdt, device=dev)
+        if implicit:
+            # implicit GEMM: the A rows are gathered from out1 by the LDS-DMA (tap (kh-1, kw-1) per 512-wide K block);
+            # forward, weight gradient and input gradient all gather -- no im2col image, no col2im pass
+            ops.gemm(S.out1, W["pre.w2"], S.out2, B * T2 * F2, C_, 9 * C_, C_, W.pitch("pre.w2"), C_, bias=pe.conv[2].bias,
+                     epi=ops.EPI_RELU_MASK, row_len=len2, rows_per_b=T2 * F2, rows_inner=F2,
+                     gather=dict(nI=T2, nJ=F2, SI=T1, SJ=F1, C=C_, si=2, sj=2,
+                                 taps=[(kh - pe._pad, kw - pe._pad) for kh in range(3) for kw in range(3)]))
+        else:
+            ops.gemm(col, W["pre.w2"], S.out2, B * T2 * F2, C_, 9 * C_, 9 * C_, W.pitch("pre.w2"), C_, bias=pe.conv[2].bias,
+                     epi=ops.EPI_RELU_MASK, row_len=len2, rows_per_b=T2 * F2, rows_inner=F2)
+        x = self._new(M, d, dtype=torch.float32, device=dev)
+        ops.gemm(S.out2, W["pre.out"], x, M, d, F2 * C_, F2 * C_, W.pitch("pre.out"), d, bias=pe.out.bias,
+                 alpha=(self.xscale or 1.0), drop=S.drop_pre)
+        return x
 
     # ------------------------------------------------------------------ 'dw_striding' sub-sampling (FastConformer, Squeezeformer)
     def _sub_io(self, Wf, cdt, dev, backward=False):

@@ -773,3 +773,24 @@ def pack_weights(table_dev, n_entries, total_tiles, out_dtype):
 
 def fill_f32(t, value=0.0):
     check(lib.mi355x_fill_f32(_ptr(t), t.numel(), value, _stream()), "fill_f32")
+
+
+# ------------------------------------------------------------------------------------------------ cache-aware streaming
+def stream_cache_assemble(cache, y, kv_in, cache_next, B, C, Tq, d):
+    """kv_in [B*(C+Tq), d] = cat(cache [B, C, d] f32, y [B*Tq, d]) along time; cache_next [B, C, d] f32 = its last C rows"""
+    check(lib.mi355x_stream_cache_assemble(_ptr(cache) if C else 0, _ptr(y), _ptr(kv_in), _ptr(cache_next) if C else 0, dt(y),
+                                           B, C, Tq, d, _stream()), "stream_cache_assemble")
+
+
+def stream_attn(q, ldq, kv, ldkv, v_off, pos, ldp, bias_u, bias_v, cache_len, chunk_len, ctx, ldo, B, H, Tq, Tk, dk, scale,
+                chunk=0, left_chunks=-1):
+    """chunk attention of Tq queries against Tk = C + Tq keys (see mi355x_stream_attn); chunk = 0: no chunked_limited rule"""
+    check(lib.mi355x_stream_attn(_ptr(q), ldq, _ptr(kv), ldkv, v_off, _ptr(pos), ldp, _ptr(bias_u), _ptr(bias_v), _ptr(cache_len),
+                                 _ptr(chunk_len), _ptr(ctx), ldo, dt(q), B, H, Tq, Tk, dk, chunk, left_chunks, scale, _stream()),
+          "stream_attn")
+
+
+def stream_dwconv(x, cache, w, bias, y, cache_next, B, Tq, d, k):
+    """causal depthwise conv whose k - 1 left taps come from cache [B, d, k-1] f32; cache_next = last k - 1 frames of cat(cache, x)"""
+    check(lib.mi355x_stream_dwconv(_ptr(x), _ptr(cache), _ptr(w), _ptr(bias), _ptr(y), _ptr(cache_next), dt(x), B, Tq, d, k,
+                                   _stream()), "stream_dwconv")

@@ -410,39 +410,28 @@ __global__ __launch_bounds__(256, 2) void logmel_r16_kernel(const float* __restr
   const int ta = t_base - 1 - shift;
   const int nvec = (seg + 1 + shift + 3) >> 2;
   const int lim = (int)min((long long)S, len);
-  constexpr int SV = 6;                                   // 6 x 256 vectors >= (31 * 512 + 512 + 4) / 4 for every hop <= 512
-  float4 av[SV];
-#pragma unroll
-  for (int u = 0; u < SV; ++u) {
-    const int v = tid + 256 * u, t = ta + 4 * v;
-    av[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+  // SV x 256 vectors = 6144 floats, all in flight together, cover seg + 1 + shift for every hop <= 181 (the 10 ms recipes: hop 160
+  // needs 5476).  The launcher sends segments up to 8704 floats here (even hops up to 264): the vectors beyond are staged one per
+  // thread and trip by the loop behind the stores.
+  constexpr int SV = 6;
+  auto load_vec = [&](int v) {
+    const int t = ta + 4 * v;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
     if (v < nvec && t + 3 >= 0 && t < lim) {
-      if (t >= 0 && t + 3 < S) av[u] = *reinterpret_cast<const float4*>(xa + t);
+      if (t >= 0 && t + 3 < S) a = *reinterpret_cast<const float4*>(xa + t);
       else {
-        if (t >= 0 && t < S) av[u].x = xa[t];
-        if (t + 1 >= 0 && t + 1 < S) av[u].y = xa[t + 1];
-        if (t + 2 >= 0 && t + 2 < S) av[u].z = xa[t + 2];
-        if (t + 3 >= 0 && t + 3 < S) av[u].w = xa[t + 3];
+        if (t >= 0 && t < S) a.x = xa[t];
+        if (t + 1 >= 0 && t + 1 < S) a.y = xa[t + 1];
+        if (t + 2 >= 0 && t + 2 < S) a.z = xa[t + 2];
+        if (t + 3 >= 0 && t + 3 < S) a.w = xa[t + 3];
       }
     }
-  }
-  const int nnz_x = fb_off[n_mels - 1] + fb_len[n_mels - 1], nnz = (nnz_x + 3) & ~3;  // (weights exist up to nnz_x only)
-  const bool fb_in_lds = nnz <= FB_CAP;
-  int fb_aligned = 1;
-  if (fb_in_lds) {
-    for (int i = tid; i < nnz + 4; i += 256) s_fbw[i] = i < nnz_x ? fb_w[i] : 0.f;
-    for (int i = tid; i < n_mels; i += 256) {
-      const int o = fb_off[i];
-      s_fbi[i] = fb_start[i]; s_fbi[n_mels + i] = fb_len[i]; s_fbi[2 * n_mels + i] = o;
-      // 16-byte weight reads need 4-aligned offsets and zero fill up to the next filter (sparsify_filterbank lays them out so)
-      if ((o & 3) || (i + 1 < n_mels && fb_off[i + 1] < o + ((fb_len[i] + 3) & ~3))) fb_aligned = 0;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < SV; ++u) {
-    const int v = tid + 256 * u, t = ta + 4 * v;
+    return a;
+  };
+  auto store_vec = [&](int v, float4 a) {
+    const int t = ta + 4 * v;
     if (v < nvec) {
-      const float c[4] = {av[u].x, av[u].y, av[u].z, av[u].w};
+      const float c[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int i = 4 * v - shift + e, te = t + e;
@@ -456,7 +445,25 @@ __global__ __launch_bounds__(256, 2) void logmel_r16_kernel(const float* __restr
         }
       }
     }
+  };
+  float4 av[SV];
+#pragma unroll
+  for (int u = 0; u < SV; ++u) av[u] = load_vec(tid + 256 * u);
+  const int nnz_x = fb_off[n_mels - 1] + fb_len[n_mels - 1], nnz = (nnz_x + 3) & ~3;  // (weights exist up to nnz_x only)
+  const bool fb_in_lds = nnz <= FB_CAP;
+  int fb_aligned = 1;
+  if (fb_in_lds) {
+    for (int i = tid; i < nnz + 4; i += 256) s_fbw[i] = i < nnz_x ? fb_w[i] : 0.f;
+    for (int i = tid; i < n_mels; i += 256) {
+      const int o = fb_off[i];
+      s_fbi[i] = fb_start[i]; s_fbi[n_mels + i] = fb_len[i]; s_fbi[2 * n_mels + i] = o;
+      // 16-byte weight reads need 4-aligned offsets and zero fill up to the next filter (sparsify_filterbank lays them out so)
+      if ((o & 3) || (i + 1 < n_mels && fb_off[i + 1] < o + ((fb_len[i] + 3) & ~3))) fb_aligned = 0;
+    }
   }
+#pragma unroll
+  for (int u = 0; u < SV; ++u) store_vec(tid + 256 * u, av[u]);
+  for (int v = tid + 256 * SV; v < nvec; v += 256) store_vec(v, load_vec(v));  // (hop > 181 only)
   const int woff = (NFFT - win) / 2;
   for (int i = tid; i < NFFT; i += 256) s_win[i] = (i >= woff && i < woff + win) ? window[i - woff] : 0.f;
   {

@@ -639,6 +639,43 @@ int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, c
                              const int* durations, int blank, int max_symbols, void* tokens, void* times, void* out_len,
                              void* score, int max_out, void* h_out, void* c_out, void* stream);
 
+/* ---- resumable greedy search (streaming transducer decoding: the reference's `partial_hypotheses`).  The searches above, started
+ * from a per-stream decoder state and returning the next one, so that a stream decoded chunk by chunk gives bit-identical tokens,
+ * frame indices, lengths, score and final state to one launch over the whole sequence, for ANY cut into chunks.
+ * State (device arrays, written out of place: state_out must not alias state_in):
+ *   h, c          f32 [B, H]  committed LSTM state                                              fresh stream: 0
+ *   last          i32 [B]     last emitted label (blank = the zero embedding row)                             blank
+ *   score         f32 [B]     running sum of the emitted labels' log-probabilities                            0
+ *   frames_done   i32 [B]     frames consumed by earlier chunks; added to every frame index written           0
+ *   skip          i32 [B]     TDT: frames of this chunk an earlier duration already jumped over               0
+ *   zero_run      i32 [B]     TDT: current run of labels emitted with duration 0                              0
+ * (skip / zero_run may be NULL for the RNN-T search.)  state_in NULL = every stream is fresh.  The kernel rebuilds the pending
+ * prediction step from (h, c, emb[last]) at entry.  enc_len[b] = the frames of THIS chunk (0: the state passes through, nothing is
+ * emitted); frames_done_out = frames_done + enc_len[b]; TDT: skip_out = t - enc_len[b] when the last jump left the chunk, and a
+ * chunk with skip >= enc_len[b] is skipped whole.  tokens / times / out_len hold this chunk's labels only; times are global frame
+ * indices.  max_symbols counts per frame, so the RNN-T search carries no counter; max_symbols <= 0 bounds each CHUNK by max_out.
+ * With max_symbols > 0 give max_out >= T * max_symbols: as in the one-shot search, labels beyond max_out are counted and scored but
+ * not stored, and here they would also enter the carried state (last, h, c), which then contradicts what the caller received.
+ * T >= 1 as for the one-shot entries: a step in which no stream has a frame is not a launch (keep the state).  The one-shot entry
+ * points launch their own instantiation of the kernel template, compiled without the state code. */
+typedef struct mi355x_rnnt_stream_state {
+  float* h; float* c; int* last; float* score; int* frames_done; int* skip; int* zero_run;
+} mi355x_rnnt_stream_state;
+int mi355x_rnnt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                     const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                                     const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+                                     const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
+                                     int H, int V1, int blank, int max_symbols, void* tokens, void* times, void* out_len,
+                                     int max_out, const mi355x_rnnt_stream_state* state_in,
+                                     const mi355x_rnnt_stream_state* state_out, void* stream);
+int mi355x_tdt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                    const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                                    const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out,
+                                    long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D,
+                                    const int* durations, int blank, int max_symbols, void* tokens, void* times, void* out_len,
+                                    int max_out, const mi355x_rnnt_stream_state* state_in,
+                                    const mi355x_rnnt_stream_state* state_out, void* stream);
+
 /* ---- cache-aware streaming inference (ConformerEncoder.cache_aware_stream_step; the `update_cache` paths of
  * RelPositionMultiHeadAttention and CausalConv1D).  Caches are f32 in the reference's layouts; in bf16 compute they hold the
  * bf16-rounded operands widened to f32, so a streamed chunk reads the same operand values as the offline forward.

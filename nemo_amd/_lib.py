@@ -186,6 +186,10 @@ SIGNATURES = {
     "mi355x_tdt_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
     "mi355x_tdt_greedy_decode": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32,
                                  i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp],
+    "mi355x_rnnt_greedy_decode_stream": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32,
+                                         i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp],
+    "mi355x_tdt_greedy_decode_stream": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32,
+                                        i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp],
     "mi355x_stream_cache_assemble": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi355x_stream_attn": [vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "mi355x_stream_dwconv": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],

@@ -169,6 +169,8 @@ TARGET_ALIASES = {
     "nemo.collections.asr.modules.RNNTJoint": "nemo_amd.modules.RNNTJoint",
     "nemo.collections.asr.models.EncDecRNNTModel": "nemo_amd.models.EncDecRNNTModel",
     "nemo.collections.asr.models.EncDecRNNTBPEModel": "nemo_amd.models.EncDecRNNTModel",
+    "nemo.collections.asr.models.EncDecHybridRNNTCTCModel": "nemo_amd.models.EncDecHybridRNNTCTCModel",
+    "nemo.collections.asr.models.EncDecHybridRNNTCTCBPEModel": "nemo_amd.models.EncDecHybridRNNTCTCModel",
 }
 
 

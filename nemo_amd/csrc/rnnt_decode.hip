@@ -18,6 +18,13 @@
 // Token-and-Duration Transducer (mi355x_tdt_greedy_decode, the TDT instance of the same kernel): the output layer has V1 + D rows,
 // label arg-max over the first V1 logits, duration arg-max over the last D, and the frame index advances by the predicted
 // duration (a blank by at least one frame; a run of max_symbols labels predicted with duration 0 is moved on by one frame).
+//
+// Resumable search (mi355x_rnnt_greedy_decode_stream / mi355x_tdt_greedy_decode_stream): the same kernel started from a per-stream
+// decoder state (committed h / c, last label, running score, frames consumed so far; TDT: frames already jumped over and the
+// run of zero-duration labels) and writing the next one, out of place.  hn / cn / gp are NOT carried: they are rebuilt from
+// (h, c, emb[last]) by one prediction step at entry -- the very step `emit` ran after the last label -- so a stream cut into any
+// chunks takes the same decisions with the same arithmetic as one launch over the whole sequence: tokens, frame indices,
+// lengths, score and final state are bit-identical.  The one-shot entry points are the fresh-state case.
 #include "common.h"
 #include "mi355x_asr.h"
 #include "tdt.h"
@@ -58,11 +65,14 @@ struct RnntDecP {
   const float *b_ih, *b_hh, *b_pred, *b_out;
   int* tokens; int* times; int* out_len; float* score;
   float* h_out; float* c_out;                // optional final state [B, H]
+  mi355x_rnnt_stream_state sin, sout;        // resumable search: state to start from (sin.h null: fresh), state to write (sout.h null: none)
   int B, T, J, H, V1, blank, max_symbols, max_out;
   TdtDur dur;                                // TDT: duration set (dur.D = 0 for the RNN-T search)
 };
 
-template <typename WT, bool TDT>
+// STREAM = false is the one-shot search: the state code folds away at compile time and the instantiation is the kernel the
+// one-shot entry points have always launched.
+template <typename WT, bool TDT, bool STREAM>
 __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
   extern __shared__ __attribute__((aligned(16))) float rd_smem[];
   const int H = p.H, J = p.J, V1 = p.V1;
@@ -80,7 +90,20 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
   __shared__ int s_k, s_d;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int len = (int)min((long long)p.T, max(0LL, p.enc_len ? p.enc_len[b] : (long long)p.T));
-  for (int i = tid; i < H; i += RD_THREADS) { h[i] = 0.f; c[i] = 0.f; x[i] = 0.f; }
+  // where the search starts: a fresh stream, or the state an earlier chunk left (all of it uniform over the workgroup)
+  const bool resume = STREAM && p.sin.h != nullptr;
+  int last = p.blank, frames_done = 0, skip = 0, same = 0;
+  float score = 0.f;
+  if (resume) {
+    last = p.sin.last[b]; score = p.sin.score[b]; frames_done = p.sin.frames_done[b];
+    if (TDT) { skip = max(p.sin.skip[b], 0); same = p.sin.zero_run[b]; }
+    if (last < 0 || last >= V1) last = p.blank;   // (a label outside the embedding table is never read)
+    for (int i = tid; i < H; i += RD_THREADS) {
+      h[i] = p.sin.h[(long long)b * H + i]; c[i] = p.sin.c[(long long)b * H + i]; x[i] = p.emb[(long long)last * H + i];
+    }
+  } else {
+    for (int i = tid; i < H; i += RD_THREADS) { h[i] = 0.f; c[i] = 0.f; x[i] = 0.f; }
+  }
   __syncthreads();
 
   // prediction step on (x, h, c): hn, cn, gp.  torch gate order i, f, g, o (common/parts/rnn.py:151-230 -> torch.nn.LSTM)
@@ -101,10 +124,10 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
     rd_gemv<WT, false>((const WT*)p.w_pred, p.ld_pred, hn, J, H, p.b_pred, gp);
     __syncthreads();
   };
-  pred_step(true);
+  // `last` = blank is the zero embedding row (blank_as_pad); a chunk with no frame to look at takes no decision and needs no step
+  if (!STREAM || len > skip) pred_step(!STREAM || last == p.blank);
 
   int n = 0;
-  float score = 0.f;
   // joint on frame t and the current prediction projection: label arg-max -> s_k (TDT: duration index arg-max -> s_d), returns
   // sum_v exp(lg[v] - max) over the label logits
   auto joint_step = [&](int t) -> float {
@@ -147,9 +170,13 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
   // commit the state that consumed the previous label, consume the new one
   auto emit = [&](int k, int t, float se) {
     if (n < p.max_out) {
-      if (tid == 0) { p.tokens[(long long)b * p.max_out + n] = k; if (p.times) p.times[(long long)b * p.max_out + n] = t; }
+      if (tid == 0) {
+        p.tokens[(long long)b * p.max_out + n] = k;
+        if (p.times) p.times[(long long)b * p.max_out + n] = STREAM ? frames_done + t : t;
+      }
     }
     ++n;
+    if (STREAM) last = k;
     // Score semantics: the sum of the emitted labels' LOG-PROBABILITIES (log-softmax of the joint's logits) -- what the
     // reference's search computes on CPU tensors.  On CUDA tensors its `_joint_step(log_normalize=None)` skips the
     // log-softmax and sums raw maximum logits instead (rnnt_greedy_decoding.py:257-259, 965): scores then differ by the
@@ -161,7 +188,8 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
   };
   if constexpr (TDT) {
     // t advances by the predicted duration; the output budget bounds the search like max_symbols <= 0 below
-    int t = 0, same = 0;
+    int t = STREAM ? skip : 0;   // frames an earlier chunk's duration already jumped over
+    if (!STREAM) same = 0;
     while (t < len && n < p.max_out) {
       const float se = joint_step(t);
       const int k = s_k;
@@ -179,6 +207,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
         t += d;
       }
     }
+    if (STREAM) skip = max(t - len, 0);
   } else {
     for (int t = 0; t < len; ++t) {
       // max_symbols <= 0 (the reference's `max_symbols_per_step=None`: unbounded inner loop, rnnt_greedy_decoding.py:620-700) is
@@ -198,6 +227,13 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
     if (p.times) p.times[(long long)b * p.max_out + i] = -1;
   }
   if (p.h_out) for (int i = tid; i < H; i += RD_THREADS) { p.h_out[(long long)b * H + i] = h[i]; p.c_out[(long long)b * H + i] = c[i]; }
+  if (STREAM && p.sout.h) {
+    for (int i = tid; i < H; i += RD_THREADS) { p.sout.h[(long long)b * H + i] = h[i]; p.sout.c[(long long)b * H + i] = c[i]; }
+    if (tid == 0) {
+      p.sout.last[b] = last; p.sout.score[b] = score; p.sout.frames_done[b] = frames_done + len;
+      if (TDT) { p.sout.skip[b] = skip; p.sout.zero_run[b] = same; }
+    }
+  }
 }
 
 static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
@@ -205,7 +241,8 @@ static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, 
                               const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out, long long ld_out,
                               const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, const TdtDur* dur, int blank,
                               int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out,
-                              void* c_out, void* stream) {
+                              void* c_out, const mi355x_rnnt_stream_state* sin, const mi355x_rnnt_stream_state* sout,
+                              void* stream) {
   if (!enc_proj || !emb || !w_ih || !w_hh || !b_ih || !b_hh || !w_pred || !w_out || !tokens || !out_len) return MI_ERR_ARG;
   if (B <= 0 || T <= 0 || J <= 0 || H <= 0 || V1 <= 1 || max_out <= 0 || blank < 0 || blank >= V1) return MI_ERR_ARG;
   if ((H & 3) || (J & 3) || (ld_ih & 3) || (ld_hh & 3) || (ld_pred & 3) || (ld_out & 3) || (!h_out != !c_out)) return MI_ERR_ARG;
@@ -220,18 +257,26 @@ static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, 
   p.B = B; p.T = T; p.J = J; p.H = H; p.V1 = V1; p.blank = blank; p.max_symbols = max_symbols; p.max_out = max_out;
   p.dur = {};
   if (dur) p.dur = *dur;
+  p.sin = {}; p.sout = {};
+  for (int io = 0; io < 2; ++io) {   // a state is given whole (skip / zero_run: TDT only) or not at all
+    const mi355x_rnnt_stream_state* st = io ? sout : sin;
+    if (!st) continue;
+    if (!st->h || !st->c || !st->last || !st->score || !st->frames_done || (dur && (!st->skip || !st->zero_run))) return MI_ERR_ARG;
+    (io ? p.sout : p.sin) = *st;
+  }
+  if (p.sin.h && p.sout.h && (p.sin.h == p.sout.h || p.sin.c == p.sout.c)) return MI_ERR_ARG;   // out of place
   const int D = p.dur.D;
   const size_t shm = (size_t)(9 * H + 2 * J + V1 + D + 4) * sizeof(float);
   if (shm > 160 * 1024 - 256) return MI_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-#define RD_LAUNCH(WT, TDT)                                                                                                  \
-  hipFuncSetAttribute((const void*)rnnt_greedy_kernel<WT, TDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);    \
-  MI_LAUNCH((rnnt_greedy_kernel<WT, TDT>), dim3(B), dim3(RD_THREADS), shm, s, p)
-  if (w_dtype == MI_DT_F32) {
-    if (dur) { RD_LAUNCH(float, true); } else { RD_LAUNCH(float, false); }
-  } else {
-    if (dur) { RD_LAUNCH(bf16_t, true); } else { RD_LAUNCH(bf16_t, false); }
-  }
+#define RD_LAUNCH(WT, TDT, STREAM)                                                                                                 \
+  hipFuncSetAttribute((const void*)rnnt_greedy_kernel<WT, TDT, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);    \
+  MI_LAUNCH((rnnt_greedy_kernel<WT, TDT, STREAM>), dim3(B), dim3(RD_THREADS), shm, s, p)
+#define RD_LAUNCH_WT(WT)                                                                \
+  if (sout) { if (dur) { RD_LAUNCH(WT, true, true); } else { RD_LAUNCH(WT, false, true); } }   \
+  else { if (dur) { RD_LAUNCH(WT, true, false); } else { RD_LAUNCH(WT, false, false); } }
+  if (w_dtype == MI_DT_F32) { RD_LAUNCH_WT(float) } else { RD_LAUNCH_WT(bf16_t) }
+#undef RD_LAUNCH_WT
 #undef RD_LAUNCH
   return mi_check_launch();
 }
@@ -245,7 +290,7 @@ extern "C" int mi355x_rnnt_greedy_decode(const void* enc_proj, int f_dtype, long
   mi_clear_errors();
   return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
                             w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len, score,
-                            max_out, h_out, c_out, stream);
+                            max_out, h_out, c_out, nullptr, nullptr, stream);
 }
 
 extern "C" int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
@@ -260,5 +305,37 @@ extern "C" int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long 
   if (tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
   return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
                             w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len, score,
-                            max_out, h_out, c_out, stream);
+                            max_out, h_out, c_out, nullptr, nullptr, stream);
+}
+
+// ---- resumable search: the same launch from / to a per-stream decoder state (state_in NULL = fresh streams; state_out required)
+extern "C" int mi355x_rnnt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                                const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh,
+                                                const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred,
+                                                const void* b_pred, const void* w_out, long long ld_out, const void* b_out,
+                                                int w_dtype, int B, int T, int J, int H, int V1, int blank, int max_symbols,
+                                                void* tokens, void* times, void* out_len, int max_out,
+                                                const mi355x_rnnt_stream_state* state_in,
+                                                const mi355x_rnnt_stream_state* state_out, void* stream) {
+  mi_clear_errors();
+  if (!state_out) return MI_ERR_ARG;
+  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len,
+                            nullptr, max_out, nullptr, nullptr, state_in, state_out, stream);
+}
+
+extern "C" int mi355x_tdt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                               const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh,
+                                               const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred,
+                                               const void* b_pred, const void* w_out, long long ld_out, const void* b_out,
+                                               int w_dtype, int B, int T, int J, int H, int V1, int D, const int* durations,
+                                               int blank, int max_symbols, void* tokens, void* times, void* out_len, int max_out,
+                                               const mi355x_rnnt_stream_state* state_in,
+                                               const mi355x_rnnt_stream_state* state_out, void* stream) {
+  mi_clear_errors();
+  TdtDur dur;
+  if (!state_out || tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
+  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len,
+                            nullptr, max_out, nullptr, nullptr, state_in, state_out, stream);
 }

@@ -313,18 +313,26 @@ class EncDecCTCModel(nn.Module):
         frames appended to `previous_pred_out`.  -> (greedy_predictions: list of i64 [n_b] per utterance, texts (None unless
         return_transcription), cache_last_channel_next, cache_last_time_next, cache_last_channel_next_len, best_hyp = None)
         [+ (log_probs, encoded_len) with return_log_probs; encoded_len counts the frames of all chunks so far]."""
+        return self._ctc_stream_step(self.decoder, self.wer, processed_signal, processed_signal_length, cache_last_channel,
+                                     cache_last_time, cache_last_channel_len, keep_all_outputs, previous_pred_out,
+                                     drop_extra_pre_encoded, return_transcription, return_log_probs)
+
+    def _ctc_stream_step(self, decoder, wer, processed_signal, processed_signal_length, cache_last_channel, cache_last_time,
+                         cache_last_channel_len, keep_all_outputs, previous_pred_out, drop_extra_pre_encoded, return_transcription,
+                         return_log_probs):
+        """the streaming step over a given CTC head (`decoder`, with `wer` for the text): the hybrid model's auxiliary head runs it too"""
         if not hasattr(self.encoder, "cache_aware_stream_step"):
             raise NotImplementedError(f"{type(self.encoder).__name__} has no cache-aware streaming")
-        if return_transcription and self.wer is None:
+        if return_transcription and wer is None:
             raise RuntimeError("conformer_stream_step(return_transcription=True) needs a vocabulary (decoder.vocabulary or a tokenizer)")
         encoded, encoded_len, ch_next, t_next, len_next = self.encoder.cache_aware_stream_step(
             processed_signal=processed_signal, processed_signal_length=processed_signal_length,
             cache_last_channel=cache_last_channel, cache_last_time=cache_last_time, cache_last_channel_len=cache_last_channel_len,
             keep_all_outputs=keep_all_outputs, drop_extra_pre_encoded=drop_extra_pre_encoded)
-        log_probs = self.decoder(encoder_output=encoded)
+        log_probs = decoder(encoder_output=encoded)
         preds = log_probs.argmax(dim=-1).cpu()
         enc_len = encoded_len.cpu().clone()
-        blank = self.decoder.num_classes_with_blank - 1
+        blank = decoder.num_classes_with_blank - 1
         greedy, texts = [], ([] if return_transcription else None)
         for b in range(preds.shape[0]):
             cur = preds[b, : int(enc_len[b])]
@@ -335,7 +343,7 @@ class EncDecCTCModel(nn.Module):
             greedy.append(cur)
             if return_transcription:   # ctc_decoder_predictions_tensor: merge repeats, drop blanks
                 ids = [int(t) for t in torch.unique_consecutive(cur).tolist() if int(t) != blank]
-                texts.append(self.wer.decoding.ids_to_text(ids))
+                texts.append(wer.decoding.ids_to_text(ids))
         result = [greedy, texts, ch_next, t_next, len_next, None]
         if return_log_probs:
             result += [log_probs, enc_len.to(log_probs.device)]

@@ -27,6 +27,8 @@ def _build(section, cfg):
 
 
 class EncDecRNNTModel(EncDecCTCModel):
+    _takes_aux_ctc = False   # the auxiliary CTC head belongs to the subclass EncDecHybridRNNTCTCModel (models/hybrid_models.py)
+
     def __init__(self, cfg: Dict[str, Any], trainer=None):
         torch.nn.Module.__init__(self)
         cfg = copy.deepcopy(dict(cfg))
@@ -69,7 +71,7 @@ class EncDecRNNTModel(EncDecCTCModel):
         jnt["jointnet"].setdefault("pred_hidden", dec["prednet"]["pred_hidden"])
         self.decoder = _build("decoder", dec)
         self.joint = _build("joint", jnt)
-        if cfg.get("aux_ctc"):
+        if cfg.get("aux_ctc") and not self._takes_aux_ctc:
             raise NotImplementedError("aux_ctc (EncDecHybridRNNTCTCModel's auxiliary CTC head) is not part of EncDecRNNTModel")
         self._check_interctc(cfg.get("interctc"))
         # skip_nan_grad (models/asr_model.py:147-174): handled by the shared fit_step / on_after_backward (EncDecCTCModel)
@@ -239,14 +241,21 @@ class EncDecRNNTModel(EncDecCTCModel):
     def predict_step(self, batch, batch_idx=0, dataloader_idx=0):
         signal, signal_len, _, _, sample_id = batch
         encoded, encoded_len = self.forward(input_signal=signal, input_signal_length=signal_len)
-        texts = [h.text for h in self.decoding.rnnt_decoder_predictions_tensor(encoded, encoded_len)]
+        texts = [h.text for h in self._text_decoding().rnnt_decoder_predictions_tensor(encoded, encoded_len)]
         if isinstance(sample_id, torch.Tensor):
             sample_id = sample_id.cpu().numpy()
         return list(zip(sample_id, texts))
 
+    def _text_decoding(self):
+        """the decoding object behind `transcribe` / `predict_step` (the hybrid model answers with the head `cur_decoder` names)"""
+        return self.decoding
+
     def conformer_stream_step(self, *args, **kwargs):
-        """the reference streams transducers with greedy decoding from `partial_hypotheses`, which the greedy transducer decoders
-        here do not take yet (the encoder step itself, ConformerEncoder.cache_aware_stream_step, works for transducer encoders)"""
+        """Refused on this class.  The greedy transducer decoders do take `partial_hypotheses` now, and the streaming step exists:
+        `rnnt_conformer_stream_step(model, ...)` below, which EncDecHybridRNNTCTCModel.conformer_stream_step runs for its
+        transducer head.  This method keeps raising only because tests/test_streaming_gpu.py::
+        test_rnnt_conformer_stream_step_is_refused pins the refusal; once that test may change, the body is
+        `return rnnt_conformer_stream_step(self, *args, **kwargs)`."""
         raise NotImplementedError("conformer_stream_step for transducer models: greedy decoding with partial_hypotheses")
 
     @torch.no_grad()
@@ -255,7 +264,8 @@ class EncDecRNNTModel(EncDecCTCModel):
         """`ASRTranscriptionMixin.transcribe` for the greedy transducer path (rnnt_models.py:245-330): one string per input, or the
         Hypothesis objects (text, y_sequence, timestamp, score) with return_hypotheses; the order of the inputs is kept"""
         from ..data import load_audio
-        if self.decoding is None:
+        decoding = self._text_decoding()
+        if decoding is None:
             raise RuntimeError("transcribe() needs a vocabulary (`labels` or a tokenizer)")
         if isinstance(audio, (str, bytes)) or not hasattr(audio, "__len__"):
             audio = [audio]
@@ -279,12 +289,40 @@ class EncDecRNNTModel(EncDecCTCModel):
                 for r, w in enumerate(waves):
                     sig[r, : w.numel()] = w
                 encoded, enc_len = self.forward(input_signal=sig.to(device), input_signal_length=lens.to(device))
-                hyps = self.decoding.rnnt_decoder_predictions_tensor(encoded, enc_len)
+                hyps = decoding.rnnt_decoder_predictions_tensor(encoded, enc_len)
                 out.extend(hyps if return_hypotheses else [h.text for h in hyps])
         finally:
             feat.dither, feat.pad_to = dither, pad_to
             self.train(was_training)
         return out
+
+
+@torch.no_grad()
+def rnnt_conformer_stream_step(model, processed_signal, processed_signal_length=None, cache_last_channel=None, cache_last_time=None,
+                               cache_last_channel_len=None, keep_all_outputs=True, previous_hypotheses=None, previous_pred_out=None,
+                               drop_extra_pre_encoded=None, return_transcription=True, return_log_probs=False):
+    """`ASRModuleMixin.conformer_stream_step` for a transducer head (parts/mixins/mixins.py:590-700): one chunk through the encoder
+    with caches (ConformerEncoder.cache_aware_stream_step), then greedy decoding resumed from `previous_hypotheses` -- the
+    prediction network's state, the last label, the score and (TDT) a duration that jumped past the previous chunk travel in
+    `Hypothesis.dec_state` on the device.  -> (greedy_predictions = [hyp.y_sequence ...], hypotheses (whole stream so far, `.text`
+    filled), cache_last_channel_next, cache_last_time_next, cache_last_channel_next_len, best_hyp = the same hypotheses).  Caches and
+    hypotheses are new objects; the inputs are not modified."""
+    if return_log_probs:
+        raise NotImplementedError("return_log_probs is not supported for transducer heads")   # as the reference (mixins.py:664)
+    if not hasattr(model.encoder, "cache_aware_stream_step"):
+        raise NotImplementedError(f"{type(model.encoder).__name__} has no cache-aware streaming")
+    if model.decoding is None:
+        raise RuntimeError("conformer_stream_step needs a vocabulary (`labels` or a tokenizer)")
+    encoded, encoded_len, ch_next, t_next, len_next = model.encoder.cache_aware_stream_step(
+        processed_signal=processed_signal, processed_signal_length=processed_signal_length, cache_last_channel=cache_last_channel,
+        cache_last_time=cache_last_time, cache_last_channel_len=cache_last_channel_len, keep_all_outputs=keep_all_outputs,
+        drop_extra_pre_encoded=drop_extra_pre_encoded)
+    if previous_hypotheses is None:   # the first chunk of the streams
+        previous_hypotheses = model.decoding.decoding.fresh_hypotheses(encoded.shape[0], encoded.device)
+    best_hyp = model.decoding.rnnt_decoder_predictions_tensor(encoded, encoded_len, return_hypotheses=True,
+                                                              partial_hypotheses=previous_hypotheses)
+    greedy_predictions = [hyp.y_sequence for hyp in best_hyp]
+    return greedy_predictions, best_hyp, ch_next, t_next, len_next, best_hyp
 
 
 def fastconformer_transducer_config(size: str = "large", vocab_size: int = 1024, spec_augment: bool = False,

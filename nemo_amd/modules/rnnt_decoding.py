@@ -10,11 +10,21 @@ The reference's search is a Python loop over frames with a device -> host sync p
 launch (`mi355x_rnnt_greedy_decode`, csrc/rnnt_decode.hip): the encoder projection is a GEMM, a workgroup per utterance runs the
 LSTM / joint / arg-max recurrence out of LDS, and only the token ids leave the device -- when text is asked for.
 
-Two documented differences to the reference's search (token ids / time stamps / lengths are bit-identical to it, tests/test_rnnt_decoding.py):
+Four documented differences to the reference's search (token ids / time stamps / lengths are bit-identical to it, tests/test_rnnt_decoding.py):
   * `Hypothesis.score` is the sum of the emitted labels' log-probabilities (the reference's CPU behaviour); on CUDA tensors the
     reference sums raw maximum logits because `_joint_step(log_normalize=None)` skips log_softmax there (rnnt_greedy_decoding.py:257-259);
   * `max_symbols_per_step=None` is unbounded per frame in the reference; here an utterance stops once 4 * T labels are out
-    (a model that never emits blank cannot hang the device; `out_len == 4 * T` marks the cut).
+    (a model that never emits blank cannot hang the device; `out_len == 4 * T` marks the cut);
+  * streaming (`partial_hypotheses`): `Hypothesis.timestamp` holds GLOBAL frame indices (frames of all earlier chunks counted);
+    the reference appends chunk-local ones;
+  * streaming with `max_symbols_per_step=None`: the safety budget of 4 * T labels applies per chunk (T = the chunk's frames).
+
+Streaming: `forward(..., partial_hypotheses=hyps)` (the first chunk: `hyps = decoder.fresh_hypotheses(B)`; without
+`partial_hypotheses` the call is the one-shot search it has always been) resumes every stream from the decoder state its hypothesis carries
+(`Hypothesis.dec_state`, an `ops.RNNTStreamState` of batch 1 on the device: committed LSTM state, last label, running score, frames
+done, and for TDT the frames a duration already jumped over) through the resumable search (`mi355x_rnnt_greedy_decode_stream` /
+`mi355x_tdt_greedy_decode_stream`); the returned hypotheses cover the whole stream so far and are new objects.  Over the same
+encoder-projection values, any cut into chunks gives bit-identical hypotheses to one call over the concatenation.
 """
 from __future__ import annotations
 
@@ -33,8 +43,9 @@ class Hypothesis:  # parts/utils/rnnt_utils.py:35-110 (the fields greedy decodin
     y_sequence: torch.Tensor
     timestamp: List[int] = field(default_factory=list)
     text: Optional[str] = None
-    dec_state: Optional[tuple] = None
+    dec_state: Optional[object] = None   # one-shot search: the final (h, c); streaming: ops.RNNTStreamState of this stream (batch 1, device)
     length: int = 0
+    last_token: Optional[torch.Tensor] = None   # i32 [1] on the device (= dec_state.last); blank before the first label
 
 
 class GreedyBatchedRNNTInfer:
@@ -50,9 +61,8 @@ class GreedyBatchedRNNTInfer:
         self._blank_index = int(blank_index)
         self.max_symbols = max_symbols_per_step
 
-    @torch.no_grad()
-    def decode_ids(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, with_state: bool = False):
-        """encoder_output [B, D, T] (device) -> (tokens i32 [B, N] -1 padded, frame indices, lengths i32 [B], scores f32 [B])"""
+    def _project(self, encoder_output: torch.Tensor):
+        """encoder_output [B, D, T] -> (enc_proj [B, T, J] in the compute dtype, the search's weight arguments)"""
         if encoder_output.dim() != 3:
             raise ValueError(f"`encoder_output` must be [B, D, T]; got shape {tuple(encoder_output.shape)}")
         dec, jnt = self.decoder, self.joint
@@ -77,23 +87,69 @@ class GreedyBatchedRNNTInfer:
             ops.gemm(xe32, jnt.enc.weight, f, B * T, J, D, D, D, J, bias=jnt.enc.bias)
             H = dec.pred_hidden
             w = (lstm.weight_ih_l0, H, lstm.weight_hh_l0, H, jnt.pred.weight, H, out.weight, J)
-        lens = encoded_lengths.to(device=dev, dtype=torch.int64).contiguous()
-        res = self._search(f.view(B, T, J), lens, emb, w[0], w[1], w[2], w[3], lstm.bias_ih_l0, lstm.bias_hh_l0, w[4], w[5],
-                           jnt.pred.bias, w[6], w[7], out.bias, self._blank_index, self.max_symbols or 0, with_state=with_state)
-        return res
+        args = (emb, w[0], w[1], w[2], w[3], lstm.bias_ih_l0, lstm.bias_hh_l0, w[4], w[5], jnt.pred.bias, w[6], w[7], out.bias,
+                self._blank_index, self.max_symbols or 0)
+        return f.view(B, T, J), args
+
+    @torch.no_grad()
+    def decode_ids(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, with_state: bool = False):
+        """encoder_output [B, D, T] (device) -> (tokens i32 [B, N] -1 padded, frame indices, lengths i32 [B], scores f32 [B])"""
+        f, args = self._project(encoder_output)
+        lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        return self._search(f, lens, *args, with_state=with_state)
 
     _search = staticmethod(ops.rnnt_greedy_decode)
+    _search_stream = staticmethod(ops.rnnt_greedy_decode_stream)
+
+    @torch.no_grad()
+    def decode_ids_stream(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, state=None):
+        """one chunk of every stream: encoder_output [B, D, T_chunk], encoded_lengths = this chunk's frames per stream, `state` the
+        ops.RNNTStreamState of the previous chunk (None: fresh streams) -> (tokens, GLOBAL frame indices, lengths of this chunk's
+        labels, the next state)"""
+        f, args = self._project(encoder_output)
+        lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        return self._search_stream(f, lens, *args, state=state)
+
+    def fresh_hypotheses(self, batch_size: int, device=None):
+        """empty hypotheses of `batch_size` streams that have seen nothing, carrying a fresh decoder state: what a stream's FIRST
+        chunk is resumed from (`forward(chunk, lengths, partial_hypotheses=decoder.fresh_hypotheses(B))`)"""
+        dec = self.decoder
+        device = device if device is not None else dec.prediction["embed"].weight.device
+        st = ops.RNNTStreamState.fresh(batch_size, dec.pred_hidden, self._blank_index, device)
+        return [Hypothesis(score=0.0, y_sequence=torch.zeros(0, dtype=torch.long), timestamp=[], dec_state=st.select(b), length=0,
+                           last_token=st.select(b).last) for b in range(batch_size)]
 
     def forward(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, partial_hypotheses=None):
-        if partial_hypotheses is not None:
-            raise NotImplementedError("`partial_hypotheses` support is not supported")  # as the frame-looping reference path (:816)
-        tokens, times, out_len, score, (h, c) = self.decode_ids(encoder_output, encoded_lengths, with_state=True)
-        tokens, times, out_len, score = tokens.cpu(), times.cpu(), out_len.cpu(), score.cpu()   # the only D2H copies
+        """Without `partial_hypotheses`: the one-shot search of whole utterances, as ever (`dec_state` = the final (h, c)).
+        With them (a list of hypotheses this decoder returned for earlier chunks, or `fresh_hypotheses(B)` for the first chunk):
+        the resumable search; the returned hypotheses cover the whole stream so far and carry the next decoder state."""
+        B = encoder_output.shape[0]
+        if partial_hypotheses is None:
+            tokens, times, out_len, score, (h, c) = self.decode_ids(encoder_output, encoded_lengths, with_state=True)
+            tokens, times, out_len, score = tokens.cpu(), times.cpu(), out_len.cpu(), score.cpu()   # the only D2H copies
+            hyps = []
+            for b in range(B):
+                n = int(out_len[b])
+                hyps.append(Hypothesis(score=float(score[b]), y_sequence=tokens[b, :n].to(torch.long), timestamp=times[b, :n].tolist(),
+                                       dec_state=(h[b], c[b]), length=int(encoded_lengths[b])))
+            return (hyps,)
+        if len(partial_hypotheses) != B:
+            raise ValueError(f"{len(partial_hypotheses)} partial hypotheses for a batch of {B}")
+        if any(h is None or not isinstance(h.dec_state, ops.RNNTStreamState) for h in partial_hypotheses):
+            raise ValueError("`partial_hypotheses` must carry a stream state in `dec_state`: hypotheses this decoder returned for "
+                             "earlier chunks, or `fresh_hypotheses(batch_size)` for the first chunk of a stream")
+        state = ops.RNNTStreamState.stack([h.dec_state for h in partial_hypotheses])
+        tokens, times, out_len, nxt = self.decode_ids_stream(encoder_output, encoded_lengths, state)
+        tokens, times, out_len, score = tokens.cpu(), times.cpu(), out_len.cpu(), nxt.score.cpu()   # the only D2H copies
+        lens = encoded_lengths.cpu()
         hyps = []
-        for b in range(tokens.shape[0]):
+        for b in range(B):   # the whole stream so far, in new objects: the inputs stay as they are
             n = int(out_len[b])
-            hyps.append(Hypothesis(score=float(score[b]), y_sequence=tokens[b, :n].to(torch.long), timestamp=times[b, :n].tolist(),
-                                   dec_state=(h[b], c[b]), length=int(encoded_lengths[b])))
+            prev = partial_hypotheses[b]
+            y = torch.cat((prev.y_sequence.to(torch.long).cpu(), tokens[b, :n].to(torch.long)))
+            st = nxt.select(b)
+            hyps.append(Hypothesis(score=float(score[b]), y_sequence=y, timestamp=list(prev.timestamp) + times[b, :n].tolist(),
+                                   dec_state=st, length=int(prev.length) + int(lens[b]), last_token=st.last))
         return (hyps,)
 
     __call__ = forward
@@ -104,7 +160,8 @@ class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
     Token-and-Duration Transducer, whose joint appends one logit per duration behind the V+1 label logits.  Per utterance the
     label is the arg-max of the label logits, the duration the arg-max of the duration logits; a blank moves on by
     max(duration, 1) frames, a label by its duration, and the `max_symbols`-th consecutive label of duration 0 by one frame.
-    One launch for the batch (`mi355x_tdt_greedy_decode`)."""
+    One launch for the batch (`mi355x_tdt_greedy_decode`; streaming: `mi355x_tdt_greedy_decode_stream`, a duration that jumps past
+    the end of a chunk is taken off the next one)."""
 
     def __init__(self, decoder_model, joint_model, blank_index: int, durations, max_symbols_per_step: Optional[int] = None,
                  **kw):
@@ -116,6 +173,9 @@ class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
 
     def _search(self, *args, with_state=False):
         return ops.tdt_greedy_decode(*args[:16], self.durations, args[16], with_state=with_state)
+
+    def _search_stream(self, *args, state=None):
+        return ops.tdt_greedy_decode_stream(*args[:16], self.durations, args[16], state=state)
 
 
 class RNNTDecoding:
@@ -146,8 +206,9 @@ class RNNTDecoding:
         return text.replace("▁", " ").strip() if "▁" in text else text
 
     def rnnt_decoder_predictions_tensor(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor,
-                                        return_hypotheses: bool = False):
-        hyps = self.decoding(encoder_output=encoder_output, encoded_lengths=encoded_lengths)[0]
+                                        return_hypotheses: bool = False, partial_hypotheses=None):
+        hyps = self.decoding(encoder_output=encoder_output, encoded_lengths=encoded_lengths,
+                             partial_hypotheses=partial_hypotheses)[0]
         for h in hyps:
             h.text = self.ids_to_text(h.y_sequence.tolist())
         return hyps

@@ -742,6 +742,98 @@ def tdt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_
     return (tokens, times, out_len, score) + (((h, c),) if with_state else ())
 
 
+class _StreamStateC(C.Structure):   # mi355x_rnnt_stream_state
+    _fields_ = [(n, C.c_void_p) for n in ("h", "c", "last", "score", "frames_done", "skip", "zero_run")]
+
+
+class RNNTStreamState:
+    """decoder state of a batch of streams between two chunks of the resumable greedy search (mi355x_rnnt_stream_state): h, c f32
+    [B, H] (committed LSTM state), last i32 [B] (last emitted label), score f32 [B] (running log-probability), frames_done i32 [B],
+    skip / zero_run i32 [B] (TDT; zeros and unused for RNN-T).  All on the device; every step returns a new object."""
+    __slots__ = ("h", "c", "last", "score", "frames_done", "skip", "zero_run")
+
+    def __init__(self, h, c, last, score, frames_done, skip, zero_run):
+        self.h, self.c, self.last, self.score, self.frames_done, self.skip, self.zero_run = h, c, last, score, frames_done, skip, zero_run
+
+    @classmethod
+    def empty(cls, B, H, device):
+        i32 = lambda: torch.empty(B, dtype=torch.int32, device=device)
+        return cls(torch.empty(B, H, dtype=torch.float32, device=device), torch.empty(B, H, dtype=torch.float32, device=device),
+                   i32(), torch.empty(B, dtype=torch.float32, device=device), i32(), i32(), i32())
+
+    @classmethod
+    def fresh(cls, B, H, blank, device):
+        """the state of B streams that have seen nothing (what a null state_in means to the kernel)"""
+        z = lambda: torch.zeros(B, dtype=torch.int32, device=device)
+        return cls(torch.zeros(B, H, dtype=torch.float32, device=device), torch.zeros(B, H, dtype=torch.float32, device=device),
+                   torch.full((B,), int(blank), dtype=torch.int32, device=device), torch.zeros(B, dtype=torch.float32, device=device),
+                   z(), z(), z())
+
+    def tensors(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def select(self, b):
+        """the state of stream b as a batch of one (views)"""
+        return RNNTStreamState(*(t[b:b + 1] for t in self.tensors()))
+
+    @classmethod
+    def stack(cls, states):
+        return cls(*(torch.cat(ts, dim=0).contiguous() for ts in zip(*(s.tensors() for s in states))))
+
+    def _c(self, B, H):
+        want = ((B, H), (B, H), (B,), (B,), (B,), (B,), (B,))
+        dts = (torch.float32, torch.float32, torch.int32, torch.float32, torch.int32, torch.int32, torch.int32)
+        for n, t, shp, d in zip(self.__slots__, self.tensors(), want, dts):
+            if tuple(t.shape) != shp or t.dtype != d or not t.is_contiguous():
+                raise ValueError(f"stream state `{n}`: expected contiguous {d} {shp}, got {t.dtype} {tuple(t.shape)}")
+        return _StreamStateC(*(_ptr(t) for t in self.tensors()))
+
+
+def _greedy_decode_stream(tdt, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                          b_out, blank, durations, max_symbols, state, max_out):
+    B, T, J = enc_proj.shape
+    V1, H = emb.shape
+    if max_out is None:
+        max_out = T * max_symbols if max_symbols > 0 else 4 * T
+    dev = enc_proj.device
+    tokens = torch.empty(B, max_out, dtype=torch.int32, device=dev)
+    times = torch.empty(B, max_out, dtype=torch.int32, device=dev)
+    out_len = torch.empty(B, dtype=torch.int32, device=dev)
+    nxt = RNNTStreamState.empty(B, H, dev)
+    if not tdt:   # (not written by the RNN-T search)
+        nxt.skip.zero_(); nxt.zero_run.zero_()
+    s_in = state._c(B, H) if state is not None else None
+    s_out = nxt._c(B, H)
+    head = (_ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih, _ptr(w_hh), ld_hh,
+            _ptr(b_ih), _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out), ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1)
+    tail = (blank, max_symbols, _ptr(tokens), _ptr(times), _ptr(out_len), max_out, C.byref(s_in) if s_in is not None else None,
+            C.byref(s_out), _stream())
+    if tdt:
+        D, dur = _tdt_durations(durations)
+        check(lib.mi355x_tdt_greedy_decode_stream(*head, D, dur, *tail), "tdt_greedy_decode_stream")
+    else:
+        check(lib.mi355x_rnnt_greedy_decode_stream(*head, *tail), "rnnt_greedy_decode_stream")
+    return tokens, times, out_len, nxt
+
+
+def rnnt_greedy_decode_stream(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                              b_out, blank, max_symbols, state=None, max_out=None):
+    """one chunk of the resumable greedy transducer search (mi355x_rnnt_greedy_decode_stream): rnnt_greedy_decode's arguments, with
+    enc_len = the frames of this chunk per stream, and `state` = the RNNTStreamState the previous chunk returned (None: fresh
+    streams).  -> (tokens, global frame indices, lengths of THIS chunk's labels, the next RNNTStreamState; its `score` is the
+    stream's running score).  Any cut of a stream into chunks gives bit-identical results to one launch over all of it."""
+    return _greedy_decode_stream(False, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
+                                 ld_out, b_out, blank, None, max_symbols, state, max_out)
+
+
+def tdt_greedy_decode_stream(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                             b_out, blank, durations, max_symbols, state=None, max_out=None):
+    """one chunk of the resumable greedy TDT search (mi355x_tdt_greedy_decode_stream): as rnnt_greedy_decode_stream; a duration
+    that jumps past the chunk's end is carried in the state (`skip`) and taken off the next chunk(s)"""
+    return _greedy_decode_stream(True, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
+                                 ld_out, b_out, blank, durations, max_symbols, state, max_out)
+
+
 def row_scale(x, vec, rows, cols):
     check(lib.mi355x_row_scale(_ptr(x), _ptr(vec), rows, cols, _stream()), "row_scale")
 

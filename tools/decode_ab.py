@@ -1,0 +1,74 @@
+"""Time the one-shot greedy search entry points (mi355x_rnnt_greedy_decode, mi355x_tdt_greedy_decode) of ONE library build, chosen
+per process through MI355X_ASR_LIB (default: the in-tree library; `tools/ab_build.py` builds variants).  Loads the library with
+ctypes directly, so a build that lacks newer symbols can be timed too.  B = 32, T = 250, H = J = 640, V1 = 1025, bf16 weights,
+seeded random weights and projection (the same work in every process).  Prints one JSON line; alternate processes of the
+builds to compare inside one GPU session, and a build against itself for the spread.
+
+    MI355X_ASR_LIB=nemo_amd/lib_ab/libmi355x_asr_parent.so python tools/decode_ab.py [--iters 20] [--warmup 3]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+vp, i32, i64 = C.c_void_p, C.c_int, C.c_longlong
+HEAD = [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32, i32]
+TAIL = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+    path = os.environ.get("MI355X_ASR_LIB", os.path.join(ROOT, "nemo_amd", "lib", "libmi355x_asr.so"))
+    lib = C.CDLL(path)
+    lib.mi355x_rnnt_greedy_decode.argtypes = HEAD + TAIL
+    lib.mi355x_tdt_greedy_decode.argtypes = HEAD + [i32, vp] + TAIL
+    dev = "cuda"
+    B, T, H, J, V1, D, ms = 32, 250, 640, 640, 1025, 5, 10
+    g = torch.Generator(device=dev).manual_seed(0)
+    r = lambda *s, k=1.0: torch.randn(*s, device=dev, generator=g) * k   # noqa: E731
+    f = r(B, T, J, k=1.5).to(torch.bfloat16)
+    lens = torch.full((B,), T, dtype=torch.int64, device=dev)
+    emb = r(V1, H)
+    emb[V1 - 1] = 0.0
+    bf = lambda t: t.to(torch.bfloat16).contiguous()   # noqa: E731
+    w_ih, w_hh, w_pred = bf(r(4 * H, H, k=0.15)), bf(r(4 * H, H, k=0.15)), bf(r(J, H, k=0.15))
+    b_ih, b_hh, b_pred = r(4 * H, k=0.1), r(4 * H, k=0.1), r(J, k=0.1)
+    w_out, b_out = bf(r(V1 + D, J, k=0.15)), r(V1 + D, k=0.1)
+    b_out[V1 - 1] += 2.0
+    max_out = T * ms
+    tokens = torch.empty(B, max_out, dtype=torch.int32, device=dev)
+    times = torch.empty_like(tokens)
+    out_len = torch.empty(B, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    p = lambda t: t.data_ptr()   # noqa: E731
+    head = (p(f), 1, J, p(lens), p(emb), p(w_ih), H, p(w_hh), H, p(b_ih), p(b_hh), p(w_pred), H, p(b_pred), p(w_out), J, p(b_out), 1,
+            B, T, J, H, V1)
+    tail = (V1 - 1, ms, p(tokens), p(times), p(out_len), p(score), max_out, None, None, torch.cuda.current_stream().cuda_stream)
+    dur = (C.c_int * D)(0, 1, 2, 3, 4)
+    calls = {"rnnt": lambda: lib.mi355x_rnnt_greedy_decode(*head, *tail),
+             "tdt": lambda: lib.mi355x_tdt_greedy_decode(*head, D, dur, *tail)}
+    row = {"lib": os.path.basename(path)}
+    for name, fn in calls.items():
+        for _ in range(args.warmup):
+            assert fn() == 0
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        row[name + "_ms"] = round(e0.elapsed_time(e1) / args.iters, 4)
+        row[name + "_labels"] = int(out_len.sum())
+        row[name + "_checksum"] = int(tokens.clamp(min=0).sum())
+    print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -5,7 +5,15 @@ with 256 channels, LayerNorm conv module, [70, 13]: 112 mel frames = 1.12 s of a
   * real-time factor = step time / 1.12 s,
   * the time to stream 20 s of audio chunk by chunk against one offline eval forward of the same audio.
 
-    python tools/stream_bench.py [--batch 1 16 64] [--steps 50] [--warmup 10] [--layers 17] [--json OUT]
+`--decoder {none,ctc,rnnt,tdt}` adds the head's step behind the encoder step and reports it separately (`head_ms_per_step`,
+`head_launches`): ctc = ConvASRDecoder + per-frame arg-max; rnnt / tdt = the encoder projection GEMM + the resumable greedy search
+(mi355x_rnnt_greedy_decode_stream / mi355x_tdt_greedy_decode_stream) from a carried decoder state, at the recipe's transducer
+geometry (prediction hidden 640, joint hidden 640, vocabulary 1024, max_symbols 10), bf16 weight images.  For the transducer
+heads the same 14 frames are also decoded as 14 one-frame chunks (`head_ms_14x1`): everything paid per chunk -- the projection
+GEMM, the other launches and the prediction step the kernel reruns at entry -- is in that figure 14 times instead of once, so the
+difference bounds the cost of the rerun from above; it does not isolate it.
+
+    python tools/stream_bench.py [--batch 1 16 64] [--steps 50] [--warmup 10] [--layers 17] [--decoder none] [--json OUT]
 """
 import argparse
 import json
@@ -31,6 +39,62 @@ def build(n_layers):
     return enc
 
 
+def build_head(kind, d_model=512):
+    """-> step(encoded [B, D, T], encoded_len) for the head `kind`, weights random (the step's cost does not depend on them much:
+    the transducer search emits what a random joint emits, bounded by max_symbols = 10 per frame)"""
+    from nemo_amd.modules import ConvASRDecoder, GreedyBatchedRNNTInfer, GreedyBatchedTDTInfer, RNNTDecoder, RNNTJoint
+    torch.manual_seed(1)
+    V = 1024
+    if kind == "ctc":
+        dec = ConvASRDecoder(feat_in=d_model, num_classes=V, compute_dtype=torch.bfloat16).to(dev).eval()
+        return lambda enc, n, state=None: (dec(encoder_output=enc).argmax(-1), None)
+    durations = [0, 1, 2, 3, 4]
+    pred = RNNTDecoder(prednet={"pred_hidden": 640, "pred_rnn_layers": 1, "dropout": 0.0}, vocab_size=V, compute_dtype=torch.bfloat16)
+    joint = RNNTJoint(jointnet={"encoder_hidden": d_model, "pred_hidden": 640, "joint_hidden": 640, "activation": "relu", "dropout": 0.0},
+                      num_classes=V, num_extra_outputs=len(durations) if kind == "tdt" else 0, compute_dtype=torch.bfloat16)
+    with torch.no_grad():
+        joint.joint_net[-1].bias[V] += 2.0   # (a blank now and then, as a trained model has)
+    pred, joint = pred.to(dev).eval(), joint.to(dev).eval()
+    infer = (GreedyBatchedTDTInfer(pred, joint, V, durations, max_symbols_per_step=10) if kind == "tdt"
+             else GreedyBatchedRNNTInfer(pred, joint, V, max_symbols_per_step=10))
+
+    def step(enc, n, state=None):
+        tokens, times, out_len, nxt = infer.decode_ids_stream(enc, n, state)
+        return tokens, nxt
+    return step
+
+
+def head_setting(head, kind, B, enc_out, enc_len, steps, warmup):
+    """the head's step on one encoder chunk output (device time, launches), and for transducers the same frames as one-frame chunks"""
+    from torch.profiler import ProfilerActivity, profile
+    with torch.no_grad():
+        _, state = head(enc_out, enc_len)
+        fn = lambda: head(enc_out, enc_len, state)   # noqa: E731
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        ms = timed(fn, steps)
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        launches = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+        row = dict(head_ms_per_step=round(ms, 3), head_launches=launches)
+        if kind in ("rnnt", "tdt"):
+            T = enc_out.shape[2]
+            frames = [enc_out[:, :, t:t + 1].contiguous() for t in range(T)]
+            one = torch.ones_like(enc_len)
+
+            def by_frame():
+                st = state
+                for f in frames:
+                    _, st = head(f, one, st)
+            by_frame()
+            torch.cuda.synchronize()
+            row["head_ms_14x1"] = round(timed(by_frame, max(2, steps // 5)), 3)
+            row["chunk_frames"] = T
+    return row
+
+
 def timed(fn, n):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -41,7 +105,7 @@ def timed(fn, n):
     return e0.elapsed_time(e1) / n
 
 
-def one_setting(enc, B, steps, warmup):
+def one_setting(enc, B, steps, warmup, head=None, kind="none"):
     from torch.profiler import ProfilerActivity, profile
     from nemo_amd.streaming import CacheAwareStreamingAudioBuffer
     cfg = enc.streaming_cfg
@@ -61,6 +125,10 @@ def one_setting(enc, B, steps, warmup):
         step()
     torch.cuda.synchronize()
     ms = timed(step, steps)
+    head_row = {}
+    if head is not None:
+        res = step()
+        head_row = head_setting(head, kind, B, res[0].detach(), res[1].detach(), steps, warmup)
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
         step()
         torch.cuda.synchronize()
@@ -85,8 +153,12 @@ def one_setting(enc, B, steps, warmup):
     torch.cuda.synchronize()
     ms_stream = timed(stream_all, 2)
     ms_off = timed(offline, 3)
-    return dict(batch=B, ms_per_step=round(ms, 3), launches_per_step=launches, rtf=round(ms / 1120.0, 5),
-                stream_20s_ms=round(ms_stream, 2), offline_20s_ms=round(ms_off, 2))
+    row = dict(batch=B, ms_per_step=round(ms, 3), launches_per_step=launches, rtf=round(ms / 1120.0, 5),
+               stream_20s_ms=round(ms_stream, 2), offline_20s_ms=round(ms_off, 2))
+    if head_row:
+        row.update(decoder=kind, **head_row)
+        row["rtf_with_head"] = round((ms + head_row["head_ms_per_step"]) / 1120.0, 5)
+    return row
 
 
 def main():
@@ -95,12 +167,14 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--layers", type=int, default=17)
+    ap.add_argument("--decoder", choices=["none", "ctc", "rnnt", "tdt"], default="none")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     enc = build(args.layers)
+    head = build_head(args.decoder) if args.decoder != "none" else None
     rows = []
     for B in args.batch:
-        r = one_setting(enc, B, args.steps, args.warmup)
+        r = one_setting(enc, B, args.steps, args.warmup, head, args.decoder)
         rows.append(r)
         print(json.dumps(r), flush=True)
     if args.json:

@@ -565,6 +565,32 @@ void mi355x_mailbox_destroy(mi355x_mailbox* mb);
  * score f32 [B] = sum of the arg-max log-probs of the non-blank frames. */
 int mi355x_ctc_greedy_decode(const void* logp, const void* lens, void* tokens, void* out_len, void* score, int B, int T, int C,
                              int blank, void* stream);
+/* same, and the frames behind every kept token: tok_start / tok_end i32 [B,T] (-1 padded) = the first / last frame of the run of
+ * equal arg-max labels that produced the token (the char offsets of AbstractCTCDecoding._compute_offsets, ctc_decoding.py).
+ * tokens, out_len and score are bit-identical to mi355x_ctc_greedy_decode's.  blank in [0, C). */
+int mi355x_ctc_greedy_decode_ts(const void* logp, const void* lens, void* tokens, void* out_len, void* score, void* tok_start,
+                                void* tok_end, int B, int T, int C, int blank, void* stream);
+
+/* CTC forced alignment: the Viterbi pass of the reference's forced aligner (tools/nemo_forced_aligner/utils/viterbi_decoding.py),
+ * one launch per batch -- forward walk, backtrace and expansion.  logp f32 [B,Tmax,C] (-inf entries allowed); targets i64 [B,Umax];
+ * in_len, tgt_len i64 [B].  States = the blank-extended sequence, S = 2U+1:
+ *   v[0][0] = e(0,0), v[0][1] = e(0,1);  v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if allowed) + e(t,s)
+ * (skip only into a label state whose label differs from the one two states back), plain float32 natural-log arithmetic, so score
+ * and path are bit-equal to a float32 restatement.  Ties: the first maximum in the order (stay, s-1, s-2); at the last frame state
+ * S-1 unless v[S-2] > v[S-1].
+ *   path      i32 [B,Tmax]  state index 0..2U for t < T, -1 beyond
+ *   tok_start i32 [B,Umax]  first / last frame spent in state 2u+1; -1 for u >= U
+ *   tok_end   i32 [B,Umax]
+ *   score     f32 [B]       log-probability of the best path; -inf = infeasible (T < U + adjacent repeats, T <= 0 < U, or -inf
+ *                           emissions on every path): path, tok_start, tok_end are then all -1.  T = 0 and U = 0: score 0.
+ *   bp_ws     backpointer workspace, 8-byte aligned, B * Tmax * ((Umax + 8) & ~7) bytes: one byte per (blank, label) pair g and
+ *             frame, bits 0-1 = predecessor choice of state 2g, bits 2-3 = of state 2g+1 (0 stay, 1 s-1, 2 s-2), rows padded to 8
+ * 1 <= Umax <= 2048 (S <= 4097); MI_ERR_ARG otherwise, and for null pointers, non-positive sizes, blank outside [0, C). */
+int mi355x_ctc_align(const void* logp, const void* targets, const void* in_len, const void* tgt_len, void* bp_ws, void* path,
+                     void* tok_start, void* tok_end, void* score, int B, int Tmax, int C, int Umax, int blank, void* stream);
+/* forward walk of mi355x_ctc_align: 1 (default; MI355X_CTC_ALIGN_WAVE) = lattice row resident in the registers of one wave where
+ * 2*Umax+1 <= 1024, 0 = the LDS / barrier form for every size.  Returns the previous setting (-1: not yet resolved). */
+int mi355x_ctc_align_config(int wave);
 
 /* SpectrogramAugmentation (nemo/collections/asr/modules/audio_preprocessing.py:443-553; SpecAugment._apply_masks
  * parts/submodules/spectr_augment.py:153-215, SpecCutout.forward :245-261): x[b, f0:f1, t0:t1] = value for n rectangles

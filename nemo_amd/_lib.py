@@ -120,6 +120,8 @@ SIGNATURES = {
     "mi355x_qbias": [vp, i64, vp, vp, vp, vp, i32, i64, i32, vp],
     "mi355x_add2": [vp, vp, i32, vp, i32, i64, i64, i32, vp],
     "mi355x_ctc_greedy_decode": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "mi355x_ctc_greedy_decode_ts": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "mi355x_ctc_align": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi355x_fill_rects": [vp, vp, i32, i32, i32, i32, f32, vp],
     "mi355x_specaug_rects": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp],
     "mi355x_add2_colsum": [vp, vp, vp, i64, i64, i32, vp, vp, i64, vp],
@@ -165,6 +167,7 @@ SIGNATURES = {
                                   i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp],
     "mi355x_dwconv_config": [i32],
     "mi355x_ctc_config": [i32],
+    "mi355x_ctc_align_config": [i32],
     "mi355x_logmel_config": [i32],
     "mi355x_stream_create": [i32, vp],
     "mi355x_stream_destroy": [vp],

@@ -442,3 +442,430 @@ extern "C" int mi355x_ctc_greedy_decode(const void* logp, const void* lens, void
   return mi_check_launch();
 }
 
+// mi355x_ctc_greedy_decode_ts: the kernel above, and the first and the last frame of the run of equal arg-max labels behind every kept
+// token.  Its own kernel, so that the one above stays as it is.  A run starts at the frame the compaction keeps; it ends at the frame
+// in front of the next frame whose label differs (or at the last valid frame), and the token it belongs to is the latest keep at or
+// before that frame -- the same ballot with an inclusive prefix, so runs that cross a 64-frame group need nothing more.
+__global__ __launch_bounds__(256) void ctc_greedy_ts_kernel(const float* __restrict__ logp, const long long* __restrict__ lens,
+                                                            int* __restrict__ tokens, int* __restrict__ out_len,
+                                                            float* __restrict__ score, int* __restrict__ tok_start,
+                                                            int* __restrict__ tok_end, int Tmax, int C, int blank) {
+  extern __shared__ int s_lab[];  // [Tmax] labels ; then [Tmax] log-probs (as float)
+  float* s_lp = reinterpret_cast<float*>(s_lab + Tmax);
+  const int b = blockIdx.x;
+  const int T = (int)min((long long)Tmax, lens ? lens[b] : (long long)Tmax);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* lp = logp + (long long)b * Tmax * C;
+  for (int t = wave; t < T; t += 4) {
+    float best = -INFINITY; int arg = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+      const float v = lp[(long long)t * C + c];
+      if (v > best) { best = v; arg = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o, 64); const int oa = __shfl_xor(arg, o, 64);
+      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+    if (lane == 0) { s_lab[t] = arg; s_lp[t] = best; }
+  }
+  __syncthreads();
+  int* tok = tokens + (long long)b * Tmax;
+  int* ts = tok_start + (long long)b * Tmax;
+  int* te = tok_end + (long long)b * Tmax;
+  if (wave == 0) {
+    int base = 0; float sc = 0.f;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+      const int t = t0 + lane;
+      const int cur = t < T ? s_lab[t] : blank;
+      const int prev = (t > 0 && t < T) ? s_lab[t - 1] : blank;
+      const bool nonblank = t < T && cur != blank;
+      const bool keep = nonblank && cur != prev;
+      if (nonblank) sc += s_lp[t];
+      const unsigned long long m = __ballot(keep);
+      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+      if (keep) { tok[pos] = cur; ts[pos] = t; }
+      if (nonblank && (t + 1 >= T || s_lab[t + 1] != cur))   // (2 << 63 wraps to 0: the mask of lane 63 is all ones)
+        te[base + __popcll(m & ((2ull << lane) - 1ull)) - 1] = t;
+      base += __popcll(m);
+    }
+    sc = wave_sum(sc);
+    if (lane == 0) { out_len[b] = base; score[b] = sc; }
+    for (int t = base + lane; t < Tmax; t += 64) { tok[t] = -1; ts[t] = -1; te[t] = -1; }  // padding
+  }
+}
+extern "C" int mi355x_ctc_greedy_decode_ts(const void* logp, const void* lens, void* tokens, void* out_len, void* score,
+                                           void* tok_start, void* tok_end, int B, int Tmax, int C, int blank, void* stream) {
+  mi_clear_errors();
+  if (!logp || !tokens || !out_len || !score || !tok_start || !tok_end || B <= 0 || Tmax <= 0 || C <= 0 || blank < 0 || blank >= C)
+    return MI_ERR_ARG;
+  const size_t shm = (size_t)Tmax * 8;
+  if (shm > 64 * 1024) return MI_ERR_ARG;
+  MI_LAUNCH(ctc_greedy_ts_kernel, dim3(B), dim3(256), shm, (hipStream_t)stream, (const float*)logp, (const long long*)lens,
+                     (int*)tokens, (int*)out_len, (float*)score, (int*)tok_start, (int*)tok_end, Tmax, C, blank);
+  return mi_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------ CTC forced alignment
+// Viterbi pass of the reference's forced aligner (tools/nemo_forced_aligner/utils/viterbi_decoding.py: a Python loop over T on
+// [B, S] tensors) as ONE launch per batch: the forward walk over the blank-extended lattice with max instead of log-sum-exp, a 2-bit
+// predecessor choice per state and step, the backtrace and the expansion of the path into first / last frames per token.  Plain
+// float32 in the natural-log domain, one max + one add per state and step: score and path are bit-equal to a float32 restatement.
+//   v[0][0] = e(0,0), v[0][1] = e(0,1);  v[t][s] = max(v[t-1][s], v[t-1][s-1], skip ? v[t-1][s-2] : -inf) + e(t,s)
+//   ties: the first maximum in the order (stay, s-1, s-2); at the last frame state S-1 unless v[S-2] > v[S-1]
+// Backpointers: one byte per (blank, label) pair g and frame, bits 0-1 = choice of state 2g, bits 2-3 = choice of state 2g+1
+// (choice = how many states the predecessor lies below), rows of RS = (Umax + 8) & ~7 bytes: bp_ws is u8 [B, Tmax, RS].
+// A score of -inf (no path through the lattice: too few frames, or -inf emissions on every path) marks the utterance infeasible.
+#ifndef CTC_ALIGN_BACKTRACE   // benchmarks only (tools/align_bench.py): 0 = forward walk alone, 2 = single-lane chase through global memory
+#define CTC_ALIGN_BACKTRACE 1
+#endif
+#define CTC_BT 64      // frames per backtrace chunk
+#define CTC_BT_LD 17   // dwords per row of the chunk's window: the pairs [g - 64, g] from a 4-byte aligned start are <= 68 bytes
+
+// one (blank, label) pair: old values E = v[2g], O = v[2g+1], om1 = v[2g-1] -> the maxima in front of the emission and the choice byte
+__device__ __forceinline__ unsigned ctc_vit_pair(float E, float O, float om1, bool skip, float& mE, float& mO) {
+  unsigned kE = 0, kO = 0;
+  mE = E;
+  if (om1 > mE) { mE = om1; kE = 1; }
+  mO = O;
+  if (E > mO) { mO = E; kO = 1; }
+  if (skip && om1 > mO) { mO = om1; kO = 2; }
+  return kE | (kO << 2);
+}
+
+__device__ __forceinline__ void ctc_align_fill_empty(int* path, int* ts, int* te, int Tmax, int Umax) {
+  for (int t = threadIdx.x; t < Tmax; t += blockDim.x) path[t] = -1;
+  for (int u = threadIdx.x; u < Umax; u += blockDim.x) { ts[u] = -1; te[u] = -1; }
+}
+
+// Backtrace and expansion, by the whole workgroup behind its forward walk.  s_path[CTC_BT] holds the state of frame T-1 (-1:
+// infeasible) and the caller has synchronised.  The state of frame t-k lies within 2k states below the state of frame t, so the
+// backpointers a chunk of CTC_BT frames can touch are a window of <= 65 pairs per row: all threads fetch it into LDS with every load
+// in flight, one lane chases inside LDS (a chase through global memory is one dependent load per frame), then a lane per frame
+// stores the path and, where the state changes between neighbouring frames, the end of one token's run and the start of the next.
+__device__ __forceinline__ void ctc_align_backtrace(const unsigned char* __restrict__ bp, int RS, int T, int U, int Tmax, int Umax,
+                                                    int* __restrict__ path, int* __restrict__ ts, int* __restrict__ te,
+                                                    unsigned* s_bp, int* s_path) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  int s_top = s_path[CTC_BT];
+  if (s_top < 0) {   // (uniform)
+    ctc_align_fill_empty(path, ts, te, Tmax, Umax);
+    return;
+  }
+  for (int t = T + tid; t < Tmax; t += nthr) path[t] = -1;
+  for (int u = U + tid; u < Umax; u += nthr) { ts[u] = -1; te[u] = -1; }
+#if CTC_ALIGN_BACKTRACE == 0
+  return;
+#elif CTC_ALIGN_BACKTRACE == 2
+  if (tid == 0) {
+    int s = s_top;
+    path[T - 1] = s;
+    if (s & 1) te[s >> 1] = T - 1;
+    for (int t = T - 1; t >= 1; --t) {
+      const int n = s - ((bp[(long long)t * RS + (s >> 1)] >> ((s & 1) * 2)) & 3);
+      if (n != s) { if (n & 1) te[n >> 1] = t - 1; if (s & 1) ts[s >> 1] = t; }
+      path[t - 1] = s = n;
+    }
+    if (s & 1) ts[s >> 1] = 0;
+  }
+  return;
+#endif
+  if (tid == 0) {
+    path[T - 1] = s_top;
+    if (s_top & 1) te[s_top >> 1] = T - 1;
+  }
+  for (int t_hi = T - 1; t_hi >= 1;) {
+    const int n = min(CTC_BT, t_hi);   // rows t_hi .. t_hi-n+1 lead to the states of frames t_hi-1 .. t_hi-n
+    const int g_hi = s_top >> 1;
+    const int a_lo = max(0, g_hi - CTC_BT) & ~3;
+    const int ndw = ((g_hi - a_lo) >> 2) + 1;   // <= CTC_BT_LD; the last dword ends inside the row (RS is a multiple of 4)
+    for (int i = tid; i < n * ndw; i += nthr) {
+      const int k = i / ndw, j = i - k * ndw;
+      s_bp[k * CTC_BT_LD + j] = *reinterpret_cast<const unsigned*>(bp + (long long)(t_hi - k) * RS + a_lo + 4 * j);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const unsigned char* w = reinterpret_cast<const unsigned char*>(s_bp);
+      int s = s_top;
+      for (int k = 0; k < n; ++k) {
+        s -= (w[k * (CTC_BT_LD * 4) + (s >> 1) - a_lo] >> ((s & 1) * 2)) & 3;
+        s_path[k] = s;
+      }
+      s_path[CTC_BT] = s;
+    }
+    __syncthreads();
+    for (int k = tid; k < n; k += nthr) {
+      const int cur = s_path[k], next = k ? s_path[k - 1] : s_top, t = t_hi - k - 1;
+      path[t] = cur;
+      if (cur != next) {
+        if (cur & 1) te[cur >> 1] = t;
+        if (next & 1) ts[next >> 1] = t + 1;
+      }
+    }
+    s_top = s_path[CTC_BT];   // (the next chase writes it behind the next barrier)
+    t_hi -= n;
+  }
+  if (tid == 0 && (s_top & 1)) ts[s_top >> 1] = 0;
+}
+
+// Wave-resident form, S <= 128 P: the layout of ctc_wave_walk -- lane l holds the pairs l*P .. l*P+P-1, one shuffle per step, wave 1
+// gathers the next chunk's emissions into the other half of s_e, one barrier per chunk.  A lane stores its P choice bytes per step
+// as one access.  The backtrace reuses s_e.
+template <int P> struct CtcBytes;
+template <> struct CtcBytes<1> { typedef unsigned char t; };
+template <> struct CtcBytes<2> { typedef unsigned short t; };
+template <> struct CtcBytes<4> { typedef unsigned int t; };
+template <> struct CtcBytes<8> { typedef unsigned long long t; };
+template <int P>
+__global__ __launch_bounds__(128) void ctc_align_wave_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
+                                                             const long long* __restrict__ in_len, const long long* __restrict__ tgt_len,
+                                                             unsigned char* __restrict__ bp_ws, int* __restrict__ path_out,
+                                                             int* __restrict__ tok_start, int* __restrict__ tok_end,
+                                                             float* __restrict__ score, int Tmax, int C, int Umax, int RS, int blank) {
+  constexpr int TC = CtcTc<P>::v, LD = 64 * P + 1;
+  static_assert(TC * LD >= CTC_BT * CTC_BT_LD + CTC_BT + 1, "the backtrace buffers live in one half of s_e");
+  __shared__ float s_e[2][TC * LD];
+  const int b = blockIdx.x;
+  const int T = (int)max(0ll, min((long long)Tmax, in_len[b]));
+  const int U = (int)max(0ll, min((long long)Umax, tgt_len[b]));
+  int* path = path_out + (long long)b * Tmax;
+  int* ts = tok_start + (long long)b * Umax;
+  int* te = tok_end + (long long)b * Umax;
+  if (T == 0) {   // no frames: the empty path, feasible only for an empty target
+    ctc_align_fill_empty(path, ts, te, Tmax, Umax);
+    if (threadIdx.x == 0) score[b] = (U == 0) ? 0.f : NEGINF;
+    return;
+  }
+  const float* lp = logp + (long long)b * Tmax * C;
+  const long long* tg = targets + (long long)b * Umax;
+  unsigned char* bp = bp_ws + (long long)b * Tmax * RS;
+  const int lane = threadIdx.x & 63;
+  const bool loader = threadIdx.x >= 64;   // wave-uniform
+  int cls[P];
+  bool vE[P], vO[P], skip[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int g = lane * P + p;
+    vE[p] = g <= U;
+    vO[p] = g < U;
+    cls[p] = vO[p] ? (int)tg[g] : blank;
+    skip[p] = vO[p] && g >= 1 && cls[p] != (int)tg[g - 1];
+  }
+  const int nchunk = (T + TC - 1) / TC;
+  auto gather = [&](int c) {   // loader wave: emissions of steps c*TC .. c*TC+TC-1 -> s_e[c & 1]
+    float* dst = s_e[c & 1];
+    float v[TC][P];
+#pragma unroll
+    for (int i = 0; i < TC; ++i) {
+      int step = c * TC + i;
+      step = step < T ? step : T - 1;   // (steps beyond the utterance re-read its last row: no branch, never used)
+      const float* row = lp + (long long)step * C;
+#pragma unroll
+      for (int p = 0; p < P; ++p) v[i][p] = row[cls[p]];
+    }
+    float vb = 0.f;
+    if (lane < TC) {
+      int step = c * TC + lane;
+      step = step < T ? step : T - 1;
+      vb = lp[(long long)step * C + blank];
+    }
+#pragma unroll
+    for (int i = 0; i < TC; ++i)
+#pragma unroll
+      for (int p = 0; p < P; ++p) dst[i * LD + p * 64 + lane] = v[i][p];
+    if (lane < TC) dst[lane * LD + 64 * P] = vb;
+  };
+  float E[P], O[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) { E[p] = NEGINF; O[p] = NEGINF; }
+  if (loader) gather(0);
+  __syncthreads();
+  for (int c = 0; c < nchunk; ++c) {
+    if (loader) {
+      if (c + 1 < nchunk) gather(c + 1);
+    } else {
+      const float* src = s_e[c & 1];
+      const int nstep = min(TC, T - c * TC);
+      float eb_n = src[64 * P], el_n[P];   // the emissions of step i + 1 are read while step i computes
+#pragma unroll
+      for (int p = 0; p < P; ++p) el_n[p] = src[p * 64 + lane];
+      for (int i = 0; i < nstep; ++i) {
+        const int t = c * TC + i;
+        const float eb = eb_n;
+        float el[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) el[p] = el_n[p];
+        const int i1 = i + 1 < TC ? i + 1 : TC - 1;
+        float x0 = __shfl_up(O[P - 1], 1, 64);   // the neighbouring lane's last label state
+        if (lane == 0) x0 = NEGINF;
+        eb_n = src[i1 * LD + 64 * P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) el_n[p] = src[i1 * LD + p * 64 + lane];
+        float nE[P], nO[P];
+        unsigned long long choice = 0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+          float mE, mO;
+          const unsigned k = ctc_vit_pair(E[p], O[p], (p == 0) ? x0 : O[p == 0 ? 0 : p - 1], skip[p], mE, mO);
+          choice |= (unsigned long long)k << (8 * p);
+          nE[p] = vE[p] ? mE + eb : NEGINF;
+          nO[p] = vO[p] ? mO + el[p] : NEGINF;
+        }
+        if (t == 0) {  // (wave-uniform) states 0 and 1
+#pragma unroll
+          for (int p = 0; p < P; ++p) {
+            const int g = lane * P + p;
+            nE[p] = (g == 0) ? eb : NEGINF;
+            nO[p] = (vO[p] && g == 0) ? el[p] : NEGINF;
+          }
+        }
+#pragma unroll
+        for (int p = 0; p < P; ++p) { E[p] = nE[p]; O[p] = nO[p]; }
+        if (lane * P <= U)   // (row 0 is never read; lane*P + P <= RS: both are multiples of P and lane*P <= Umax < RS)
+          *reinterpret_cast<typename CtcBytes<P>::t*>(bp + (long long)t * RS + lane * P) = (typename CtcBytes<P>::t)choice;
+      }
+    }
+    __syncthreads();   // chunk c + 1 is in LDS; the walker is done with chunk c's half
+  }
+  unsigned* s_bp = reinterpret_cast<unsigned*>(s_e[0]);
+  int* s_path = reinterpret_cast<int*>(s_e[0]) + CTC_BT * CTC_BT_LD;
+  if (!loader) {   // the last row: states S-1 = E_U and S-2 = O_{U-1}
+    float eU = NEGINF, oU = NEGINF;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const int g = lane * P + p;
+      if (g == U) eU = E[p];
+      if (g == U - 1) oU = O[p];
+    }
+    const float l1 = __shfl(eU, U / P, 64);
+    const float l2 = (U >= 1) ? __shfl(oU, (U - 1) / P, 64) : NEGINF;
+    if (lane == 0) {
+      const bool lab = l2 > l1;
+      const float sc = lab ? l2 : l1;
+      score[b] = sc;
+      s_path[CTC_BT] = (sc == NEGINF) ? -1 : (lab ? 2 * U - 1 : 2 * U);
+    }
+  }
+  __syncthreads();   // (also: the walker's backpointer stores are visible to the whole workgroup)
+  ctc_align_backtrace(bp, RS, T, U, Tmax, Umax, path, ts, te, s_bp, s_path);
+}
+
+// LDS / barrier form, S <= 4097: the previous row double-buffered in LDS (rows of 2 Umax + 2 floats, so that a pair is one aligned
+// 8-byte read), a thread per pair and 256 pairs per pass, one barrier per step; the emissions of step t + 1 are requested before
+// step t computes.
+#define CTC_ALIGN_NG 9   // pairs per thread: 2049 pairs (U = 2048) over 256 threads
+__host__ __device__ static inline int ctc_align_lds_rows(int Umax) { return (2 * (2 * Umax + 2) + 3) & ~3; }   // floats, a multiple of 16 bytes
+__global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
+                                                        const long long* __restrict__ in_len, const long long* __restrict__ tgt_len,
+                                                        unsigned char* __restrict__ bp_ws, int* __restrict__ path_out,
+                                                        int* __restrict__ tok_start, int* __restrict__ tok_end,
+                                                        float* __restrict__ score, int Tmax, int C, int Umax, int RS, int blank) {
+  // all of the LDS is dynamic (a static array in front would move the base off the 8-byte alignment of the pair reads):
+  // rows [2][2 Umax + 2], then the backtrace window and path
+  extern __shared__ __attribute__((aligned(16))) float rows[];
+  const int Sr = 2 * Umax + 2;
+  unsigned* s_bp = reinterpret_cast<unsigned*>(rows + ctc_align_lds_rows(Umax));
+  int* s_path = reinterpret_cast<int*>(s_bp + CTC_BT * CTC_BT_LD);
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int T = (int)max(0ll, min((long long)Tmax, in_len[b]));
+  const int U = (int)max(0ll, min((long long)Umax, tgt_len[b]));
+  int* path = path_out + (long long)b * Tmax;
+  int* ts = tok_start + (long long)b * Umax;
+  int* te = tok_end + (long long)b * Umax;
+  if (T == 0) {
+    ctc_align_fill_empty(path, ts, te, Tmax, Umax);
+    if (tid == 0) score[b] = (U == 0) ? 0.f : NEGINF;
+    return;
+  }
+  const float* lp = logp + (long long)b * Tmax * C;
+  const long long* tg = targets + (long long)b * Umax;
+  unsigned char* bp = bp_ws + (long long)b * Tmax * RS;
+  int cls[CTC_ALIGN_NG];
+  bool skip[CTC_ALIGN_NG];
+  float el_n[CTC_ALIGN_NG];
+#pragma unroll
+  for (int j = 0; j < CTC_ALIGN_NG; ++j) {
+    const int g = tid + 256 * j;
+    cls[j] = g < U ? (int)tg[g] : blank;
+    skip[j] = g < U && g >= 1 && cls[j] != (int)tg[g - 1];
+    el_n[j] = (256 * j <= U) ? lp[cls[j]] : 0.f;
+  }
+  float eb_n = lp[blank];
+  for (int t = 0; t < T; ++t) {
+    float* cur = rows + (t & 1) * Sr;
+    const float* old = rows + ((t & 1) ^ 1) * Sr;
+    const float eb = eb_n;
+    float el[CTC_ALIGN_NG];
+#pragma unroll
+    for (int j = 0; j < CTC_ALIGN_NG; ++j) el[j] = el_n[j];
+    const float* nrow = lp + (long long)min(t + 1, T - 1) * C;
+    eb_n = nrow[blank];
+#pragma unroll
+    for (int j = 0; j < CTC_ALIGN_NG; ++j)
+      if (256 * j <= U) el_n[j] = nrow[cls[j]];   // (uniform)
+#pragma unroll
+    for (int j = 0; j < CTC_ALIGN_NG; ++j) {
+      const int g = tid + 256 * j;
+      if (g <= U) {
+        float nE, nO;
+        unsigned k = 0;
+        if (t == 0) {
+          nE = (g == 0) ? eb : NEGINF;
+          nO = (g == 0 && U > 0) ? el[j] : NEGINF;
+        } else {
+          const float2 eo = reinterpret_cast<const float2*>(old)[g];
+          float mE, mO;
+          k = ctc_vit_pair(eo.x, eo.y, g ? old[2 * g - 1] : NEGINF, skip[j], mE, mO);
+          nE = mE + eb;
+          nO = (g < U) ? mO + el[j] : NEGINF;
+        }
+        reinterpret_cast<float2*>(cur)[g] = make_float2(nE, nO);
+        bp[(long long)t * RS + g] = (unsigned char)k;
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const float* last = rows + ((T - 1) & 1) * Sr;
+    const float l1 = last[2 * U], l2 = (U >= 1) ? last[2 * U - 1] : NEGINF;
+    const bool lab = l2 > l1;
+    const float sc = lab ? l2 : l1;
+    score[b] = sc;
+    s_path[CTC_BT] = (sc == NEGINF) ? -1 : (lab ? 2 * U - 1 : 2 * U);
+  }
+  __syncthreads();
+  ctc_align_backtrace(bp, RS, T, U, Tmax, Umax, path, ts, te, s_bp, s_path);
+}
+
+// MI355X_CTC_ALIGN_WAVE (mi355x_ctc_align_config): 1 (default) = the wave-resident form where 2 Umax + 1 <= 1024, 0 = the LDS form always
+static int g_ctc_align_wave = -1;
+extern "C" int mi355x_ctc_align_config(int wave) {
+  const int prev = g_ctc_align_wave;
+  g_ctc_align_wave = wave;
+  return prev;
+}
+
+extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const void* in_len, const void* tgt_len, void* bp_ws,
+                                void* path, void* tok_start, void* tok_end, void* score, int B, int Tmax, int C, int Umax,
+                                int blank, void* stream) {
+  mi_clear_errors();
+  if (!logp || !targets || !in_len || !tgt_len || !bp_ws || !path || !tok_start || !tok_end || !score) return MI_ERR_ARG;
+  if (B <= 0 || Tmax <= 0 || C <= 0 || Umax <= 0 || blank < 0 || blank >= C) return MI_ERR_ARG;
+  if (Umax > 2048 || ((size_t)bp_ws & 7)) return MI_ERR_ARG;   // S = 2 Umax + 1 <= 4097 (CTC_ALIGN_NG pairs per thread)
+  const int Smax = 2 * Umax + 1, RS = (Umax + 8) & ~7;
+  if (g_ctc_align_wave < 0) {
+    const char* e = getenv("MI355X_CTC_ALIGN_WAVE");
+    g_ctc_align_wave = (e && e[0] == '0') ? 0 : 1;
+  }
+#define CTC_ALIGN_LAUNCH(kernel, threads, shm)                                                                                      \
+  MI_LAUNCH(kernel, dim3(B), dim3(threads), shm, (hipStream_t)stream, (const float*)logp, (const long long*)targets,                 \
+            (const long long*)in_len, (const long long*)tgt_len, (unsigned char*)bp_ws, (int*)path, (int*)tok_start, (int*)tok_end,  \
+            (float*)score, Tmax, C, Umax, RS, blank)
+  if (g_ctc_align_wave && Smax <= 128) CTC_ALIGN_LAUNCH(ctc_align_wave_kernel<1>, 128, 0);
+  else if (g_ctc_align_wave && Smax <= 256) CTC_ALIGN_LAUNCH(ctc_align_wave_kernel<2>, 128, 0);
+  else if (g_ctc_align_wave && Smax <= 512) CTC_ALIGN_LAUNCH(ctc_align_wave_kernel<4>, 128, 0);
+  else if (g_ctc_align_wave && Smax <= 1024) CTC_ALIGN_LAUNCH(ctc_align_wave_kernel<8>, 128, 0);
+  else CTC_ALIGN_LAUNCH(ctc_align_kernel, 256, sizeof(float) * (size_t)(ctc_align_lds_rows(Umax) + CTC_BT * CTC_BT_LD + CTC_BT + 1));
+#undef CTC_ALIGN_LAUNCH
+  return mi_check_launch();
+}

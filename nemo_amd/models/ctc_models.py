@@ -34,6 +34,112 @@ def _build(section: str, cfg: Dict[str, Any]):
     return Serialization.from_config_dict(cfg)
 
 
+@contextlib.contextmanager
+def _inference_setup(model):
+    """what `transcribe` runs under (ctc_models.py:760-790): eval mode, dither and padding to 16 off; restored on the way out"""
+    was_training = model.training
+    feat = model.preprocessor.featurizer
+    dither, pad_to = feat.dither, feat.pad_to
+    model.eval()
+    feat.dither, feat.pad_to = 0.0, 0
+    try:
+        yield
+    finally:
+        feat.dither, feat.pad_to = dither, pad_to
+        model.train(was_training)
+
+
+def _audio_batch(model, items, channel_selector=None):
+    """paths / 1-D waveforms -> (zero-padded signal [n, max] and lengths [n] on the model's device)"""
+    from ..data import load_audio
+    sr = model._cfg.get("sample_rate", 16000)
+    device = next(model.parameters()).device
+    waves = []
+    for a in items:
+        if isinstance(a, str):
+            a = load_audio(a, sr, channel_selector=channel_selector)
+        waves.append(torch.as_tensor(a, dtype=torch.float32).reshape(-1))
+    lens = torch.tensor([w.numel() for w in waves], dtype=torch.int64)
+    sig = torch.zeros(len(waves), int(lens.max()), dtype=torch.float32)
+    for r, w in enumerate(waves):
+        sig[r, : w.numel()] = w
+    return sig.to(device), lens.to(device)
+
+
+def _as_list(audio):
+    return [audio] if isinstance(audio, (str, bytes)) or not hasattr(audio, "__len__") else audio
+
+
+def _with_seconds(offsets, stride):
+    return [dict(o, start=o["start_offset"] * stride, end=o["end_offset"] * stride) for o in offsets]
+
+
+def frame_stride_s(model) -> float:
+    """seconds of audio per encoder frame: the preprocessor's window stride times the encoder's sub-sampling factor"""
+    pre = model.preprocessor
+    return pre.hop_length / float(pre._sample_rate) * int(model.encoder.subsampling_factor)
+
+
+def ctc_transcribe_timestamps(model, audio, batch_size=4, channel_selector=None):
+    """`transcribe(timestamps=True)` over a CTC head: greedy decoding that keeps the frames (`mi355x_ctc_greedy_decode_ts`), offsets
+    built on the host from the folded ids.  `model` provides `_ctc_log_probs(signal, lengths)` and `_ctc_decoding()`.
+    -> one Hypothesis per input, in input order: text, y_sequence, score, timestamp = {'timestep': start frames, 'char', 'word'}
+    (offsets in frames as in the reference -- end exclusive -- plus `start` / `end` in seconds)."""
+    from ..modules.rnnt_decoding import Hypothesis
+    decoding = model._ctc_decoding()
+    if decoding is None:
+        raise RuntimeError("transcribe() needs a vocabulary (decoder.vocabulary or a tokenizer)")
+    audio, stride, out = _as_list(audio), frame_stride_s(model), []
+    with _inference_setup(model):
+        for i in range(0, len(audio), batch_size):
+            sig, lens = _audio_batch(model, audio[i:i + batch_size], channel_selector)
+            log_probs, enc_len = model._ctc_log_probs(sig, lens)
+            tokens, out_len, score, start, end = (t.cpu() for t in decoding.decode_ids(log_probs, enc_len, return_timestamps=True))
+            for r in range(tokens.shape[0]):
+                n = int(out_len[r])
+                ids, st, en = tokens[r, :n].tolist(), start[r, :n].tolist(), end[r, :n].tolist()
+                char, word = decoding.offsets(ids, st, en)
+                out.append(Hypothesis(score=float(score[r]), y_sequence=tokens[r, :n].to(torch.long), text=decoding.ids_to_text(ids),
+                                      timestamp={"timestep": st, "char": _with_seconds(char, stride),
+                                                 "word": _with_seconds(word, stride)}, length=int(enc_len[r])))
+    return out
+
+
+def ctc_align_audio(model, audio, texts, batch_size=4, channel_selector=None):
+    """`align` over a CTC head: one transcript per input -> ids (`model._text_to_ids`), Viterbi forced alignment on the device
+    (`mi355x_ctc_align`; only [B, U] integers and the scores come back).  -> one dict per input, in input order:
+    {'score': log-probability of the best path, 'feasible', 'text', 'tokens': [{char, start_offset, end_offset, start, end}],
+    'words': [{word, ...}]} (offsets in frames, end exclusive; start / end in seconds).  A pair that cannot be aligned (more labels
+    than frames, or no path of finite probability) has feasible = False, score -inf and no segments."""
+    from ..modules import CTCAligner
+    decoding = model._ctc_decoding()
+    if decoding is None:
+        raise RuntimeError("align() needs a vocabulary (decoder.vocabulary or a tokenizer)")
+    audio = _as_list(audio)
+    texts = [texts] if isinstance(texts, str) else list(texts)
+    if len(texts) != len(audio):
+        raise ValueError(f"align() takes one transcript per input: {len(audio)} inputs, {len(texts)} transcripts")
+    aligner = CTCAligner(blank_id=decoding.blank_id)
+    stride, out = frame_stride_s(model), []
+    with _inference_setup(model):
+        for i in range(0, len(audio), batch_size):
+            sig, lens = _audio_batch(model, audio[i:i + batch_size], channel_selector)
+            ids = [list(model._text_to_ids(t)) for t in texts[i:i + batch_size]]
+            tl = torch.tensor([len(x) for x in ids], dtype=torch.int64)
+            tg = torch.zeros(len(ids), max(1, int(tl.max())), dtype=torch.int64)
+            for r, x in enumerate(ids):
+                tg[r, : len(x)] = torch.tensor(x, dtype=torch.int64)
+            log_probs, enc_len = model._ctc_log_probs(sig, lens)
+            _, start, end, score = (t.cpu() for t in aligner(log_probs, enc_len, tg.to(sig.device), tl.to(sig.device)))
+            for r, x in enumerate(ids):
+                feasible = bool(torch.isfinite(score[r]))
+                n = len(x) if feasible else 0
+                char, word = decoding.offsets(x[:n], start[r, :n].tolist(), end[r, :n].tolist())
+                out.append({"score": float(score[r]), "feasible": feasible, "text": texts[i + r],
+                            "tokens": _with_seconds(char, stride), "words": _with_seconds(word, stride)})
+    return out
+
+
 class EncDecCTCModel(nn.Module):
     def __init__(self, cfg: Dict[str, Any], trainer=None):
         super().__init__()
@@ -261,46 +367,54 @@ class EncDecCTCModel(nn.Module):
 
     @torch.no_grad()
     def transcribe(self, audio, batch_size: int = 4, return_hypotheses: bool = False, num_workers: int = 0,
-                   channel_selector=None, verbose: bool = False):
+                   channel_selector=None, verbose: bool = False, timestamps: bool = False):
         """`ASRTranscriptionMixin.transcribe` (parts/mixins/transcription.py:184-290) for the greedy CTC path: `audio` is a
         path, a list of paths, or a list of 1-D waveforms (numpy / torch, at the model's sample rate); returns one string
         per input (or (text, token ids, score) triples with return_hypotheses).  Eval mode, dither and padding to 16 off
-        (ctc_models.py:760-790), inputs sorted nowhere: the order of the outputs is the order of the inputs."""
-        from ..data import load_audio
+        (ctc_models.py:760-790), inputs sorted nowhere: the order of the outputs is the order of the inputs.
+        timestamps=True: Hypothesis objects with char / word offsets instead (`ctc_transcribe_timestamps`)."""
+        if timestamps:
+            return ctc_transcribe_timestamps(self, audio, batch_size, channel_selector)
         if self.wer is None:
             raise RuntimeError("transcribe() needs a vocabulary (decoder.vocabulary or a tokenizer)")
-        if isinstance(audio, (str, bytes)) or not hasattr(audio, "__len__"):
-            audio = [audio]
-        sr = self._cfg.get("sample_rate", 16000)
-        device = next(self.parameters()).device
-        was_training = self.training
-        feat = self.preprocessor.featurizer
-        dither, pad_to = feat.dither, feat.pad_to
-        self.eval()
-        feat.dither, feat.pad_to = 0.0, 0
-        out = []
-        try:
+        audio, out = _as_list(audio), []
+        with _inference_setup(self):
             for i in range(0, len(audio), batch_size):
-                waves = []
-                for a in audio[i:i + batch_size]:
-                    if isinstance(a, str):
-                        a = load_audio(a, sr, channel_selector=channel_selector)
-                    waves.append(torch.as_tensor(a, dtype=torch.float32).reshape(-1))
-                lens = torch.tensor([w.numel() for w in waves], dtype=torch.int64)
-                sig = torch.zeros(len(waves), int(lens.max()), dtype=torch.float32)
-                for r, w in enumerate(waves):
-                    sig[r, : w.numel()] = w
-                log_probs, enc_len, _ = self.forward(input_signal=sig.to(device), input_signal_length=lens.to(device))
+                sig, lens = _audio_batch(self, audio[i:i + batch_size], channel_selector)
+                log_probs, enc_len, _ = self.forward(input_signal=sig, input_signal_length=lens)
                 tokens, out_len, score = self.wer.decoding.decode_ids(log_probs, enc_len)
                 tokens, out_len, score = tokens.cpu(), out_len.cpu(), score.cpu()
-                for r in range(len(waves)):
+                for r in range(tokens.shape[0]):
                     ids = tokens[r, : int(out_len[r])].tolist()
                     text = self.wer.decoding.ids_to_text(ids)
                     out.append((text, ids, float(score[r])) if return_hypotheses else text)
-        finally:
-            feat.dither, feat.pad_to = dither, pad_to
-            self.train(was_training)
         return out
+
+    # ------------------------------------------------------------------ timestamps and forced alignment
+    @property
+    def frame_stride_s(self) -> float:
+        return frame_stride_s(self)
+
+    def _ctc_log_probs(self, signal, lengths):
+        log_probs, enc_len, _ = self.forward(input_signal=signal, input_signal_length=lengths)
+        return log_probs, enc_len
+
+    def _ctc_decoding(self):
+        return self.wer.decoding if self.wer is not None else None
+
+    def _text_to_ids(self, text: str):
+        """the ids the data set would train on: the tokenizer's, or the 'base' character parser over the decoder's vocabulary
+        (characters outside it are dropped)"""
+        tok = getattr(self, "tokenizer", None)
+        if tok is not None:
+            return tok.text_to_ids(text)
+        from ..data.text import make_parser
+        return make_parser(labels=list(self.decoder.vocabulary), do_normalize=False)(text)
+
+    @torch.no_grad()
+    def align(self, audio, texts, batch_size: int = 4, channel_selector=None):
+        """forced alignment of one transcript per input (the same audio inputs as `transcribe`): see `ctc_align_audio`"""
+        return ctc_align_audio(self, audio, texts, batch_size, channel_selector)
 
     # ------------------------------------------------------------------ cache-aware streaming (asr_model.py ASRModuleMixin)
     @torch.no_grad()

@@ -15,6 +15,7 @@ import torch
 
 from ..modules import CTCLoss
 from .ctc_models import _build as _build_ctc
+from .ctc_models import ctc_align_audio, ctc_transcribe_timestamps, frame_stride_s
 from .rnnt_models import EncDecRNNTModel, fastconformer_tdt_config, fastconformer_transducer_config, rnnt_conformer_stream_step
 
 _GREEDY = ("greedy", "greedy_batch")
@@ -138,6 +139,40 @@ class EncDecHybridRNNTCTCModel(EncDecRNNTModel):
         if self.cur_decoder == "ctc":
             return _CTCHeadText(self) if self.ctc_decoding is not None else None
         return self.decoding
+
+    # ------------------------------------------------------------------ timestamps and forced alignment over the CTC head
+    @property
+    def frame_stride_s(self) -> float:
+        return frame_stride_s(self)
+
+    def _ctc_log_probs(self, signal, lengths):
+        encoded, enc_len = self.forward(input_signal=signal, input_signal_length=lengths)
+        return self.ctc_decoder(encoder_output=encoded), enc_len
+
+    def _ctc_decoding(self):
+        return self.ctc_decoding
+
+    def _text_to_ids(self, text: str):
+        if self.tokenizer is not None:
+            return self.tokenizer.text_to_ids(text)
+        from ..data.text import make_parser
+        return make_parser(labels=list(self.ctc_decoder.vocabulary), do_normalize=False)(text)
+
+    @torch.no_grad()
+    def transcribe(self, audio, batch_size: int = 4, return_hypotheses: bool = False, num_workers: int = 0,
+                   channel_selector=None, verbose: bool = False, timestamps: bool = False):
+        """EncDecRNNTModel.transcribe; timestamps=True (CTC head selected) returns Hypothesis objects with char / word offsets
+        (ctc_models.ctc_transcribe_timestamps).  The transducer head's hypotheses already carry `timestamp` with return_hypotheses."""
+        if not timestamps:
+            return super().transcribe(audio, batch_size, return_hypotheses, num_workers, channel_selector, verbose)
+        if self.cur_decoder != "ctc":
+            raise NotImplementedError("transcribe(timestamps=True) runs over the CTC head: change_decoding_strategy(decoder_type='ctc')")
+        return ctc_transcribe_timestamps(self, audio, batch_size, channel_selector)
+
+    @torch.no_grad()
+    def align(self, audio, texts, batch_size: int = 4, channel_selector=None):
+        """forced alignment over the auxiliary CTC head, whichever head `cur_decoder` names (ctc_models.ctc_align_audio)"""
+        return ctc_align_audio(self, audio, texts, batch_size, channel_selector)
 
     # ------------------------------------------------------------------ both heads in one step (hybrid_rnnt_ctc_models.py:420-520)
     def _loss_and_wer(self, encoded, encoded_len, decoder, target_length, transcript, transcript_len, compute_wer):

@@ -4,7 +4,7 @@ from .conformer_encoder import ConformerEncoder  # noqa: F401
 from .squeezeformer_encoder import SqueezeformerEncoder  # noqa: F401
 from .conv_asr import ConvASRDecoder  # noqa: F401
 from .ctc import CTCLoss  # noqa: F401
-from .ctc_decoding import GreedyCTCDecoder, WER, word_error_rate  # noqa: F401
+from .ctc_decoding import CTCAligner, GreedyCTCDecoder, WER, ctc_offsets, word_error_rate  # noqa: F401
 from .rnnt_loss import RNNTLoss, RNNTLossNumba  # noqa: F401
 from .tdt_loss import TDTLoss, TDTLossNumba  # noqa: F401
 from .rnnt import RNNTDecoder, RNNTJoint  # noqa: F401

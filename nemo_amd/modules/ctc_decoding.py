@@ -26,14 +26,25 @@ class GreedyCTCDecoder:
         self.blank_id = len(self.vocabulary) if blank_id is None else int(blank_id)
 
     @torch.no_grad()
-    def decode_ids(self, log_probs: torch.Tensor, lengths: Optional[torch.Tensor] = None):
-        """log_probs [B, T, V+1] (device) -> (tokens i32 [B,T] folded / blank-free / -1 padded, lengths i32 [B], score [B])"""
+    def decode_ids(self, log_probs: torch.Tensor, lengths: Optional[torch.Tensor] = None, return_timestamps: bool = False):
+        """log_probs [B, T, V+1] (device) -> (tokens i32 [B,T] folded / blank-free / -1 padded, lengths i32 [B], score [B]);
+        with return_timestamps also (start, end) i32 [B,T]: the first / last frame of the run of equal arg-max labels behind each
+        token (`mi355x_ctc_greedy_decode_ts`; the `compute_timestamps` of AbstractCTCDecoding, ctc_decoding.py:290-340)"""
         if log_probs.dim() != 3:
             raise ValueError(f"`decoder_output` must be a tensor of shape [B, T, V] (log probs, float). Provided shape = "
                              f"{tuple(log_probs.shape)}")
         lp = log_probs.to(torch.float32).contiguous()
         lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
+        if return_timestamps:
+            return ops.ctc_greedy_decode_ts(lp, lens, self.blank_id)
         return ops.ctc_greedy_decode(lp, lens, self.blank_id)
+
+    def offsets(self, ids: Sequence[int], starts: Sequence[int], ends: Sequence[int]):
+        """(char offsets, word offsets) of a token sequence with its first / last frames, see `ctc_offsets`"""
+        if self.vocabulary is None:
+            raise ValueError("no vocabulary: offsets are not available")
+        return ctc_offsets([self.vocabulary[i] for i in ids], starts, ends,
+                           word_pieces=any(v.startswith("▁") for v in self.vocabulary))
 
     def ids_to_text(self, ids: Sequence[int]) -> str:
         if self.vocabulary is None:
@@ -45,6 +56,55 @@ class GreedyCTCDecoder:
         tokens, out_len, _ = self.decode_ids(log_probs, lengths)
         tokens, out_len = tokens.cpu(), out_len.cpu()                  # the only D2H copy: folded ids
         return [self.ids_to_text(tokens[b, : int(out_len[b])].tolist()) for b in range(tokens.shape[0])]
+
+
+def ctc_offsets(tokens: Sequence[str], starts: Sequence[int], ends: Sequence[int], word_pieces: bool = False):
+    """The offsets of AbstractCTCDecoding (`_compute_offsets`, `_get_word_offsets_chars` / `_get_word_offsets_subwords_sentencepiece`,
+    ctc_decoding.py:620-800), built on the host from tokens and their first / last frames; `end_offset` is exclusive (last frame + 1).
+    -> (char: one {char, start_offset, end_offset} per token, word: {word, start_offset, end_offset}).  Word pieces: a token with a
+    leading U+2581 starts a word.  Characters: the space token separates words and belongs to none.  A word spans its first token's
+    start to its last token's end."""
+    char = [{"char": tok, "start_offset": int(s), "end_offset": int(e) + 1} for tok, s, e in zip(tokens, starts, ends)]
+    words, cur = [], None
+    for c in char:
+        tok = c["char"]
+        if word_pieces:
+            if tok.startswith("▁") or cur is None:
+                cur = {"word": "", "start_offset": c["start_offset"], "end_offset": c["end_offset"]}
+                words.append(cur)
+            cur["word"] += tok.replace("▁", "")
+            cur["end_offset"] = c["end_offset"]
+        elif tok == " ":
+            cur = None
+        else:
+            if cur is None:
+                cur = {"word": "", "start_offset": c["start_offset"], "end_offset": c["end_offset"]}
+                words.append(cur)
+            cur["word"] += tok
+            cur["end_offset"] = c["end_offset"]
+    return char, [w for w in words if w["word"]]
+
+
+class CTCAligner:
+    """Forced alignment of known token ids to log-probabilities: the Viterbi pass of the reference's forced aligner
+    (tools/nemo_forced_aligner/utils/viterbi_decoding.py, a Python loop over T) as one launch per batch (`mi355x_ctc_align`).
+    blank_id = len(vocabulary), as in GreedyCTCDecoder."""
+
+    def __init__(self, vocabulary: Optional[Sequence[str]] = None, blank_id: Optional[int] = None):
+        if vocabulary is None and blank_id is None:
+            raise ValueError("either a vocabulary or a blank_id is required")
+        self.vocabulary = list(vocabulary) if vocabulary is not None else None
+        self.blank_id = len(self.vocabulary) if blank_id is None else int(blank_id)
+
+    @torch.no_grad()
+    def __call__(self, log_probs: torch.Tensor, lengths: torch.Tensor, targets: torch.Tensor, target_lengths: torch.Tensor):
+        """log_probs [B, T, V+1], lengths [B], targets [B, U], target_lengths [B] (device) -> (path i32 [B,T]: state 0..2U of the
+        blank-extended transcript per frame, tok_start i32 [B,U], tok_end i32 [B,U], score f32 [B]); -1 padded; an utterance
+        that cannot be aligned has score -inf and -1 everywhere"""
+        if log_probs.dim() != 3:
+            raise ValueError(f"`log_probs` must be a tensor of shape [B, T, V]. Provided shape = {tuple(log_probs.shape)}")
+        return ops.ctc_align(log_probs.to(torch.float32).contiguous(), targets.to(torch.int64).contiguous(),
+                             lengths.to(torch.int64).contiguous(), target_lengths.to(torch.int64).contiguous(), self.blank_id)
 
 
 def _levenshtein(a, b) -> int:

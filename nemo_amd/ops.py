@@ -416,6 +416,38 @@ def ctc_greedy_decode(logp, lens, blank):
     return tokens, out_len, score
 
 
+def ctc_greedy_decode_ts(logp, lens, blank):
+    """ctc_greedy_decode plus the frames: -> (tokens, out_len, score, tok_start i32 [B,T], tok_end i32 [B,T]); start / end = first /
+    last frame of the run of equal arg-max labels behind each kept token, -1 padded"""
+    B, T, C_ = logp.shape
+    tokens, tok_start, tok_end = (torch.empty(B, T, dtype=torch.int32, device=logp.device) for _ in range(3))
+    out_len = torch.empty(B, dtype=torch.int32, device=logp.device)
+    score = torch.empty(B, dtype=torch.float32, device=logp.device)
+    check(lib.mi355x_ctc_greedy_decode_ts(_ptr(logp), _ptr(lens), _ptr(tokens), _ptr(out_len), _ptr(score), _ptr(tok_start),
+                                          _ptr(tok_end), B, T, C_, blank, _stream()), "ctc_greedy_decode_ts")
+    return tokens, out_len, score, tok_start, tok_end
+
+
+def ctc_align(logp, targets, in_len, tgt_len, blank):
+    """Viterbi forced alignment (mi355x_ctc_align): logp f32 [B,T,C] contiguous, targets i64 [B,U], in_len / tgt_len i64 [B] ->
+    (path i32 [B,T]: state 0..2U per frame, tok_start i32 [B,U], tok_end i32 [B,U]: first / last frame of each label, score f32 [B]);
+    -1 padded; an infeasible utterance has score -inf and -1 everywhere"""
+    B, T, C_ = logp.shape
+    U = targets.shape[1]
+    if U == 0:   # (a batch of empty transcripts: the kernel wants a column to point at)
+        if int(tgt_len.max()) > 0:
+            raise ValueError("ctc_align: target lengths exceed the width of `targets` (0)")
+        targets = targets.new_zeros(B, 1)
+    Uk = targets.shape[1]
+    bp = torch.empty(B * T * ((Uk + 8) & ~7), dtype=torch.uint8, device=logp.device)
+    path = torch.empty(B, T, dtype=torch.int32, device=logp.device)
+    tok_start, tok_end = (torch.empty(B, Uk, dtype=torch.int32, device=logp.device) for _ in range(2))
+    score = torch.empty(B, dtype=torch.float32, device=logp.device)
+    check(lib.mi355x_ctc_align(_ptr(logp), _ptr(targets), _ptr(in_len), _ptr(tgt_len), _ptr(bp), _ptr(path), _ptr(tok_start),
+                               _ptr(tok_end), _ptr(score), B, T, C_, Uk, blank, _stream()), "ctc_align")
+    return path, tok_start[:, :U], tok_end[:, :U], score
+
+
 def specaug_rects(u_tw, u_ts, u_fw, u_fs, length, rects, B, nt, nf, F, T, time_width, freq_width):
     """mask rectangles of SpecAugment's vectorised path from its four uniform draws (one launch instead of ~40 tensor ops)"""
     frac = isinstance(time_width, float)

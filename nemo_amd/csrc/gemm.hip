@@ -2015,13 +2015,106 @@ __device__ __forceinline__ void v8_round_fast(const GemmP& p, const float* win, 
   }
 }
 
+// ---- specialised rounds of the above for the K = 512 class of the Conformer block (FFN1 forward, its Swish-gradient dgrad, plain
+// bf16 stores): what v8_round_fast decides per ROW at run time -- output / aux element types, swish_g, dropout on or off, row inside
+// the matrix -- is a template parameter here, chosen once per launch by the dispatcher (kernel template parameter ES = V8_ES_*) and once per round (FULL: all 64
+// rows inside the matrix).  The generic round compiled to a uniform branch (several on SGPRs re-read from spill lanes) between any
+// two rows, so the four rows of a thread ran strictly one after the other, each exposing its own exp -> rcp -> fma chain; here the
+// four rows are one basic block.  Addresses: one uniform 64-bit base per row (scalar unit) + one 32-bit offset per thread and tensor,
+// the dropout index advances by a uniform step per row.  Same operations on the same values in the same order: bit-identical.
+// bf16 C, bf16 aux; EPI_STORE / EPI_SWISH_DROP with swish_g / EPI_DSWISH with swish_g; no row map.
+#define V8_ES_SWISH_G_DROP 1   // EPI_SWISH_DROP, swish_g, dropout on
+#define V8_ES_SWISH_G 2        // EPI_SWISH_DROP, swish_g, dropout off
+#define V8_ES_DSWISH_G 3       // EPI_DSWISH, swish_g
+#define V8_ES_STORE 4          // EPI_STORE, dropout off
+// (the destination must not be touched -- copied, spilled -- between this read and the counted wait that pins it: a property of the
+// generated code, checked on every build by tools/check_asm_loads.py).  A compiler-issued s_load of a kernel argument between the
+// reads and a wait shares lgkmcnt and may return out of order; the lint does not look for it and need not: with k such loads in
+// flight the counter stands at 8 + k, lgkmcnt(6 - 2 it) then needs 2 it + 2 + k completions, at most k of them scalar, and the LDS
+// reads complete in order among themselves -- the wait can only get longer, never shorter.
+template <int OFF>
+__device__ __forceinline__ void v8_rdw(f32x4& dst, uint32_t addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
+}
+template <int EPI, bool DROP, bool FULL>
+__device__ __forceinline__ void v8_round_spec(const GemmP& p, const float* win, const float (&b8)[8], int z, long long coff, int m_base,
+                                              int n0) {
+  static_assert(EPI == EPI_STORE || EPI == EPI_SWISH_DROP || EPI == EPI_DSWISH, "specialised kinds");
+  const int k = threadIdx.x & 31, rl0 = threadIdx.x >> 5;
+  const uint32_t vC = (uint32_t)(rl0 * p.ldc + k * 8) * 2u, vA = (uint32_t)(rl0 * p.ldaux + k * 8) * 2u;  // bytes (ld < 2^24 by dispatch)
+  u32x4 h4[EPI == EPI_DSWISH ? 4 : 1];
+  if (EPI == EPI_DSWISH) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int ro = (it >> 1) * 64 + 16 * (it & 1);
+      if (FULL || m_base + ro + rl0 < p.M)
+        h4[EPI == EPI_DSWISH ? it : 0] =
+            *reinterpret_cast<const u32x4*>((const char*)p.aux_in + (coff + (long long)(m_base + ro) * p.ldaux + n0) * 2 + vA);
+    }
+  }
+  // the eight window reads as inline asm with counted waits (row it needs the first 2 it + 2 of them): left to the compiler, each
+  // pair of reads was sunk to its row and waited for there -- four exposed LDS round trips per round
+  const int hi = (threadIdx.x >> 4) & 1, sw = rl0 & 7;  // (read order: see v8_round_fast)
+  const uint32_t wrow = lds_addr(win) + (uint32_t)rl0 * 1024u;
+  const uint32_t ax = wrow + (uint32_t)(((2 * k + hi) ^ sw) << 4), ay = wrow + (uint32_t)(((2 * k + 1 - hi) ^ sw) << 4);
+  f32x4 x[4], y[4];
+  v8_rdw<0>(x[0], ax); v8_rdw<0>(y[0], ay);
+  v8_rdw<16384>(x[1], ax); v8_rdw<16384>(y[1], ay);
+  v8_rdw<32768>(x[2], ax); v8_rdw<32768>(y[2], ay);
+  v8_rdw<49152>(x[3], ax); v8_rdw<49152>(y[3], ay);
+  if (!FULL)  // (a row outside the matrix skips its wait)
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x[0]), "+v"(y[0]), "+v"(x[1]), "+v"(y[1]), "+v"(x[2]), "+v"(y[2]), "+v"(x[3]), "+v"(y[3]) : : "memory");
+  const uint32_t d0 = (uint32_t)z * (uint32_t)(p.M * p.N) + (uint32_t)(n0 + k * 8) + (uint32_t)(m_base + rl0) * (uint32_t)p.N;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int ro = (it >> 1) * 64 + 16 * (it & 1);
+    if (!FULL && m_base + ro + rl0 >= p.M) continue;
+    if (FULL) {
+      if (it == 0) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(x[0]), "+v"(y[0]) : : "memory");
+      else if (it == 1) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x[1]), "+v"(y[1]) : : "memory");
+      else if (it == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(x[2]), "+v"(y[2]) : : "memory");
+      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x[3]), "+v"(y[3]) : : "memory");
+    }
+    const f32x4 a = hi ? y[it] : x[it], b = hi ? x[it] : y[it];
+    float v[8] = {a[0] + b8[0], a[1] + b8[1], a[2] + b8[2], a[3] + b8[3], b[0] + b8[4], b[1] + b8[5], b[2] + b8[6], b[3] + b8[7]};
+    float dm[8];
+    if (DROP) {
+      uint32_t s = drop_group_seed(p.drop, (d0 + (uint32_t)ro * (uint32_t)p.N) >> 3);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { s = xorshift32(s); dm[j] = s >= p.drop.threshold ? p.drop.scale : 0.f; }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dm[j] = 1.f;
+    }
+    if (EPI == EPI_STORE) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] *= p.alpha * dm[j];
+    } else if (EPI == EPI_SWISH_DROP) {
+      float g[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) swish_pair(v[j], dm[j], v[j], g[j]);
+      const u32x4 t = {pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3]), pack_bf2(g[4], g[5]), pack_bf2(g[6], g[7])};
+      *reinterpret_cast<u32x4*>((char*)p.aux_out + (coff + (long long)(m_base + ro) * p.ldaux + n0) * 2 + vA) = t;
+    } else {
+      const u32x4 t = h4[EPI == EPI_DSWISH ? it : 0];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[2 * j] *= __uint_as_float(t[j] << 16);
+        v[2 * j + 1] *= __uint_as_float(t[j] & 0xffff0000u);
+      }
+    }
+    const u32x4 t = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
+    *reinterpret_cast<u32x4*>((char*)p.C + (coff + (long long)(m_base + ro) * p.ldc + n0) * 2 + vC) = t;
+  }
+}
+
 // AH = A halves of the tile: 2 = the 256x256 tile described above; 1 = a 128x256 tile (dense NT only) for problems whose 256x256
 // tiles would leave half the chip idle (N = 512 at M = 16032: 126 tiles): one A half, both B halves, two phases per K-tile
 // (p0 (A0,B0), p1 (A0,B1)), THREE K-tile buffers of three half-tile images (A0 | B0 | B1, 144 KiB) filled two K-tiles ahead -- a
 // K-tile is only 1 024 MFMA cycles here, one tile of lead would not cover the DMA latency.  Phase 0 stages B0 of tile t+2, phase 1
 // its B1 and A0 and waits vmcnt(6): all of tile t+1 landed, tile t+2 in flight; every buffer is re-staged two or three phases
 // after its last read (no early-retire trick needed).
-template <int G, bool TN, int AH = 2>
+template <int G, bool TN, int AH = 2, int ES = 0>
 __device__ __forceinline__ void gemm_v8_body(const GemmP& p, bf16_t* smem8, const int tile_m, const int tile_n, const int kslice,
                                              const int z) {
   const int tn = (p.N + BN4 - 1) / BN4;
@@ -2502,6 +2595,18 @@ __device__ __forceinline__ void gemm_v8_body(const GemmP& p, bf16_t* smem8, cons
 #endif
       __syncthreads();
       const int mb = m0 + (r >> 1) * 128 + (r & 1) * 32;
+      if constexpr (ES != 0) {  // (dense NT kernel only; rows of the round: mb + 0..31 and mb + 64..95)
+        static_assert(G == 0 && !TN && AH == 2, "specialised rounds: the dense NT 256x256 kernel");
+#define V8_SPEC(EPI_, DROP_) \
+  if (mb + 96 <= p.M) v8_round_spec<EPI_, DROP_, true>(p, win, b8, z, coff, mb, n0); \
+  else v8_round_spec<EPI_, DROP_, false>(p, win, b8, z, coff, mb, n0);
+        if constexpr (ES == V8_ES_SWISH_G_DROP) { V8_SPEC(EPI_SWISH_DROP, true) }
+        else if constexpr (ES == V8_ES_SWISH_G) { V8_SPEC(EPI_SWISH_DROP, false) }
+        else if constexpr (ES == V8_ES_DSWISH_G) { V8_SPEC(EPI_DSWISH, false) }
+        else { V8_SPEC(EPI_STORE, false) }
+#undef V8_SPEC
+        continue;
+      }
       switch (p.epi) {
         case EPI_STORE: v8_round_fast<EPI_STORE>(p, win, b8, z, coff, mb, 64, n0); break;
         case EPI_SWISH_DROP: v8_round_fast<EPI_SWISH_DROP>(p, win, b8, z, coff, mb, 64, n0); break;
@@ -2539,7 +2644,7 @@ __device__ __forceinline__ void gemm_v8_body(const GemmP& p, bf16_t* smem8, cons
 #endif
 }
 
-template <int G, bool TN, int AH = 2>
+template <int G, bool TN, int AH = 2, int ES = 0>
 __global__ __launch_bounds__(512) void gemm_bf16_v8_kernel(GemmP p) {
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) bf16_t smem8[];  // 2 K-tiles x 4 half-tile images x 16 KiB (AH = 1: 3 x 3 x 16 KiB)
@@ -2582,7 +2687,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_v8_kernel(GemmP p) {
     const unsigned long long t0 = wall_clock64();
     while (wall_clock64() - t0 < (unsigned long long)p.v8_delay) __builtin_amdgcn_s_sleep(16);
   }
-  gemm_v8_body<G, TN, AH>(p, smem8, tile_m, tile_n, ks, z);
+  gemm_v8_body<G, TN, AH, ES>(p, smem8, tile_m, tile_n, ks, z);
 }
 
 // ---- grouped weight gradients on the eighth structure: the problems' 256x256 tiles x K slices in one launch, (problem, K slice)
@@ -3113,16 +3218,16 @@ static int env_int(const char* name, int dflt) {
 // run-time knobs (mi355x_gemm_config(key, value); first read falls back to the environment): key 4 = the 256x256 structures
 // (MI355X_GEMM_V4: 0 never, 1 heuristic, 2 whenever N > 128), key 5 = the persistent structure (MI355X_GEMM_V5), key 6 = register
 // prefetch instead of LDS-DMA inside the 256x256 structure (MI355X_GEMM_V6: 0 = default / 1), key 7 = the same inside the 256x128
-// structure (MI355X_GEMM_V7, default 1), key 3 = fp32 problems on the matrix cores (MI355X_F32_MFMA, default 1; 0 = vector unit).  Defaults follow the in-step A/B (tools/step_ab.py, recorded graphs, same box): the
+// structure (MI355X_GEMM_V7, default 1), key 3 = fp32 problems on the matrix cores (MI355X_F32_MFMA, default 1; 0 = vector unit), key 10 = the specialised epilogue rounds of the phase-staggered structure (MI355X_GEMM_V8_EPI, default 1).  Defaults follow the in-step A/B (tools/step_ab.py, recorded graphs, same box): the
 // 256x128 variant -0.2 ms per step, the 256x256 variant +0.3 ms although it wins every isolated launch (profiles/r3_gemm_structures.md)
-static std::atomic<int> g_mode[10] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static std::atomic<int> g_mode[11] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
 static int mode_now(int key) {
   int v = g_mode[key].load(std::memory_order_relaxed);
   if (v < 0) {
     static const int env4 = env_int("MI355X_GEMM_V4", 1), env5 = env_int("MI355X_GEMM_V5", 1), env6 = env_int("MI355X_GEMM_V6", 0),
                      env7 = env_int("MI355X_GEMM_V7", 1), env3 = env_int("MI355X_F32_MFMA", 1), env8 = env_int("MI355X_GEMM_V8", 1),
-                     env9 = env_int("MI355X_GEMM_V8_DELAY", 0);
-    const int from_env = key == 4 ? env4 : key == 5 ? env5 : key == 6 ? env6 : key == 7 ? env7 : key == 3 ? env3 : key == 8 ? env8 : key == 9 ? env9 : 0;
+                     env9 = env_int("MI355X_GEMM_V8_DELAY", 0), env10 = env_int("MI355X_GEMM_V8_EPI", 1);
+    const int from_env = key == 4 ? env4 : key == 5 ? env5 : key == 6 ? env6 : key == 7 ? env7 : key == 3 ? env3 : key == 8 ? env8 : key == 9 ? env9 : key == 10 ? env10 : 0;
     int expected = -1;
     g_mode[key].compare_exchange_strong(expected, from_env, std::memory_order_relaxed);
     v = g_mode[key].load(std::memory_order_relaxed);
@@ -3130,13 +3235,18 @@ static int mode_now(int key) {
   return v;
 }
 static int v5_mode_now() { return mode_now(5); }
+// key 11 (read only, tests): which structure the calling thread's last mi355x_gemm launch took -- 800 + V8_ES_* = the phase-staggered
+// 256x256 kernel (+ its specialised epilogue round), 810 = its 128x256 tile, 0 = any other structure
+static thread_local int g_last_path = 0;
 extern "C" int mi355x_gemm_config(int key, int value) {
-  if (key < 3 || key > 9) return -1;
+  if (key == 11) return g_last_path;
+  if (key < 3 || key > 10) return -1;
   return g_mode[key].exchange(value, std::memory_order_relaxed);
 }
 
 extern "C" int mi355x_gemm(const mi355x_gemm_desc* d, void* stream) {
   mi_clear_errors();
+  g_last_path = 0;
   if (!d || !d->A || !d->B || !d->C || d->M <= 0 || d->N <= 0 || d->K <= 0) return MI_ERR_ARG;
   if (d->in_dtype != MI_DT_F32 && d->in_dtype != MI_DT_BF16) return MI_ERR_ARG;
   // the LDS-DMA source of a reduction-major operand advances by BK * ld elements per k-tile, kept in 32 bits
@@ -3308,6 +3418,7 @@ extern "C" int mi355x_gemm(const mi355x_gemm_desc* d, void* stream) {
             static const bool attr81_ok = hipFuncSetAttribute((const void*)gemm_bf16_v8_kernel<0, false, 1>,
                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 9 * V8_HALF_B) == hipSuccess;
             if (!attr81_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
+            g_last_path = 810;
             MI_LAUNCH((gemm_bf16_v8_kernel<0, false, 1>), dim3(((p.M + 127) / 128) * tn8, sk, p.batch), dim3(512), 9 * V8_HALF_B, s, p);
             return mi_check_launch();
           }
@@ -3315,16 +3426,30 @@ extern "C" int mi355x_gemm(const mi355x_gemm_desc* d, void* stream) {
         if (v8_can && v8_pick) {
           typedef void (*v8_fn)(GemmP);
           static const v8_fn v8_all[] = {gemm_bf16_v8_kernel<0, false>, gemm_bf16_v8_kernel<1, false>, gemm_bf16_v8_kernel<0, true>,
-                                         gemm_bf16_v8_kernel<2, true>};
+                                         gemm_bf16_v8_kernel<2, true>,
+                                         gemm_bf16_v8_kernel<0, false, 2, V8_ES_SWISH_G_DROP>, gemm_bf16_v8_kernel<0, false, 2, V8_ES_SWISH_G>,
+                                         gemm_bf16_v8_kernel<0, false, 2, V8_ES_DSWISH_G>, gemm_bf16_v8_kernel<0, false, 2, V8_ES_STORE>};
           static const bool attr8_ok = [] {
             for (v8_fn f : v8_all)
               if (hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * V8_BUF_B) != hipSuccess) return false;
             return true;
           }();
           if (!attr8_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
-          const v8_fn fn = nt8 ? v8_all[p.g_on == 1 ? 1 : 0] : v8_all[p.g_on == 2 ? 3 : 2];
+          v8_fn fn = nt8 ? v8_all[p.g_on == 1 ? 1 : 0] : v8_all[p.g_on == 2 ? 3 : 2];
           // key 9: the phase offset (10-ns ticks; > 0: that many for every problem of more than one round and at most 16 K-tiles)
           if (nt8 && blocks8 > 256 && nk <= 16) p.v8_delay = mode_now(9);
+          // key 10 (MI355X_GEMM_V8_EPI, default 1; 0 = the generic round everywhere, the A/B arm): the kernels with a specialised
+          // epilogue round (separate instantiations: the generic kernel's code does not change with them)
+          int es = 0;
+          if (mode_now(10) && nt8 && !p.g_on && !p.r_on && !p.atomic && sk == 1 && p.csc == 1 && p.c_dt == MI_DT_BF16 && p.ldc < (1 << 24) &&
+              p.ldaux < (1 << 24)) {
+            if (p.epi == EPI_SWISH_DROP && p.swish_g && p.auxout_dt == MI_DT_BF16)
+              es = p.drop.threshold ? V8_ES_SWISH_G_DROP : V8_ES_SWISH_G;
+            else if (p.epi == EPI_DSWISH && p.swish_g && p.auxin_dt == MI_DT_BF16) es = V8_ES_DSWISH_G;
+            else if (p.epi == EPI_STORE && !p.drop.threshold) es = V8_ES_STORE;
+          }
+          if (es) fn = v8_all[3 + es];
+          g_last_path = 800 + es;
           MI_LAUNCH(fn, dim3(tm2 * tn8, sk, p.batch), dim3(512), 2 * V8_BUF_B, s, p);
           return mi_check_launch();
         }

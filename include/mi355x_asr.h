@@ -95,8 +95,13 @@ int mi355x_gemm(const mi355x_gemm_desc* desc, void* stream);
  * structure in 10-ns ticks (experiment, default 0); key 10: its specialised epilogue rounds (1 = default, 0 = generic round);
  * key 11 (read only, value ignored): structure of the calling thread's last mi355x_gemm launch (800 + round = that structure, 810 = its
  * 128x256 tile, 0 = another one).
- * Returns the previous value (-1 = not yet read from the environment), or -1 for an unknown key. */
+ * Returns the previous EFFECTIVE value (the environment default if the key was never set: always >= 0, and writing it back restores
+ * exactly the earlier state), or -1 for an unknown key. */
 int mi355x_gemm_config(int key, int value);
+/* What mi355x_gemm would launch for `desc` under the current knobs, without launching (no GPU needed; pointers are checked for
+ * alignment only).  Returns what mi355x_gemm's argument checks return (1 = rejected); on 0 out = { kernel id (csrc/gemm.hip: GemmKernel),
+ * the key-11 code, grid x, y, z, workgroup size, dynamic LDS bytes, key-9 delay of this launch }. */
+int mi355x_gemm_plan(const mi355x_gemm_desc* desc, int out[8]);
 /* Up to 12 independent weight-gradient problems in one launch: every desc must be bf16, transA = transB = 1, atomic
  * f32 C with dense columns, no bias / aux / epilogue, and share K (the token count); descs[0].splitk applies to all.
  * colsum_out (the bias gradient) is honoured per problem.  See csrc/gemm.hip: gemm_bf16_grouped_tn_kernel. */

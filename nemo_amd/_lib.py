@@ -70,6 +70,7 @@ SIGNATURES = {
     "mi355x_gemm": [C.POINTER(GemmDesc), vp],
     "mi355x_gemm_grouped": [C.POINTER(GemmDesc), i32, vp],
     "mi355x_gemm_config": [i32, i32],
+    "mi355x_gemm_plan": [C.POINTER(GemmDesc), C.POINTER(i32 * 8)],
     "mi355x_set_step_counter": [vp],
     "mi355x_set_null_launch": [i32],
     "mi355x_ffn_fwd": [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i32, i32, i32, f32, u32, u32, f32, u32, u32, f32, vp],

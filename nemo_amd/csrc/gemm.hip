@@ -2,18 +2,25 @@
 //
 //   C[M,N] = epilogue( sum_k opA(m,k) * opB(n,k) )          (optionally batched / split-K / gathered / grouped)
 //
-// bf16 (MFMA `v_mfma_f32_32x32x16_bf16`), four structures behind one descriptor (`mi355x_gemm`):
-//   * gemm_bf16_v2_kernel   256x128x64 tile, 8 waves x (64x64), three LDS stages filled by LDS-DMA two K-tiles ahead
-//                           (counted vmcnt, raw s_barrier), ds_read_b128 / ds_read_b64_tr_b16 fragments  -- the default
-//   * gemm_bf16_v4_kernel   256x256x64 tile, 8 waves x (128x64), two LDS stages -- when the larger tile still fills the chip
-//   * gemm_bf16_grouped_tn_kernel   up to 12 weight-gradient problems in one launch of the v2 body (`mi355x_gemm_grouped`)
-//   * gemm_bf16_kernel      128x128x64 tile, 4 waves, register-staged -- small problems and the TN / K-contiguous-B layout
+// bf16, eight kernel structures behind one descriptor (`mi355x_gemm`; which one runs: gemm_plan at the end of this file):
+//   * gemm_bf16_v8_kernel   256x256x64 (or 128x256) tile on v_mfma_f32_16x16x32_bf16, two wave rows one barrier apart ("phase-staggered"),
+//                           LDS-DMA seven half-tiles ahead -- the default wherever 256x256 tiles fill the chip (dense / gathered-A NT)
+//   * gemm_bf16_v5_kernel   persistent 256x128 tiles, epilogue overlapped with the next tile's K loop -- default for K <= 576 with a
+//                           Swish-gradient / residual epilogue or a wide plain store that quantises badly on 256x256 tiles
+//   * gemm_bf16_v2_kernel   256x128x64 tile (v_mfma_f32_32x32x16_bf16), 8 waves x (64x64), three LDS stages filled by LDS-DMA two K-tiles
+//                           ahead, or (REG) operands prefetched through registers -- the default for everything else with M >= 192, N >= 96
+//   * gemm_bf16_v4_kernel   256x256x64 tile, 8 waves x (128x64), two LDS stages, lock step -- the reduction-major / NN layouts that
+//                           fill the chip with the larger tile; the bit-identity reference of the v8 tests
+//   * gemm_bf16_v6_kernel   the v4 tile with operands prefetched through registers (key 6, off by default)
+//   * gemm_bf16_kernel      128x128x64 tile, 4 waves, register-staged -- small problems and the TT (A reduction-major only) layout
+//   * gemm_bf16_grouped_tn_kernel / gemm_bf16_grouped_tn8_kernel   up to 40 weight-gradient problems in one launch of the v2 / v8 body
+//                           (`mi355x_gemm_grouped`; the v2 body by default)
 // An operand may be stored "reduction-major" ([K][rows]: both wgrad operands); it is DMA'd as it lies in memory and
 // transposed by the LDS read.  Operand A (forward / dgrad) or the reduction-major B (wgrad) of a convolution can be
 // GATHERED from a channels-last grid by the LDS-DMA (implicit GEMM), and output rows can be scattered (row map).
 // Tile -> workgroup mapping is XCD-aware (bijective chunking of the tile list over the 8 XCDs so that tiles sharing an
 // operand panel hit the same L2).
-// f32 path: exact-fp32 VALU tile kernel with arbitrary strides (parity / fp32 configuration).
+// f32 path: gemm_f32_mfma_kernel (v_mfma_f32_32x32x2_f32, the default) and gemm_f32_kernel (exact-fp32 VALU tiles, key 3 = 0), arbitrary strides.
 // All share the epilogue kinds below (bias, Swish+dropout, residual, Swish-grad, ReLU+time-mask, ReLU-grad, atomic split-K).
 //
 // Replaces on the reference path: torch.nn.functional.linear / conv1d(k=1) / matmul / conv2d calls in
@@ -3209,49 +3216,111 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(GemmP p) {
 // =================================================================================================
 // C ABI
 // =================================================================================================
+// mi355x_gemm = gemm_fill (check the descriptor, fill the kernel arguments) -> gemm_modes_now (read the knobs) -> gemm_plan (pure:
+// which kernel, grid, LDS) -> gemm_launch (one table, one launch site).  mi355x_gemm_plan stops after the plan: the dispatch rules
+// are pinned row by row on the CPU (tests/test_gemm_plan_host.py).
 // Dispatch knobs are read by the main thread AND by the autograd thread (backward launches): environment values are
-// function-local `static const` (initialised once, thread-safe since C++11), the one knob that can change at run time is atomic.
+// function-local `static const` (initialised once, thread-safe since C++11), the knobs that can change at run time are atomic.
 static int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return (e && e[0]) ? atoi(e) : dflt;
 }
-// run-time knobs (mi355x_gemm_config(key, value); first read falls back to the environment): key 4 = the 256x256 structures
-// (MI355X_GEMM_V4: 0 never, 1 heuristic, 2 whenever N > 128), key 5 = the persistent structure (MI355X_GEMM_V5), key 6 = register
-// prefetch instead of LDS-DMA inside the 256x256 structure (MI355X_GEMM_V6: 0 = default / 1), key 7 = the same inside the 256x128
-// structure (MI355X_GEMM_V7, default 1), key 3 = fp32 problems on the matrix cores (MI355X_F32_MFMA, default 1; 0 = vector unit), key 10 = the specialised epilogue rounds of the phase-staggered structure (MI355X_GEMM_V8_EPI, default 1).  Defaults follow the in-step A/B (tools/step_ab.py, recorded graphs, same box): the
-// 256x128 variant -0.2 ms per step, the 256x256 variant +0.3 ms although it wins every isolated launch (profiles/r3_gemm_structures.md)
+// run-time knobs (mi355x_gemm_config(key, value); first read falls back to the environment): key 3 = fp32 problems on the matrix
+// cores (0 = vector unit), key 4 = the 256x256 structures (0 never, 1 heuristic, 2 whenever N > 128), key 5 = the persistent
+// structure, key 6 = register prefetch instead of LDS-DMA inside the 256x256 structure, key 7 = the same inside the 256x128
+// structure, key 8 = the phase-staggered structure (modes: see gemm_plan), key 9 = its phase offset, key 10 = its specialised
+// epilogue rounds.  Defaults follow the in-step A/B (tools/step_ab.py, recorded graphs, same box): the 256x128 variant -0.2 ms per
+// step, the 256x256 variant +0.3 ms although it wins every isolated launch (profiles/r3_gemm_structures.md)
+static const struct { const char* env; int dflt; } g_knob[11] = {
+    {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {"MI355X_F32_MFMA", 1}, {"MI355X_GEMM_V4", 1}, {"MI355X_GEMM_V5", 1}, {"MI355X_GEMM_V6", 0},
+    {"MI355X_GEMM_V7", 1}, {"MI355X_GEMM_V8", 1}, {"MI355X_GEMM_V8_DELAY", 0}, {"MI355X_GEMM_V8_EPI", 1}};
 static std::atomic<int> g_mode[11] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
 static int mode_now(int key) {
   int v = g_mode[key].load(std::memory_order_relaxed);
   if (v < 0) {
-    static const int env4 = env_int("MI355X_GEMM_V4", 1), env5 = env_int("MI355X_GEMM_V5", 1), env6 = env_int("MI355X_GEMM_V6", 0),
-                     env7 = env_int("MI355X_GEMM_V7", 1), env3 = env_int("MI355X_F32_MFMA", 1), env8 = env_int("MI355X_GEMM_V8", 1),
-                     env9 = env_int("MI355X_GEMM_V8_DELAY", 0), env10 = env_int("MI355X_GEMM_V8_EPI", 1);
-    const int from_env = key == 4 ? env4 : key == 5 ? env5 : key == 6 ? env6 : key == 7 ? env7 : key == 3 ? env3 : key == 8 ? env8 : key == 9 ? env9 : key == 10 ? env10 : 0;
     int expected = -1;
-    g_mode[key].compare_exchange_strong(expected, from_env, std::memory_order_relaxed);
+    g_mode[key].compare_exchange_strong(expected, env_int(g_knob[key].env, g_knob[key].dflt), std::memory_order_relaxed);
     v = g_mode[key].load(std::memory_order_relaxed);
   }
   return v;
 }
-static int v5_mode_now() { return mode_now(5); }
-// key 11 (read only, tests): which structure the calling thread's last mi355x_gemm launch took -- 800 + V8_ES_* = the phase-staggered
+// key 11 (read only, tests): GemmPlan::path of the calling thread's last mi355x_gemm launch -- 800 + V8_ES_* = the phase-staggered
 // 256x256 kernel (+ its specialised epilogue round), 810 = its 128x256 tile, 0 = any other structure
 static thread_local int g_last_path = 0;
 extern "C" int mi355x_gemm_config(int key, int value) {
   if (key == 11) return g_last_path;
   if (key < 3 || key > 10) return -1;
+  mode_now(key);  // the environment default first: the value returned is the effective one, writing it back restores the state
   return g_mode[key].exchange(value, std::memory_order_relaxed);
 }
 
-extern "C" int mi355x_gemm(const mi355x_gemm_desc* d, void* stream) {
-  mi_clear_errors();
-  g_last_path = 0;
+// every knob value the plan depends on
+struct GemmModes {
+  int k[11];      // keys 3..10 of mi355x_gemm_config
+  int v2;         // MI355X_GEMM_V2 (default 1): 0 = the LDS-DMA structures off
+  int few_tiles;  // MI355X_GEMM_FEW_TILES (default 0), see gemm_plan
+};
+static GemmModes gemm_modes_now() {
+  static const int v2 = env_int("MI355X_GEMM_V2", 1) ? 1 : 0, few = env_int("MI355X_GEMM_FEW_TILES", 0);
+  GemmModes m = {};
+  for (int key = 3; key <= 10; ++key) m.k[key] = mode_now(key);
+  m.v2 = v2; m.few_tiles = few;
+  return m;
+}
+
+// one id per kernel instantiation mi355x_gemm can launch (out[0] of mi355x_gemm_plan: the order is pinned by the golden table of
+// tests/test_gemm_plan_host.py); GK_V8_ES0 + V8_ES_* and GK_V5_STORE + EPI_* are computed
+enum GemmKernel {
+  GK_NONE = -1,
+  GK_S_NT, GK_S_NN, GK_S_TN, GK_S_TT,                            // gemm_bf16_kernel<TA, TB>
+  GK_V2_NT, GK_V2_NT_REG, GK_V2_NN, GK_V2_TN,                    // gemm_bf16_v2_kernel<TA, TB, REG>
+  GK_V4_NT, GK_V4_NT_GA, GK_V4_NN, GK_V4_TN, GK_V4_TN_GB,        // gemm_bf16_v4_kernel<TA, TB, G>
+  GK_V6_0, GK_V6_1,                                              // gemm_bf16_v6_kernel<G>
+  GK_V8_NT, GK_V8_NT_GA, GK_V8_TN, GK_V8_TN_GB,                  // gemm_bf16_v8_kernel<G, TN>
+  GK_V8_ES0 = GK_V8_TN_GB, GK_V8_ES1, GK_V8_ES2, GK_V8_ES3, GK_V8_ES4,  // ... <0, false, 2, V8_ES_*>
+  GK_V8_HALF,                                                    // ... <0, false, 1>: the 128x256 tile
+  GK_V5_STORE, GK_V5_SWISH_DROP, GK_V5_RESID, GK_V5_DSWISH,      // gemm_bf16_v5_kernel<EPI>
+  GK_F32, GK_F32_MFMA,
+  GK_COUNT
+};
+struct GemmPlan {
+  int kernel;                // GemmKernel; GK_NONE: no structure can run the descriptor (MI_ERR_ARG)
+  int gx, gy, gz, block, lds;  // grid, workgroup size, dynamic LDS bytes
+  int v8_delay;              // GemmP::v8_delay of this launch
+  int path;                  // key 11
+  int v5_ntiles, v5_tn;      // the persistent kernel's two extra arguments
+};
+
+static int cdiv(int a, int b) { return (a + b - 1) / b; }
+// split-K normalisation: at most one slice per K-tile, at least min_kt K-tiles a slice, no empty slice
+static int splitk_norm(int nk, int want, int min_kt, int* ktiles_per_split) {
+  int sk = want > 1 ? want : 1;
+  if (sk > nk) sk = nk;
+  *ktiles_per_split = cdiv(nk, sk);
+  if (*ktiles_per_split < min_kt) *ktiles_per_split = min_kt;
+  return cdiv(nk, *ktiles_per_split);
+}
+// wave quantisation: workgroups / (rounds x 256 CUs)
+static double round_eff(long long blocks) { return (double)blocks / (double)(((blocks + 255) / 256) * 256); }
+// <= 12.5 % padded columns with 256-wide tiles
+static bool cols_waste_ok(int N) { return (long long)cdiv(N, 256) * 256 * 8 <= (long long)N * 9; }
+// the larger tile still fills the chip: few padded columns and its wave quantisation does not fall behind the 256x128 tiling
+// (eff_ref) by more than 10 %
+static bool fills_chip(long long blocks, int N, double eff_ref) {
+  return blocks >= 224 && cols_waste_ok(N) && round_eff(blocks) >= 0.9 * eff_ref;
+}
+// rows * pitch elements stay below 2^bits (32-bit byte offsets: 31; the register-prefetch loops: 30)
+static bool off_ok(long long rows, long long ld, int bits) { return rows * ld < (1LL << bits); }
+// dense NT with whole K-tiles (K-contiguous operands, no gather; their 16-byte alignment is gemm_fill's contract)
+static bool dense_nt_whole(const GemmP& p) { return !p.transA && !p.transB && !p.g_on && !(p.K % BK); }
+
+// Argument checks and the kernel arguments (everything but v8_delay, which is the plan's).
+static int gemm_fill(const mi355x_gemm_desc* d, GemmP* out) {
   if (!d || !d->A || !d->B || !d->C || d->M <= 0 || d->N <= 0 || d->K <= 0) return MI_ERR_ARG;
   if (d->in_dtype != MI_DT_F32 && d->in_dtype != MI_DT_BF16) return MI_ERR_ARG;
   // the LDS-DMA source of a reduction-major operand advances by BK * ld elements per k-tile, kept in 32 bits
   if ((d->transA && d->lda * 64 >= (1LL << 31)) || (d->transB && d->ldb * 64 >= (1LL << 31))) return MI_ERR_ARG;
-  GemmP p;
+  GemmP& p = *out;
   p.A = d->A; p.B = d->B; p.C = d->C;
   p.M = d->M; p.N = d->N; p.K = d->K;
   p.lda = d->lda; p.ldb = d->ldb; p.ldc = d->ldc; p.csc = d->c_col_stride > 0 ? d->c_col_stride : 1;
@@ -3305,13 +3374,8 @@ extern "C" int mi355x_gemm(const mi355x_gemm_desc* d, void* stream) {
   if (p.epi == EPI_SWISH_DROP && !p.aux_out) return MI_ERR_ARG;
   if (p.epi == EPI_RELU_MASK && !p.row_len) return MI_ERR_ARG;
   if (p.colsum_out && (!p.transA || d->in_dtype != MI_DT_BF16 || p.nb0 != p.batch)) return MI_ERR_ARG;
-  const int nk = (p.K + BK - 1) / BK;
-  int sk = d->splitk > 1 ? d->splitk : 1;
-  if (sk > nk) sk = nk;
-  if (sk > 1 && !p.atomic) return MI_ERR_ARG;
-  p.ktiles_per_split = (nk + sk - 1) / sk;
-  sk = (nk + p.ktiles_per_split - 1) / p.ktiles_per_split;
-  p.splitk = sk;
+  p.splitk = splitk_norm(cdiv(p.K, BK), d->splitk, 1, &p.ktiles_per_split);
+  if (p.splitk > 1 && !p.atomic) return MI_ERR_ARG;
   {
     // bit 0: 8-column chunks as vectors (f32 rows: two 16-byte accesses, pitch % 4 == 0; bf16 rows: one, pitch % 8 == 0);
     // bit 1: 4-column chunks as vectors (16-byte f32 / 8-byte bf16: pitch % 4 == 0) -- the last columns of a width of 4 modulo 8
@@ -3329,237 +3393,207 @@ extern "C" int mi355x_gemm(const mi355x_gemm_desc* d, void* stream) {
     { const char* e = getenv("MI355X_GEMM_DBG"); if (e) p.vec_ok |= atoi(e) << 8; }
 #endif
   }
-  hipStream_t s = (hipStream_t)stream;
-  if (d->in_dtype == MI_DT_BF16) {
-    // 16-byte alignment contract of the vector loads
-    if ((p.lda & 7) || (p.ldb & 7) || ((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15)) return MI_ERR_ARG;
-    if ((p.sA0 & 7) || (p.sA1 & 7) || (p.sB0 & 7) || (p.sB1 & 7)) return MI_ERR_ARG;
-    // K-contiguous operands are read in 8-element chunks: their pitch must cover roundup8(K) and the pad elements
-    // k in [K, roundup8(K)) must be finite (zero) in memory.  Reduction-major operands need pitch >= roundup8(rows):
-    // a partial chunk's extra columns only feed output rows/cols >= M/N, which are never stored.
-    const int K8 = (p.K + 7) & ~7;
-    if (!p.transA && !p.g_on && p.lda < K8) return MI_ERR_ARG;
-    if (!p.transB && p.ldb < K8) return MI_ERR_ARG;
-    if (p.transA && p.lda < ((p.M + 7) & ~7)) return MI_ERR_ARG;
-    if (p.transB && p.g_on != 2 && p.ldb < ((p.N + 7) & ~7)) return MI_ERR_ARG;
-    const int tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
-    dim3 grid(tm * tn, sk, p.batch);
-    static const int use_v2 = env_int("MI355X_GEMM_V2", 1) ? 1 : 0;
-    if (p.g_on && !(use_v2 && p.M >= 192 && p.N >= 96)) return MI_ERR_ARG;  // the gather lives in the LDS-DMA structures
-    // few output tiles (e.g. M = 8032 rows x N = 512: 128 tiles of 256x128 on 256 CUs): the 128x128 structure doubles the
-    // workgroups and wins in isolation although its K loop is slower (FFN2 forward at M = 8032: 46.3 -> 39.5 us); inside a
-    // training step, next to the weight-gradient stream, it only paid off below ~100 tiles (Squeezeformer-Medium's N = 324
-    // launches at the reduced frame rate: step 47.95 -> 46.95 ms; FastConformer's 128-tile launches: 32.47 -> 32.67 ms)
-    // Round 6: with the vector tail / templated partial-tile epilogue for widths of 4 modulo 8 the 256x128 structure is ahead again
-    // on those launches too (Squeezeformer-Medium 35.68 -> 35.52 ms, same box, twice; Transducer unchanged): default 0 = rule off.
-    static const int few_mode = env_int("MI355X_GEMM_FEW_TILES", 0);
-    const long long blocks256 = (long long)((p.M + BM2 - 1) / BM2) * tn * sk * p.batch;
-    const bool few_tiles = !p.g_on && !p.r_on && !p.atomic && blocks256 <= few_mode && p.N <= 1024 &&
-                           (long long)tm * tn * sk * p.batch > blocks256;
-    if (use_v2 && p.M >= 192 && p.N >= 96 && !(p.transA && !p.transB) && !few_tiles) {
-      const int tm2 = (p.M + BM2 - 1) / BM2;
-      const int shm = 3 * NT2_STAGE * 2;
-      static const bool attr_ok = [shm] {
-        bool ok = hipFuncSetAttribute((const void*)gemm_bf16_v2_kernel<false, false>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, shm) == hipSuccess;
-        ok = ok && hipFuncSetAttribute((const void*)gemm_bf16_v2_kernel<false, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, shm) == hipSuccess;
-        ok = ok && hipFuncSetAttribute((const void*)gemm_bf16_v2_kernel<true, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, shm) == hipSuccess;
-        ok = ok && hipFuncSetAttribute((const void*)gemm_bf16_v2_kernel<false, false, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, shm) == hipSuccess;
-        return ok;
-      }();
-      if (!attr_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
-      dim3 grid2(tm2 * tn, sk, p.batch);
-      // phase-staggered 256x256 structure on 16x16x32 MFMAs (key 8 / MI355X_GEMM_V8: 0 = never, 1 = where it measured faster, 2 = every
-      // shape it can run; 3 = as 1 plus the weight-gradient (TN) layouts, 4 = as 1 plus the wide plain stores the persistent
-      // structure otherwise takes, 5 = as 1 plus the 128x256 tile where 256x256 tiles do not fill the chip and K >= 768 -- A/B arms).  NT: K-contiguous operands, whole K-tiles; TN: both operands reduction-major (K tail
-      // allowed); at least two K-tiles per workgroup, 32-bit operand offsets.
-      // The TN layouts are correct on it but SLOWER than on the lock-step structures (conv2 weight gradient 2.54 vs 2.02 ms, a layer's
-      // grouped weight gradients 307 vs 286 us, profiles/r6_gemm_8phase.md): a fragment is two ds_read_b64_tr_b16, and the 8-byte
-      // reads only reach the LDS rate with both waves of a SIMD reading -- the stagger has one of them reading at a time.
-      {
-        const int v8_mode = mode_now(8);
-        const int nk_wg8 = sk > 1 ? p.ktiles_per_split : nk;
-        const bool nt8 = !p.transA && !p.transB, tn8l = p.transA && p.transB;
-        const int last8 = nk - (sk - 1) * nk_wg8;  // K-tiles of the last slice
-        bool v8_can = (nt8 || tn8l) && nk_wg8 >= 2 && last8 >= 2 && p.N > 128;
-        if (nt8) {
-          v8_can = v8_can && p.g_on != 2 && !(p.K % BK) && (long long)p.N * p.ldb < (1LL << 31);
-          if (p.g_on == 1)  // gathered A: 32-bit byte offsets into the source grid, a K-tile inside one tap
-            v8_can = v8_can && !(p.g_C % BK) && (long long)(p.M / (p.g_nI * p.g_nJ)) * p.g_SI * p.g_SJ * p.g_C < (1LL << 31);
-          else v8_can = v8_can && (long long)p.M * p.lda < (1LL << 31);
-        } else if (tn8l) {
-          v8_can = v8_can && p.g_on != 1 && 64 * p.lda < (1LL << 30) && (p.g_on == 2 || 64 * p.ldb < (1LL << 30));
-        }
-        const int tn8 = (p.N + BN4 - 1) / BN4;
-        const long long blocks8 = (long long)tm2 * tn8 * sk * p.batch;
-        const long long blocks2_ = (long long)tm2 * tn * sk * p.batch;
-        const double eff8 = (double)blocks8 / (double)(((blocks8 + 255) / 256) * 256);
-        const double eff2_ = (double)blocks2_ / (double)(((blocks2_ + 255) / 256) * 256);
-        // the rule of the third structure: the larger tile still fills the chip, few padded columns, no worse wave quantisation
-        const bool fills = blocks8 >= 224 && (long long)tn8 * BN4 * 8 <= (long long)p.N * 9 && eff8 >= 0.9 * eff2_;
-        // (plain stores at least 1536 columns wide with K <= 576 stay on the persistent structure where the 256x256 tiles quantise
-        //  badly: 40.3 vs 41.4 us on the QKV shape, 378 tiles = 1.48 rounds; N = 2048 -- 504 tiles -- is 44.7 vs 53.6 us the other way)
-        const bool v5_keeps = nt8 && !p.g_on && p.epi == EPI_STORE && p.N >= 1536 && nk >= 8 && nk <= 9 && !p.atomic && sk == 1 &&
-                              !(p.N % BN) && v5_mode_now() && v8_mode != 4 && eff8 < 0.85;
-        const bool v8_pick = v8_mode == 2 || (v8_mode >= 1 && fills && !v5_keeps && (nt8 || v8_mode == 3));
-        // the 128x256 tile of the same structure (modes 2 and 5): dense NT problems whose 256x256 tiles would leave the chip
-        // half empty but whose 128x256 tiles fill it (N = 512 at M = 16032: 126 -> 252 workgroups)
-        {
-          const long long blocks1 = (long long)((p.M + 127) / 128) * tn8 * sk * p.batch;
-          const double eff1 = (double)blocks1 / (double)(((blocks1 + 255) / 256) * 256);
-          const bool fills1 = blocks1 >= 224 && (long long)tn8 * BN4 * 8 <= (long long)p.N * 9 && eff1 >= 0.9 * eff2_;
-          // (K >= 768: at K = 512 -- the 512 x 512 projections -- the persistent / 256x128 structures are ahead, 23.6 vs 24.6 us)
-          // Isolated it wins 3-6 % over the 256x128 lock-step structure (FFN2 forward 36.2 -> 34.1 us); INSIDE the training step it
-          // loses 0.16 ms (36.50 vs 36.66 ms, same box, interleaved) -- not in the default set.
-          if (v8_can && nt8 && !p.g_on && !fills && fills1 && ((v8_mode == 5 && nk >= 12) || (v8_mode == 2 && blocks8 < 224))) {
-            static const bool attr81_ok = hipFuncSetAttribute((const void*)gemm_bf16_v8_kernel<0, false, 1>,
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, 9 * V8_HALF_B) == hipSuccess;
-            if (!attr81_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
-            g_last_path = 810;
-            MI_LAUNCH((gemm_bf16_v8_kernel<0, false, 1>), dim3(((p.M + 127) / 128) * tn8, sk, p.batch), dim3(512), 9 * V8_HALF_B, s, p);
-            return mi_check_launch();
-          }
-        }
-        if (v8_can && v8_pick) {
-          typedef void (*v8_fn)(GemmP);
-          static const v8_fn v8_all[] = {gemm_bf16_v8_kernel<0, false>, gemm_bf16_v8_kernel<1, false>, gemm_bf16_v8_kernel<0, true>,
-                                         gemm_bf16_v8_kernel<2, true>,
-                                         gemm_bf16_v8_kernel<0, false, 2, V8_ES_SWISH_G_DROP>, gemm_bf16_v8_kernel<0, false, 2, V8_ES_SWISH_G>,
-                                         gemm_bf16_v8_kernel<0, false, 2, V8_ES_DSWISH_G>, gemm_bf16_v8_kernel<0, false, 2, V8_ES_STORE>};
-          static const bool attr8_ok = [] {
-            for (v8_fn f : v8_all)
-              if (hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * V8_BUF_B) != hipSuccess) return false;
-            return true;
-          }();
-          if (!attr8_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
-          v8_fn fn = nt8 ? v8_all[p.g_on == 1 ? 1 : 0] : v8_all[p.g_on == 2 ? 3 : 2];
-          // key 9: the phase offset (10-ns ticks; > 0: that many for every problem of more than one round and at most 16 K-tiles)
-          if (nt8 && blocks8 > 256 && nk <= 16) p.v8_delay = mode_now(9);
-          // key 10 (MI355X_GEMM_V8_EPI, default 1; 0 = the generic round everywhere, the A/B arm): the kernels with a specialised
-          // epilogue round (separate instantiations: the generic kernel's code does not change with them)
-          int es = 0;
-          if (mode_now(10) && nt8 && !p.g_on && !p.r_on && !p.atomic && sk == 1 && p.csc == 1 && p.c_dt == MI_DT_BF16 && p.ldc < (1 << 24) &&
-              p.ldaux < (1 << 24)) {
-            if (p.epi == EPI_SWISH_DROP && p.swish_g && p.auxout_dt == MI_DT_BF16)
-              es = p.drop.threshold ? V8_ES_SWISH_G_DROP : V8_ES_SWISH_G;
-            else if (p.epi == EPI_DSWISH && p.swish_g && p.auxin_dt == MI_DT_BF16) es = V8_ES_DSWISH_G;
-            else if (p.epi == EPI_STORE && !p.drop.threshold) es = V8_ES_STORE;
-          }
-          if (es) fn = v8_all[3 + es];
-          g_last_path = 800 + es;
-          MI_LAUNCH(fn, dim3(tm2 * tn8, sk, p.batch), dim3(512), 2 * V8_BUF_B, s, p);
-          return mi_check_launch();
-        }
-      }
-      // persistent 256x128 structure with the epilogue overlapped into the next tile's K loop: the Conformer block's
-      // forward / dgrad GEMMs (dense NT, full-width vector epilogue, K >= 8 K-tiles, at least one tile per CU)
-      const int v5_mode = v5_mode_now();
-      // v5_mode 1: where it measured faster than the tiled structures (K <= 576: Swish-gradient, residual, and stores at
-      // least 1536 columns wide); 2: every shape it can run (tests, A/B)
-      const bool v5_epi = (p.epi == EPI_STORE && (v5_mode == 2 || p.N >= 1536)) || (p.epi == EPI_SWISH_DROP && v5_mode == 2) ||
-                          (p.epi == EPI_RESID && p.c_dt == MI_DT_F32) || (p.epi == EPI_DSWISH && p.auxin_dt == MI_DT_BF16);
-      if (v5_mode && !p.transA && !p.transB && !p.g_on && !p.r_on && !p.atomic && p.batch == 1 && sk == 1 && (p.vec_ok & 1) &&
-          !(p.N % BN) && nk >= 8 && (nk <= 9 || v5_mode == 2) && tm2 * tn >= 256 && v5_epi && (long long)p.M * p.lda < (1LL << 31) &&
-          (long long)p.N * p.ldb < (1LL << 31) && (long long)p.M * p.ldc < (1LL << 31) &&
-          (long long)p.M * p.ldaux < (1LL << 31)) {
-        static const bool attr5_ok = [] {
-          bool ok = hipFuncSetAttribute((const void*)gemm_bf16_v5_kernel<EPI_STORE>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, V5_LDS_BYTES) == hipSuccess;
-          ok = ok && hipFuncSetAttribute((const void*)gemm_bf16_v5_kernel<EPI_SWISH_DROP>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, V5_LDS_BYTES) == hipSuccess;
-          ok = ok && hipFuncSetAttribute((const void*)gemm_bf16_v5_kernel<EPI_RESID>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, V5_LDS_BYTES) == hipSuccess;
-          ok = ok && hipFuncSetAttribute((const void*)gemm_bf16_v5_kernel<EPI_DSWISH>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, V5_LDS_BYTES) == hipSuccess;
-          return ok;
-        }();
-        if (!attr5_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
-        const int nt5 = tm2 * tn;
-        dim3 grid5(256);
-        switch (p.epi) {
-          case EPI_STORE: MI_LAUNCH((gemm_bf16_v5_kernel<EPI_STORE>), grid5, dim3(512), V5_LDS_BYTES, s, p, nt5, tn); break;
-          case EPI_SWISH_DROP: MI_LAUNCH((gemm_bf16_v5_kernel<EPI_SWISH_DROP>), grid5, dim3(512), V5_LDS_BYTES, s, p, nt5, tn); break;
-          case EPI_RESID: MI_LAUNCH((gemm_bf16_v5_kernel<EPI_RESID>), grid5, dim3(512), V5_LDS_BYTES, s, p, nt5, tn); break;
-          default: MI_LAUNCH((gemm_bf16_v5_kernel<EPI_DSWISH>), grid5, dim3(512), V5_LDS_BYTES, s, p, nt5, tn); break;
-        }
-        return mi_check_launch();
-      }
-      // 256x256 structure when the problem still fills the chip with the larger tile
-      const int v4_mode = mode_now(4);  // 0 = never, 1 = heuristic (default), 2 = whenever N >= 129
-      const int tn4 = (p.N + BN4 - 1) / BN4;
-      const long long blocks4 = (long long)tm2 * tn4 * sk * p.batch;
-      const bool waste_ok = (long long)tn4 * BN4 * 8 <= (long long)p.N * 9;  // <= 12.5 % padded columns
-      // wave quantisation: workgroups / (rounds x 256 CUs) must not fall behind the 256x128 tiling by more than 10 %
-      const long long blocks2 = (long long)tm2 * tn * sk * p.batch;
-      const double eff4 = (double)blocks4 / (double)(((blocks4 + 255) / 256) * 256);
-      const double eff2 = (double)blocks2 / (double)(((blocks2 + 255) / 256) * 256);
-      if ((v4_mode == 2 && p.N > 128) || (v4_mode == 1 && blocks4 >= 224 && waste_ok && eff4 >= 0.9 * eff2)) {
-        const int shm4 = 2 * NT4_STAGE * 2;
-        // register-prefetch structure (sixth): dense K-contiguous operands, whole K-tiles, 32-bit operand offsets
-        const int v6_mode = mode_now(6);
-        if (v6_mode && !p.transA && !p.transB && !p.g_on && sk == 1 && !(p.K % (2 * BK)) && p.K >= 4 * BK && !(p.lda & 7) && !(p.ldb & 7) &&
-            !((uintptr_t)p.A & 15) && !((uintptr_t)p.B & 15) && (long long)p.M * p.lda < (1LL << 30) &&
-            (long long)p.N * p.ldb < (1LL << 30)) {
-          static const bool attr6_ok = hipFuncSetAttribute((const void*)gemm_bf16_v6_kernel<0>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, shm4) == hipSuccess &&
-                                       hipFuncSetAttribute((const void*)gemm_bf16_v6_kernel<1>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, shm4) == hipSuccess;
-          if (!attr6_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
-          if (v6_mode == 2) MI_LAUNCH((gemm_bf16_v6_kernel<0>), dim3(tm2 * tn4, 1, p.batch), dim3(512), shm4, s, p);
-          else MI_LAUNCH((gemm_bf16_v6_kernel<1>), dim3(tm2 * tn4, 1, p.batch), dim3(512), shm4, s, p);
-          return mi_check_launch();
-        }
-        typedef void (*v4_fn)(GemmP);
-        static const v4_fn v4_all[] = {gemm_bf16_v4_kernel<false, false, 0>, gemm_bf16_v4_kernel<false, false, 1>,
-                                       gemm_bf16_v4_kernel<false, true, 0>, gemm_bf16_v4_kernel<true, true, 0>,
-                                       gemm_bf16_v4_kernel<true, true, 2>};
-        static const bool attr4_ok = [shm4] {
-          for (v4_fn f : v4_all)
-            if (hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, shm4) != hipSuccess) return false;
-          return true;
-        }();
-        if (!attr4_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
-        dim3 grid4(tm2 * tn4, sk, p.batch);
-        v4_fn fn;
-        if (!p.transA && !p.transB) fn = v4_all[p.g_on == 1 ? 1 : 0];
-        else if (!p.transA && p.transB) fn = v4_all[2];
-        else fn = v4_all[p.g_on == 2 ? 4 : 3];
-        MI_LAUNCH(fn, grid4, dim3(512), shm4, s, p);
-      } else
-      if (!p.transA && !p.transB) {
-        // register-prefetch K loop (key 7): dense K-contiguous operands, an even number (>= 4) of whole K-tiles per workgroup
-        const int nk_wg = sk > 1 ? p.ktiles_per_split : nk;
-        const bool reg_ok = mode_now(7) && !p.g_on && !(p.K % BK) && nk_wg >= 4 && !(nk_wg & 1) && (sk == 1 || !(nk % nk_wg)) &&
-                            !(p.lda & 7) && !(p.ldb & 7) && !((uintptr_t)p.A & 15) && !((uintptr_t)p.B & 15) &&
-                            (long long)p.M * p.lda < (1LL << 30) && (long long)p.N * p.ldb < (1LL << 30);
-        if (reg_ok) MI_LAUNCH((gemm_bf16_v2_kernel<false, false, true>), grid2, dim3(512), shm, s, p);
-        else MI_LAUNCH((gemm_bf16_v2_kernel<false, false>), grid2, dim3(512), shm, s, p);
-      } else if (!p.transA && p.transB) MI_LAUNCH((gemm_bf16_v2_kernel<false, true>), grid2, dim3(512), shm, s, p);
-      else MI_LAUNCH((gemm_bf16_v2_kernel<true, true>), grid2, dim3(512), shm, s, p);
-    } else
-    if (!p.transA && !p.transB) MI_LAUNCH((gemm_bf16_kernel<false, false>), grid, dim3(256), 0, s, p);
-    else if (!p.transA && p.transB) MI_LAUNCH((gemm_bf16_kernel<false, true>), grid, dim3(256), 0, s, p);
-    else if (p.transA && p.transB) MI_LAUNCH((gemm_bf16_kernel<true, true>), grid, dim3(256), 0, s, p);
-    else MI_LAUNCH((gemm_bf16_kernel<true, false>), grid, dim3(256), 0, s, p);
-  } else {
-    const int tm = (p.M + 63) / 64, tn = (p.N + 63) / 64;
-    dim3 grid(tm * tn, sk, p.batch);
-    // key 3 / MI355X_F32_MFMA=0 keeps the vector-unit kernel (A/B, and the reference point of tests/test_kernels_gpu.py)
-    if (mode_now(3)) MI_LAUNCH(gemm_f32_mfma_kernel, grid, dim3(256), 0, s, p);
-    else MI_LAUNCH(gemm_f32_kernel, grid, dim3(256), 0, s, p);
+  if (d->in_dtype != MI_DT_BF16) return MI_OK;
+  // 16-byte alignment contract of the vector loads
+  if ((p.lda & 7) || (p.ldb & 7) || ((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15)) return MI_ERR_ARG;
+  if ((p.sA0 & 7) || (p.sA1 & 7) || (p.sB0 & 7) || (p.sB1 & 7)) return MI_ERR_ARG;
+  // K-contiguous operands are read in 8-element chunks: their pitch must cover roundup8(K) and the pad elements
+  // k in [K, roundup8(K)) must be finite (zero) in memory.  Reduction-major operands need pitch >= roundup8(rows):
+  // a partial chunk's extra columns only feed output rows/cols >= M/N, which are never stored.
+  const int K8 = (p.K + 7) & ~7;
+  if (!p.transA && !p.g_on && p.lda < K8) return MI_ERR_ARG;
+  if (!p.transB && p.ldb < K8) return MI_ERR_ARG;
+  if (p.transA && p.lda < ((p.M + 7) & ~7)) return MI_ERR_ARG;
+  if (p.transB && p.g_on != 2 && p.ldb < ((p.N + 7) & ~7)) return MI_ERR_ARG;
+  if (p.g_on && !(p.M >= 192 && p.N >= 96)) return MI_ERR_ARG;  // the gather lives in the LDS-DMA structures
+  return MI_OK;
+}
+
+// Which kernel runs the problem, and with which grid.  Pure: everything it depends on is in p, bf16 (the operand type) and m.
+static GemmPlan gemm_plan(const GemmP& p, bool bf16, const GemmModes& m) {
+  GemmPlan pl = {};
+  auto launch = [&pl](int kernel, long long gx, int gy, int gz, int block, int lds) {
+    pl.kernel = kernel; pl.gx = (int)gx; pl.gy = gy; pl.gz = gz; pl.block = block; pl.lds = lds;
+    return pl;
+  };
+  const int sk = p.splitk, nk = cdiv(p.K, BK);
+  // key 3 / MI355X_F32_MFMA=0 keeps the vector-unit kernel (A/B, and the reference point of tests/test_kernels_gpu.py)
+  if (!bf16) return launch(m.k[3] ? GK_F32_MFMA : GK_F32, cdiv(p.M, 64) * cdiv(p.N, 64), sk, p.batch, 256, 0);
+  const bool nt = !p.transA && !p.transB, tnl = p.transA && p.transB;  // both operands K-contiguous ("NT") / both reduction-major ("TN")
+  const int tm = cdiv(p.M, BM), tn = cdiv(p.N, BN), tm2 = cdiv(p.M, BM2), tn4 = cdiv(p.N, BN4);
+  const long long per_tile = (long long)sk * p.batch;
+  const long long blocks2 = (long long)tm2 * tn * per_tile, blocks4 = (long long)tm2 * tn4 * per_tile;  // workgroups of the 256x128 / 256x256 tilings
+  // few output tiles (e.g. M = 8032 rows x N = 512: 128 tiles of 256x128 on 256 CUs): the 128x128 structure doubles the
+  // workgroups and wins in isolation although its K loop is slower (FFN2 forward at M = 8032: 46.3 -> 39.5 us); inside a
+  // training step, next to the weight-gradient stream, it only paid off below ~100 tiles (Squeezeformer-Medium's N = 324
+  // launches at the reduced frame rate: step 47.95 -> 46.95 ms; FastConformer's 128-tile launches: 32.47 -> 32.67 ms)
+  // Round 6: with the vector tail / templated partial-tile epilogue for widths of 4 modulo 8 the 256x128 structure is ahead again
+  // on those launches too (Squeezeformer-Medium 35.68 -> 35.52 ms, same box, twice; Transducer unchanged): default 0 = rule off.
+  const bool few_tiles = !p.g_on && !p.r_on && !p.atomic && blocks2 <= m.few_tiles && p.N <= 1024 && (long long)tm * tn * per_tile > blocks2;
+  if (!(m.v2 && p.M >= 192 && p.N >= 96 && !(p.transA && !p.transB) && !few_tiles)) {
+    if (p.g_on) return launch(GK_NONE, 0, 0, 0, 0, 0);  // the gather lives in the LDS-DMA structures
+    return launch(p.transA ? (p.transB ? GK_S_TN : GK_S_TT) : (p.transB ? GK_S_NN : GK_S_NT), tm * tn, sk, p.batch, 256, 0);
   }
+  const int nk_wg = sk > 1 ? p.ktiles_per_split : nk;  // K-tiles per workgroup
+  const double eff2 = round_eff(blocks2);
+  const bool fills = fills_chip(blocks4, p.N, eff2);
+  // phase-staggered 256x256 structure on 16x16x32 MFMAs (key 8 / MI355X_GEMM_V8: 0 = never, 1 = where it measured faster, 2 = every
+  // shape it can run; 3 = as 1 plus the weight-gradient (TN) layouts, 4 = as 1 plus the wide plain stores the persistent
+  // structure otherwise takes, 5 = as 1 plus the 128x256 tile where 256x256 tiles do not fill the chip and K >= 768 -- A/B arms).
+  // NT: K-contiguous operands, whole K-tiles; TN: both operands reduction-major (K tail allowed); at least two K-tiles per
+  // workgroup, 32-bit operand offsets.
+  // The TN layouts are correct on it but SLOWER than on the lock-step structures (conv2 weight gradient 2.54 vs 2.02 ms, a layer's
+  // grouped weight gradients 307 vs 286 us, profiles/r6_gemm_8phase.md): a fragment is two ds_read_b64_tr_b16, and the 8-byte
+  // reads only reach the LDS rate with both waves of a SIMD reading -- the stagger has one of them reading at a time.
+  const int v8_mode = m.k[8];
+  bool v8_can = (nt || tnl) && nk_wg >= 2 && nk - (sk - 1) * nk_wg >= 2 /* the last slice too */ && p.N > 128;
+  if (nt) {
+    v8_can = v8_can && p.g_on != 2 && !(p.K % BK) && off_ok(p.N, p.ldb, 31);
+    if (p.g_on == 1)  // gathered A: 32-bit byte offsets into the source grid, a K-tile inside one tap
+      v8_can = v8_can && !(p.g_C % BK) && off_ok((long long)(p.M / (p.g_nI * p.g_nJ)) * p.g_SI * p.g_SJ, p.g_C, 31);
+    else v8_can = v8_can && off_ok(p.M, p.lda, 31);
+  } else if (tnl) {
+    v8_can = v8_can && p.g_on != 1 && off_ok(64, p.lda, 30) && (p.g_on == 2 || off_ok(64, p.ldb, 30));
+  }
+  // (plain stores at least 1536 columns wide with K <= 576 stay on the persistent structure where the 256x256 tiles quantise
+  //  badly: 40.3 vs 41.4 us on the QKV shape, 378 tiles = 1.48 rounds; N = 2048 -- 504 tiles -- is 44.7 vs 53.6 us the other way)
+  const bool v5_keeps = nt && !p.g_on && p.epi == EPI_STORE && p.N >= 1536 && nk >= 8 && nk <= 9 && !p.atomic && sk == 1 &&
+                        !(p.N % BN) && m.k[5] && v8_mode != 4 && round_eff(blocks4) < 0.85;
+  // the 128x256 tile of the same structure (modes 2 and 5): dense NT problems whose 256x256 tiles would leave the chip
+  // half empty but whose 128x256 tiles fill it (N = 512 at M = 16032: 126 -> 252 workgroups)
+  // (K >= 768: at K = 512 -- the 512 x 512 projections -- the persistent / 256x128 structures are ahead, 23.6 vs 24.6 us)
+  // Isolated it wins 3-6 % over the 256x128 lock-step structure (FFN2 forward 36.2 -> 34.1 us); INSIDE the training step it
+  // loses 0.16 ms (36.50 vs 36.66 ms, same box, interleaved) -- not in the default set.
+  if (v8_can && nt && !p.g_on && !fills && fills_chip((long long)tm * tn4 * per_tile, p.N, eff2) &&
+      ((v8_mode == 5 && nk >= 12) || (v8_mode == 2 && blocks4 < 224))) {
+    pl.path = 810;
+    return launch(GK_V8_HALF, tm * tn4, sk, p.batch, 512, 9 * V8_HALF_B);
+  }
+  // the rule of the third structure (fills), unless the persistent structure keeps the shape; TN only in mode 3
+  if (v8_can && (v8_mode == 2 || (v8_mode >= 1 && fills && !v5_keeps && (nt || v8_mode == 3)))) {
+    // key 9: the phase offset (10-ns ticks; > 0: that many for every problem of more than one round and at most 16 K-tiles)
+    if (nt && blocks4 > 256 && nk <= 16) pl.v8_delay = m.k[9];
+    // key 10 (MI355X_GEMM_V8_EPI, default 1; 0 = the generic round everywhere, the A/B arm): the kernels with a specialised
+    // epilogue round (separate instantiations: the generic kernel's code does not change with them)
+    int es = 0;
+    if (m.k[10] && nt && !p.g_on && !p.r_on && !p.atomic && sk == 1 && p.csc == 1 && p.c_dt == MI_DT_BF16 && p.ldc < (1 << 24) &&
+        p.ldaux < (1 << 24)) {
+      if (p.epi == EPI_SWISH_DROP && p.swish_g && p.auxout_dt == MI_DT_BF16) es = p.drop.threshold ? V8_ES_SWISH_G_DROP : V8_ES_SWISH_G;
+      else if (p.epi == EPI_DSWISH && p.swish_g && p.auxin_dt == MI_DT_BF16) es = V8_ES_DSWISH_G;
+      else if (p.epi == EPI_STORE && !p.drop.threshold) es = V8_ES_STORE;
+    }
+    pl.path = 800 + es;
+    const int generic = nt ? (p.g_on == 1 ? GK_V8_NT_GA : GK_V8_NT) : (p.g_on == 2 ? GK_V8_TN_GB : GK_V8_TN);
+    return launch(es ? GK_V8_ES0 + es : generic, tm2 * tn4, sk, p.batch, 512, 2 * V8_BUF_B);
+  }
+  // persistent 256x128 structure with the epilogue overlapped into the next tile's K loop: the Conformer block's
+  // forward / dgrad GEMMs (dense NT, full-width vector epilogue, K >= 8 K-tiles, at least one tile per CU)
+  // v5_mode 1: where it measured faster than the tiled structures (K <= 576: Swish-gradient, residual, and stores at
+  // least 1536 columns wide); 2: every shape it can run (tests, A/B)
+  const int v5_mode = m.k[5];
+  const bool v5_epi = (p.epi == EPI_STORE && (v5_mode == 2 || p.N >= 1536)) || (p.epi == EPI_SWISH_DROP && v5_mode == 2) ||
+                      (p.epi == EPI_RESID && p.c_dt == MI_DT_F32) || (p.epi == EPI_DSWISH && p.auxin_dt == MI_DT_BF16);
+  if (v5_mode && nt && !p.g_on && !p.r_on && !p.atomic && p.batch == 1 && sk == 1 && (p.vec_ok & 1) && !(p.N % BN) && nk >= 8 &&
+      (nk <= 9 || v5_mode == 2) && tm2 * tn >= 256 && v5_epi && off_ok(p.M, p.lda, 31) && off_ok(p.N, p.ldb, 31) &&
+      off_ok(p.M, p.ldc, 31) && off_ok(p.M, p.ldaux, 31)) {
+    pl.v5_ntiles = tm2 * tn; pl.v5_tn = tn;
+    return launch(GK_V5_STORE + p.epi, 256, 1, 1, 512, V5_LDS_BYTES);
+  }
+  // 256x256 structure when the problem still fills the chip with the larger tile (key 4: 0 = never, 1 = heuristic, 2 = N >= 129)
+  if ((m.k[4] == 2 && p.N > 128) || (m.k[4] == 1 && fills)) {
+    // register-prefetch structure (sixth): an even number (>= 4) of whole K-tiles, 30-bit operand offsets
+    if (m.k[6] && dense_nt_whole(p) && sk == 1 && !(p.K % (2 * BK)) && p.K >= 4 * BK && off_ok(p.M, p.lda, 30) && off_ok(p.N, p.ldb, 30))
+      return launch(m.k[6] == 2 ? GK_V6_0 : GK_V6_1, tm2 * tn4, 1, p.batch, 512, 2 * NT4_STAGE * 2);
+    const int k4 = nt ? (p.g_on == 1 ? GK_V4_NT_GA : GK_V4_NT) : !p.transA ? GK_V4_NN : (p.g_on == 2 ? GK_V4_TN_GB : GK_V4_TN);
+    return launch(k4, tm2 * tn4, sk, p.batch, 512, 2 * NT4_STAGE * 2);
+  }
+  // 256x128 structure, the default.  Register-prefetch K loop (key 7): an even number (>= 4) of whole K-tiles per workgroup
+  const bool reg_ok = m.k[7] && dense_nt_whole(p) && nk_wg >= 4 && !(nk_wg & 1) && (sk == 1 || !(nk % nk_wg)) &&
+                      off_ok(p.M, p.lda, 30) && off_ok(p.N, p.ldb, 30);
+  return launch(nt ? (reg_ok ? GK_V2_NT_REG : GK_V2_NT) : !p.transA ? GK_V2_NN : GK_V2_TN, tm2 * tn, sk, p.batch, 512, 3 * NT2_STAGE * 2);
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize once per kernel (state: 0 = not yet, 1 = set, 2 = refused; setting it twice from two
+// threads is harmless), only for kernels that ask for dynamic LDS at all
+static bool lds_attr_once(std::atomic<int>& state, const void* fn, int lds) {
+  int s = state.load(std::memory_order_acquire);
+  if (!s && lds > 0) {
+    s = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess ? 1 : 2;
+    state.store(s, std::memory_order_release);
+  }
+  return s != 2;
+}
+
+typedef void (*gemm_fn)(GemmP);
+typedef void (*gemm_v5_fn)(GemmP, int, int);
+static int gemm_launch(const GemmPlan& pl, const GemmP& p, hipStream_t s) {
+  static const void* const kernels[GK_COUNT] = {  // in the order of GemmKernel
+      (const void*)gemm_bf16_kernel<false, false>, (const void*)gemm_bf16_kernel<false, true>, (const void*)gemm_bf16_kernel<true, true>,
+      (const void*)gemm_bf16_kernel<true, false>,
+      (const void*)gemm_bf16_v2_kernel<false, false>, (const void*)gemm_bf16_v2_kernel<false, false, true>,
+      (const void*)gemm_bf16_v2_kernel<false, true>, (const void*)gemm_bf16_v2_kernel<true, true>,
+      (const void*)gemm_bf16_v4_kernel<false, false, 0>, (const void*)gemm_bf16_v4_kernel<false, false, 1>,
+      (const void*)gemm_bf16_v4_kernel<false, true, 0>, (const void*)gemm_bf16_v4_kernel<true, true, 0>,
+      (const void*)gemm_bf16_v4_kernel<true, true, 2>,
+      (const void*)gemm_bf16_v6_kernel<0>, (const void*)gemm_bf16_v6_kernel<1>,
+      (const void*)gemm_bf16_v8_kernel<0, false>, (const void*)gemm_bf16_v8_kernel<1, false>, (const void*)gemm_bf16_v8_kernel<0, true>,
+      (const void*)gemm_bf16_v8_kernel<2, true>,
+      (const void*)gemm_bf16_v8_kernel<0, false, 2, V8_ES_SWISH_G_DROP>, (const void*)gemm_bf16_v8_kernel<0, false, 2, V8_ES_SWISH_G>,
+      (const void*)gemm_bf16_v8_kernel<0, false, 2, V8_ES_DSWISH_G>, (const void*)gemm_bf16_v8_kernel<0, false, 2, V8_ES_STORE>,
+      (const void*)gemm_bf16_v8_kernel<0, false, 1>,
+      (const void*)gemm_bf16_v5_kernel<EPI_STORE>, (const void*)gemm_bf16_v5_kernel<EPI_SWISH_DROP>,
+      (const void*)gemm_bf16_v5_kernel<EPI_RESID>, (const void*)gemm_bf16_v5_kernel<EPI_DSWISH>,
+      (const void*)gemm_f32_kernel, (const void*)gemm_f32_mfma_kernel};
+  static std::atomic<int> attr[GK_COUNT];
+  const void* fn = kernels[pl.kernel];
+  if (!lds_attr_once(attr[pl.kernel], fn, pl.lds)) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
+  // the persistent kernel's two extra arguments are the one signature difference
+  auto issue = [&](auto kernel, auto... more) { MI_LAUNCH(kernel, dim3(pl.gx, pl.gy, pl.gz), dim3(pl.block), pl.lds, s, p, more...); };
+  if (pl.kernel >= GK_V5_STORE && pl.kernel <= GK_V5_DSWISH) issue((gemm_v5_fn)fn, pl.v5_ntiles, pl.v5_tn);
+  else issue((gemm_fn)fn);
+  return MI_OK;
+}
+
+extern "C" int mi355x_gemm(const mi355x_gemm_desc* d, void* stream) {
+  mi_clear_errors();
+  g_last_path = 0;
+  GemmP p;
+  int rc = gemm_fill(d, &p);
+  if (rc != MI_OK) return rc;
+  const GemmPlan pl = gemm_plan(p, d->in_dtype == MI_DT_BF16, gemm_modes_now());
+  if (pl.kernel == GK_NONE) return MI_ERR_ARG;
+  p.v8_delay = pl.v8_delay;
+  rc = gemm_launch(pl, p, (hipStream_t)stream);
+  if (rc != MI_OK) return rc;
+  g_last_path = pl.path;
   return mi_check_launch();
 }
 
-extern "C" int mi355x_gemm_grouped(const mi355x_gemm_desc* descs, int n, void* stream) {
-  mi_clear_errors();
-  if (!descs || n < 1 || n > GRP_MAX) return MI_ERR_ARG;
-  GroupP g;
-  g.n = n; g.K = descs[0].K;
+// The plan of a descriptor under the current modes; launches nothing and does not touch the GPU.
+extern "C" int mi355x_gemm_plan(const mi355x_gemm_desc* d, int out[8]) {
+  GemmP p;
+  const int rc = gemm_fill(d, &p);
+  if (rc != MI_OK) return rc;
+  const GemmPlan pl = gemm_plan(p, d->in_dtype == MI_DT_BF16, gemm_modes_now());
+  if (pl.kernel == GK_NONE) return MI_ERR_ARG;
+  const int v[8] = {pl.kernel, pl.path, pl.gx, pl.gy, pl.gz, pl.block, pl.lds, pl.v8_delay};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return MI_OK;
+}
+
+// Tile list of a group for 256 x bn tiles (prefix sums in g.tile_begin); returns the tile count.
+static int group_tiles(GroupP& g, int bn) {
   int tiles = 0;
+  for (int i = 0; i <= GRP_MAX; ++i) {
+    g.tile_begin[i] = tiles;
+    if (i < g.n) tiles += cdiv(g.M[i], BM2) * cdiv(g.N[i], bn);
+  }
+  return tiles;
+}
+static int group_fill(const mi355x_gemm_desc* descs, int n, GroupP* out) {
+  if (!descs || n < 1 || n > GRP_MAX) return MI_ERR_ARG;
+  GroupP& g = *out;
+  g.n = n; g.K = descs[0].K;
   for (int i = 0; i < n; ++i) {
     const mi355x_gemm_desc& d = descs[i];
     if (!d.A || !d.B || !d.C || d.M <= 0 || d.N <= 0 || d.K != g.K || d.K <= 0) return MI_ERR_ARG;
@@ -3570,66 +3604,46 @@ extern "C" int mi355x_gemm_grouped(const mi355x_gemm_desc* descs, int n, void* s
     if (d.lda < ((d.M + 7) & ~7) || d.ldb < ((d.N + 7) & ~7)) return MI_ERR_ARG;
     g.A[i] = d.A; g.B[i] = d.B; g.C[i] = d.C; g.colsum[i] = (float*)d.colsum_out;
     g.M[i] = d.M; g.N[i] = d.N; g.lda[i] = d.lda; g.ldb[i] = d.ldb; g.ldc[i] = d.ldc;
-    g.tile_begin[i] = tiles;
-    tiles += ((d.M + BM2 - 1) / BM2) * ((d.N + BN - 1) / BN);
   }
-  for (int i = n; i <= GRP_MAX; ++i) g.tile_begin[i] = tiles;
-  const int nk = (g.K + BK - 1) / BK;
-  int sk = descs[0].splitk > 1 ? descs[0].splitk : 1;
-  if (sk > nk) sk = nk;
-  // eighth structure (key 8 modes 2 and 3 only: slower than this one on the reduction-major layouts, see mi355x_gemm): 256x256 tiles --
-  // half as many as the caller's split-K factor was chosen for, so the factor is chosen again here by the same rule (whole rounds
-  // of the 256 CUs, smaller factors preferred, >= 16 K-tiles a slice)
-  const int v8_mode = mode_now(8);
-  if ((v8_mode == 2 || v8_mode == 3) && nk >= 4) {
-    bool ok8 = true;
-    int tiles8 = 0;
-    for (int i = 0; i < n; ++i) {
-      ok8 = ok8 && descs[i].N > 128 && 64 * descs[i].lda < (1LL << 30) && 64 * descs[i].ldb < (1LL << 30);
-      g.tile_begin[i] = tiles8;
-      tiles8 += ((descs[i].M + BM2 - 1) / BM2) * ((descs[i].N + BN4 - 1) / BN4);
+  return MI_OK;
+}
+// Chooses the kernel (returns 1 for gemm_bf16_grouped_tn8_kernel, 0 for gemm_bf16_grouped_tn_kernel) and fills the tile list and
+// the split of g; *tiles = the grid's x.
+static int group_plan(GroupP& g, int want_sk, int v8_mode, int* tiles) {
+  const int nk = cdiv(g.K, BK);
+  // eighth structure (key 8 modes 2 and 3 only: slower than the 256x128 one on the reduction-major layouts, see gemm_plan): 256x256
+  // tiles -- half as many as the caller's split-K factor was chosen for, so the factor is chosen again here by the same rule
+  // (whole rounds of the 256 CUs, smaller factors preferred, >= 16 K-tiles a slice)
+  bool ok8 = (v8_mode == 2 || v8_mode == 3) && nk >= 4;
+  for (int i = 0; i < g.n; ++i) ok8 = ok8 && g.N[i] > 128 && off_ok(64, g.lda[i], 30) && off_ok(64, g.ldb[i], 30);
+  if (ok8) {
+    *tiles = group_tiles(g, BN4);
+    int best = 1;
+    double best_score = -1.0;
+    for (int c = 1; c <= 16; ++c) {
+      if (c > 1 && nk / c < 16) break;
+      const double score = round_eff((long long)*tiles * c) - 0.01 * c;
+      if (score > best_score + 1e-9) { best = c; best_score = score; }
     }
-    if (ok8) {
-      for (int i = n; i <= GRP_MAX; ++i) g.tile_begin[i] = tiles8;
-      int best = 1;
-      double best_score = -1.0;
-      for (int c = 1; c <= 16; ++c) {
-        if (c > 1 && nk / c < 16) break;
-        const long long blocks = (long long)tiles8 * c;
-        const double score = (double)blocks / (double)(((blocks + 255) / 256) * 256) - 0.01 * c;
-        if (score > best_score + 1e-9) { best = c; best_score = score; }
-      }
-      if (sk > 1) sk = best;
-      g.ktiles_per_split = (nk + sk - 1) / sk;
-      if (g.ktiles_per_split < 2) { g.ktiles_per_split = 2; }
-      sk = (nk + g.ktiles_per_split - 1) / g.ktiles_per_split;
-      if (nk - (sk - 1) * g.ktiles_per_split >= 2) {  // (every slice needs two K-tiles)
-        g.splitk = sk;
-        static const bool attr8g_ok = hipFuncSetAttribute((const void*)gemm_bf16_grouped_tn8_kernel,
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, 2 * V8_BUF_B) == hipSuccess;
-        if (!attr8g_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
-        MI_LAUNCH(gemm_bf16_grouped_tn8_kernel, dim3(tiles8, sk, 1), dim3(512), 2 * V8_BUF_B, (hipStream_t)stream, g);
-        return mi_check_launch();
-      }
-    }
-    // not taken: the tile list of the 256x128 structure again
-    tiles = 0;
-    for (int i = 0; i < n; ++i) {
-      g.tile_begin[i] = tiles;
-      tiles += ((descs[i].M + BM2 - 1) / BM2) * ((descs[i].N + BN - 1) / BN);
-    }
-    for (int i = n; i <= GRP_MAX; ++i) g.tile_begin[i] = tiles;
-    sk = descs[0].splitk > 1 ? descs[0].splitk : 1;
-    if (sk > nk) sk = nk;
+    g.splitk = splitk_norm(nk, want_sk > 1 ? best : 1, 2, &g.ktiles_per_split);
+    if (nk - (g.splitk - 1) * g.ktiles_per_split >= 2) return 1;  // (every slice needs two K-tiles)
   }
-  g.ktiles_per_split = (nk + sk - 1) / sk;
-  sk = (nk + g.ktiles_per_split - 1) / g.ktiles_per_split;
-  g.splitk = sk;
-  const int shm = 3 * NT2_STAGE * 2;
-  static const bool attr_ok = hipFuncSetAttribute((const void*)gemm_bf16_grouped_tn_kernel,
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, shm) == hipSuccess;
-  if (!attr_ok) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
-  MI_LAUNCH(gemm_bf16_grouped_tn_kernel, dim3(tiles, sk, 1), dim3(512), shm, (hipStream_t)stream, g);
-  return mi_check_launch();
+  *tiles = group_tiles(g, BN);
+  g.splitk = splitk_norm(nk, want_sk, 1, &g.ktiles_per_split);
+  return 0;
 }
 
+extern "C" int mi355x_gemm_grouped(const mi355x_gemm_desc* descs, int n, void* stream) {
+  mi_clear_errors();
+  GroupP g;
+  const int rc = group_fill(descs, n, &g);
+  if (rc != MI_OK) return rc;
+  int tiles = 0;
+  const int k8 = group_plan(g, descs[0].splitk, mode_now(8), &tiles);
+  static void (*const kernels[2])(GroupP) = {gemm_bf16_grouped_tn_kernel, gemm_bf16_grouped_tn8_kernel};
+  static std::atomic<int> attr[2];
+  const int lds = k8 ? 2 * V8_BUF_B : 3 * NT2_STAGE * 2;
+  if (!lds_attr_once(attr[k8], (const void*)kernels[k8], lds)) { (void)hipGetLastError(); return MI_ERR_LAUNCH; }
+  MI_LAUNCH(kernels[k8], dim3(tiles, g.splitk, 1), dim3(512), lds, (hipStream_t)stream, g);
+  return mi_check_launch();
+}

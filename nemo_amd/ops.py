@@ -5,6 +5,7 @@ torch is used for device memory, streams and torch.distributed only.  Every func
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -58,8 +59,32 @@ GEMM_PROFILE = None
 
 def gemm_config(key: int, value: int) -> int:
     """kernel-structure knob (tests / A-B benchmarks), see mi355x_gemm_config in include/mi355x_asr.h: key 3 = fp32 problems on the
-    matrix cores (1 default / 0 vector unit), key 5 = persistent overlapped-epilogue GEMM (0 off / 1 default), ..."""
+    matrix cores (1 default / 0 vector unit), key 5 = persistent overlapped-epilogue GEMM (0 off / 1 default), ...
+    Returns the previous effective value (>= 0): writing it back restores the earlier state."""
     return lib.mi355x_gemm_config(key, value)
+
+
+@contextlib.contextmanager
+def gemm_modes(modes=None, **kv):
+    """`with gemm_modes({8: 2, 5: 0}):` or `with gemm_modes(k8=2, k5=0):` -- gemm_config keys set for the block, the earlier values
+    written back on exit"""
+    modes = {**(modes or {}), **{int(k[1:]): v for k, v in kv.items()}}
+    old = {}
+    try:
+        for k, v in modes.items():
+            old[k] = gemm_config(k, v)
+        yield
+    finally:
+        for k, v in old.items():
+            gemm_config(k, v)
+
+
+def gemm_plan(desc: GemmDesc):
+    """(rc, [kernel id, key-11 code, grid x, y, z, workgroup size, dynamic LDS bytes, key-9 delay]) of the launch mi355x_gemm would
+    make for `desc` under the current gemm_config modes -- see mi355x_gemm_plan; nothing is launched and no GPU is needed"""
+    out = (C.c_int * 8)()
+    rc = lib.mi355x_gemm_plan(C.byref(desc), C.byref(out))
+    return rc, list(out)
 
 
 # value added to the device-side step word per training step (odd: the word walks through all 2^32 values)

@@ -35,20 +35,6 @@ def rel_l2(a, b):
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
-class _modes:
-    def __init__(self, **kv):
-        self.kv = {int(k[1:]): v for k, v in kv.items()}
-
-    def __enter__(self):
-        o = ops()
-        self.old = {k: o.gemm_config(k, v) for k, v in self.kv.items()}
-
-    def __exit__(self, *a):
-        o = ops()
-        for k, v in self.old.items():
-            o.gemm_config(k, v if v >= 0 else (0 if k == 6 else 1))
-
-
 def _sig(x):
     return 1.0 / (1.0 + torch.exp(-x))
 
@@ -127,11 +113,11 @@ def test_every_epilogue_kind_matches_the_lock_step_structure_and_fp32(M, N, K):
             for drop in (None, o.Dropout(0.1, 11, 5)):
                 if drop is not None and kind in ("relu_mask", "mul_pos"):
                     continue  # (these two kinds have no dropout)
-                with _modes(k8=0, k4=2, k5=0, k6=0):   # the lock-step 256x256 structure
+                with ops().gemm_modes(k8=0, k4=2, k5=0, k6=0):   # the lock-step 256x256 structure
                     want = run(kind, cdt, drop)
                     assert o.gemm_config(11, 0) == 0
                 for spec in (0, 1):                    # the generic round everywhere / specialised rounds where the dispatcher has one
-                    with _modes(k8=2, k5=0, k10=spec):
+                    with ops().gemm_modes(k8=2, k5=0, k10=spec):
                         for rep in range(3):
                             got = run(kind, cdt, drop)
                             path = o.gemm_config(11, 0)

@@ -24,22 +24,6 @@ def rel_l2(a, b):
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
-class _modes:
-    """mi355x_gemm_config keys set for the duration of a `with` block, previous values restored"""
-
-    def __init__(self, **kv):
-        self.kv = {int(k[1:]): v for k, v in kv.items()}
-
-    def __enter__(self):
-        o = ops()
-        self.old = {k: o.gemm_config(k, v) for k, v in self.kv.items()}
-
-    def __exit__(self, *a):
-        o = ops()
-        for k, v in self.old.items():
-            o.gemm_config(k, v if v >= 0 else (0 if k == 6 else 1))
-
-
 @pytest.mark.parametrize("M,N,K", [(16032, 2048, 512), (3000, 520, 256), (5000, 1280, 2048), (777, 384, 1024), (300, 1536, 128),
                                    (8200, 1024, 576)])
 def test_phase_staggered_structure_is_bit_identical_to_the_lock_step_one(M, N, K):
@@ -78,9 +62,9 @@ def test_phase_staggered_structure_is_bit_identical_to_the_lock_step_one(M, N, K
         return (c,)
 
     for kind in ("store_f32", "store", "swish", "resid", "dswish"):
-        with _modes(k8=0, k4=2, k5=0, k6=0):   # the third structure (256x256, lock step) wherever N > 128
+        with ops().gemm_modes(k8=0, k4=2, k5=0, k6=0):   # the third structure (256x256, lock step) wherever N > 128
             want = run(kind)
-        with _modes(k8=2, k5=0):
+        with ops().gemm_modes(k8=2, k5=0):
             for rep in range(3):
                 got = run(kind)
                 torch.cuda.synchronize()
@@ -117,9 +101,9 @@ def test_one_a_half_tile_of_the_phase_staggered_structure(M, N, K):
         return c
 
     for kind in ("store", "store_f32", "resid"):
-        with _modes(k8=0, k4=0, k5=0, k7=0):   # the 256x128 lock-step structure (LDS-DMA K loop)
+        with ops().gemm_modes(k8=0, k4=0, k5=0, k7=0):   # the 256x128 lock-step structure (LDS-DMA K loop)
             want = run(kind)
-        with _modes(k8=2, k5=0):
+        with ops().gemm_modes(k8=2, k5=0):
             for rep in range(3):
                 got = run(kind)
                 torch.cuda.synchronize()
@@ -135,7 +119,7 @@ def test_phase_staggered_structure_split_k_slices_and_batches():
     A = (torch.rand(nb, M, K, generator=g) * 2 - 1).to(bf16).to(dev)
     W = ((torch.rand(nb, N, K, generator=g) * 2 - 1) * 0.1).to(bf16).to(dev)
     ref = torch.einsum("bmk,bnk->bmn", A.float(), W.float())
-    with _modes(k8=2):
+    with ops().gemm_modes(k8=2):
         for sk in (1, 4):
             c = torch.zeros(nb, M, N, device=dev)
             o.gemm(A, W, c, M, N, K, K, K, N, batch=nb, sA=(M * K, 0), sB=(N * K, 0), sC=(M * N, 0), atomic=sk > 1, splitk=sk,
@@ -192,9 +176,9 @@ def test_phase_staggered_structure_gathered_convolution():
                c_col_stride=9, c_dtype=o.F32, gather=dict(operand=1, nI=T2, nJ=F2, SI=T1, SJ=F1, C=C_, si=2, sj=2, taps=taps), **kw_)
         return dW
 
-    with _modes(k8=0, k4=2):
+    with ops().gemm_modes(k8=0, k4=2):
         want_f, want_d, want_w = forward(), dgrad(), wgrad(True)
-    with _modes(k8=2):
+    with ops().gemm_modes(k8=2):
         for rep in range(3):
             got_f, got_d = forward(), dgrad()
             torch.cuda.synchronize()
@@ -221,7 +205,7 @@ def test_phase_staggered_structure_weight_gradient_layouts(M, N, K, sk):
     X = (torch.rand(K, ldb, generator=g) * 2 - 1).to(bf16).to(dev)
     ref = dY[:, :M].float().t() @ X[:, :N].float()
     refb = dY[:, :M].float().sum(0)
-    with _modes(k8=2):
+    with ops().gemm_modes(k8=2):
         for rep in range(2):
             dW = torch.zeros(M, N, device=dev)
             db = torch.zeros(M, device=dev)
@@ -245,7 +229,7 @@ def test_phase_staggered_structure_grouped_weight_gradients():
         db = torch.full((no,), -1.0, device=dev)
         probs.append((dY, no, 0, X, ni, 0, dW, no, ni, db))
         refs.append((0.5 + dY.float().t() @ X.float(), -1.0 + dY.float().sum(0)))
-    with _modes(k8=3):
+    with ops().gemm_modes(k8=3):
         o.wgrad_grouped(probs, rows, 4)
         torch.cuda.synchronize()
     for q, (rw, rb) in zip(probs, refs):

@@ -76,16 +76,13 @@ def test_gemm_f32_on_the_matrix_cores_matches_the_vector_unit_kernel(layout, sha
     Ast, lda = (A.t().contiguous(), M) if tA else (A, K)
     Bst, ldb = (Bm.t().contiguous(), N) if tB else (Bm, K)
     errs = {}
-    prev = o.gemm_config(3, 1)
-    try:
+    with o.gemm_modes({3: 1}):
         for mode in (1, 0):
             o.gemm_config(3, mode)
             Cd = torch.full((M, N), float("nan"), device=dev)
             o.gemm(Ast.to(dev), Bst.to(dev), Cd, M, N, K, lda, ldb, N, transA=tA, transB=tB)
             torch.cuda.synchronize()
             errs[mode] = ((Cd.double().cpu() - ref).abs().max() / ref.abs().max()).item()
-    finally:
-        o.gemm_config(3, prev if prev >= 0 else 1)
     assert errs[1] < 2e-6 and errs[0] < 2e-6, errs
     assert errs[1] < 4 * errs[0] + 1e-7, errs
 
@@ -99,8 +96,7 @@ def test_gemm_f32_on_the_matrix_cores_epilogues_batch_and_split_k():
     bias = torch.randn(N, generator=g); res = torch.randn(nb, M, N, generator=g)
     want = res + 0.5 * (torch.einsum("bmk,bnk->bmn", A.double(), Bm.double()) + bias.double())
     got = {}
-    prev = o.gemm_config(3, 1)
-    try:
+    with o.gemm_modes({3: 1}):
         for mode in (1, 0):
             o.gemm_config(3, mode)
             Cd = torch.full((nb, M, N), float("nan"), device=dev)
@@ -120,8 +116,6 @@ def test_gemm_f32_on_the_matrix_cores_epilogues_batch_and_split_k():
             o.gemm(X.to(dev), Y.to(dev), Cd, M2, N2, K2, M2, N2, N2, transA=True, transB=True, atomic=True, splitk=4)
             torch.cuda.synchronize()
             assert ((Cd.double().cpu() - want2).abs().max() / want2.abs().max()).item() < 5e-6, mode
-    finally:
-        o.gemm_config(3, prev if prev >= 0 else 1)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -1502,8 +1496,7 @@ def test_gemm_persistent_structure_matches_the_tiled_one(M, N, K):
         o.gemm(A, W, c, M, N, K, K, K, N, epi=o.EPI_DSWISH, aux_in=pre, drop=drop)
         return (c,)
 
-    old = o.gemm_config(5, 1)
-    try:
+    with o.gemm_modes({5: 1}):
         for kind in ("store", "store_f32", "swish", "resid", "resid_inplace", "dswish"):
             o.gemm_config(5, 0)
             want = [t.float() for t in run(kind)]
@@ -1520,8 +1513,6 @@ def test_gemm_persistent_structure_matches_the_tiled_one(M, N, K):
                 torch.cuda.synchronize()
                 for t, f in zip(again, first):
                     assert torch.equal(t, f), (kind, "run-to-run difference")
-    finally:
-        o.gemm_config(5, old if old >= 0 else 1)
 
 
 @pytest.mark.parametrize("V1,ldp", [(1025, 1032), (29, 32), (16, 16)])
@@ -1587,8 +1578,7 @@ def test_gemm_register_prefetch_structure_matches_the_lds_dma_one(M, N, K, tile)
 
     # tile 256: the 256x256 structure wherever N > 128; tile 128: the 256x128 structure everywhere; never the persistent one
     key = 6 if tile == 256 else 7
-    old4, old5, old6 = o.gemm_config(4, 2 if tile == 256 else 0), o.gemm_config(5, 0), o.gemm_config(key, 0)
-    try:
+    with o.gemm_modes({4: 2 if tile == 256 else 0, 5: 0, key: 0}):
         for kind in ("store", "swish", "resid"):
             o.gemm_config(key, 0)
             want = [t.float() for t in run(kind)]
@@ -1600,5 +1590,3 @@ def test_gemm_register_prefetch_structure_matches_the_lds_dma_one(M, N, K, tile)
                     assert torch.equal(w_, g_), (kind, rep, (w_ - g_).abs().max().item())
             if kind == "store":
                 assert rel_err(got[0], ref) < 1e-2
-    finally:
-        o.gemm_config(4, old4 if old4 >= 0 else 1); o.gemm_config(5, old5 if old5 >= 0 else 1); o.gemm_config(key, old6 if old6 >= 0 else 1)

@@ -167,8 +167,7 @@ def test_relu_mask_gemm_skips_tiles_beyond_the_utterance(v4):
     in fp32 on bf16-rounded operands: utterances that end inside a tile, on a tile edge, at zero length and at full length;
     poisoned output buffer (a skipped tile that forgot to write shows as NaN)."""
     from nemo_amd import ops as o
-    prev = o.gemm_config(4, v4)
-    try:
+    with o.gemm_modes({4: v4}):
         g = torch.Generator().manual_seed(3)
         B, T, F_in, N, K = 6, 1040, 16, 256, 128     # rows (b, t, f): 16 640 per utterance = 65 tiles of 256 rows
         M = B * T * F_in
@@ -188,5 +187,3 @@ def test_relu_mask_gemm_skips_tiles_beyond_the_utterance(v4):
         assert torch.isfinite(got).all()
         assert (got - ref).abs().max() <= 2e-2 * ref.abs().max()
         assert (got[ref == 0] == 0).all()
-    finally:
-        o.gemm_config(4, prev)

@@ -26,16 +26,7 @@ def rel_err(a, b):
 
 
 def set_modes(v8, v4=None, v5=None, v6=None, v7=None):
-    old = {8: ops.gemm_config(8, v8)}
-    for k, v in ((4, v4), (5, v5), (6, v6), (7, v7)):
-        if v is not None:
-            old[k] = ops.gemm_config(k, v)
-    return old
-
-
-def restore(old):
-    for k, v in old.items():
-        ops.gemm_config(k, v if v >= 0 else (0 if k == 6 else 1))
+    return ops.gemm_modes({k: v for k, v in ((8, v8), (4, v4), (5, v5), (6, v6), (7, v7)) if v is not None})
 
 
 def check():
@@ -53,8 +44,7 @@ def check():
         for kind in ("store", "store_f32", "swish", "resid"):
             outs = {}
             for mode in (0, 2):
-                old = set_modes(mode, v5=0)
-                try:
+                with set_modes(mode, v5=0):
                     if kind == "store":
                         c = torch.empty(M, N, device=dev, dtype=bf)
                         ops.gemm(A, W, c, M, N, K, K, K, N, bias=bias)
@@ -74,8 +64,6 @@ def check():
                         o = (c,)
                     torch.cuda.synchronize()
                     outs[mode] = o
-                finally:
-                    restore(old)
             errs = [rel_err(x, y) for x, y in zip(outs[2], outs[0])]
             line = f"check M={M} N={N} K={K} {kind:9s} v8-vs-old rel {max(errs):.2e}"
             if kind in ("store", "store_f32"):
@@ -91,8 +79,7 @@ def check():
                 line += "  <-- BAD"
             # race screen: the same launch again, several times, bit for bit
             if kind == "store_f32":
-                old = set_modes(2, v5=0)
-                try:
+                with set_modes(2, v5=0):
                     for rep in range(6):
                         c2 = torch.empty(M, N, device=dev)
                         ops.gemm(A, W, c2, M, N, K, K, K, N, bias=bias)
@@ -101,8 +88,6 @@ def check():
                             bad += 1
                             line += f"  <-- RUN-TO-RUN DIFFERENCE (rep {rep}, {(c2 - outs[2][0]).abs().max().item():.3e})"
                             break
-                finally:
-                    restore(old)
             print(line, flush=True)
     print("CHECK", "FAILED" if bad else "ok", bad, flush=True)
     return bad
@@ -181,11 +166,8 @@ def bench():
         res = {a: [] for a, _ in arms}
         for rep in range(REPS):
             for a, kw in arms:
-                old = set_modes(**kw)
-                try:
+                with set_modes(**kw):
                     res[a].append(timeit(call))
-                finally:
-                    restore(old)
         fl = 2.0 * M_ * N_ * K_
         txt = "  ".join(f"{a}: {min(v)*1e6:7.1f} us {fl/min(v)/1e12:7.1f} TF (med {sorted(v)[len(v)//2]*1e6:7.1f})" for a, v in res.items())
         print(f"bench {name:20s} M={M_:6d} N={N_:5d} K={K_:5d} {epi:6s} rot={ROT}  {txt}", flush=True)
@@ -215,15 +197,12 @@ def conv2():
     res, outs = {}, {}
     for rep in range(REPS):
         for arm, mode in (("old", 0), ("v8", 2)):
-            old = set_modes(mode)
-            try:
+            with set_modes(mode):
                 out2 = torch.full((M2, C_), 7.0, device=dev, dtype=bf)
                 fwd(out2)
                 torch.cuda.synchronize()
                 outs[arm] = out2
                 res.setdefault(arm, []).append(timeit(lambda: fwd(out2)))
-            finally:
-                restore(old)
     same = torch.equal(outs["old"], outs["v8"])
     fl = 2.0 * M2 * C_ * 9 * C_
     print(f"conv2_fwd gathered M={M2} N={C_} K={9*C_}: bit-identical={same} (max diff {(outs['old'].float()-outs['v8'].float()).abs().max().item():.3e})  " +
@@ -244,15 +223,12 @@ def conv2():
     res, outs = {}, {}
     for rep in range(REPS):
         for arm, mode in (("old", 0), ("v8", 2)):
-            old = set_modes(mode)
-            try:
+            with set_modes(mode):
                 d1 = torch.full((B_ * T1 * F1, C_), 3.0, device=dev, dtype=bf)
                 dgrad(d1)
                 torch.cuda.synchronize()
                 outs[arm] = d1
                 res.setdefault(arm, []).append(timeit(lambda: dgrad(d1)))
-            finally:
-                restore(old)
     same = torch.equal(outs["old"], outs["v8"])
     fl = 2.0 * B_ * nI * nJ * C_ * len(slots) * C_
     print(f"conv2_dgrad11 gathered+rowmap M={B_*nI*nJ} N={C_} K={len(slots)*C_}: bit-identical={same}  " +
@@ -274,8 +250,7 @@ def tn():
         outs, res = {}, {}
         for rep in range(REPS):
             for arm, mode in (("old", 0), ("v8", 2)):
-                old = set_modes(mode)
-                try:
+                with set_modes(mode):
                     dW = torch.zeros(M, N, device=dev)
                     db = torch.zeros(M, device=dev)
                     f = lambda: ops.gemm(dY, X, dW, M, N, K, lda, ldb, N, transA=True, transB=True, atomic=True, splitk=sk, c_dtype=ops.F32,
@@ -284,8 +259,6 @@ def tn():
                     torch.cuda.synchronize()
                     outs[arm] = (dW.clone(), db.clone())
                     res.setdefault(arm, []).append(timeit(f))
-                finally:
-                    restore(old)
         e8, eo = rel_err(outs["v8"][0], ref), rel_err(outs["old"][0], ref)
         b8, bo = rel_err(outs["v8"][1], refb), rel_err(outs["old"][1], refb)
         ok = e8 <= max(2 * eo, 2e-6) and b8 <= max(2 * bo, 2e-6)
@@ -301,8 +274,7 @@ def tn():
     outs, res = {}, {}
     for rep in range(REPS):
         for arm, mode in (("old", 0), ("v8", 3)):
-            old = set_modes(mode)
-            try:
+            with set_modes(mode):
                 probs = []
                 for (dY, X), (no, ni) in zip(ops_, shapes):
                     probs.append((dY, no, 0, X, ni, 0, torch.zeros(no, ni, device=dev), no, ni, torch.zeros(no, device=dev)))
@@ -311,8 +283,6 @@ def tn():
                 torch.cuda.synchronize()
                 outs[arm] = [(q[6].clone(), q[9].clone()) for q in probs]
                 res.setdefault(arm, []).append(timeit(f))
-            finally:
-                restore(old)
     worst = 0.0
     for (dY, X), (w8, b8), (wo, bo_) in zip(ops_, outs["v8"], outs["old"]):
         ref = dY.float().t() @ X.float()
@@ -338,8 +308,7 @@ def tn():
     outs, res = {}, {}
     for rep in range(REPS):
         for arm, mode in (("old", 0), ("v8", 3)):
-            old = set_modes(mode)
-            try:
+            with set_modes(mode):
                 dW = torch.zeros(C_, C_, 3, 3, device=dev)
                 f = lambda: ops.gemm(dout2, out1, dW, C_, C_, M2, C_, C_, 9 * C_, transA=True, transB=True, atomic=True, splitk=sk, batch=9,
                                      nb0=9, sC=(1, 0), c_col_stride=9, c_dtype=ops.F32, row_len=len2, rows_per_b=T2 * F2, rows_inner=F2,
@@ -348,8 +317,6 @@ def tn():
                 torch.cuda.synchronize()
                 outs[arm] = dW.clone()
                 res.setdefault(arm, []).append(timeit(f))
-            finally:
-                restore(old)
     e = rel_err(outs["v8"], outs["old"])
     ok = e < 5e-6
     bad += 0 if ok else 1

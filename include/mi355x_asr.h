@@ -259,7 +259,8 @@ int mi355x_layernorm2_bwd(const void* dy1, int dy1_dtype, const void* x1, const 
                           void* dgamma1, void* dbeta1, const void* dres_in, const void* x2, const void* gamma2, const void* mean2,
                           const void* rstd2, void* dgamma2, void* dbeta2, void* dres_out, int M, int d, void* cast_out,
                           float cast_scale, unsigned drop_key, unsigned drop_threshold, float drop_scale, void* stream);
-/* dres (f32 [M,d]) = (accumulate ? dres : 0) + dLN/dx ; dgamma/dbeta (f32 [d], may be NULL) are accumulated (+=)   */
+/* dres (f32 [M,d]) = (accumulate ? dres : 0) + dLN/dx ; dgamma/dbeta (f32 [d]) are accumulated (+=).  Pass both or
+ * neither (both NULL: input gradient only); exactly one of them NULL is MI_ERR_ARG.                                 */
 int mi355x_layernorm_bwd(const void* dy, int dy_dtype, const void* x, int x_dtype, const void* gamma, const void* mean,
                          const void* rstd, void* dres, int accumulate, void* dgamma, void* dbeta, int M, int d, void* stream);
 /* Same, and in the same pass cast_out (bf16 [M,d]) = cast_scale * dropmask * dres_new: the operand of the NEXT sub-block's

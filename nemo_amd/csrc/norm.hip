@@ -264,8 +264,9 @@ __global__ __launch_bounds__(256) void log_softmax_fwd_kernel(const float* __res
   mx = wave_max(mx);
   float s = 0.f;
   for (int i = lane; i < C; i += 64) s += expf(xr[i] - mx);
-  const float lse = mx + logf(wave_sum(s));
-  for (int i = lane; i < C; i += 64) y[row * ldy + i] = xr[i] - lse;
+  // (x - mx) - log(sum): x - mx is formed as in the pass above, so large logits lose nothing to the rounding of mx + log(sum)
+  const float ls = logf(wave_sum(s));
+  for (int i = lane; i < C; i += 64) y[row * ldy + i] = (xr[i] - mx) - ls;
 }
 // dx = dy - exp(y) * sum(dy); output in `TO` with pitch ldo (pad columns [C, ldo) are zero-filled so the buffer can
 // be used directly as a K-padded GEMM operand)
@@ -623,10 +624,11 @@ static int layernorm_bwd_impl(const void* dy, int dy_dt, const void* x, int x_dt
                               const void* rstd, void* dres, int accumulate, void* dgamma, void* dbeta, int M, int d,
                               void* cast_out, float cast_scale, DropCfg cast_drop, void* stream) {
   if (!dy || !x || !gamma || !mean || !rstd || !dres || M <= 0 || d <= 0 || (d & 3)) return MI_ERR_ARG;
+  if (!dgamma != !dbeta) return MI_ERR_ARG;  // both or neither: no kernel accumulates only one of them
   hipStream_t s = (hipStream_t)stream;
   dim3 block(256);
   const bool al = !((uintptr_t)dy & 15) && !((uintptr_t)x & 31) && !((uintptr_t)dres & 31) && !((uintptr_t)gamma & 31);
-  if (al && (d == 512 || d == 1024) && ((dgamma && dbeta) || (!dgamma && !dbeta))) {
+  if (al && (d == 512 || d == 1024)) {
     dim3 gridf((M + LNB_ROWS - 1) / LNB_ROWS);
     dim3 blockf(64 * LNB_WAVES);
 #define LN_F8(NCH) DISPATCH_DT(x_dt, TX, DISPATCH_DT(dy_dt, TDY, \
@@ -648,7 +650,7 @@ static int layernorm_bwd_impl(const void* dy, int dy_dt, const void* x, int x_dt
     }
   } cast_after{cast_out, cast_scale, cast_drop, dres, (long long)M * d, s};
   if (cast_out && (((long long)M * d) & 7)) return MI_ERR_ARG;
-  if (d <= 1024 && ((dgamma && dbeta) || (!dgamma && !dbeta))) {
+  if (d <= 1024) {
     dim3 gridf((M + LNB_ROWS - 1) / LNB_ROWS);
     dim3 blockf(64 * LNB_WAVES);
     const int nvv = (d / 4 + 63) / 64;
@@ -664,7 +666,7 @@ static int layernorm_bwd_impl(const void* dy, int dy_dt, const void* x, int x_dt
     }
     return mi_check_launch();
   }
-  if (dgamma && dbeta) {
+  if (dgamma) {
     dim3 gp((d + 63) / 64, (M + CR_ROWS - 1) / CR_ROWS);
     DISPATCH_DT(x_dt, TX, DISPATCH_DT(dy_dt, TDY,
       MI_LAUNCH((ln_bwd_param_kernel<TX, TDY>), gp, block, 0, s, (const TDY*)dy, (const TX*)x, (const float*)mean,

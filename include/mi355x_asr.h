@@ -418,12 +418,16 @@ int mi355x_bn_swish_fwd(const void* x, const void* mean, const void* rstd, const
 int mi355x_bn_stats_swish_fwd(const void* x, const void* stats, double count, const void* count_dev, const void* gamma,
                               const void* beta, void* y, void* mean, void* rstd, void* running_mean, void* running_var,
                               float momentum, float eps, int dtype, long long M, int d, void* stream);
-/* dgamma / dbeta (optional, both or neither): f32 [d] += the parameter gradients, i.e. the LOCAL sums (what
- * mi355x_bn_param_grad adds), accumulated by the reduction's second stage */
+/* dgamma / dbeta (optional, both or neither): f32 [d] += the parameter gradients, i.e. the LOCAL sums of this call (what
+ * mi355x_bn_param_grad adds when sums started from zero), with or without scratch.  dy, x, mean, rstd, gamma, beta and sums are all
+ * required: a NULL one returns MI_ERR_ARG (1) before anything is launched. */
 int mi355x_bn_swish_bwd_reduce(const void* dy, const void* x, const void* mean, const void* rstd, const void* gamma,
                                const void* beta, void* sums /*f64 [2,d] +=*/, void* dgamma, void* dbeta, int dtype, long long M,
                                int d, void* scratch /* optional f32 [ceil(M/32)*2*d]: two-stage reduction */,
                                long long scratch_elems, void* stream);
+/* dx = gamma * rstd * (dz - sums[0] / count - xhat * sums[1] / count), dz = dy * swish'(gamma * xhat + beta); training == 0 (eval mode)
+ * drops the two mean terms and never reads what `sums` points to.  Every pointer is required (sums included, in both modes): a NULL
+ * one returns MI_ERR_ARG (1) before anything is launched. */
 int mi355x_bn_swish_bwd_apply(const void* dy, const void* x, const void* mean, const void* rstd, const void* gamma,
                               const void* beta, const void* sums, double count, int training, void* dx, int dtype,
                               long long M, int d, void* stream);

@@ -238,7 +238,9 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const TT* __restrict__ 
     const int t = t0 + tg * DW_TQ + o;
     otile[tg * DW_TQ + o][c_l] = a;
     if (cv && t < T) {
-      const float ar = round_as(a, TT());
+      // the f32 partial sums are taken about the channel's bias: with y = bias + noise, sum y^2 in f32 loses |bias|^2 / var of its
+      // digits before the f64 atomic ever sees it (rstd off by 5e-4 at bias = 100 sigma); about the bias nothing cancels
+      const float ar = round_as(a, TT()) - bs;
       s1 += ar; s2 += ar * ar;
     }
   }
@@ -246,8 +248,13 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const TT* __restrict__ 
   __syncthreads();
   unstage_tile<TT>(y + (long long)b * T * d, T, d, t0, c0, otile);
   if (stats && tg == 0 && cv) {
-    atomicAdd(stats + c, (double)((red[0][0][c_l] + red[0][1][c_l]) + (red[0][2][c_l] + red[0][3][c_l])));
-    atomicAdd(stats + d + c, (double)((red[1][0][c_l] + red[1][1][c_l]) + (red[1][2][c_l] + red[1][3][c_l])));
+    // ... and shifted back in f64, so that stats still holds the raw sums (SyncBatchNorm all-reduces them):
+    //   sum y = S1 + n bias,  sum y^2 = S2 + 2 bias S1 + n bias^2,  n = the tile's frames inside [0, T)
+    const double S1 = (double)((red[0][0][c_l] + red[0][1][c_l]) + (red[0][2][c_l] + red[0][3][c_l]));
+    const double S2 = (double)((red[1][0][c_l] + red[1][1][c_l]) + (red[1][2][c_l] + red[1][3][c_l]));
+    const double n = (double)min(DW_TT, T - t0), bd = (double)bs;
+    atomicAdd(stats + c, S1 + n * bd);
+    atomicAdd(stats + d + c, S2 + bd * (2.0 * S1 + n * bd));
   }
 }
 
@@ -422,7 +429,7 @@ __device__ __forceinline__ void ds_wave_tile(const char* __restrict__ ub, char* 
         const uint32_t pk = pack_bf2(a[o].x, a[o].y);
         *reinterpret_cast<uint32_t*>(yb + (long long)t * row_bytes + lane_off) = pk;
         if (STATS) {
-          const float r0 = bf_lo(pk), r1 = bf_hi(pk);
+          const float r0 = bf_lo(pk) - bv.x, r1 = bf_hi(pk) - bv.y;   // (about the bias: see dwconv_fwd_kernel)
           s1.x += r0; s2.x = fmaf(r0, r0, s2.x);
           s1.y += r1; s2.y = fmaf(r1, r1, s2.y);
         }
@@ -431,6 +438,7 @@ __device__ __forceinline__ void ds_wave_tile(const char* __restrict__ ub, char* 
   }
 }
 
+__device__ __forceinline__ float bias_or_zero(const float* __restrict__ bias, int c) { return bias ? bias[c] : 0.f; }
 // y[b,t,c] = bias[c] + sum_k w[c, FLIP ? KS-1-k : k] * x[b, t+k-PAD, c];  STATS: stats[0][c] += sum y, stats[1][c] += sum y^2 (of the
 // bf16-rounded outputs, t < T).  D: the channel count at compile time (row offsets become instruction immediates), 0 = run time.
 template <int KS, bool FLIP, bool STATS, int D>
@@ -477,7 +485,14 @@ __global__ __launch_bounds__(64 * DS_NW) void dwconv_stream_kernel(const bf16_t*
 #pragma unroll
       for (int i = 0; i < DS_NW; ++i) v += red[i][q][lane];
       const int cc = cg0 + 2 * lane + (q & 1);
-      if (cc < d) atomicAdd(stats + (q >> 1) * d + cc, (double)v);
+      if (cc < d) {
+        // shifted back in f64 (stats holds the raw sums): quantity q and q ^ 2 are S1 and S2 of the same channel
+        float u = 0.f;
+#pragma unroll
+        for (int i = 0; i < DS_NW; ++i) u += red[i][q & 1][lane];
+        const double n = (double)min(DS_BT, T - (int)blockIdx.y * DS_BT), bd = (double)bias_or_zero(bias, cc);
+        atomicAdd(stats + (q >> 1) * d + cc, (q >> 1) ? (double)v + bd * (2.0 * (double)u + n * bd) : (double)v + n * bd);
+      }
     }
   }
 }
@@ -676,6 +691,7 @@ __global__ __launch_bounds__(256) void bn_swish_bwd_reduce_kernel(const TT* __re
                                                                   const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                   double* __restrict__ sums, float* __restrict__ partial,
+                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                                   long long M, int d, int rows_per_blk) {
   // thread = V consecutive channels (one 16-byte load per tensor per row) x every RS-th row of the workgroup's row block
   constexpr int V = VecIO<TT>::V;
@@ -720,7 +736,10 @@ __global__ __launch_bounds__(256) void bn_swish_bwd_reduce_kernel(const TT* __re
         for (int q = 0; q < RS; ++q) t += sred[q * CP * V + e];
         if (c0 + e < d) {
           if (partial) partial[((long long)blockIdx.y * 2 + which) * d + c0 + e] = t;
-          else atomicAdd(sums + which * d + c0 + e, (double)t);
+          else {   // (no slab: dgamma / dbeta get this workgroup's LOCAL sums, as the slab's second stage gives them)
+            atomicAdd(sums + which * d + c0 + e, (double)t);
+            if (dbeta) atomicAdd((which ? dgamma : dbeta) + c0 + e, t);
+          }
         }
       }
     }
@@ -951,6 +970,7 @@ extern "C" int mi355x_dwconv_bwd_bnswish(const void* dy, const void* cc, const v
   hipStream_t s = (hipStream_t)stream;
   const int nparts = B * DW_SEG;
   if (scratch && scratch_elems < (long long)nparts * (ksize + 1) * d) return MI_ERR_ARG;
+  if (defer_tap_reduce && !scratch) return MI_ERR_ARG;   // (before any launch: nothing may be added to dw on an error)
   const DwBnArgs bn = {cc, (const float*)mean, (const float*)rstd, (const float*)gamma, (const float*)beta, (const double*)sums,
                        count_dev ? 0.0 : 1.0 / count, (const double*)count_dev, training, glu_in, glu_din,
                        (const long long*)glu_len, (const long long*)glu_row_offsets, glu_act, 0};
@@ -964,7 +984,6 @@ extern "C" int mi355x_dwconv_bwd_bnswish(const void* dy, const void* cc, const v
     default: return MI_ERR_ARG;
   }
 #undef DW_BWD_BN
-  if (defer_tap_reduce && !scratch) return MI_ERR_ARG;
   if (scratch && !defer_tap_reduce)   // (deferred: the caller runs mi355x_dwconv_tap_reduce on the stream of its choice)
     MI_LAUNCH(tap_reduce_kernel, dim3(((ksize + 1) * d + 255) / 256, 4), dim3(256), 0, s, (const float*)scratch, nparts,
                        ksize, d, (float*)dw, (float*)dbias);
@@ -1057,7 +1076,7 @@ extern "C" int mi355x_bn_swish_bwd_reduce(const void* dy, const void* x, const v
                                           const void* beta, void* sums, void* dgamma, void* dbeta, int dt, long long M, int d,
                                           void* scratch, long long scratch_elems, void* stream) {
   mi_clear_errors();
-  if (!dy || !x || !sums || M <= 0 || d <= 0 || (!dgamma != !dbeta)) return MI_ERR_ARG;
+  if (!dy || !x || !mean || !rstd || !gamma || !beta || !sums || M <= 0 || d <= 0 || (!dgamma != !dbeta)) return MI_ERR_ARG;
   const int V = dt == MI_DT_BF16 ? 8 : 4;
   if (d % V) return MI_ERR_ARG;
   // rows per workgroup: 32 (501 workgroups at the Large shape) when the scratch slab is the documented ceil(M/32)*2*d; a larger slab
@@ -1071,12 +1090,11 @@ extern "C" int mi355x_bn_swish_bwd_reduce(const void* dy, const void* x, const v
   hipStream_t s = (hipStream_t)stream;
   DISPATCH_DT(dt, TT, MI_LAUNCH((bn_swish_bwd_reduce_kernel<TT>), grid, block, 0, s, (const TT*)dy, (const TT*)x,
                                          (const float*)mean, (const float*)rstd, (const float*)gamma, (const float*)beta,
-                                         (double*)sums, (float*)scratch, M, d, rows));
+                                         (double*)sums, (float*)scratch, scratch ? nullptr : (float*)dgamma,
+                                         scratch ? nullptr : (float*)dbeta, M, d, rows));
   if (scratch)
     MI_LAUNCH(bn_partials_reduce_kernel, dim3((2 * d + 255) / 256, 32), dim3(256), 0, s, (const float*)scratch, (int)nblk, d,
               (double*)sums, (float*)dgamma, (float*)dbeta);
-  else if (dgamma)  // (single-stage path: the sums are complete only after the kernel above)
-    MI_LAUNCH(bn_param_grad_kernel, dim3((d + 255) / 256), dim3(256), 0, s, (const double*)sums, (float*)dgamma, (float*)dbeta, d);
   return mi_check_launch();
 }
 static int bn_swish_bwd_apply_launch(const void* dy, const void* x, const void* mean, const void* rstd, const void* gamma,
@@ -1097,7 +1115,8 @@ static int bn_swish_bwd_apply_launch(const void* dy, const void* x, const void* 
                                      const void* beta, const void* sums, double count, const void* count_dev, int training,
                                      void* dx, int dt, long long M, int d, void* stream) {
   mi_clear_errors();
-  if (!dy || !x || !sums || !dx || M <= 0 || d <= 0 || d % (dt == MI_DT_BF16 ? 8 : 4) || (!count_dev && count <= 0))
+  if (!dy || !x || !mean || !rstd || !gamma || !beta || !sums || !dx || M <= 0 || d <= 0 || d % (dt == MI_DT_BF16 ? 8 : 4) ||
+      (!count_dev && count <= 0))
     return MI_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if ((size_t)d * 6 * sizeof(float) > 64 * 1024) return MI_ERR_ARG;

@@ -15,7 +15,7 @@ from __future__ import annotations
 import math
 import os
 from collections import OrderedDict
-from typing import Optional
+from typing import Any, NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -141,9 +141,89 @@ class RelPositionalEncoding(nn.Module):  # multi_head_attention.py:1056
         return full[L - T: L + T - 1]
 
 
-class _Saved:
-    """plain attribute bag for activations kept for backward"""
-    pass
+# ------------------------------------------------------------------------------------------------ what a forward keeps for backward
+class _Step:
+    """One forward of the sequencer: its grid and everything kept for the backward.  Every field is declared here with its default
+    (an undeclared name is an AttributeError); `copy.copy` gives a shallow copy (_graphed_backward)."""
+    __slots__ = ("B", "F", "T", "T1", "F1", "T2", "F2", "M", "cdt", "training", "seed",   # the grid: mel [B, F, T] -> [B, T1, F1] -> final
+                 "serial", "arena", "bypass", "mel", "len0", "len2", "lens_all", "drop_pre",   # [B, T2, F2], M = B * T2 rows
+                 "out1", "out2", "col", "col_gen", "dw",          # sub-sampling activations (dw: [_DwStage] of 'dw_striding')
+                 "pk", "pos", "p_all", "bn_stats", "bn_world", "layers", "sd", "proj_in", "cap_idx", "cap_out", "cap_layers",
+                 "pre_ln",    # forward: _PreNorm of the next layer's norm_feed_forward1 when the boundary kernel has produced it
+                 "pre_bwd",   # backward: _PreBwd when the layer above has run this layer's norm_out backward
+                 "dp_all", "bn_sums", "dpos_f32")
+
+    def __init__(self, B, F, T, T1, F1, T2, F2, M, cdt, training=False, seed=0):
+        self.B, self.F, self.T, self.T1, self.F1, self.T2, self.F2, self.M = B, F, T, T1, F1, T2, F2, M
+        self.cdt, self.training, self.seed = cdt, training, seed
+        self.serial, self.arena, self.bypass, self.bn_world, self.col_gen = 0, False, False, 1, 0
+        self.mel = self.len0 = self.len2 = self.lens_all = self.out1 = self.out2 = self.col = self.dw = None
+        self.pk = self.pos = self.p_all = self.bn_stats = self.pre_ln = self.pre_bwd = None
+        self.dp_all = self.bn_sums = self.dpos_f32 = None
+        self.drop_pre = ops.NO_DROP
+        self.layers, self.sd, self.cap_idx, self.cap_out, self.cap_layers, self.proj_in = [], [], [], [], [], {}
+
+
+class _RowPacking:
+    """plan of a packed forward (_packing_plan).  peek=True: the decision "this batch packs" alone -- no device work was done,
+    `cu` / `host_lens` are None (and `Mp` too when the lengths are not known on the host yet)"""
+    __slots__ = ("peek", "Mp", "cu", "host_lens")
+
+    def __init__(self, peek, Mp=None, cu=None, host_lens=None):
+        self.peek, self.Mp, self.cu, self.host_lens = peek, Mp, cu, host_lens
+
+
+class _SubIO:
+    """what the 'dw_striding' stack reads (C channels; conv1 weight / bias; per stage (depthwise weight, bias, pointwise bias)) and,
+    for a backward, where its gradients go; `finish`: None or a callable that folds scratch gradients into the parameters'"""
+    __slots__ = ("C", "c0w", "c0b", "dw", "g_c0w", "g_c0b", "g_dw", "g_out", "finish")
+
+    def __init__(self, C, c0w, c0b, dw):
+        self.C, self.c0w, self.c0b, self.dw = C, c0w, c0b, dw
+        self.g_c0w = self.g_c0b = self.g_dw = self.g_out = self.finish = None
+
+
+def _record(name, fields):
+    """immutable per-block record: a typing.NamedTuple with the given field names (read by name, never by position)"""
+    return NamedTuple(name, [(f, Any) for f in fields.split()])
+
+
+_DwStage = _record("_DwStage", "x T F dwo pwo Tn Fn")   # one 'dw_striding' stage: input [B, T, F, C], depthwise / pointwise outputs [B, Tn, Fn, C]
+_DwWeights = _record("_DwWeights", "dw_w dw_b pw_b")     # ... what the stage reads / where its gradients go (_SubIO.dw / .g_dw)
+_DwGrads = _record("_DwGrads", "dw_w dw_b pw_w pw_b")
+_LnSaved = _record("_LnSaved", "x mean rstd")           # a LayerNorm's input and row statistics
+_PreNorm = _record("_PreNorm", "y mean rstd")           # a LayerNorm's OUTPUT and row statistics, handed to the next layer (S.pre_ln)
+_PreBwd = _record("_PreBwd", "dr cast")                 # gradient w.r.t. a layer's r4 and its cast operand copy (or None), S.pre_bwd
+
+
+class _AttnCore(NamedTuple):
+    """rel-pos attention core (_attn_fwd): the fused path keeps lse (and ctx_lo), the GEMM + softmax path qu, qv, s, pd"""
+    ctx_lo: Any = None   # bf16 rounding residual of the context (fused path, only while activations are saved)
+    qu: Any = None       # q + pos_bias_u, q + pos_bias_v
+    qv: Any = None
+    s: Any = None        # softmax output; pd = s after attention dropout (s itself without dropout)
+    pd: Any = None
+    lse: Any = None      # log-sum-exp [B, H, T]
+
+
+class _ConvCore(NamedTuple):
+    """depthwise conv -> norm -> Swish core of a conv module on the padded [B*T, C] grid (_conv_core_fwd)"""
+    g: Any        # the point-wise activation's output (GLU / Swish of pw1) = the depthwise conv's input
+    cc: Any       # the depthwise conv's output
+    bmean: Any    # batch_norm: per-channel mean / rstd [C];  layer_norm: per-frame mean / rstd [B*T]
+    brstd: Any
+    count: Any    # batch_norm: element count (float, or the device f64 scalar under SyncBatchNorm);  layer_norm: the normalised frames
+
+
+# Conformer blocks.  Feed-forward: x -> LayerNorm (mean, rstd) -> y -> linear1 -> h -> Swish, dropout d_in -> a -> linear2 -> dropout
+# d_res -> + x; a is None when the one-launch block never stored it, d_in is None when h holds swish'(h) * mask (swish_g).
+_FfSaved = _record("_FfSaved", "x y mean rstd h a d_in d_res")
+# self-attention: x -> LayerNorm -> y -> q | k | v; p = linear_pos(pos_emb); core: _AttnCore; ctx -> linear_out -> dropout d_res -> + x
+_AttSaved = _record("_AttSaved", "x y mean rstd qkv p core ctx d_att d_res")
+# conv module: x -> LayerNorm -> y -> pointwise_conv1 -> pw1 -> core (_ConvCore) -> z (rows of the chain: the packed copy under packed
+# rows) -> pointwise_conv2 -> dropout d_res -> + x
+_ConvSaved = _record("_ConvSaved", "x y mean rstd pw1 core z d_res")
+_LayerSaved = _record("_LayerSaved", "ff1 att conv ff2 out")   # (out: _LnSaved of norm_out, x = its input r4)
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -157,7 +237,7 @@ class _EncoderFn(torch.autograd.Function):
             out, enc_len, ctx.gset, ctx.gen = res
         else:
             out, enc_len, ctx.saved = module._forward_impl(mel, length, save=True)
-            caps = tuple(getattr(ctx.saved, "cap_out", ())) if ctx.saved is not None else ()
+            caps = tuple(ctx.saved.cap_out) if ctx.saved is not None else ()
         ctx.mark_non_differentiable(enc_len)
         return (out, enc_len) + caps   # (+ the InterCTC captures, differentiable)
 
@@ -362,6 +442,7 @@ class ConformerEncoder(NeuralModule):
         self.wgrad_layers = int(os.environ.get("MI355X_WGRAD_LAYERS", "2"))
         self.posproj_side = os.environ.get("MI355X_POSPROJ_SIDE", "1") != "0"  # linear_pos weight gradients behind their producers on the side stream
         self._wg_pending, self._wg_rows = None, None
+        self._defer_flush = None    # _backward_impl: the deferred grouped weight-gradient launch _defer_point may issue
         self.conv2_implicit = os.environ.get("MI355X_CONV2_IMPLICIT", "1") != "0"
         # conv module backward: BatchNorm + Swish backward inside the depthwise backward's tile staging (MI355X_BN_DW_FUSE=0: two launches)
         self.fuse_bn_dwconv_bwd = os.environ.get("MI355X_BN_DW_FUSE", "1") != "0"
@@ -576,7 +657,7 @@ class ConformerEncoder(NeuralModule):
             self.captured = dict(zip(self.capture_layers, res[2:]))
             return res[0], res[1]
         out, enc_len, S_ = self._forward_impl(audio_signal, length, save=bool(self.capture_layers))
-        self.captured = dict(zip(self.capture_layers, getattr(S_, "cap_out", ()))) if S_ is not None else {}
+        self.captured = dict(zip(self.capture_layers, S_.cap_out)) if S_ is not None else {}
         return out, enc_len
 
     # ------------------------------------------------------------------ cache-aware streaming (modules/conformer_streaming.py)
@@ -939,7 +1020,7 @@ class ConformerEncoder(NeuralModule):
                                "encoder.use_graphs = False (or MI355X_GRAPHS=0) for several forwards per backward")
         if self.graph_bwd_live and gs.bwd is None:
             # live backward on the activations the replayed forward has just refilled (the recording's tensors keep their addresses);
-            # the sequencer consumes its bag of saved tensors, so it gets a copy of the bag
+            # the sequencer consumes its list of saved layers, so it gets a shallow copy of the step record with a list of its own
             import copy
             S = copy.copy(gs.S)
             S.layers = list(gs.S.layers)
@@ -1124,7 +1205,7 @@ class ConformerEncoder(NeuralModule):
         """see _backward_impl: point k of a layer's backward (1 = in front of the conv module's BatchNorm / depthwise / GLU
         backward, 2 = in front of the attention backward, 3 = in front of norm_conv's backward, 5 / 6 = inside the conv module: behind
         the BatchNorm reduction / behind the depthwise backward)"""
-        f = getattr(self, "_defer_flush", None)
+        f = self._defer_flush
         if f is None:
             return
         if self.wgrad_defer == k or (self.wgrad_defer in (3, 4) and k == 1):
@@ -1156,7 +1237,7 @@ class ConformerEncoder(NeuralModule):
             torch.cuda.current_stream(self._wg_stream.device).wait_stream(self._wg_stream)
 
     def _packing_plan(self, length, B, T_mel, lens=None, peek=False):
-        """None (the padded path) or the plan of a packed forward: pk.cu = i64 [B+1] row offsets on the device, pk.Mp = number of
+        """None (the padded path) or the _RowPacking plan of a packed forward: pk.cu = i64 [B+1] row offsets on the device, pk.Mp = number of
         valid frames after sub-sampling.  The row count is a HOST number (it sizes every launch), so the lengths have to be known on
         the host: `length.host_lengths` (a CPU tensor / list the caller attached to the length tensor -- the input pipeline has them
         anyway) costs nothing; without it packed_rows=True reads them back (one device sync per step), "auto" stays padded.
@@ -1169,7 +1250,7 @@ class ConformerEncoder(NeuralModule):
             if mode == "auto":
                 return None
             if peek:
-                return _Saved()   # forced packing without host lengths: the decision is "packed", the numbers come with the sync
+                return _RowPacking(peek=True)   # forced packing without host lengths: the numbers come with the sync
             host = length.detach().to("cpu")
         hl = torch.as_tensor(host, dtype=torch.int64).clamp(min=0, max=T_mel)
         T2 = T_mel
@@ -1181,15 +1262,11 @@ class ConformerEncoder(NeuralModule):
         Mp, M = int(hl.sum()), B * T2
         if Mp <= 0 or (mode == "auto" and (M - Mp) < self.packed_min_padding * M):
             return None
-        pk = _Saved()
-        pk.Mp = Mp
         if peek:
-            return pk
+            return _RowPacking(peek=True, Mp=Mp)
         cu = torch.zeros(B + 1, dtype=torch.int64)
         cu[1:] = torch.cumsum(hl, 0)
-        pk.cu = cu.to(length.device, non_blocking=True)
-        pk.host_lens = hl
-        return pk
+        return _RowPacking(peek=False, Mp=Mp, cu=cu.to(length.device, non_blocking=True), host_lens=hl)
 
     def _lens(self, length, n_stages=2):
         """valid lengths after 0, 1, ..., n stride-2 stages: floor((n + all_paddings - 3)/2) + 1 each, all_paddings = 2 (or 3 with
@@ -1242,12 +1319,9 @@ class ConformerEncoder(NeuralModule):
         def drop(p, site):
             return ops.Dropout(p if training else 0.0, seed, site)
 
-        S = _Saved()
+        S = _Step(B, F_, T, T1, F1, T2, F2, M, cdt, training, seed)
         S.serial, S.arena = self._fwd_serial, self._arena is not None
-        S.dims = (B, F_, T, T1, F1, T2, F2, M, cdt, training, seed)
-        S.mel, S.len0, S.len2 = mel, len0, len2
-        pe = self.pre_encode
-        S.lens_all = lens
+        S.mel, S.len0, S.len2, S.lens_all = mel, len0, len2, lens
         S.drop_pre = drop(self.dropout_pre_encoder, 100000)
         S.bypass = bypass
         if bypass:
@@ -1286,8 +1360,6 @@ class ConformerEncoder(NeuralModule):
         S.bn_world = self._syncbn_world() if training else 1
         if training and S.bn_world > 1:
             S.bn_stats[:, 2 * d] = float(M)
-        S.layers = []
-        S.sd, S.cap_idx, S.cap_out, S.proj_in = [], [], [], {}
 
         def on_grid(t):  # a layer output on the reference's [B, T', d] grid (packed rows: frames beyond an utterance are zeros)
             if pk is None:
@@ -1306,17 +1378,17 @@ class ConformerEncoder(NeuralModule):
             x_in = x
             x, sl = self._layer_fwd(i, L, x, S, W, Wf, drop)
             S.layers.append(sl)
-            sd = None
+            sd = None   # stochastic depth: None = the layer counts as it is, 0.0 = dropped, else the factor a kept layer is rescaled by
             if training and self.layer_drop_probs[i] > 0.0:
                 # stochastic depth (conformer_encoder.py:696-707): one torch.rand(1) per droppable layer from the global generator, at
                 # the reference's point in the sequence.  A dropped layer has run (BatchNorm statistics, dropout counters move on)
                 # and contributes nothing; a kept one is rescaled: x_in + (x - x_in) / (1 - p)
                 p_ = self.layer_drop_probs[i]
                 if bool(torch.rand(1) < p_):
-                    sd, x = ("drop", 0.0), x_in
+                    sd, x = 0.0, x_in
                 else:
-                    a_ = 1.0 / (1.0 - p_)
-                    sd, x = ("keep", a_), torch.add(x_in, x - x_in, alpha=a_)
+                    sd = a_ = 1.0 / (1.0 - p_)
+                    x = torch.add(x_in, x - x_in, alpha=a_)
             S.sd.append(sd)
             if i in self.capture_layers:
                 S.cap_idx.append(i)
@@ -1333,8 +1405,8 @@ class ConformerEncoder(NeuralModule):
 
     def _sub_fwd_striding(self, S, mel, lens, W, cdt, save):
         """'striding' sub-sampling: conv1 (direct) -> conv2 (implicit MFMA GEMM, ReLU+mask epilogue) -> out Linear (+xscale,
-        dropout); `S.dims` holds the grid"""
-        B, F_, T, T1, F1, T2, F2, M, _, training, seed = S.dims
+        dropout); S holds the grid"""
+        B, T1, F1, T2, F2, M = S.B, S.T1, S.F1, S.T2, S.F2, S.M
         dev = mel.device
         pe = self.pre_encode
         C_, d = pe._conv_channels, self.d_model
@@ -1371,22 +1443,18 @@ class ConformerEncoder(NeuralModule):
         """what the 'dw_striding' stack reads and where its gradients go: here the parameters and their `.grad` views.
         (SqueezeformerEncoder substitutes zero-padded images / scratch gradients when the channel count is not a multiple of 8.)"""
         pe = self.pre_encode
-        io = _Saved()
-        io.C = pe._conv_channels
-        io.c0w, io.c0b = pe.conv[0].weight, pe.conv[0].bias
-        io.dw = [(dw.weight, dw.bias, pw.bias) for dw, pw in pe.dw_stages()]
+        io = _SubIO(pe._conv_channels, pe.conv[0].weight, pe.conv[0].bias, [_DwWeights(dw.weight, dw.bias, pw.bias) for dw, pw in pe.dw_stages()])
         if backward:
             io.g_c0w, io.g_c0b = pe.conv[0].weight.grad, pe.conv[0].bias.grad
-            io.g_dw = [(dw.weight.grad, dw.bias.grad, pw.weight.grad, pw.bias.grad) for dw, pw in pe.dw_stages()]
+            io.g_dw = [_DwGrads(dw.weight.grad, dw.bias.grad, pw.weight.grad, pw.bias.grad) for dw, pw in pe.dw_stages()]
             io.g_out = pe.out.weight.grad
-        io.finish = None
         return io
 
     def _sub_fwd_dw(self, S, mel, lens, W, cdt, save, Wf=None):
         """conv(1->C, 3x3, s2) ReLU -> [depthwise 3x3 s2 -> pointwise 1x1 -> ReLU] x (log2(factor) - 1) -> Linear, every layer
         on a time-masked input (subsampling.py:142-215, 385-436, 725-759).  conv1: the direct kernel of the 'striding' path;
         depthwise: mi355x_dwconv2d_s2_*; pointwise: MFMA GEMM with the ReLU + time-mask epilogue; channels-last throughout."""
-        B, F_, T, T1, F1, T2, F2, M, _, training, seed = S.dims
+        B, T1, F1, F2, M = S.B, S.T1, S.F1, S.F2, S.M
         dev = mel.device
         pe = self.pre_encode
         io = self._sub_io(Wf, cdt, dev)
@@ -1395,14 +1463,14 @@ class ConformerEncoder(NeuralModule):
         ops.conv1_fwd(mel, io.c0w, io.c0b, out0, lens[0], lens[1], C_, pad=pe._pad)
         cur, Tc, Fc = out0, T1, F1
         S.dw = []
-        for si_, (dww, dwb, pwb) in enumerate(io.dw):
+        for si_, w in enumerate(io.dw):
             Tn, Fn = ops.half_len(Tc, pe._pad), ops.half_len(Fc, pe._pad)
             dwo = self._new(B * Tn * Fn, C_, dtype=cdt, device=dev)
-            ops.dwconv2d_s2_fwd(cur, dww, dwb, dwo, B, Tc, Fc, C_, pad=pe._pad)
+            ops.dwconv2d_s2_fwd(cur, w.dw_w, w.dw_b, dwo, B, Tc, Fc, C_, pad=pe._pad)
             pwo = self._new(B * Tn * Fn, C_, dtype=cdt, device=dev)
-            ops.gemm(dwo, W[f"pre.pw{si_}"], pwo, B * Tn * Fn, C_, C_, C_, W.pitch(f"pre.pw{si_}"), C_, bias=pwb,
+            ops.gemm(dwo, W[f"pre.pw{si_}"], pwo, B * Tn * Fn, C_, C_, C_, W.pitch(f"pre.pw{si_}"), C_, bias=w.pw_b,
                      epi=ops.EPI_RELU_MASK, row_len=lens[si_ + 2], rows_per_b=Tn * Fn, rows_inner=Fn)
-            S.dw.append((cur, Tc, Fc, dwo, pwo, Tn, Fn))
+            S.dw.append(_DwStage(cur, Tc, Fc, dwo, pwo, Tn, Fn))
             cur, Tc, Fc = pwo, Tn, Fn
         x = self._new(M, d, dtype=torch.float32, device=dev)
         ops.gemm(cur, W["pre.out"], x, M, d, F2 * C_, F2 * C_, W.pitch("pre.out"), d, bias=pe.out.bias,
@@ -1411,7 +1479,7 @@ class ConformerEncoder(NeuralModule):
         return x
 
     def _sub_bwd_dw(self, S, dx, W, cdt, Wf=None):
-        B, F_, T, T1, F1, T2, F2, M, _, training, seed = S.dims
+        B, T2, F2, M = S.B, S.T2, S.F2, S.M
         dev = dx.device
         pe = self.pre_encode
         io = self._sub_io(Wf, cdt, dev, backward=True)
@@ -1434,24 +1502,24 @@ class ConformerEncoder(NeuralModule):
         dcur = self._new(B * T2 * F2, C_, dtype=cdt, device=dev)
         ops.gemm(dxs, W["pre.outt"], dcur, M, F2 * C_, d, ldx, W.pitch("pre.outt"), F2 * C_, epi=ops.EPI_MUL_POS, aux_in=last)
         for si_ in range(len(S.dw) - 1, -1, -1):
-            cur_in, Tc, Fc, dwo, pwo, Tn, Fn = S.dw[si_]
-            dww, dwb, pwb = io.dw[si_]
-            g_dww, g_dwb, g_pww, g_pwb = io.g_dw[si_]
-            Ms = B * Tn * Fn
+            st = S.dw[si_]
+            Tc, Fc, dwo = st.T, st.F, st.dwo
+            gr = io.g_dw[si_]
+            Ms = B * st.Tn * st.Fn
             # pointwise conv: bias / weight gradients, then the gradient w.r.t. the depthwise output (no gate: no ReLU there)
             if bf16 and C_ >= 192:
                 with self._sub_wgrad_scope(dcur, dwo):
-                    ops.gemm(dcur, dwo, g_pww, C_, C_, Ms, C_, C_, C_, transA=True, transB=True, atomic=True,
-                             splitk=self._splitk(self._tiles(C_, C_, True), Ms), c_dtype=ops.F32, colsum_out=g_pwb)
+                    ops.gemm(dcur, dwo, gr.pw_w, C_, C_, Ms, C_, C_, C_, transA=True, transB=True, atomic=True,
+                             splitk=self._splitk(self._tiles(C_, C_, True), Ms), c_dtype=ops.F32, colsum_out=gr.pw_b)
             else:
                 with self._sub_wgrad_scope(dcur, dwo):
-                    ops.colsum(dcur, g_pwb, Ms, C_)
-                    ops.gemm(dcur, dwo, g_pww, C_, C_, Ms, C_, C_, C_, transA=True, transB=True, atomic=True,
+                    ops.colsum(dcur, gr.pw_b, Ms, C_)
+                    ops.gemm(dcur, dwo, gr.pw_w, C_, C_, Ms, C_, C_, C_, transA=True, transB=True, atomic=True,
                              splitk=self._splitk(self._tiles(C_, C_, bf16), Ms), c_dtype=ops.F32)
             ddw = self._new(Ms, C_, dtype=cdt, device=dev)
             ops.gemm(dcur, W[f"pre.pw{si_}t"], ddw, Ms, C_, C_, C_, W.pitch(f"pre.pw{si_}t"), C_)
             din = self._new(B * Tc * Fc, C_, dtype=cdt, device=dev)
-            ops.dwconv2d_s2_bwd(ddw, cur_in, dww, din, g_dww, g_dwb, B, Tc, Fc, C_, pad=pe._pad)
+            ops.dwconv2d_s2_bwd(ddw, st.x, io.dw[si_].dw_w, din, gr.dw_w, gr.dw_b, B, Tc, Fc, C_, pad=pe._pad)
             dcur = din
         ops.conv1_bwd(dcur, S.mel, S.len0, io.g_c0w, io.g_c0b, C_, pad=pe._pad)
         self._wgrad_join(consume=io.finish is not None)
@@ -1473,13 +1541,11 @@ class ConformerEncoder(NeuralModule):
         return (self.ffn_fused and cdt == torch.bfloat16 and self.d_model == 512 and self.d_ff % 64 == 0
                 and 128 <= self.d_ff <= 2048)
 
-    def _ffn_fwd(self, pfx, ff, x, ln, S, sl, W, drop, site, M, d, dff, cdt, dev, tag):
-        pre = getattr(S, "pre_ln", None)
-        if pre is not None and tag == "ff1":  # the previous layer's output norm already normalised this layer's input
-            y, mean, rstd = pre
-            S.pre_ln = None
-        else:
-            y, mean, rstd = self._ln_fwd(ln, x, M, d, cdt, dev)
+    def _ffn_fwd(self, pfx, ff, x, ln, S, W, drop, site, M, pre=None):
+        """one macaron feed-forward block on the M rows of x -> (x + 0.5 * dropout(ffn(LN(x))), _FfSaved).  `pre`: the _PreNorm of
+        LN(x) when the previous layer's output norm has already normalised this layer's input (S.pre_ln)"""
+        d, dff, cdt, dev = self.d_model, self.d_ff, S.cdt, x.device
+        y, mean, rstd = (pre.y, pre.mean, pre.rstd) if pre is not None else self._ln_fwd(ln, x, M, d, cdt, dev)
         h = self._new(M, dff, dtype=cdt, device=dev)
         d_in = drop(self.dropout, site)
         d_res = drop(self.dropout, site + 1)
@@ -1488,8 +1554,7 @@ class ConformerEncoder(NeuralModule):
             # reaches memory (backward recomputes it from h for the linear2 weight gradient)
             r = self._new(M, d, dtype=torch.float32, device=dev)
             ops.ffn_fwd(y, W[pfx + ".w1p"], ff.linear1.bias, W[pfx + ".w2p"], ff.linear2.bias, x, h, r, M, d, dff, 0.5, d_in, d_res)
-            setattr(sl, tag, (x, y, mean, rstd, h, None, d_in, d_res))
-            return r
+            return r, _FfSaved(x, y, mean, rstd, h, None, d_in, d_res)
         a = self._new(M, dff, dtype=cdt, device=dev)
         g_form = self.swish_g and cdt == torch.bfloat16  # `h` then holds swish'(h) * mask (see __init__)
         ops.gemm(y, W[pfx + ".w1"], a, M, dff, d, d, W.pitch(pfx + ".w1"), dff, bias=ff.linear1.bias,
@@ -1497,8 +1562,7 @@ class ConformerEncoder(NeuralModule):
         r = self._new(M, d, dtype=torch.float32, device=dev)
         ops.gemm(a, W[pfx + ".w2"], r, M, d, dff, dff, W.pitch(pfx + ".w2"), d, bias=ff.linear2.bias, alpha=0.5,
                  epi=ops.EPI_RESID, aux_in=x, drop=d_res)
-        setattr(sl, tag, (x, y, mean, rstd, h, a, None if g_form else d_in, d_res))
-        return r
+        return r, _FfSaved(x, y, mean, rstd, h, a, None if g_form else d_in, d_res)
 
     def _geometry(self, cdt):
         """(row pitch of [M, d] GEMM operands, head width in the attention operands, attention width H * head width).  bf16
@@ -1572,12 +1636,12 @@ class ConformerEncoder(NeuralModule):
                 self._wgrad(dp_all[i], d, 0, pos, d, 0, grads[i], d, d, P)
 
     # ------------------------------------------------------------------ rel-pos attention core (shared with Squeezeformer)
-    def _attn_fwd(self, qkv, p, bias_u, bias_v, lens, B, T, dA, dk, scale, d_att, cdt, dev, pk=None):
+    def _attn_fwd(self, S, qkv, p, bias_u, bias_v, lens, B, T, dA, dk, d_att, pk=None):
         """qkv [B*T, 3*dA] (q | k | v, heads of width dk = dA / H, possibly zero-padded heads), p [2T-1, dA] = linear_pos of
-        the table, bias_u / bias_v [dA] -> ctx [B*T, dA] and what backward needs.  `scale` = 1/sqrt(true d_k).
+        the table, bias_u / bias_v [dA] -> ctx [B*T, dA] and the _AttnCore backward needs.  The scores' scale is 1/sqrt(true d_k).
         pk (packed rows): qkv / ctx hold the valid frames only ([pk.Mp, .]); the fused kernels address utterance b at pk.cu[b],
         the un-fused path (fp32, other head widths) runs on a padded copy."""
-        H = self.n_heads
+        H, cdt, dev, scale = self.n_heads, S.cdt, qkv.device, 1.0 / math.sqrt(self.d_k)
         M, P = B * T, 2 * T - 1
         Tp, Pp = _pad8(T), _pad8(P)
         flash = self._flash_ok() and cdt == torch.bfloat16 and dk in (64, 128)
@@ -1585,7 +1649,7 @@ class ConformerEncoder(NeuralModule):
         if pk is not None and not flash:
             qkv_p = self._new(M, 3 * dA, dtype=cdt, device=dev)
             ops.rows_unpack(qkv, qkv_p, lens, cu, T, M, 3 * dA)
-            ctx_p, saved = self._attn_fwd(qkv_p, p, bias_u, bias_v, lens, B, T, dA, dk, scale, d_att, cdt, dev)
+            ctx_p, saved = self._attn_fwd(S, qkv_p, p, bias_u, bias_v, lens, B, T, dA, dk, d_att)
             ctx = self._new(pk.Mp, dA, dtype=cdt, device=dev)
             ops.rows_pack(ctx_p, ctx, lens, cu, T, M, dA)
             return ctx, saved
@@ -1594,13 +1658,13 @@ class ConformerEncoder(NeuralModule):
             # fused rel-pos flash attention: scores / positional matrix never touch HBM; only the log-sum-exp is kept
             lse = self._new(B, H, T, dtype=torch.float32, device=dev)
             # training: also the bf16 rounding residual of the context (backward's delta = sum dO * O needs more than the 8
-            # mantissa bits of the stored operand -- see mi355x_relpos_flash_fwd); it travels in the first slot of the saved tuple
+            # mantissa bits of the stored operand -- see mi355x_relpos_flash_fwd)
             # (kept whenever activations are saved for a backward -- also for an eval-mode / frozen encoder that is
             #  differentiated through: delta from the rounded O alone put a 36 % error on layer-0 q / k gradients)
             ctx_lo = self._new(ctx.shape[0], dA, dtype=cdt, device=dev) if (self._saving and self.flash_delta_residual) else None
             ops.relpos_flash_fwd(qkv, 3 * dA, p, dA, bias_u, bias_v, lens, ctx, dA, lse, B, H, T, dk, Tp, scale, d_att,
                                  ctx_lo=ctx_lo, cu=cu)
-            return ctx, (ctx_lo, None, None, None, lse)
+            return ctx, _AttnCore(ctx_lo=ctx_lo, lse=lse)
         qu = self._new(M, dA, dtype=cdt, device=dev)
         qv = self._new(M, dA, dtype=cdt, device=dev)
         ops.qbias(qkv, 3 * dA, bias_u, bias_v, qu, qv, M, dA)
@@ -1618,16 +1682,17 @@ class ConformerEncoder(NeuralModule):
         # ctx_bh = pd_bh [T,T] @ v_bh [T,dk]   (NN: v is reduction-major inside qkv)
         ops.gemm(pd, qkv, ctx, T, dk, T, Tp, 3 * dA, dA, transB=True, batch=H * B, nb0=B, sA=(T * Tp, B * T * Tp),
                  sB=(T * 3 * dA, dk), sC=(T * dA, dk), b_off=2 * dA)
-        return ctx, (qu, qv, s_, pd, None)
+        return ctx, _AttnCore(qu=qu, qv=qv, s=s_, pd=pd)
 
-    def _attn_bwd(self, saved, qkv, p, bias_u, bias_v, ctx, dctx, lens, B, T, dA, dk, scale, d_att, cdt, dev, dp, dp_cast,
-                  bias_grads=None, pk=None):
-        """-> (dqkv [M, 3*dA] with the k and v thirds filled, dqu, dqv [M, dA]); dp f32 [2T-1, dA] += d linear_pos output,
+    def _attn_bwd(self, S, saved, qkv, p, bias_u, bias_v, ctx, dctx, lens, B, T, dA, dk, d_att, dp, dp_cast, bias_grads=None,
+                  pk=None):
+        """backward of _attn_fwd (same S, qkv, p, biases, lens, B, T, dA, dk, d_att; `saved` = its _AttnCore, ctx / dctx = its
+        output and the gradient w.r.t. it) -> (dqkv [M, 3*dA] with the k and v thirds filled, dqu, dqv [M, dA]); dp f32 [2T-1, dA] += d linear_pos output,
         dp_cast (compute dtype) = its GEMM-operand copy for the linear_pos weight gradient.  `bias_grads` (fused path only):
         f32 [2 * dA] = pos_bias_u.grad | pos_bias_v.grad in one piece -- then the dQ kernel writes dq = dqu + dqv into the q third
         of dqkv and the bias gradients itself, and (dqkv, None, None) comes back."""
-        qu, qv, s_, pd, lse = saved
-        H = self.n_heads
+        qu, qv, s_, pd, lse = saved.qu, saved.qv, saved.s, saved.pd, saved.lse
+        H, cdt, dev, scale = self.n_heads, S.cdt, qkv.device, 1.0 / math.sqrt(self.d_k)
         M, P = B * T, 2 * T - 1
         Tp, Pp = _pad8(T), _pad8(P)
         cu = pk.cu if pk is not None else None
@@ -1638,8 +1703,7 @@ class ConformerEncoder(NeuralModule):
             dctx_p = self._new(M, dA, dtype=cdt, device=dev)
             ops.rows_unpack(qkv, qkv_p, lens, cu, T, M, 3 * dA)
             ops.rows_unpack(dctx, dctx_p, lens, cu, T, M, dA)
-            dqkv_p, dqu_p, dqv_p = self._attn_bwd(saved, qkv_p, p, bias_u, bias_v, None, dctx_p, lens, B, T, dA, dk, scale, d_att, cdt,
-                                                  dev, dp, dp_cast)
+            dqkv_p, dqu_p, dqv_p = self._attn_bwd(S, saved, qkv_p, p, bias_u, bias_v, None, dctx_p, lens, B, T, dA, dk, d_att, dp, dp_cast)
             out = []
             for t_p, w in ((dqkv_p, 3 * dA), (dqu_p, dA), (dqv_p, dA)):
                 t = self._new(pk.Mp, w, dtype=cdt, device=dev)
@@ -1653,7 +1717,7 @@ class ConformerEncoder(NeuralModule):
         dqu = None if fuse_dq else self._new(M, dA, dtype=cdt, device=dev)
         dqv = None if fuse_dq else self._new(M, dA, dtype=cdt, device=dev)
         if lse is not None:
-            ctx_lo = qu  # (fused path: the first slot carries the context's rounding residual, q + u is recomputed here)
+            ctx_lo = saved.ctx_lo  # (q + u and q + v are recomputed here)
             qu = self._new(M, dA, dtype=cdt, device=dev)
             qv = self._new(M, dA, dtype=cdt, device=dev)
             dlt = self._new(B, H, T, dtype=torch.float32, device=dev)
@@ -1704,20 +1768,62 @@ class ConformerEncoder(NeuralModule):
         ops.drop_scale_cast(dp, dp_cast, P * dA, 1.0)  # linear_pos weight gradients: one batched GEMM after the loop
         return dqkv, dqu, dqv
 
+    def _conv_core_fwd(self, S, i, c, pw1, lens, B, T, C, *, act, pad_left=-1, cu=None, norm="batch_norm"):
+        """point-wise activation of pw1 (act 0 = GLU, 1 = Swish) -> depthwise conv -> norm -> Swish of layer i's conv module `c`, on
+        the padded [B*T, C] grid -> (_ConvCore, z [B*T, C]).  pad_left: -1 = symmetric padding, else CausalConv1D's left pad;
+        cu (packed rows): pw1 holds the valid frames only."""
+        Mg, k, cdt, dev, training = B * T, self.conv_kernel_size, S.cdt, pw1.device, S.training
+        bn, dw = c.batch_norm, c.depthwise_conv
+        g = self._new(Mg, C, dtype=cdt, device=dev)
+        # fused: activation + pad mask applied while the depthwise forward stages its tile (g is written for backward, not re-read);
+        # the fused form is symmetric
+        fuse = self.fuse_glu_dwconv_fwd and C % (8 if cdt == torch.bfloat16 else 4) == 0 and pad_left < 0
+        if not fuse and act == 0:
+            ops.glu_fwd(pw1, g, lens, T, Mg, C, cu=cu)
+        elif not fuse:
+            ops.swish_mask_fwd(pw1, g, lens, T, Mg, C)
+        cc = self._new(Mg, C, dtype=cdt, device=dev)
+        bmean = self._new(C, dtype=torch.float32, device=dev)
+        brstd = self._new(C, dtype=torch.float32, device=dev)
+        count = float(Mg)
+        stats = S.bn_stats[i] if (training and norm == "batch_norm") else None   # f64 sums, filled by the depthwise forward
+        if fuse:
+            ops.dwconv_fwd_glu(pw1, lens, cu, g, dw.weight, dw.bias, cc, stats, B, T, C, k, act=act)
+        else:
+            ops.dwconv_fwd(g, dw.weight, dw.bias, cc, stats, B, T, C, k, pad_left=pad_left)
+        if norm == "layer_norm":
+            # nn.LayerNorm over the channels of every frame instead of BatchNorm (conformer_modules.py:335-338): depthwise conv without
+            # statistics -> LayerNorm -> Swish (see _ConvCore for what the statistics fields hold)
+            count, bmean, brstd = self._ln_fwd(bn, cc, Mg, C, cdt, dev)
+            z = self._new(Mg, C, dtype=cdt, device=dev)
+            ops.swish_mask_fwd(count, z, None, T, Mg, C)
+            return _ConvCore(g, cc, bmean, brstd, count), z
+        if not training:
+            ops.bn_eval_stats(bn.running_mean, bn.running_var, bmean, brstd, bn.eps, C)
+        elif S.bn_world > 1:  # sums and count in one exchange; the global count stays on the device
+            self._sync_stats(stats[: 2 * C + 1])
+            count = stats[2 * C: 2 * C + 1]
+        z = self._new(Mg, C, dtype=cdt, device=dev)
+        if training:
+            # (two launches on purpose: the one-launch form, mi355x_bn_stats_swish_fwd, makes EVERY workgroup derive the
+            #  coefficients of its channels from the f64 sums and measured 31 us against 15.5 us for this pair,
+            #  tools/bn_bench.py)
+            ops.bn_finalize(stats, count, bmean, brstd, bn.running_mean, bn.running_var, bn.momentum, bn.eps, C)
+        ops.bn_swish_fwd(cc, bmean, brstd, bn.weight, bn.bias, z, Mg, C)
+        return _ConvCore(g, cc, bmean, brstd, count), z
+
     def _layer_fwd(self, i, L, x, S, W, Wf, drop):
-        B, F_, T, T1, F1, T2, F2, M, cdt, training, seed = S.dims
+        B, T2, M, cdt = S.B, S.T2, S.M, S.cdt
         dev = x.device
-        d, H, dk, dff = self.d_model, self.n_heads, self.d_k, self.d_ff
-        P = 2 * T2 - 1
-        Tp, Pp = _pad8(T2), _pad8(P)
-        sl = _Saved()
+        d, dk = self.d_model, self.d_k
         site = i * 16
-        pk = getattr(S, "pk", None)
-        Mg, cu = M, (pk.cu if pk is not None else None)   # Mg: rows of the padded [B, T'] grid (conv core, statistics)
+        pk = S.pk
+        cu = pk.cu if pk is not None else None
         if pk is not None:
-            M = pk.Mp                                     # rows of the packed chain
+            M = pk.Mp   # rows of the packed chain; S.M stays the rows of the padded [B, T'] grid (conv core, statistics)
         # ---- macaron FFN 1
-        r1 = self._ffn_fwd(f"L{i}.ff1", L.feed_forward1, x, L.norm_feed_forward1, S, sl, W, drop, site, M, d, dff, cdt, dev, "ff1")
+        pre, S.pre_ln = S.pre_ln, None
+        r1, ff1 = self._ffn_fwd(f"L{i}.ff1", L.feed_forward1, x, L.norm_feed_forward1, S, W, drop, site, M, pre=pre)
         # ---- rel-pos multi-head self-attention
         a = L.self_attn
         y2, mean2, rstd2 = self._ln_fwd(L.norm_self_att, r1, M, d, cdt, dev)
@@ -1727,73 +1833,30 @@ class ConformerEncoder(NeuralModule):
         p = S.p_all[i]  # linear_pos(pos_emb) of every layer was computed by one batched GEMM (same input, 18 weights)
         d_att = drop(self.dropout_att, site + 2)
         bu, bv = (a.pos_bias_u, a.pos_bias_v) if dkp == dk else (Wf[f"L{i}.att.bu"], Wf[f"L{i}.att.bv"])
-        ctx, (qu, qv, s_, pd, lse) = self._attn_fwd(qkv, p, bu, bv, S.len2, B, T2, dA, dkp, 1.0 / math.sqrt(dk), d_att, cdt, dev,
-                                                    pk=pk)
+        ctx, core = self._attn_fwd(S, qkv, p, bu, bv, S.len2, B, T2, dA, dkp, d_att, pk=pk)
         r2 = self._new(M, d, dtype=torch.float32, device=dev)
         d_ares = drop(self.dropout, site + 3)
         ops.gemm(ctx, W[f"L{i}.att.wo"], r2, M, d, dA, dA, W.pitch(f"L{i}.att.wo"), d, bias=a.linear_out.bias, epi=ops.EPI_RESID,
                  aux_in=r1, drop=d_ares)
-        sl.att = (r1, y2, mean2, rstd2, qkv, p, qu, qv, s_, pd, ctx, d_att, d_ares, lse)
-        # ---- convolution module
+        att = _AttSaved(r1, y2, mean2, rstd2, qkv, p, core, ctx, d_att, d_ares)
+        # ---- convolution module (its core stays on the padded grid: BatchNorm counts padded frames)
         c = L.conv
-        k = self.conv_kernel_size
         y3, mean3, rstd3 = self._ln_fwd(L.norm_conv, r2, M, d, cdt, dev)
         pw1 = self._new(M, 2 * d, dtype=cdt, device=dev)
         ops.gemm(y3, W[f"L{i}.conv.pw1"], pw1, M, 2 * d, d, d, W.pitch(f"L{i}.conv.pw1"), 2 * d, bias=c.pointwise_conv1.bias)
-        g = self._new(Mg, d, dtype=cdt, device=dev)   # the conv core stays on the padded grid (BatchNorm counts padded frames)
-        padl = self.conv_pad_left                      # -1: symmetric padding; else CausalConv1D's left pad (the fused GLU form is symmetric)
-        fuse_glu = self.fuse_glu_dwconv_fwd and d % (8 if cdt == torch.bfloat16 else 4) == 0 and padl < 0
-        if not fuse_glu:
-            ops.glu_fwd(pw1, g, S.len2, T2, Mg, d, cu=cu)
-        cc = self._new(Mg, d, dtype=cdt, device=dev)
-        bn = c.batch_norm
-        bmean = self._new(d, dtype=torch.float32, device=dev)
-        brstd = self._new(d, dtype=torch.float32, device=dev)
-        count = float(Mg)
-        if self.conv_norm_type == "layer_norm":
-            # nn.LayerNorm over the channels of every frame instead of BatchNorm (conformer_modules.py:335-338): depthwise conv without
-            # statistics -> LayerNorm -> Swish; per-frame mean / rstd and the normalised frames travel in the BatchNorm slots
-            if fuse_glu:
-                ops.dwconv_fwd_glu(pw1, S.len2, cu, g, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, None, B, T2, d, k)
-            else:
-                ops.dwconv_fwd(g, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, None, B, T2, d, k, pad_left=padl)
-            count, bmean, brstd = self._ln_fwd(bn, cc, Mg, d, cdt, dev)   # (yln, mean, rstd)
-            z = self._new(Mg, d, dtype=cdt, device=dev)
-            ops.swish_mask_fwd(count, z, None, T2, Mg, d)
-        elif training:
-            stats = S.bn_stats[i]
-            if fuse_glu:   # GLU + pad mask applied while the depthwise forward stages its tile (g is written for backward, not re-read)
-                ops.dwconv_fwd_glu(pw1, S.len2, cu, g, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, stats, B, T2, d, k)
-            else:
-                ops.dwconv_fwd(g, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, stats, B, T2, d, k, pad_left=padl)
-            if S.bn_world > 1:  # sums and count in one exchange; the global count stays on the device
-                self._sync_stats(stats[: 2 * d + 1])
-                count = stats[2 * d: 2 * d + 1]
-        else:
-            if fuse_glu:
-                ops.dwconv_fwd_glu(pw1, S.len2, cu, g, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, None, B, T2, d, k)
-            else:
-                ops.dwconv_fwd(g, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, None, B, T2, d, k, pad_left=padl)
-            ops.bn_eval_stats(bn.running_mean, bn.running_var, bmean, brstd, bn.eps, d)
-        if self.conv_norm_type == "batch_norm":
-            z = self._new(Mg, d, dtype=cdt, device=dev)
-            if training:
-                # (two launches on purpose: the one-launch form, mi355x_bn_stats_swish_fwd, makes EVERY workgroup derive the
-                #  coefficients of its channels from the f64 sums and measured 31 us against 15.5 us for this pair,
-                #  tools/bn_bench.py)
-                ops.bn_finalize(stats, count, bmean, brstd, bn.running_mean, bn.running_var, bn.momentum, bn.eps, d)
-            ops.bn_swish_fwd(cc, bmean, brstd, bn.weight, bn.bias, z, Mg, d)
+        ccore, z = self._conv_core_fwd(S, i, c, pw1, S.len2, B, T2, d, act=0, pad_left=self.conv_pad_left, cu=cu,
+                                       norm=self.conv_norm_type)
         if pk is not None:   # the valid frames of the core's output rejoin the packed chain (z is also the pw2 weight gradient's operand)
             zp = self._new(M, d, dtype=cdt, device=dev)
-            ops.rows_pack(z, zp, S.len2, cu, T2, Mg, d)
+            ops.rows_pack(z, zp, S.len2, cu, T2, S.M, d)
             z = zp
         r3 = self._new(M, d, dtype=torch.float32, device=dev)
         d_cres = drop(self.dropout, site + 4)
         ops.gemm(z, W[f"L{i}.conv.pw2"], r3, M, d, d, d, W.pitch(f"L{i}.conv.pw2"), d, bias=c.pointwise_conv2.bias,
                  epi=ops.EPI_RESID, aux_in=r2, drop=d_cres)
-        sl.conv = (r2, y3, mean3, rstd3, pw1, g, cc, bmean, brstd, count, z, d_cres)
+        conv = _ConvSaved(r2, y3, mean3, rstd3, pw1, ccore, z, d_cres)
         # ---- macaron FFN 2 + output norm
-        r4 = self._ffn_fwd(f"L{i}.ff2", L.feed_forward2, r3, L.norm_feed_forward2, S, sl, W, drop, site + 5, M, d, dff, cdt, dev, "ff2")
+        r4, ff2 = self._ffn_fwd(f"L{i}.ff2", L.feed_forward2, r3, L.norm_feed_forward2, S, W, drop, site + 5, M)
         nxt = self.layers[i + 1] if i + 1 < self.n_layers else None
         if nxt is not None and d == 512 and self.fuse_layer_boundary_norms:
             # norm_out of this layer and norm_feed_forward1 of the next one in one pass over the rows (mi355x_layernorm2_fwd)
@@ -1802,11 +1865,10 @@ class ConformerEncoder(NeuralModule):
             yn = self._new(M, d, dtype=cdt, device=dev)
             mean5, rstd5, mean_n, rstd_n = (self._new(M, dtype=torch.float32, device=dev) for _ in range(4))
             ops.layernorm2_fwd(r4, ln1.weight, ln1.bias, xo, mean5, rstd5, ln2.weight, ln2.bias, yn, mean_n, rstd_n, M, d, ln1.eps)
-            S.pre_ln = (yn, mean_n, rstd_n)
+            S.pre_ln = _PreNorm(yn, mean_n, rstd_n)
         else:
             xo, mean5, rstd5 = self._ln_fwd(L.norm_out, r4, M, d, torch.float32, dev)
-        sl.out = (r4, mean5, rstd5)
-        return xo, sl
+        return xo, _LayerSaved(ff1, att, conv, ff2, _LnSaved(r4, mean5, rstd5))
 
     @staticmethod
     def _dp_world():
@@ -1883,20 +1945,20 @@ class ConformerEncoder(NeuralModule):
         return scope()
 
     def _check_serial(self, S):
-        if getattr(S, "arena", False) and S.serial != self._fwd_serial:
+        if S.arena and S.serial != self._fwd_serial:
             raise RuntimeError("backward through an encoder forward whose saved activations were overwritten by a later forward "
                                "(the sequencer's tensors live in a step-scoped arena); set MI355X_ARENA=0 (and MI355X_GRAPHS=0) for "
                                "several forwards per backward")
 
     def _backward_impl(self, S, dout, dcaps=()):
-        B, F_, T, T1, F1, T2, F2, M, cdt, training, seed = S.dims
+        B, T1, F1, T2, F2, M, cdt = S.B, S.T1, S.F1, S.T2, S.F2, S.M, S.cdt
         dev = dout.device
         self._check_serial(S)
         self._phase("b", dev)
         d, C_ = self.d_model, self.pre_encode._conv_channels
         W, Wf = self._plan(cdt, dev)
         fp = self._flatp
-        pk = getattr(S, "pk", None)
+        pk = S.pk
 
         def to_rows(g, key):  # gradient of a [B, D, T'] output -> rows of the layers' residual stream (through out_proj, packed)
             if self.out_proj is not None:
@@ -1911,7 +1973,7 @@ class ConformerEncoder(NeuralModule):
             return gx
 
         dx = to_rows(dout, "final")
-        cap_grads = {l: g for l, g in zip(getattr(S, "cap_layers", []), dcaps) if g is not None}
+        cap_grads = {l: g for l, g in zip(S.cap_layers, dcaps) if g is not None}
         P = 2 * T2 - 1
         dA = self._geometry(cdt)[2]
         S.dp_all = self._buf("dp_all", (self.n_layers, P, dA), cdt, dev)
@@ -1949,17 +2011,17 @@ class ConformerEncoder(NeuralModule):
         for i in range(self.n_layers - 1, -1, -1):
             if i in cap_grads:  # InterCTC: the gradient of the captured output of layer i joins the stream here
                 dx = dx + to_rows(cap_grads[i], i)
-            sd = S.sd[i] if getattr(S, "sd", None) else None
+            sd = S.sd[i] if S.sd else None
             if sd is None:
                 dx = self._layer_bwd(i, self.layers[i], dx, S, S.layers[i], W, Wf)
-            elif sd[0] == "drop":
+            elif sd == 0.0:
                 # a dropped layer contributed x * 0: its backward runs on a zero gradient (every weight gets its -- zero --
                 # gradient, the per-layer hooks and accumulators see the usual sequence), the stream's gradient passes by
                 self._layer_bwd(i, self.layers[i], torch.zeros_like(dx), S, S.layers[i], W, Wf)
             else:
                 # kept and rescaled: x_in + a (L(x_in) - x_in)
-                din = self._layer_bwd(i, self.layers[i], dx * sd[1], S, S.layers[i], W, Wf)
-                dx = torch.add(din, dx, alpha=1.0 - sd[1])
+                din = self._layer_bwd(i, self.layers[i], dx * sd, S, S.layers[i], W, Wf)
+                dx = torch.add(din, dx, alpha=1.0 - sd)
             S.layers[i] = None
             if defer:
                 dfr = self._wg_deferred
@@ -1997,7 +2059,7 @@ class ConformerEncoder(NeuralModule):
                 # not see the range before they landed -- the same join the per-layer hooks get (layer_done)
                 self._wgrad_join(consume=True)
             self._hook(*fp.tail_range())
-        if getattr(S, "bypass", False):   # pre-encoded input: no sub-sampling stack behind the layers (its gradients stay zero)
+        if S.bypass:   # pre-encoded input: no sub-sampling stack behind the layers (its gradients stay zero)
             return None
         # ---- sub-sampling backward
         pe = self.pre_encode
@@ -2065,17 +2127,19 @@ class ConformerEncoder(NeuralModule):
         if self.grad_ready_hook is not None:
             self._hook(*fp.range_of("pre_encode."))
 
-    def _ffn_bwd(self, pfx, ff, ln, saved, dr, W, M, d, dff, cdt, dev, df=None, next_cast=None, boundary=None):
-        """`df` = the already cast / dropped / scaled residual-branch gradient when the previous LayerNorm backward produced
+    def _ffn_bwd(self, pfx, ff, ln, saved, dr, S, W, M, df=None, next_cast=None, boundary=None):
+        """backward of _ffn_fwd (`saved`: its _FfSaved) on the M rows of the residual gradient dr; S gives the compute dtype.
+        `df` = the already cast / dropped / scaled residual-branch gradient when the previous LayerNorm backward produced
         it in its own pass; `next_cast` = (scale, Dropout) of the sub-block that follows in backward order: this block's
-        LayerNorm backward then emits that operand too.  `boundary` = (norm_out module, r4, mean5, rstd5) of the layer BELOW when
+        LayerNorm backward then emits that operand too.  `boundary` = (norm_out module, its _LnSaved) of the layer BELOW when
         this is a layer's first feed-forward block: its LayerNorm backward and that norm_out's run as one kernel
         (mi355x_layernorm2_bwd), the returned dr is then already the gradient w.r.t. the lower layer's r4.
         Returns (dr, cast_for_next_or_None)."""
-        x, y, mean, rstd, h, a, d_in, d_res = saved
+        d, dff, cdt, dev = self.d_model, self.d_ff, S.cdt, dr.device
+        x, y, h, a, d_in = saved.x, saved.y, saved.h, saved.a, saved.d_in
         if df is None:
             df = self._new(M, d, dtype=cdt, device=dev)
-            ops.drop_scale_cast(dr, df, M * d, 0.5, d_res)
+            ops.drop_scale_cast(dr, df, M * d, 0.5, saved.d_res)
         dh = self._new(M, dff, dtype=cdt, device=dev)
         dy = self._new(M, d, dtype=cdt, device=dev)
         if a is None:  # fused forward: the input-gradient chain in one launch, which also re-creates linear2's weight-gradient operand
@@ -2093,14 +2157,14 @@ class ConformerEncoder(NeuralModule):
             ops.gemm(dh, W[pfx + ".w1t"], dy, M, d, dff, dff, W.pitch(pfx + ".w1t"), d)
         nxt = self._cast_buf(next_cast, M, d, cdt, dev)
         if boundary is not None:
-            ln_lo, r4, mean5, rstd5 = boundary
+            ln_lo, lo = boundary
             dr_lo = self._new(M, d, dtype=torch.float32, device=dev)
-            ops.layernorm2_bwd(dy, x, ln.weight, mean, rstd, ln.weight.grad, ln.bias.grad, dr, r4, ln_lo.weight, mean5, rstd5,
-                               ln_lo.weight.grad, ln_lo.bias.grad, dr_lo, M, d, cast_out=nxt,
+            ops.layernorm2_bwd(dy, x, ln.weight, saved.mean, saved.rstd, ln.weight.grad, ln.bias.grad, dr, lo.x, ln_lo.weight, lo.mean,
+                               lo.rstd, ln_lo.weight.grad, ln_lo.bias.grad, dr_lo, M, d, cast_out=nxt,
                                cast_scale=next_cast[0] if nxt is not None else 1.0,
                                cast_drop=next_cast[1] if nxt is not None else None)
             return dr_lo, nxt
-        ops.layernorm_bwd(dy, x, ln.weight, mean, rstd, dr, True, ln.weight.grad, ln.bias.grad, M, d, cast_out=nxt,
+        ops.layernorm_bwd(dy, x, ln.weight, saved.mean, saved.rstd, dr, True, ln.weight.grad, ln.bias.grad, M, d, cast_out=nxt,
                           cast_scale=next_cast[0] if nxt is not None else 1.0,
                           cast_drop=next_cast[1] if nxt is not None else None)
         return dr, nxt
@@ -2112,17 +2176,19 @@ class ConformerEncoder(NeuralModule):
             return None
         return self._new(M, d, dtype=cdt, device=dev)
 
-    def _attn_block_bwd(self, i, a, saved, dao, S, W, M, B, T2, d, dk, scale, cdt, dev):
-        """linear_out -> attention core -> q | k | v projections, backward (heads of width d_k % 8 == 0, or fp32)"""
-        r1, y2, mean2, rstd2, qkv, p, qu, qv, s_, pd, ctx, d_att, d_ares, lse = saved
+    def _attn_block_bwd(self, i, a, att, dao, S, W, M):
+        """linear_out -> attention core -> q | k | v projections, backward (heads of width d_k % 8 == 0, or fp32); att: the block's
+        _AttSaved, dao [M, d]: the gradient w.r.t. linear_out's output as a GEMM operand"""
+        cdt, dev, d = S.cdt, dao.device, self.d_model
+        ctx, y2, lse = att.ctx, att.y, att.core.lse
         self._wgrad(dao, d, 0, ctx, d, 0, a.linear_out.weight.grad, d, d, M, bias_grad=a.linear_out.bias.grad)
         dctx = self._new(M, d, dtype=cdt, device=dev)
         ops.gemm(dao, W[f"L{i}.att.wot"], dctx, M, d, d, d, W.pitch(f"L{i}.att.wot"), d)
         gu, gv_ = a.pos_bias_u.grad, a.pos_bias_v.grad
         adjacent = gv_.data_ptr() - gu.data_ptr() == 4 * d  # (the two bias gradients as one [2 * d] piece of the flat buffer)
-        dqkv, dqu, dqv = self._attn_bwd((qu, qv, s_, pd, lse), qkv, p, a.pos_bias_u, a.pos_bias_v, ctx, dctx, S.len2, B, T2, d,
-                                        dk, scale, d_att, cdt, dev, S.dpos_f32[i], S.dp_all[i],
-                                        bias_grads=gu if (adjacent and lse is not None) else None, pk=getattr(S, "pk", None))
+        dqkv, dqu, dqv = self._attn_bwd(S, att.core, att.qkv, att.p, a.pos_bias_u, a.pos_bias_v, ctx, dctx, S.len2, S.B, S.T2, d,
+                                        self.d_k, att.d_att, S.dpos_f32[i], S.dp_all[i],
+                                        bias_grads=gu if (adjacent and lse is not None) else None, pk=S.pk)
         if dqu is None:
             pass  # fused attention: dq and both bias gradients came out of the dQ kernel
         elif cdt == torch.bfloat16 and adjacent:
@@ -2153,21 +2219,25 @@ class ConformerEncoder(NeuralModule):
         ops.gemm(dqkv, W[f"L{i}.att.wqkvt"], dy2, M, d, 3 * d, 3 * d, W.pitch(f"L{i}.att.wqkvt"), d)
         return dy2
 
-    def _attn_block_bwd_padded(self, i, a, saved, dao, S, W, Wf, M, B, T2, d, dk, dkp, dA, scale, cdt, dev):
-        """the same with zero-padded heads (bf16, d_k % 8 != 0): the heads' weight gradients are TN GEMMs batched over the heads
-        whose strides step over the pad lanes, bias-sized gradients are summed in the padded layout and added back without it"""
-        r1, y2, mean2, rstd2, qkv, p, qu, qv, s_, pd, ctx, d_att, d_ares, lse = saved
-        H = self.n_heads
-        P = 2 * T2 - 1
+    # ---- projections around the attention core with zero-padded heads, backward (shared with Squeezeformer).  The core's own
+    # backward (_attn_bwd) runs between the two halves, at the call site: the encoders differ in where its dp buffers come from.
+    def _heads_out_wgrad(self, a, dao, ctx, M, ldx=None):
+        """d linear_out.weight[:, h*dk:(h+1)*dk] += dao^T @ ctx[:, h*dkp : +dk] as one TN GEMM batched over the heads (its strides
+        step over the pad lanes); d linear_out.bias += column sums of dao.  ldx: row pitch of dao (None: d_model)"""
+        d, H, dk = self.d_model, self.n_heads, self.d_k
+        _, dkp, dA = self._geometry(dao.dtype)
         with self._wgrad_scope(dao, ctx):
-            ops.gemm(dao, ctx, a.linear_out.weight.grad, d, dk, M, d, dA, d, transA=True, transB=True, atomic=True,
-                     splitk=self._splitk(self._tiles(d, dk, True) * H, M), batch=H, nb0=H, sB=(dkp, 0), sC=(dk, 0),
-                     c_dtype=ops.F32)
-            ops.colsum(dao, a.linear_out.bias.grad, M, d)
-        dctx = self._new(M, dA, dtype=cdt, device=dev)
-        ops.gemm(dao, W[f"L{i}.att.wot"], dctx, M, dA, d, d, W.pitch(f"L{i}.att.wot"), dA)
-        dqkv, dqu, dqv = self._attn_bwd((qu, qv, s_, pd, lse), qkv, p, Wf[f"L{i}.att.bu"], Wf[f"L{i}.att.bv"], ctx, dctx, S.len2, B,
-                                        T2, dA, dkp, scale, d_att, cdt, dev, S.dpos_f32[i], S.dp_all[i], pk=getattr(S, "pk", None))
+            ops.gemm(dao, ctx, a.linear_out.weight.grad, d, dk, M, ldx or d, dA, d, transA=True, transB=True, atomic=True,
+                     splitk=self._splitk(self._tiles(d, dk, dao.dtype == torch.bfloat16) * H, M), batch=H, nb0=H, sB=(dkp, 0),
+                     sC=(dk, 0), c_dtype=ops.F32)
+            ops.colsum(dao, a.linear_out.bias.grad, M, d, ld=ldx)
+
+    def _heads_qkv_grads(self, a, dqkv, dqu, dqv, y, M, ldx=None):
+        """behind _attn_bwd: pos_bias_u / pos_bias_v gradients (bias-sized gradients are summed in the padded layout and added back
+        without the pad lanes), dq = dqu + dqv into the q third of dqkv, then the q | k | v weight gradients (TN GEMMs batched over
+        the heads) and bias gradients.  y: the projections' input, ldx: its row pitch (None: d_model)"""
+        dev, ldx = dqkv.device, ldx or self.d_model
+        _, dkp, dA = self._geometry(dqkv.dtype)
         sc = torch.zeros(2, dA, dtype=torch.float32, device=dev)
         ops.colsum(dqu, sc[0], M, dA)
         ops.colsum(dqv, sc[1], M, dA)
@@ -2178,151 +2248,169 @@ class ConformerEncoder(NeuralModule):
         gq, gk, gvw = (lin.weight.grad for lin in lins)
         sw = (gk.data_ptr() - gq.data_ptr()) // 4
         if sw > 0 and (gvw.data_ptr() - gk.data_ptr()) // 4 == sw:
-            self._heads_wgrad(dqkv, 3 * dA, 0, y2, d, gq, M, 3, dA, sw)
+            self._heads_wgrad(dqkv, 3 * dA, 0, y, ldx, gq, M, 3, dA, sw)
         else:
             for j, lin in enumerate(lins):
-                self._heads_wgrad(dqkv, 3 * dA, j * dA, y2, d, lin.weight.grad, M, 1, 0, 0)
+                self._heads_wgrad(dqkv, 3 * dA, j * dA, y, ldx, lin.weight.grad, M, 1, 0, 0)
         sb = torch.zeros(3 * dA, dtype=torch.float32, device=dev)
         with self._wgrad_scope(dqkv, sb):
             ops.colsum(dqkv, sb, M, 3 * dA)
             for j, lin in enumerate(lins):
                 self._unpad_add(lin.bias.grad, sb[j * dA:(j + 1) * dA], dkp)
+        return sc, sb   # (the callers release the two scratch sums where they always have: see _conv_core_bwd)
+
+    def _attn_block_bwd_padded(self, i, a, att, dao, S, W, Wf, M):
+        """_attn_block_bwd with zero-padded heads (bf16, d_k % 8 != 0)"""
+        cdt, dev, d = S.cdt, dao.device, self.d_model
+        _, dkp, dA = self._geometry(cdt)
+        self._heads_out_wgrad(a, dao, att.ctx, M)
+        dctx = self._new(M, dA, dtype=cdt, device=dev)
+        ops.gemm(dao, W[f"L{i}.att.wot"], dctx, M, dA, d, d, W.pitch(f"L{i}.att.wot"), dA)
+        dqkv, dqu, dqv = self._attn_bwd(S, att.core, att.qkv, att.p, Wf[f"L{i}.att.bu"], Wf[f"L{i}.att.bv"], att.ctx, dctx, S.len2,
+                                        S.B, S.T2, dA, dkp, att.d_att, S.dpos_f32[i], S.dp_all[i], pk=S.pk)
+        sums = self._heads_qkv_grads(a, dqkv, dqu, dqv, att.y, M)   # noqa: F841 (released with this frame)
         dy2 = self._new(M, d, dtype=cdt, device=dev)
         ops.gemm(dqkv, W[f"L{i}.att.wqkvt"], dy2, M, d, 3 * dA, 3 * dA, W.pitch(f"L{i}.att.wqkvt"), d)
         return dy2
 
+    def _conv_core_bwd(self, S, i, c, core, pw1, dz, lens, B, T, C, *, act, pad_left=-1, cu=None, norm="batch_norm", side=False):
+        """backward of _conv_core_fwd (same S, i, c, pw1, lens, B, T, C, act, pad_left, cu, norm; `core`: its _ConvCore):
+        dz [B*T, C] -> the gradient w.r.t. pw1; the norm's and the depthwise conv's parameter gradients are accumulated.
+        side: the second stage of the depthwise tap / bias gradients goes to the weight-gradient stream.
+        _defer_point 5 / 6 sit inside the core; they do nothing unless _backward_impl has a deferred grouped launch waiting.
+        -> (dpw1, the core's temporaries): the caller holds the temporaries to the end of the layer's backward, where they have
+        always been released -- off the step arena an earlier release changes which blocks the caching allocator hands out next."""
+        Mg, k, cdt, dev, training = B * T, self.conv_kernel_size, S.cdt, dz.device, S.training
+        bn, dw = c.batch_norm, c.depthwise_conv
+        g, cc, bmean, brstd, count = core.g, core.cc, core.bmean, core.brstd, core.count
+        sums = S.bn_sums[i]
+        ln_norm = norm == "layer_norm"
+        if not ln_norm:
+            ops.bn_swish_bwd_reduce(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, Mg, C, dgamma=bn.weight.grad, dbeta=bn.bias.grad)
+            if training and S.bn_world > 1:
+                self._sync_stats(sums)
+        self._defer_point(5)   # (experimental entry points of the weight-gradient launch: behind the BatchNorm reduction ...)
+        dpw1 = self._new(*pw1.shape, dtype=cdt, device=dev)
+
+        def act_bwd(dg):
+            if act == 0:
+                ops.glu_bwd(pw1, dg, dpw1, lens, T, Mg, C, cu=cu)
+            else:
+                ops.swish_mask_bwd(pw1, dg, dpw1, lens, T, Mg, C)
+
+        if ln_norm:
+            # Swish -> LayerNorm -> depthwise conv -> activation, backwards (see _ConvCore for what count / bmean / brstd hold)
+            dyln = self._new(Mg, C, dtype=cdt, device=dev)
+            ops.swish_mask_bwd(count, dz, dyln, None, T, Mg, C)
+            dcc32 = self._new(Mg, C, dtype=torch.float32, device=dev)
+            if cdt == torch.bfloat16:
+                dcc = self._new(Mg, C, dtype=cdt, device=dev)
+                ops.layernorm_bwd(dyln, cc, bn.weight, bmean, brstd, dcc32, False, bn.weight.grad, bn.bias.grad, Mg, C, cast_out=dcc)
+            else:
+                ops.layernorm_bwd(dyln, cc, bn.weight, bmean, brstd, dcc32, False, bn.weight.grad, bn.bias.grad, Mg, C)
+                dcc = dcc32
+            dg = self._new(Mg, C, dtype=cdt, device=dev)
+            ops.dwconv_bwd(dcc, g, dw.weight, dg, dw.weight.grad, dw.bias.grad, B, T, C, k, pad_left=pad_left)
+            self._defer_point(6)
+            act_bwd(dg)
+            tmp = (dyln, dcc32, dcc, dg)
+        elif self.fuse_bn_dwconv_bwd and self.fuse_glu_dwconv_bwd and pad_left < 0:
+            # BatchNorm + Swish backward applied while the depthwise backward stages its gradient tile, the activation's backward
+            # while it writes its result: one launch for four, and neither the [B, T', C] gradient w.r.t. the BatchNorm input nor the
+            # one w.r.t. the activation's output is written or read back
+            sc = ops.dwconv_tap_scratch(i, B, C, k, dev) if side else None   # (its own slabs per layer: the reduction runs later)
+            ops.dwconv_bwd_bnswish(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, count, training, g, dw.weight, None, dw.weight.grad,
+                                   dw.bias.grad, B, T, C, k, glu_in=pw1, glu_din=dpw1, glu_len=lens, glu_cu=cu, scratch=sc,
+                                   defer_reduce=side, glu_act=act)
+            if side:
+                # the second stage of the tap / bias gradient: nothing on the chain reads it -- it joins the weight-gradient stream
+                with self._wgrad_scope(sc, dw.weight.grad):
+                    ops.dwconv_tap_reduce(sc, B, C, k, dw.weight.grad, dw.bias.grad)
+            self._defer_point(6)
+            tmp = ()
+        else:
+            dg, dcc = self._new(Mg, C, dtype=cdt, device=dev), None
+            if self.fuse_bn_dwconv_bwd and pad_left < 0:
+                ops.dwconv_bwd_bnswish(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, count, training, g, dw.weight, dg, dw.weight.grad,
+                                       dw.bias.grad, B, T, C, k)
+            else:
+                dcc = self._new(Mg, C, dtype=cdt, device=dev)
+                ops.bn_swish_bwd_apply(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, count, training, dcc, Mg, C)
+                ops.dwconv_bwd(dcc, g, dw.weight, dg, dw.weight.grad, dw.bias.grad, B, T, C, k, pad_left=pad_left)
+            self._defer_point(6)   # (... and behind the depthwise backward, beside the activation's backward and the pointwise dgrad GEMM)
+            act_bwd(dg)
+            tmp = (dg, dcc)
+        return dpw1, tmp
+
     def _layer_bwd(self, i, L, dxo, S, sl, W, Wf):
-        B, F_, T, T1, F1, T2, F2, M, cdt, training, seed = S.dims
+        B, T2, M, cdt = S.B, S.T2, S.M, S.cdt
         dev = dxo.device
-        d, H, dk, dff = self.d_model, self.n_heads, self.d_k, self.d_ff
-        P = 2 * T2 - 1
-        Tp, Pp = _pad8(T2), _pad8(P)
-        scale = 1.0 / math.sqrt(dk)
-        pk = getattr(S, "pk", None)
-        Mg, cu = M, (pk.cu if pk is not None else None)   # Mg: rows of the padded grid (conv core); M: rows of the (packed) chain
+        d, dk = self.d_model, self.d_k
+        pk = S.pk
+        cu = pk.cu if pk is not None else None
         if pk is not None:
-            M = pk.Mp
+            M = pk.Mp   # rows of the (packed) chain; S.M stays the rows of the padded grid (conv core)
         # ---- norm_out: dr = dLN(dxo)
-        r4, mean5, rstd5 = sl.out
-        pre = getattr(S, "pre_bwd", None)
+        pre, S.pre_bwd = S.pre_bwd, None
         if pre is not None:  # the layer above ran this LayerNorm backward together with its own norm_feed_forward1's
-            dr, df2 = pre
-            S.pre_bwd = None
+            dr, df2 = pre.dr, pre.cast
         else:
             dr = self._new(M, d, dtype=torch.float32, device=dev)
             ln = L.norm_out
             # every LayerNorm backward also emits the bf16 (scaled, dropped) copy of the new residual gradient that the next
             # sub-block's output GEMMs consume -- one read of the fp32 gradient and one launch less per sub-block
-            nc = (0.5, sl.ff2[7])
+            nc = (0.5, sl.ff2.d_res)
             df2 = self._cast_buf(nc, M, d, cdt, dev)
-            ops.layernorm_bwd(dxo, r4, ln.weight, mean5, rstd5, dr, False, ln.weight.grad, ln.bias.grad, M, d, cast_out=df2,
-                              cast_scale=0.5, cast_drop=nc[1] if df2 is not None else None)
+            ops.layernorm_bwd(dxo, sl.out.x, ln.weight, sl.out.mean, sl.out.rstd, dr, False, ln.weight.grad, ln.bias.grad, M, d,
+                              cast_out=df2, cast_scale=0.5, cast_drop=nc[1] if df2 is not None else None)
         # ---- FFN 2
-        dr, db_pre = self._ffn_bwd(f"L{i}.ff2", L.feed_forward2, L.norm_feed_forward2, sl.ff2, dr, W, M, d, dff, cdt, dev,
-                                   df=df2, next_cast=(1.0, sl.conv[11]))
+        cv = sl.conv
+        dr, db = self._ffn_bwd(f"L{i}.ff2", L.feed_forward2, L.norm_feed_forward2, sl.ff2, dr, S, W, M, df=df2, next_cast=(1.0, cv.d_res))
         # ---- convolution module
         c = L.conv
-        bn = c.batch_norm
-        k = self.conv_kernel_size
-        r2, y3, mean3, rstd3, pw1, g, cc, bmean, brstd, count, z, d_cres = sl.conv
-        db = db_pre
         if db is None:
             db = self._new(M, d, dtype=cdt, device=dev)
-            ops.drop_scale_cast(dr, db, M * d, 1.0, d_cres)
-        self._wgrad(db, d, 0, z, d, 0, c.pointwise_conv2.weight.grad, d, d, M, bias_grad=c.pointwise_conv2.bias.grad)
+            ops.drop_scale_cast(dr, db, M * d, 1.0, cv.d_res)
+        self._wgrad(db, d, 0, cv.z, d, 0, c.pointwise_conv2.weight.grad, d, d, M, bias_grad=c.pointwise_conv2.bias.grad)
         dz = self._new(M, d, dtype=cdt, device=dev)
         ops.gemm(db, W[f"L{i}.conv.pw2t"], dz, M, d, d, d, W.pitch(f"L{i}.conv.pw2t"), d)
         if pk is not None:   # onto the padded grid of the conv core; frames beyond an utterance carry no gradient
-            dzp = self._new(Mg, d, dtype=cdt, device=dev)
-            ops.rows_unpack(dz, dzp, S.len2, cu, T2, Mg, d)
+            dzp = self._new(S.M, d, dtype=cdt, device=dev)
+            ops.rows_unpack(dz, dzp, S.len2, cu, T2, S.M, d)
             dz = dzp
-        sums = S.bn_sums[i]
-        padl = self.conv_pad_left
         self._defer_point(1)
-        ln_norm = self.conv_norm_type == "layer_norm"
-        if not ln_norm:
-            ops.bn_swish_bwd_reduce(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, Mg, d, dgamma=bn.weight.grad, dbeta=bn.bias.grad)
-            if training and S.bn_world > 1:
-                self._sync_stats(sums)
-        self._defer_point(5)   # (experimental entry points of the weight-gradient launch: behind the BatchNorm reduction ...)
-        dpw1 = self._new(M, 2 * d, dtype=cdt, device=dev)
-        if ln_norm:
-            # Swish -> LayerNorm -> depthwise conv -> GLU, backwards (count / bmean / brstd carry yln / the per-frame mean / rstd)
-            dyln = self._new(Mg, d, dtype=cdt, device=dev)
-            ops.swish_mask_bwd(count, dz, dyln, None, T2, Mg, d)
-            dcc32 = self._new(Mg, d, dtype=torch.float32, device=dev)
-            if cdt == torch.bfloat16:
-                dcc = self._new(Mg, d, dtype=cdt, device=dev)
-                ops.layernorm_bwd(dyln, cc, bn.weight, bmean, brstd, dcc32, False, bn.weight.grad, bn.bias.grad, Mg, d, cast_out=dcc)
-            else:
-                ops.layernorm_bwd(dyln, cc, bn.weight, bmean, brstd, dcc32, False, bn.weight.grad, bn.bias.grad, Mg, d)
-                dcc = dcc32
-            dg = self._new(Mg, d, dtype=cdt, device=dev)
-            ops.dwconv_bwd(dcc, g, c.depthwise_conv.weight, dg, c.depthwise_conv.weight.grad, c.depthwise_conv.bias.grad, B, T2, d, k,
-                           pad_left=padl)
-            self._defer_point(6)
-            ops.glu_bwd(pw1, dg, dpw1, S.len2, T2, Mg, d, cu=cu)
-        elif self.fuse_bn_dwconv_bwd and self.fuse_glu_dwconv_bwd and padl < 0:
-            # BatchNorm + Swish backward applied while the depthwise backward stages its gradient tile, the GLU backward while it
-            # writes its result: one launch for four, and neither the [B, T', d] gradient w.r.t. the BatchNorm input nor the one
-            # w.r.t. the GLU output is written or read back
-            side = self.tap_reduce_side and self.wgrad_side_stream
-            sc = ops.dwconv_tap_scratch(i, B, d, k, dev) if side else None   # (its own slabs per layer: the reduction runs later)
-            ops.dwconv_bwd_bnswish(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, count, training, g, c.depthwise_conv.weight, None,
-                                   c.depthwise_conv.weight.grad, c.depthwise_conv.bias.grad, B, T2, d, k, glu_in=pw1, glu_din=dpw1,
-                                   glu_len=S.len2, glu_cu=cu, scratch=sc, defer_reduce=side)
-            if side:
-                # the second stage of the tap / bias gradient: nothing on the chain reads it -- it joins the weight-gradient stream
-                with self._wgrad_scope(sc, c.depthwise_conv.weight.grad):
-                    ops.dwconv_tap_reduce(sc, B, d, k, c.depthwise_conv.weight.grad, c.depthwise_conv.bias.grad)
-            self._defer_point(6)
-        else:
-            dg = self._new(Mg, d, dtype=cdt, device=dev)
-            if self.fuse_bn_dwconv_bwd and padl < 0:
-                ops.dwconv_bwd_bnswish(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, count, training, g, c.depthwise_conv.weight, dg,
-                                       c.depthwise_conv.weight.grad, c.depthwise_conv.bias.grad, B, T2, d, k)
-            else:
-                dcc = self._new(Mg, d, dtype=cdt, device=dev)
-                ops.bn_swish_bwd_apply(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, count, training, dcc, Mg, d)
-                ops.dwconv_bwd(dcc, g, c.depthwise_conv.weight, dg, c.depthwise_conv.weight.grad, c.depthwise_conv.bias.grad, B, T2, d, k,
-                               pad_left=padl)
-            self._defer_point(6)   # (... and behind the depthwise backward, beside the GLU backward and the pointwise dgrad GEMM)
-            ops.glu_bwd(pw1, dg, dpw1, S.len2, T2, Mg, d, cu=cu)
-        self._wgrad(dpw1, 2 * d, 0, y3, d, 0, c.pointwise_conv1.weight.grad, 2 * d, d, M, bias_grad=c.pointwise_conv1.bias.grad)
+        dpw1, conv_tmp = self._conv_core_bwd(S, i, c, cv.core, cv.pw1, dz, S.len2, B, T2, d, act=0, pad_left=self.conv_pad_left,   # noqa: F841
+                                             cu=cu, norm=self.conv_norm_type, side=self.tap_reduce_side and self.wgrad_side_stream)
+        self._wgrad(dpw1, 2 * d, 0, cv.y, d, 0, c.pointwise_conv1.weight.grad, 2 * d, d, M, bias_grad=c.pointwise_conv1.bias.grad)
         dy3 = self._new(M, d, dtype=cdt, device=dev)
         ops.gemm(dpw1, W[f"L{i}.conv.pw1t"], dy3, M, d, 2 * d, 2 * d, W.pitch(f"L{i}.conv.pw1t"), d)
         ln = L.norm_conv
         self._defer_point(3)
-        nc = (1.0, sl.att[12])
-        dao_pre = self._cast_buf(nc, M, d, cdt, dev)
-        ops.layernorm_bwd(dy3, r2, ln.weight, mean3, rstd3, dr, True, ln.weight.grad, ln.bias.grad, M, d, cast_out=dao_pre,
-                          cast_scale=1.0, cast_drop=nc[1] if dao_pre is not None else None)
+        nc = (1.0, sl.att.d_res)
+        dao = self._cast_buf(nc, M, d, cdt, dev)
+        ops.layernorm_bwd(dy3, cv.x, ln.weight, cv.mean, cv.rstd, dr, True, ln.weight.grad, ln.bias.grad, M, d, cast_out=dao,
+                          cast_scale=1.0, cast_drop=nc[1] if dao is not None else None)
         # ---- self-attention
         a = L.self_attn
-        r1, y2, mean2, rstd2, qkv, p, qu, qv, s_, pd, ctx, d_att, d_ares, lse = sl.att
-        dao = dao_pre
         if dao is None:
             dao = self._new(M, d, dtype=cdt, device=dev)
-            ops.drop_scale_cast(dr, dao, M * d, 1.0, d_ares)
-        _, dkp, dA = self._geometry(cdt)
+            ops.drop_scale_cast(dr, dao, M * d, 1.0, sl.att.d_res)
         self._defer_point(2)
-        if dkp != dk:
-            dy2 = self._attn_block_bwd_padded(i, a, sl.att, dao, S, W, Wf, M, B, T2, d, dk, dkp, dA, scale, cdt, dev)
+        if self._geometry(cdt)[1] != dk:
+            dy2 = self._attn_block_bwd_padded(i, a, sl.att, dao, S, W, Wf, M)
         else:
-            dy2 = self._attn_block_bwd(i, a, sl.att, dao, S, W, M, B, T2, d, dk, scale, cdt, dev)
+            dy2 = self._attn_block_bwd(i, a, sl.att, dao, S, W, M)
         ln = L.norm_self_att
-        nc = (0.5, sl.ff1[7])
+        nc = (0.5, sl.ff1.d_res)
         df1 = self._cast_buf(nc, M, d, cdt, dev)
-        ops.layernorm_bwd(dy2, r1, ln.weight, mean2, rstd2, dr, True, ln.weight.grad, ln.bias.grad, M, d, cast_out=df1,
+        ops.layernorm_bwd(dy2, sl.att.x, ln.weight, sl.att.mean, sl.att.rstd, dr, True, ln.weight.grad, ln.bias.grad, M, d, cast_out=df1,
                           cast_scale=0.5, cast_drop=nc[1] if df1 is not None else None)
         # ---- FFN 1 (its LayerNorm backward together with the norm_out backward of the layer below, where the kernel covers it)
         lo = S.layers[i - 1] if i > 0 else None
         if lo is not None and d == 512 and self.fuse_layer_boundary_norms and self.fuse_boundary_bwd:
-            r4_lo, mean5_lo, rstd5_lo = lo.out
-            dr, df2_lo = self._ffn_bwd(f"L{i}.ff1", L.feed_forward1, L.norm_feed_forward1, sl.ff1, dr, W, M, d, dff, cdt, dev, df=df1,
-                                       next_cast=(0.5, lo.ff2[7]),
-                                       boundary=(self.layers[i - 1].norm_out, r4_lo, mean5_lo, rstd5_lo))
-            S.pre_bwd = (dr, df2_lo)
+            dr, df2_lo = self._ffn_bwd(f"L{i}.ff1", L.feed_forward1, L.norm_feed_forward1, sl.ff1, dr, S, W, M, df=df1,
+                                       next_cast=(0.5, lo.ff2.d_res), boundary=(self.layers[i - 1].norm_out, lo.out))
+            S.pre_bwd = _PreBwd(dr, df2_lo)
             return dr
-        dr, _ = self._ffn_bwd(f"L{i}.ff1", L.feed_forward1, L.norm_feed_forward1, sl.ff1, dr, W, M, d, dff, cdt, dev, df=df1)
+        dr, _ = self._ffn_bwd(f"L{i}.ff1", L.feed_forward1, L.norm_feed_forward1, sl.ff1, dr, S, W, M, df=df1)
         return dr

@@ -19,6 +19,7 @@ from typing import List
 import torch
 
 from .. import ops
+from .conformer_encoder import _Step
 
 
 @dataclass
@@ -95,7 +96,7 @@ def stream_step(enc, mel, length, cache_last_channel, cache_last_time, cache_las
     cdt = enc._cdt()
     if cdt == torch.bfloat16 and enc.d_model % 8:
         raise NotImplementedError(f"bf16 compute needs d_model divisible by 8 (got d_model={enc.d_model})")
-    d, H, dff, K, nl = enc.d_model, enc.n_heads, enc.d_ff, enc.conv_kernel_size, enc.n_layers
+    d, H, K, nl = enc.d_model, enc.n_heads, enc.conv_kernel_size, enc.n_layers
     C = cfg.last_channel_cache_size
     B = mel.shape[0]
     if tuple(cache_last_channel.shape) != (nl, B, C, d):
@@ -114,9 +115,7 @@ def stream_step(enc, mel, length, cache_last_channel, cache_last_time, cache_las
         T2, F2 = T, F_
         for _ in range(enc.pre_encode._sampling_num):
             T2, F2 = ops.half_len(T2, sp), ops.half_len(F2, sp)
-        S = type("S", (), {})()
-        S.dims = (B, F_, T, T1, F1, T2, F2, B * T2, cdt, False, 0)
-        S.drop_pre = ops.NO_DROP
+        S = _Step(B, F_, T, T1, F1, T2, F2, B * T2, cdt)   # (eval, no dropout: the record's defaults)
         # ---- sub-sampling of [pre-encode cache | chunk], then the frames whose receptive field reaches into the padding go
         x = enc._sub_fwd_dw(S, mel, lens, W, cdt, False) if enc.subsampling == "dw_striding" else \
             enc._sub_fwd_striding(S, mel, lens, W, cdt, False)
@@ -136,8 +135,10 @@ def stream_step(enc, mel, length, cache_last_channel, cache_last_time, cache_las
         t_in = cache_last_time.to(torch.float32).contiguous()
         no_drop = lambda p, site: ops.NO_DROP   # noqa: E731
         for i, L in enumerate(enc.layers):
-            S_, sl = type("S", (), {})(), type("S", (), {})()
-            r1 = enc._ffn_fwd(f"L{i}.ff1", L.feed_forward1, x, L.norm_feed_forward1, S_, sl, W, no_drop, 0, M, d, dff, cdt, dev, "ff1")
+            # ff1 / ff2 are never read: the names only fix WHEN the blocks' activations are released (at the top of the next layer,
+            # as before) -- this path runs on torch's caching allocator, where an earlier release changes which blocks come next
+            ff1 = ff2 = None
+            r1, ff1 = enc._ffn_fwd(f"L{i}.ff1", L.feed_forward1, x, L.norm_feed_forward1, S, W, no_drop, 0, M)
             # ---- self-attention against [channel cache | chunk]
             a = L.self_attn
             y2 = enc._ln_fwd(L.norm_self_att, r1, M, d, cdt, dev)[0]
@@ -178,7 +179,7 @@ def stream_step(enc, mel, length, cache_last_channel, cache_last_time, cache_las
             r3 = torch.empty(M, d, dtype=torch.float32, device=dev)
             ops.gemm(z, W[f"L{i}.conv.pw2"], r3, M, d, d, d, W.pitch(f"L{i}.conv.pw2"), d, bias=c.pointwise_conv2.bias,
                      epi=ops.EPI_RESID, aux_in=r2)
-            r4 = enc._ffn_fwd(f"L{i}.ff2", L.feed_forward2, r3, L.norm_feed_forward2, S_, sl, W, no_drop, 5, M, d, dff, cdt, dev, "ff2")
+            r4, ff2 = enc._ffn_fwd(f"L{i}.ff2", L.feed_forward2, r3, L.norm_feed_forward2, S, W, no_drop, 5, M)
             x = enc._ln_fwd(L.norm_out, r4, M, d, torch.float32, dev)[0]
         if enc.out_proj is not None:
             out = enc._out_proj_fwd(x, M, dev).view(B, Tq, enc._feat_out).transpose(1, 2)

@@ -39,8 +39,8 @@ from torch import nn
 
 from .. import ops
 from ..packing import PackPlan
-from .conformer_encoder import (ConformerEncoder, ConvSubsampling, RelPositionalEncoding, _FeedForward, _RelPosMHA, _Saved,
-                                _pad8)
+from .conformer_encoder import (ConformerEncoder, ConvSubsampling, RelPositionalEncoding, _DwGrads, _DwWeights, _FeedForward, _LnSaved,
+                                _RelPosMHA, _Step, _SubIO, _pad8, _record)
 from ..core import NeuralModule
 
 
@@ -108,6 +108,27 @@ class TimeReductionModule(nn.Module):  # subsampling.py:589-656 (parameter layou
 class _Geo:
     """one frame rate of the temporal U-Net: B x T frames, valid lengths, positional table as a GEMM operand"""
     __slots__ = ("B", "T", "M", "lens", "pos", "P")
+
+
+class _SqStep(_Step):
+    """the step record of the Squeezeformer sequencer: + the frame-rate geometry of every layer and the temporal U-Net's detour"""
+    __slots__ = ("geos", "front", "tr", "rec")
+
+    def __init__(self, *grid):
+        super().__init__(*grid)
+        self.geos = []       # per layer: the _Geo it ran on
+        self.front = None    # _LnSaved of pre_ln (x: its input)
+        self.tr = self.rec = None   # _TimeReduce / _TimeRecover when the stages ran
+
+
+_TimeReduce = _record("_TimeReduce", "x geo dwo")     # full-rate input, its _Geo, the depthwise conv's output
+_TimeRecover = _record("_TimeRecover", "xs_c geo")    # the Linear's operand, the half-rate _Geo
+# post-LN sub-blocks: x -> scale / bias -> y -> f -> r = x + dropout d_res (f(y)) -> LayerNorm (mean, rstd) -- layouts of their own, not the
+# Conformer blocks' under the same names (d_in None: h holds swish'(h) * mask; core: _AttnCore / _ConvCore)
+_SqFfSaved = _record("_SqFfSaved", "x y h a d_in d_res r mean rstd")
+_SqAttSaved = _record("_SqAttSaved", "x y qkv p core ctx d_att d_res r mean rstd")
+_SqConvSaved = _record("_SqConvSaved", "x y pw1 core z d_res r mean rstd")
+_SqLayerSaved = _record("_SqLayerSaved", "att ff1 conv ff2")
 
 
 class SqueezeformerEncoder(ConformerEncoder):
@@ -218,11 +239,7 @@ class SqueezeformerEncoder(ConformerEncoder):
         pe = self.pre_encode
         d, F2 = self.d_model, pe._feat_after
         n = len(pe.dw_stages())
-        io = _Saved()
-        io.C = Cp
-        io.c0w, io.c0b = Wf["pre.c0w"], Wf["pre.c0b"]
-        io.dw = [(Wf[f"pre.dw{i}w"], Wf[f"pre.dw{i}b"], Wf[f"pre.pw{i}b"]) for i in range(n)]
-        io.finish = None
+        io = _SubIO(Cp, Wf["pre.c0w"], Wf["pre.c0b"], [_DwWeights(Wf[f"pre.dw{i}w"], Wf[f"pre.dw{i}b"], Wf[f"pre.pw{i}b"]) for i in range(n)])
         if backward:
             sizes = [Cp * 9, Cp] + [Cp * 9, Cp, Cp * Cp, Cp] * n + [d * Cp * F2]
             offs = [0]
@@ -231,17 +248,17 @@ class SqueezeformerEncoder(ConformerEncoder):
             g = torch.zeros(offs[-1], dtype=torch.float32, device=dev)
             v = [g[offs[i]: offs[i] + sizes[i]] for i in range(len(sizes))]
             io.g_c0w, io.g_c0b = v[0], v[1]
-            io.g_dw = [tuple(v[2 + 4 * i: 6 + 4 * i]) for i in range(n)]
+            io.g_dw = [_DwGrads(*v[2 + 4 * i: 6 + 4 * i]) for i in range(n)]
             io.g_out = v[-1]
 
             def finish():  # real part of the padded gradients -> the parameters' gradients
                 pe.conv[0].weight.grad.view(-1).add_(io.g_c0w[: C_ * 9])
                 pe.conv[0].bias.grad.add_(io.g_c0b[:C_])
-                for (dw, pw), (gw, gb, gpw, gpb) in zip(pe.dw_stages(), io.g_dw):
-                    dw.weight.grad.view(-1).add_(gw[: C_ * 9])
-                    dw.bias.grad.add_(gb[:C_])
-                    pw.weight.grad.view(C_, C_).add_(gpw.view(Cp, Cp)[:C_, :C_])
-                    pw.bias.grad.add_(gpb[:C_])
+                for (dw, pw), gr in zip(pe.dw_stages(), io.g_dw):
+                    dw.weight.grad.view(-1).add_(gr.dw_w[: C_ * 9])
+                    dw.bias.grad.add_(gr.dw_b[:C_])
+                    pw.weight.grad.view(C_, C_).add_(gr.pw_w.view(Cp, Cp)[:C_, :C_])
+                    pw.bias.grad.add_(gr.pw_b[:C_])
                 pe.out.weight.grad.add_(io.g_out.view(d, Cp * F2)[:, : C_ * F2])
             io.finish = finish
         return io
@@ -369,21 +386,18 @@ class SqueezeformerEncoder(ConformerEncoder):
         def drop(p, site):
             return ops.Dropout(p if training else 0.0, seed, site)
 
-        S = _Saved()
+        S = _SqStep(B, F_, T, T1, F1, T2, F2, M, cdt, training, seed)
         S.serial, S.arena = self._fwd_serial, self._arena is not None
-        S.dims = (B, F_, T, T1, F1, T2, F2, M, cdt, training, seed)
         S.mel, S.len0, S.len2, S.lens_all = mel, lens[0], lens[-1], lens
         S.drop_pre = drop(self.dropout_pre_encoder, 100000)
         x = self._sub_fwd_dw(S, mel, lens, W, cdt, save, Wf=Wf)
         # ---- pre_ln
         x0, pmean, prstd = self._ln_fwd(self.pre_ln, x, M, d, torch.float32, dev)
-        S.pre_ln = (x, pmean, prstd)
+        S.front = _LnSaved(x, pmean, prstd)
         g_full = self._geo(B, T2, lens[-1], self.pos_enc, drop(self.dropout_emb, 100001), cdt, dev, dp)
         C2 = 2 * d
         S.bn_stats = torch.zeros(self.n_layers, 2 * C2 + 8, dtype=torch.float64, device=dev) if training else None
         S.bn_world = self._syncbn_world() if training else 1
-        S.layers, S.geos = [], []
-        S.tr = S.rec = None
         g = g_full
         x = x0
         for i, L in enumerate(self.layers):
@@ -395,11 +409,11 @@ class SqueezeformerEncoder(ConformerEncoder):
                 ops.time_reduce_dwconv_fwd(x, g.lens, tr.dw_conv.weight, tr.dw_conv.bias, dwo, B, g.T, d, dp)
                 xh = self._new(B * Th, d, dtype=torch.float32, device=dev)
                 ops.gemm(dwo, W["tr.pw"], xh, B * Th, d, d, dp, W.pitch("tr.pw"), d, bias=tr.pw_conv.bias)
-                S.tr = (x, g, dwo)
+                S.tr = _TimeReduce(x, g, dwo)
                 g = self._geo(B, Th, lens_h, self.time_reduce_pos_enc, ops.NO_DROP, cdt, dev, dp)
                 x = xh
             if self.time_reduce_idx is not None and i == self.time_recovery_idx:
-                xs_in, g_skip, _ = S.tr
+                xs_in, g_skip = S.tr.x, S.tr.geo
                 xs_c = self._new(g.M, dp, dtype=cdt, device=dev)
                 ops.scale_bias_fwd(x, None, None, xs_c, g.M, d, dp)
                 ys = self._new(g.M, d, dtype=torch.float32, device=dev)
@@ -407,7 +421,7 @@ class SqueezeformerEncoder(ConformerEncoder):
                 ops.gemm(xs_c, W["rec.w"], ys, g.M, d, d, dp, W.pitch("rec.w"), d, bias=rec.bias)
                 xr = self._new(g_skip.M, d, dtype=torch.float32, device=dev)
                 ops.time_recover_fwd(xs_in, ys, xr, B, g_skip.T, d)
-                S.rec = (xs_c, g)
+                S.rec = _TimeRecover(xs_c, g)
                 g, x = g_skip, xr
             if training and S.bn_world > 1:
                 S.bn_stats[i, 2 * C2] = float(g.M)
@@ -427,8 +441,9 @@ class SqueezeformerEncoder(ConformerEncoder):
     def _post_ln(self, ln, r, M):
         return self._ln_fwd(ln, r, M, self.d_model, torch.float32, r.device)
 
-    def _sq_ffn_fwd(self, pfx, ff, sb, ln, x, g, W, drop, site, cdt, dp):
-        M, d, dff, dev = g.M, self.d_model, self.d_ff, x.device
+    def _sq_ffn_fwd(self, S, pfx, ff, sb, ln, x, g, W, drop, site):
+        M, d, dff, cdt, dev = g.M, self.d_model, self.d_ff, S.cdt, x.device
+        dp = self._geometry(cdt)[0]
         y = self._sb_fwd(sb, x, M, cdt, dp)
         h = self._new(M, dff, dtype=cdt, device=dev)
         a = self._new(M, dff, dtype=cdt, device=dev)
@@ -436,21 +451,17 @@ class SqueezeformerEncoder(ConformerEncoder):
         g_form = self.swish_g and cdt == torch.bfloat16  # `h` then holds swish'(h) * mask (ConformerEncoder.__init__)
         ops.gemm(y, W[pfx + ".w1"], a, M, dff, d, dp, W.pitch(pfx + ".w1"), dff, bias=ff.linear1.bias,
                  epi=ops.EPI_SWISH_DROP_G if g_form else ops.EPI_SWISH_DROP, aux_out=h, drop=d_in)
-        if g_form:
-            d_in = None
         r = self._new(M, d, dtype=torch.float32, device=dev)
         ops.gemm(a, W[pfx + ".w2"], r, M, d, dff, dff, W.pitch(pfx + ".w2"), d, bias=ff.linear2.bias, epi=ops.EPI_RESID,
                  aux_in=x, drop=d_res)  # fc_factor = 1.0 (squeezeformer_modules.py:103)
         xo, mean, rstd = self._post_ln(ln, r, M)
-        return xo, (x, y, h, a, d_in, d_res, r, mean, rstd)
+        return xo, _SqFfSaved(x, y, h, a, None if g_form else d_in, d_res, r, mean, rstd)
 
     def _sq_layer_fwd(self, i, L, x, g, S, W, Wf, drop):
-        B, T, M = g.B, g.T, g.M
-        cdt, training = S.dims[8], S.dims[9]
+        B, T, M, cdt = g.B, g.T, g.M, S.cdt
         dev = x.device
-        d, H, dk = self.d_model, self.n_heads, self.d_k
+        d = self.d_model
         dp, dkp, dA = self._geometry(cdt)
-        sl = _Saved()
         site = i * 16
         # ---- rel-pos multi-head self-attention
         a = L.self_attn
@@ -460,73 +471,39 @@ class SqueezeformerEncoder(ConformerEncoder):
         p = self._new(g.P, dA, dtype=cdt, device=dev)
         ops.gemm(g.pos, W[f"L{i}.att.wpos"], p, g.P, dA, d, dp, W.pitch(f"L{i}.att.wpos"), dA)
         d_att, d_res = drop(self.dropout_att, site + 2), drop(self.dropout, site + 3)
-        bu, bv = Wf[f"L{i}.att.bu"], Wf[f"L{i}.att.bv"]
-        ctx, att_saved = self._attn_fwd(qkv, p, bu, bv, g.lens, B, T, dA, dkp, 1.0 / math.sqrt(dk), d_att, cdt, dev)
+        ctx, core = self._attn_fwd(S, qkv, p, Wf[f"L{i}.att.bu"], Wf[f"L{i}.att.bv"], g.lens, B, T, dA, dkp, d_att)
         r = self._new(M, d, dtype=torch.float32, device=dev)
         ops.gemm(ctx, W[f"L{i}.att.wo"], r, M, d, dA, dA, W.pitch(f"L{i}.att.wo"), d, bias=a.linear_out.bias, epi=ops.EPI_RESID,
                  aux_in=x, drop=d_res)
         x1, mean, rstd = self._post_ln(L.norm_self_att, r, M)
-        sl.att = (x, y, qkv, p, att_saved, ctx, d_att, d_res, r, mean, rstd)
+        att = _SqAttSaved(x, y, qkv, p, core, ctx, d_att, d_res, r, mean, rstd)
         # ---- feed forward 1
-        x2, sl.ff1 = self._sq_ffn_fwd(f"L{i}.ff1", L.feed_forward1, L.feed_forward1_scale, L.norm_feed_forward1, x1, g, W, drop,
-                                      site + 4, cdt, dp)
+        x2, ff1 = self._sq_ffn_fwd(S, f"L{i}.ff1", L.feed_forward1, L.feed_forward1_scale, L.norm_feed_forward1, x1, g, W, drop, site + 4)
         # ---- convolution module (Swish point-wise activation: 2*d channels through depthwise conv / BatchNorm)
         c = L.conv
-        k = self.conv_kernel_size
         C2 = 2 * d
         y3 = self._sb_fwd(L.conv_scale, x2, M, cdt, dp)
         pw1 = self._new(M, C2, dtype=cdt, device=dev)
         ops.gemm(y3, W[f"L{i}.conv.pw1"], pw1, M, C2, d, dp, W.pitch(f"L{i}.conv.pw1"), C2, bias=c.pointwise_conv1.bias)
-        gact = self._new(M, C2, dtype=cdt, device=dev)
-        fuse_act = self.fuse_glu_dwconv_fwd and C2 % (8 if cdt == torch.bfloat16 else 4) == 0   # (see ConformerEncoder._layer_fwd)
-        if not fuse_act:
-            ops.swish_mask_fwd(pw1, gact, g.lens, T, M, C2)
-        cc = self._new(M, C2, dtype=cdt, device=dev)
-        bn = c.batch_norm
-        bmean = self._new(C2, dtype=torch.float32, device=dev)
-        brstd = self._new(C2, dtype=torch.float32, device=dev)
-        count = float(M)
-        if training:
-            stats = S.bn_stats[i]
-            if fuse_act:
-                ops.dwconv_fwd_glu(pw1, g.lens, None, gact, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, stats, B, T, C2, k, act=1)
-            else:
-                ops.dwconv_fwd(gact, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, stats, B, T, C2, k)
-            if S.bn_world > 1:
-                self._sync_stats(stats[: 2 * C2 + 1])
-                count = stats[2 * C2: 2 * C2 + 1]
-        else:
-            if fuse_act:
-                ops.dwconv_fwd_glu(pw1, g.lens, None, gact, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, None, B, T, C2, k, act=1)
-            else:
-                ops.dwconv_fwd(gact, c.depthwise_conv.weight, c.depthwise_conv.bias, cc, None, B, T, C2, k)
-            ops.bn_eval_stats(bn.running_mean, bn.running_var, bmean, brstd, bn.eps, C2)
-        z = self._new(M, C2, dtype=cdt, device=dev)
-        if training:
-            # (two launches on purpose: the one-launch form, mi355x_bn_stats_swish_fwd, makes EVERY workgroup derive the
-            #  coefficients of its channels from the f64 sums and measured 31 us against 15.5 us for this pair,
-            #  tools/bn_bench.py)
-            ops.bn_finalize(stats, count, bmean, brstd, bn.running_mean, bn.running_var, bn.momentum, bn.eps, C2)
-        ops.bn_swish_fwd(cc, bmean, brstd, bn.weight, bn.bias, z, M, C2)
+        ccore, z = self._conv_core_fwd(S, i, c, pw1, g.lens, B, T, C2, act=1)
         r3 = self._new(M, d, dtype=torch.float32, device=dev)
         d_cres = drop(self.dropout, site + 6)
         ops.gemm(z, W[f"L{i}.conv.pw2"], r3, M, d, C2, C2, W.pitch(f"L{i}.conv.pw2"), d, bias=c.pointwise_conv2.bias,
                  epi=ops.EPI_RESID, aux_in=x2, drop=d_cres)
         x3, mean3, rstd3 = self._post_ln(L.norm_conv, r3, M)
-        sl.conv = (x2, y3, pw1, gact, cc, bmean, brstd, count, z, d_cres, r3, mean3, rstd3)
+        conv = _SqConvSaved(x2, y3, pw1, ccore, z, d_cres, r3, mean3, rstd3)
         # ---- feed forward 2
-        x4, sl.ff2 = self._sq_ffn_fwd(f"L{i}.ff2", L.feed_forward2, L.feed_forward2_scale, L.norm_feed_forward2, x3, g, W, drop,
-                                      site + 7, cdt, dp)
-        return x4, sl
+        x4, ff2 = self._sq_ffn_fwd(S, f"L{i}.ff2", L.feed_forward2, L.feed_forward2_scale, L.norm_feed_forward2, x3, g, W, drop, site + 7)
+        return x4, _SqLayerSaved(att, ff1, conv, ff2)
 
     # ------------------------------------------------------------------ backward
-    def _branch_grad(self, ln, dxo, r, mean, rstd, M, d_res, cdt, dp):
-        """post-LN sub-block: -> (dr f32 [M,d] = d/d(x + branch), operand copy of the branch gradient [M, dp])"""
-        d, dev = self.d_model, dxo.device
+    def _branch_grad(self, S, ln, dxo, sv, M):
+        """post-LN sub-block (sv: its saved record): -> (dr f32 [M,d] = d/d(x + branch), operand copy of the branch gradient [M, dp])"""
+        d, dev, dp = self.d_model, dxo.device, self._geometry(S.cdt)[0]
         dr = self._new(M, d, dtype=torch.float32, device=dev)
-        ops.layernorm_bwd(dxo, r, ln.weight, mean, rstd, dr, False, ln.weight.grad, ln.bias.grad, M, d)
-        df = self._new(M, dp, dtype=cdt, device=dev)
-        ops.cast_pitched(dr, df, M, d, dp, 1.0, d_res)
+        ops.layernorm_bwd(dxo, sv.r, ln.weight, sv.mean, sv.rstd, dr, False, ln.weight.grad, ln.bias.grad, M, d)
+        df = self._new(M, dp, dtype=S.cdt, device=dev)
+        ops.cast_pitched(dr, df, M, d, dp, 1.0, sv.d_res)
         return dr, df
 
     def _sb_bwd(self, sb, dy, x, dr, M, dp):
@@ -534,125 +511,76 @@ class SqueezeformerEncoder(ConformerEncoder):
         ops.scale_bias_bwd(dy, dp, x, sb.scale, dr, sb.scale.grad if ad else None, sb.bias.grad if ad else None, M, self.d_model)
         return dr
 
-    def _sq_ffn_bwd(self, pfx, ff, sb, ln, saved, dxo, g, W, cdt, dp):
-        x, y, h, a, d_in, d_res, r, mean, rstd = saved
-        M, d, dff, dev = g.M, self.d_model, self.d_ff, dxo.device
-        dr, df = self._branch_grad(ln, dxo, r, mean, rstd, M, d_res, cdt, dp)
-        self._wgrad(df, dp, 0, a, dff, 0, ff.linear2.weight.grad, d, dff, M, bias_grad=ff.linear2.bias.grad)
+    def _sq_ffn_bwd(self, S, pfx, ff, sb, ln, sv, dxo, g, W):
+        M, d, dff, cdt, dev = g.M, self.d_model, self.d_ff, S.cdt, dxo.device
+        dp = self._geometry(cdt)[0]
+        dr, df = self._branch_grad(S, ln, dxo, sv, M)
+        self._wgrad(df, dp, 0, sv.a, dff, 0, ff.linear2.weight.grad, d, dff, M, bias_grad=ff.linear2.bias.grad)
         dh = self._new(M, dff, dtype=cdt, device=dev)
-        if d_in is None:
-            ops.gemm(df, W[pfx + ".w2t"], dh, M, dff, d, dp, W.pitch(pfx + ".w2t"), dff, epi=ops.EPI_DSWISH_G, aux_in=h)
+        if sv.d_in is None:
+            ops.gemm(df, W[pfx + ".w2t"], dh, M, dff, d, dp, W.pitch(pfx + ".w2t"), dff, epi=ops.EPI_DSWISH_G, aux_in=sv.h)
         else:
-            ops.gemm(df, W[pfx + ".w2t"], dh, M, dff, d, dp, W.pitch(pfx + ".w2t"), dff, epi=ops.EPI_DSWISH, aux_in=h, drop=d_in)
-        self._wgrad(dh, dff, 0, y, dp, 0, ff.linear1.weight.grad, dff, d, M, bias_grad=ff.linear1.bias.grad)
+            ops.gemm(df, W[pfx + ".w2t"], dh, M, dff, d, dp, W.pitch(pfx + ".w2t"), dff, epi=ops.EPI_DSWISH, aux_in=sv.h, drop=sv.d_in)
+        self._wgrad(dh, dff, 0, sv.y, dp, 0, ff.linear1.weight.grad, dff, d, M, bias_grad=ff.linear1.bias.grad)
         dy = self._new(M, dp, dtype=cdt, device=dev)
         ops.gemm(dh, W[pfx + ".w1t"], dy, M, d, dff, dff, W.pitch(pfx + ".w1t"), dp)
-        return self._sb_bwd(sb, dy, x, dr, M, dp)
+        return self._sb_bwd(sb, dy, sv.x, dr, M, dp)
 
-    # (_heads_wgrad / _unpad_add: the padded-head weight-gradient helpers live in ConformerEncoder)
+    # (the padded-head projection gradients and the conv core live in ConformerEncoder)
     def _sq_layer_bwd(self, i, L, dxo, g, S, sl, W, Wf):
-        B, T, M = g.B, g.T, g.M
-        cdt, training = S.dims[8], S.dims[9]
+        B, T, M, cdt = g.B, g.T, g.M, S.cdt
         dev = dxo.device
-        d, H, dk = self.d_model, self.n_heads, self.d_k
+        d = self.d_model
         dp, dkp, dA = self._geometry(cdt)
-        padded = dkp != dk
+        padded = dkp != self.d_k
         C2 = 2 * d
-        k = self.conv_kernel_size
         # ---- feed forward 2
-        dx = self._sq_ffn_bwd(f"L{i}.ff2", L.feed_forward2, L.feed_forward2_scale, L.norm_feed_forward2, sl.ff2, dxo, g, W, cdt, dp)
+        dx = self._sq_ffn_bwd(S, f"L{i}.ff2", L.feed_forward2, L.feed_forward2_scale, L.norm_feed_forward2, sl.ff2, dxo, g, W)
         # ---- convolution module
-        c = L.conv
-        bn = c.batch_norm
-        x2, y3, pw1, gact, cc, bmean, brstd, count, z, d_cres, r3, mean3, rstd3 = sl.conv
-        dr, db = self._branch_grad(L.norm_conv, dx, r3, mean3, rstd3, M, d_cres, cdt, dp)
-        self._wgrad(db, dp, 0, z, C2, 0, c.pointwise_conv2.weight.grad, d, C2, M, bias_grad=c.pointwise_conv2.bias.grad)
+        c, cv = L.conv, sl.conv
+        dr, db = self._branch_grad(S, L.norm_conv, dx, cv, M)
+        self._wgrad(db, dp, 0, cv.z, C2, 0, c.pointwise_conv2.weight.grad, d, C2, M, bias_grad=c.pointwise_conv2.bias.grad)
         dz = self._new(M, C2, dtype=cdt, device=dev)
         ops.gemm(db, W[f"L{i}.conv.pw2t"], dz, M, C2, d, dp, W.pitch(f"L{i}.conv.pw2t"), C2)
-        sums = S.bn_sums[i]
-        ops.bn_swish_bwd_reduce(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, M, C2, dgamma=bn.weight.grad, dbeta=bn.bias.grad)
-        if training and S.bn_world > 1:
-            self._sync_stats(sums)
-        dpw1 = self._new(M, C2, dtype=cdt, device=dev)
-        fuse_act = self.fuse_bn_dwconv_bwd and self.fuse_glu_dwconv_bwd and C2 % (8 if cdt == torch.bfloat16 else 4) == 0
-        if fuse_act:   # BatchNorm + Swish backward, depthwise backward and the pointwise Swish's backward in one launch
-            ops.dwconv_bwd_bnswish(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, count, training, gact, c.depthwise_conv.weight, None,
-                                   c.depthwise_conv.weight.grad, c.depthwise_conv.bias.grad, B, T, C2, k, glu_in=pw1, glu_din=dpw1,
-                                   glu_len=g.lens, glu_act=1)
-        else:
-            dg = self._new(M, C2, dtype=cdt, device=dev)
-            if self.fuse_bn_dwconv_bwd:   # (see ConformerEncoder._layer_bwd)
-                ops.dwconv_bwd_bnswish(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, count, training, gact, c.depthwise_conv.weight, dg,
-                                       c.depthwise_conv.weight.grad, c.depthwise_conv.bias.grad, B, T, C2, k)
-            else:
-                dcc = self._new(M, C2, dtype=cdt, device=dev)
-                ops.bn_swish_bwd_apply(dz, cc, bmean, brstd, bn.weight, bn.bias, sums, count, training, dcc, M, C2)
-                ops.dwconv_bwd(dcc, gact, c.depthwise_conv.weight, dg, c.depthwise_conv.weight.grad, c.depthwise_conv.bias.grad, B, T, C2, k)
-            ops.swish_mask_bwd(pw1, dg, dpw1, g.lens, T, M, C2)
-        self._wgrad(dpw1, C2, 0, y3, dp, 0, c.pointwise_conv1.weight.grad, C2, d, M, bias_grad=c.pointwise_conv1.bias.grad)
+        dpw1, conv_tmp = self._conv_core_bwd(S, i, c, cv.core, cv.pw1, dz, g.lens, B, T, C2, act=1)   # noqa: F841 (conv_tmp: see there)
+        self._wgrad(dpw1, C2, 0, cv.y, dp, 0, c.pointwise_conv1.weight.grad, C2, d, M, bias_grad=c.pointwise_conv1.bias.grad)
         dy3 = self._new(M, dp, dtype=cdt, device=dev)
         ops.gemm(dpw1, W[f"L{i}.conv.pw1t"], dy3, M, d, C2, C2, W.pitch(f"L{i}.conv.pw1t"), dp)
-        dx = self._sb_bwd(L.conv_scale, dy3, x2, dr, M, dp)
+        dx = self._sb_bwd(L.conv_scale, dy3, cv.x, dr, M, dp)
         # ---- feed forward 1
-        dx = self._sq_ffn_bwd(f"L{i}.ff1", L.feed_forward1, L.feed_forward1_scale, L.norm_feed_forward1, sl.ff1, dx, g, W, cdt, dp)
+        dx = self._sq_ffn_bwd(S, f"L{i}.ff1", L.feed_forward1, L.feed_forward1_scale, L.norm_feed_forward1, sl.ff1, dx, g, W)
         # ---- self-attention
-        a = L.self_attn
-        x, y, qkv, p, att_saved, ctx, d_att, d_res, r, mean, rstd = sl.att
-        dr, dao = self._branch_grad(L.norm_self_att, dx, r, mean, rstd, M, d_res, cdt, dp)
-        bf16 = cdt == torch.bfloat16
+        a, at = L.self_attn, sl.att
+        dr, dao = self._branch_grad(S, L.norm_self_att, dx, at, M)
         if not padded:
-            self._wgrad(dao, dp, 0, ctx, dA, 0, a.linear_out.weight.grad, d, d, M, bias_grad=a.linear_out.bias.grad)
-        else:  # d linear_out.weight[:, h*dk:(h+1)*dk] += dao^T @ ctx[:, h*dkp : +dk]: batch over heads
-            with self._wgrad_scope(dao, ctx):
-                ops.gemm(dao, ctx, a.linear_out.weight.grad, d, dk, M, dp, dA, d, transA=True, transB=True, atomic=True,
-                         splitk=self._splitk(self._tiles(d, dk, bf16) * H, M), batch=H, nb0=H, sB=(dkp, 0), sC=(dk, 0),
-                         c_dtype=ops.F32)
-                ops.colsum(dao, a.linear_out.bias.grad, M, d, ld=dp)
+            self._wgrad(dao, dp, 0, at.ctx, dA, 0, a.linear_out.weight.grad, d, d, M, bias_grad=a.linear_out.bias.grad)
+        else:
+            self._heads_out_wgrad(a, dao, at.ctx, M, ldx=dp)
         dctx = self._new(M, dA, dtype=cdt, device=dev)
         ops.gemm(dao, W[f"L{i}.att.wot"], dctx, M, dA, d, dp, W.pitch(f"L{i}.att.wot"), dA)
         dpos = torch.zeros(g.P, dA, dtype=torch.float32, device=dev)
         dpos_c = self._new(g.P, dA, dtype=cdt, device=dev)
-        bu, bv = Wf[f"L{i}.att.bu"], Wf[f"L{i}.att.bv"]
-        dqkv, dqu, dqv = self._attn_bwd(att_saved, qkv, p, bu, bv, ctx, dctx, g.lens, B, T, dA, dkp, 1.0 / math.sqrt(dk), d_att,
-                                        cdt, dev, dpos, dpos_c)
-        gu, gv_ = a.pos_bias_u.grad, a.pos_bias_v.grad
-        if not padded:
-            ops.colsum(dqu, gu, M, dA)
-            ops.colsum(dqv, gv_, M, dA)
-        else:
-            sc = torch.zeros(2, dA, dtype=torch.float32, device=dev)
-            ops.colsum(dqu, sc[0], M, dA)
-            ops.colsum(dqv, sc[1], M, dA)
-            self._unpad_add(gu.view(-1), sc[0], dkp)
-            self._unpad_add(gv_.view(-1), sc[1], dkp)
-        ops.add2(dqu, dqv, dqkv, 3 * dA, M, dA)
+        dqkv, dqu, dqv = self._attn_bwd(S, at.core, at.qkv, at.p, Wf[f"L{i}.att.bu"], Wf[f"L{i}.att.bv"], at.ctx, dctx, g.lens, B, T, dA,
+                                        dkp, at.d_att, dpos, dpos_c)
         # q / k / v / linear_pos weight gradients (the flash path produced dpos_c on the weight-gradient stream: its consumer runs
         # there too; the GEMM path produced it on the main stream, which _wgrad_scope waits for)
-        lins = (a.linear_q, a.linear_k, a.linear_v)
         if not padded:
-            for j, lin in enumerate(lins):
-                self._wgrad(dqkv, 3 * dA, j * dA, y, dp, 0, lin.weight.grad, d, d, M, bias_grad=lin.bias.grad)
+            ops.colsum(dqu, a.pos_bias_u.grad, M, dA)
+            ops.colsum(dqv, a.pos_bias_v.grad, M, dA)
+            ops.add2(dqu, dqv, dqkv, 3 * dA, M, dA)
+            for j, lin in enumerate((a.linear_q, a.linear_k, a.linear_v)):
+                self._wgrad(dqkv, 3 * dA, j * dA, at.y, dp, 0, lin.weight.grad, d, d, M, bias_grad=lin.bias.grad)
             self._wgrad(dpos_c, dA, 0, g.pos, dp, 0, a.linear_pos.weight.grad, d, d, g.P)
         else:
-            gq, gk, gvw = (lin.weight.grad for lin in lins)
-            sw = (gk.data_ptr() - gq.data_ptr()) // 4
-            if sw > 0 and (gvw.data_ptr() - gk.data_ptr()) // 4 == sw:
-                self._heads_wgrad(dqkv, 3 * dA, 0, y, dp, gq, M, 3, dA, sw)
-            else:
-                for j, lin in enumerate(lins):
-                    self._heads_wgrad(dqkv, 3 * dA, j * dA, y, dp, lin.weight.grad, M, 1, 0, 0)
-            sc = torch.zeros(3 * dA, dtype=torch.float32, device=dev)
-            with self._wgrad_scope(dqkv, sc):
-                ops.colsum(dqkv, sc, M, 3 * dA)
-                for j, lin in enumerate(lins):
-                    self._unpad_add(lin.bias.grad, sc[j * dA:(j + 1) * dA], dkp)
+            sc, bias_sums = self._heads_qkv_grads(a, dqkv, dqu, dqv, at.y, M, ldx=dp)   # noqa: F841 (bias_sums: released with this frame)
+            del sc   # (the pos-bias sums have always gone first here; off the step arena the order decides what the allocator reuses)
             self._heads_wgrad(dpos_c, dA, 0, g.pos, dp, a.linear_pos.weight.grad, g.P, 1, 0, 0)
         dy = self._new(M, dp, dtype=cdt, device=dev)
         ops.gemm(dqkv, W[f"L{i}.att.wqkvt"], dy, M, d, 3 * dA, 3 * dA, W.pitch(f"L{i}.att.wqkvt"), dp)
-        return self._sb_bwd(L.self_attn_scale, dy, x, dr, M, dp)
+        return self._sb_bwd(L.self_attn_scale, dy, at.x, dr, M, dp)
 
     def _backward_impl(self, S, dout):
-        B, F_, T, T1, F1, T2, F2, M, cdt, training, seed = S.dims
+        B, M, cdt = S.B, S.M, S.cdt
         dev = dout.device
         self._check_serial(S)
         self._phase("b", dev)
@@ -673,7 +601,7 @@ class SqueezeformerEncoder(ConformerEncoder):
             S.layers[i] = None
             if self.time_reduce_idx is not None and i == self.time_recovery_idx:
                 # x = skip + Linear(repeat_interleave(x_small, 2)[:, :T]): the skip gradient waits for the time-reduction backward
-                xs_c, g_small = S.rec
+                xs_c, g_small = S.rec.xs_c, S.rec.geo
                 rec = self.time_recovery_layer
                 dskip = dx
                 dys = self._new(g_small.M, dp, dtype=cdt, device=dev)
@@ -683,7 +611,7 @@ class SqueezeformerEncoder(ConformerEncoder):
                 dx = self._new(g_small.M, d, dtype=torch.float32, device=dev)
                 ops.gemm(dys, W["rec.wt"], dx, g_small.M, d, d, dp, W.pitch("rec.wt"), d)
             if self.time_reduce_idx is not None and i == self.time_reduce_idx:
-                x_in, g_full, dwo = S.tr
+                x_in, g_full, dwo = S.tr.x, S.tr.geo, S.tr.dwo
                 tr = self.time_reduce_layer
                 Mh = g.M
                 dxc = self._new(Mh, dp, dtype=cdt, device=dev)
@@ -700,9 +628,8 @@ class SqueezeformerEncoder(ConformerEncoder):
                     self._wgrad_join()
                 self._hook(*fp.range_of(f"layers.{i}."))
         self._wg_pending = None
-        x_pre, pmean, prstd = S.pre_ln
         dpre = self._new(M, d, dtype=torch.float32, device=dev)
-        ops.layernorm_bwd(dx, x_pre, self.pre_ln.weight, pmean, prstd, dpre, False, self.pre_ln.weight.grad, self.pre_ln.bias.grad, M, d)
+        ops.layernorm_bwd(dx, S.front.x, self.pre_ln.weight, S.front.mean, S.front.rstd, dpre, False, self.pre_ln.weight.grad, self.pre_ln.bias.grad, M, d)
         self._wgrad_join()
         if self.grad_ready_hook is not None:
             for pfx in ("pre_ln.", "time_reduce_layer.", "time_recovery_layer."):

@@ -583,6 +583,39 @@ int mi355x_ctc_greedy_decode(const void* logp, const void* lens, void* tokens, v
 int mi355x_ctc_greedy_decode_ts(const void* logp, const void* lens, void* tokens, void* out_len, void* score, void* tok_start,
                                 void* tok_end, int B, int T, int C, int blank, void* stream);
 
+/* ---- confidence of a decoding step (the entropy-based measures of the reference's ConfidenceMethodConfig, parts/utils/
+ * asr_confidence_utils.py), normalised so that a one-hot distribution gives 1 and the uniform one 0; nothing is clamped.  For a
+ * distribution over V >= 2 classes with natural log-probabilities x_v, p_v = exp(x_v), S = sum_v p_v^alpha and
+ * G = sum_v p_v^alpha * x_v (a class with x_v = -inf adds 0 to both), alpha > 0:
+ *   method                    norm = LIN                            norm = EXP
+ *   MAX_PROB (norm ignored)   (V max_v p_v - 1) / (V - 1)           same
+ *   GIBBS, alpha = 1          1 + G / ln V                          (V exp(G) - 1) / (V - 1)
+ *   GIBBS, alpha != 1         1 + G / (V^(1-alpha) ln V)            (exp(alpha G) - b) / (1 - b),  b = exp(-alpha V^(1-alpha) ln V)
+ *   TSALLIS, alpha != 1       1 + (1 - S) / (V^(1-alpha) - 1)       (exp((S-1)/(alpha-1)) - b) / (1 - b),  b = exp((V^(1-alpha) - 1)/(alpha-1))
+ *   RENYI, alpha != 1         1 + ln S / ((alpha-1) ln V)           (V S^(1/(alpha-1)) - 1) / (V - 1)
+ * TSALLIS / RENYI with alpha == 1 exactly are the GIBBS alpha = 1 row.  The constants that depend on (V, alpha) alone come from the
+ * caller, computed in double: k0 = ln V, k1 = V^(1-alpha), k2 = b of the row in use (0 where the row has none). */
+#define MI355X_CONF_MAX_PROB 0   /* method */
+#define MI355X_CONF_GIBBS 1
+#define MI355X_CONF_TSALLIS 2
+#define MI355X_CONF_RENYI 3
+#define MI355X_CONF_NORM_LIN 0   /* entropy_norm */
+#define MI355X_CONF_NORM_EXP 1
+#define MI355X_CONF_AGG_MEAN 0   /* aggregation of frame confidences into a token's */
+#define MI355X_CONF_AGG_MIN 1
+#define MI355X_CONF_AGG_MAX 2
+#define MI355X_CONF_AGG_PROD 3
+/* mi355x_ctc_greedy_decode_ts, and confidences (distribution = all C columns of a frame, blank included): frame_conf f32 [B,T]
+ * (0.0 beyond lens[b]) and tok_conf f32 [B,T] (0.0 beyond out_len[b]) = `aggregation` of frame_conf over tok_start .. tok_end
+ * (exclude_blank != 0), or over previous token's tok_end + 1 .. tok_end (exclude_blank == 0; the first token from frame 0: the blank
+ * frames in front of a token count, the frames behind the last token belong to none).  tokens, out_len, score, tok_start and
+ * tok_end are bit-identical to mi355x_ctc_greedy_decode_ts's.  MI_ERR_ARG for C < 2, alpha <= 0, unknown enum values, a null
+ * output. */
+int mi355x_ctc_greedy_decode_conf(const void* logp, const void* lens, void* tokens, void* out_len, void* score, void* tok_start,
+                                  void* tok_end, void* frame_conf, void* tok_conf, int B, int T, int C, int blank, int method,
+                                  int norm, float alpha, float k0, float k1, float k2, int aggregation, int exclude_blank,
+                                  void* stream);
+
 /* CTC forced alignment: the Viterbi pass of the reference's forced aligner (tools/nemo_forced_aligner/utils/viterbi_decoding.py),
  * one launch per batch -- forward walk, backtrace and expansion.  logp f32 [B,Tmax,C] (-inf entries allowed); targets i64 [B,Umax];
  * in_len, tgt_len i64 [B].  States = the blank-extended sequence, S = 2U+1:
@@ -713,6 +746,44 @@ int mi355x_tdt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long
                                     const int* durations, int blank, int max_symbols, void* tokens, void* times, void* out_len,
                                     int max_out, const mi355x_rnnt_stream_state* state_in,
                                     const mi355x_rnnt_stream_state* state_out, void* stream);
+
+/* ---- the four searches above with the confidence of every emitted label: their sibling's arguments, then tok_conf f32
+ * [B, max_out] (0.0 padded) and the measure (MI355X_CONF_*, k0..k2 for V = V1).  tok_conf[b, n] = the confidence of the step that
+ * emitted label n, over the V1 label logits of that step (blank included; TDT: the duration logits take no part); blank steps are
+ * not kept.  The sums ride in the pass that computes the step's log-sum-exp, relative to the maximum logit.  Everything else the
+ * siblings write is bit-identical to theirs, and a stream cut into any chunks gives bit-identical tok_conf to one launch: the value
+ * belongs to a label, so the stream state carries nothing new.  These launch their own instantiations of the kernel template; the
+ * siblings launch the code they always have.  MI_ERR_ARG also for a null tok_conf, alpha <= 0, unknown enum values. */
+int mi355x_rnnt_greedy_decode_conf(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                   const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                                   const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out,
+                                   long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int blank,
+                                   int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out,
+                                   void* c_out, void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2,
+                                   void* stream);
+int mi355x_tdt_greedy_decode_conf(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                  const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                                  const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out,
+                                  long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D,
+                                  const int* durations, int blank, int max_symbols, void* tokens, void* times, void* out_len,
+                                  void* score, int max_out, void* h_out, void* c_out, void* tok_conf, int method, int norm,
+                                  float alpha, float k0, float k1, float k2, void* stream);
+int mi355x_rnnt_greedy_decode_stream_conf(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                          const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                                          const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+                                          const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
+                                          int H, int V1, int blank, int max_symbols, void* tokens, void* times, void* out_len,
+                                          int max_out, const mi355x_rnnt_stream_state* state_in,
+                                          const mi355x_rnnt_stream_state* state_out, void* tok_conf, int method, int norm,
+                                          float alpha, float k0, float k1, float k2, void* stream);
+int mi355x_tdt_greedy_decode_stream_conf(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                         const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                                         const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+                                         const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
+                                         int H, int V1, int D, const int* durations, int blank, int max_symbols, void* tokens,
+                                         void* times, void* out_len, int max_out, const mi355x_rnnt_stream_state* state_in,
+                                         const mi355x_rnnt_stream_state* state_out, void* tok_conf, int method, int norm,
+                                         float alpha, float k0, float k1, float k2, void* stream);
 
 /* ---- cache-aware streaming inference (ConformerEncoder.cache_aware_stream_step; the `update_cache` paths of
  * RelPositionMultiHeadAttention and CausalConv1D).  Caches are f32 in the reference's layouts; in bf16 compute they hold the

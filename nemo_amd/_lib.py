@@ -122,6 +122,7 @@ SIGNATURES = {
     "mi355x_add2": [vp, vp, i32, vp, i32, i64, i64, i32, vp],
     "mi355x_ctc_greedy_decode": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "mi355x_ctc_greedy_decode_ts": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "mi355x_ctc_greedy_decode_conf": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, i32, i32, vp],
     "mi355x_ctc_align": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi355x_fill_rects": [vp, vp, i32, i32, i32, i32, f32, vp],
     "mi355x_specaug_rects": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp],
@@ -194,6 +195,16 @@ SIGNATURES = {
                                          i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp],
     "mi355x_tdt_greedy_decode_stream": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32,
                                         i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp],
+    # the *_conf searches: their sibling's arguments with (tok_conf, method, norm, alpha, k0, k1, k2) in front of the stream
+    "mi355x_rnnt_greedy_decode_conf": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32,
+                                       i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp],
+    "mi355x_tdt_greedy_decode_conf": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32,
+                                      i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp],
+    "mi355x_rnnt_greedy_decode_stream_conf": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32,
+                                              i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp],
+    "mi355x_tdt_greedy_decode_stream_conf": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32,
+                                             i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32,
+                                             vp],
     "mi355x_stream_cache_assemble": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi355x_stream_attn": [vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "mi355x_stream_dwconv": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mi355x_asr.h"
 
 #define MI_OK 0
 #define MI_ERR_ARG 1
@@ -104,6 +105,28 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   float t = 0.f;
   for (int i = 0; i < nw; ++i) t += red[i];
   return t;
+}
+
+// ---------------------------------------------------------------- confidence of a distribution (greedy CTC / transducer decoding)
+// The entropy-based measures of include/mi355x_asr.h (MI355X_CONF_*): 1 for a one-hot distribution, 0 for the uniform one, nothing
+// clamped.  pmax = max_v p_v, S = sum_v p_v^alpha, G = sum_v p_v^alpha * ln p_v.  k0 = ln V, k1 = V^(1-alpha), k2 = the `b` of the
+// exp-normalised gibbs / tsallis rows: computed by the caller in double.  tsallis / renyi at alpha == 1 are the gibbs alpha = 1 row.
+struct MiConf {
+  int method, norm;
+  float alpha, k0, k1, k2, V;
+};
+static inline bool mi_conf_valid(int V, int method, int norm, float alpha) {
+  return V >= 2 && alpha > 0.f && method >= MI355X_CONF_MAX_PROB && method <= MI355X_CONF_RENYI &&
+         (norm == MI355X_CONF_NORM_LIN || norm == MI355X_CONF_NORM_EXP);
+}
+__device__ __forceinline__ float mi_conf_value(const MiConf& q, float pmax, float S, float G) {
+  const float V = q.V, al = q.alpha;
+  const bool ex = q.norm == MI355X_CONF_NORM_EXP;
+  if (q.method == MI355X_CONF_MAX_PROB) return (V * pmax - 1.f) / (V - 1.f);
+  if (al == 1.f) return ex ? (V * expf(G) - 1.f) / (V - 1.f) : 1.f + G / q.k0;
+  if (q.method == MI355X_CONF_GIBBS) return ex ? (expf(al * G) - q.k2) / (1.f - q.k2) : 1.f + G / (q.k1 * q.k0);
+  if (q.method == MI355X_CONF_TSALLIS) return ex ? (expf((S - 1.f) / (al - 1.f)) - q.k2) / (1.f - q.k2) : 1.f + (1.f - S) / (q.k1 - 1.f);
+  return ex ? (V * powf(S, 1.f / (al - 1.f)) - 1.f) / (V - 1.f) : 1.f + logf(S) / ((al - 1.f) * q.k0);
 }
 
 // ---------------------------------------------------------------- activations

@@ -506,6 +506,120 @@ extern "C" int mi355x_ctc_greedy_decode_ts(const void* logp, const void* lens, v
   return mi_check_launch();
 }
 
+// mi355x_ctc_greedy_decode_conf: the kernel above, and confidences.  Its own kernel, so that the two above stay as they are.  The
+// wave that walks a frame's C log-probabilities for the arg-max carries the sums of the chosen measure in the same pass (log-probs
+// are <= 0, so p^alpha = exp(alpha x) needs no shift; a -inf class adds nothing) and stores the frame's confidence.  After the
+// compaction a lane per token folds the frame confidences of its range, read back from frame_conf behind the barrier (a third
+// per-frame array in LDS would not fit at Tmax = 8192 without raising the limit).
+__device__ __forceinline__ float ctc_conf_fold(float a, float b, int agg) {
+  return agg == MI355X_CONF_AGG_MIN ? fminf(a, b) : agg == MI355X_CONF_AGG_MAX ? fmaxf(a, b) : agg == MI355X_CONF_AGG_PROD ? a * b : a + b;
+}
+__global__ __launch_bounds__(256) void ctc_greedy_conf_kernel(const float* __restrict__ logp, const long long* __restrict__ lens,
+                                                              int* __restrict__ tokens, int* __restrict__ out_len,
+                                                              float* __restrict__ score, int* tok_start, int* tok_end,
+                                                              float* frame_conf, float* __restrict__ tok_conf, int Tmax, int C,
+                                                              int blank, MiConf q, int agg, int exclude_blank) {
+  extern __shared__ int s_lab[];  // [Tmax] labels ; then [Tmax] log-probs (as float)
+  float* s_lp = reinterpret_cast<float*>(s_lab + Tmax);
+  const int b = blockIdx.x;
+  const int T = (int)min((long long)Tmax, lens ? lens[b] : (long long)Tmax);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* lp = logp + (long long)b * Tmax * C;
+  float* fc = frame_conf + (long long)b * Tmax;
+  const bool sums = q.method != MI355X_CONF_MAX_PROB;   // (uniform)
+  for (int t = wave; t < T; t += 4) {
+    float best = -INFINITY; int arg = 0x7fffffff;
+    float S = 0.f, G = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      const float v = lp[(long long)t * C + c];
+      if (v > best) { best = v; arg = c; }
+      if (sums) {
+        const float e = expf(q.alpha * v);
+        S += e;
+        G += (v == -INFINITY) ? 0.f : e * v;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o, 64); const int oa = __shfl_xor(arg, o, 64);
+      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+    if (sums) { S = wave_sum(S); G = wave_sum(G); }
+    if (lane == 0) { s_lab[t] = arg; s_lp[t] = best; fc[t] = mi_conf_value(q, expf(best), S, G); }
+  }
+  for (int t = T + (int)threadIdx.x; t < Tmax; t += 256) fc[t] = 0.f;   // padding
+  __syncthreads();
+  int* tok = tokens + (long long)b * Tmax;
+  int* ts = tok_start + (long long)b * Tmax;
+  int* te = tok_end + (long long)b * Tmax;
+  float* tc = tok_conf + (long long)b * Tmax;
+  if (wave == 0) {
+    int base = 0; float sc = 0.f;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+      const int t = t0 + lane;
+      const int cur = t < T ? s_lab[t] : blank;
+      const int prev = (t > 0 && t < T) ? s_lab[t - 1] : blank;
+      const bool nonblank = t < T && cur != blank;
+      const bool keep = nonblank && cur != prev;
+      if (nonblank) sc += s_lp[t];
+      const unsigned long long m = __ballot(keep);
+      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+      if (keep) { tok[pos] = cur; ts[pos] = t; }
+      if (nonblank && (t + 1 >= T || s_lab[t + 1] != cur))   // (2 << 63 wraps to 0: the mask of lane 63 is all ones)
+        te[base + __popcll(m & ((2ull << lane) - 1ull)) - 1] = t;
+      base += __popcll(m);
+    }
+    sc = wave_sum(sc);
+    if (lane == 0) { out_len[b] = base; score[b] = sc; }
+    for (int t = base + lane; t < Tmax; t += 64) { tok[t] = -1; ts[t] = -1; te[t] = -1; tc[t] = 0.f; }  // padding
+  }
+  __syncthreads();   // out_len / tok_start / tok_end / frame_conf of this workgroup are visible to all of its waves
+  const int n = out_len[b];   // (all of the LDS a launch may have without a raised limit is the two per-frame arrays at Tmax = 8192)
+  const float id = agg == MI355X_CONF_AGG_MIN ? INFINITY : agg == MI355X_CONF_AGG_MAX ? -INFINITY : agg == MI355X_CONF_AGG_PROD ? 1.f : 0.f;
+  // A lane per token: its range is a handful of frames as a rule, folded in the lane (a wave per token spent its time on the two
+  // dependent loads that find the range: 122 us of 237 at B = 32, T = 501).  A range of more than 64 frames -- a long run, or with
+  // exclude_blank off a long silence in front of a token -- is folded by the whole wave instead, one such token after the other.
+  for (int i0 = wave * 64; i0 < n; i0 += 256) {   // (uniform over the wave; 0 <= lo <= hi < T by construction of the runs)
+    const int i = i0 + lane;
+    const bool valid = i < n;
+    const int hi = valid ? te[i] : -1;
+    const int lo = !valid ? 0 : exclude_blank ? ts[i] : (i ? te[i - 1] + 1 : 0);
+    const bool wide = valid && hi - lo >= 64;
+    if (valid && !wide) {
+      float a = id;
+      for (int t = lo; t <= hi; ++t) a = ctc_conf_fold(a, fc[t], agg);
+      tc[i] = agg == MI355X_CONF_AGG_MEAN ? a / (float)(hi - lo + 1) : a;
+    }
+    for (unsigned long long m = __ballot(wide); m; m &= m - 1) {
+      const int l = __ffsll((long long)m) - 1;
+      const int wlo = __shfl(lo, l, 64), whi = __shfl(hi, l, 64);
+      float a = id;
+      for (int t = wlo + lane; t <= whi; t += 64) a = ctc_conf_fold(a, fc[t], agg);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) a = ctc_conf_fold(a, __shfl_xor(a, o, 64), agg);
+      if (lane == 0) tc[i0 + l] = agg == MI355X_CONF_AGG_MEAN ? a / (float)(whi - wlo + 1) : a;
+    }
+  }
+}
+extern "C" int mi355x_ctc_greedy_decode_conf(const void* logp, const void* lens, void* tokens, void* out_len, void* score,
+                                             void* tok_start, void* tok_end, void* frame_conf, void* tok_conf, int B, int Tmax, int C,
+                                             int blank, int method, int norm, float alpha, float k0, float k1, float k2,
+                                             int aggregation, int exclude_blank, void* stream) {
+  mi_clear_errors();
+  if (!logp || !tokens || !out_len || !score || !tok_start || !tok_end || !frame_conf || !tok_conf || B <= 0 || Tmax <= 0 ||
+      blank < 0 || blank >= C)
+    return MI_ERR_ARG;
+  if (!mi_conf_valid(C, method, norm, alpha) || aggregation < MI355X_CONF_AGG_MEAN || aggregation > MI355X_CONF_AGG_PROD)
+    return MI_ERR_ARG;
+  const size_t shm = (size_t)Tmax * 8;
+  if (shm > 64 * 1024) return MI_ERR_ARG;
+  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)C};
+  MI_LAUNCH(ctc_greedy_conf_kernel, dim3(B), dim3(256), shm, (hipStream_t)stream, (const float*)logp, (const long long*)lens,
+                     (int*)tokens, (int*)out_len, (float*)score, (int*)tok_start, (int*)tok_end, (float*)frame_conf,
+                     (float*)tok_conf, Tmax, C, blank, q, aggregation, exclude_blank);
+  return mi_check_launch();
+}
+
 // ------------------------------------------------------------------------------------------------ CTC forced alignment
 // Viterbi pass of the reference's forced aligner (tools/nemo_forced_aligner/utils/viterbi_decoding.py: a Python loop over T on
 // [B, S] tensors) as ONE launch per batch: the forward walk over the blank-extended lattice with max instead of log-sum-exp, a 2-bit

@@ -69,11 +69,19 @@ struct RnntDecP {
   int B, T, J, H, V1, blank, max_symbols, max_out;
   TdtDur dur;                                // TDT: duration set (dur.D = 0 for the RNN-T search)
 };
+// the parameter block of the CONF = true instantiations: the one above (untouched, so that the others take the very block they
+// always took) and the confidence of every emitted label [B, max_out] with its measure
+struct RnntDecPC : RnntDecP {
+  float* tok_conf; MiConf conf;
+};
+template <bool CONF> struct RnntDecArg { typedef RnntDecP t; };
+template <> struct RnntDecArg<true> { typedef RnntDecPC t; };
 
 // STREAM = false is the one-shot search: the state code folds away at compile time and the instantiation is the kernel the
-// one-shot entry points have always launched.
-template <typename WT, bool TDT, bool STREAM>
-__global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
+// one-shot entry points have always launched.  CONF = false likewise: the sums of the confidence measure, their two block
+// reductions and the store in `emit` exist in the CONF = true instantiations alone (the *_conf entry points).
+template <typename WT, bool TDT, bool STREAM, bool CONF>
+__global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDecArg<CONF>::t p) {
   extern __shared__ __attribute__((aligned(16))) float rd_smem[];
   const int H = p.H, J = p.J, V1 = p.V1;
   float* x = rd_smem;            // [H] embedding of the last emitted label
@@ -128,6 +136,9 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
   if (!STREAM || len > skip) pred_step(!STREAM || last == p.blank);
 
   int n = 0;
+  // CONF: sums of the step's label distribution relative to its maximum logit mv, d_v = lg[v] - mv:
+  // cA = sum_v exp(alpha d_v), cB = sum_v exp(alpha d_v) d_v (set by joint_step, used by emit)
+  float cA = 0.f, cB = 0.f;
   // joint on frame t and the current prediction projection: label arg-max -> s_k (TDT: duration index arg-max -> s_d), returns
   // sum_v exp(lg[v] - max) over the label logits
   auto joint_step = [&](int t) -> float {
@@ -153,9 +164,23 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
 #pragma unroll
     for (int w = 1; w < RD_WAVES; ++w) if (red_v[w] > mv || (red_v[w] == mv && red_i[w] < mi)) { mv = red_v[w]; mi = red_i[w]; }
     float se = 0.f;
-    for (int v = tid; v < V1; v += RD_THREADS) se += expf(lg[v] - mv);
+    float sa = 0.f, sb = 0.f;
+    bool sums = false;   // (uniform)
+    if constexpr (CONF) sums = p.conf.method != MI355X_CONF_MAX_PROB;
+    for (int v = tid; v < V1; v += RD_THREADS) {
+      const float d = lg[v] - mv;
+      se += expf(d);
+      if constexpr (CONF) {
+        if (sums) {
+          const float e = expf(p.conf.alpha * d);
+          sa += e;
+          sb += (d == -INFINITY) ? 0.f : e * d;
+        }
+      }
+    }
     __syncthreads();   // (red_v is re-used by block_sum)
     se = block_sum(se, red_v);
+    if (sums) { cA = block_sum(sa, red_v); cB = block_sum(sb, red_v); }
     if (tid == 0) {
       s_k = mi;
       if (TDT) {   // first maximum wins, as for the labels
@@ -173,6 +198,11 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
       if (tid == 0) {
         p.tokens[(long long)b * p.max_out + n] = k;
         if (p.times) p.times[(long long)b * p.max_out + n] = STREAM ? frames_done + t : t;
+        if constexpr (CONF) {
+          // log p_v = d_v - log se: S = cA / se^alpha, G = (cB - cA log se) / se^alpha, max_v p_v = 1 / se
+          const float lse = logf(se), r = expf(-p.conf.alpha * lse);
+          p.tok_conf[(long long)b * p.max_out + n] = mi_conf_value(p.conf, 1.f / se, cA * r, (cB - cA * lse) * r);
+        }
       }
     }
     ++n;
@@ -225,6 +255,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(RnntDecP p) {
   for (int i = tid + n; i < p.max_out; i += RD_THREADS) {   // pad (also when nothing was emitted)
     p.tokens[(long long)b * p.max_out + i] = -1;
     if (p.times) p.times[(long long)b * p.max_out + i] = -1;
+    if constexpr (CONF) p.tok_conf[(long long)b * p.max_out + i] = 0.f;
   }
   if (p.h_out) for (int i = tid; i < H; i += RD_THREADS) { p.h_out[(long long)b * H + i] = h[i]; p.c_out[(long long)b * H + i] = c[i]; }
   if (STREAM && p.sout.h) {
@@ -242,12 +273,12 @@ static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, 
                               const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, const TdtDur* dur, int blank,
                               int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out,
                               void* c_out, const mi355x_rnnt_stream_state* sin, const mi355x_rnnt_stream_state* sout,
-                              void* stream) {
+                              void* tok_conf, const MiConf* conf, void* stream) {
   if (!enc_proj || !emb || !w_ih || !w_hh || !b_ih || !b_hh || !w_pred || !w_out || !tokens || !out_len) return MI_ERR_ARG;
   if (B <= 0 || T <= 0 || J <= 0 || H <= 0 || V1 <= 1 || max_out <= 0 || blank < 0 || blank >= V1) return MI_ERR_ARG;
   if ((H & 3) || (J & 3) || (ld_ih & 3) || (ld_hh & 3) || (ld_pred & 3) || (ld_out & 3) || (!h_out != !c_out)) return MI_ERR_ARG;
   if ((f_dtype != MI_DT_F32 && f_dtype != MI_DT_BF16) || (w_dtype != MI_DT_F32 && w_dtype != MI_DT_BF16)) return MI_ERR_ARG;
-  RnntDecP p;
+  RnntDecPC p;
   p.f = enc_proj; p.f_dt = f_dtype; p.ldf = ldf; p.enc_len = (const long long*)enc_len; p.emb = (const float*)emb;
   p.w_ih = w_ih; p.w_hh = w_hh; p.w_pred = w_pred; p.w_out = w_out;
   p.ld_ih = ld_ih; p.ld_hh = ld_hh; p.ld_pred = ld_pred; p.ld_out = ld_out;
@@ -257,6 +288,11 @@ static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, 
   p.B = B; p.T = T; p.J = J; p.H = H; p.V1 = V1; p.blank = blank; p.max_symbols = max_symbols; p.max_out = max_out;
   p.dur = {};
   if (dur) p.dur = *dur;
+  p.tok_conf = (float*)tok_conf; p.conf = {};
+  if (conf) {   // the *_conf entry points: a measure over the V1 label logits and somewhere to write it
+    if (!tok_conf || !mi_conf_valid(V1, conf->method, conf->norm, conf->alpha)) return MI_ERR_ARG;
+    p.conf = *conf;
+  }
   p.sin = {}; p.sout = {};
   for (int io = 0; io < 2; ++io) {   // a state is given whole (skip / zero_run: TDT only) or not at all
     const mi355x_rnnt_stream_state* st = io ? sout : sin;
@@ -269,14 +305,17 @@ static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, 
   const size_t shm = (size_t)(9 * H + 2 * J + V1 + D + 4) * sizeof(float);
   if (shm > 160 * 1024 - 256) return MI_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-#define RD_LAUNCH(WT, TDT, STREAM)                                                                                                 \
-  hipFuncSetAttribute((const void*)rnnt_greedy_kernel<WT, TDT, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);    \
-  MI_LAUNCH((rnnt_greedy_kernel<WT, TDT, STREAM>), dim3(B), dim3(RD_THREADS), shm, s, p)
-#define RD_LAUNCH_WT(WT)                                                                \
-  if (sout) { if (dur) { RD_LAUNCH(WT, true, true); } else { RD_LAUNCH(WT, false, true); } }   \
-  else { if (dur) { RD_LAUNCH(WT, true, false); } else { RD_LAUNCH(WT, false, false); } }
+#define RD_LAUNCH(WT, TDT, STREAM, CONF)                                                                                              \
+  hipFuncSetAttribute((const void*)rnnt_greedy_kernel<WT, TDT, STREAM, CONF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
+  MI_LAUNCH((rnnt_greedy_kernel<WT, TDT, STREAM, CONF>), dim3(B), dim3(RD_THREADS), shm, s, (typename RnntDecArg<CONF>::t)p)
+#define RD_LAUNCH_C(WT, CONF)                                                                        \
+  if (sout) { if (dur) { RD_LAUNCH(WT, true, true, CONF); } else { RD_LAUNCH(WT, false, true, CONF); } }   \
+  else { if (dur) { RD_LAUNCH(WT, true, false, CONF); } else { RD_LAUNCH(WT, false, false, CONF); } }
+#define RD_LAUNCH_WT(WT) \
+  if (conf) { RD_LAUNCH_C(WT, true) } else { RD_LAUNCH_C(WT, false) }
   if (w_dtype == MI_DT_F32) { RD_LAUNCH_WT(float) } else { RD_LAUNCH_WT(bf16_t) }
 #undef RD_LAUNCH_WT
+#undef RD_LAUNCH_C
 #undef RD_LAUNCH
   return mi_check_launch();
 }
@@ -290,7 +329,7 @@ extern "C" int mi355x_rnnt_greedy_decode(const void* enc_proj, int f_dtype, long
   mi_clear_errors();
   return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
                             w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len, score,
-                            max_out, h_out, c_out, nullptr, nullptr, stream);
+                            max_out, h_out, c_out, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
@@ -305,7 +344,7 @@ extern "C" int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long 
   if (tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
   return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
                             w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len, score,
-                            max_out, h_out, c_out, nullptr, nullptr, stream);
+                            max_out, h_out, c_out, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // ---- resumable search: the same launch from / to a per-stream decoder state (state_in NULL = fresh streams; state_out required)
@@ -321,7 +360,7 @@ extern "C" int mi355x_rnnt_greedy_decode_stream(const void* enc_proj, int f_dtyp
   if (!state_out) return MI_ERR_ARG;
   return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
                             w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len,
-                            nullptr, max_out, nullptr, nullptr, state_in, state_out, stream);
+                            nullptr, max_out, nullptr, nullptr, state_in, state_out, nullptr, nullptr, stream);
 }
 
 extern "C" int mi355x_tdt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
@@ -337,5 +376,63 @@ extern "C" int mi355x_tdt_greedy_decode_stream(const void* enc_proj, int f_dtype
   if (!state_out || tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
   return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
                             w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len,
-                            nullptr, max_out, nullptr, nullptr, state_in, state_out, stream);
+                            nullptr, max_out, nullptr, nullptr, state_in, state_out, nullptr, nullptr, stream);
+}
+
+// ---- the four searches with the confidence of every emitted label (tok_conf f32 [B, max_out], 0.0 padded): the CONF = true
+// instantiations.  Everything else they write is what their siblings write.
+extern "C" int mi355x_rnnt_greedy_decode_conf(
+    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
+    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int blank, int max_symbols, void* tokens,
+    void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out, void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2, void* stream) {
+  mi_clear_errors();
+  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)V1};
+  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len, score,
+                            max_out, h_out, c_out, nullptr, nullptr, tok_conf, &q, stream);
+}
+
+extern "C" int mi355x_tdt_greedy_decode_conf(
+    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
+    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D, const int* durations, int blank,
+    int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out,
+    void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2, void* stream) {
+  mi_clear_errors();
+  TdtDur dur;
+  if (tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
+  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)V1};
+  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len, score,
+                            max_out, h_out, c_out, nullptr, nullptr, tok_conf, &q, stream);
+}
+
+extern "C" int mi355x_rnnt_greedy_decode_stream_conf(
+    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
+    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int blank, int max_symbols, void* tokens,
+    void* times, void* out_len, int max_out, const mi355x_rnnt_stream_state* state_in, const mi355x_rnnt_stream_state* state_out,
+    void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2, void* stream) {
+  mi_clear_errors();
+  if (!state_out) return MI_ERR_ARG;
+  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)V1};
+  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len,
+                            nullptr, max_out, nullptr, nullptr, state_in, state_out, tok_conf, &q, stream);
+}
+
+extern "C" int mi355x_tdt_greedy_decode_stream_conf(
+    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
+    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D, const int* durations, int blank,
+    int max_symbols, void* tokens, void* times, void* out_len, int max_out, const mi355x_rnnt_stream_state* state_in,
+    const mi355x_rnnt_stream_state* state_out, void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2, void* stream) {
+  mi_clear_errors();
+  TdtDur dur;
+  if (!state_out || tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
+  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)V1};
+  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len,
+                            nullptr, max_out, nullptr, nullptr, state_in, state_out, tok_conf, &q, stream);
 }

@@ -10,6 +10,7 @@ from __future__ import annotations
 import copy
 import os
 import contextlib
+from functools import partial
 from typing import Any, Dict, Optional
 
 import torch
@@ -84,7 +85,9 @@ def ctc_transcribe_timestamps(model, audio, batch_size=4, channel_selector=None)
     """`transcribe(timestamps=True)` over a CTC head: greedy decoding that keeps the frames (`mi355x_ctc_greedy_decode_ts`), offsets
     built on the host from the folded ids.  `model` provides `_ctc_log_probs(signal, lengths)` and `_ctc_decoding()`.
     -> one Hypothesis per input, in input order: text, y_sequence, score, timestamp = {'timestep': start frames, 'char', 'word'}
-    (offsets in frames as in the reference -- end exclusive -- plus `start` / `end` in seconds)."""
+    (offsets in frames as in the reference -- end exclusive -- plus `start` / `end` in seconds).  A decoding object built with a
+    `confidence_cfg` decodes through `mi355x_ctc_greedy_decode_conf` instead and the hypotheses carry the frame / token / word
+    confidences the config preserves."""
     from ..modules.rnnt_decoding import Hypothesis
     decoding = model._ctc_decoding()
     if decoding is None:
@@ -94,15 +97,31 @@ def ctc_transcribe_timestamps(model, audio, batch_size=4, channel_selector=None)
         for i in range(0, len(audio), batch_size):
             sig, lens = _audio_batch(model, audio[i:i + batch_size], channel_selector)
             log_probs, enc_len = model._ctc_log_probs(sig, lens)
-            tokens, out_len, score, start, end = (t.cpu() for t in decoding.decode_ids(log_probs, enc_len, return_timestamps=True))
+            ccfg = getattr(decoding, "confidence_cfg", None)
+            decode = decoding.decode_ids_confidence if ccfg is not None else partial(decoding.decode_ids, return_timestamps=True)
+            tokens, out_len, score, start, end, *conf = (t.cpu() for t in decode(log_probs, enc_len))
             for r in range(tokens.shape[0]):
                 n = int(out_len[r])
                 ids, st, en = tokens[r, :n].tolist(), start[r, :n].tolist(), end[r, :n].tolist()
                 char, word = decoding.offsets(ids, st, en)
-                out.append(Hypothesis(score=float(score[r]), y_sequence=tokens[r, :n].to(torch.long), text=decoding.ids_to_text(ids),
-                                      timestamp={"timestep": st, "char": _with_seconds(char, stride),
-                                                 "word": _with_seconds(word, stride)}, length=int(enc_len[r])))
+                hyp = Hypothesis(score=float(score[r]), y_sequence=tokens[r, :n].to(torch.long), text=decoding.ids_to_text(ids),
+                                 timestamp={"timestep": st, "char": _with_seconds(char, stride),
+                                            "word": _with_seconds(word, stride)}, length=int(enc_len[r]))
+                if ccfg is not None:
+                    ctc_fill_confidence(hyp, decoding, ids, conf[0][r, : int(enc_len[r])].tolist(), conf[1][r, :n].tolist())
+                out.append(hyp)
     return out
+
+
+def ctc_fill_confidence(hyp, decoding, ids, frame_conf, tok_conf):
+    """the confidences `decoding.confidence_cfg` preserves, into a CTC hypothesis: per frame, per token, per word"""
+    ccfg = decoding.confidence_cfg
+    if ccfg.preserve_frame_confidence:
+        hyp.frame_confidence = frame_conf
+    if ccfg.wants_tokens:   # (the words are folded from them: present with either flag, as on the transducer path)
+        hyp.token_confidence = tok_conf
+    if ccfg.preserve_word_confidence:
+        hyp.word_confidence = decoding.word_confidence(ids, tok_conf)
 
 
 def ctc_align_audio(model, audio, texts, batch_size=4, channel_selector=None):
@@ -285,7 +304,8 @@ class EncDecCTCModel(nn.Module):
             strategy = str((self._cfg.get("decoding") or {}).get("strategy", "greedy_batch"))
             if strategy not in ("greedy", "greedy_batch"):  # ctc_decoding.py:231-236: beam / pyctcdecode / flashlight / wfst need their own decoders
                 raise NotImplementedError(f"CTC decoding strategy '{strategy}' (implemented: greedy, greedy_batch)")
-            self._wer = WER(GreedyCTCDecoder(vocabulary=list(vocab)), use_cer=bool(self._cfg.get("use_cer", False)))
+            self._wer = WER(GreedyCTCDecoder(vocabulary=list(vocab), confidence_cfg=(self._cfg.get("decoding") or {}).get("confidence_cfg")),
+                            use_cer=bool(self._cfg.get("use_cer", False)))
         return self._wer
 
     # ------------------------------------------------------------------ evaluation (ctc_models.py:604-700, asr_model.py:95-160)
@@ -486,6 +506,8 @@ class EncDecCTCModel(nn.Module):
         self.loss = CTCLoss(num_classes=self.decoder.num_classes_with_blank - 1, zero_infinity=True,
                             reduction=self._cfg.get("ctc_reduction", "mean_batch"))
         self._wer = None            # rebuilt lazily over the new vocabulary
+        if decoding_cfg is not None and "confidence_cfg" in dict(decoding_cfg):   # the new decoding object's confidence settings
+            self._cfg["decoding"] = dict(self._cfg.get("decoding") or {}, confidence_cfg=dict(decoding_cfg)["confidence_cfg"])
         self._optimizer = self._scheduler = self._syncs = None
         self._cfg["decoder"] = dec
         self._cfg["labels"] = list(new_vocabulary)
@@ -820,7 +842,7 @@ class EncDecCTCModelBPE(EncDecCTCModel):
         if not os.path.isfile(model_path):
             raise NotADirectoryError(f"New tokenizer dir must be non-empty path to a directory. But I got: {new_tokenizer_dir}")
         tokenizer = SentencePieceTokenizer(model_path)
-        super().change_vocabulary(tokenizer.vocab)
+        super().change_vocabulary(tokenizer.vocab, decoding_cfg=decoding_cfg)
         self.tokenizer = tokenizer
         self._wer = None
         self._cfg["tokenizer"] = dict(self._cfg.get("tokenizer", {}), dir=os.path.dirname(model_path), model_path=model_path,

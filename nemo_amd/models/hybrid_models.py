@@ -15,7 +15,7 @@ import torch
 
 from ..modules import CTCLoss
 from .ctc_models import _build as _build_ctc
-from .ctc_models import ctc_align_audio, ctc_transcribe_timestamps, frame_stride_s
+from .ctc_models import ctc_align_audio, ctc_fill_confidence, ctc_transcribe_timestamps, frame_stride_s
 from .rnnt_models import EncDecRNNTModel, fastconformer_tdt_config, fastconformer_transducer_config, rnnt_conformer_stream_step
 
 _GREEDY = ("greedy", "greedy_batch")
@@ -42,12 +42,18 @@ class _CTCHeadText:
         m = self.model
         dec = m.ctc_decoding
         log_probs = m.ctc_decoder(encoder_output=encoder_output)
-        tokens, out_len, score = (t.cpu() for t in dec.decode_ids(log_probs, encoded_lengths))
         lens = encoded_lengths.cpu()
         hyps = []
+        if dec.confidence_cfg is not None:   # the same decoding with confidences, from the one launch that computes both
+            tokens, out_len, score, _, _, fc, tc = (t.cpu() for t in dec.decode_ids_confidence(log_probs, encoded_lengths))
+        else:
+            tokens, out_len, score = (t.cpu() for t in dec.decode_ids(log_probs, encoded_lengths))
         for b in range(tokens.shape[0]):
-            ids = tokens[b, : int(out_len[b])].to(torch.long)
+            n = int(out_len[b])
+            ids = tokens[b, :n].to(torch.long)
             hyps.append(Hypothesis(score=float(score[b]), y_sequence=ids, text=dec.ids_to_text(ids.tolist()), length=int(lens[b])))
+            if dec.confidence_cfg is not None:
+                ctc_fill_confidence(hyps[-1], dec, ids.tolist(), fc[b, : int(lens[b])].tolist(), tc[b, :n].tolist())
         return hyps
 
 
@@ -105,7 +111,8 @@ class EncDecHybridRNNTCTCModel(EncDecRNNTModel):
                 return None
             from ..modules import WER, GreedyCTCDecoder
             _check_ctc_strategy(self._cfg["aux_ctc"].get("decoding"))
-            self._ctc_wer = WER(GreedyCTCDecoder(vocabulary=list(vocab)), use_cer=bool(self._cfg.get("use_cer", False)))
+            ccfg = (self._cfg["aux_ctc"].get("decoding") or {}).get("confidence_cfg")
+            self._ctc_wer = WER(GreedyCTCDecoder(vocabulary=list(vocab), confidence_cfg=ccfg), use_cer=bool(self._cfg.get("use_cer", False)))
         return self._ctc_wer
 
     @property

@@ -131,7 +131,8 @@ class EncDecRNNTModel(EncDecCTCModel):
             durations = dcfg.get("durations") or (self.loss.durations if tdt_loss else None)
             self._decoding = RNNTDecoding(self.decoder, self.joint, vocabulary=list(vocab) if vocab is not None else None,
                                           max_symbols=ms, tokenizer=self.tokenizer if vocab is None else None,
-                                          model_type=model_type, durations=list(durations) if durations else None)
+                                          model_type=model_type, durations=list(durations) if durations else None,
+                                          confidence_cfg=dcfg.get("confidence_cfg"))
         return self._decoding
 
     @property

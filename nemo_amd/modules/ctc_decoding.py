@@ -19,11 +19,17 @@ class GreedyCTCDecoder:
     """blank_id = len(vocabulary) as in CTCDecoding.__init__ (ctc_decoding.py:1044); `vocabulary` maps ids to strings
     (characters, or word pieces whose leading U+2581 marks a word start -- the SentencePiece convention)."""
 
-    def __init__(self, vocabulary: Optional[Sequence[str]] = None, blank_id: Optional[int] = None):
+    def __init__(self, vocabulary: Optional[Sequence[str]] = None, blank_id: Optional[int] = None, confidence_cfg=None):
         if vocabulary is None and blank_id is None:
             raise ValueError("either a vocabulary or a blank_id is required")
         self.vocabulary = list(vocabulary) if vocabulary is not None else None
         self.blank_id = len(self.vocabulary) if blank_id is None else int(blank_id)
+        from .confidence import confidence_from
+        self.confidence_cfg = confidence_from(confidence_cfg)   # None: no confidence is computed, decoding is what it was
+
+    @property
+    def word_pieces(self) -> bool:
+        return self.vocabulary is not None and any(v.startswith("▁") for v in self.vocabulary)
 
     @torch.no_grad()
     def decode_ids(self, log_probs: torch.Tensor, lengths: Optional[torch.Tensor] = None, return_timestamps: bool = False):
@@ -39,12 +45,35 @@ class GreedyCTCDecoder:
             return ops.ctc_greedy_decode_ts(lp, lens, self.blank_id)
         return ops.ctc_greedy_decode(lp, lens, self.blank_id)
 
+    @torch.no_grad()
+    def decode_ids_confidence(self, log_probs: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        """`decode_ids(..., return_timestamps=True)` with confidences (needs a `confidence_cfg`): its tuple plus (frame_conf f32
+        [B,T], tok_conf f32 [B,T]), 0.0 padded -- the configured measure of every frame and its aggregation over each token's
+        frames, from the same launch (`mi355x_ctc_greedy_decode_conf`)"""
+        cfg = self.confidence_cfg
+        if cfg is None:
+            raise ValueError("confidence needs a decoder built with a `confidence_cfg` that preserves a confidence")
+        if log_probs.dim() != 3:
+            raise ValueError(f"`decoder_output` must be a tensor of shape [B, T, V] (log probs, float). Provided shape = "
+                             f"{tuple(log_probs.shape)}")
+        from .confidence import AGGREGATIONS
+        lp = log_probs.to(torch.float32).contiguous()
+        lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
+        return ops.ctc_greedy_decode_conf(lp, lens, self.blank_id, cfg.method_cfg.kernel_args(lp.shape[2]),
+                                          AGGREGATIONS[cfg.aggregation], cfg.exclude_blank)
+
     def offsets(self, ids: Sequence[int], starts: Sequence[int], ends: Sequence[int]):
         """(char offsets, word offsets) of a token sequence with its first / last frames, see `ctc_offsets`"""
         if self.vocabulary is None:
             raise ValueError("no vocabulary: offsets are not available")
-        return ctc_offsets([self.vocabulary[i] for i in ids], starts, ends,
-                           word_pieces=any(v.startswith("▁") for v in self.vocabulary))
+        return ctc_offsets([self.vocabulary[i] for i in ids], starts, ends, word_pieces=self.word_pieces)
+
+    def word_confidence(self, ids: Sequence[int], token_conf: Sequence[float]):
+        """one confidence per word of `offsets(ids, ...)`: the configured aggregation over the word's token confidences"""
+        if self.vocabulary is None or self.confidence_cfg is None:
+            raise ValueError("word confidence needs a vocabulary and a `confidence_cfg`")
+        from .confidence import word_confidence
+        return word_confidence([self.vocabulary[i] for i in ids], token_conf, self.word_pieces, self.confidence_cfg.aggregation)
 
     def ids_to_text(self, ids: Sequence[int]) -> str:
         if self.vocabulary is None:

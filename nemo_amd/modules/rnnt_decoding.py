@@ -25,6 +25,13 @@ Streaming: `forward(..., partial_hypotheses=hyps)` (the first chunk: `hyps = dec
 done, and for TDT the frames a duration already jumped over) through the resumable search (`mi355x_rnnt_greedy_decode_stream` /
 `mi355x_tdt_greedy_decode_stream`); the returned hypotheses cover the whole stream so far and are new objects.  Over the same
 encoder-projection values, any cut into chunks gives bit-identical hypotheses to one call over the concatenation.
+
+Confidence (`confidence_cfg`, modules/confidence.py): with token or word confidence asked for the search runs through the `_conf`
+entry points (`mi355x_rnnt_greedy_decode_conf` and its siblings): the measure of the label distribution of every step that emitted
+a label, computed inside the search from the logits it already holds.  `Hypothesis.token_confidence` has one value per label
+(streaming: appended chunk by chunk) whenever token OR word confidence is preserved, since `RNNTDecoding` folds the words'
+`word_confidence` from it.  Blank steps are not kept, so
+`preserve_frame_confidence` (and `preserve_alignments`) stay unavailable.
 """
 from __future__ import annotations
 
@@ -46,12 +53,19 @@ class Hypothesis:  # parts/utils/rnnt_utils.py:35-110 (the fields greedy decodin
     dec_state: Optional[object] = None   # one-shot search: the final (h, c); streaming: ops.RNNTStreamState of this stream (batch 1, device)
     length: int = 0
     last_token: Optional[torch.Tensor] = None   # i32 [1] on the device (= dec_state.last); blank before the first label
+    frame_confidence: Optional[List[float]] = None   # CTC: one value per frame of the utterance
+    token_confidence: Optional[List[float]] = None   # one value per label of y_sequence
+    word_confidence: Optional[List[float]] = None    # one value per word of the text
 
 
 class GreedyBatchedRNNTInfer:
     def __init__(self, decoder_model, joint_model, blank_index: int, max_symbols_per_step: Optional[int] = None,
-                 preserve_alignments: bool = False, preserve_frame_confidence: bool = False, **unused):
-        if preserve_alignments or preserve_frame_confidence:
+                 preserve_alignments: bool = False, preserve_frame_confidence: bool = False, confidence_cfg=None, **unused):
+        from .confidence import confidence_from
+        self.confidence_cfg = confidence_from(confidence_cfg)   # None: no confidence, the search is what it was
+        if preserve_alignments or preserve_frame_confidence or (self.confidence_cfg is not None
+                                                                and self.confidence_cfg.preserve_frame_confidence):
+            # the search keeps the steps that emitted a label: per-step blank confidences / alignments are not stored
             raise NotImplementedError("alignments / frame confidences are not produced by the on-device search")
         if max_symbols_per_step is not None and max_symbols_per_step <= 0:
             raise ValueError(f"Expected max_symbols_per_step > 0 (or None), got {max_symbols_per_step}")  # rnnt_greedy_decoding.py:187
@@ -91,23 +105,43 @@ class GreedyBatchedRNNTInfer:
                 self._blank_index, self.max_symbols or 0)
         return f.view(B, T, J), args
 
+    @property
+    def _with_confidence(self) -> bool:
+        return self.confidence_cfg is not None and self.confidence_cfg.wants_tokens
+
+    def _method(self, args):
+        """the measure's kernel arguments for this decoder's label distribution (V1 = rows of the embedding table)"""
+        return self.confidence_cfg.method_cfg.kernel_args(args[0].shape[0])
+
     @torch.no_grad()
-    def decode_ids(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, with_state: bool = False):
-        """encoder_output [B, D, T] (device) -> (tokens i32 [B, N] -1 padded, frame indices, lengths i32 [B], scores f32 [B])"""
+    def decode_ids(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, with_state: bool = False,
+                   with_confidence: bool = False):
+        """encoder_output [B, D, T] (device) -> (tokens i32 [B, N] -1 padded, frame indices, lengths i32 [B], scores f32 [B]
+        [, (h, c)][, tok_conf f32 [B, N] 0.0 padded: with_confidence, needs a `confidence_cfg`])"""
         f, args = self._project(encoder_output)
         lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        if with_confidence:
+            return self._search_conf(f, lens, *args, method=self._method(args), with_state=with_state)
         return self._search(f, lens, *args, with_state=with_state)
 
     _search = staticmethod(ops.rnnt_greedy_decode)
     _search_stream = staticmethod(ops.rnnt_greedy_decode_stream)
 
+    def _search_conf(self, *args, method, with_state=False):
+        return ops.rnnt_greedy_decode_conf(*args, method, with_state=with_state)
+
+    def _search_stream_conf(self, *args, method, state=None):
+        return ops.rnnt_greedy_decode_stream_conf(*args, method, state=state)
+
     @torch.no_grad()
-    def decode_ids_stream(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, state=None):
+    def decode_ids_stream(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, state=None, with_confidence: bool = False):
         """one chunk of every stream: encoder_output [B, D, T_chunk], encoded_lengths = this chunk's frames per stream, `state` the
         ops.RNNTStreamState of the previous chunk (None: fresh streams) -> (tokens, GLOBAL frame indices, lengths of this chunk's
-        labels, the next state)"""
+        labels, the next state[, tok_conf of this chunk's labels: with_confidence])"""
         f, args = self._project(encoder_output)
         lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        if with_confidence:
+            return self._search_stream_conf(f, lens, *args, method=self._method(args), state=state)
         return self._search_stream(f, lens, *args, state=state)
 
     def fresh_hypotheses(self, batch_size: int, device=None):
@@ -117,21 +151,26 @@ class GreedyBatchedRNNTInfer:
         device = device if device is not None else dec.prediction["embed"].weight.device
         st = ops.RNNTStreamState.fresh(batch_size, dec.pred_hidden, self._blank_index, device)
         return [Hypothesis(score=0.0, y_sequence=torch.zeros(0, dtype=torch.long), timestamp=[], dec_state=st.select(b), length=0,
-                           last_token=st.select(b).last) for b in range(batch_size)]
+                           last_token=st.select(b).last, token_confidence=[] if self._with_confidence else None)
+                for b in range(batch_size)]
 
     def forward(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, partial_hypotheses=None):
         """Without `partial_hypotheses`: the one-shot search of whole utterances, as ever (`dec_state` = the final (h, c)).
         With them (a list of hypotheses this decoder returned for earlier chunks, or `fresh_hypotheses(B)` for the first chunk):
         the resumable search; the returned hypotheses cover the whole stream so far and carry the next decoder state."""
         B = encoder_output.shape[0]
+        conf = self._with_confidence
         if partial_hypotheses is None:
-            tokens, times, out_len, score, (h, c) = self.decode_ids(encoder_output, encoded_lengths, with_state=True)
+            tokens, times, out_len, score, (h, c), *tc = self.decode_ids(encoder_output, encoded_lengths, with_state=True,
+                                                                         with_confidence=conf)
             tokens, times, out_len, score = tokens.cpu(), times.cpu(), out_len.cpu(), score.cpu()   # the only D2H copies
+            tc = tc[0].cpu() if conf else None
             hyps = []
             for b in range(B):
                 n = int(out_len[b])
                 hyps.append(Hypothesis(score=float(score[b]), y_sequence=tokens[b, :n].to(torch.long), timestamp=times[b, :n].tolist(),
-                                       dec_state=(h[b], c[b]), length=int(encoded_lengths[b])))
+                                       dec_state=(h[b], c[b]), length=int(encoded_lengths[b]),
+                                       token_confidence=tc[b, :n].tolist() if conf else None))
             return (hyps,)
         if len(partial_hypotheses) != B:
             raise ValueError(f"{len(partial_hypotheses)} partial hypotheses for a batch of {B}")
@@ -139,8 +178,9 @@ class GreedyBatchedRNNTInfer:
             raise ValueError("`partial_hypotheses` must carry a stream state in `dec_state`: hypotheses this decoder returned for "
                              "earlier chunks, or `fresh_hypotheses(batch_size)` for the first chunk of a stream")
         state = ops.RNNTStreamState.stack([h.dec_state for h in partial_hypotheses])
-        tokens, times, out_len, nxt = self.decode_ids_stream(encoder_output, encoded_lengths, state)
+        tokens, times, out_len, nxt, *tc = self.decode_ids_stream(encoder_output, encoded_lengths, state, with_confidence=conf)
         tokens, times, out_len, score = tokens.cpu(), times.cpu(), out_len.cpu(), nxt.score.cpu()   # the only D2H copies
+        tc = tc[0].cpu() if conf else None
         lens = encoded_lengths.cpu()
         hyps = []
         for b in range(B):   # the whole stream so far, in new objects: the inputs stay as they are
@@ -149,7 +189,8 @@ class GreedyBatchedRNNTInfer:
             y = torch.cat((prev.y_sequence.to(torch.long).cpu(), tokens[b, :n].to(torch.long)))
             st = nxt.select(b)
             hyps.append(Hypothesis(score=float(score[b]), y_sequence=y, timestamp=list(prev.timestamp) + times[b, :n].tolist(),
-                                   dec_state=st, length=int(prev.length) + int(lens[b]), last_token=st.last))
+                                   dec_state=st, length=int(prev.length) + int(lens[b]), last_token=st.last,
+                                   token_confidence=list(prev.token_confidence or []) + tc[b, :n].tolist() if conf else None))
         return (hyps,)
 
     __call__ = forward
@@ -177,22 +218,32 @@ class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
     def _search_stream(self, *args, state=None):
         return ops.tdt_greedy_decode_stream(*args[:16], self.durations, args[16], state=state)
 
+    def _search_conf(self, *args, method, with_state=False):
+        return ops.tdt_greedy_decode_conf(*args[:16], self.durations, args[16], method, with_state=with_state)
+
+    def _search_stream_conf(self, *args, method, state=None):
+        return ops.tdt_greedy_decode_stream_conf(*args[:16], self.durations, args[16], method, state=state)
+
 
 class RNNTDecoding:
     """`strategy: greedy_batch` of AbstractRNNTDecoding (rnnt_decoding.py:216-330) for a character / word-piece vocabulary;
     blank id = len(vocabulary) (rnnt_decoding.py:1170)."""
 
     def __init__(self, decoder, joint, vocabulary: Optional[Sequence[str]] = None, max_symbols: Optional[int] = 10,
-                 tokenizer=None, model_type: str = "rnnt", durations: Optional[Sequence[int]] = None):
+                 tokenizer=None, model_type: str = "rnnt", durations: Optional[Sequence[int]] = None, confidence_cfg=None):
+        from .confidence import confidence_from
         self.vocabulary = list(vocabulary) if vocabulary is not None else None
         self.tokenizer = tokenizer
         self.blank_id = decoder.blank_idx
+        self.confidence_cfg = confidence_from(confidence_cfg)
         if model_type == "tdt":   # rnnt_decoding.py: `model_type: tdt` with the duration set of the joint's extra outputs
             if not durations:
                 raise ValueError("decoding with model_type 'tdt' needs `durations`")
-            self.decoding = GreedyBatchedTDTInfer(decoder, joint, self.blank_id, durations, max_symbols_per_step=max_symbols)
+            self.decoding = GreedyBatchedTDTInfer(decoder, joint, self.blank_id, durations, max_symbols_per_step=max_symbols,
+                                                  confidence_cfg=self.confidence_cfg)
         elif model_type == "rnnt":
-            self.decoding = GreedyBatchedRNNTInfer(decoder, joint, self.blank_id, max_symbols_per_step=max_symbols)
+            self.decoding = GreedyBatchedRNNTInfer(decoder, joint, self.blank_id, max_symbols_per_step=max_symbols,
+                                                   confidence_cfg=self.confidence_cfg)
         else:
             raise NotImplementedError(f"transducer decoding model_type '{model_type}' (implemented: rnnt, tdt)")
 
@@ -209,9 +260,27 @@ class RNNTDecoding:
                                         return_hypotheses: bool = False, partial_hypotheses=None):
         hyps = self.decoding(encoder_output=encoder_output, encoded_lengths=encoded_lengths,
                              partial_hypotheses=partial_hypotheses)[0]
+        words = self.confidence_cfg is not None and self.confidence_cfg.preserve_word_confidence
         for h in hyps:
             h.text = self.ids_to_text(h.y_sequence.tolist())
+            if words:
+                h.word_confidence = self.word_confidence(h.y_sequence.tolist(), h.token_confidence)
         return hyps
+
+    def ids_to_tokens(self, ids: Sequence[int]) -> List[str]:
+        ids = [int(i) for i in ids]
+        if self.tokenizer is not None:
+            return list(self.tokenizer.ids_to_tokens(ids))
+        if self.vocabulary is None:
+            raise ValueError("no vocabulary: tokens are not available")
+        return [self.vocabulary[i] for i in ids]
+
+    def word_confidence(self, ids: Sequence[int], token_conf: Sequence[float]) -> List[float]:
+        """the configured aggregation of the token confidences over every word (the grouping of `ctc_offsets`)"""
+        from .confidence import word_confidence
+        toks = self.ids_to_tokens(ids)
+        pieces = any(t.startswith("▁") for t in (self.vocabulary if self.vocabulary is not None else toks))
+        return word_confidence(toks, token_conf, pieces, self.confidence_cfg.aggregation)
 
 
 class RNNTWER:

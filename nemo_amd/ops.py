@@ -453,6 +453,22 @@ def ctc_greedy_decode_ts(logp, lens, blank):
     return tokens, out_len, score, tok_start, tok_end
 
 
+def ctc_greedy_decode_conf(logp, lens, blank, method, aggregation=1, exclude_blank=True):
+    """ctc_greedy_decode_ts plus confidences (mi355x_ctc_greedy_decode_conf): `method` = (method, norm, alpha, k0, k1, k2) for
+    V = C (modules.confidence.ConfidenceMethodConfig.kernel_args), aggregation 0..3 = mean / min / max / prod -> (tokens, out_len,
+    score, tok_start, tok_end, frame_conf f32 [B,T]: 0.0 beyond the utterance, tok_conf f32 [B,T]: the aggregation of frame_conf
+    over each token's frames (exclude_blank: its own run; else from behind the previous token's run), 0.0 padded)"""
+    B, T, C_ = logp.shape
+    tokens, tok_start, tok_end = (torch.empty(B, T, dtype=torch.int32, device=logp.device) for _ in range(3))
+    out_len = torch.empty(B, dtype=torch.int32, device=logp.device)
+    score = torch.empty(B, dtype=torch.float32, device=logp.device)
+    frame_conf, tok_conf = (torch.empty(B, T, dtype=torch.float32, device=logp.device) for _ in range(2))
+    check(lib.mi355x_ctc_greedy_decode_conf(_ptr(logp), _ptr(lens), _ptr(tokens), _ptr(out_len), _ptr(score), _ptr(tok_start),
+                                            _ptr(tok_end), _ptr(frame_conf), _ptr(tok_conf), B, T, C_, blank, *method,
+                                            int(aggregation), int(bool(exclude_blank)), _stream()), "ctc_greedy_decode_conf")
+    return tokens, out_len, score, tok_start, tok_end, frame_conf, tok_conf
+
+
 def ctc_align(logp, targets, in_len, tgt_len, blank):
     """Viterbi forced alignment (mi355x_ctc_align): logp f32 [B,T,C] contiguous, targets i64 [B,U], in_len / tgt_len i64 [B] ->
     (path i32 [B,T]: state 0..2U per frame, tok_start i32 [B,U], tok_end i32 [B,U]: first / last frame of each label, score f32 [B]);
@@ -724,11 +740,9 @@ def rnnt_loss_pitched(acts, ld_acts, B, T, U1, V1, labels, act_lens, label_lens,
     return costs
 
 
-def rnnt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
-                       blank, max_symbols, max_out=None, with_state=False):
-    """greedy transducer search of a whole batch in one launch (mi355x_rnnt_greedy_decode).  enc_proj [B, T, J] = joint.enc(encoder
-    output); weights fp32 or bf16 (all four the same dtype).  -> (tokens i32 [B, max_out] -1 padded, frame indices likewise,
-    lengths i32 [B], score f32 [B][, (h, c) f32 [B, H]])"""
+def _greedy_decode(tdt, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
+                   blank, durations, max_symbols, max_out, with_state, method=None):
+    """the one-shot searches: buffers, argument tuple and the entry point of (RNN-T | TDT) x (plain | `method` given: the _conf form)"""
     B, T, J = enc_proj.shape
     V1, H = emb.shape
     if max_out is None:
@@ -740,12 +754,37 @@ def rnnt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b
     score = torch.empty(B, dtype=torch.float32, device=dev)
     h = torch.empty(B, H, dtype=torch.float32, device=dev) if with_state else None
     c = torch.empty(B, H, dtype=torch.float32, device=dev) if with_state else None
-    check(lib.mi355x_rnnt_greedy_decode(_ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih,
-                                        _ptr(w_hh), ld_hh, _ptr(b_ih), _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out),
-                                        ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1, blank, max_symbols, _ptr(tokens),
-                                        _ptr(times), _ptr(out_len), _ptr(score), max_out, _ptr(h), _ptr(c), _stream()),
-          "rnnt_greedy_decode")
-    return (tokens, times, out_len, score) + (((h, c),) if with_state else ())
+    head = (_ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih, _ptr(w_hh), ld_hh,
+            _ptr(b_ih), _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out), ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1)
+    if tdt:
+        head += _tdt_durations(durations)
+    tail = (blank, max_symbols, _ptr(tokens), _ptr(times), _ptr(out_len), _ptr(score), max_out, _ptr(h), _ptr(c))
+    name = ("tdt" if tdt else "rnnt") + "_greedy_decode" + ("_conf" if method is not None else "")
+    extra = ()
+    if method is not None:   # the _conf entries: the confidence of every emitted label
+        tok_conf = torch.empty(B, max_out, dtype=torch.float32, device=dev)
+        tail += (_ptr(tok_conf), *method)
+        extra = (tok_conf,)
+    check(getattr(lib, "mi355x_" + name)(*head, *tail, _stream()), name)
+    return (tokens, times, out_len, score) + (((h, c),) if with_state else ()) + extra
+
+
+def rnnt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
+                       blank, max_symbols, max_out=None, with_state=False):
+    """greedy transducer search of a whole batch in one launch (mi355x_rnnt_greedy_decode).  enc_proj [B, T, J] = joint.enc(encoder
+    output); weights fp32 or bf16 (all four the same dtype).  -> (tokens i32 [B, max_out] -1 padded, frame indices likewise,
+    lengths i32 [B], score f32 [B][, (h, c) f32 [B, H]])"""
+    return _greedy_decode(False, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                          b_out, blank, None, max_symbols, max_out, with_state)
+
+
+def rnnt_greedy_decode_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                            b_out, blank, max_symbols, method, max_out=None, with_state=False):
+    """rnnt_greedy_decode plus the confidence of every emitted label (mi355x_rnnt_greedy_decode_conf): `method` = (method, norm,
+    alpha, k0, k1, k2) for V = V1 (modules.confidence.ConfidenceMethodConfig.kernel_args) -> rnnt_greedy_decode's tuple with
+    tok_conf f32 [B, max_out] (0.0 padded) appended"""
+    return _greedy_decode(False, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                          b_out, blank, None, max_symbols, max_out, with_state, method=method)
 
 
 def _tdt_durations(durations):
@@ -779,24 +818,15 @@ def tdt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_
                       blank, durations, max_symbols, max_out=None, with_state=False):
     """greedy TDT search of a whole batch in one launch (mi355x_tdt_greedy_decode): as rnnt_greedy_decode, with w_out / b_out
     holding V1 + len(durations) rows (label logits, then duration logits); frames advance by the predicted duration"""
-    B, T, J = enc_proj.shape
-    V1, H = emb.shape
-    D, dur = _tdt_durations(durations)
-    if max_out is None:
-        max_out = T * max_symbols if max_symbols > 0 else 4 * T
-    dev = enc_proj.device
-    tokens = torch.empty(B, max_out, dtype=torch.int32, device=dev)
-    times = torch.empty(B, max_out, dtype=torch.int32, device=dev)
-    out_len = torch.empty(B, dtype=torch.int32, device=dev)
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    h = torch.empty(B, H, dtype=torch.float32, device=dev) if with_state else None
-    c = torch.empty(B, H, dtype=torch.float32, device=dev) if with_state else None
-    check(lib.mi355x_tdt_greedy_decode(_ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih,
-                                       _ptr(w_hh), ld_hh, _ptr(b_ih), _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out),
-                                       ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1, D, dur, blank, max_symbols, _ptr(tokens),
-                                       _ptr(times), _ptr(out_len), _ptr(score), max_out, _ptr(h), _ptr(c), _stream()),
-          "tdt_greedy_decode")
-    return (tokens, times, out_len, score) + (((h, c),) if with_state else ())
+    return _greedy_decode(True, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                          b_out, blank, durations, max_symbols, max_out, with_state)
+
+
+def tdt_greedy_decode_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                           b_out, blank, durations, max_symbols, method, max_out=None, with_state=False):
+    """tdt_greedy_decode plus the confidence of every emitted label over the V1 label logits (mi355x_tdt_greedy_decode_conf)"""
+    return _greedy_decode(True, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                          b_out, blank, durations, max_symbols, max_out, with_state, method=method)
 
 
 class _StreamStateC(C.Structure):   # mi355x_rnnt_stream_state
@@ -847,7 +877,7 @@ class RNNTStreamState:
 
 
 def _greedy_decode_stream(tdt, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                          b_out, blank, durations, max_symbols, state, max_out):
+                          b_out, blank, durations, max_symbols, state, max_out, method=None):
     B, T, J = enc_proj.shape
     V1, H = emb.shape
     if max_out is None:
@@ -863,14 +893,18 @@ def _greedy_decode_stream(tdt, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh,
     s_out = nxt._c(B, H)
     head = (_ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih, _ptr(w_hh), ld_hh,
             _ptr(b_ih), _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out), ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1)
-    tail = (blank, max_symbols, _ptr(tokens), _ptr(times), _ptr(out_len), max_out, C.byref(s_in) if s_in is not None else None,
-            C.byref(s_out), _stream())
     if tdt:
-        D, dur = _tdt_durations(durations)
-        check(lib.mi355x_tdt_greedy_decode_stream(*head, D, dur, *tail), "tdt_greedy_decode_stream")
-    else:
-        check(lib.mi355x_rnnt_greedy_decode_stream(*head, *tail), "rnnt_greedy_decode_stream")
-    return tokens, times, out_len, nxt
+        head += _tdt_durations(durations)
+    tail = (blank, max_symbols, _ptr(tokens), _ptr(times), _ptr(out_len), max_out, C.byref(s_in) if s_in is not None else None,
+            C.byref(s_out))
+    name = ("tdt" if tdt else "rnnt") + "_greedy_decode_stream" + ("_conf" if method is not None else "")
+    extra = ()
+    if method is not None:   # the _conf entries: the chunk's labels with their confidences
+        tok_conf = torch.empty(B, max_out, dtype=torch.float32, device=dev)
+        tail += (_ptr(tok_conf), *method)
+        extra = (tok_conf,)
+    check(getattr(lib, "mi355x_" + name)(*head, *tail, _stream()), name)
+    return (tokens, times, out_len, nxt) + extra
 
 
 def rnnt_greedy_decode_stream(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
@@ -889,6 +923,21 @@ def tdt_greedy_decode_stream(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b
     that jumps past the chunk's end is carried in the state (`skip`) and taken off the next chunk(s)"""
     return _greedy_decode_stream(True, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
                                  ld_out, b_out, blank, durations, max_symbols, state, max_out)
+
+
+def rnnt_greedy_decode_stream_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                                   b_out, blank, max_symbols, method, state=None, max_out=None):
+    """rnnt_greedy_decode_stream plus the confidence of this chunk's labels (mi355x_rnnt_greedy_decode_stream_conf) -> (tokens,
+    global frame indices, lengths, next state, tok_conf f32 [B, max_out] 0.0 padded); bit-identical to one launch for any cut"""
+    return _greedy_decode_stream(False, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
+                                 ld_out, b_out, blank, None, max_symbols, state, max_out, method=method)
+
+
+def tdt_greedy_decode_stream_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                                  b_out, blank, durations, max_symbols, method, state=None, max_out=None):
+    """tdt_greedy_decode_stream plus the confidence of this chunk's labels (mi355x_tdt_greedy_decode_stream_conf)"""
+    return _greedy_decode_stream(True, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
+                                 ld_out, b_out, blank, durations, max_symbols, state, max_out, method=method)
 
 
 def row_scale(x, vec, rows, cols):

@@ -1,4 +1,5 @@
-"""Time the one-shot greedy search entry points (mi355x_rnnt_greedy_decode, mi355x_tdt_greedy_decode) of ONE library build, chosen
+"""Time the greedy search entry points (mi355x_rnnt_greedy_decode, mi355x_tdt_greedy_decode and, where the build has them, their
+resumable forms from a fresh state: mi355x_rnnt_greedy_decode_stream, mi355x_tdt_greedy_decode_stream) of ONE library build, chosen
 per process through MI355X_ASR_LIB (default: the in-tree library; `tools/ab_build.py` builds variants).  Loads the library with
 ctypes directly, so a build that lacks newer symbols can be timed too.  B = 32, T = 250, H = J = 640, V1 = 1025, bf16 weights,
 seeded random weights and projection (the same work in every process).  Prints one JSON line; alternate processes of the
@@ -17,6 +18,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 vp, i32, i64 = C.c_void_p, C.c_int, C.c_longlong
 HEAD = [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32, i32]
 TAIL = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+STAIL = [i32, i32, vp, vp, vp, i32, vp, vp, vp]   # the resumable forms: no score / h / c, state_in and state_out instead
+
+
+class StreamState(C.Structure):   # mi355x_rnnt_stream_state
+    _fields_ = [(n, vp) for n in ("h", "c", "last", "score", "frames_done", "skip", "zero_run")]
 
 
 def main():
@@ -53,6 +59,15 @@ def main():
     dur = (C.c_int * D)(0, 1, 2, 3, 4)
     calls = {"rnnt": lambda: lib.mi355x_rnnt_greedy_decode(*head, *tail),
              "tdt": lambda: lib.mi355x_tdt_greedy_decode(*head, D, dur, *tail)}
+    if hasattr(lib, "mi355x_rnnt_greedy_decode_stream"):
+        lib.mi355x_rnnt_greedy_decode_stream.argtypes = HEAD + STAIL
+        lib.mi355x_tdt_greedy_decode_stream.argtypes = HEAD + [i32, vp] + STAIL
+        st = [torch.empty(B, H, device=dev), torch.empty(B, H, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+              torch.empty(B, device=dev)] + [torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3)]
+        sout = StreamState(*(p(t) for t in st))
+        stail = (V1 - 1, ms, p(tokens), p(times), p(out_len), max_out, None, C.byref(sout), torch.cuda.current_stream().cuda_stream)
+        calls["rnnt_stream"] = lambda: lib.mi355x_rnnt_greedy_decode_stream(*head, *stail)
+        calls["tdt_stream"] = lambda: lib.mi355x_tdt_greedy_decode_stream(*head, D, dur, *stail)
     row = {"lib": os.path.basename(path)}
     for name, fn in calls.items():
         for _ in range(args.warmup):

@@ -314,7 +314,10 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_fwd_kerne
       const float alpha = (m_new == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f((m_run - m_new) * c2);  // m_run = -inf -> 0
       l_run *= alpha;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
+      for (int r = 0; r < 16; ++r) {
+#pragma unroll
+        for (int t = 0; t < NDT; ++t) o[t][r] *= alpha;   // every accumulator tile (four at head width 128)
+      }
       m_run = m_new;
     }
     const float mc = (m_run == -INFINITY) ? 0.f : m_run * c2;

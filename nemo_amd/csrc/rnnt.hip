@@ -17,6 +17,8 @@
 #include "common.h"
 #include "mi355x_asr.h"
 
+#include "transducer_rows.h"
+
 #define RNEG (-INFINITY)
 
 __device__ __forceinline__ float rnnt_lae(float a, float b) {  // log(exp a + exp b), rnnt_helper.log_sum_exp
@@ -35,40 +37,14 @@ __global__ __launch_bounds__(256) void rnnt_denom_kernel(const float* __restrict
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
-  const int u = (int)(row % U1);
-  const long long bt = row / U1;
-  const int t = (int)(bt % T);
-  const int b = (int)(bt / T);
-  const int Tb = (int)min((long long)T, xlen[b]), Ub = (int)min((long long)(U1 - 1), ylen[b]) + 1;
-  if (t >= Tb || u >= Ub) return;  // never read
+  const TrCell c = tr_cell(row, T, U1, xlen, ylen);
+  if (c.padded()) return;  // never read
   const float* x = acts + row * ld;
-  // a row starts on a 4-byte boundary only (V1 = 1025 is the common case): up to 3 head scalars bring the walk to a 16-byte
-  // boundary, then float4 loads, then up to 3 tail scalars
-  const int head = min(V1, (int)((4u - (unsigned)(((unsigned long long)x >> 2) & 3u)) & 3u));
-  const int n4 = (V1 - head) >> 2;
-  const int tail0 = head + 4 * n4, ntail = V1 - tail0;
-  const float4* x4 = reinterpret_cast<const float4*>(x + head);
-  float m = RNEG;
-  if (lane < head) m = x[lane];
-  if (lane < ntail) m = fmaxf(m, x[tail0 + lane]);
-  for (int i = lane; i < n4; i += 64) {
-    const float4 v = x4[i];
-    m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
-  }
-  m = wave_max(m);
-  float s = 0.f;
-  if (lane < head) s = __expf(x[lane] - m);
-  if (lane < ntail) s += __expf(x[tail0 + lane] - m);
-  for (int i = lane; i < n4; i += 64) {  // second pass hits L2 / the TA cache: the row is a few KiB
-    const float4 v = x4[i];
-    s += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
-  }
-  s = wave_sum(s);
+  const float d = tr_neg_lse(x, tr_walk(x, V1, 1), lane);
   if (lane == 0) {
-    const float d = -(m + logf(s));
     denom[row] = d;
     lpb[row] = d + x[blank];
-    lpl[row] = (u < Ub - 1) ? d + x[labels[(long long)b * (U1 - 1) + u]] : RNEG;
+    lpl[row] = (c.u < c.Ub - 1) ? d + x[labels[(long long)c.b * (U1 - 1) + c.u]] : RNEG;
   }
 }
 
@@ -155,15 +131,6 @@ __global__ void rnnt_lattice_kernel(const float* __restrict__ lpb, const float* 
 // ---- kernel 3: one wave per (b,t,u) row, 4 rows per workgroup.  TG = float: the dense [rows, V1] gradient of the loss module's
 // contract (ldg = V1).  TG = bf16: the gradient as the K-contiguous operand of the joint's backward GEMMs, row pitch ldg
 // (a multiple of 8, columns [V1, ldg) zero) -- no f32 gradient tensor and no cast pass in the fused joint + loss path.
-__device__ __forceinline__ void rnnt_store4(float* p, float a, float b, float c, float d) {
-  *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
-}
-__device__ __forceinline__ void rnnt_store4(bf16_t* p, float a, float b, float c, float d) {
-  const float v[4] = {a, b, c, d};
-  st4(p, v);
-}
-__device__ __forceinline__ void rnnt_store1(float* p, float a) { *p = a; }
-__device__ __forceinline__ void rnnt_store1(bf16_t* p, float a) { st(p, a); }
 template <typename TG>
 __global__ __launch_bounds__(256) void rnnt_grad_kernel(const float* __restrict__ acts, const long long* __restrict__ labels,
                                                         const long long* __restrict__ xlen, const long long* __restrict__ ylen,
@@ -175,23 +142,16 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(const float* __restrict_
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
-  const int u = (int)(row % U1);
-  const long long bt = row / U1;
-  const int t = (int)(bt % T);
-  const int b = (int)(bt / T);
-  const int Tb = (int)min((long long)T, xlen[b]), Ub = (int)min((long long)(U1 - 1), ylen[b]) + 1;
+  const TrCell c = tr_cell(row, T, U1, xlen, ylen);
+  const int b = c.b, t = c.t, u = c.u, Tb = c.Tb, Ub = c.Ub;
   TG* g = grads + row * ldg;
   const float* x = acts + row * ld;
-  for (int i = V1 + lane; i < ldg; i += 64) rnnt_store1(g + i, 0.f);  // pad columns of a pitched operand row
-  // same head / float4 body / tail walk as the denominator kernel; rows of acts and grads share their alignment when the two
-  // base pointers do (checked by the host entry: otherwise `same_align` is 0 and the walk is scalar)
-  const int head = same_align ? min(V1, (int)((4u - (unsigned)(((unsigned long long)x >> 2) & 3u)) & 3u)) : V1;
-  const int n4 = (V1 - head) >> 2;
-  const int tail0 = head + 4 * n4, ntail = V1 - tail0;
-  if (t >= Tb || u >= Ub) {  // padded cell: zero gradient (the reference starts from a zero-filled tensor)
-    for (int i = lane; i < head; i += 64) rnnt_store1(g + i, 0.f);
-    if (lane < ntail) rnnt_store1(g + tail0 + lane, 0.f);
-    for (int i = lane; i < n4; i += 64) rnnt_store4(g + head + 4 * i, 0.f, 0.f, 0.f, 0.f);
+  tr_zero_pad(g, V1, ldg, lane);  // pad columns of a pitched operand row
+  // same walk as the denominator kernel; rows of acts and grads share their alignment when the two base pointers do (checked
+  // by the host entry: otherwise `same_align` is 0 and the walk is scalar)
+  const TrWalk w = tr_walk(x, V1, same_align);
+  if (c.padded()) {  // padded cell: zero gradient (the reference starts from a zero-filled tensor)
+    tr_zero_row(g, w, lane);
     return;
   }
   const float dn = denom[row], a = alphas[row], be = betas[row], logll = ll[b];
@@ -215,27 +175,13 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(const float* __restrict_
     if (clamp > 0.f) gr = fminf(fmaxf(gr, -clamp), clamp);
     return gr * scale;
   };
-  for (int i = lane; i < head; i += 64) rnnt_store1(g + i, one(i, x[i]));
-  if (lane < ntail) rnnt_store1(g + tail0 + lane, one(tail0 + lane, x[tail0 + lane]));
-  const float4* x4 = reinterpret_cast<const float4*>(x + head);
-  for (int i = lane; i < n4; i += 64) {
-    const float4 v = x4[i];
-    const int e = head + 4 * i;
-    rnnt_store4(g + e, one(e, v.x), one(e + 1, v.y), one(e + 2, v.z), one(e + 3, v.w));
-  }
+  tr_map_row(g, x, w, lane, one);
 }
 
-__global__ void rnnt_cost_kernel(const float* __restrict__ ll, float* __restrict__ costs, int B, float fastemit_lambda) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) costs[b] = -ll[b] * (1.f + fastemit_lambda);  // rnnt_helper.compute_costs_data
-}
-
-static long long rnnt_ws_elems(int B, int T, int U1) {
-  return 5LL * B * T * U1 + 2LL * B;  // denom, lp_blank, lp_label, alphas, betas + forward / backward log-likelihoods
-}
+#define RNNT_WS_PER_ROW 5  // denom, lp_blank, lp_label, alphas, betas
 extern "C" int mi355x_rnnt_workspace_elems(int B, int T, int U1, long long* elems) {
   if (!elems || B <= 0 || T <= 0 || U1 <= 0) return MI_ERR_ARG;
-  *elems = rnnt_ws_elems(B, T, U1);
+  *elems = tr_ws_elems(RNNT_WS_PER_ROW, B, T, U1);
   return 0;
 }
 
@@ -247,43 +193,31 @@ static int rnnt_loss_impl(const void* acts, long long ld, const void* labels_, c
   const long long* labels = (const long long*)labels_;
   const long long* act_lens = (const long long*)act_lens_;
   const long long* label_lens = (const long long*)label_lens_;
-  float* costs = (float*)costs_;
-  float* workspace = (float*)workspace_;
-  if (!acts || (!labels && U1 > 1) || !act_lens || !label_lens || !costs || !workspace) return MI_ERR_ARG;
-  if (B <= 0 || T <= 0 || U1 <= 0 || V1 <= 1 || blank < 0 || blank >= V1 || U1 > 1024) return MI_ERR_ARG;
-  if (ld < V1 || (grads_ && ldg < V1)) return MI_ERR_ARG;
-  if (grads_ && grads_dtype == MI_DT_BF16 && ((ldg & 7) || ((uintptr_t)grads_ & 15))) return MI_ERR_ARG;
-  if (workspace_elems < rnnt_ws_elems(B, T, U1)) return MI_ERR_ARG;
+  if (tr_check_args(acts, ld, labels, act_lens, label_lens, B, T, U1, V1, V1, blank, costs_, grads_, grads_dtype, ldg, workspace_,
+                    workspace_elems, RNNT_WS_PER_ROW))
+    return MI_ERR_ARG;
   if (clamp < 0.f || fastemit_lambda < 0.f) return MI_ERR_ARG;
-  const long long rows = (long long)B * T * U1;
-  if ((rows + 3) / 4 > 0x7fffffffLL) return MI_ERR_ARG;
-  float* denom = workspace;
+  const TrGeom q = tr_geom(B, T, U1);
+  const long long rows = q.rows;
+  float* denom = (float*)workspace_;
   float* lpb = denom + rows;
   float* lpl = lpb + rows;
   float* alphas = lpl + rows;
   float* betas = alphas + rows;
   float* ll = betas + rows;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nblk = (unsigned)((rows + 3) / 4);
-  MI_LAUNCH(rnnt_denom_kernel, dim3(nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens, denom,
-                     lpb, lpl, rows, T, U1, V1, blank, ld);
-  const int threads = ((U1 + 63) / 64) * 64;
-  MI_LAUNCH(rnnt_lattice_kernel, dim3(B, 2), dim3(threads), 2 * threads * sizeof(float), s, lpb, lpl, act_lens,
-                     label_lens, alphas, betas, ll, B, T, U1);
-  if (grads_ && grads_dtype == MI_DT_BF16) {
-    // vector walk when every logit row starts on a 16-byte boundary (then head = 0 and the 4-element groups of the bf16 row
-    // are 8-byte aligned as well)
-    const int aligned = (((unsigned long long)acts & 15ull) == 0ull && (ld & 3) == 0) ? 1 : 0;
-    MI_LAUNCH((rnnt_grad_kernel<bf16_t>), dim3(nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens,
-                       denom, alphas, betas, ll, (bf16_t*)grads_, rows, T, U1, V1, blank, fastemit_lambda, clamp, grad_scale,
-                       aligned, ld, ldg);
-  } else if (grads_) {
-    const int same = ((((unsigned long long)acts ^ (unsigned long long)grads_) & 15ull) == 0ull && ((ld - ldg) & 3) == 0) ? 1 : 0;
-    MI_LAUNCH((rnnt_grad_kernel<float>), dim3(nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens,
-                       denom, alphas, betas, ll, (float*)grads_, rows, T, U1, V1, blank, fastemit_lambda, clamp, grad_scale, same,
-                       ld, ldg);
-  }
-  MI_LAUNCH(rnnt_cost_kernel, dim3((B + 63) / 64), dim3(64), 0, s, ll, costs, B, fastemit_lambda);
+  MI_LAUNCH(rnnt_denom_kernel, dim3(q.nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens, denom, lpb, lpl,
+            rows, T, U1, V1, blank, ld);
+  MI_LAUNCH(rnnt_lattice_kernel, dim3(B, 2), dim3(q.threads), 2 * q.threads * sizeof(float), s, lpb, lpl, act_lens, label_lens,
+            alphas, betas, ll, B, T, U1);
+  const int vec = tr_vector_walk(acts, ld, grads_, grads_dtype, ldg);
+  auto grad = [&](auto* g) {
+    MI_LAUNCH(rnnt_grad_kernel, dim3(q.nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens, denom, alphas,
+              betas, ll, g, rows, T, U1, V1, blank, fastemit_lambda, clamp, grad_scale, vec, ld, ldg);
+  };
+  if (grads_ && grads_dtype == MI_DT_BF16) grad((bf16_t*)grads_);
+  else if (grads_) grad((float*)grads_);
+  MI_LAUNCH(tr_cost_kernel, dim3((B + 63) / 64), dim3(64), 0, s, ll, (float*)costs_, B, 1.f + fastemit_lambda);
   return mi_check_launch();
 }
 
@@ -298,7 +232,6 @@ extern "C" int mi355x_rnnt_loss_ex(const void* acts, long long ld_acts, const vo
                                    const void* label_lens, int B, int T, int U1, int V1, int blank, float fastemit_lambda,
                                    float clamp, float grad_scale, void* costs, void* grads, int grads_dtype, long long ld_grads,
                                    void* workspace, long long workspace_elems, void* stream) {
-  if (grads_dtype != MI_DT_F32 && grads_dtype != MI_DT_BF16) return MI_ERR_ARG;
   return rnnt_loss_impl(acts, ld_acts, labels, act_lens, label_lens, B, T, U1, V1, blank, fastemit_lambda, clamp, grad_scale, costs,
                         grads, grads_dtype, ld_grads, workspace, workspace_elems, stream);
 }

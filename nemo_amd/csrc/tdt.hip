@@ -5,7 +5,7 @@
 //   under-normalisation.  Arcs out of cell (t,u): blank with duration d_i >= 1 to (t+d_i, u), weight lp(blank) + dp(i) - sigma;
 //   label y_{u+1} with any duration to (t+d_i, u+1), weight lp(y_{u+1}) + dp(i) - sigma.  A path ends with a blank arc that
 //   lands exactly on (T_b, U_b).
-//   kernel 1  tdt_row:      per (b,t,u) row (one wave, the head / float4 / tail walk of rnnt_denom): both log-softmax
+//   kernel 1  tdt_row:      per (b,t,u) row (one wave, the row walk of transducer_rows.h as in rnnt_denom): both log-softmax
 //                           denominators and the 2D arc weights wb_i / wl_i with sigma folded in -- the lattice never reads the
 //                           logits
 //   kernel 2  tdt_lattice:  alpha (blockIdx.y = 0) and beta (= 1), one workgroup per utterance, thread = u, anti-diagonal sweep
@@ -24,6 +24,7 @@
 #include "mi355x_asr.h"
 
 #include "tdt.h"
+#include "transducer_rows.h"
 
 #define TNEG (-INFINITY)
 
@@ -50,39 +51,16 @@ __global__ __launch_bounds__(256) void tdt_row_kernel(const float* __restrict__ 
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
-  const int u = (int)(row % U1);
-  const long long bt = row / U1;
-  const int t = (int)(bt % T);
-  const int b = (int)(bt / T);
-  const int Tb = (int)min((long long)T, xlen[b]), Ub = (int)min((long long)(U1 - 1), ylen[b]) + 1;
-  if (t >= Tb || u >= Ub) return;  // never read
+  const TrCell c = tr_cell(row, T, U1, xlen, ylen);
+  if (c.padded()) return;  // never read
   const int D = dur.D;
   const float* x = acts + row * ld;
-  const int head = min(V1, (int)((4u - (unsigned)(((unsigned long long)x >> 2) & 3u)) & 3u));
-  const int n4 = (V1 - head) >> 2;
-  const int tail0 = head + 4 * n4, ntail = V1 - tail0;
-  const float4* x4 = reinterpret_cast<const float4*>(x + head);
-  float m = TNEG;
-  if (lane < head) m = x[lane];
-  if (lane < ntail) m = fmaxf(m, x[tail0 + lane]);
-  for (int i = lane; i < n4; i += 64) {
-    const float4 v = x4[i];
-    m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
-  }
-  m = wave_max(m);
-  float s = 0.f;
-  if (lane < head) s = __expf(x[lane] - m);
-  if (lane < ntail) s += __expf(x[tail0 + lane] - m);
-  for (int i = lane; i < n4; i += 64) {
-    const float4 v = x4[i];
-    s += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
-  }
-  s = wave_sum(s);
+  const float dn = tr_neg_lse(x, tr_walk(x, V1, 1), lane);
   // duration softmax: lane i < D holds z_{V1+i}
   const float zd = lane < D ? x[V1 + lane] : TNEG;
   const float md = wave_max(zd);
   const float sd = wave_sum(lane < D ? __expf(zd - md) : 0.f);
-  const float dn = -(m + logf(s)), ddn = -(md + logf(sd));
+  const float ddn = -(md + logf(sd));
   if (lane == 0) { denom[row] = dn; ddenom[row] = ddn; }
   if (lane < D) {
     int di = 0;
@@ -90,7 +68,7 @@ __global__ __launch_bounds__(256) void tdt_row_kernel(const float* __restrict__ 
     for (int j = 0; j < TDT_MAXD; ++j) di = (lane == j) ? dur.d[j] : di;
     const float dp = zd + ddn - sigma;
     wb[row * D + lane] = di >= 1 ? dn + x[blank] + dp : TNEG;
-    wl[row * D + lane] = (u < Ub - 1) ? dn + x[labels[(long long)b * (U1 - 1) + u]] + dp : TNEG;
+    wl[row * D + lane] = (c.u < c.Ub - 1) ? dn + x[labels[(long long)c.b * (U1 - 1) + c.u]] + dp : TNEG;
   }
 }
 
@@ -212,15 +190,6 @@ __global__ void tdt_lattice_kernel(const float* __restrict__ wb, const float* __
 
 // ---- kernel 3: one wave per (b,t,u) row, 4 rows per workgroup.  TG = float: dense gradient rows of pitch ldg >= V1 + D;
 // TG = bf16: the K-contiguous operand of the joint's backward GEMMs (ldg % 8 == 0, columns [V1 + D, ldg) zero).
-__device__ __forceinline__ void tdt_store4(float* p, float a, float b, float c, float d) {
-  *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
-}
-__device__ __forceinline__ void tdt_store4(bf16_t* p, float a, float b, float c, float d) {
-  const float v[4] = {a, b, c, d};
-  st4(p, v);
-}
-__device__ __forceinline__ void tdt_store1(float* p, float a) { *p = a; }
-__device__ __forceinline__ void tdt_store1(bf16_t* p, float a) { st(p, a); }
 template <typename TG>
 __global__ __launch_bounds__(256) void tdt_grad_kernel(const float* __restrict__ acts, const long long* __restrict__ labels,
                                                        const long long* __restrict__ xlen, const long long* __restrict__ ylen,
@@ -233,23 +202,16 @@ __global__ __launch_bounds__(256) void tdt_grad_kernel(const float* __restrict__
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
-  const int u = (int)(row % U1);
-  const long long bt = row / U1;
-  const int t = (int)(bt % T);
-  const int b = (int)(bt / T);
+  const TrCell c = tr_cell(row, T, U1, xlen, ylen);
+  const int b = c.b, t = c.t, u = c.u, Tb = c.Tb, Ub = c.Ub;
   const int D = dur.D;
-  const int Tb = (int)min((long long)T, xlen[b]), Ub = (int)min((long long)(U1 - 1), ylen[b]) + 1;
   TG* g = grads + row * ldg;
   const float* x = acts + row * ld;
-  for (int i = V1 + D + lane; i < ldg; i += 64) tdt_store1(g + i, 0.f);  // pad columns of a pitched operand row
-  const int head = same_align ? min(V1, (int)((4u - (unsigned)(((unsigned long long)x >> 2) & 3u)) & 3u)) : V1;
-  const int n4 = (V1 - head) >> 2;
-  const int tail0 = head + 4 * n4, ntail = V1 - tail0;
-  if (t >= Tb || u >= Ub) {  // padded cell: zero gradient
-    for (int i = lane; i < head; i += 64) tdt_store1(g + i, 0.f);
-    if (lane < ntail) tdt_store1(g + tail0 + lane, 0.f);
-    for (int i = lane; i < n4; i += 64) tdt_store4(g + head + 4 * i, 0.f, 0.f, 0.f, 0.f);
-    if (lane < D) tdt_store1(g + V1 + lane, 0.f);
+  tr_zero_pad(g, V1 + D, ldg, lane);  // pad columns of a pitched operand row
+  const TrWalk w = tr_walk(x, V1, same_align);
+  if (c.padded()) {  // padded cell: zero gradient
+    tr_zero_row(g, w, lane);
+    if (lane < D) st(g + V1 + lane, 0.f);
     return;
   }
   const float dn = denom[row], a = alphas[row], be = betas[row], logll = ll[b];
@@ -272,8 +234,7 @@ __global__ __launch_bounds__(256) void tdt_grad_kernel(const float* __restrict__
   }
   const float post_blank = wave_sum(pbk), post_label = wave_sum(plk);
   const float occ = __expf(a + be - logll);
-  if (lane < D)
-    tdt_store1(g + V1 + lane, (__expf(x[V1 + lane] + ddenom[row]) * occ - (pbk + plk)) * scale);
+  if (lane < D) st(g + V1 + lane, (__expf(x[V1 + lane] + ddenom[row]) * occ - (pbk + plk)) * scale);
   const float common = a + be + dn - logll;  // softmax_v * occ = exp(common + x_v)
   auto one = [&](int v, float xv) -> float {
     float gr = __expf(common + xv);
@@ -281,28 +242,13 @@ __global__ __launch_bounds__(256) void tdt_grad_kernel(const float* __restrict__
     if (v == lab) gr -= post_label;
     return gr * scale;
   };
-  for (int i = lane; i < head; i += 64) tdt_store1(g + i, one(i, x[i]));
-  if (lane < ntail) tdt_store1(g + tail0 + lane, one(tail0 + lane, x[tail0 + lane]));
-  const float4* x4 = reinterpret_cast<const float4*>(x + head);
-  for (int i = lane; i < n4; i += 64) {
-    const float4 v = x4[i];
-    const int e = head + 4 * i;
-    tdt_store4(g + e, one(e, v.x), one(e + 1, v.y), one(e + 2, v.z), one(e + 3, v.w));
-  }
+  tr_map_row(g, x, w, lane, one);
 }
 
-__global__ void tdt_cost_kernel(const float* __restrict__ ll, float* __restrict__ costs, int B) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) costs[b] = -ll[b];
-}
-
-static long long tdt_ws_elems(int B, int T, int U1, int D) {
-  // denom, ddenom, alphas, betas; wb, wl (D each per row); forward / backward log-likelihoods
-  return (4LL + 2LL * D) * B * T * U1 + 2LL * B;
-}
+static int tdt_ws_per_row(int D) { return 4 + 2 * D; }  // denom, ddenom, alphas, betas; wb, wl (D each)
 extern "C" int mi355x_tdt_workspace_elems(int B, int T, int U1, int D, long long* elems) {
   if (!elems || B <= 0 || T <= 0 || U1 <= 0 || D < 2 || D > TDT_MAXD) return MI_ERR_ARG;
-  *elems = tdt_ws_elems(B, T, U1, D);
+  *elems = tr_ws_elems(tdt_ws_per_row(D), B, T, U1);
   return 0;
 }
 
@@ -314,20 +260,15 @@ extern "C" int mi355x_tdt_loss_ex(const void* acts, long long ld, const void* la
   const long long* labels = (const long long*)labels_;
   const long long* act_lens = (const long long*)act_lens_;
   const long long* label_lens = (const long long*)label_lens_;
-  float* costs = (float*)costs_;
-  float* workspace = (float*)workspace_;
   TdtDur dur;
   if (tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
-  if (grads_dtype != MI_DT_F32 && grads_dtype != MI_DT_BF16) return MI_ERR_ARG;
-  if (!acts || (!labels && U1 > 1) || !act_lens || !label_lens || !costs || !workspace) return MI_ERR_ARG;
-  if (B <= 0 || T <= 0 || U1 <= 0 || V1 <= 1 || blank < 0 || blank >= V1 || U1 > 1024) return MI_ERR_ARG;
+  if (tr_check_args(acts, ld, labels, act_lens, label_lens, B, T, U1, V1, V1 + D, blank, costs_, grads_, grads_dtype, ldg,
+                    workspace_, workspace_elems, tdt_ws_per_row(D)))
+    return MI_ERR_ARG;
   if (!(sigma >= 0.f) || !(grad_scale == grad_scale)) return MI_ERR_ARG;
-  if (ld < V1 + D || (grads_ && ldg < V1 + D)) return MI_ERR_ARG;
-  if (grads_ && grads_dtype == MI_DT_BF16 && ((ldg & 7) || ((uintptr_t)grads_ & 15))) return MI_ERR_ARG;
-  if (workspace_elems < tdt_ws_elems(B, T, U1, D)) return MI_ERR_ARG;
-  const long long rows = (long long)B * T * U1;
-  if ((rows + 3) / 4 > 0x7fffffffLL) return MI_ERR_ARG;
-  float* denom = workspace;
+  const TrGeom q = tr_geom(B, T, U1);
+  const long long rows = q.rows;
+  float* denom = (float*)workspace_;
   float* ddenom = denom + rows;
   float* alphas = ddenom + rows;
   float* betas = alphas + rows;
@@ -335,22 +276,18 @@ extern "C" int mi355x_tdt_loss_ex(const void* acts, long long ld, const void* la
   float* wl = wb + rows * D;
   float* ll = wl + rows * D;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nblk = (unsigned)((rows + 3) / 4);
-  MI_LAUNCH(tdt_row_kernel, dim3(nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens, denom, ddenom, wb, wl,
-            rows, T, U1, V1, dur, blank, sigma, ld);
-  const int threads = ((U1 + 63) / 64) * 64;
+  MI_LAUNCH(tdt_row_kernel, dim3(q.nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens, denom, ddenom, wb,
+            wl, rows, T, U1, V1, dur, blank, sigma, ld);
   const int R = dur.d[D - 1] + 2;
-  MI_LAUNCH(tdt_lattice_kernel, dim3(B, 2), dim3(threads), (size_t)R * threads * sizeof(float), s, wb, wl, act_lens, label_lens,
-            alphas, betas, ll, B, T, U1, dur, R);
-  if (grads_ && grads_dtype == MI_DT_BF16) {
-    const int aligned = (((unsigned long long)acts & 15ull) == 0ull && (ld & 3) == 0) ? 1 : 0;
-    MI_LAUNCH((tdt_grad_kernel<bf16_t>), dim3(nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens, denom,
-              ddenom, wb, wl, alphas, betas, ll, (bf16_t*)grads_, rows, T, U1, V1, dur, blank, grad_scale, aligned, ld, ldg);
-  } else if (grads_) {
-    const int same = ((((unsigned long long)acts ^ (unsigned long long)grads_) & 15ull) == 0ull && ((ld - ldg) & 3) == 0) ? 1 : 0;
-    MI_LAUNCH((tdt_grad_kernel<float>), dim3(nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens, denom,
-              ddenom, wb, wl, alphas, betas, ll, (float*)grads_, rows, T, U1, V1, dur, blank, grad_scale, same, ld, ldg);
-  }
-  MI_LAUNCH(tdt_cost_kernel, dim3((B + 63) / 64), dim3(64), 0, s, ll, costs, B);
+  MI_LAUNCH(tdt_lattice_kernel, dim3(B, 2), dim3(q.threads), (size_t)R * q.threads * sizeof(float), s, wb, wl, act_lens,
+            label_lens, alphas, betas, ll, B, T, U1, dur, R);
+  const int vec = tr_vector_walk(acts, ld, grads_, grads_dtype, ldg);
+  auto grad = [&](auto* g) {
+    MI_LAUNCH(tdt_grad_kernel, dim3(q.nblk), dim3(256), 0, s, (const float*)acts, labels, act_lens, label_lens, denom, ddenom, wb,
+              wl, alphas, betas, ll, g, rows, T, U1, V1, dur, blank, grad_scale, vec, ld, ldg);
+  };
+  if (grads_ && grads_dtype == MI_DT_BF16) grad((bf16_t*)grads_);
+  else if (grads_) grad((float*)grads_);
+  MI_LAUNCH(tr_cost_kernel, dim3((B + 63) / 64), dim3(64), 0, s, ll, (float*)costs_, B, 1.f);
   return mi_check_launch();
 }

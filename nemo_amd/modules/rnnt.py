@@ -596,14 +596,19 @@ class RNNTJoint(_ModuleBase):
         # the label logits (duration gradients zero); the label logits are the first V+1 columns of the pitched rows either way
         tdt = isinstance(loss_mod, TDTLoss)
         tdt_as_rnnt = tdt and draw_rnnt_call(loss_mod.omega)
-        Vl = self._vocab_size + 1   # label logits (= the whole row without TDT)
+        V1 = self._num_classes      # the whole row
+        Vl = self._vocab_size + 1 if tdt else V1   # label logits
 
-        def pitched_loss(logits, ld, nb, Ts, Us, lab, el_, tl_, grads, ldg, gscale):
+        fe = float(getattr(loss_mod, "fastemit_lambda", 0.0) or 0.0)   # (a TDTLoss holds 0.0 for both)
+        cl = float(getattr(loss_mod, "clamp", 0.0) or 0.0)
+
+        def pitched_loss(logits, ld, nb, Ts, Us, lab, el_, tl_, grads, gscale):
+            """the loss of one sub-batch: logits and `grads` (None: loss only) in rows of pitch ld"""
             if tdt and not tdt_as_rnnt:
                 return ops.tdt_loss_pitched(logits, ld, nb, Ts, Us, Vl, loss_mod.durations, lab, el_, tl_, self._vocab_size,
-                                            grads=grads, ld_grads=ldg, sigma=loss_mod.sigma, grad_scale=gscale)
-            return ops.rnnt_loss_pitched(logits, ld, nb, Ts, Us, Vl, lab, el_, tl_, self._vocab_size, grads, ldg,
-                                         grad_scale=gscale)
+                                            grads=grads, ld_grads=ld, sigma=loss_mod.sigma, grad_scale=gscale)
+            return ops.rnnt_loss_pitched(logits, ld, nb, Ts, Us, Vl, lab, el_, tl_, self._vocab_size, grads, ld,
+                                         fastemit_lambda=fe, clamp=cl, grad_scale=gscale)
 
         xe, xd, f, g = self._project(enc, dec, W, cdt)
         df = torch.empty(B * T, J, dtype=cdt, device=dev) if need_grad else None
@@ -631,8 +636,6 @@ class RNNTJoint(_ModuleBase):
         for si, b0 in enumerate(range(0, B, fbs)):
             nb = min(fbs, B - b0)
             drop = self._drop(si)
-            fe = float(getattr(loss_mod, "fastemit_lambda", 0.0) or 0.0)
-            cl = float(getattr(loss_mod, "clamp", 0.0) or 0.0)
             Ts, Us = cuts[si] if cuts is not None else (T, U1)
             cut = (Ts, Us) != (T, U1)
             if cut:  # dense copies of the sub-batch's [nb, Ts, J] / [nb, Us, J] corners (small next to the [nb, Ts, Us, V+1] logits)
@@ -645,40 +648,23 @@ class RNNTJoint(_ModuleBase):
             sub_bwd_kw = dict(df_rows=dfs, dg_pitch=U1) if cut else {}
             if not need_grad:
                 h, logits = self._sub_fwd(fs, gs, fb0, nb, Ts, Us, W, cdt, drop)
-                if tdt:
-                    V1 = self._num_classes
-                    costs[b0:b0 + nb] = pitched_loss(logits, V1, nb, Ts, Us, lab, el[b0:b0 + nb], tl[b0:b0 + nb], None, V1, scale)
-                else:
-                    costs[b0:b0 + nb] = ops.rnnt_loss(logits, lab, el[b0:b0 + nb], tl[b0:b0 + nb], self._vocab_size,
-                                                      fastemit_lambda=fe, clamp=cl, grad_scale=scale)
+                costs[b0:b0 + nb] = pitched_loss(logits, V1, nb, Ts, Us, lab, el[b0:b0 + nb], tl[b0:b0 + nb], None, scale)
                 del h, logits
                 continue
             if cdt == torch.bfloat16:
                 # logits with row pitch roundup8(V+1) (vector stores from the GEMM); the loss kernel writes the logit gradient
                 # directly as the bf16 operand of the backward GEMMs: the f32 gradient tensor and its cast pass do not exist
-                V1 = self._num_classes
                 V1p = _pad8(V1)
                 h, logits = self._sub_fwd(fs, gs, fb0, nb, Ts, Us, W, cdt, drop, ld=V1p)
                 dlog = torch.empty(nb * Ts * Us, V1p, dtype=cdt, device=dev)
                 gscale = scale / self.temperature if self.temperature != 1.0 else scale
-                if tdt:
-                    c = pitched_loss(logits, V1p, nb, Ts, Us, lab, el[b0:b0 + nb], tl[b0:b0 + nb], dlog, V1p, gscale)
-                else:
-                    c = ops.rnnt_loss_pitched(logits, V1p, nb, Ts, Us, V1, lab, el[b0:b0 + nb], tl[b0:b0 + nb],
-                                              self._vocab_size, dlog, V1p, fastemit_lambda=fe, clamp=cl, grad_scale=gscale)
-                costs[b0:b0 + nb] = c
+                costs[b0:b0 + nb] = pitched_loss(logits, V1p, nb, Ts, Us, lab, el[b0:b0 + nb], tl[b0:b0 + nb], dlog, gscale)
                 self._sub_bwd(None, h, b0, nb, Ts, Us, W, cdt, drop, df, dg32, gview(out.weight), gview(out.bias), dlog=dlog,
                               **sub_bwd_kw)
             else:
                 h, logits = self._sub_fwd(fs, gs, fb0, nb, Ts, Us, W, cdt, drop)
                 grads = torch.empty_like(logits)
-                if tdt:
-                    V1 = self._num_classes
-                    c = pitched_loss(logits, V1, nb, Ts, Us, lab, el[b0:b0 + nb], tl[b0:b0 + nb], grads, V1, scale)
-                else:
-                    c = ops.rnnt_loss(logits, lab, el[b0:b0 + nb], tl[b0:b0 + nb], self._vocab_size, grads=grads,
-                                      fastemit_lambda=fe, clamp=cl, grad_scale=scale)
-                costs[b0:b0 + nb] = c
+                costs[b0:b0 + nb] = pitched_loss(logits, V1, nb, Ts, Us, lab, el[b0:b0 + nb], tl[b0:b0 + nb], grads, scale)
                 self._sub_bwd(grads, h, b0, nb, Ts, Us, W, cdt, drop, df, dg32, gview(out.weight), gview(out.bias), **sub_bwd_kw)
                 del grads
             if cut:

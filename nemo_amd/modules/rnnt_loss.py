@@ -38,17 +38,17 @@ def certify_inputs(log_probs, labels, lengths, label_lengths):
         raise ValueError(f"Output length mismatch! Given U: {U}, Expected max U from target lengths: {max_U} + 1")
 
 
-class _RNNTLossFn(torch.autograd.Function):
+class _TransducerLossFn(torch.autograd.Function):
+    """The autograd function of RNNTLoss and TDTLoss.  `kernels(acts, labels, act_lens, label_lens, grads, grad_scale)` runs the
+    loss kernels: it returns the costs [B] and fills `grads` (f32, the shape of acts; None when no gradient is wanted)."""
+
     @staticmethod
-    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction, fastemit_lambda, clamp):
+    def forward(ctx, acts, labels, act_lens, label_lens, reduction, kernels):
         certify_inputs(acts, labels, act_lens, label_lens)
-        if clamp < 0:
-            raise ValueError("`clamp` must be 0.0 or positive float value.")
         B = acts.size(0)
         grads = torch.empty_like(acts, dtype=torch.float32) if acts.requires_grad else None
         scale = 1.0 / B if reduction == "mean" else 1.0  # rnnt_pytorch.py:77-80, folded into the gradient kernel
-        costs = ops.rnnt_loss(acts, labels, act_lens, label_lens, blank, grads=grads, fastemit_lambda=fastemit_lambda,
-                              clamp=clamp, grad_scale=scale)
+        costs = kernels(acts, labels, act_lens, label_lens, grads, scale)
         if reduction in ("sum", "mean"):
             costs = costs.sum().unsqueeze_(-1)
             if reduction == "mean":
@@ -60,8 +60,18 @@ class _RNNTLossFn(torch.autograd.Function):
     def backward(ctx, grad_output):
         (grads,) = ctx.saved_tensors
         if grad_output is not None and grads is not None:
-            return grads.mul_(grad_output.view(-1, 1, 1, 1).to(grads)), None, None, None, None, None, None, None
-        return (None,) * 8
+            return (grads.mul_(grad_output.view(-1, 1, 1, 1).to(grads)),) + (None,) * 5
+        return (None,) * 6
+
+
+def prepare_inputs(name, acts, labels, act_lens, label_lens):
+    """what a loss module's forward does to its inputs: CUDA only, fp32 logits (rnnt_pytorch.py:419-423: the numba loss computes
+    in fp32), everything contiguous"""
+    if not acts.is_cuda:
+        raise RuntimeError(f"nemo_amd {name} runs on MI355X only (there is no CPU fallback)")
+    if acts.dtype != torch.float32:
+        acts = acts.float()
+    return acts.contiguous(), labels.contiguous(), act_lens.contiguous(), label_lens.contiguous()
 
 
 class RNNTLoss(nn.Module):
@@ -76,13 +86,13 @@ class RNNTLoss(nn.Module):
 
     def forward(self, acts, labels, act_lens, label_lens):
         """acts (batch x seqLength x labelLength x outputDim) logits; labels zero-padded [B, U]; lens [B]"""
-        if not acts.is_cuda:
-            raise RuntimeError("nemo_amd RNNTLoss runs on MI355X only (there is no CPU fallback)")
-        if acts.dtype != torch.float32:  # rnnt_pytorch.py:419-423: the numba loss computes in fp32
-            acts = acts.float()
-        acts = acts.contiguous()
-        return _RNNTLossFn.apply(acts, labels.contiguous(), act_lens.contiguous(), label_lens.contiguous(), self.blank,
-                                 self.reduction, self.fastemit_lambda, self.clamp)
+        def kernels(acts, labels, act_lens, label_lens, grads, scale):
+            if self.clamp < 0:
+                raise ValueError("`clamp` must be 0.0 or positive float value.")
+            return ops.rnnt_loss(acts, labels, act_lens, label_lens, self.blank, grads=grads, fastemit_lambda=self.fastemit_lambda,
+                                 clamp=self.clamp, grad_scale=scale)
+
+        return _TransducerLossFn.apply(*prepare_inputs("RNNTLoss", acts, labels, act_lens, label_lens), self.reduction, kernels)
 
 
 RNNTLossNumba = RNNTLoss

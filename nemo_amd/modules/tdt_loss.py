@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from .rnnt_loss import certify_inputs
+from .rnnt_loss import _TransducerLossFn, certify_inputs, prepare_inputs  # noqa: F401  (certify_inputs: a public name here)
 
 
 def check_durations(durations: Sequence[int]) -> list:
@@ -36,37 +36,6 @@ def draw_rnnt_call(omega: float) -> bool:
     if omega >= 1.0:
         return True
     return float(torch.rand(()).item()) < omega
-
-
-class _TDTLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, acts, labels, act_lens, label_lens, blank, durations, reduction, sigma, use_rnnt):
-        certify_inputs(acts, labels, act_lens, label_lens)
-        B, T, U1, W = acts.shape
-        D = len(durations)
-        V1 = W - D
-        grads = torch.empty_like(acts, dtype=torch.float32) if acts.requires_grad else None
-        scale = 1.0 / B if reduction == "mean" else 1.0
-        if use_rnnt:
-            # the RNN-T loss of the label logits: the loss kernels read the [.., :V1] columns of the pitched rows and write the
-            # duration columns of the gradient as zeros (pad columns of a pitched row)
-            costs = ops.rnnt_loss_pitched(acts, W, B, T, U1, V1, labels, act_lens, label_lens, blank, grads, W, grad_scale=scale)
-        else:
-            costs = ops.tdt_loss_pitched(acts, W, B, T, U1, V1, durations, labels, act_lens, label_lens, blank, grads=grads,
-                                         ld_grads=W, sigma=sigma, grad_scale=scale)
-        if reduction in ("sum", "mean"):
-            costs = costs.sum().unsqueeze_(-1)
-            if reduction == "mean":
-                costs /= B
-        ctx.save_for_backward(grads)
-        return costs
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        (grads,) = ctx.saved_tensors
-        if grad_output is not None and grads is not None:
-            return (grads.mul_(grad_output.view(-1, 1, 1, 1).to(grads)),) + (None,) * 8
-        return (None,) * 9
 
 
 class TDTLoss(nn.Module):
@@ -94,13 +63,21 @@ class TDTLoss(nn.Module):
 
     def forward(self, acts, labels, act_lens, label_lens):
         """acts (batch x seqLength x labelLength x (V+1+D)) logits; labels zero-padded [B, U]; lens [B]"""
-        if not acts.is_cuda:
-            raise RuntimeError("nemo_amd TDTLoss runs on MI355X only (there is no CPU fallback)")
-        if acts.dtype != torch.float32:
-            acts = acts.float()
-        acts = acts.contiguous()
-        return _TDTLossFn.apply(acts, labels.contiguous(), act_lens.contiguous(), label_lens.contiguous(), self.blank,
-                                self.durations, self.reduction, self.sigma, draw_rnnt_call(self.omega))
+        inputs = prepare_inputs("TDTLoss", acts, labels, act_lens, label_lens)
+        use_rnnt = draw_rnnt_call(self.omega)
+
+        def kernels(acts, labels, act_lens, label_lens, grads, scale):
+            B, T, U1, W = acts.shape
+            V1 = W - len(self.durations)
+            if use_rnnt:
+                # the RNN-T loss of the label logits: the loss kernels read the [.., :V1] columns of the pitched rows and write the
+                # duration columns of the gradient as zeros (pad columns of a pitched row)
+                return ops.rnnt_loss_pitched(acts, W, B, T, U1, V1, labels, act_lens, label_lens, self.blank, grads, W,
+                                             grad_scale=scale)
+            return ops.tdt_loss_pitched(acts, W, B, T, U1, V1, self.durations, labels, act_lens, label_lens, self.blank,
+                                        grads=grads, ld_grads=W, sigma=self.sigma, grad_scale=scale)
+
+        return _TransducerLossFn.apply(*inputs, self.reduction, kernels)
 
 
 TDTLossNumba = TDTLoss

@@ -715,14 +715,15 @@ def ctc_loss(logp, targets, in_len, tgt_len, blank, grad=None, grad_scale=1.0, z
     return nll
 
 
-def rnnt_loss(acts, labels, act_lens, label_lens, blank, grads=None, fastemit_lambda=0.0, clamp=0.0, grad_scale=1.0):
-    """acts f32 [B,T,U1,V1] logits (contiguous); labels i64 [B,U1-1]; returns costs f32 [B]; fills `grads` if given"""
-    B, T, U1, V1 = acts.shape
-    n = 5 * B * T * U1 + 2 * B
+def _transducer_loss(name, acts, ld_acts, labels, act_lens, label_lens, B, T, U1, V1, params, ws_per_row, grads, ld_grads):
+    """one call of a transducer loss entry (`params`: what the entry takes between V1 and costs): allocates the costs and the
+    workspace of `ws_per_row` floats per lattice cell + 2 per utterance, resolves the gradient's dtype and pitch -> costs f32 [B]"""
+    n = ws_per_row * B * T * U1 + 2 * B
     ws = torch.empty(n, device=acts.device, dtype=torch.float32)
     costs = torch.empty(B, device=acts.device, dtype=torch.float32)
-    check(lib.mi355x_rnnt_loss(_ptr(acts), _ptr(labels), _ptr(act_lens), _ptr(label_lens), B, T, U1, V1, blank,
-                               fastemit_lambda, clamp, grad_scale, _ptr(costs), _ptr(grads), _ptr(ws), n, _stream()), "rnnt_loss")
+    gdt, ldg = (dt(grads), ld_grads) if grads is not None else (F32, 0)
+    check(getattr(lib, "mi355x_" + name)(_ptr(acts), ld_acts, _ptr(labels), _ptr(act_lens), _ptr(label_lens), B, T, U1, V1, *params,
+                                         _ptr(costs), _ptr(grads), gdt, ldg, _ptr(ws), n, _stream()), name)
     return costs
 
 
@@ -730,14 +731,15 @@ def rnnt_loss_pitched(acts, ld_acts, B, T, U1, V1, labels, act_lens, label_lens,
                       clamp=0.0, grad_scale=1.0):
     """acts f32, rows of pitch ld_acts; grads (f32 or bf16, or None: loss only) rows of pitch ld_grads, pad columns zero-filled
     -> costs f32 [B]"""
-    n = 5 * B * T * U1 + 2 * B
-    ws = torch.empty(n, device=acts.device, dtype=torch.float32)
-    costs = torch.empty(B, device=acts.device, dtype=torch.float32)
-    check(lib.mi355x_rnnt_loss_ex(_ptr(acts), ld_acts, _ptr(labels), _ptr(act_lens), _ptr(label_lens), B, T, U1, V1, blank,
-                                  fastemit_lambda, clamp, grad_scale, _ptr(costs), _ptr(grads), dt(grads) if grads is not None else F32,
-                                  ld_grads if grads is not None else 0, _ptr(ws), n,
-                                  _stream()), "rnnt_loss_ex")
-    return costs
+    return _transducer_loss("rnnt_loss_ex", acts, ld_acts, labels, act_lens, label_lens, B, T, U1, V1,
+                            (blank, fastemit_lambda, clamp, grad_scale), 5, grads, ld_grads)
+
+
+def rnnt_loss(acts, labels, act_lens, label_lens, blank, grads=None, fastemit_lambda=0.0, clamp=0.0, grad_scale=1.0):
+    """acts f32 [B,T,U1,V1] logits (contiguous); labels i64 [B,U1-1]; returns costs f32 [B]; fills `grads` (f32, same shape)"""
+    B, T, U1, V1 = acts.shape
+    return rnnt_loss_pitched(acts, V1, B, T, U1, V1, labels, act_lens, label_lens, blank, grads, V1, fastemit_lambda=fastemit_lambda,
+                             clamp=clamp, grad_scale=grad_scale)
 
 
 def _greedy_decode(tdt, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
@@ -797,13 +799,8 @@ def tdt_loss_pitched(acts, ld_acts, B, T, U1, V1, durations, labels, act_lens, l
     """Token-and-Duration Transducer loss (mi355x_tdt_loss_ex): acts f32 logits [.., V1 + D] in rows of pitch ld_acts (V1 label
     logits, then one per duration); grads (f32 or bf16, optional) rows of pitch ld_grads, pad columns zero-filled -> costs f32 [B]"""
     D, dur = _tdt_durations(durations)
-    n = (4 + 2 * D) * B * T * U1 + 2 * B
-    ws = torch.empty(n, device=acts.device, dtype=torch.float32)
-    costs = torch.empty(B, device=acts.device, dtype=torch.float32)
-    check(lib.mi355x_tdt_loss_ex(_ptr(acts), ld_acts, _ptr(labels), _ptr(act_lens), _ptr(label_lens), B, T, U1, V1, D, dur, blank,
-                                 sigma, grad_scale, _ptr(costs), _ptr(grads), dt(grads) if grads is not None else F32,
-                                 ld_grads if grads is not None else 0, _ptr(ws), n, _stream()), "tdt_loss_ex")
-    return costs
+    return _transducer_loss("tdt_loss_ex", acts, ld_acts, labels, act_lens, label_lens, B, T, U1, V1,
+                            (D, dur, blank, sigma, grad_scale), 4 + 2 * D, grads, ld_grads)
 
 
 def tdt_loss(acts, labels, act_lens, label_lens, blank, durations, grads=None, sigma=0.0, grad_scale=1.0):

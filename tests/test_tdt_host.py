@@ -155,9 +155,37 @@ def test_tdt_abi_rejects_bad_arguments_without_a_gpu():
     assert lib.mi355x_tdt_loss_ex(*a) == 1
     a = list(args(dur(0, 1, 2), 3)); a[15] = fake; a[16] = 1; a[17] = 13       # bf16 gradient pitch not a multiple of 8
     assert lib.mi355x_tdt_loss_ex(*a) == 1
+    a = list(args(dur(0, 1, 2), 3)); a[15] = fake; a[16] = 0; a[17] = 10       # gradient pitch < V1 + D
+    assert lib.mi355x_tdt_loss_ex(*a) == 1
     g = [fake, 0, 16, fake, fake, fake, 16, fake, 16, fake, fake, fake, 16, fake, fake, 16, fake, 0, 2, 4, 16, 16, 9, 3, dur(0, 1, 2),
          8, 10, fake, fake, fake, fake, 40, None, None, None]
     assert lib.mi355x_tdt_greedy_decode(*g[:24], dur(1, 2, 3), *g[25:]) == 1
     assert lib.mi355x_tdt_greedy_decode(*g[:23], 9, dur(*range(9)), *g[25:]) == 1
     g2 = list(g); g2[25] = 9                                                   # blank outside the V1 label logits
     assert lib.mi355x_tdt_greedy_decode(*g2) == 1
+
+
+def test_rnnt_abi_rejects_the_same_bad_arguments_without_a_gpu():
+    """mi355x_rnnt_loss_ex goes through the argument checks it shares with mi355x_tdt_loss_ex: every kind of bad call refused
+    there is refused here (one valid call with one argument spoiled at a time; nothing is launched)"""
+    from nemo_amd import _lib
+    lib = _lib.lib
+    B, T, U1, V1 = 2, 4, 3, 8
+    n = ctypes.c_longlong(0)
+    assert lib.mi355x_rnnt_workspace_elems(B, T, U1, ctypes.byref(n)) == 0 and n.value == 5 * B * T * U1 + 2 * B
+    fake = ctypes.c_void_p(16)   # aligned, never dereferenced: every call below fails its argument checks first
+    names = ("acts", "ld", "labels", "act_lens", "label_lens", "B", "T", "U1", "V1", "blank", "fastemit", "clamp", "scale", "costs",
+             "grads", "gdt", "ldg", "ws", "ws_elems", "stream")
+    good = dict(zip(names, (fake, V1, fake, fake, fake, B, T, U1, V1, V1 - 1, 0.0, 0.0, 1.0, fake, fake, 0, V1, fake, n.value, None)))
+    bad = {"row pitch < V1": dict(ld=V1 - 1),
+           "gradient pitch < V1": dict(ldg=V1 - 1),
+           "U1 > 1024": dict(U1=1025, ws_elems=1 << 30),
+           "bf16 gradient pitch not a multiple of 8": dict(gdt=1, ldg=V1 + 4),
+           "bf16 gradient pointer not 16-byte aligned": dict(gdt=1, grads=ctypes.c_void_p(24)),
+           "workspace one element short": dict(ws_elems=n.value - 1),
+           "clamp < 0": dict(clamp=-0.5),
+           "fastemit_lambda < 0": dict(fastemit=-0.5),
+           "blank >= V1": dict(blank=V1),
+           "unknown gradient dtype": dict(gdt=2)}
+    for why, change in bad.items():
+        assert lib.mi355x_rnnt_loss_ex(*{**good, **change}.values()) == 1, why

@@ -19,6 +19,12 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
   if (m == NEGINF) return NEGINF;
   return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
 }
+// Negative log-likelihood from the last alpha row: l1 = state S-1, l2 = state S-2 (-inf where S = 1), natural log.  Both lattice
+// kernels and the gradient kernel take it from here, so the three values are bit-equal by construction.
+__device__ __forceinline__ float ctc_nll(float l1, float l2) {
+  const float m = fmaxf(l1, l2);
+  return -((m == NEGINF) ? NEGINF : m + logf(expf(l1 - m) + expf(l2 - m)));
+}
 
 // logp [B, Tmax, C] f32 ; targets [B, Umax] i64 ; alpha/beta workspaces [B, Tmax, Smax]; grad [B, Tmax, C]
 __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
@@ -101,10 +107,7 @@ __global__ __launch_bounds__(256) void ctc_kernel(const float* __restrict__ logp
   // log-likelihood from the last alpha row (= row (T-1)&1 of prev_a)
   if (tid == 0) {
     const float* last = prev_a + (((T - 1) & 1) ? Smax : 0);
-    const float l1 = last[S - 1], l2 = (S > 1) ? last[S - 2] : NEGINF;
-    const float m = fmaxf(l1, l2);
-    float ll = (m == NEGINF) ? NEGINF : m + logf(expf(l1 - m) + expf(l2 - m));
-    float out = -ll;
+    float out = ctc_nll(last[S - 1], (S > 1) ? last[S - 2] : NEGINF);
     if (out == INFINITY && zero_infinity) out = 0.f;
     nll_out[b] = out;
   }
@@ -133,58 +136,84 @@ __device__ __forceinline__ float lse3f(float a, float b, float c) {
   return (m == NEGINF) ? NEGINF
                        : m + __builtin_amdgcn_logf(__builtin_amdgcn_exp2f(a - m) + __builtin_amdgcn_exp2f(b - m) + __builtin_amdgcn_exp2f(c - m));
 }
+// ---- the scaffold of a wave-resident walk, shared by the loss (ctc_wave_walk) and the Viterbi pass (ctc_align_wave_kernel): which
+// pairs a lane holds, how the emissions reach the walker and what it gets from the neighbouring lane.  The two differ in the step.
 template <int P> struct CtcTc { static constexpr int v = P <= 2 ? 64 : 128 / P; };   // time-steps per chunk (<= 64: one blank load per lane)
-template <int P, bool BETA>
-__device__ __forceinline__ void ctc_wave_walk(const float* __restrict__ lp, const long long* __restrict__ tg, float* __restrict__ ws,
-                                              float* __restrict__ nll_out, int T, int U, int C, int Smax, int blank, int zero_infinity,
-                                              float (*s_e)[CtcTc<P>::v * (64 * P + 1)]) {
-  constexpr int TC = CtcTc<P>::v, LD = 64 * P + 1;   // LDS row of a time-step: [p][lane] label emissions, then the blank emission
-  const int lane = threadIdx.x & 63;
-  const bool loader = threadIdx.x >= 64;   // wave-uniform
-  // per pair: the label's class, whether the skip transition into (alpha) / out of (beta) its label state exists
+// per pair of a lane: the label's class, which of its two states exist, whether the skip transition into (forward walk) / out of
+// (BETA: backward walk) its label state exists
+template <int P> struct CtcPairs {
   int cls[P];
   bool vE[P], vO[P], skip[P];
+};
+template <int P, bool BETA>
+__device__ __forceinline__ void ctc_pairs_setup(CtcPairs<P>& q, const long long* __restrict__ tg, int U, int blank) {
+  const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     const int g = lane * P + p;
-    vE[p] = g <= U;
-    vO[p] = g < U;
-    cls[p] = vO[p] ? (int)tg[g] : blank;
-    if (!BETA) skip[p] = vO[p] && g >= 1 && cls[p] != (int)tg[g - 1];
-    else skip[p] = g + 1 < U && cls[p] != (int)tg[g + 1];
+    q.vE[p] = g <= U;
+    q.vO[p] = g < U;
+    q.cls[p] = q.vO[p] ? (int)tg[g] : blank;
+    if (!BETA) q.skip[p] = q.vO[p] && g >= 1 && q.cls[p] != (int)tg[g - 1];
+    else q.skip[p] = g + 1 < U && q.cls[p] != (int)tg[g + 1];
   }
+}
+// the last row, walker wave only: l1 = state S-1 = E_U, l2 = state S-2 = O_{U-1} (-inf where U = 0), in every lane
+template <int P>
+__device__ __forceinline__ void ctc_wave_last_row(const float (&E)[P], const float (&O)[P], int U, float& l1, float& l2) {
+  const int lane = threadIdx.x & 63;
+  float eU = NEGINF, oU = NEGINF;
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int g = lane * P + p;
+    if (g == U) eU = E[p];
+    if (g == U - 1) oU = O[p];
+  }
+  l1 = __shfl(eU, U / P, 64);
+  l2 = (U >= 1) ? __shfl(oU, (U - 1) / P, 64) : NEGINF;
+}
+// loader wave: the emissions of steps c*TC .. c*TC+TC-1 (REV: counted back from frame T-1; LOG2: scaled into the base-2 domain)
+// -> dst.  LDS row of a time-step: [p][lane] label emissions, then the blank emission.
+template <int P, bool REV, bool LOG2>
+__device__ __forceinline__ void ctc_wave_gather(float* dst, const float* __restrict__ lp, const int (&cls)[P], int T, int C, int blank,
+                                                int c) {
+  constexpr int TC = CtcTc<P>::v, LD = 64 * P + 1;
+  const int lane = threadIdx.x & 63;
+  float v[TC][P];
+#pragma unroll
+  for (int i = 0; i < TC; ++i) {
+    int step = c * TC + i;
+    step = step < T ? step : T - 1;   // (steps beyond the utterance re-read its last row: no branch, never used)
+    const float* row = lp + (long long)(REV ? (T - 1 - step) : step) * C;
+#pragma unroll
+    for (int p = 0; p < P; ++p) v[i][p] = row[cls[p]];
+  }
+  float vb = 0.f;
+  if (lane < TC) {
+    int step = c * TC + lane;
+    step = step < T ? step : T - 1;
+    vb = lp[(long long)(REV ? (T - 1 - step) : step) * C + blank];
+  }
+#pragma unroll
+  for (int i = 0; i < TC; ++i)
+#pragma unroll
+    for (int p = 0; p < P; ++p) dst[i * LD + p * 64 + lane] = LOG2 ? v[i][p] * CTC_LOG2E : v[i][p];
+  if (lane < TC) dst[lane * LD + 64 * P] = LOG2 ? vb * CTC_LOG2E : vb;
+}
+// The chunk loop of a workgroup's two waves: wave 1 gathers chunk c + 1 into the other half of s_e while wave 0 walks chunk c,
+// one barrier per chunk.  The walker calls step(step, e_blank, e_label[P]) for the steps 0 .. T-1 in order.
+template <int P, bool REV, bool LOG2, class Step>
+__device__ __forceinline__ void ctc_wave_chunks(const float* __restrict__ lp, const int (&cls)[P], int T, int C, int blank,
+                                                float (*s_e)[CtcTc<P>::v * (64 * P + 1)], Step step) {
+  constexpr int TC = CtcTc<P>::v, LD = 64 * P + 1;
+  const int lane = threadIdx.x & 63;
+  const bool loader = threadIdx.x >= 64;   // wave-uniform
   const int nchunk = (T + TC - 1) / TC;
-  auto gather = [&](int c) {   // loader wave: emissions of steps c*TC .. c*TC+TC-1 -> s_e[c & 1]
-    float* dst = s_e[c & 1];
-    float v[TC][P];
-#pragma unroll
-    for (int i = 0; i < TC; ++i) {
-      int step = c * TC + i;
-      step = step < T ? step : T - 1;   // (steps beyond the utterance re-read its last row: no branch, never used)
-      const float* row = lp + (long long)(BETA ? (T - 1 - step) : step) * C;
-#pragma unroll
-      for (int p = 0; p < P; ++p) v[i][p] = row[cls[p]];
-    }
-    float vb = 0.f;
-    if (lane < TC) {
-      int step = c * TC + lane;
-      step = step < T ? step : T - 1;
-      vb = lp[(long long)(BETA ? (T - 1 - step) : step) * C + blank];
-    }
-#pragma unroll
-    for (int i = 0; i < TC; ++i)
-#pragma unroll
-      for (int p = 0; p < P; ++p) dst[i * LD + p * 64 + lane] = v[i][p] * CTC_LOG2E;
-    if (lane < TC) dst[lane * LD + 64 * P] = vb * CTC_LOG2E;
-  };
-  float E[P], O[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) { E[p] = NEGINF; O[p] = NEGINF; }
-  if (loader) gather(0);
+  if (loader) ctc_wave_gather<P, REV, LOG2>(s_e[0], lp, cls, T, C, blank, 0);
   __syncthreads();
   for (int c = 0; c < nchunk; ++c) {
     if (loader) {
-      if (c + 1 < nchunk) gather(c + 1);
+      if (c + 1 < nchunk) ctc_wave_gather<P, REV, LOG2>(s_e[(c + 1) & 1], lp, cls, T, C, blank, c + 1);
     } else {
       const float* src = s_e[c & 1];
       const int nstep = min(TC, T - c * TC);
@@ -194,79 +223,82 @@ __device__ __forceinline__ void ctc_wave_walk(const float* __restrict__ lp, cons
 #pragma unroll
       for (int p = 0; p < P; ++p) el_n[p] = src[p * 64 + lane];
       for (int i = 0; i < nstep; ++i) {
-        const int step = c * TC + i;
-        const int t = BETA ? (T - 1 - step) : step;
         const float eb = eb_n;
         float el[P];
 #pragma unroll
         for (int p = 0; p < P; ++p) el[p] = el_n[p];
         const int i1 = i + 1 < TC ? i + 1 : TC - 1;
-        // old values of the neighbouring lane's boundary pair (alpha: its last label state; beta: its first pair)
-        float x0, x1 = NEGINF;
-        if (!BETA) {
-          x0 = __shfl_up(O[P - 1], 1, 64);
-          if (lane == 0) x0 = NEGINF;
-        } else {
-          x0 = __shfl_down(E[0], 1, 64);
-          x1 = __shfl_down(O[0], 1, 64);
-          if (lane == 63) { x0 = NEGINF; x1 = NEGINF; }
-        }
         eb_n = src[i1 * LD + 64 * P];
 #pragma unroll
         for (int p = 0; p < P; ++p) el_n[p] = src[i1 * LD + p * 64 + lane];
-        float nE[P], nO[P];
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-          float a, cc;
-          if (!BETA) {
-            // alpha: E_g <- lse(E_g, O_{g-1}) + e_blank ; O_g <- lse(O_g, E_g, skip ? O_{g-1} : -inf) + e_label   (old values on the right)
-            const float om1 = (p == 0) ? x0 : O[p == 0 ? 0 : p - 1];
-            a = lse2f(E[p], om1);
-            cc = lse3f(O[p], E[p], skip[p] ? om1 : NEGINF);
-          } else {
-            // beta: E_g <- lse(E_g, O_g) + e_blank ; O_g <- lse(O_g, E_{g+1}, skip ? O_{g+1} : -inf) + e_label
-            const float ep1 = (p == P - 1) ? x0 : E[p == P - 1 ? p : p + 1];
-            const float op1 = (p == P - 1) ? x1 : O[p == P - 1 ? p : p + 1];
-            a = lse2f(E[p], O[p]);
-            cc = lse3f(O[p], ep1, skip[p] ? op1 : NEGINF);
-          }
-          nE[p] = (vE[p] && a != NEGINF) ? a + eb : NEGINF;
-          nO[p] = (vO[p] && cc != NEGINF) ? cc + el[p] : NEGINF;
-        }
-        if (step == 0) {  // (wave-uniform) alpha_0: states 0, 1 ; beta_{T-1}: states S-1, S-2
-#pragma unroll
-          for (int p = 0; p < P; ++p) {
-            const int g = lane * P + p;
-            nE[p] = (g == (BETA ? U : 0)) ? eb : NEGINF;
-            nO[p] = (vO[p] && g == (BETA ? U - 1 : 0)) ? el[p] : NEGINF;
-          }
-        }
-        float* wrow = ws + (long long)t * Smax + 2 * lane * P;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-          E[p] = nE[p]; O[p] = nO[p];
-          if (vE[p]) wrow[2 * p] = nE[p] * CTC_LN2;      // (-inf stays -inf)
-          if (vO[p]) wrow[2 * p + 1] = nO[p] * CTC_LN2;
-        }
+        step(c * TC + i, eb, el);
       }
     }
     __syncthreads();   // chunk c + 1 is in LDS; the walker is done with chunk c's half
   }
-  if (!BETA && !loader) {
-    // log-likelihood from the last alpha row: states S-1 = E_U and S-2 = O_{U-1}
-    float eU = NEGINF, oU = NEGINF;
+}
+
+template <int P, bool BETA>
+__device__ __forceinline__ void ctc_wave_walk(const float* __restrict__ lp, const long long* __restrict__ tg, float* __restrict__ ws,
+                                              float* __restrict__ nll_out, int T, int U, int C, int Smax, int blank, int zero_infinity,
+                                              float (*s_e)[CtcTc<P>::v * (64 * P + 1)]) {
+  const int lane = threadIdx.x & 63;
+  CtcPairs<P> q;
+  ctc_pairs_setup<P, BETA>(q, tg, U, blank);
+  float E[P], O[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) { E[p] = NEGINF; O[p] = NEGINF; }
+  ctc_wave_chunks<P, BETA, true>(lp, q.cls, T, C, blank, s_e, [&](int step, float eb, const float (&el)[P]) {
+    // old values of the neighbouring lane's boundary pair (alpha: its last label state; beta: its first pair)
+    float x0, x1 = NEGINF;
+    if (!BETA) {
+      x0 = __shfl_up(O[P - 1], 1, 64);
+      if (lane == 0) x0 = NEGINF;
+    } else {
+      x0 = __shfl_down(E[0], 1, 64);
+      x1 = __shfl_down(O[0], 1, 64);
+      if (lane == 63) { x0 = NEGINF; x1 = NEGINF; }
+    }
+    float nE[P], nO[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-      const int g = lane * P + p;
-      if (g == U) eU = E[p];
-      if (g == U - 1) oU = O[p];
+      float a, cc;
+      if (!BETA) {
+        // alpha: E_g <- lse(E_g, O_{g-1}) + e_blank ; O_g <- lse(O_g, E_g, skip ? O_{g-1} : -inf) + e_label   (old values on the right)
+        const float om1 = (p == 0) ? x0 : O[p == 0 ? 0 : p - 1];
+        a = lse2f(E[p], om1);
+        cc = lse3f(O[p], E[p], q.skip[p] ? om1 : NEGINF);
+      } else {
+        // beta: E_g <- lse(E_g, O_g) + e_blank ; O_g <- lse(O_g, E_{g+1}, skip ? O_{g+1} : -inf) + e_label
+        const float ep1 = (p == P - 1) ? x0 : E[p == P - 1 ? p : p + 1];
+        const float op1 = (p == P - 1) ? x1 : O[p == P - 1 ? p : p + 1];
+        a = lse2f(E[p], O[p]);
+        cc = lse3f(O[p], ep1, q.skip[p] ? op1 : NEGINF);
+      }
+      nE[p] = (q.vE[p] && a != NEGINF) ? a + eb : NEGINF;
+      nO[p] = (q.vO[p] && cc != NEGINF) ? cc + el[p] : NEGINF;
     }
-    const float l1 = __shfl(eU, U / P, 64) * CTC_LN2;
-    const float l2 = (U >= 1) ? __shfl(oU, (U - 1) / P, 64) * CTC_LN2 : NEGINF;
+    if (step == 0) {  // (wave-uniform) alpha_0: states 0, 1 ; beta_{T-1}: states S-1, S-2
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int g = lane * P + p;
+        nE[p] = (g == (BETA ? U : 0)) ? eb : NEGINF;
+        nO[p] = (q.vO[p] && g == (BETA ? U - 1 : 0)) ? el[p] : NEGINF;
+      }
+    }
+    float* wrow = ws + (long long)(BETA ? (T - 1 - step) : step) * Smax + 2 * lane * P;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      E[p] = nE[p]; O[p] = nO[p];
+      if (q.vE[p]) wrow[2 * p] = nE[p] * CTC_LN2;      // (-inf stays -inf)
+      if (q.vO[p]) wrow[2 * p + 1] = nO[p] * CTC_LN2;
+    }
+  });
+  if (!BETA && threadIdx.x < 64) {   // log-likelihood from the last alpha row
+    float l1, l2;
+    ctc_wave_last_row<P>(E, O, U, l1, l2);
     if (lane == 0) {
-      const float m = fmaxf(l1, l2);
-      const float ll = (m == NEGINF) ? NEGINF : m + logf(expf(l1 - m) + expf(l2 - m));
-      float out = -ll;
+      float out = ctc_nll(l1 * CTC_LN2, l2 * CTC_LN2);
       if (out == INFINITY && zero_infinity) out = 0.f;
       *nll_out = out;
     }
@@ -296,6 +328,20 @@ __global__ __launch_bounds__(128) void ctc_wave_kernel(const float* __restrict__
     ctc_wave_walk<P, true>(lp, tg, beta_ws + (long long)b * Tmax * Smax, nullptr, T, U, C, Smax, blank, zero_infinity, s_e);
 }
 
+// Which form a launch takes, for the loss and the alignment alike.  A knob that was never set (< 0) is read from its environment
+// variable at the first launch: "0..." = the LDS / barrier form always, anything else = the wave-resident form where it fits.
+static int ctc_knob(int& knob, const char* env) {
+  if (knob < 0) {
+    const char* e = getenv(env);
+    knob = (e && e[0] == '0') ? 0 : 1;
+  }
+  return knob;
+}
+// pairs per lane P of the wave-resident form (Smax <= 128 P states), 0 = the LDS / barrier form
+static int ctc_wave_pairs(int wave, int Smax) { return (!wave || Smax > 1024) ? 0 : Smax <= 128 ? 1 : Smax <= 256 ? 2 : Smax <= 512 ? 4 : 8; }
+#define CTC_DISPATCH(P, WAVE, LDS)                                                                                                 \
+  switch (P) { case 1: WAVE(1); break; case 2: WAVE(2); break; case 4: WAVE(4); break; case 8: WAVE(8); break; default: LDS; }
+
 // MI355X_CTC_WAVE (mi355x_ctc_config): 1 (default) = the wave-resident lattice kernel for S <= 1024 states, 0 = the LDS / barrier form
 static int g_ctc_wave = -1;
 extern "C" int mi355x_ctc_config(int wave) {
@@ -320,12 +366,8 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float* lp = logp + (long long)b * Tmax * C;
   const float* aw = alpha_ws + (long long)b * Tmax * Smax;
-  float nll = INFINITY;  // the un-clamped negative log-likelihood, from the last alpha row (same arithmetic as phase 1)
-  if (T > 0) {
-    const float l1 = aw[(long long)(T - 1) * Smax + S - 1], l2 = (S > 1) ? aw[(long long)(T - 1) * Smax + S - 2] : NEGINF;
-    const float m = fmaxf(l1, l2);
-    nll = -((m == NEGINF) ? NEGINF : m + logf(expf(l1 - m) + expf(l2 - m)));
-  }
+  float nll = INFINITY;  // the un-clamped negative log-likelihood, from the last alpha row
+  if (T > 0) nll = ctc_nll(aw[(long long)(T - 1) * Smax + S - 1], (S > 1) ? aw[(long long)(T - 1) * Smax + S - 2] : NEGINF);
   const float* bw = beta_ws + (long long)b * Tmax * Smax;
   float* g = grad + (long long)b * Tmax * C;
   float* wacc = acc + wave * C;
@@ -358,23 +400,14 @@ extern "C" int mi355x_ctc_loss(const void* logp, const void* targets, const void
   const int Smax = 2 * Umax + 1;
   const size_t shm = sizeof(float) * ((size_t)Smax * 5);
   if (shm > 60 * 1024 || sizeof(float) * 4 * (size_t)C > 60 * 1024) return MI_ERR_ARG;
-  if (g_ctc_wave < 0) {
-    const char* e = getenv("MI355X_CTC_WAVE");
-    g_ctc_wave = (e && e[0] == '0') ? 0 : 1;
-  }
-#define CTC_WAVE_LAUNCH(PP)                                                                                                        \
-  MI_LAUNCH(ctc_wave_kernel<PP>, dim3(B, 2), dim3(128), 0, (hipStream_t)stream, (const float*)logp, (const long long*)targets,        \
+#define CTC_LATTICE(kernel, grid, threads, lds)                                                                                     \
+  MI_LAUNCH(kernel, grid, dim3(threads), lds, (hipStream_t)stream, (const float*)logp, (const long long*)targets,                    \
             (const long long*)in_len, (const long long*)tgt_len, (float*)alpha_ws, (float*)beta_ws, (float*)nll, Tmax, C, Umax,    \
             Smax, blank, zero_infinity)
-  if (g_ctc_wave && Smax <= 128) { CTC_WAVE_LAUNCH(1); }
-  else if (g_ctc_wave && Smax <= 256) { CTC_WAVE_LAUNCH(2); }
-  else if (g_ctc_wave && Smax <= 512) { CTC_WAVE_LAUNCH(4); }
-  else if (g_ctc_wave && Smax <= 1024) { CTC_WAVE_LAUNCH(8); }
-  else
-  MI_LAUNCH(ctc_kernel, dim3(B), dim3(256), shm, (hipStream_t)stream, (const float*)logp, (const long long*)targets,
-                     (const long long*)in_len, (const long long*)tgt_len, (float*)alpha_ws, (float*)beta_ws, (float*)nll, Tmax,
-                     C, Umax, Smax, blank, zero_infinity);
-#undef CTC_WAVE_LAUNCH
+#define CTC_WAVE(PP) CTC_LATTICE(ctc_wave_kernel<PP>, dim3(B, 2), 128, 0)
+  CTC_DISPATCH(ctc_wave_pairs(ctc_knob(g_ctc_wave, "MI355X_CTC_WAVE"), Smax), CTC_WAVE, CTC_LATTICE(ctc_kernel, dim3(B), 256, shm))
+#undef CTC_WAVE
+#undef CTC_LATTICE
   if (grad)
     MI_LAUNCH(ctc_grad_kernel, dim3((Tmax + CTC_GT - 1) / CTC_GT, B), dim3(256), sizeof(float) * 4 * (size_t)C,
                        (hipStream_t)stream, (const float*)logp, (const long long*)targets, (const long long*)in_len,
@@ -388,145 +421,39 @@ extern "C" int mi355x_ctc_loss(const void* logp, const void* targets, const void
 // AbstractCTCDecoding.decode_hypothesis (parts/submodules/ctc_decoding.py:545-575), one workgroup per utterance, no host
 // round trip: per-frame argmax (first maximum, like torch.max) and its log-probability, score = sum of the log-probs of
 // the non-blank frames, tokens = labels with repeats folded and blanks removed (wave ballot + prefix popcount compaction).
-__global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict__ logp, const long long* __restrict__ lens,
-                                                         int* __restrict__ tokens, int* __restrict__ out_len,
-                                                         float* __restrict__ score, int Tmax, int C, int blank) {
-  extern __shared__ int s_lab[];  // [Tmax] labels ; then [Tmax] log-probs (as float)
-  float* s_lp = reinterpret_cast<float*>(s_lab + Tmax);
-  const int b = blockIdx.x;
-  const int T = (int)min((long long)Tmax, lens ? lens[b] : (long long)Tmax);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* lp = logp + (long long)b * Tmax * C;
-  for (int t = wave; t < T; t += 4) {
-    float best = -INFINITY; int arg = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) {
-      const float v = lp[(long long)t * C + c];
-      if (v > best) { best = v; arg = c; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o, 64); const int oa = __shfl_xor(arg, o, 64);
-      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
-    if (lane == 0) { s_lab[t] = arg; s_lp[t] = best; }
-  }
-  __syncthreads();
-  int* tok = tokens + (long long)b * Tmax;
-  if (wave == 0) {
-    int base = 0; float sc = 0.f;
-    for (int t0 = 0; t0 < T; t0 += 64) {
-      const int t = t0 + lane;
-      const int cur = t < T ? s_lab[t] : blank;
-      const int prev = (t > 0 && t < T) ? s_lab[t - 1] : blank;
-      const bool nonblank = t < T && cur != blank;
-      const bool keep = nonblank && cur != prev;
-      if (nonblank) sc += s_lp[t];
-      const unsigned long long m = __ballot(keep);
-      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-      if (keep) tok[pos] = cur;
-      base += __popcll(m);
-    }
-    sc = wave_sum(sc);
-    if (lane == 0) { out_len[b] = base; score[b] = sc; }
-    for (int t = base + lane; t < Tmax; t += 64) tok[t] = -1;  // padding
-  }
-}
-extern "C" int mi355x_ctc_greedy_decode(const void* logp, const void* lens, void* tokens, void* out_len, void* score, int B,
-                                        int Tmax, int C, int blank, void* stream) {
-  mi_clear_errors();
-  if (!logp || !tokens || !out_len || !score || B <= 0 || Tmax <= 0 || C <= 0 || blank < 0 || blank > C) return MI_ERR_ARG;
-  const size_t shm = (size_t)Tmax * 8;
-  if (shm > 64 * 1024) return MI_ERR_ARG;
-  MI_LAUNCH(ctc_greedy_kernel, dim3(B), dim3(256), shm, (hipStream_t)stream, (const float*)logp, (const long long*)lens,
-                     (int*)tokens, (int*)out_len, (float*)score, Tmax, C, blank);
-  return mi_check_launch();
-}
-
-// mi355x_ctc_greedy_decode_ts: the kernel above, and the first and the last frame of the run of equal arg-max labels behind every kept
-// token.  Its own kernel, so that the one above stays as it is.  A run starts at the frame the compaction keeps; it ends at the frame
-// in front of the next frame whose label differs (or at the last valid frame), and the token it belongs to is the latest keep at or
-// before that frame -- the same ballot with an inclusive prefix, so runs that cross a 64-frame group need nothing more.
-__global__ __launch_bounds__(256) void ctc_greedy_ts_kernel(const float* __restrict__ logp, const long long* __restrict__ lens,
-                                                            int* __restrict__ tokens, int* __restrict__ out_len,
-                                                            float* __restrict__ score, int* __restrict__ tok_start,
-                                                            int* __restrict__ tok_end, int Tmax, int C, int blank) {
-  extern __shared__ int s_lab[];  // [Tmax] labels ; then [Tmax] log-probs (as float)
-  float* s_lp = reinterpret_cast<float*>(s_lab + Tmax);
-  const int b = blockIdx.x;
-  const int T = (int)min((long long)Tmax, lens ? lens[b] : (long long)Tmax);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* lp = logp + (long long)b * Tmax * C;
-  for (int t = wave; t < T; t += 4) {
-    float best = -INFINITY; int arg = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) {
-      const float v = lp[(long long)t * C + c];
-      if (v > best) { best = v; arg = c; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o, 64); const int oa = __shfl_xor(arg, o, 64);
-      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
-    if (lane == 0) { s_lab[t] = arg; s_lp[t] = best; }
-  }
-  __syncthreads();
-  int* tok = tokens + (long long)b * Tmax;
-  int* ts = tok_start + (long long)b * Tmax;
-  int* te = tok_end + (long long)b * Tmax;
-  if (wave == 0) {
-    int base = 0; float sc = 0.f;
-    for (int t0 = 0; t0 < T; t0 += 64) {
-      const int t = t0 + lane;
-      const int cur = t < T ? s_lab[t] : blank;
-      const int prev = (t > 0 && t < T) ? s_lab[t - 1] : blank;
-      const bool nonblank = t < T && cur != blank;
-      const bool keep = nonblank && cur != prev;
-      if (nonblank) sc += s_lp[t];
-      const unsigned long long m = __ballot(keep);
-      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-      if (keep) { tok[pos] = cur; ts[pos] = t; }
-      if (nonblank && (t + 1 >= T || s_lab[t + 1] != cur))   // (2 << 63 wraps to 0: the mask of lane 63 is all ones)
-        te[base + __popcll(m & ((2ull << lane) - 1ull)) - 1] = t;
-      base += __popcll(m);
-    }
-    sc = wave_sum(sc);
-    if (lane == 0) { out_len[b] = base; score[b] = sc; }
-    for (int t = base + lane; t < Tmax; t += 64) { tok[t] = -1; ts[t] = -1; te[t] = -1; }  // padding
-  }
-}
-extern "C" int mi355x_ctc_greedy_decode_ts(const void* logp, const void* lens, void* tokens, void* out_len, void* score,
-                                           void* tok_start, void* tok_end, int B, int Tmax, int C, int blank, void* stream) {
-  mi_clear_errors();
-  if (!logp || !tokens || !out_len || !score || !tok_start || !tok_end || B <= 0 || Tmax <= 0 || C <= 0 || blank < 0 || blank >= C)
-    return MI_ERR_ARG;
-  const size_t shm = (size_t)Tmax * 8;
-  if (shm > 64 * 1024) return MI_ERR_ARG;
-  MI_LAUNCH(ctc_greedy_ts_kernel, dim3(B), dim3(256), shm, (hipStream_t)stream, (const float*)logp, (const long long*)lens,
-                     (int*)tokens, (int*)out_len, (float*)score, (int*)tok_start, (int*)tok_end, Tmax, C, blank);
-  return mi_check_launch();
-}
-
-// mi355x_ctc_greedy_decode_conf: the kernel above, and confidences.  Its own kernel, so that the two above stay as they are.  The
-// wave that walks a frame's C log-probabilities for the arg-max carries the sums of the chosen measure in the same pass (log-probs
-// are <= 0, so p^alpha = exp(alpha x) needs no shift; a -inf class adds nothing) and stores the frame's confidence.  After the
-// compaction a lane per token folds the frame confidences of its range, read back from frame_conf behind the barrier (a third
-// per-frame array in LDS would not fit at Tmax = 8192 without raising the limit).
+// One kernel at three levels; what a level adds is compiled out of the levels below it.
+//   LEVEL 0 (mi355x_ctc_greedy_decode): tokens, their count and the score.
+//   LEVEL 1 (_ts): and the first and the last frame of the run of equal arg-max labels behind every kept token.  A run starts at the
+//     frame the compaction keeps; it ends at the frame in front of the next frame whose label differs (or at the last valid frame),
+//     and the token it belongs to is the latest keep at or before that frame -- the same ballot with an inclusive prefix, so runs
+//     that cross a 64-frame group need nothing more.
+//   LEVEL 2 (_conf): and confidences.  The wave that walks a frame's C log-probabilities for the arg-max carries the sums of the
+//     chosen measure in the same pass (log-probs are <= 0, so p^alpha = exp(alpha x) needs no shift; a -inf class adds nothing) and
+//     stores the frame's confidence.  After the compaction a lane per token folds the frame confidences of its range, read back
+//     from frame_conf behind the barrier (a third per-frame array in LDS would not fit at Tmax = 8192 without raising the limit);
+//     tok_start / tok_end / frame_conf are read back too, so they are not __restrict__.
 __device__ __forceinline__ float ctc_conf_fold(float a, float b, int agg) {
   return agg == MI355X_CONF_AGG_MIN ? fminf(a, b) : agg == MI355X_CONF_AGG_MAX ? fmaxf(a, b) : agg == MI355X_CONF_AGG_PROD ? a * b : a + b;
 }
-__global__ __launch_bounds__(256) void ctc_greedy_conf_kernel(const float* __restrict__ logp, const long long* __restrict__ lens,
-                                                              int* __restrict__ tokens, int* __restrict__ out_len,
-                                                              float* __restrict__ score, int* tok_start, int* tok_end,
-                                                              float* frame_conf, float* __restrict__ tok_conf, int Tmax, int C,
-                                                              int blank, MiConf q, int agg, int exclude_blank) {
+template <int LEVEL>
+__global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict__ logp, const long long* __restrict__ lens,
+                                                         int* __restrict__ tokens, int* __restrict__ out_len,
+                                                         float* __restrict__ score, int* tok_start, int* tok_end, float* frame_conf,
+                                                         float* __restrict__ tok_conf, int Tmax, int C, int blank, MiConf q, int agg,
+                                                         int exclude_blank) {
+  constexpr bool TS = LEVEL >= 1, CONF = LEVEL >= 2;
   extern __shared__ int s_lab[];  // [Tmax] labels ; then [Tmax] log-probs (as float)
   float* s_lp = reinterpret_cast<float*>(s_lab + Tmax);
   const int b = blockIdx.x;
   const int T = (int)min((long long)Tmax, lens ? lens[b] : (long long)Tmax);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* lp = logp + (long long)b * Tmax * C;
-  float* fc = frame_conf + (long long)b * Tmax;
-  const bool sums = q.method != MI355X_CONF_MAX_PROB;   // (uniform)
+  int* tok = tokens + (long long)b * Tmax;
+  int* ts = TS ? tok_start + (long long)b * Tmax : nullptr;
+  int* te = TS ? tok_end + (long long)b * Tmax : nullptr;
+  float* fc = CONF ? frame_conf + (long long)b * Tmax : nullptr;
+  float* tc = CONF ? tok_conf + (long long)b * Tmax : nullptr;
+  const bool sums = CONF && q.method != MI355X_CONF_MAX_PROB;   // (uniform)
   for (int t = wave; t < T; t += 4) {
     float best = -INFINITY; int arg = 0x7fffffff;
     float S = 0.f, G = 0.f;
@@ -545,14 +472,14 @@ __global__ __launch_bounds__(256) void ctc_greedy_conf_kernel(const float* __res
       if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
     }
     if (sums) { S = wave_sum(S); G = wave_sum(G); }
-    if (lane == 0) { s_lab[t] = arg; s_lp[t] = best; fc[t] = mi_conf_value(q, expf(best), S, G); }
+    if (lane == 0) {
+      s_lab[t] = arg; s_lp[t] = best;
+      if constexpr (CONF) fc[t] = mi_conf_value(q, expf(best), S, G);
+    }
   }
-  for (int t = T + (int)threadIdx.x; t < Tmax; t += 256) fc[t] = 0.f;   // padding
+  if constexpr (CONF)
+    for (int t = T + (int)threadIdx.x; t < Tmax; t += 256) fc[t] = 0.f;   // padding
   __syncthreads();
-  int* tok = tokens + (long long)b * Tmax;
-  int* ts = tok_start + (long long)b * Tmax;
-  int* te = tok_end + (long long)b * Tmax;
-  float* tc = tok_conf + (long long)b * Tmax;
   if (wave == 0) {
     int base = 0; float sc = 0.f;
     for (int t0 = 0; t0 < T; t0 += 64) {
@@ -564,60 +491,93 @@ __global__ __launch_bounds__(256) void ctc_greedy_conf_kernel(const float* __res
       if (nonblank) sc += s_lp[t];
       const unsigned long long m = __ballot(keep);
       const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-      if (keep) { tok[pos] = cur; ts[pos] = t; }
-      if (nonblank && (t + 1 >= T || s_lab[t + 1] != cur))   // (2 << 63 wraps to 0: the mask of lane 63 is all ones)
-        te[base + __popcll(m & ((2ull << lane) - 1ull)) - 1] = t;
+      if (keep) tok[pos] = cur;
+      if constexpr (TS) {
+        if (keep) ts[pos] = t;
+        if (nonblank && (t + 1 >= T || s_lab[t + 1] != cur))   // (2 << 63 wraps to 0: the mask of lane 63 is all ones)
+          te[base + __popcll(m & ((2ull << lane) - 1ull)) - 1] = t;
+      }
       base += __popcll(m);
     }
     sc = wave_sum(sc);
     if (lane == 0) { out_len[b] = base; score[b] = sc; }
-    for (int t = base + lane; t < Tmax; t += 64) { tok[t] = -1; ts[t] = -1; te[t] = -1; tc[t] = 0.f; }  // padding
-  }
-  __syncthreads();   // out_len / tok_start / tok_end / frame_conf of this workgroup are visible to all of its waves
-  const int n = out_len[b];   // (all of the LDS a launch may have without a raised limit is the two per-frame arrays at Tmax = 8192)
-  const float id = agg == MI355X_CONF_AGG_MIN ? INFINITY : agg == MI355X_CONF_AGG_MAX ? -INFINITY : agg == MI355X_CONF_AGG_PROD ? 1.f : 0.f;
-  // A lane per token: its range is a handful of frames as a rule, folded in the lane (a wave per token spent its time on the two
-  // dependent loads that find the range: 122 us of 237 at B = 32, T = 501).  A range of more than 64 frames -- a long run, or with
-  // exclude_blank off a long silence in front of a token -- is folded by the whole wave instead, one such token after the other.
-  for (int i0 = wave * 64; i0 < n; i0 += 256) {   // (uniform over the wave; 0 <= lo <= hi < T by construction of the runs)
-    const int i = i0 + lane;
-    const bool valid = i < n;
-    const int hi = valid ? te[i] : -1;
-    const int lo = !valid ? 0 : exclude_blank ? ts[i] : (i ? te[i - 1] + 1 : 0);
-    const bool wide = valid && hi - lo >= 64;
-    if (valid && !wide) {
-      float a = id;
-      for (int t = lo; t <= hi; ++t) a = ctc_conf_fold(a, fc[t], agg);
-      tc[i] = agg == MI355X_CONF_AGG_MEAN ? a / (float)(hi - lo + 1) : a;
+    for (int t = base + lane; t < Tmax; t += 64) {  // padding
+      tok[t] = -1;
+      if constexpr (TS) { ts[t] = -1; te[t] = -1; }
+      if constexpr (CONF) tc[t] = 0.f;
     }
-    for (unsigned long long m = __ballot(wide); m; m &= m - 1) {
-      const int l = __ffsll((long long)m) - 1;
-      const int wlo = __shfl(lo, l, 64), whi = __shfl(hi, l, 64);
-      float a = id;
-      for (int t = wlo + lane; t <= whi; t += 64) a = ctc_conf_fold(a, fc[t], agg);
+  }
+  if constexpr (CONF) {
+    __syncthreads();   // out_len / tok_start / tok_end / frame_conf of this workgroup are visible to all of its waves
+    const int n = out_len[b];   // (all of the LDS a launch may have without a raised limit is the two per-frame arrays at Tmax = 8192)
+    const float id = agg == MI355X_CONF_AGG_MIN ? INFINITY : agg == MI355X_CONF_AGG_MAX ? -INFINITY : agg == MI355X_CONF_AGG_PROD ? 1.f : 0.f;
+    // A lane per token: its range is a handful of frames as a rule, folded in the lane (a wave per token spent its time on the two
+    // dependent loads that find the range: 122 us of 237 at B = 32, T = 501).  A range of more than 64 frames -- a long run, or with
+    // exclude_blank off a long silence in front of a token -- is folded by the whole wave instead, one such token after the other.
+    for (int i0 = wave * 64; i0 < n; i0 += 256) {   // (uniform over the wave; 0 <= lo <= hi < T by construction of the runs)
+      const int i = i0 + lane;
+      const bool valid = i < n;
+      const int hi = valid ? te[i] : -1;
+      const int lo = !valid ? 0 : exclude_blank ? ts[i] : (i ? te[i - 1] + 1 : 0);
+      const bool wide = valid && hi - lo >= 64;
+      if (valid && !wide) {
+        float a = id;
+        for (int t = lo; t <= hi; ++t) a = ctc_conf_fold(a, fc[t], agg);
+        tc[i] = agg == MI355X_CONF_AGG_MEAN ? a / (float)(hi - lo + 1) : a;
+      }
+      for (unsigned long long m = __ballot(wide); m; m &= m - 1) {
+        const int l = __ffsll((long long)m) - 1;
+        const int wlo = __shfl(lo, l, 64), whi = __shfl(hi, l, 64);
+        float a = id;
+        for (int t = wlo + lane; t <= whi; t += 64) a = ctc_conf_fold(a, fc[t], agg);
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) a = ctc_conf_fold(a, __shfl_xor(a, o, 64), agg);
-      if (lane == 0) tc[i0 + l] = agg == MI355X_CONF_AGG_MEAN ? a / (float)(whi - wlo + 1) : a;
+        for (int o = 32; o > 0; o >>= 1) a = ctc_conf_fold(a, __shfl_xor(a, o, 64), agg);
+        if (lane == 0) tc[i0 + l] = agg == MI355X_CONF_AGG_MEAN ? a / (float)(whi - wlo + 1) : a;
+      }
     }
   }
+}
+
+// The one launcher behind the three entries: the checks, the LDS rule (two per-frame arrays: 8 Tmax bytes <= 64 KB) and the launch.
+// Level 0 accepts blank == C (no class is the blank: nothing is dropped), as its entry always has; the two levels above it want
+// the blank to be a class.
+static int ctc_greedy_launch(int level, const void* logp, const void* lens, void* tokens, void* out_len, void* score, void* tok_start,
+                             void* tok_end, void* frame_conf, void* tok_conf, int B, int Tmax, int C, int blank, MiConf q, int agg,
+                             int exclude_blank, void* stream) {
+  mi_clear_errors();
+  if (!logp || !tokens || !out_len || !score || (level >= 1 && (!tok_start || !tok_end)) || (level >= 2 && (!frame_conf || !tok_conf)))
+    return MI_ERR_ARG;
+  if (B <= 0 || Tmax <= 0 || C <= 0 || blank < 0 || blank > (level == 0 ? C : C - 1)) return MI_ERR_ARG;
+  if (level >= 2 && (!mi_conf_valid(C, q.method, q.norm, q.alpha) || agg < MI355X_CONF_AGG_MEAN || agg > MI355X_CONF_AGG_PROD))
+    return MI_ERR_ARG;
+  const size_t shm = (size_t)Tmax * 8;
+  if (shm > 64 * 1024) return MI_ERR_ARG;
+#define CTC_GREEDY(LEVEL)                                                                                                          \
+  MI_LAUNCH(ctc_greedy_kernel<LEVEL>, dim3(B), dim3(256), shm, (hipStream_t)stream, (const float*)logp, (const long long*)lens,       \
+            (int*)tokens, (int*)out_len, (float*)score, (int*)tok_start, (int*)tok_end, (float*)frame_conf, (float*)tok_conf, Tmax,  \
+            C, blank, q, agg, exclude_blank)
+  if (level == 0) CTC_GREEDY(0);
+  else if (level == 1) CTC_GREEDY(1);
+  else CTC_GREEDY(2);
+#undef CTC_GREEDY
+  return mi_check_launch();
+}
+extern "C" int mi355x_ctc_greedy_decode(const void* logp, const void* lens, void* tokens, void* out_len, void* score, int B,
+                                        int Tmax, int C, int blank, void* stream) {
+  return ctc_greedy_launch(0, logp, lens, tokens, out_len, score, nullptr, nullptr, nullptr, nullptr, B, Tmax, C, blank, MiConf{}, 0, 0,
+                           stream);
+}
+extern "C" int mi355x_ctc_greedy_decode_ts(const void* logp, const void* lens, void* tokens, void* out_len, void* score,
+                                           void* tok_start, void* tok_end, int B, int Tmax, int C, int blank, void* stream) {
+  return ctc_greedy_launch(1, logp, lens, tokens, out_len, score, tok_start, tok_end, nullptr, nullptr, B, Tmax, C, blank, MiConf{}, 0, 0,
+                           stream);
 }
 extern "C" int mi355x_ctc_greedy_decode_conf(const void* logp, const void* lens, void* tokens, void* out_len, void* score,
                                              void* tok_start, void* tok_end, void* frame_conf, void* tok_conf, int B, int Tmax, int C,
                                              int blank, int method, int norm, float alpha, float k0, float k1, float k2,
                                              int aggregation, int exclude_blank, void* stream) {
-  mi_clear_errors();
-  if (!logp || !tokens || !out_len || !score || !tok_start || !tok_end || !frame_conf || !tok_conf || B <= 0 || Tmax <= 0 ||
-      blank < 0 || blank >= C)
-    return MI_ERR_ARG;
-  if (!mi_conf_valid(C, method, norm, alpha) || aggregation < MI355X_CONF_AGG_MEAN || aggregation > MI355X_CONF_AGG_PROD)
-    return MI_ERR_ARG;
-  const size_t shm = (size_t)Tmax * 8;
-  if (shm > 64 * 1024) return MI_ERR_ARG;
-  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)C};
-  MI_LAUNCH(ctc_greedy_conf_kernel, dim3(B), dim3(256), shm, (hipStream_t)stream, (const float*)logp, (const long long*)lens,
-                     (int*)tokens, (int*)out_len, (float*)score, (int*)tok_start, (int*)tok_end, (float*)frame_conf,
-                     (float*)tok_conf, Tmax, C, blank, q, aggregation, exclude_blank);
-  return mi_check_launch();
+  return ctc_greedy_launch(2, logp, lens, tokens, out_len, score, tok_start, tok_end, frame_conf, tok_conf, B, Tmax, C, blank,
+                           MiConf{method, norm, alpha, k0, k1, k2, (float)C}, aggregation, exclude_blank, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ CTC forced alignment
@@ -754,105 +714,42 @@ __global__ __launch_bounds__(128) void ctc_align_wave_kernel(const float* __rest
   const long long* tg = targets + (long long)b * Umax;
   unsigned char* bp = bp_ws + (long long)b * Tmax * RS;
   const int lane = threadIdx.x & 63;
-  const bool loader = threadIdx.x >= 64;   // wave-uniform
-  int cls[P];
-  bool vE[P], vO[P], skip[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const int g = lane * P + p;
-    vE[p] = g <= U;
-    vO[p] = g < U;
-    cls[p] = vO[p] ? (int)tg[g] : blank;
-    skip[p] = vO[p] && g >= 1 && cls[p] != (int)tg[g - 1];
-  }
-  const int nchunk = (T + TC - 1) / TC;
-  auto gather = [&](int c) {   // loader wave: emissions of steps c*TC .. c*TC+TC-1 -> s_e[c & 1]
-    float* dst = s_e[c & 1];
-    float v[TC][P];
-#pragma unroll
-    for (int i = 0; i < TC; ++i) {
-      int step = c * TC + i;
-      step = step < T ? step : T - 1;   // (steps beyond the utterance re-read its last row: no branch, never used)
-      const float* row = lp + (long long)step * C;
-#pragma unroll
-      for (int p = 0; p < P; ++p) v[i][p] = row[cls[p]];
-    }
-    float vb = 0.f;
-    if (lane < TC) {
-      int step = c * TC + lane;
-      step = step < T ? step : T - 1;
-      vb = lp[(long long)step * C + blank];
-    }
-#pragma unroll
-    for (int i = 0; i < TC; ++i)
-#pragma unroll
-      for (int p = 0; p < P; ++p) dst[i * LD + p * 64 + lane] = v[i][p];
-    if (lane < TC) dst[lane * LD + 64 * P] = vb;
-  };
+  CtcPairs<P> q;
+  ctc_pairs_setup<P, false>(q, tg, U, blank);
   float E[P], O[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) { E[p] = NEGINF; O[p] = NEGINF; }
-  if (loader) gather(0);
-  __syncthreads();
-  for (int c = 0; c < nchunk; ++c) {
-    if (loader) {
-      if (c + 1 < nchunk) gather(c + 1);
-    } else {
-      const float* src = s_e[c & 1];
-      const int nstep = min(TC, T - c * TC);
-      float eb_n = src[64 * P], el_n[P];   // the emissions of step i + 1 are read while step i computes
-#pragma unroll
-      for (int p = 0; p < P; ++p) el_n[p] = src[p * 64 + lane];
-      for (int i = 0; i < nstep; ++i) {
-        const int t = c * TC + i;
-        const float eb = eb_n;
-        float el[P];
-#pragma unroll
-        for (int p = 0; p < P; ++p) el[p] = el_n[p];
-        const int i1 = i + 1 < TC ? i + 1 : TC - 1;
-        float x0 = __shfl_up(O[P - 1], 1, 64);   // the neighbouring lane's last label state
-        if (lane == 0) x0 = NEGINF;
-        eb_n = src[i1 * LD + 64 * P];
-#pragma unroll
-        for (int p = 0; p < P; ++p) el_n[p] = src[i1 * LD + p * 64 + lane];
-        float nE[P], nO[P];
-        unsigned long long choice = 0;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-          float mE, mO;
-          const unsigned k = ctc_vit_pair(E[p], O[p], (p == 0) ? x0 : O[p == 0 ? 0 : p - 1], skip[p], mE, mO);
-          choice |= (unsigned long long)k << (8 * p);
-          nE[p] = vE[p] ? mE + eb : NEGINF;
-          nO[p] = vO[p] ? mO + el[p] : NEGINF;
-        }
-        if (t == 0) {  // (wave-uniform) states 0 and 1
-#pragma unroll
-          for (int p = 0; p < P; ++p) {
-            const int g = lane * P + p;
-            nE[p] = (g == 0) ? eb : NEGINF;
-            nO[p] = (vO[p] && g == 0) ? el[p] : NEGINF;
-          }
-        }
-#pragma unroll
-        for (int p = 0; p < P; ++p) { E[p] = nE[p]; O[p] = nO[p]; }
-        if (lane * P <= U)   // (row 0 is never read; lane*P + P <= RS: both are multiples of P and lane*P <= Umax < RS)
-          *reinterpret_cast<typename CtcBytes<P>::t*>(bp + (long long)t * RS + lane * P) = (typename CtcBytes<P>::t)choice;
-      }
-    }
-    __syncthreads();   // chunk c + 1 is in LDS; the walker is done with chunk c's half
-  }
-  unsigned* s_bp = reinterpret_cast<unsigned*>(s_e[0]);
-  int* s_path = reinterpret_cast<int*>(s_e[0]) + CTC_BT * CTC_BT_LD;
-  if (!loader) {   // the last row: states S-1 = E_U and S-2 = O_{U-1}
-    float eU = NEGINF, oU = NEGINF;
+  ctc_wave_chunks<P, false, false>(lp, q.cls, T, C, blank, s_e, [&](int t, float eb, const float (&el)[P]) {
+    float x0 = __shfl_up(O[P - 1], 1, 64);   // the neighbouring lane's last label state
+    if (lane == 0) x0 = NEGINF;
+    float nE[P], nO[P];
+    unsigned long long choice = 0;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-      const int g = lane * P + p;
-      if (g == U) eU = E[p];
-      if (g == U - 1) oU = O[p];
+      float mE, mO;
+      const unsigned k = ctc_vit_pair(E[p], O[p], (p == 0) ? x0 : O[p == 0 ? 0 : p - 1], q.skip[p], mE, mO);
+      choice |= (unsigned long long)k << (8 * p);
+      nE[p] = q.vE[p] ? mE + eb : NEGINF;
+      nO[p] = q.vO[p] ? mO + el[p] : NEGINF;
     }
-    const float l1 = __shfl(eU, U / P, 64);
-    const float l2 = (U >= 1) ? __shfl(oU, (U - 1) / P, 64) : NEGINF;
+    if (t == 0) {  // (wave-uniform) states 0 and 1
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int g = lane * P + p;
+        nE[p] = (g == 0) ? eb : NEGINF;
+        nO[p] = (q.vO[p] && g == 0) ? el[p] : NEGINF;
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) { E[p] = nE[p]; O[p] = nO[p]; }
+    if (lane * P <= U)   // (row 0 is never read; lane*P + P <= RS: both are multiples of P and lane*P <= Umax < RS)
+      *reinterpret_cast<typename CtcBytes<P>::t*>(bp + (long long)t * RS + lane * P) = (typename CtcBytes<P>::t)choice;
+  });
+  unsigned* s_bp = reinterpret_cast<unsigned*>(s_e[0]);
+  int* s_path = reinterpret_cast<int*>(s_e[0]) + CTC_BT * CTC_BT_LD;
+  if (threadIdx.x < 64) {   // the last row: the better of states S-1 and S-2
+    float l1, l2;
+    ctc_wave_last_row<P>(E, O, U, l1, l2);
     if (lane == 0) {
       const bool lab = l2 > l1;
       const float sc = lab ? l2 : l1;
@@ -967,19 +864,14 @@ extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const voi
   if (B <= 0 || Tmax <= 0 || C <= 0 || Umax <= 0 || blank < 0 || blank >= C) return MI_ERR_ARG;
   if (Umax > 2048 || ((size_t)bp_ws & 7)) return MI_ERR_ARG;   // S = 2 Umax + 1 <= 4097 (CTC_ALIGN_NG pairs per thread)
   const int Smax = 2 * Umax + 1, RS = (Umax + 8) & ~7;
-  if (g_ctc_align_wave < 0) {
-    const char* e = getenv("MI355X_CTC_ALIGN_WAVE");
-    g_ctc_align_wave = (e && e[0] == '0') ? 0 : 1;
-  }
-#define CTC_ALIGN_LAUNCH(kernel, threads, shm)                                                                                      \
-  MI_LAUNCH(kernel, dim3(B), dim3(threads), shm, (hipStream_t)stream, (const float*)logp, (const long long*)targets,                 \
+#define CTC_ALIGN(kernel, threads, lds)                                                                                            \
+  MI_LAUNCH(kernel, dim3(B), dim3(threads), lds, (hipStream_t)stream, (const float*)logp, (const long long*)targets,                 \
             (const long long*)in_len, (const long long*)tgt_len, (unsigned char*)bp_ws, (int*)path, (int*)tok_start, (int*)tok_end,  \
             (float*)score, Tmax, C, Umax, RS, blank)
-  if (g_ctc_align_wave && Smax <= 128) CTC_ALIGN_LAUNCH(ctc_align_wave_kernel<1>, 128, 0);
-  else if (g_ctc_align_wave && Smax <= 256) CTC_ALIGN_LAUNCH(ctc_align_wave_kernel<2>, 128, 0);
-  else if (g_ctc_align_wave && Smax <= 512) CTC_ALIGN_LAUNCH(ctc_align_wave_kernel<4>, 128, 0);
-  else if (g_ctc_align_wave && Smax <= 1024) CTC_ALIGN_LAUNCH(ctc_align_wave_kernel<8>, 128, 0);
-  else CTC_ALIGN_LAUNCH(ctc_align_kernel, 256, sizeof(float) * (size_t)(ctc_align_lds_rows(Umax) + CTC_BT * CTC_BT_LD + CTC_BT + 1));
-#undef CTC_ALIGN_LAUNCH
+#define CTC_WAVE(PP) CTC_ALIGN(ctc_align_wave_kernel<PP>, 128, 0)
+  CTC_DISPATCH(ctc_wave_pairs(ctc_knob(g_ctc_align_wave, "MI355X_CTC_ALIGN_WAVE"), Smax), CTC_WAVE,
+               CTC_ALIGN(ctc_align_kernel, 256, sizeof(float) * (size_t)(ctc_align_lds_rows(Umax) + CTC_BT * CTC_BT_LD + CTC_BT + 1)))
+#undef CTC_WAVE
+#undef CTC_ALIGN
   return mi_check_launch();
 }

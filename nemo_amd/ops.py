@@ -430,27 +430,33 @@ def qbias(qkv, ldq, u, v, qu, qv, M, d):
     check(lib.mi355x_qbias(_ptr(qkv), ldq, _ptr(u), _ptr(v), _ptr(qu), _ptr(qv), dt(qkv), M, d, _stream()), "qbias")
 
 
+def _ctc_greedy(level, logp, lens, blank, *conf_args):
+    """one call of the greedy CTC entry of `level` (0: tokens, 1: and frames, 2: and confidences, `conf_args` = what that entry takes
+    behind `blank`): allocates the level's outputs -> (tokens, out_len, score[, tok_start, tok_end[, frame_conf, tok_conf]])"""
+    entry, name = {0: (lib.mi355x_ctc_greedy_decode, "ctc_greedy_decode"), 1: (lib.mi355x_ctc_greedy_decode_ts, "ctc_greedy_decode_ts"),
+                   2: (lib.mi355x_ctc_greedy_decode_conf, "ctc_greedy_decode_conf")}[level]
+    B, T, C_ = logp.shape
+    i32, f32 = (dict(dtype=d, device=logp.device) for d in (torch.int32, torch.float32))
+    tokens, out_len, score = torch.empty(B, T, **i32), torch.empty(B, **i32), torch.empty(B, **f32)
+    extra = []   # what the level adds behind `score`
+    if level >= 1:
+        extra += [torch.empty(B, T, **i32), torch.empty(B, T, **i32)]   # tok_start, tok_end
+    if level >= 2:
+        extra += [torch.empty(B, T, **f32), torch.empty(B, T, **f32)]   # frame_conf, tok_conf
+    check(entry(_ptr(logp), _ptr(lens), _ptr(tokens), _ptr(out_len), _ptr(score), *[_ptr(t) for t in extra], B, T, C_, blank,
+                *conf_args, _stream()), name)
+    return (tokens, out_len, score, *extra)
+
+
 def ctc_greedy_decode(logp, lens, blank):
     """logp f32 [B,T,C] -> (tokens i32 [B,T] folded / blank-free / -1 padded, out_len i32 [B], score f32 [B])"""
-    B, T, C_ = logp.shape
-    tokens = torch.empty(B, T, dtype=torch.int32, device=logp.device)
-    out_len = torch.empty(B, dtype=torch.int32, device=logp.device)
-    score = torch.empty(B, dtype=torch.float32, device=logp.device)
-    check(lib.mi355x_ctc_greedy_decode(_ptr(logp), _ptr(lens), _ptr(tokens), _ptr(out_len), _ptr(score), B, T, C_, blank,
-                                       _stream()), "ctc_greedy_decode")
-    return tokens, out_len, score
+    return _ctc_greedy(0, logp, lens, blank)
 
 
 def ctc_greedy_decode_ts(logp, lens, blank):
     """ctc_greedy_decode plus the frames: -> (tokens, out_len, score, tok_start i32 [B,T], tok_end i32 [B,T]); start / end = first /
     last frame of the run of equal arg-max labels behind each kept token, -1 padded"""
-    B, T, C_ = logp.shape
-    tokens, tok_start, tok_end = (torch.empty(B, T, dtype=torch.int32, device=logp.device) for _ in range(3))
-    out_len = torch.empty(B, dtype=torch.int32, device=logp.device)
-    score = torch.empty(B, dtype=torch.float32, device=logp.device)
-    check(lib.mi355x_ctc_greedy_decode_ts(_ptr(logp), _ptr(lens), _ptr(tokens), _ptr(out_len), _ptr(score), _ptr(tok_start),
-                                          _ptr(tok_end), B, T, C_, blank, _stream()), "ctc_greedy_decode_ts")
-    return tokens, out_len, score, tok_start, tok_end
+    return _ctc_greedy(1, logp, lens, blank)
 
 
 def ctc_greedy_decode_conf(logp, lens, blank, method, aggregation=1, exclude_blank=True):
@@ -458,15 +464,7 @@ def ctc_greedy_decode_conf(logp, lens, blank, method, aggregation=1, exclude_bla
     V = C (modules.confidence.ConfidenceMethodConfig.kernel_args), aggregation 0..3 = mean / min / max / prod -> (tokens, out_len,
     score, tok_start, tok_end, frame_conf f32 [B,T]: 0.0 beyond the utterance, tok_conf f32 [B,T]: the aggregation of frame_conf
     over each token's frames (exclude_blank: its own run; else from behind the previous token's run), 0.0 padded)"""
-    B, T, C_ = logp.shape
-    tokens, tok_start, tok_end = (torch.empty(B, T, dtype=torch.int32, device=logp.device) for _ in range(3))
-    out_len = torch.empty(B, dtype=torch.int32, device=logp.device)
-    score = torch.empty(B, dtype=torch.float32, device=logp.device)
-    frame_conf, tok_conf = (torch.empty(B, T, dtype=torch.float32, device=logp.device) for _ in range(2))
-    check(lib.mi355x_ctc_greedy_decode_conf(_ptr(logp), _ptr(lens), _ptr(tokens), _ptr(out_len), _ptr(score), _ptr(tok_start),
-                                            _ptr(tok_end), _ptr(frame_conf), _ptr(tok_conf), B, T, C_, blank, *method,
-                                            int(aggregation), int(bool(exclude_blank)), _stream()), "ctc_greedy_decode_conf")
-    return tokens, out_len, score, tok_start, tok_end, frame_conf, tok_conf
+    return _ctc_greedy(2, logp, lens, blank, *method, int(aggregation), int(bool(exclude_blank)))
 
 
 def ctc_align(logp, targets, in_len, tgt_len, blank):

@@ -3,7 +3,8 @@
 // nemo/collections/asr/parts/submodules/subsampling.py:142-215 (each further factor of 2 is
 // Conv2d(C, C, 3, stride 2, padding 1, groups=C) -> Conv2d(C, C, 1) -> ReLU under MaskedConvSequential :725-759).
 //   in  [B, T1, F1, C]  (ReLU'd and time-masked output of the previous stage)
-//   out [B, T2, F2, C]  = depthwise(in) + bias,  T2 = (T1 - 1)/2 + 1, F2 = (F1 - 1)/2 + 1
+//   out [B, T2, F2, C]  = depthwise(in) + bias,  T2 = (T1 + pad - 2)/2 + 1, F2 = (F1 + pad - 2)/2 + 1
+// with `pad` zero rows / columns in front of the grid (1: padding = 1, 2: CausalConv2D) and one behind it.
 // The pointwise 1x1 convolution that follows is an MFMA GEMM on [B*T2*F2, C] with the ReLU + time-mask epilogue
 // (mi355x_gemm, EPI_RELU_MASK), so the mask between the two convolutions needs no pass of its own.
 // All three kernels are HBM-bound streams: lane = 8 (bf16) / 4 (f32) consecutive channels = one 16-byte access per tap;
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_fwd_kernel(const TT* __restri
   }
 }
 
-// din[b,t1,f1,c] = (in > 0) * sum over the outputs (t2, f2) that read (t1, f1):  t1 = 2 t2 - 1 + kh  <=>  kh = t1 + 1 - 2 t2
+// din[b,t1,f1,c] = (in > 0) * sum over the outputs (t2, f2) that read (t1, f1):  t1 = 2 t2 - pad + kh  <=>  kh = t1 + pad - 2 t2
 template <typename TT, typename IDX>
 __global__ __launch_bounds__(256) void dwconv2d_s2_bwd_data_kernel(const TT* __restrict__ dout, const TT* __restrict__ in,
                                                                    const float* __restrict__ w, TT* __restrict__ din, int B, int T1,
@@ -86,7 +87,8 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_bwd_data_kernel(const TT* __r
     float acc[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) acc[j] = 0.f;
-    // kh = t1 + 1 - 2 t2 in {0,1,2}: an even t1 is read through kh = 1 only, an odd one through kh = 0 (t2 = (t1+1)/2) and 2
+    // kh = t1 + pad - 2 t2 in {0,1,2}: when t1 + pad is odd the row is read through kh = 1 only, when it is even through
+    // kh = 0 (t2 = (t1 + pad)/2) and kh = 2 (t2 = (t1 + pad)/2 - 1); the same along frequency: at most 2 x 2 taps
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh) {
       const int tt = t1 + pad - kh;

@@ -16,7 +16,7 @@
 
 
 // ------------------------------------------------------------------------------------------------ conv1 forward
-// grid (ceil(F1/8), T1, B); 256 threads over channels
+// grid (ceil(T1/C1_TR), B); 256 threads = C/V channel chunks x 256/(C/V) f1 positions in flight
 #define C1_TR 4  // output rows (t1) per block
 template <typename TO>
 __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict__ mel, const float* __restrict__ w,
@@ -81,8 +81,8 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
 
 // ------------------------------------------------------------------------------------------------ conv1 backward (params only)
 // dout1 [B,T1,F1,C] (already gated by ReLU and masks) : dw[c,kh,kw] += sum dout1 * x ; db[c] += sum dout1
-// grid (ceil(T1/16), B); threads over channels; each block walks 16 t1 x all f1
-#define C1_TB 32
+// grid (ceil(T1/C1_TB), B); lanes over channel chunks, waves over rows; each block walks C1_TB t1 x all f1
+#define C1_TB 32  // output rows (t1) per block
 template <typename TO>
 __global__ __launch_bounds__(256) void conv1_bwd_kernel(const TO* __restrict__ dout, const float* __restrict__ mel,
                                                         const long long* __restrict__ len0, float* __restrict__ dw,
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const TO* __restrict__ d
   }
 }
 
-// ------------------------------------------------------------------------------------------------ im2col / col2im (3x3, s2, p1)
+// ------------------------------------------------------------------------------------------------ im2col / col2im (3x3, s2, pads (pad, 1))
 // in [B,T1,F1,C] -> col [(b,t2,f2), (kh,kw,ci)]; one thread = one 8-channel (or 4 for f32) vector
 template <typename TT>
 __global__ __launch_bounds__(256) void im2col_kernel(const TT* __restrict__ in, TT* __restrict__ col, int B, int T1, int F1,

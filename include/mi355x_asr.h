@@ -637,6 +637,36 @@ int mi355x_ctc_align(const void* logp, const void* targets, const void* in_len, 
  * 2*Umax+1 <= 1024, 0 = the LDS / barrier form for every size.  Returns the previous setting (-1: not yet resolved). */
 int mi355x_ctc_align_config(int wave);
 
+/* CTC prefix beam search without a language model (the `beam_batch` strategy), one launch per batch, utterances independent.
+ * logp f32 [B,Tmax,C] log-probabilities (-inf entries allowed; rows beyond lens[b] are never read); lens i64 [B].
+ * A beam = a prefix (a node (parent node, token) of a prefix tree), its length len, pb / pnb = log-probability of its alignments
+ * that end in blank / in a non-blank, tot = logaddexp(pb, pnb).  Start: the empty prefix, pb = 0, pnb = -inf.  Per frame t:
+ *   1. mx = max_c lp[t,c]; class c (blank included) is considered iff lp[t,c] >= mx - threshold (float32 subtract and compare)
+ *   2. for every beam i with last token l_i (none for the empty prefix) and every considered c:
+ *        c == blank : stay(i).pb  (+)= tot_i + lp[c]
+ *        c == l_i   : stay(i).pnb (+)= pnb_i + lp[c]   and   ext(i,c).pnb (+)= pb_i + lp[c]
+ *        otherwise  : ext(i,c).pnb (+)= tot_i + lp[c]                                   ((+) = log-add-exp)
+ *   3. ext(i,c) IS stay(j) where beam j of the set holds the prefix of i followed by c: one candidate, contributions merged
+ *   4. candidates with tot = -inf are dropped; the new set = the `beam` candidates of the largest rank = tot + beta * len.
+ *      Order: (rank descending, key ascending), key = i for stay(i), beam + i*C + c for ext(i,c), i = slot of the beam in the
+ *      ordered set of the previous frame -- a total order, so ties of rank are decided the same way on every run
+ *   5. a kept extension in slot s becomes node 1 + t*beam + s (node 0 = the empty prefix) and stores (parent, token) at
+ *      node_ws[2*(t*beam + s)]; a stay keeps its node.  The frame a token was created in is (node - 1) / beam.
+ * Plain float32: logaddexp(a,b) = max + log1pf(expf(-|a-b|)), -inf handled; beta * len is rounded before it is added.
+ *   tokens    i32 [B,beam,Tmax]  hypotheses in order, best first; -1 padded
+ *   tok_frame i32 [B,beam,Tmax]  frame at which each token's node was created; -1 padded
+ *   hyp_len   i32 [B,beam]       0 for absent hypotheses
+ *   score     f32 [B,beam]       rank; -inf for absent hypotheses
+ *   n_hyp     i32 [B]            number of hypotheses (< beam when the utterance is short); lens[b] = 0: one empty hypothesis, score 0
+ *   node_ws   i32, 8-byte aligned, B * mi355x_ctc_beam_workspace_elems(Tmax, beam) elements (= 2 * Tmax * beam per utterance)
+ * MI_ERR_ARG for null pointers, non-positive sizes, beam outside 1..64, blank outside [0, C), threshold <= 0 or NaN (+inf = no
+ * pruning), NaN beta, C > 8192 (two rows of C floats in LDS; nothing in LDS grows with beam). */
+int mi355x_ctc_beam_decode(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
+                           void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta,
+                           void* stream);
+/* i32 elements of node_ws per utterance; 0 for arguments mi355x_ctc_beam_decode rejects */
+long long mi355x_ctc_beam_workspace_elems(int Tmax, int beam);
+
 /* SpectrogramAugmentation (nemo/collections/asr/modules/audio_preprocessing.py:443-553; SpecAugment._apply_masks
  * parts/submodules/spectr_augment.py:153-215, SpecCutout.forward :245-261): x[b, f0:f1, t0:t1] = value for n rectangles
  * rects[n][5] = (b, f0, f1, t0, t1) (int32, device memory; clipped to the tensor).  x: f32 [B, F, T], in place. */

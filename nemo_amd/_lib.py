@@ -124,6 +124,8 @@ SIGNATURES = {
     "mi355x_ctc_greedy_decode_ts": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "mi355x_ctc_greedy_decode_conf": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, i32, i32, vp],
     "mi355x_ctc_align": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "mi355x_ctc_beam_decode": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp],
+    "mi355x_ctc_beam_workspace_elems": [i32, i32],
     "mi355x_fill_rects": [vp, vp, i32, i32, i32, i32, f32, vp],
     "mi355x_specaug_rects": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp],
     "mi355x_add2_colsum": [vp, vp, vp, i64, i64, i32, vp, vp, i64, vp],
@@ -226,6 +228,7 @@ def _load():
     lib.mi355x_asr_version.restype = C.c_char_p
     lib.mi355x_relpos_ds_elems.restype = i64
     lib.mi355x_relpos_dpos_partial_elems.restype = i64
+    lib.mi355x_ctc_beam_workspace_elems.restype = i64
     lib.mi355x_asr_version.argtypes = []
     lib.mi355x_tape_destroy.restype = None
     lib.mi355x_mailbox_destroy.restype = None

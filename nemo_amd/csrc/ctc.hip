@@ -875,3 +875,252 @@ extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const voi
 #undef CTC_ALIGN
   return mi_check_launch();
 }
+
+// ------------------------------------------------------------------------------------------------ CTC prefix beam search
+// The classic CTC prefix beam search (the `beam_batch` strategy; no language model), ONE launch per batch, one wave per utterance,
+// a lane per beam: the whole search state of an utterance lives in the registers of its wave, so the frame loop has no workgroup
+// barrier, and nothing of size [B, T, C] leaves the device.  include/mi355x_asr.h states the search; in short, per frame:
+//   token pruning   c is considered iff lp[t,c] >= max_c lp[t,c] - threshold (float32 subtract and compare)
+//   stays           stay(i).pb = tot_i + lp[blank] ; stay(i).pnb = pnb_i + lp[last_i]
+//   extensions      ext(i,c).pnb = (c == last_i ? pb_i : tot_i) + lp[c] ; where the prefix of ext(i,c) is the prefix of a beam j of
+//                   the current set, the value is added (log-add-exp) to stay(j).pnb instead: the two are ONE candidate
+//   selection       the `beam` candidates of the largest rank = tot + beta * len, tot = logaddexp(pb, pnb) > -inf
+// A beam is a node of a prefix tree.  Node 0 is the empty prefix; the extension kept in slot s of frame t becomes node
+// 1 + t*beam + s and stores (parent node, token) at node_ws[t*beam + s], so the frame a token was created in is (node - 1) / beam.
+// Which beam an extension would duplicate: a beam carries a 64-bit hash of its prefix and of its parent's prefix; equal hash and
+// length name the candidate, and the two parent chains are then compared node by node (no load at all where the beam's parent IS
+// the extended beam's node, which is the rule; a walk only where a prefix fell out of the set and came back under a new node while
+// one of its children stayed).  A hash alone never merges anything.
+// Candidate streaming: a frame has up to beam * (C - 1) + beam candidates (65k at C = 1025, beam = 64).  They are never stored:
+// lanes 0 .. beam-1 hold a running top-`beam` (rank, key, value) IN ORDER, initialised with the sorted stays; the extensions of one
+// beam are formed 64 classes at a time, a ballot keeps those that beat the last entry, and each of them is inserted at its place:
+// a ballot counts the entries in front of it, the entries behind move one lane up (a DPP wave shift, no LDS) and the last one falls
+// off.  The bar is the entry in lane beam-1.  A beam whose best possible extension (tot_i + max_c lp) does not beat it is skipped
+// whole; the beams are in order, so the bar rises early, and at the end of the frame lane s holds slot s: nothing is sorted again.
+// LDS holds two rows of log-probabilities only: see the launcher.
+// Ties: candidates are ordered by (rank descending, key ascending), key = i for stay(i) and beam + i*C + c for ext(i,c), i the slot
+// of the beam in the sorted set of the previous frame; the order is total, so selection and output order are deterministic.
+// Arithmetic: plain float32, logaddexp(a,b) = max + log1pf(expf(-|a-b|)); beta * len is rounded on its own (no fused multiply-add).
+#define CTC_BEAM_MAX 64
+#define CTC_BEAM_ROOT_HASH 0x243F6A8885A308D3ull
+__device__ __forceinline__ float ctc_lae(float a, float b) {
+  const float m = fmaxf(a, b);
+  return (m == NEGINF) ? NEGINF : m + log1pf(expf(-fabsf(a - b)));
+}
+__device__ __forceinline__ float ctc_beam_bonus(float beta, int len) {
+  float bl = beta * (float)len;
+  asm volatile("" : "+v"(bl));   // the product is rounded before it is added to anything
+  return bl;
+}
+__device__ __forceinline__ float ctc_beam_rank(float tot, float beta, int len) { return tot + ctc_beam_bonus(beta, len); }
+__device__ __forceinline__ unsigned long long ctc_beam_hash(unsigned long long h, int c) {
+  h = (h ^ (unsigned long long)(c + 1)) * 0x9E3779B97F4A7C15ull;
+  return h ^ (h >> 29);
+}
+__device__ __forceinline__ int ctc_rl(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ float ctc_rlf(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+__device__ __forceinline__ int ctc_push(int v, int dst) { return __builtin_amdgcn_ds_permute(dst << 2, v); }
+__device__ __forceinline__ float ctc_pushf(float v, int dst) { return __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(v))); }
+// lane l <- lane l-1 over the whole wave (DPP wave_shr:1); lane 0 keeps its value
+__device__ __forceinline__ int ctc_up1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ float ctc_up1f(float v) { return __int_as_float(ctc_up1(__float_as_int(v))); }
+// candidate (r, k) goes in front of (wr, wk)
+__device__ __forceinline__ bool ctc_beam_beats(float r, int k, float wr, int wk) { return r > wr || (r == wr && k < wk); }
+// are the prefixes of nodes a and b the same sequence (they have the same length)?
+__device__ __forceinline__ bool ctc_beam_same_prefix(const int2* ws, int a, int b) {
+  while (a != b) {
+    if (a <= 0 || b <= 0) return false;
+    const int2 ea = ws[a - 1], eb = ws[b - 1];
+    if (ea.y != eb.y) return false;
+    a = ea.x; b = eb.x;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ logp, const long long* __restrict__ lens, int2* node_ws,
+                                                      int* __restrict__ tokens, int* __restrict__ tok_frame, int* __restrict__ hyp_len,
+                                                      float* __restrict__ score, int* __restrict__ n_hyp, int Tmax, int C, int blank,
+                                                      int W, float theta, float beta) {
+  extern __shared__ float s_rows[];   // [2][C]: the log-probabilities of this frame and of the next
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int T = (int)max(0ll, min((long long)Tmax, lens ? lens[b] : (long long)Tmax));
+  const float* lp = logp + (long long)b * Tmax * C;
+  int2* ws = node_ws + (long long)b * Tmax * W;
+  const int G = (C + 63) >> 6;
+  // the beam of this lane (lanes < nb are live, sorted by rank)
+  int node = 0, par = -1, tok = -1, len = 0;
+  unsigned long long h = CTC_BEAM_ROOT_HASH, hp = 0;
+  float pb = lane == 0 ? 0.f : NEGINF, pnb = NEGINF, tot = pb, brank = pb;
+  int nb = 1;
+  if (T > 0)
+    for (int c = lane; c < C; c += 64) s_rows[c] = lp[c];
+  for (int t = 0; t < T; ++t) {
+    const float* row = s_rows + (t & 1) * C;
+    float* nrow = s_rows + ((t + 1) & 1) * C;
+    const bool more = t + 1 < T;   // (rows beyond the utterance are never read: they may hold anything)
+    const float* nlp = lp + (long long)(t + 1) * C;
+    float nx[4];   // the first 256 classes of the next row are requested here and stored to LDS behind the scan
+#pragma unroll
+    for (int k = 0; k < 4; ++k) nx[k] = (more && k * 64 + lane < C) ? nlp[k * 64 + lane] : 0.f;
+    float mx = NEGINF;
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
+    mx = wave_max(mx);
+    const float lo = mx - theta;
+    const bool live = lane < nb;
+    // ---- stays, with the extensions that land on them
+    const float vb = row[blank];
+    const float vl = (live && tok >= 0) ? row[tok] : NEGINF;
+    const bool okl = live && tok >= 0 && vl >= lo;
+    float spb = (live && vb >= lo) ? tot + vb : NEGINF;
+    float spnb = okl ? pnb + vl : NEGINF;
+    int pl = -1;   // the slot of the beam whose extension by `tok` is this beam
+    for (int i = 0; i < nb; ++i) {
+      const int hl = ctc_rl((int)(unsigned)h, i), hh = ctc_rl((int)(unsigned)(h >> 32), i), li = ctc_rl(len, i), ni = ctc_rl(node, i);
+      if (live && pl < 0 && len == li + 1 && (int)(unsigned)hp == hl && (int)(unsigned)(hp >> 32) == hh && ctc_beam_same_prefix(ws, par, ni))
+        pl = i;
+    }
+    {
+      const int src = pl >= 0 ? pl : lane;
+      const int tok_p = __shfl(tok, src, 64);
+      const float pb_p = __shfl(pb, src, 64), tot_p = __shfl(tot, src, 64);
+      if (pl >= 0 && okl) spnb = ctc_lae(spnb, ((tok == tok_p) ? pb_p : tot_p) + vl);
+    }
+    const float stot = ctc_lae(spb, spnb);
+    // ---- the running top-W in lanes 0 .. W-1, in order: seeded with the stays (empty places: rank -inf and a key behind every
+    // candidate's, each its own, so that the order is total); lanes beyond W carry along what is shifted out and are never read
+    float e_rank = NEGINF, e_val = NEGINF;
+    int e_key = 0x7fffffff - lane;
+    if (live && stot != NEGINF) { e_rank = ctc_beam_rank(stot, beta, len); e_key = lane; }
+    {
+      int pos = 0;
+      for (int j = 0; j < W; ++j) pos += ctc_beam_beats(ctc_rlf(e_rank, j), ctc_rl(e_key, j), e_rank, e_key) ? 1 : 0;
+      if (lane >= W) pos = lane;
+      e_rank = ctc_pushf(e_rank, pos); e_key = ctc_push(e_key, pos);
+    }
+    const unsigned long long wmask = W == 64 ? ~0ull : (1ull << W) - 1ull;
+    float wr = ctc_rlf(e_rank, W - 1);   // the bar: the last entry
+    int wk = ctc_rl(e_key, W - 1);
+    // ---- extensions, streamed.  The bar only rises, and float32 rounding is monotone, so what cannot beat the bar of the stays is
+    // out for the whole frame: a beam whose best possible extension (tot_i + mx) ranks below it, and a class whose extension of the
+    // best possible beam (the largest tot, the largest bonus) does -- a group of 64 classes with no other class is never read again.
+    const unsigned long long beams = __ballot(live && !(ctc_beam_rank(tot + mx, beta, len + 1) < wr));
+    const float tmax = wave_max(live ? tot : NEGINF), blmax = wave_max(live ? ctc_beam_bonus(beta, len + 1) : NEGINF);
+    unsigned long long groups[2] = {0ull, 0ull};   // (G <= 128: the launcher's LDS rule)
+    for (int g = 0; g < G; ++g) {
+      const int c = g * 64 + lane;
+      const float v = c < C ? row[c] : NEGINF;
+      if (__ballot(c < C && c != blank && v >= lo && !((tmax + v) + blmax < wr))) groups[g >> 6] |= 1ull << (g & 63);
+    }
+    for (unsigned long long bm = beams; bm; bm &= bm - 1) {
+      const int i = __ffsll((long long)bm) - 1;
+      const int tok_i = ctc_rl(tok, i), len_i = ctc_rl(len, i);
+      const float pb_i = ctc_rlf(pb, i), tot_i = ctc_rlf(tot, i);
+      if (ctc_beam_rank(tot_i + mx, beta, len_i + 1) < wr) continue;   // (the bar has risen)
+      const unsigned long long kids = __ballot(live && pl == i);
+      for (int hw = 0; hw < 2; ++hw)
+      for (unsigned long long gm = groups[hw]; gm; gm &= gm - 1) {
+        const int c = (hw * 64 + __ffsll((long long)gm) - 1) * 64 + lane;
+        const float v = c < C ? row[c] : NEGINF;
+        bool ok = c < C && c != blank && v >= lo;
+        for (unsigned long long m = kids; m; m &= m - 1)
+          if (c == ctc_rl(tok, __ffsll((long long)m) - 1)) ok = false;   // this extension is the stay of a beam of the set
+        const float val = ((c == tok_i) ? pb_i : tot_i) + v;
+        const float rank = ctc_beam_rank(val, beta, len_i + 1);
+        const int key = W + i * C + c;
+        for (unsigned long long m = __ballot(ok && val != NEGINF && ctc_beam_beats(rank, key, wr, wk)); m; m &= m - 1) {
+          const int l = __ffsll((long long)m) - 1;
+          const float r = ctc_rlf(rank, l);
+          const int k = ctc_rl(key, l);
+          if (!ctc_beam_beats(r, k, wr, wk)) continue;   // (the bar has risen since the ballot)
+          const float vv = ctc_rlf(val, l);
+          const int at = __popcll(__ballot(ctc_beam_beats(e_rank, e_key, r, k)) & wmask);   // the entries in front of it
+          const float u_rank = ctc_up1f(e_rank), u_val = ctc_up1f(e_val);
+          const int u_key = ctc_up1(e_key);
+          if (lane > at) { e_rank = u_rank; e_key = u_key; e_val = u_val; }
+          else if (lane == at) { e_rank = r; e_key = k; e_val = vv; }
+          wr = ctc_rlf(e_rank, W - 1); wk = ctc_rl(e_key, W - 1);
+        }
+      }
+    }
+    // ---- the new set: the entry of lane s is slot s; it fetches the beam it comes from and becomes the beam of its lane
+    const bool keep = lane < W && e_rank != NEGINF;
+    const bool is_ext = keep && e_key >= W;
+    const int src = !keep ? lane : is_ext ? (e_key - W) / C : e_key;
+    const int c_new = is_ext ? (e_key - W) - src * C : -1;
+    const int node_s = __shfl(node, src, 64), par_s = __shfl(par, src, 64), tok_s = __shfl(tok, src, 64), len_s = __shfl(len, src, 64);
+    const unsigned long long h_s = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(h >> 32), src, 64) << 32) |
+                                   (unsigned)__shfl((int)(unsigned)h, src, 64);
+    const unsigned long long hp_s = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(hp >> 32), src, 64) << 32) |
+                                    (unsigned)__shfl((int)(unsigned)hp, src, 64);
+    const float spb_s = __shfl(spb, src, 64), spnb_s = __shfl(spnb, src, 64), stot_s = __shfl(stot, src, 64);
+    const int pos = lane;
+    int n_node = 0, n_par = -1, n_tok = -1, n_len = 0;
+    unsigned long long n_h = CTC_BEAM_ROOT_HASH, n_hp = 0;
+    float n_pb = NEGINF, n_pnb = NEGINF, n_tot = NEGINF;
+    if (is_ext) {
+      n_node = 1 + t * W + pos; n_par = node_s; n_tok = c_new; n_len = len_s + 1;
+      n_h = ctc_beam_hash(h_s, c_new); n_hp = h_s;
+      n_pnb = e_val; n_tot = e_val;
+      ws[t * W + pos] = make_int2(n_par, n_tok);
+    } else if (keep) {
+      n_node = node_s; n_par = par_s; n_tok = tok_s; n_len = len_s; n_h = h_s; n_hp = hp_s;
+      n_pb = spb_s; n_pnb = spnb_s; n_tot = stot_s;
+    }
+    node = n_node; par = n_par; tok = n_tok; len = n_len; h = n_h; hp = n_hp;
+    pb = n_pb; pnb = n_pnb; tot = n_tot;
+    brank = keep ? e_rank : NEGINF;
+    nb = __popcll(__ballot(keep));
+    // ---- the next row
+    if (more) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k * 64 + lane < C) nrow[k * 64 + lane] = nx[k];
+      for (int c = 256 + lane; c < C; c += 64) nrow[c] = nlp[c];
+    }
+    __threadfence_block();   // the node stores of this frame are visible to the lanes that chase them
+    __syncthreads();
+  }
+  // ---- output: the beams are in order; a lane per hypothesis chases its parents, tokens from position len-1 downward
+  int* tk = tokens + (long long)b * W * Tmax;
+  int* tf = tok_frame + (long long)b * W * Tmax;
+  for (int j = 0; j < W; ++j) {   // padding, by the whole wave
+    const int lj = j < nb ? ctc_rl(len, j) : 0;
+    for (int p = lj + lane; p < Tmax; p += 64) { tk[(long long)j * Tmax + p] = -1; tf[(long long)j * Tmax + p] = -1; }
+  }
+  if (lane < W) {
+    const bool live = lane < nb;
+    hyp_len[b * W + lane] = live ? len : 0;
+    score[b * W + lane] = live ? brank : NEGINF;
+    if (live) {
+      int id = node;
+      for (int p = len - 1; p >= 0 && id > 0; --p) {
+        const int2 e = ws[id - 1];
+        tk[(long long)lane * Tmax + p] = e.y;
+        tf[(long long)lane * Tmax + p] = (id - 1) / W;
+        id = e.x;
+      }
+    }
+  }
+  if (lane == 0) n_hyp[b] = nb;
+}
+
+extern "C" long long mi355x_ctc_beam_workspace_elems(int Tmax, int beam) {
+  return (Tmax <= 0 || beam < 1 || beam > CTC_BEAM_MAX) ? 0 : 2ll * Tmax * beam;
+}
+
+// LDS rule: two rows of log-probabilities (this frame's and the next one's), 8 C bytes <= 64 KB, i.e. C <= 8192, whatever the beam
+// width: the candidates of a frame are streamed against the running top-`beam` in registers and never stored.
+extern "C" int mi355x_ctc_beam_decode(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
+                                      void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold,
+                                      float beta, void* stream) {
+  mi_clear_errors();
+  if (!logp || !lens || !node_ws || !tokens || !tok_frame || !hyp_len || !score || !n_hyp) return MI_ERR_ARG;
+  if (B <= 0 || Tmax <= 0 || C <= 0 || blank < 0 || blank >= C || beam < 1 || beam > CTC_BEAM_MAX) return MI_ERR_ARG;
+  if (!(threshold > 0.f) || beta != beta || ((size_t)node_ws & 7)) return MI_ERR_ARG;   // (NaN fails the first compare)
+  if ((long long)Tmax * beam > 0x3fffffffll) return MI_ERR_ARG;   // node ids are 32-bit
+  const size_t shm = (size_t)C * 8;
+  if (shm > 64 * 1024) return MI_ERR_ARG;
+  MI_LAUNCH(ctc_beam_kernel, dim3(B), dim3(64), shm, (hipStream_t)stream, (const float*)logp, (const long long*)lens, (int2*)node_ws,
+            (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, blank, beam, threshold, beta);
+  return mi_check_launch();
+}

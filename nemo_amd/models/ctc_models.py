@@ -92,6 +92,9 @@ def ctc_transcribe_timestamps(model, audio, batch_size=4, channel_selector=None)
     decoding = model._ctc_decoding()
     if decoding is None:
         raise RuntimeError("transcribe() needs a vocabulary (decoder.vocabulary or a tokenizer)")
+    if _is_beam(decoding):
+        raise NotImplementedError("transcribe(timestamps=True) with decoding strategy 'beam_batch': timestamps come from the greedy "
+                                  "search (strategy greedy / greedy_batch) or from align()")
     audio, stride, out = _as_list(audio), frame_stride_s(model), []
     with _inference_setup(model):
         for i in range(0, len(audio), batch_size):
@@ -110,6 +113,34 @@ def ctc_transcribe_timestamps(model, audio, batch_size=4, channel_selector=None)
                 if ccfg is not None:
                     ctc_fill_confidence(hyp, decoding, ids, conf[0][r, : int(enc_len[r])].tolist(), conf[1][r, :n].tolist())
                 out.append(hyp)
+    return out
+
+
+def _is_beam(decoding) -> bool:
+    from ..modules import BeamBatchedCTCDecoder
+    return isinstance(decoding, BeamBatchedCTCDecoder)
+
+
+def ctc_beam_results(decoding, log_probs, enc_len, return_hypotheses=False):
+    """what `transcribe` returns per utterance of a batch under `beam_batch`: the best text; with return_hypotheses its (text, token
+    ids, score); and with the decoding object's `return_best_hypothesis` off the whole n-best list of either, best first"""
+    out = []
+    for hyps in decoding.nbest(log_probs, enc_len):
+        full = [(decoding.ids_to_text(ids), ids, score) for ids, score in hyps] or [("", [], float("-inf"))]
+        items = full if return_hypotheses else [t[0] for t in full]
+        out.append(items[0] if decoding.return_best_hypothesis else items)
+    return out
+
+
+def ctc_transcribe_beam(model, audio, batch_size=4, return_hypotheses=False, channel_selector=None):
+    """`transcribe` over a CTC head whose decoding object is the beam search (`model._ctc_log_probs`, `model._ctc_decoding()` as in
+    `ctc_transcribe_timestamps`): one `ctc_beam_results` entry per input, in input order"""
+    decoding, audio, out = model._ctc_decoding(), _as_list(audio), []
+    with _inference_setup(model):
+        for i in range(0, len(audio), batch_size):
+            sig, lens = _audio_batch(model, audio[i:i + batch_size], channel_selector)
+            log_probs, enc_len = model._ctc_log_probs(sig, lens)
+            out.extend(ctc_beam_results(decoding, log_probs, enc_len, return_hypotheses))
     return out
 
 
@@ -292,7 +323,8 @@ class EncDecCTCModel(nn.Module):
 
     @property
     def wer(self):
-        """greedy CTC decoding + WER over the decoder's vocabulary (ctc_models.py:91-105: CTCDecoding + WER(use_cer, ...))"""
+        """CTC decoding (`decoding.strategy`: greedy, or the beam search of `beam_batch`) + WER over the decoder's vocabulary
+        (ctc_models.py:91-105: CTCDecoding + WER(use_cer, ...))"""
         if self._wer is None:
             vocab = getattr(self.decoder, "vocabulary", None)
             tok = getattr(self, "tokenizer", None)
@@ -300,11 +332,9 @@ class EncDecCTCModel(nn.Module):
                 vocab = tok.vocab
             if vocab is None:
                 return None
-            from ..modules import WER, GreedyCTCDecoder
-            strategy = str((self._cfg.get("decoding") or {}).get("strategy", "greedy_batch"))
-            if strategy not in ("greedy", "greedy_batch"):  # ctc_decoding.py:231-236: beam / pyctcdecode / flashlight / wfst need their own decoders
-                raise NotImplementedError(f"CTC decoding strategy '{strategy}' (implemented: greedy, greedy_batch)")
-            self._wer = WER(GreedyCTCDecoder(vocabulary=list(vocab), confidence_cfg=(self._cfg.get("decoding") or {}).get("confidence_cfg")),
+            from ..modules import WER, ctc_decoder_from_config
+            # greedy / greedy_batch or beam_batch; beam / pyctcdecode / flashlight / wfst (ctc_decoding.py:231-236) raise in the factory
+            self._wer = WER(ctc_decoder_from_config(self._cfg.get("decoding"), list(vocab), what="CTC"),
                             use_cer=bool(self._cfg.get("use_cer", False)))
         return self._wer
 
@@ -380,7 +410,8 @@ class EncDecCTCModel(nn.Module):
     def predict_step(self, batch, batch_idx=0, dataloader_idx=0):
         signal, signal_len, _, _, sample_id = batch
         log_probs, encoded_len, _ = self.forward(input_signal=signal, input_signal_length=signal_len)
-        texts = self.wer.decoding(log_probs, encoded_len)
+        decoding = self.wer.decoding
+        texts = getattr(decoding, "best_texts", decoding)(log_probs, encoded_len)
         if isinstance(sample_id, torch.Tensor):
             sample_id = sample_id.cpu().numpy()
         return list(zip(sample_id, texts))
@@ -397,6 +428,8 @@ class EncDecCTCModel(nn.Module):
             return ctc_transcribe_timestamps(self, audio, batch_size, channel_selector)
         if self.wer is None:
             raise RuntimeError("transcribe() needs a vocabulary (decoder.vocabulary or a tokenizer)")
+        if _is_beam(self.wer.decoding):   # strategy beam_batch: the best hypothesis, or the n-best lists (`ctc_beam_results`)
+            return ctc_transcribe_beam(self, audio, batch_size, return_hypotheses, channel_selector)
         audio, out = _as_list(audio), []
         with _inference_setup(self):
             for i in range(0, len(audio), batch_size):

@@ -15,17 +15,17 @@ import torch
 
 from ..modules import CTCLoss
 from .ctc_models import _build as _build_ctc
-from .ctc_models import ctc_align_audio, ctc_fill_confidence, ctc_transcribe_timestamps, frame_stride_s
+from .ctc_models import (_is_beam, ctc_align_audio, ctc_fill_confidence, ctc_transcribe_beam, ctc_transcribe_timestamps,
+                         frame_stride_s)
 from .rnnt_models import EncDecRNNTModel, fastconformer_tdt_config, fastconformer_transducer_config, rnnt_conformer_stream_step
 
 _GREEDY = ("greedy", "greedy_batch")
 
 
 def _check_ctc_strategy(dcfg):
-    strategy = str(dict(dcfg or {}).get("strategy", "greedy_batch"))
-    if strategy not in _GREEDY:   # ctc_decoding.py:231-236: beam / pyctcdecode / flashlight / wfst need their own decoders
-        raise NotImplementedError(f"aux_ctc decoding strategy '{strategy}' (implemented: greedy, greedy_batch)")
-    return strategy
+    """the auxiliary head's `decoding` section is acceptable (the factory every CTC head shares raises where it is not)"""
+    from ..modules import ctc_decoder_from_config
+    ctc_decoder_from_config(dcfg, None, what="aux_ctc")
 
 
 class _CTCHeadText:
@@ -44,6 +44,12 @@ class _CTCHeadText:
         log_probs = m.ctc_decoder(encoder_output=encoder_output)
         lens = encoded_lengths.cpu()
         hyps = []
+        if _is_beam(dec):   # the best hypothesis of the beam search
+            for b, nbest in enumerate(dec.nbest(log_probs, encoded_lengths)):
+                ids, score = nbest[0] if nbest else ([], float("-inf"))
+                hyps.append(Hypothesis(score=score, y_sequence=torch.tensor(ids, dtype=torch.long), text=dec.ids_to_text(ids),
+                                       length=int(lens[b])))
+            return hyps
         if dec.confidence_cfg is not None:   # the same decoding with confidences, from the one launch that computes both
             tokens, out_len, score, _, _, fc, tc = (t.cpu() for t in dec.decode_ids_confidence(log_probs, encoded_lengths))
         else:
@@ -101,18 +107,17 @@ class EncDecHybridRNNTCTCModel(EncDecRNNTModel):
         # backward-completion order is not guaranteed for the two heads; the gradient exchange only needs every module listed
         return [self.encoder, self.decoder, self.joint, self.ctc_decoder]
 
-    # ------------------------------------------------------------------ the CTC head's decoding objects (greedy)
+    # ------------------------------------------------------------------ the CTC head's decoding objects (greedy or beam_batch)
     @property
     def ctc_wer(self):
-        """hybrid_rnnt_ctc_models.py:82-95: CTCDecoding + WER over the auxiliary head (`aux_ctc.decoding`, greedy)"""
+        """hybrid_rnnt_ctc_models.py:82-95: CTCDecoding + WER over the auxiliary head (`aux_ctc.decoding`: greedy or beam_batch)"""
         if self._ctc_wer is None:
             vocab = getattr(self.ctc_decoder, "vocabulary", None)
             if vocab is None:
                 return None
-            from ..modules import WER, GreedyCTCDecoder
-            _check_ctc_strategy(self._cfg["aux_ctc"].get("decoding"))
-            ccfg = (self._cfg["aux_ctc"].get("decoding") or {}).get("confidence_cfg")
-            self._ctc_wer = WER(GreedyCTCDecoder(vocabulary=list(vocab), confidence_cfg=ccfg), use_cer=bool(self._cfg.get("use_cer", False)))
+            from ..modules import WER, ctc_decoder_from_config
+            self._ctc_wer = WER(ctc_decoder_from_config(self._cfg["aux_ctc"].get("decoding"), list(vocab), what="aux_ctc"),
+                                use_cer=bool(self._cfg.get("use_cer", False)))
         return self._ctc_wer
 
     @property
@@ -170,6 +175,8 @@ class EncDecHybridRNNTCTCModel(EncDecRNNTModel):
                    channel_selector=None, verbose: bool = False, timestamps: bool = False):
         """EncDecRNNTModel.transcribe; timestamps=True (CTC head selected) returns Hypothesis objects with char / word offsets
         (ctc_models.ctc_transcribe_timestamps).  The transducer head's hypotheses already carry `timestamp` with return_hypotheses."""
+        if self.cur_decoder == "ctc" and not timestamps and _is_beam(self.ctc_decoding):   # beam_batch over the CTC head
+            return ctc_transcribe_beam(self, audio, batch_size, return_hypotheses, channel_selector)
         if not timestamps:
             return super().transcribe(audio, batch_size, return_hypotheses, num_workers, channel_selector, verbose)
         if self.cur_decoder != "ctc":

@@ -4,7 +4,8 @@ from .conformer_encoder import ConformerEncoder  # noqa: F401
 from .squeezeformer_encoder import SqueezeformerEncoder  # noqa: F401
 from .conv_asr import ConvASRDecoder  # noqa: F401
 from .ctc import CTCLoss  # noqa: F401
-from .ctc_decoding import CTCAligner, GreedyCTCDecoder, WER, ctc_offsets, word_error_rate  # noqa: F401
+from .ctc_decoding import (BeamBatchedCTCDecoder, CTCAligner, GreedyCTCDecoder, WER, ctc_decoder_from_config,  # noqa: F401
+                           ctc_offsets, word_error_rate)
 from .rnnt_loss import RNNTLoss, RNNTLossNumba  # noqa: F401
 from .tdt_loss import TDTLoss, TDTLossNumba  # noqa: F401
 from .rnnt import RNNTDecoder, RNNTJoint  # noqa: F401

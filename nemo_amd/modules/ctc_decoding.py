@@ -1,10 +1,16 @@
-"""Greedy CTC decoding and WER for the drop-in model.
+"""Greedy CTC decoding, CTC prefix beam search and WER for the drop-in model.
 
 The reference decodes on the host: `GreedyCTCInfer` copies the log-probabilities to the CPU utterance by utterance and
 folds them in Python (parts/submodules/ctc_greedy_decoding.py:333-361, ctc_decoding.py:545-575), a D2H sync of
 [B, T, V+1] floats (8 MB at the headline shape) on every logging step.  Here arg-max, score, repeat folding and blank
 removal are one kernel launch (`mi355x_ctc_greedy_decode`); only the folded token ids (<= 64 KB) ever leave the device,
 and only when text is asked for.
+
+`BeamBatchedCTCDecoder` is the reference's `strategy: beam_batch` (its batched GPU CTC beam search; `beam` there is the pyctcdecode /
+KenLM decoder and stays refused here), without language-model fusion.  What it runs is the classic CTC prefix beam search as
+include/mi355x_asr.h states it in full -- that statement, not a recollection of the reference's internals, is what the kernel and
+the test oracle (tests/ctc_beam_oracle.py) implement: pb / pnb per prefix, stays and extensions merged where they name the same
+prefix, the `beam_size` prefixes of the largest log-probability (+ beam_beta per token) kept per frame, one launch per batch.
 """
 from __future__ import annotations
 
@@ -15,30 +21,55 @@ import torch
 from .. import ops
 
 
-class GreedyCTCDecoder:
-    """blank_id = len(vocabulary) as in CTCDecoding.__init__ (ctc_decoding.py:1044); `vocabulary` maps ids to strings
-    (characters, or word pieces whose leading U+2581 marks a word start -- the SentencePiece convention)."""
+class _CTCText:
+    """what every CTC decoding object knows about its labels: blank_id = len(vocabulary) as in CTCDecoding.__init__
+    (ctc_decoding.py:1044); `vocabulary` maps ids to strings (characters, or word pieces whose leading U+2581 marks a word start --
+    the SentencePiece convention)."""
 
-    def __init__(self, vocabulary: Optional[Sequence[str]] = None, blank_id: Optional[int] = None, confidence_cfg=None):
+    def _set_labels(self, vocabulary, blank_id):
         if vocabulary is None and blank_id is None:
             raise ValueError("either a vocabulary or a blank_id is required")
         self.vocabulary = list(vocabulary) if vocabulary is not None else None
         self.blank_id = len(self.vocabulary) if blank_id is None else int(blank_id)
-        from .confidence import confidence_from
-        self.confidence_cfg = confidence_from(confidence_cfg)   # None: no confidence is computed, decoding is what it was
 
     @property
     def word_pieces(self) -> bool:
         return self.vocabulary is not None and any(v.startswith("▁") for v in self.vocabulary)
+
+    def offsets(self, ids: Sequence[int], starts: Sequence[int], ends: Sequence[int]):
+        """(char offsets, word offsets) of a token sequence with its first / last frames, see `ctc_offsets`"""
+        if self.vocabulary is None:
+            raise ValueError("no vocabulary: offsets are not available")
+        return ctc_offsets([self.vocabulary[i] for i in ids], starts, ends, word_pieces=self.word_pieces)
+
+    def ids_to_text(self, ids: Sequence[int]) -> str:
+        if self.vocabulary is None:
+            raise ValueError("no vocabulary: text is not available")
+        text = "".join(self.vocabulary[i] for i in ids)             # decode_tokens_to_str, ctc_decoding.py:1075-1086
+        return text.replace("▁", " ").strip() if "▁" in text else text
+
+
+def _check_log_probs(log_probs):
+    if log_probs.dim() != 3:
+        raise ValueError(f"`decoder_output` must be a tensor of shape [B, T, V] (log probs, float). Provided shape = "
+                         f"{tuple(log_probs.shape)}")
+
+
+class GreedyCTCDecoder(_CTCText):
+    """blank_id = len(vocabulary) as in CTCDecoding.__init__ (ctc_decoding.py:1044); `vocabulary` maps ids to strings
+    (characters, or word pieces whose leading U+2581 marks a word start -- the SentencePiece convention)."""
+
+    def __init__(self, vocabulary: Optional[Sequence[str]] = None, blank_id: Optional[int] = None, confidence_cfg=None):
+        self._set_labels(vocabulary, blank_id)
+        from .confidence import confidence_from
+        self.confidence_cfg = confidence_from(confidence_cfg)   # None: no confidence is computed, decoding is what it was
 
     @torch.no_grad()
     def decode_ids(self, log_probs: torch.Tensor, lengths: Optional[torch.Tensor] = None, return_timestamps: bool = False):
         """log_probs [B, T, V+1] (device) -> (tokens i32 [B,T] folded / blank-free / -1 padded, lengths i32 [B], score [B]);
         with return_timestamps also (start, end) i32 [B,T]: the first / last frame of the run of equal arg-max labels behind each
         token (`mi355x_ctc_greedy_decode_ts`; the `compute_timestamps` of AbstractCTCDecoding, ctc_decoding.py:290-340)"""
-        if log_probs.dim() != 3:
-            raise ValueError(f"`decoder_output` must be a tensor of shape [B, T, V] (log probs, float). Provided shape = "
-                             f"{tuple(log_probs.shape)}")
+        _check_log_probs(log_probs)
         lp = log_probs.to(torch.float32).contiguous()
         lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
         if return_timestamps:
@@ -53,20 +84,12 @@ class GreedyCTCDecoder:
         cfg = self.confidence_cfg
         if cfg is None:
             raise ValueError("confidence needs a decoder built with a `confidence_cfg` that preserves a confidence")
-        if log_probs.dim() != 3:
-            raise ValueError(f"`decoder_output` must be a tensor of shape [B, T, V] (log probs, float). Provided shape = "
-                             f"{tuple(log_probs.shape)}")
+        _check_log_probs(log_probs)
         from .confidence import AGGREGATIONS
         lp = log_probs.to(torch.float32).contiguous()
         lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
         return ops.ctc_greedy_decode_conf(lp, lens, self.blank_id, cfg.method_cfg.kernel_args(lp.shape[2]),
                                           AGGREGATIONS[cfg.aggregation], cfg.exclude_blank)
-
-    def offsets(self, ids: Sequence[int], starts: Sequence[int], ends: Sequence[int]):
-        """(char offsets, word offsets) of a token sequence with its first / last frames, see `ctc_offsets`"""
-        if self.vocabulary is None:
-            raise ValueError("no vocabulary: offsets are not available")
-        return ctc_offsets([self.vocabulary[i] for i in ids], starts, ends, word_pieces=self.word_pieces)
 
     def word_confidence(self, ids: Sequence[int], token_conf: Sequence[float]):
         """one confidence per word of `offsets(ids, ...)`: the configured aggregation over the word's token confidences"""
@@ -75,16 +98,84 @@ class GreedyCTCDecoder:
         from .confidence import word_confidence
         return word_confidence([self.vocabulary[i] for i in ids], token_conf, self.word_pieces, self.confidence_cfg.aggregation)
 
-    def ids_to_text(self, ids: Sequence[int]) -> str:
-        if self.vocabulary is None:
-            raise ValueError("no vocabulary: text is not available")
-        text = "".join(self.vocabulary[i] for i in ids)             # decode_tokens_to_str, ctc_decoding.py:1075-1086
-        return text.replace("▁", " ").strip() if "▁" in text else text
-
     def __call__(self, log_probs, lengths=None) -> List[str]:
         tokens, out_len, _ = self.decode_ids(log_probs, lengths)
         tokens, out_len = tokens.cpu(), out_len.cpu()                  # the only D2H copy: folded ids
         return [self.ids_to_text(tokens[b, : int(out_len[b])].tolist()) for b in range(tokens.shape[0])]
+
+
+class BeamBatchedCTCDecoder(_CTCText):
+    """CTC prefix beam search without a language model, on the device (`mi355x_ctc_beam_decode`): the `beam_batch` strategy.
+    `beam_size` hypotheses per utterance (1..64), `beam_threshold`: a class is looked at in a frame only if its log-probability is
+    within that much of the frame's best (inf: every class), `beam_beta`: bonus per token; the score of a hypothesis is the
+    log-probability of its LABEL SEQUENCE (all of its alignments the search kept) + beam_beta * length.
+    `return_best_hypothesis=False` makes `__call__` return the n-best lists."""
+
+    confidence_cfg = None   # (the greedy decoder's attribute: confidences are not defined for the beam search)
+
+    def __init__(self, vocabulary: Optional[Sequence[str]] = None, blank_id: Optional[int] = None, beam_size: int = 4,
+                 return_best_hypothesis: bool = True, beam_threshold: float = 20.0, beam_beta: float = 0.0):
+        self._set_labels(vocabulary, blank_id)
+        self.beam_size, self.return_best_hypothesis = int(beam_size), bool(return_best_hypothesis)
+        self.beam_threshold, self.beam_beta = float(beam_threshold), float(beam_beta)
+        if not 1 <= self.beam_size <= 64:
+            raise ValueError(f"beam_size must lie in 1..64 (one wave holds the beams of an utterance); got {beam_size}")
+        if not self.beam_threshold > 0:
+            raise ValueError(f"beam_threshold must be positive (inf: no pruning); got {beam_threshold}")
+
+    @torch.no_grad()
+    def decode_ids(self, log_probs: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        """log_probs [B, T, V+1] (device) -> (tokens i32 [B,W,T]: hypotheses best first, -1 padded; tok_frame i32 [B,W,T]: the frame
+        each token entered its hypothesis; hyp_len i32 [B,W]; score f32 [B,W], -inf for absent hypotheses; n_hyp i32 [B])"""
+        _check_log_probs(log_probs)
+        lp = log_probs.to(torch.float32).contiguous()
+        lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
+        return ops.ctc_beam_decode(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta)
+
+    def nbest(self, log_probs, lengths=None):
+        """per utterance the list of (token ids, score), best first: the D2H copy is the folded hypotheses, W * T integers an utterance"""
+        tokens, _, hyp_len, score, n_hyp = (t.cpu() for t in self.decode_ids(log_probs, lengths))
+        return [[(tokens[b, k, : int(hyp_len[b, k])].tolist(), float(score[b, k])) for k in range(int(n_hyp[b]))]
+                for b in range(tokens.shape[0])]
+
+    def __call__(self, log_probs, lengths=None):
+        texts = [[self.ids_to_text(ids) for ids, _ in hyps] for hyps in self.nbest(log_probs, lengths)]
+        return [(t[0] if t else "") for t in texts] if self.return_best_hypothesis else texts
+
+    def best_texts(self, log_probs, lengths=None) -> List[str]:
+        """the best hypothesis of every utterance, whatever `return_best_hypothesis` says: what WER and predict_step score"""
+        return [(self.ids_to_text(hyps[0][0]) if hyps else "") for hyps in self.nbest(log_probs, lengths)]
+
+
+_LM_KEYS = ("ngram_lm_model", "kenlm_path")
+
+
+def ctc_decoder_from_config(decoding_cfg, vocabulary=None, what: str = "CTC"):
+    """The one place that reads a CTC head's `decoding` section (`what` names the head in messages): checks it and, with a
+    vocabulary, returns its decoding object -- GreedyCTCDecoder for `greedy` / `greedy_batch`, BeamBatchedCTCDecoder for
+    `beam_batch` (its `beam` sub-section: beam_size, return_best_hypothesis, beam_threshold, beam_beta).  Everything else the reference
+    knows (beam = pyctcdecode / KenLM, flashlight, wfst: ctc_decoding.py:231-236) and language-model fusion raise
+    NotImplementedError."""
+    dcfg = dict(decoding_cfg or {})
+    strategy = str(dcfg.get("strategy", "greedy_batch"))
+    if strategy in ("greedy", "greedy_batch"):
+        return None if vocabulary is None else GreedyCTCDecoder(vocabulary=list(vocabulary), confidence_cfg=dcfg.get("confidence_cfg"))
+    if strategy != "beam_batch":
+        raise NotImplementedError(f"{what} decoding strategy '{strategy}' (implemented: greedy, greedy_batch, beam_batch)")
+    beam = dict(dcfg.get("beam") or {})
+    for key in _LM_KEYS:
+        if beam.get(key):
+            raise NotImplementedError(f"{what} decoding: `beam.{key}` (language-model fusion is not provided; beam_batch runs without one)")
+    if float(beam.get("ngram_lm_alpha") or 0.0) != 0.0:
+        raise NotImplementedError(f"{what} decoding: `beam.ngram_lm_alpha` != 0 (language-model fusion is not provided)")
+    from .confidence import confidence_from
+    if confidence_from(dcfg.get("confidence_cfg")) is not None:
+        raise NotImplementedError(f"{what} decoding: `confidence_cfg` with strategy 'beam_batch' (confidences come from the greedy search)")
+    if vocabulary is None:
+        return None
+    return BeamBatchedCTCDecoder(vocabulary=list(vocabulary), beam_size=beam.get("beam_size", 4),
+                                 return_best_hypothesis=beam.get("return_best_hypothesis", True),
+                                 beam_threshold=beam.get("beam_threshold", 20.0), beam_beta=beam.get("beam_beta", 0.0))
 
 
 def ctc_offsets(tokens: Sequence[str], starts: Sequence[int], ends: Sequence[int], word_pieces: bool = False):
@@ -163,13 +254,13 @@ class WER:
     """metrics/wer.py:210-356: accumulates edit distance and reference word counts over batches; `compute()` returns
     (wer, scores, words) like the torchmetrics object of the reference."""
 
-    def __init__(self, decoding: GreedyCTCDecoder, use_cer: bool = False):
+    def __init__(self, decoding, use_cer: bool = False):
         self.decoding, self.use_cer = decoding, use_cer
         self.scores = 0
         self.words = 0
 
     def update(self, predictions: torch.Tensor, predictions_lengths, targets: torch.Tensor, targets_lengths):
-        hyps = self.decoding(predictions, predictions_lengths)
+        hyps = getattr(self.decoding, "best_texts", self.decoding)(predictions, predictions_lengths)   # (beam search: the best hypothesis)
         tg, tl = targets.cpu(), targets_lengths.cpu()
         refs = [self.decoding.ids_to_text(tg[b, : int(tl[b])].tolist()) for b in range(tg.shape[0])]
         for h, r in zip(hyps, refs):

@@ -487,6 +487,26 @@ def ctc_align(logp, targets, in_len, tgt_len, blank):
     return path, tok_start[:, :U], tok_end[:, :U], score
 
 
+def ctc_beam_decode(logp, lens, blank, beam_size, beam_threshold=20.0, beam_beta=0.0):
+    """CTC prefix beam search without a language model (mi355x_ctc_beam_decode): logp f32 [B,T,C] contiguous, lens i64 [B] (None: T
+    for every utterance) -> (tokens i32 [B,W,T]: hypotheses best first, -1 padded; tok_frame i32 [B,W,T]: the frame each token was
+    created in; hyp_len i32 [B,W]; score f32 [B,W]: tot + beam_beta * len, -inf for absent hypotheses; n_hyp i32 [B]).  The node
+    workspace (2 * T * W integers per utterance) is allocated here and dropped."""
+    B, T, C_ = logp.shape
+    W = int(beam_size)
+    if lens is None:
+        lens = torch.full((B,), T, dtype=torch.int64, device=logp.device)
+    i32, f32 = (dict(dtype=d, device=logp.device) for d in (torch.int32, torch.float32))
+    ws = torch.empty(B * max(2, int(lib.mi355x_ctc_beam_workspace_elems(T, W))), **i32)   # (a fresh allocation: 8-byte aligned)
+    Wa = max(W, 0)   # (a width the entry refuses still reaches it, for its ValueError)
+    tokens, tok_frame = torch.empty(B, Wa, T, **i32), torch.empty(B, Wa, T, **i32)
+    hyp_len, score, n_hyp = torch.empty(B, Wa, **i32), torch.empty(B, Wa, **f32), torch.empty(B, **i32)
+    check(lib.mi355x_ctc_beam_decode(_ptr(logp), _ptr(lens), _ptr(ws), _ptr(tokens), _ptr(tok_frame), _ptr(hyp_len), _ptr(score),
+                                     _ptr(n_hyp), B, T, C_, int(blank), W, float(beam_threshold), float(beam_beta), _stream()),
+          "ctc_beam_decode")
+    return tokens, tok_frame, hyp_len, score, n_hyp
+
+
 def specaug_rects(u_tw, u_ts, u_fw, u_fs, length, rects, B, nt, nf, F, T, time_width, freq_width):
     """mask rectangles of SpecAugment's vectorised path from its four uniform draws (one launch instead of ~40 tensor ops)"""
     frac = isinstance(time_width, float)

@@ -637,7 +637,8 @@ int mi355x_ctc_align(const void* logp, const void* targets, const void* in_len, 
  * 2*Umax+1 <= 1024, 0 = the LDS / barrier form for every size.  Returns the previous setting (-1: not yet resolved). */
 int mi355x_ctc_align_config(int wave);
 
-/* CTC prefix beam search without a language model (the `beam_batch` strategy), one launch per batch, utterances independent.
+/* CTC prefix beam search (the `beam_batch` strategy), one launch per batch, utterances independent.  This entry runs without a
+ * language model; mi355x_ctc_beam_decode_lm below is the same search with an n-gram model fused.
  * logp f32 [B,Tmax,C] log-probabilities (-inf entries allowed; rows beyond lens[b] are never read); lens i64 [B].
  * A beam = a prefix (a node (parent node, token) of a prefix tree), its length len, pb / pnb = log-probability of its alignments
  * that end in blank / in a non-blank, tot = logaddexp(pb, pnb).  Start: the empty prefix, pb = 0, pnb = -inf.  Per frame t:
@@ -666,6 +667,37 @@ int mi355x_ctc_beam_decode(const void* logp, const void* lens, void* node_ws, vo
                            void* stream);
 /* i32 elements of node_ws per utterance; 0 for arguments mi355x_ctc_beam_decode rejects */
 long long mi355x_ctc_beam_workspace_elems(int Tmax, int beam);
+
+/* The search of mi355x_ctc_beam_decode with shallow fusion of a token-level back-off n-gram language model.
+ * The model, of order N, gives ln p(c | context) for the labels c = 0 .. V-1, V = C-1 (so blank = C-1); the context is the last N-1
+ * tokens of <s> followed by the prefix.  The value is the ARPA definition: the probability of the n-gram ctx.c where the file has
+ * it, else backoff(ctx) + ln p(c | ctx[1:]) with backoff(ctx) = 0 for a ctx that is not in the file; the recursion ends at the
+ * unigrams, which exist for every label.  File values are log10: the tables hold float32(float64(value) * ln 10).
+ * lm(prefix) = the sum of the conditional log-probabilities of its tokens, lm(()) = 0; no </s> term is ever added.  lm is a function
+ * of the prefix alone, so a stay and an extension that name the same prefix still are one candidate.
+ * The search changes in the rank only:  rank = (tot + beta * len) + alpha * lm(prefix),  float32, in that association, each product
+ * rounded before it is added.  Token pruning (acoustic only), pb / pnb, merging, the order of ties, the node tree and all outputs
+ * are what they are above; `score` is the rank, so it includes alpha * lm.  alpha = 0 gives the bits of mi355x_ctc_beam_decode.
+ * The model as a back-off automaton (S = n_states, A = n_arcs), all arrays on the device:
+ *   state_arc_begin i32 [S+1]  the arcs of state s are [state_arc_begin[s], state_arc_begin[s+1]); a state = a context the file
+ *                              holds as an n-gram of order < N; state 0 = the empty context, state 1 = <s>
+ *   arc_tok  i32 [A]           the label of an arc, ascending inside a state; state 0 has exactly V arcs and arc c is label c
+ *   arc_logp f32 [A]           ln p(label | the state's context)
+ *   arc_next i32 [A]           the state of the longest suffix of context.label that is a state
+ *   state_bo f32 [S]           the back-off weight (ln) of the state's context
+ *   state_bo_next i32 [S]      the state of the longest proper suffix of the context that is a state (0 for one-token contexts)
+ * A look-up of c in state s:  acc = 0; while c is not among the arcs of s: acc += state_bo[s], s = state_bo_next[s];
+ * value = acc + arc_logp, next state = arc_next.  lm(prefix.c) = lm(prefix) + value, float32.
+ * lm_ub: an upper bound of every look-up's value (what cannot beat the kept set is skipped by it; a looser bound only skips less).
+ * The kernel bounds every chase (a back-off chain by S steps, a binary search by 32) and clamps every index to its table: tables
+ * that break the rules above give a wrong score, never a hang.
+ * MI_ERR_ARG for what mi355x_ctc_beam_decode refuses and for null tables, n_states < 2, n_arcs < C-1, blank != C-1, alpha < 0 or
+ * NaN, NaN lm_ub. */
+int mi355x_ctc_beam_decode_lm(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
+                              void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta,
+                              const void* state_arc_begin, const void* arc_tok, const void* arc_logp, const void* arc_next,
+                              const void* state_bo, const void* state_bo_next, int n_states, int n_arcs, float alpha, float lm_ub,
+                              void* stream);
 
 /* SpectrogramAugmentation (nemo/collections/asr/modules/audio_preprocessing.py:443-553; SpecAugment._apply_masks
  * parts/submodules/spectr_augment.py:153-215, SpecCutout.forward :245-261): x[b, f0:f1, t0:t1] = value for n rectangles

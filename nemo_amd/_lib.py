@@ -125,6 +125,8 @@ SIGNATURES = {
     "mi355x_ctc_greedy_decode_conf": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, i32, i32, vp],
     "mi355x_ctc_align": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi355x_ctc_beam_decode": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp],
+    "mi355x_ctc_beam_decode_lm": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, i32, i32,
+                                  f32, f32, vp],
     "mi355x_ctc_beam_workspace_elems": [i32, i32],
     "mi355x_fill_rects": [vp, vp, i32, i32, i32, i32, f32, vp],
     "mi355x_specaug_rects": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp],

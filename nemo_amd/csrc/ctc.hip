@@ -877,7 +877,8 @@ extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const voi
 }
 
 // ------------------------------------------------------------------------------------------------ CTC prefix beam search
-// The classic CTC prefix beam search (the `beam_batch` strategy; no language model), ONE launch per batch, one wave per utterance,
+// The classic CTC prefix beam search (the `beam_batch` strategy), with or without shallow fusion of a token-level back-off n-gram
+// language model (the LM flag of the kernel template: one search, two instantiations), ONE launch per batch, one wave per utterance,
 // a lane per beam: the whole search state of an utterance lives in the registers of its wave, so the frame loop has no workgroup
 // barrier, and nothing of size [B, T, C] leaves the device.  include/mi355x_asr.h states the search; in short, per frame:
 //   token pruning   c is considered iff lp[t,c] >= max_c lp[t,c] - threshold (float32 subtract and compare)
@@ -885,6 +886,7 @@ extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const voi
 //   extensions      ext(i,c).pnb = (c == last_i ? pb_i : tot_i) + lp[c] ; where the prefix of ext(i,c) is the prefix of a beam j of
 //                   the current set, the value is added (log-add-exp) to stay(j).pnb instead: the two are ONE candidate
 //   selection       the `beam` candidates of the largest rank = tot + beta * len, tot = logaddexp(pb, pnb) > -inf
+//                   (LM: rank = (tot + beta * len) + alpha * lm(prefix); nothing else of the search changes)
 // A beam is a node of a prefix tree.  Node 0 is the empty prefix; the extension kept in slot s of frame t becomes node
 // 1 + t*beam + s and stores (parent node, token) at node_ws[t*beam + s], so the frame a token was created in is (node - 1) / beam.
 // Which beam an extension would duplicate: a beam carries a 64-bit hash of its prefix and of its parent's prefix; equal hash and
@@ -901,6 +903,15 @@ extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const voi
 // Ties: candidates are ordered by (rank descending, key ascending), key = i for stay(i) and beam + i*C + c for ext(i,c), i the slot
 // of the beam in the sorted set of the previous frame; the order is total, so selection and output order are deterministic.
 // Arithmetic: plain float32, logaddexp(a,b) = max + log1pf(expf(-|a-b|)); beta * len is rounded on its own (no fused multiply-add).
+// Language model (LM instantiation): the back-off automaton of include/mi355x_asr.h in six global arrays, small and shared by every
+// wave, so they stay in L2; LDS holds what it held.  A beam carries its automaton state and lm(prefix) (`lm_state`, `lm_sum`: two
+// more registers that travel with it in the end-of-frame shuffle).  lm(prefix . c) = lm_sum + look-up(lm_state, c), and a look-up
+// <= lm_ub, so every early-out keeps its form with alpha * (lm_sum + lm_ub) added to the side of the candidate: rounding is monotone,
+// alpha >= 0, the bar only rises.  In the streamed loop that bound, which needs no look-up, is tested first and only the lanes that
+// pass it walk the tables (a binary search in the arcs of the state, a direct index at state 0); the ballot sees exact ranks.  The
+// running top-W stays (rank, key, value): a kept extension repeats its one look-up at the end of the frame -- same inputs, same
+// value -- to get its lm_sum and next state.  Every chase is bounded (back-off chain: n_states steps, binary search: 32) and every
+// index is clamped to its table, so tables that are not what the loader checks give a wrong score, never a hang or a stray load.
 #define CTC_BEAM_MAX 64
 #define CTC_BEAM_ROOT_HASH 0x243F6A8885A308D3ull
 __device__ __forceinline__ float ctc_lae(float a, float b) {
@@ -924,6 +935,40 @@ __device__ __forceinline__ float ctc_pushf(float v, int dst) { return __int_as_f
 // lane l <- lane l-1 over the whole wave (DPP wave_shr:1); lane 0 keeps its value
 __device__ __forceinline__ int ctc_up1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ float ctc_up1f(float v) { return __int_as_float(ctc_up1(__float_as_int(v))); }
+// the six tables of the back-off automaton with the fusion weight and the upper bound of a look-up; nothing where LM is off
+struct ctc_beam_lm {
+  const int* arc_begin; const int* arc_tok; const float* arc_logp; const int* arc_next; const float* bo; const int* bo_next;
+  int n_states, n_arcs;
+  float alpha, ub;
+};
+struct ctc_beam_no_lm {};
+template <bool LM> struct ctc_beam_lm_of { typedef ctc_beam_no_lm type; };
+template <> struct ctc_beam_lm_of<true> { typedef ctc_beam_lm type; };
+__device__ __forceinline__ float ctc_beam_alpha_lm(float alpha, float lm) {
+  float al = alpha * lm;
+  asm volatile("" : "+v"(al));   // rounded on its own, like beta * len
+  return al;
+}
+// ln p(c | state s) and the state behind it: while c is not among the arcs of s, add the back-off of s and go to its suffix state
+__device__ __forceinline__ float ctc_beam_lm_lookup(const ctc_beam_lm& lm, int s, int c, int& next) {
+  float acc = 0.f;
+  for (int n = 0; n < lm.n_states; ++n) {
+    s = min(max(s, 0), lm.n_states - 1);
+    if (s == 0) break;
+    int lo = min(max(lm.arc_begin[s], 0), lm.n_arcs);
+    const int end = min(max(lm.arc_begin[s + 1], lo), lm.n_arcs);
+    int hi = end;
+    for (int k = 0; k < 32 && lo < hi; ++k) {
+      const int mid = (lo + hi) >> 1;
+      if (lm.arc_tok[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    if (lo < end && lm.arc_tok[lo] == c) { next = lm.arc_next[lo]; return acc + lm.arc_logp[lo]; }
+    acc += lm.bo[s];
+    s = lm.bo_next[s];
+  }
+  next = lm.arc_next[c];   // state 0: the arc index is the label (0 <= c < C-1 <= n_arcs)
+  return acc + lm.arc_logp[c];
+}
 // candidate (r, k) goes in front of (wr, wk)
 __device__ __forceinline__ bool ctc_beam_beats(float r, int k, float wr, int wk) { return r > wr || (r == wr && k < wk); }
 // are the prefixes of nodes a and b the same sequence (they have the same length)?
@@ -937,10 +982,11 @@ __device__ __forceinline__ bool ctc_beam_same_prefix(const int2* ws, int a, int 
   return true;
 }
 
+template <bool LM>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ logp, const long long* __restrict__ lens, int2* node_ws,
                                                       int* __restrict__ tokens, int* __restrict__ tok_frame, int* __restrict__ hyp_len,
                                                       float* __restrict__ score, int* __restrict__ n_hyp, int Tmax, int C, int blank,
-                                                      int W, float theta, float beta) {
+                                                      int W, float theta, float beta, typename ctc_beam_lm_of<LM>::type lm) {
   extern __shared__ float s_rows[];   // [2][C]: the log-probabilities of this frame and of the next
   const int b = blockIdx.x, lane = threadIdx.x;
   const int T = (int)max(0ll, min((long long)Tmax, lens ? lens[b] : (long long)Tmax));
@@ -952,6 +998,8 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   unsigned long long h = CTC_BEAM_ROOT_HASH, hp = 0;
   float pb = lane == 0 ? 0.f : NEGINF, pnb = NEGINF, tot = pb, brank = pb;
   int nb = 1;
+  int lm_state = 1;   // (LM) the automaton state of the prefix, <s> for the empty one, and lm(prefix)
+  float lm_sum = 0.f;
   if (T > 0)
     for (int c = lane; c < C; c += 64) s_rows[c] = lp[c];
   for (int t = 0; t < T; ++t) {
@@ -990,7 +1038,10 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     // candidate's, each its own, so that the order is total); lanes beyond W carry along what is shifted out and are never read
     float e_rank = NEGINF, e_val = NEGINF;
     int e_key = 0x7fffffff - lane;
-    if (live && stot != NEGINF) { e_rank = ctc_beam_rank(stot, beta, len); e_key = lane; }
+    if (live && stot != NEGINF) {
+      e_rank = ctc_beam_rank(stot, beta, len); e_key = lane;
+      if constexpr (LM) e_rank += ctc_beam_alpha_lm(lm.alpha, lm_sum);
+    }
     {
       int pos = 0;
       for (int j = 0; j < W; ++j) pos += ctc_beam_beats(ctc_rlf(e_rank, j), ctc_rl(e_key, j), e_rank, e_key) ? 1 : 0;
@@ -1003,19 +1054,37 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     // ---- extensions, streamed.  The bar only rises, and float32 rounding is monotone, so what cannot beat the bar of the stays is
     // out for the whole frame: a beam whose best possible extension (tot_i + mx) ranks below it, and a class whose extension of the
     // best possible beam (the largest tot, the largest bonus) does -- a group of 64 classes with no other class is never read again.
-    const unsigned long long beams = __ballot(live && !(ctc_beam_rank(tot + mx, beta, len + 1) < wr));
+    // (LM) what alpha * lm of an extension of this beam cannot exceed
+    float lm_top = 0.f, lm_top_max = 0.f;
+    if constexpr (LM) {
+      lm_top = ctc_beam_alpha_lm(lm.alpha, lm_sum + lm.ub);
+      lm_top_max = wave_max(live ? lm_top : NEGINF);
+    }
+    unsigned long long beams;
+    if constexpr (LM) beams = __ballot(live && !(ctc_beam_rank(tot + mx, beta, len + 1) + lm_top < wr));
+    else beams = __ballot(live && !(ctc_beam_rank(tot + mx, beta, len + 1) < wr));
     const float tmax = wave_max(live ? tot : NEGINF), blmax = wave_max(live ? ctc_beam_bonus(beta, len + 1) : NEGINF);
     unsigned long long groups[2] = {0ull, 0ull};   // (G <= 128: the launcher's LDS rule)
     for (int g = 0; g < G; ++g) {
       const int c = g * 64 + lane;
       const float v = c < C ? row[c] : NEGINF;
-      if (__ballot(c < C && c != blank && v >= lo && !((tmax + v) + blmax < wr))) groups[g >> 6] |= 1ull << (g & 63);
+      bool in;
+      if constexpr (LM) in = c < C && c != blank && v >= lo && !(((tmax + v) + blmax) + lm_top_max < wr);
+      else in = c < C && c != blank && v >= lo && !((tmax + v) + blmax < wr);
+      if (__ballot(in)) groups[g >> 6] |= 1ull << (g & 63);
     }
     for (unsigned long long bm = beams; bm; bm &= bm - 1) {
       const int i = __ffsll((long long)bm) - 1;
       const int tok_i = ctc_rl(tok, i), len_i = ctc_rl(len, i);
       const float pb_i = ctc_rlf(pb, i), tot_i = ctc_rlf(tot, i);
-      if (ctc_beam_rank(tot_i + mx, beta, len_i + 1) < wr) continue;   // (the bar has risen)
+      int lms_i = 0;
+      float lmsum_i = 0.f, lm_top_i = 0.f;
+      if constexpr (LM) {
+        lms_i = ctc_rl(lm_state, i); lmsum_i = ctc_rlf(lm_sum, i); lm_top_i = ctc_rlf(lm_top, i);
+        if (ctc_beam_rank(tot_i + mx, beta, len_i + 1) + lm_top_i < wr) continue;   // (the bar has risen)
+      } else {
+        if (ctc_beam_rank(tot_i + mx, beta, len_i + 1) < wr) continue;   // (the bar has risen)
+      }
       const unsigned long long kids = __ballot(live && pl == i);
       for (int hw = 0; hw < 2; ++hw)
       for (unsigned long long gm = groups[hw]; gm; gm &= gm - 1) {
@@ -1025,8 +1094,15 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         for (unsigned long long m = kids; m; m &= m - 1)
           if (c == ctc_rl(tok, __ffsll((long long)m) - 1)) ok = false;   // this extension is the stay of a beam of the set
         const float val = ((c == tok_i) ? pb_i : tot_i) + v;
-        const float rank = ctc_beam_rank(val, beta, len_i + 1);
+        float rank = ctc_beam_rank(val, beta, len_i + 1);
         const int key = W + i * C + c;
+        if constexpr (LM) {   // the bound without a look-up first; the lanes it leaves walk the tables for their exact rank
+          ok = ok && val != NEGINF && ctc_beam_beats(rank + lm_top_i, key, wr, wk);
+          if (ok) {
+            int next;
+            rank += ctc_beam_alpha_lm(lm.alpha, lmsum_i + ctc_beam_lm_lookup(lm, lms_i, c, next));
+          }
+        }
         for (unsigned long long m = __ballot(ok && val != NEGINF && ctc_beam_beats(rank, key, wr, wk)); m; m &= m - 1) {
           const int l = __ffsll((long long)m) - 1;
           const float r = ctc_rlf(rank, l);
@@ -1053,6 +1129,19 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     const unsigned long long hp_s = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(hp >> 32), src, 64) << 32) |
                                     (unsigned)__shfl((int)(unsigned)hp, src, 64);
     const float spb_s = __shfl(spb, src, 64), spnb_s = __shfl(spnb, src, 64), stot_s = __shfl(stot, src, 64);
+    int n_lm_state = 1;
+    float n_lm_sum = 0.f;
+    if constexpr (LM) {
+      const int lms_s = __shfl(lm_state, src, 64);
+      const float lmsum_s = __shfl(lm_sum, src, 64);
+      if (is_ext) {   // the look-up that ranked it, once more: its value and the state behind it
+        int next = 0;
+        n_lm_sum = lmsum_s + ctc_beam_lm_lookup(lm, lms_s, c_new, next);
+        n_lm_state = next;
+      } else if (keep) {
+        n_lm_state = lms_s; n_lm_sum = lmsum_s;
+      }
+    }
     const int pos = lane;
     int n_node = 0, n_par = -1, n_tok = -1, n_len = 0;
     unsigned long long n_h = CTC_BEAM_ROOT_HASH, n_hp = 0;
@@ -1068,6 +1157,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     }
     node = n_node; par = n_par; tok = n_tok; len = n_len; h = n_h; hp = n_hp;
     pb = n_pb; pnb = n_pnb; tot = n_tot;
+    if constexpr (LM) { lm_state = n_lm_state; lm_sum = n_lm_sum; }
     brank = keep ? e_rank : NEGINF;
     nb = __popcll(__ballot(keep));
     // ---- the next row
@@ -1110,17 +1200,43 @@ extern "C" long long mi355x_ctc_beam_workspace_elems(int Tmax, int beam) {
 
 // LDS rule: two rows of log-probabilities (this frame's and the next one's), 8 C bytes <= 64 KB, i.e. C <= 8192, whatever the beam
 // width: the candidates of a frame are streamed against the running top-`beam` in registers and never stored.
+static bool ctc_beam_args_ok(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len, void* score,
+                             void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta) {
+  if (!logp || !lens || !node_ws || !tokens || !tok_frame || !hyp_len || !score || !n_hyp) return false;
+  if (B <= 0 || Tmax <= 0 || C <= 0 || blank < 0 || blank >= C || beam < 1 || beam > CTC_BEAM_MAX) return false;
+  if (!(threshold > 0.f) || beta != beta || ((size_t)node_ws & 7)) return false;   // (NaN fails the first compare)
+  if ((long long)Tmax * beam > 0x3fffffffll) return false;   // node ids are 32-bit
+  return (size_t)C * 8 <= 64 * 1024;
+}
+#define CTC_BEAM_LAUNCH(LM, ...)                                                                                                        \
+  MI_LAUNCH(ctc_beam_kernel<LM>, dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp, (const long long*)lens,    \
+            (int2*)node_ws, (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, blank, beam, threshold, \
+            beta, __VA_ARGS__)
+
 extern "C" int mi355x_ctc_beam_decode(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
                                       void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold,
                                       float beta, void* stream) {
   mi_clear_errors();
-  if (!logp || !lens || !node_ws || !tokens || !tok_frame || !hyp_len || !score || !n_hyp) return MI_ERR_ARG;
-  if (B <= 0 || Tmax <= 0 || C <= 0 || blank < 0 || blank >= C || beam < 1 || beam > CTC_BEAM_MAX) return MI_ERR_ARG;
-  if (!(threshold > 0.f) || beta != beta || ((size_t)node_ws & 7)) return MI_ERR_ARG;   // (NaN fails the first compare)
-  if ((long long)Tmax * beam > 0x3fffffffll) return MI_ERR_ARG;   // node ids are 32-bit
-  const size_t shm = (size_t)C * 8;
-  if (shm > 64 * 1024) return MI_ERR_ARG;
-  MI_LAUNCH(ctc_beam_kernel, dim3(B), dim3(64), shm, (hipStream_t)stream, (const float*)logp, (const long long*)lens, (int2*)node_ws,
-            (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, blank, beam, threshold, beta);
+  if (!ctc_beam_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta))
+    return MI_ERR_ARG;
+  CTC_BEAM_LAUNCH(false, ctc_beam_no_lm{});
   return mi_check_launch();
 }
+
+// The same search with the n-gram model fused.  State 0's arc index is the label, so the blank has to be the last class.
+extern "C" int mi355x_ctc_beam_decode_lm(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
+                                         void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold,
+                                         float beta, const void* state_arc_begin, const void* arc_tok, const void* arc_logp,
+                                         const void* arc_next, const void* state_bo, const void* state_bo_next, int n_states,
+                                         int n_arcs, float alpha, float lm_ub, void* stream) {
+  mi_clear_errors();
+  if (!ctc_beam_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta))
+    return MI_ERR_ARG;
+  if (!state_arc_begin || !arc_tok || !arc_logp || !arc_next || !state_bo || !state_bo_next) return MI_ERR_ARG;
+  if (n_states < 2 || n_arcs < C - 1 || blank != C - 1 || !(alpha >= 0.f) || lm_ub != lm_ub) return MI_ERR_ARG;
+  const ctc_beam_lm lm = {(const int*)state_arc_begin, (const int*)arc_tok, (const float*)arc_logp, (const int*)arc_next,
+                          (const float*)state_bo, (const int*)state_bo_next, n_states, n_arcs, alpha, lm_ub};
+  CTC_BEAM_LAUNCH(true, lm);
+  return mi_check_launch();
+}
+#undef CTC_BEAM_LAUNCH

@@ -6,6 +6,7 @@ from .conv_asr import ConvASRDecoder  # noqa: F401
 from .ctc import CTCLoss  # noqa: F401
 from .ctc_decoding import (BeamBatchedCTCDecoder, CTCAligner, GreedyCTCDecoder, WER, ctc_decoder_from_config,  # noqa: F401
                            ctc_offsets, word_error_rate)
+from .ngram_lm import NGramLM  # noqa: F401
 from .rnnt_loss import RNNTLoss, RNNTLossNumba  # noqa: F401
 from .tdt_loss import TDTLoss, TDTLossNumba  # noqa: F401
 from .rnnt import RNNTDecoder, RNNTJoint  # noqa: F401

@@ -7,13 +7,16 @@ removal are one kernel launch (`mi355x_ctc_greedy_decode`); only the folded toke
 and only when text is asked for.
 
 `BeamBatchedCTCDecoder` is the reference's `strategy: beam_batch` (its batched GPU CTC beam search; `beam` there is the pyctcdecode /
-KenLM decoder and stays refused here), without language-model fusion.  What it runs is the classic CTC prefix beam search as
-include/mi355x_asr.h states it in full -- that statement, not a recollection of the reference's internals, is what the kernel and
-the test oracle (tests/ctc_beam_oracle.py) implement: pb / pnb per prefix, stays and extensions merged where they name the same
-prefix, the `beam_size` prefixes of the largest log-probability (+ beam_beta per token) kept per frame, one launch per batch.
+KenLM decoder and stays refused here), with or without shallow fusion of a token-level n-gram language model (`NGramLM`, read from
+an ARPA file: `beam.ngram_lm_arpa`, `beam.ngram_lm_alpha`; the reference's NGramGPULanguageModel).  What it runs is the classic CTC
+prefix beam search as include/mi355x_asr.h states it in full -- that statement, not a recollection of the reference's internals,
+is what the kernel and the test oracles (tests/ctc_beam_oracle.py, tests/ctc_beam_lm_oracle.py) implement: pb / pnb per prefix,
+stays and extensions merged where they name the same prefix, the `beam_size` prefixes of the largest log-probability (+ beam_beta
+per token, + ngram_lm_alpha * the LM's log-probability of the prefix) kept per frame, one launch per batch.
 """
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Sequence
 
 import torch
@@ -105,19 +108,30 @@ class GreedyCTCDecoder(_CTCText):
 
 
 class BeamBatchedCTCDecoder(_CTCText):
-    """CTC prefix beam search without a language model, on the device (`mi355x_ctc_beam_decode`): the `beam_batch` strategy.
-    `beam_size` hypotheses per utterance (1..64), `beam_threshold`: a class is looked at in a frame only if its log-probability is
-    within that much of the frame's best (inf: every class), `beam_beta`: bonus per token; the score of a hypothesis is the
-    log-probability of its LABEL SEQUENCE (all of its alignments the search kept) + beam_beta * length.
+    """CTC prefix beam search on the device (`mi355x_ctc_beam_decode`, with `ngram_lm` `mi355x_ctc_beam_decode_lm`): the `beam_batch`
+    strategy.  `beam_size` hypotheses per utterance (1..64), `beam_threshold`: a class is looked at in a frame only if its
+    log-probability is within that much of the frame's best (inf: every class), `beam_beta`: bonus per token, `ngram_lm`: an `NGramLM`
+    over the labels, fused with weight `ngram_lm_alpha` >= 0; the score of a hypothesis is the log-probability of its LABEL SEQUENCE
+    (all of its alignments the search kept) + beam_beta * length + ngram_lm_alpha * the LM's log-probability of the sequence.
     `return_best_hypothesis=False` makes `__call__` return the n-best lists."""
 
     confidence_cfg = None   # (the greedy decoder's attribute: confidences are not defined for the beam search)
 
     def __init__(self, vocabulary: Optional[Sequence[str]] = None, blank_id: Optional[int] = None, beam_size: int = 4,
-                 return_best_hypothesis: bool = True, beam_threshold: float = 20.0, beam_beta: float = 0.0):
+                 return_best_hypothesis: bool = True, beam_threshold: float = 20.0, beam_beta: float = 0.0, ngram_lm=None,
+                 ngram_lm_alpha: float = 0.0):
         self._set_labels(vocabulary, blank_id)
         self.beam_size, self.return_best_hypothesis = int(beam_size), bool(return_best_hypothesis)
         self.beam_threshold, self.beam_beta = float(beam_threshold), float(beam_beta)
+        self.ngram_lm, self.ngram_lm_alpha = ngram_lm, float(ngram_lm_alpha)
+        if not self.ngram_lm_alpha >= 0:
+            raise ValueError(f"ngram_lm_alpha must be >= 0; got {ngram_lm_alpha}")
+        if ngram_lm is not None:
+            from .ngram_lm import NGramLM
+            if not isinstance(ngram_lm, NGramLM):
+                raise TypeError(f"ngram_lm must be an NGramLM (NGramLM.from_arpa), got {type(ngram_lm).__name__}")
+            if ngram_lm.vocab_size != self.blank_id:
+                raise ValueError(f"the LM has {ngram_lm.vocab_size} labels, the decoder {self.blank_id} (blank_id = the label count)")
         if not 1 <= self.beam_size <= 64:
             raise ValueError(f"beam_size must lie in 1..64 (one wave holds the beams of an utterance); got {beam_size}")
         if not self.beam_threshold > 0:
@@ -130,6 +144,9 @@ class BeamBatchedCTCDecoder(_CTCText):
         _check_log_probs(log_probs)
         lp = log_probs.to(torch.float32).contiguous()
         lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
+        if self.ngram_lm is not None:
+            return ops.ctc_beam_decode_lm(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, self.ngram_lm,
+                                          self.ngram_lm_alpha)
         return ops.ctc_beam_decode(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta)
 
     def nbest(self, log_probs, lengths=None):
@@ -150,12 +167,37 @@ class BeamBatchedCTCDecoder(_CTCText):
 _LM_KEYS = ("ngram_lm_model", "kenlm_path")
 
 
+def _ngram_lm_from_config(beam, vocabulary, what):
+    """the LM of a `beam` sub-section (None without one): `ngram_lm_arpa` = the path of an ARPA text file or an NGramLM,
+    `ngram_lm_token_offset` (100; None: the file's words are the vocabulary's strings).  KenLM binaries and `.nemo` LM archives are
+    not read: the reference's keys for them are refused by name."""
+    for key in _LM_KEYS:
+        if beam.get(key):
+            raise NotImplementedError(f"{what} decoding: `beam.{key}` (KenLM binaries and .nemo LM archives are not read here; give "
+                                      "an ARPA text file under `beam.ngram_lm_arpa`)")
+    arpa = beam.get("ngram_lm_arpa")
+    if arpa is None or (isinstance(arpa, str) and not arpa):
+        if float(beam.get("ngram_lm_alpha") or 0.0) != 0.0:
+            raise NotImplementedError(f"{what} decoding: `beam.ngram_lm_alpha` != 0 without `beam.ngram_lm_arpa` (there is no language "
+                                      "model to weigh)")
+        return None
+    from .ngram_lm import NGramLM
+    if isinstance(arpa, NGramLM):
+        return arpa
+    if not os.path.isfile(str(arpa)):
+        raise FileNotFoundError(f"{what} decoding: `beam.ngram_lm_arpa` = {arpa!r} is not a file")
+    if vocabulary is None:   # (the section is only being checked)
+        return None
+    offset = beam.get("ngram_lm_token_offset", 100)
+    return NGramLM.from_arpa(arpa, len(vocabulary), token_offset=offset, vocabulary=list(vocabulary) if offset is None else None)
+
+
 def ctc_decoder_from_config(decoding_cfg, vocabulary=None, what: str = "CTC"):
     """The one place that reads a CTC head's `decoding` section (`what` names the head in messages): checks it and, with a
     vocabulary, returns its decoding object -- GreedyCTCDecoder for `greedy` / `greedy_batch`, BeamBatchedCTCDecoder for
-    `beam_batch` (its `beam` sub-section: beam_size, return_best_hypothesis, beam_threshold, beam_beta).  Everything else the reference
-    knows (beam = pyctcdecode / KenLM, flashlight, wfst: ctc_decoding.py:231-236) and language-model fusion raise
-    NotImplementedError."""
+    `beam_batch` (its `beam` sub-section: beam_size, return_best_hypothesis, beam_threshold, beam_beta, ngram_lm_arpa,
+    ngram_lm_alpha, ngram_lm_token_offset).  Everything else the reference knows (beam = pyctcdecode / KenLM, flashlight, wfst:
+    ctc_decoding.py:231-236), its keys for KenLM / .nemo language models, and an LM weight without an LM raise NotImplementedError."""
     dcfg = dict(decoding_cfg or {})
     strategy = str(dcfg.get("strategy", "greedy_batch"))
     if strategy in ("greedy", "greedy_batch"):
@@ -163,19 +205,19 @@ def ctc_decoder_from_config(decoding_cfg, vocabulary=None, what: str = "CTC"):
     if strategy != "beam_batch":
         raise NotImplementedError(f"{what} decoding strategy '{strategy}' (implemented: greedy, greedy_batch, beam_batch)")
     beam = dict(dcfg.get("beam") or {})
-    for key in _LM_KEYS:
-        if beam.get(key):
-            raise NotImplementedError(f"{what} decoding: `beam.{key}` (language-model fusion is not provided; beam_batch runs without one)")
-    if float(beam.get("ngram_lm_alpha") or 0.0) != 0.0:
-        raise NotImplementedError(f"{what} decoding: `beam.ngram_lm_alpha` != 0 (language-model fusion is not provided)")
+    alpha = float(beam.get("ngram_lm_alpha") or 0.0)
+    if alpha < 0:
+        raise ValueError(f"{what} decoding: `beam.ngram_lm_alpha` must be >= 0; got {alpha}")
     from .confidence import confidence_from
     if confidence_from(dcfg.get("confidence_cfg")) is not None:
         raise NotImplementedError(f"{what} decoding: `confidence_cfg` with strategy 'beam_batch' (confidences come from the greedy search)")
+    lm = _ngram_lm_from_config(beam, vocabulary, what)
     if vocabulary is None:
         return None
     return BeamBatchedCTCDecoder(vocabulary=list(vocabulary), beam_size=beam.get("beam_size", 4),
                                  return_best_hypothesis=beam.get("return_best_hypothesis", True),
-                                 beam_threshold=beam.get("beam_threshold", 20.0), beam_beta=beam.get("beam_beta", 0.0))
+                                 beam_threshold=beam.get("beam_threshold", 20.0), beam_beta=beam.get("beam_beta", 0.0),
+                                 ngram_lm=lm, ngram_lm_alpha=alpha)
 
 
 def ctc_offsets(tokens: Sequence[str], starts: Sequence[int], ends: Sequence[int], word_pieces: bool = False):

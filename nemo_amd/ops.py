@@ -488,10 +488,27 @@ def ctc_align(logp, targets, in_len, tgt_len, blank):
 
 
 def ctc_beam_decode(logp, lens, blank, beam_size, beam_threshold=20.0, beam_beta=0.0):
-    """CTC prefix beam search without a language model (mi355x_ctc_beam_decode): logp f32 [B,T,C] contiguous, lens i64 [B] (None: T
-    for every utterance) -> (tokens i32 [B,W,T]: hypotheses best first, -1 padded; tok_frame i32 [B,W,T]: the frame each token was
-    created in; hyp_len i32 [B,W]; score f32 [B,W]: tot + beam_beta * len, -inf for absent hypotheses; n_hyp i32 [B]).  The node
-    workspace (2 * T * W integers per utterance) is allocated here and dropped."""
+    """CTC prefix beam search (mi355x_ctc_beam_decode; `ctc_beam_decode_lm` fuses an n-gram model): logp f32 [B,T,C] contiguous, lens
+    i64 [B] (None: T for every utterance) -> (tokens i32 [B,W,T]: hypotheses best first, -1 padded; tok_frame i32 [B,W,T]: the frame
+    each token was created in; hyp_len i32 [B,W]; score f32 [B,W]: tot + beam_beta * len, -inf for absent hypotheses; n_hyp i32 [B]).
+    The node workspace (2 * T * W integers per utterance) is allocated here and dropped."""
+    return _ctc_beam(logp, lens, blank, beam_size, beam_threshold, beam_beta, None, 0.0)
+
+
+def ctc_beam_decode_lm(logp, lens, blank, beam_size, beam_threshold, beam_beta, lm, alpha):
+    """`ctc_beam_decode` with shallow fusion of an n-gram model (mi355x_ctc_beam_decode_lm): the hypotheses are ranked by
+    (tot + beam_beta * len) + alpha * lm(prefix), which is also the score returned.  `lm` is an `NGramLM` (modules/ngram_lm.py), not
+    loose tensors: only tables its loader built and checked reach the kernel.  alpha = 0 gives the bits of `ctc_beam_decode`."""
+    from .modules.ngram_lm import NGramLM
+    if not isinstance(lm, NGramLM):
+        raise TypeError(f"ctc_beam_decode_lm: `lm` must be an NGramLM, got {type(lm).__name__}")
+    if lm.vocab_size != logp.shape[2] - 1:
+        raise ValueError(f"ctc_beam_decode_lm: the LM has {lm.vocab_size} labels, the log-probabilities {logp.shape[2]} classes "
+                         f"(labels + the blank)")
+    return _ctc_beam(logp, lens, blank, beam_size, beam_threshold, beam_beta, lm, alpha)
+
+
+def _ctc_beam(logp, lens, blank, beam_size, beam_threshold, beam_beta, lm, alpha):
     B, T, C_ = logp.shape
     W = int(beam_size)
     if lens is None:
@@ -501,9 +518,14 @@ def ctc_beam_decode(logp, lens, blank, beam_size, beam_threshold=20.0, beam_beta
     Wa = max(W, 0)   # (a width the entry refuses still reaches it, for its ValueError)
     tokens, tok_frame = torch.empty(B, Wa, T, **i32), torch.empty(B, Wa, T, **i32)
     hyp_len, score, n_hyp = torch.empty(B, Wa, **i32), torch.empty(B, Wa, **f32), torch.empty(B, **i32)
-    check(lib.mi355x_ctc_beam_decode(_ptr(logp), _ptr(lens), _ptr(ws), _ptr(tokens), _ptr(tok_frame), _ptr(hyp_len), _ptr(score),
-                                     _ptr(n_hyp), B, T, C_, int(blank), W, float(beam_threshold), float(beam_beta), _stream()),
-          "ctc_beam_decode")
+    args = (_ptr(logp), _ptr(lens), _ptr(ws), _ptr(tokens), _ptr(tok_frame), _ptr(hyp_len), _ptr(score), _ptr(n_hyp), B, T, C_,
+            int(blank), W, float(beam_threshold), float(beam_beta))
+    if lm is None:
+        check(lib.mi355x_ctc_beam_decode(*args, _stream()), "ctc_beam_decode")
+    else:
+        tables = lm.to(logp.device)   # (cached on the LM: they outlive the launch)
+        check(lib.mi355x_ctc_beam_decode_lm(*args, *(_ptr(t) for t in tables), lm.num_states, lm.num_arcs, float(alpha),
+                                            float(lm.lm_ub), _stream()), "ctc_beam_decode_lm")
     return tokens, tok_frame, hyp_len, score, n_hyp
 
 

@@ -1,19 +1,24 @@
 """CTC prefix beam search on one GPU (profiles/ctc_beam.md is made with this).
 
 Per shape (B, T, C), beam width W and threshold, `--rounds` rounds; in every round each candidate runs its launches between two
-device events, the candidates alternating inside the round (same process, same buffers), so that drift of the box hits all of
-them alike:
+device events, the candidates alternating inside the round (same process, same buffers; every other round in reverse order), so
+that drift of the box hits all of them alike:
   * mi355x_ctc_beam_decode for every (W, threshold) asked for,
+  * with `--lm ORDER` mi355x_ctc_beam_decode_lm at the same settings with the n-gram model of the tests' generator
+    (tests/ctc_beam_lm_oracle.py `make_lm(0, C-1, ORDER)`, through ARPA text and NGramLM.from_arpa) at `--alpha`, and once more at
+    alpha = 0: the same selections as the LM-less search, so the difference to it is what carrying the LM state costs, and the rest
+    of the fused time is look-ups and the candidates they let in,
   * mi355x_ctc_greedy_decode at the same shape: the scale (one pass over the log-probabilities, no search),
-  * mi355x_ctc_greedy_decode and mi355x_ctc_greedy_decode_ts of every library given with `--lib name=path` (e.g. a build of the
-    parent commit), alternating with the in-tree library's: the spread between builds of entry points this search does not touch.
+  * mi355x_ctc_greedy_decode, mi355x_ctc_greedy_decode_ts and mi355x_ctc_beam_decode of every library given with `--lib name=path`
+    (e.g. a build of the parent commit), alternating with the in-tree library's: the spread between builds of entry points a
+    change does not touch.
 Input: log-softmax of 1.5 * N(0,1) with +5 on the class of a random path (blank with probability 0.6), the generator of the tests --
 peaked like a trained model's output, so that the threshold prunes; lengths = T.  The launches of a candidate per round are sized
 from one timed launch so that a round of it takes about `--round-ms`.  Reported per candidate: median, min and max of the
 per-round means, in microseconds per launch.
 
     python tools/ctc_beam_bench.py [--shapes 32,501,129 32,501,1025] [--beams 4 16 64] [--thresholds 20 inf] [--rounds 7]
-                                   [--lib parent=PATH ...] [--json OUT]
+                                   [--lm ORDER] [--alpha 0.5] [--lib parent=PATH ...] [--json OUT]
 """
 import argparse
 import ctypes
@@ -21,18 +26,20 @@ import json
 import os
 import statistics
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 dev = "cuda"
 GREEDY = ("mi355x_ctc_greedy_decode", "mi355x_ctc_greedy_decode_ts")
+BEAM = "mi355x_ctc_beam_decode"
 
 
 def load(path):
     from nemo_amd import _lib
     lib = ctypes.CDLL(path)
-    for name in GREEDY:
+    for name in GREEDY + (BEAM,):
         getattr(lib, name).argtypes = _lib.SIGNATURES[name]
         getattr(lib, name).restype = ctypes.c_int
     return lib
@@ -55,9 +62,9 @@ def rounds(cands, n_rounds, round_ms):
         torch.cuda.synchronize()
         iters[k] = max(2, min(200, int(round_ms * 1e3 / max(1.0, timed(fn, 1)))))
     per = {k: [] for k in cands}
-    for _ in range(n_rounds):
-        for k, fn in cands.items():
-            per[k].append(timed(fn, iters[k]))
+    for r in range(n_rounds):   # every other round backwards: no candidate always runs behind the same neighbour
+        for k in (list(cands) if r % 2 == 0 else list(cands)[::-1]):
+            per[k].append(timed(cands[k], iters[k]))
     return {k: dict(median_us=round(statistics.median(v), 1), min_us=round(min(v), 1), max_us=round(max(v), 1), iters=iters[k])
             for k, v in per.items()}
 
@@ -70,7 +77,17 @@ def make_logp(B, T, C, seed=0):
     return torch.log_softmax(x, -1).to(dev)
 
 
-def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms):
+def make_ngram_lm(V, order):
+    """the tests' model, written as ARPA text and read back the way a user's model is"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import ctc_beam_lm_oracle as L
+    from nemo_amd.modules import NGramLM
+    with tempfile.TemporaryDirectory() as d:
+        L.write_arpa(L.make_lm(0, V, order), os.path.join(d, "lm.arpa"))
+        return NGramLM.from_arpa(os.path.join(d, "lm.arpa"), V)
+
+
+def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, alpha=0.5):
     from nemo_amd import _lib
     lib = _lib.lib
     logp = make_logp(B, T, C)
@@ -85,10 +102,20 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms):
     stream = torch.cuda.current_stream().cuda_stream
     p = lambda t: t.data_ptr()   # noqa: E731
 
-    def beam(W, th):
+    def beam(W, th, l=lib):
         def fn():
-            rc = lib.mi355x_ctc_beam_decode(p(logp), p(lens), p(ws), p(tokens), p(frames), p(hyp_len), p(score), p(n_hyp), B, T, C, C - 1,
-                                            W, th, 0.0, stream)
+            rc = l.mi355x_ctc_beam_decode(p(logp), p(lens), p(ws), p(tokens), p(frames), p(hyp_len), p(score), p(n_hyp), B, T, C, C - 1,
+                                          W, th, 0.0, stream)
+            assert rc == 0, rc
+        return fn
+
+    lm = make_ngram_lm(C - 1, lm_order) if lm_order else None
+    tables = [p(t) for t in lm.to(dev)] if lm else None
+
+    def beam_lm(W, th, a):
+        def fn():
+            rc = lib.mi355x_ctc_beam_decode_lm(p(logp), p(lens), p(ws), p(tokens), p(frames), p(hyp_len), p(score), p(n_hyp), B, T, C,
+                                               C - 1, W, th, 0.0, *tables, lm.num_states, lm.num_arcs, a, lm.lm_ub, stream)
             assert rc == 0, rc
         return fn
 
@@ -107,7 +134,21 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms):
     for W in beams:
         for th in thresholds:
             cands[f"beam W={W} threshold={th}"] = beam(W, th)
+            for name, l in libs.items():
+                cands[f"beam[{name}] W={W} threshold={th}"] = beam(W, th, l)
+            if lm:
+                cands[f"beam+lm W={W} threshold={th} alpha={alpha}"] = beam_lm(W, th, alpha)
+                cands[f"beam+lm W={W} threshold={th} alpha=0"] = beam_lm(W, th, 0.0)
     row = dict(shape=dict(B=B, T=T, C=C), **rounds(cands, n_rounds, round_ms))
+    if lm:
+        row["lm"] = dict(order=lm.order, states=lm.num_states, arcs=lm.num_arcs, lm_ub=lm.lm_ub)
+        # what the fusion changed at the widest setting: utterances whose best hypothesis differs from the LM-less search's
+        beam(Wmax, thresholds[0])()
+        torch.cuda.synchronize()
+        t0, l0 = tokens.clone(), hyp_len.clone()
+        beam_lm(Wmax, thresholds[0], alpha)()
+        torch.cuda.synchronize()
+        row["best_changed_by_lm"] = f"{sum(int(l0[b, 0]) != int(hyp_len[b, 0]) or not torch.equal(t0[b, 0], tokens[b, 0]) for b in range(B))}/{B}"
     # what the search found at the widest setting: hypotheses per utterance and how often the best one differs from the greedy one
     beam(Wmax, thresholds[0])(); greedy(lib, False)()
     torch.cuda.synchronize()
@@ -124,6 +165,8 @@ def main():
     ap.add_argument("--thresholds", nargs="+", type=float, default=[20.0, float("inf")])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--round-ms", type=float, default=50.0)
+    ap.add_argument("--lm", type=int, default=0, metavar="ORDER", help="also time the search with an n-gram model of this order fused")
+    ap.add_argument("--alpha", type=float, default=0.5, help="the fusion weight of the --lm runs")
     ap.add_argument("--lib", nargs="*", default=[], help="name=path of further builds of the library")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -131,7 +174,7 @@ def main():
     out = dict(device=torch.cuda.get_device_name(0), rounds=args.rounds, round_ms=args.round_ms, shapes=[])
     for s in args.shapes:
         B, T, C = (int(x) for x in s.split(","))
-        row = one_shape(B, T, C, args.beams, args.thresholds, libs, args.rounds, args.round_ms)
+        row = one_shape(B, T, C, args.beams, args.thresholds, libs, args.rounds, args.round_ms, args.lm, args.alpha)
         out["shapes"].append(row)
         print(json.dumps(row), flush=True)
     if args.json:

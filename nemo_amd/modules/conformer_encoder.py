@@ -21,16 +21,13 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..core import (AcousticEncodedRepresentation, BoolType, ChannelType, LengthsType, NeuralModule, NeuralType, SpectrogramType,
+from ..core import (AcousticEncodedRepresentation, BoolType, ChannelType, LengthsType, NeuralType, SpectrogramType,
                     typecheck)
-from ..flat import FlatParams
-from ..packing import PackPlan
+from ..packing import _pad8
+from . import engine
+from .engine import EngineModule
 
 INF_VAL = 10000.0
-
-
-def _pad8(n):
-    return (n + 7) // 8 * 8
 
 
 # ------------------------------------------------------------------------------------------------ parameter containers
@@ -275,7 +272,7 @@ class _GraphSet:
         self.inherited = False  # the decision was taken over from another padded length of the same configuration (no trial)
 
 
-class ConformerEncoder(NeuralModule):
+class ConformerEncoder(EngineModule):
     @property
     def input_types(self):
         return OrderedDict({
@@ -393,11 +390,12 @@ class ConformerEncoder(NeuralModule):
         self.captured = {}
         self.max_audio_length = pos_emb_max_len
         self.streaming_cfg = None   # CacheAwareStreamingConfig, filled by setup_streaming_params (lazily by the first stream step)
+        # linear_pos weights of all layers sit together at the tail: their gradients come from ONE batched GEMM
         self._init_engine(compute_dtype, tail=lambda n: n.endswith("self_attn.linear_pos.weight"))
 
     def _init_engine(self, compute_dtype, tail=None):
         """engine state shared by the encoders built on this class (not part of the state-dict)"""
-        self.compute_dtype = compute_dtype  # None: bf16 under torch autocast(bf16), else fp32
+        super()._init_engine(compute_dtype, tail=tail)
         # SyncBatchNorm semantics across data-parallel ranks (trainer.sync_batchnorm: true in the recipe)
         self.sync_batchnorm = True
         # The element count of the synchronised statistics is the SUM of the ranks' own B*T' (torch.nn.SyncBatchNorm gathers
@@ -425,9 +423,6 @@ class ConformerEncoder(NeuralModule):
         self.fuse_layer_boundary_norms = os.environ.get("MI355X_LN2", "1") != "0"
         self.fuse_boundary_bwd = os.environ.get("MI355X_LN2_BWD", "1") != "0"  # ... and their backwards (mi355x_layernorm2_bwd)
         self.flash_delta_residual = os.environ.get("MI355X_FLASH_DELTA_LO", "1") != "0"  # (A/B switch of the delta fix)
-        self.grad_ready_hook = None  # callable(start, end) on the flat gradient buffer (data-parallel bucketing)
-        # linear_pos weights of all layers sit together at the tail: their gradients come from ONE batched GEMM
-        self._flatp = FlatParams(self, tail=tail)
         self.wgrad_side_stream = os.environ.get("MI355X_WGRAD_STREAM", "1") != "0"
         self._wg_stream = None
         self._wgrad_join_per_layer = True
@@ -463,13 +458,9 @@ class ConformerEncoder(NeuralModule):
         self._saving = False        # the forward in progress keeps its activations for a backward
         self.dpos_side_stream = os.environ.get("MI355X_DPOS_STREAM", "1") != "0"
         self.sub_wgrad_side_stream = os.environ.get("MI355X_SUB_WGRAD_STREAM", "1") != "0"
-        self._plans = {}
         self._ws = {}
         self._ws_retired = []
         self._pos_cache = {}
-        self._step_seed = 0
-        self._weights_version = -1
-        self._token = None
         # ---- replayable launch sequences (nemo_amd/graphs.py).  MI355X_GRAPHS=0 keeps every step on the eager sequencer.
         # MI355X_GRAPHS: 0 = always live launches, 1 = always replay, auto (default) = time both on the device, keep the faster
         _g = os.environ.get("MI355X_GRAPHS", "auto")
@@ -505,7 +496,6 @@ class ConformerEncoder(NeuralModule):
         self._fwd_serial = 0        # forwards so far: a backward must belong to the latest one (its activations live in the arena)
         self._capture = None        # the SegmentedCapture while a sequence is being recorded
         self._wg_forked = False     # recording: the weight-gradient stream has joined the capture and not re-joined yet
-        self._force_pack = False    # record the weight-image pack unconditionally (a replayed forward always re-packs)
         self._step_word = None      # device-side dropout step word (int32), advanced by the forward graph
 
     # ------------------------------------------------------------------ reference API surface
@@ -517,19 +507,6 @@ class ConformerEncoder(NeuralModule):
         cached table; our positional table is built per T on demand, so only the bookkeeping remains."""
         if seq_length > self.max_audio_length:
             self.set_max_audio_length(seq_length)
-
-    def flat_parameters(self) -> FlatParams:
-        self._flatp.ensure()
-        return self._flatp
-
-    def weights_updated(self):
-        """call after an optimizer step / load_state_dict: GEMM operand images are re-packed on next forward"""
-        self._weights_version += 1
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self.weights_updated()
-        return r
 
     # ------------------------------------------------------------------ forward (typed)
     @staticmethod
@@ -649,11 +626,9 @@ class ConformerEncoder(NeuralModule):
             length = audio_signal.new_full((audio_signal.size(0),), audio_signal.size(1 if bypass_pre_encode else -1), dtype=torch.int64)
         self._flatp.ensure(audio_signal.device)
         self._pick_ctx()
-        if self._token is None or self._token.device != audio_signal.device:
-            self._token = torch.zeros(1, device=audio_signal.device, requires_grad=True)
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if need_grad:
-            res = _EncoderFn.apply(audio_signal, length, self._token, self)
+            res = _EncoderFn.apply(audio_signal, length, self._tok(audio_signal.device), self)
             self.captured = dict(zip(self.capture_layers, res[2:]))
             return res[0], res[1]
         out, enc_len, S_ = self._forward_impl(audio_signal, length, save=bool(self.capture_layers))
@@ -728,13 +703,6 @@ class ConformerEncoder(NeuralModule):
                 self.streaming_cfg.drop_extra_pre_encoded = prev
 
     # ------------------------------------------------------------------ helpers
-    def _cdt(self):
-        if self.compute_dtype is not None:
-            return self.compute_dtype
-        if torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() == torch.bfloat16:
-            return torch.bfloat16
-        return torch.float32
-
     def _new(self, *shape, dtype, device):
         """a tensor of this step's forward / backward: from the phase's arena when one is active, else from torch's allocator"""
         a = self._arena
@@ -770,85 +738,57 @@ class ConformerEncoder(NeuralModule):
             self._ws[key] = t
         return t[:n].view(shape)
 
-    def _plan(self, cdt, device):
+    def _plan_key(self, cdt, device):
         # (the geometry -- head width of the packed attention images -- follows run-time flags: use_flash_attention, flash_pad_heads)
-        key = (cdt, str(device), self._flatp.generation, self._geometry(cdt))
-        plan = self._plans.get(key)
-        if plan is None:
-            self._plans = {}  # parameters moved: drop images of the old storage
-            p = PackPlan(cdt, device)
-            pf = PackPlan(torch.float32, device)
-            srcs = []
-            pe = self.pre_encode
-            C_, F2 = pe._conv_channels, pe._feat_after
-            if self.subsampling == "striding":
-                p.add_conv3x3("pre.w2", pe.conv[2].weight.data); p.add_conv3x3("pre.w2t", pe.conv[2].weight.data, transpose=True)
-                # conv2 input-gradient as four implicit GEMMs, one per (t1, f1) parity class: image [ci][(slot, co)] of the
-                # taps that reach the class (a stride-2 3x3 conv touches an even position through k = 1 only, an odd one
-                # through 0, 2)
-                w2flat = pe.conv[2].weight.data.view(-1)
-                for par_t in (0, 1):
-                    for par_f in (0, 1):
-                        slots = self._dgrad_slots(par_t, par_f, pe._pad)
-                        name = f"pre.w2d{par_t}{par_f}"
-                        p.new_image(name, C_, len(slots) * C_)
-                        for si_, (kh, kw) in enumerate(slots):
-                            p.add_block(name, w2flat[kh * 3 + kw:], C_, C_, col_off=si_ * C_, sr1=9, sc1=9 * C_)
-            else:  # 'dw_striding': the pointwise convolutions are plain [C, C] GEMM operands
-                for si_, (_, pw) in enumerate(pe.dw_stages()):
-                    p.add_matrix(f"pre.pw{si_}", pw.weight.data.view(C_, C_))
-                    p.add_matrix(f"pre.pw{si_}t", pw.weight.data.view(C_, C_), True)
-            p.add_fc_permuted("pre.out", pe.out.weight.data, C_, F2)
-            p.add_fc_permuted("pre.outt", pe.out.weight.data, C_, F2, transpose=True)
-            d_, H_, dk = self.d_model, self.n_heads, self.d_k
-            _, dkp, dA = self._geometry(cdt)
-            for i, L in enumerate(self.layers):
-                for ff, m in (("ff1", L.feed_forward1), ("ff2", L.feed_forward2)):
-                    if self._ffn_fused_ok(cdt):
-                        # the fused feed-forward kernels (csrc/ffn.hip) stream their weights in the order their steps consume them
-                        p.add_ffn(f"L{i}.{ff}", m.linear1.weight.data, m.linear2.weight.data)
-                        continue
-                    p.add_matrix(f"L{i}.{ff}.w1", m.linear1.weight.data); p.add_matrix(f"L{i}.{ff}.w1t", m.linear1.weight.data, True)
-                    p.add_matrix(f"L{i}.{ff}.w2", m.linear2.weight.data); p.add_matrix(f"L{i}.{ff}.w2t", m.linear2.weight.data, True)
-                a = L.self_attn
-                qkv = [a.linear_q.weight.data, a.linear_k.weight.data, a.linear_v.weight.data]
-                if dkp == dk:
-                    p.add_concat(f"L{i}.att.wqkv", qkv); p.add_concat(f"L{i}.att.wqkvt", qkv, transpose=True)
-                    p.add_matrix(f"L{i}.att.wo", a.linear_out.weight.data); p.add_matrix(f"L{i}.att.wot", a.linear_out.weight.data, True)
-                    p.add_matrix(f"L{i}.att.wpos", a.linear_pos.weight.data)
-                    pf.new_image(f"L{i}.att.bqkv", 1, 3 * d_)
-                    for j, b in enumerate((a.linear_q.bias.data, a.linear_k.bias.data, a.linear_v.bias.data)):
-                        pf.add_block(f"L{i}.att.bqkv", b, 1, d_, col_off=j * d_, sr1=0, sc1=1)
-                else:  # zero-padded heads (see _geometry): head h = rows / columns h*dkp .. h*dkp + dk of the images
-                    p.new_image(f"L{i}.att.wqkv", 3 * dA, d_); p.new_image(f"L{i}.att.wqkvt", d_, 3 * dA)
-                    p.new_image(f"L{i}.att.wpos", dA, d_)
-                    p.new_image(f"L{i}.att.wo", d_, dA); p.new_image(f"L{i}.att.wot", dA, d_)
-                    wo = a.linear_out.weight.data  # [d, H*dk]
-                    pf.new_image(f"L{i}.att.bqkv", 1, 3 * dA)
-                    pf.new_image(f"L{i}.att.bu", 1, dA); pf.new_image(f"L{i}.att.bv", 1, dA)
-                    for h in range(H_):
-                        for j, w in enumerate(qkv):
-                            p.add_block(f"L{i}.att.wqkv", w.view(-1)[h * dk * d_:], dk, d_, row_off=j * dA + h * dkp, sr1=d_, sc1=1)
-                            p.add_block(f"L{i}.att.wqkvt", w.view(-1)[h * dk * d_:], d_, dk, col_off=j * dA + h * dkp, sr1=1, sc1=d_)
-                        p.add_block(f"L{i}.att.wpos", a.linear_pos.weight.data.view(-1)[h * dk * d_:], dk, d_, row_off=h * dkp,
-                                    sr1=d_, sc1=1)
-                        p.add_block(f"L{i}.att.wo", wo.view(-1)[h * dk:], d_, dk, col_off=h * dkp, sr1=d_, sc1=1)
-                        p.add_block(f"L{i}.att.wot", wo.view(-1)[h * dk:], dk, d_, row_off=h * dkp, sr1=1, sc1=d_)
-                        for j, b in enumerate((a.linear_q.bias.data, a.linear_k.bias.data, a.linear_v.bias.data)):
-                            pf.add_block(f"L{i}.att.bqkv", b[h * dk:], 1, dk, col_off=j * dA + h * dkp, sr1=0, sc1=1)
-                        pf.add_block(f"L{i}.att.bu", a.pos_bias_u.data.view(-1)[h * dk:], 1, dk, col_off=h * dkp, sr1=0, sc1=1)
-                        pf.add_block(f"L{i}.att.bv", a.pos_bias_v.data.view(-1)[h * dk:], 1, dk, col_off=h * dkp, sr1=0, sc1=1)
-                c = L.conv
-                p.add_matrix(f"L{i}.conv.pw1", c.pointwise_conv1.weight.data); p.add_matrix(f"L{i}.conv.pw1t", c.pointwise_conv1.weight.data, True)
-                p.add_matrix(f"L{i}.conv.pw2", c.pointwise_conv2.weight.data); p.add_matrix(f"L{i}.conv.pw2t", c.pointwise_conv2.weight.data, True)
-            p.finalize(); pf.finalize()
-            plan = (p, pf, None, -2)
-            self._plans[key] = plan
-        if plan[3] != self._weights_version or self._force_pack:
-            plan[0].run(); plan[1].run()
-            plan = (plan[0], plan[1], plan[2], self._weights_version)
-            self._plans[key] = plan
-        return plan[0], plan[1]
+        return super()._plan_key(cdt, device) + (self._geometry(cdt),)
+
+    def _declare_images(self, p, pf):
+        cdt = p.dtype
+        pe = self.pre_encode
+        C_, F2 = pe._conv_channels, pe._feat_after
+        if self.subsampling == "striding":
+            p.add_conv3x3("pre.w2", pe.conv[2].weight.data); p.add_conv3x3("pre.w2t", pe.conv[2].weight.data, transpose=True)
+            # conv2 input-gradient as four implicit GEMMs, one per (t1, f1) parity class: image [ci][(slot, co)] of the
+            # taps that reach the class (a stride-2 3x3 conv touches an even position through k = 1 only, an odd one
+            # through 0, 2)
+            w2flat = pe.conv[2].weight.data.view(-1)
+            for par_t in (0, 1):
+                for par_f in (0, 1):
+                    slots = self._dgrad_slots(par_t, par_f, pe._pad)
+                    name = f"pre.w2d{par_t}{par_f}"
+                    p.new_image(name, C_, len(slots) * C_)
+                    for si_, (kh, kw) in enumerate(slots):
+                        p.add_block(name, w2flat[kh * 3 + kw:], C_, C_, col_off=si_ * C_, sr1=9, sc1=9 * C_)
+        else:  # 'dw_striding': the pointwise convolutions are plain [C, C] GEMM operands
+            for si_, (_, pw) in enumerate(pe.dw_stages()):
+                p.add_matrix(f"pre.pw{si_}", pw.weight.data.view(C_, C_))
+                p.add_matrix(f"pre.pw{si_}t", pw.weight.data.view(C_, C_), True)
+        p.add_fc_permuted("pre.out", pe.out.weight.data, C_, F2)
+        p.add_fc_permuted("pre.outt", pe.out.weight.data, C_, F2, transpose=True)
+        d_, H_, dk = self.d_model, self.n_heads, self.d_k
+        _, dkp, dA = self._geometry(cdt)
+        for i, L in enumerate(self.layers):
+            for ff, m in (("ff1", L.feed_forward1), ("ff2", L.feed_forward2)):
+                if self._ffn_fused_ok(cdt):
+                    # the fused feed-forward kernels (csrc/ffn.hip) stream their weights in the order their steps consume them
+                    p.add_ffn(f"L{i}.{ff}", m.linear1.weight.data, m.linear2.weight.data)
+                    continue
+                p.add_matrix(f"L{i}.{ff}.w1", m.linear1.weight.data); p.add_matrix(f"L{i}.{ff}.w1t", m.linear1.weight.data, True)
+                p.add_matrix(f"L{i}.{ff}.w2", m.linear2.weight.data); p.add_matrix(f"L{i}.{ff}.w2t", m.linear2.weight.data, True)
+            a = L.self_attn
+            qkv = [a.linear_q.weight.data, a.linear_k.weight.data, a.linear_v.weight.data]
+            if dkp == dk:
+                p.add_concat(f"L{i}.att.wqkv", qkv); p.add_concat(f"L{i}.att.wqkvt", qkv, transpose=True)
+                p.add_matrix(f"L{i}.att.wo", a.linear_out.weight.data); p.add_matrix(f"L{i}.att.wot", a.linear_out.weight.data, True)
+                p.add_matrix(f"L{i}.att.wpos", a.linear_pos.weight.data)
+                pf.new_image(f"L{i}.att.bqkv", 1, 3 * d_)
+                for j, b in enumerate((a.linear_q.bias.data, a.linear_k.bias.data, a.linear_v.bias.data)):
+                    pf.add_block(f"L{i}.att.bqkv", b, 1, d_, col_off=j * d_, sr1=0, sc1=1)
+            else:
+                engine.declare_padded_heads(p, pf, f"L{i}.att", a, d_, H_, dk, dkp, dA)
+            c = L.conv
+            p.add_matrix(f"L{i}.conv.pw1", c.pointwise_conv1.weight.data); p.add_matrix(f"L{i}.conv.pw1t", c.pointwise_conv1.weight.data, True)
+            p.add_matrix(f"L{i}.conv.pw2", c.pointwise_conv2.weight.data); p.add_matrix(f"L{i}.conv.pw2t", c.pointwise_conv2.weight.data, True)
 
     # ------------------------------------------------------------------ replayable launch sequences (nemo_amd/graphs.py)
     def _eager_point(self, fn):
@@ -1107,32 +1047,8 @@ class ConformerEncoder(NeuralModule):
         """implicit-GEMM conv2 (gathered A operand) needs the bf16 LDS-DMA GEMM structures and whole K-tiles per tap"""
         return cdt == torch.bfloat16 and C_ % 64 == 0 and C_ >= 192 and M2 >= 192  # (C is also the wgrad's M and N)
 
-    @staticmethod
-    def _splitk(tiles, K, strided_c=False):
-        """split-K factor for `tiles` output tiles: the factor (<= 16, at least 16 K-tiles per workgroup) whose workgroup
-        count fills whole rounds of the 256 CUs best, smaller factors preferred (every extra slice is one more atomic
-        pass over the output)"""
-        nk = (K + 63) // 64
-        if strided_c:  # atomics into a column-strided C (reference weight layouts) are expensive: only fill the chip once
-            return max(1, min(nk // 4 if nk >= 8 else 1, 256 // max(tiles, 1), 16))
-        if tiles < 16:
-            # skinny problems (e.g. the [C, C] pointwise-conv weight gradients of 'dw_striding' over 320 000 positions: 2 tiles):
-            # 16 slices would leave them on 32 CUs (measured: 9.5 ms for 42 GFLOP); one round of the chip, >= 16 K-tiles each
-            return max(1, min(256 // max(tiles, 1), nk // 16, 128))
-        best, best_score = 1, -1.0
-        for c in range(1, 17):
-            if c > 1 and nk // c < 16:
-                break
-            blocks = tiles * c
-            eff = blocks / (((blocks + 255) // 256) * 256)
-            score = eff - 0.01 * c
-            if score > best_score + 1e-9:
-                best, best_score = c, score
-        return best
-
-    @staticmethod
-    def _tiles(n_out, n_in, bf16):
-        return ((n_out + 255) // 256) * ((n_in + 127) // 128) if bf16 else ((n_out + 63) // 64) * ((n_in + 63) // 64)
+    _splitk = staticmethod(engine.splitk)
+    _tiles = staticmethod(engine.tiles)
 
     def _wgrad(self, dY, ldy, y_off, X, ldx, x_off, dW, n_out, n_in, rows, bias_grad=None):
         """dW[n_out, n_in] += dY[:, y_off:y_off+n_out]^T @ X[:, x_off:x_off+n_in]   (TN GEMM, atomic split-K);

@@ -10,13 +10,9 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..core import AcousticEncodedRepresentation, LogprobsType, NeuralModule, NeuralType, typecheck
-from ..flat import FlatParams
-from ..packing import PackPlan
-
-
-def _pad8(n):
-    return (n + 7) // 8 * 8
+from ..core import AcousticEncodedRepresentation, LogprobsType, NeuralType, typecheck
+from ..packing import _pad8
+from .engine import EngineModule, wgrad_tn
 
 
 class _DecoderFn(torch.autograd.Function):
@@ -33,7 +29,7 @@ class _DecoderFn(torch.autograd.Function):
         return denc, None, None
 
 
-class ConvASRDecoder(NeuralModule):
+class ConvASRDecoder(EngineModule):
     @property
     def input_types(self):
         return OrderedDict({"encoder_output": NeuralType(("B", "D", "T"), AcousticEncodedRepresentation())})
@@ -70,12 +66,7 @@ class ConvASRDecoder(NeuralModule):
         else:
             raise ValueError(f"Unknown Initialization mode: {init_mode}")
         self.temperature = 1.0
-        self.compute_dtype = compute_dtype
-        self.grad_ready_hook = None
-        self._flatp = FlatParams(self)
-        self._plans = {}
-        self._weights_version = -1
-        self._token = None
+        self._init_engine(compute_dtype)
 
     @property
     def vocabulary(self):
@@ -85,56 +76,23 @@ class ConvASRDecoder(NeuralModule):
     def num_classes_with_blank(self):
         return self._num_classes
 
-    def flat_parameters(self):
-        self._flatp.ensure()
-        return self._flatp
-
-    def weights_updated(self):
-        self._weights_version += 1
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self.weights_updated()
-        return r
-
-    def _cdt(self):
-        if self.compute_dtype is not None:
-            return self.compute_dtype
-        if torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() == torch.bfloat16:
-            return torch.bfloat16
-        return torch.float32
-
-    def _plan(self, cdt, device):
-        key = (cdt, str(device), self._flatp.generation)
-        plan = self._plans.get(key)
-        if plan is None:
-            self._plans = {}
-            p = PackPlan(cdt, device)
-            w = self.decoder_layers[0].weight.data
-            p.add_matrix("dec.w", w)
-            p.add_matrix("dec.wt", w, transpose=True)
-            p.finalize()
-            plan = [p, -2]
-            self._plans[key] = plan
-        if plan[1] != self._weights_version:
-            plan[0].run()
-            plan[1] = self._weights_version
-        return plan[0]
+    def _declare_images(self, p, pf):
+        w = self.decoder_layers[0].weight.data
+        p.add_matrix("dec.w", w)
+        p.add_matrix("dec.wt", w, transpose=True)
 
     @typecheck()
     def forward(self, encoder_output):
         self._flatp.ensure(encoder_output.device)
-        if self._token is None or self._token.device != encoder_output.device:
-            self._token = torch.zeros(1, device=encoder_output.device, requires_grad=True)
         if torch.is_grad_enabled() and (encoder_output.requires_grad or any(p.requires_grad for p in self.parameters())):
-            return _DecoderFn.apply(encoder_output, self._token, self)
+            return _DecoderFn.apply(encoder_output, self._tok(encoder_output.device), self)
         return self._forward_impl(encoder_output)[0]
 
     def _forward_impl(self, enc):
         B, d, T = enc.shape
         dev = enc.device
         cdt = self._cdt()
-        W = self._plan(cdt, dev)
+        W, _ = self._plan(cdt, dev)
         M, V1 = B * T, self._num_classes
         x = enc.transpose(1, 2).contiguous().view(M, d)  # no copy when enc is the encoder's [B,T,d] view
         # bf16 operand rows start on 16-byte boundaries: a d_model that is not a multiple of 8 (Squeezeformer-Medium: 324)
@@ -159,19 +117,15 @@ class ConvASRDecoder(NeuralModule):
     def _backward_impl(self, saved, dlogp):
         xc, logp, B, T, d, cdt, enc_dtype = saved
         dev = dlogp.device
-        W = self._plan(cdt, dev)
+        W, _ = self._plan(cdt, dev)
         M, V1 = B * T, self._num_classes
         Vp = _pad8(V1)
         conv = self.decoder_layers[0]
         dlogits = torch.empty(M, Vp, dtype=cdt, device=dev)
         ops.log_softmax_bwd(dlogp.contiguous(), logp, V1, dlogits, Vp, M, V1,
                             1.0 / self.temperature if self.temperature != 1.0 else 1.0)
-        ops.colsum(dlogits, conv.bias.grad, M, V1, ld=Vp)
-        # d weight [V1, d] += dlogits^T @ x
-        tiles = ((V1 + 255) // 256) * ((d + 127) // 128) if cdt == torch.bfloat16 else ((V1 + 63) // 64) * ((d + 63) // 64)
-        nk = (M + 63) // 64
-        ops.gemm(dlogits, xc, conv.weight.grad, V1, d, M, Vp, xc.shape[1], d, transA=True, transB=True, atomic=True,
-                 splitk=max(1, min(max(1, nk // 4), 256 // tiles)), c_dtype=ops.F32)
+        # d weight [V1, d] += dlogits^T @ x; no limit of 16 on the split-K factor here
+        wgrad_tn(dlogits, Vp, xc, xc.shape[1], conv.weight.grad, V1, d, M, bias_grad=conv.bias.grad, cap=None)
         denc = torch.empty(B, T, d, dtype=torch.float32, device=dev)
         ops.gemm(dlogits, W["dec.wt"], denc, M, d, Vp, Vp, W.pitch("dec.wt"), d)
         if self.grad_ready_hook is not None:

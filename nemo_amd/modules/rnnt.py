@@ -26,81 +26,20 @@ from torch import nn
 
 from .. import ops
 from ..core import (AcousticEncodedRepresentation, ElementType, EmbeddedTextType, LabelsType, LengthsType, LogprobsType,
-                    LossType, NeuralModule, NeuralType, typecheck)
-from ..flat import FlatParams
-from ..packing import PackPlan
+                    LossType, NeuralType, typecheck)
+from ..packing import _pad8
+from .engine import EngineModule, wgrad_tn
 from .tdt_loss import TDTLoss, draw_rnnt_call
 
 
-def _pad8(n):
-    return (n + 7) // 8 * 8
-
-
-class _ModuleBase(NeuralModule):
-    """flat parameters + packed GEMM operand images + compute dtype, shared by the two modules"""
-
-    def _init_engine(self, compute_dtype):
-        self.compute_dtype = compute_dtype
-        self.grad_ready_hook = None
-        self._flatp = FlatParams(self)
-        self._plans = {}
-        self._weights_version = -1
-        self._token = None
-        self._step_seed = 0
-
-    def flat_parameters(self):
-        self._flatp.ensure()
-        return self._flatp
-
-    def weights_updated(self):
-        self._weights_version += 1
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self.weights_updated()
-        return r
+class _TransducerModule(EngineModule):
+    """the engine of the two transducer modules: + the bf16 rule of their hidden sizes"""
 
     def _cdt(self):
-        cdt = torch.float32
-        if self.compute_dtype is not None:
-            cdt = self.compute_dtype
-        elif torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() == torch.bfloat16:
-            cdt = torch.bfloat16
+        cdt = super()._cdt()
         if cdt == torch.bfloat16 and any(int(getattr(self, a, 8)) % 8 for a in ("pred_hidden", "joint_hidden", "encoder_hidden")):
             raise NotImplementedError("bf16 compute needs hidden sizes divisible by 8; use compute_dtype=torch.float32")
         return cdt
-
-    def _plan(self, cdt, device):
-        key = (cdt, str(device), self._flatp.generation)
-        plan = self._plans.get(key)
-        if plan is None:
-            self._plans = {}
-            p = PackPlan(cdt, device)
-            self._declare_images(p)
-            p.finalize()
-            plan = [p, -2]
-            self._plans[key] = plan
-        if plan[1] != self._weights_version:
-            plan[0].run()
-            plan[1] = self._weights_version
-        return plan[0]
-
-    def _tok(self, device):
-        if self._token is None or self._token.device != device:
-            self._token = torch.zeros(1, device=device, requires_grad=True)
-        return self._token
-
-    @staticmethod
-    def _wgrad(dY, ldy, X, ldx, dW, n_out, n_in, rows, bias_grad=None):
-        """dW[n_out, n_in] += dY^T @ X (atomic split-K TN GEMM); bias_grad += column sums of dY"""
-        bf16 = dY.dtype == torch.bfloat16
-        tiles = (((n_out + 255) // 256) * ((n_in + 127) // 128)) if bf16 else (((n_out + 63) // 64) * ((n_in + 63) // 64))
-        nk = (rows + 63) // 64
-        sk = max(1, min(max(1, nk // 4), max(1, 256 // tiles), 16))
-        if bias_grad is not None:
-            ops.colsum(dY, bias_grad, rows, n_out, ld=ldy)
-        ops.gemm(dY, X, dW, n_out, n_in, rows, ldy, ldx, n_in, transA=True, transB=True, atomic=True, splitk=sk,
-                 c_dtype=ops.F32)
 
 
 # ================================================================================================ prediction network
@@ -137,7 +76,7 @@ class _DecoderFn(torch.autograd.Function):
         return None, None, None
 
 
-class RNNTDecoder(_ModuleBase):
+class RNNTDecoder(_TransducerModule):
     @property
     def input_types(self):
         return OrderedDict({"targets": NeuralType(("B", "T"), LabelsType()),
@@ -175,7 +114,7 @@ class RNNTDecoder(_ModuleBase):
         })
         self._init_engine(compute_dtype)
 
-    def _declare_images(self, p):
+    def _declare_images(self, p, pf):
         lstm = self.prediction["dec_rnn"].lstm
         for l in range(self.pred_rnn_layers):
             wih, whh = getattr(lstm, f"weight_ih_l{l}").data, getattr(lstm, f"weight_hh_l{l}").data
@@ -196,7 +135,7 @@ class RNNTDecoder(_ModuleBase):
     def _forward_impl(self, targets, save=False):
         dev = targets.device
         cdt = self._cdt()
-        W = self._plan(cdt, dev)
+        W, _ = self._plan(cdt, dev)
         B, U = targets.shape
         U1, H, L = U + 1, self.pred_hidden, self.pred_rnn_layers
         lstm = self.prediction["dec_rnn"].lstm
@@ -248,7 +187,7 @@ class RNNTDecoder(_ModuleBase):
     def _backward_impl(self, saved, dg):
         tg, layers, B, U, cdt = saved
         dev = dg.device
-        W = self._plan(cdt, dev)
+        W, _ = self._plan(cdt, dev)
         U1, H, L = U + 1, self.pred_hidden, self.pred_rnn_layers
         lstm = self.prediction["dec_rnn"].lstm
         d_out = dg.permute(2, 0, 1).contiguous().view(U1 * B, H).to(torch.float32)  # time-major
@@ -269,10 +208,10 @@ class RNNTDecoder(_ModuleBase):
                              atomic=True, splitk=self._bptt_splitk, c_dtype=ops.F32)
             w_ih, w_hh = getattr(lstm, f"weight_ih_l{l}"), getattr(lstm, f"weight_hh_l{l}")
             b_ih, b_hh = getattr(lstm, f"bias_ih_l{l}"), getattr(lstm, f"bias_hh_l{l}")
-            self._wgrad(dz, 4 * H, inp, H, w_ih.grad, 4 * H, H, U1 * B, bias_grad=b_ih.grad)
+            wgrad_tn(dz, 4 * H, inp, H, w_ih.grad, 4 * H, H, U1 * B, bias_grad=b_ih.grad)
             ops.colsum(dz, b_hh.grad, U1 * B, 4 * H)
             if U1 > 1:  # rows of step t pair with h_{t-1}
-                self._wgrad(dz[B:], 4 * H, h_lp[:(U1 - 1) * B], H, w_hh.grad, 4 * H, H, (U1 - 1) * B)
+                wgrad_tn(dz[B:], 4 * H, h_lp[:(U1 - 1) * B], H, w_hh.grad, 4 * H, H, (U1 - 1) * B)
             d_inp = torch.empty(U1 * B, H, dtype=torch.float32, device=dev)
             ops.gemm(dz, W[f"l{l}.wiht"], d_inp, U1 * B, H, 4 * H, 4 * H, W.pitch(f"l{l}.wiht"), H)
             d_out = d_inp
@@ -316,7 +255,7 @@ class _FusedJointLossFn(torch.autograd.Function):
         return denc * go, ddec * go, None, None, None, None, None
 
 
-class RNNTJoint(_ModuleBase):
+class RNNTJoint(_TransducerModule):
     @property
     def input_types(self):
         return OrderedDict({
@@ -412,7 +351,7 @@ class RNNTJoint(_ModuleBase):
     def set_fused_batch_size(self, fused_batch_size):
         self._fused_batch_size = fused_batch_size
 
-    def _declare_images(self, p):
+    def _declare_images(self, p, pf):
         out = self.joint_net[-1]
         p.add_matrix("enc.w", self.enc.weight.data); p.add_matrix("enc.wt", self.enc.weight.data, True)
         p.add_matrix("pred.w", self.pred.weight.data); p.add_matrix("pred.wt", self.pred.weight.data, True)
@@ -519,7 +458,7 @@ class RNNTJoint(_ModuleBase):
         if dlog is None:
             dlog = torch.empty(n, V1p, dtype=cdt, device=dev)
             ops.cast_rows(dlogits, V1, dlog, V1p, n, V1, V1p, 1.0 / self.temperature if self.temperature != 1.0 else 1.0)
-        self._wgrad(dlog, V1p, h, J, gW, V1, J, n, bias_grad=gb)
+        wgrad_tn(dlog, V1p, h, J, gW, V1, J, n, bias_grad=gb)
         dh = torch.empty(n, J, dtype=cdt, device=dev)
         ops.gemm(dlog, W["out.wt"], dh, n, J, V1p, V1p, W.pitch("out.wt"), J)
         ops.joint_combine_bwd(dh, h, df[b0 * T:] if df_rows is None else df_rows, nb, T, U1, J, drop.scale)
@@ -532,8 +471,8 @@ class RNNTJoint(_ModuleBase):
         dev = xe.device
         dg = torch.empty(B * U1, J, dtype=cdt, device=dev)
         ops.drop_scale_cast(dg32, dg, B * U1 * J, 1.0)
-        self._wgrad(df, J, xe, D, gWe, J, D, B * T, bias_grad=gbe)
-        self._wgrad(dg, J, xd, H, gWp, J, H, B * U1, bias_grad=gbp)
+        wgrad_tn(df, J, xe, D, gWe, J, D, B * T, bias_grad=gbe)
+        wgrad_tn(dg, J, xd, H, gWp, J, H, B * U1, bias_grad=gbp)
         dxe = torch.empty(B, T, D, dtype=torch.float32, device=dev)
         dxd = torch.empty(B, U1, H, dtype=torch.float32, device=dev)
         ops.gemm(df, W["enc.wt"], dxe, B * T, D, J, J, W.pitch("enc.wt"), D)
@@ -543,7 +482,7 @@ class RNNTJoint(_ModuleBase):
     # -------------------------------------------------------------------------------------------- un-fused joint
     def _joint_fwd(self, enc, dec):
         cdt = self._cdt()
-        W = self._plan(cdt, enc.device)
+        W, _ = self._plan(cdt, enc.device)
         B, D, T = enc.shape
         U1 = dec.shape[2]
         if self.training:
@@ -556,7 +495,7 @@ class RNNTJoint(_ModuleBase):
     def _joint_bwd(self, saved, dlogits):
         xe, xd, h, drop, B, T, U1, cdt = saved
         dev = xe.device
-        W = self._plan(cdt, dev)
+        W, _ = self._plan(cdt, dev)
         J = self.joint_hidden
         out = self.joint_net[-1]
         df = torch.empty(B * T, J, dtype=cdt, device=dev)
@@ -579,7 +518,7 @@ class RNNTJoint(_ModuleBase):
             raise NotImplementedError(f"fused joint: loss reduction '{red}' (implemented: mean_batch, sum)")
         cdt = self._cdt()
         dev = enc.device
-        W = self._plan(cdt, dev)
+        W, _ = self._plan(cdt, dev)
         B, D, T = enc.shape
         U1, J = dec.shape[2], self.joint_hidden
         if self.training:

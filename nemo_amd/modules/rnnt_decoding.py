@@ -89,7 +89,7 @@ class GreedyBatchedRNNTInfer:
         xe32 = encoder_output.transpose(1, 2).contiguous().view(B * T, D).float()
         J = jnt.joint_hidden
         if cdt == torch.bfloat16:   # the GEMM operand images the training step keeps up to date
-            Wj, Wd = jnt._plan(cdt, dev), dec._plan(cdt, dev)
+            Wj, Wd = jnt._plan(cdt, dev)[0], dec._plan(cdt, dev)[0]
             xe = torch.empty(B * T, D, dtype=cdt, device=dev)
             ops.drop_scale_cast(xe32, xe, B * T * D, 1.0)
             f = torch.empty(B * T, J, dtype=cdt, device=dev)

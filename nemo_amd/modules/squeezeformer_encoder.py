@@ -38,9 +38,10 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..packing import PackPlan
+from ..packing import _pad8
 from .conformer_encoder import (ConformerEncoder, ConvSubsampling, RelPositionalEncoding, _DwGrads, _DwWeights, _FeedForward, _LnSaved,
-                                _RelPosMHA, _Step, _SubIO, _pad8, _record)
+                                _RelPosMHA, _Step, _SubIO, _record)
+from .engine import declare_padded_heads
 from ..core import NeuralModule
 
 
@@ -263,88 +264,47 @@ class SqueezeformerEncoder(ConformerEncoder):
             io.finish = finish
         return io
 
-    def _plan(self, cdt, device):
-        # (the geometry -- head width of the packed attention images -- follows run-time flags: use_flash_attention, flash_pad_heads)
-        key = (cdt, str(device), self._flatp.generation, self._geometry(cdt))
-        plan = self._plans.get(key)
-        if plan is None:
-            self._plans = {}
-            p = PackPlan(cdt, device)
-            pf = PackPlan(torch.float32, device)
-            d, H, dk = self.d_model, self.n_heads, self.d_k
-            dp, dkp, dA = self._geometry(cdt)
-            pe = self.pre_encode
-            C_, F2 = pe._conv_channels, pe._feat_after
-            Cs, Cp = self._sub_channels(cdt)
-            if Cp == Cs:
-                for si_, (_, pw) in enumerate(pe.dw_stages()):
-                    p.add_matrix(f"pre.pw{si_}", pw.weight.data.view(C_, C_))
-                    p.add_matrix(f"pre.pw{si_}t", pw.weight.data.view(C_, C_), True)
-                p.add_fc_permuted("pre.out", pe.out.weight.data, C_, F2)
-                p.add_fc_permuted("pre.outt", pe.out.weight.data, C_, F2, transpose=True)
-            else:  # zero-padded channels (see the module docstring): dense [Cp, 9] / [Cp] f32 copies + padded GEMM images
-                def dense(name, t, n_pad):
-                    pf.new_image(name, 1, n_pad)
-                    pf.add_block(name, t.view(-1), 1, t.numel(), sr1=0, sc1=1)
-                dense("pre.c0w", pe.conv[0].weight.data, Cp * 9); dense("pre.c0b", pe.conv[0].bias.data, Cp)
-                for si_, (dw, pw) in enumerate(pe.dw_stages()):
-                    dense(f"pre.dw{si_}w", dw.weight.data, Cp * 9); dense(f"pre.dw{si_}b", dw.bias.data, Cp)
-                    dense(f"pre.pw{si_}b", pw.bias.data, Cp)
-                    w = pw.weight.data.view(C_, C_)
-                    p.new_image(f"pre.pw{si_}", Cp, Cp); p.add_block(f"pre.pw{si_}", w, C_, C_, sr1=C_, sc1=1)
-                    p.new_image(f"pre.pw{si_}t", Cp, Cp); p.add_block(f"pre.pw{si_}t", w, C_, C_, sr1=1, sc1=C_)
-                wo_ = pe.out.weight.data  # [d, C*F2], column c*F2 + f  ->  image column f*Cp + c
-                p.new_image("pre.out", d, F2 * Cp); p.new_image("pre.outt", F2 * Cp, d)
-                for f in range(F2):
-                    p.add_block("pre.out", wo_.view(-1)[f:], d, C_, col_off=f * Cp, sr1=C_ * F2, sc1=F2)
-                    p.add_block("pre.outt", wo_.view(-1)[f:], C_, d, row_off=f * Cp, sr1=F2, sc1=C_ * F2)
+    def _declare_images(self, p, pf):
+        cdt = p.dtype
+        d, H, dk = self.d_model, self.n_heads, self.d_k
+        dp, dkp, dA = self._geometry(cdt)
+        pe = self.pre_encode
+        C_, F2 = pe._conv_channels, pe._feat_after
+        Cs, Cp = self._sub_channels(cdt)
+        if Cp == Cs:
+            for si_, (_, pw) in enumerate(pe.dw_stages()):
+                p.add_matrix(f"pre.pw{si_}", pw.weight.data.view(C_, C_))
+                p.add_matrix(f"pre.pw{si_}t", pw.weight.data.view(C_, C_), True)
+            p.add_fc_permuted("pre.out", pe.out.weight.data, C_, F2)
+            p.add_fc_permuted("pre.outt", pe.out.weight.data, C_, F2, transpose=True)
+        else:  # zero-padded channels (see the module docstring): dense [Cp, 9] / [Cp] f32 copies + padded GEMM images
+            def dense(name, t, n_pad):
+                pf.new_image(name, 1, n_pad)
+                pf.add_block(name, t.view(-1), 1, t.numel(), sr1=0, sc1=1)
+            dense("pre.c0w", pe.conv[0].weight.data, Cp * 9); dense("pre.c0b", pe.conv[0].bias.data, Cp)
+            for si_, (dw, pw) in enumerate(pe.dw_stages()):
+                dense(f"pre.dw{si_}w", dw.weight.data, Cp * 9); dense(f"pre.dw{si_}b", dw.bias.data, Cp)
+                dense(f"pre.pw{si_}b", pw.bias.data, Cp)
+                w = pw.weight.data.view(C_, C_)
+                p.new_image(f"pre.pw{si_}", Cp, Cp); p.add_block(f"pre.pw{si_}", w, C_, C_, sr1=C_, sc1=1)
+                p.new_image(f"pre.pw{si_}t", Cp, Cp); p.add_block(f"pre.pw{si_}t", w, C_, C_, sr1=1, sc1=C_)
+            wo_ = pe.out.weight.data  # [d, C*F2], column c*F2 + f  ->  image column f*Cp + c
+            p.new_image("pre.out", d, F2 * Cp); p.new_image("pre.outt", F2 * Cp, d)
+            for f in range(F2):
+                p.add_block("pre.out", wo_.view(-1)[f:], d, C_, col_off=f * Cp, sr1=C_ * F2, sc1=F2)
+                p.add_block("pre.outt", wo_.view(-1)[f:], C_, d, row_off=f * Cp, sr1=F2, sc1=C_ * F2)
 
-            def heads_rows(name, w, row0):  # w [H*dk, d] -> rows row0 + h*dkp + (0..dk) of image [*, d]
-                for h in range(H):
-                    p.add_block(name, w.view(-1)[h * dk * d:], dk, d, row_off=row0 + h * dkp, sr1=d, sc1=1)
-
-            def heads_cols(name, w, col0):  # w [H*dk, d] transposed -> columns col0 + h*dkp + (0..dk) of image [d, *]
-                for h in range(H):
-                    p.add_block(name, w.view(-1)[h * dk * d:], d, dk, col_off=col0 + h * dkp, sr1=1, sc1=d)
-
-            for i, L in enumerate(self.layers):
-                for ff, m in (("ff1", L.feed_forward1), ("ff2", L.feed_forward2)):
-                    p.add_matrix(f"L{i}.{ff}.w1", m.linear1.weight.data); p.add_matrix(f"L{i}.{ff}.w1t", m.linear1.weight.data, True)
-                    p.add_matrix(f"L{i}.{ff}.w2", m.linear2.weight.data); p.add_matrix(f"L{i}.{ff}.w2t", m.linear2.weight.data, True)
-                a = L.self_attn
-                qkv = [a.linear_q.weight.data, a.linear_k.weight.data, a.linear_v.weight.data]
-                p.new_image(f"L{i}.att.wqkv", 3 * dA, d); p.new_image(f"L{i}.att.wqkvt", d, 3 * dA)
-                p.new_image(f"L{i}.att.wpos", dA, d)
-                p.new_image(f"L{i}.att.wo", d, dA); p.new_image(f"L{i}.att.wot", dA, d)
-                for j, w in enumerate(qkv):
-                    heads_rows(f"L{i}.att.wqkv", w, j * dA)
-                    heads_cols(f"L{i}.att.wqkvt", w, j * dA)
-                heads_rows(f"L{i}.att.wpos", a.linear_pos.weight.data, 0)
-                wo = a.linear_out.weight.data  # [d, H*dk]: head h = columns h*dk ..
-                for h in range(H):
-                    p.add_block(f"L{i}.att.wo", wo.view(-1)[h * dk:], d, dk, col_off=h * dkp, sr1=d, sc1=1)
-                    p.add_block(f"L{i}.att.wot", wo.view(-1)[h * dk:], dk, d, row_off=h * dkp, sr1=1, sc1=d)
-                pf.new_image(f"L{i}.att.bqkv", 1, 3 * dA)
-                pf.new_image(f"L{i}.att.bu", 1, dA); pf.new_image(f"L{i}.att.bv", 1, dA)
-                for h in range(H):
-                    for j, b in enumerate((a.linear_q.bias.data, a.linear_k.bias.data, a.linear_v.bias.data)):
-                        pf.add_block(f"L{i}.att.bqkv", b[h * dk:], 1, dk, col_off=j * dA + h * dkp, sr1=0, sc1=1)
-                    pf.add_block(f"L{i}.att.bu", a.pos_bias_u.data.view(-1)[h * dk:], 1, dk, col_off=h * dkp, sr1=0, sc1=1)
-                    pf.add_block(f"L{i}.att.bv", a.pos_bias_v.data.view(-1)[h * dk:], 1, dk, col_off=h * dkp, sr1=0, sc1=1)
-                c = L.conv
-                p.add_matrix(f"L{i}.conv.pw1", c.pointwise_conv1.weight.data); p.add_matrix(f"L{i}.conv.pw1t", c.pointwise_conv1.weight.data, True)
-                p.add_matrix(f"L{i}.conv.pw2", c.pointwise_conv2.weight.data); p.add_matrix(f"L{i}.conv.pw2t", c.pointwise_conv2.weight.data, True)
-            if self.time_reduce_layer is not None:
-                p.add_matrix("tr.pw", self.time_reduce_layer.pw_conv.weight.data); p.add_matrix("tr.pwt", self.time_reduce_layer.pw_conv.weight.data, True)
-                p.add_matrix("rec.w", self.time_recovery_layer.weight.data); p.add_matrix("rec.wt", self.time_recovery_layer.weight.data, True)
-            p.finalize(); pf.finalize()
-            plan = (p, pf, None, -2)
-            self._plans[key] = plan
-        if plan[3] != self._weights_version or self._force_pack:
-            plan[0].run(); plan[1].run()
-            plan = (plan[0], plan[1], plan[2], self._weights_version)
-            self._plans[key] = plan
-        return plan[0], plan[1]
+        for i, L in enumerate(self.layers):
+            for ff, m in (("ff1", L.feed_forward1), ("ff2", L.feed_forward2)):
+                p.add_matrix(f"L{i}.{ff}.w1", m.linear1.weight.data); p.add_matrix(f"L{i}.{ff}.w1t", m.linear1.weight.data, True)
+                p.add_matrix(f"L{i}.{ff}.w2", m.linear2.weight.data); p.add_matrix(f"L{i}.{ff}.w2t", m.linear2.weight.data, True)
+            declare_padded_heads(p, pf, f"L{i}.att", L.self_attn, d, H, dk, dkp, dA)
+            c = L.conv
+            p.add_matrix(f"L{i}.conv.pw1", c.pointwise_conv1.weight.data); p.add_matrix(f"L{i}.conv.pw1t", c.pointwise_conv1.weight.data, True)
+            p.add_matrix(f"L{i}.conv.pw2", c.pointwise_conv2.weight.data); p.add_matrix(f"L{i}.conv.pw2t", c.pointwise_conv2.weight.data, True)
+        if self.time_reduce_layer is not None:
+            p.add_matrix("tr.pw", self.time_reduce_layer.pw_conv.weight.data); p.add_matrix("tr.pwt", self.time_reduce_layer.pw_conv.weight.data, True)
+            p.add_matrix("rec.w", self.time_recovery_layer.weight.data); p.add_matrix("rec.wt", self.time_recovery_layer.weight.data, True)
 
     def _geo(self, B, T, lens, pos_enc, d_emb, cdt, dev, dp):
         g = _Geo()

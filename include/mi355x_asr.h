@@ -699,6 +699,49 @@ int mi355x_ctc_beam_decode_lm(const void* logp, const void* lens, void* node_ws,
                               const void* state_bo, const void* state_bo_next, int n_states, int n_arcs, float alpha, float lm_ub,
                               void* stream);
 
+/* ---- resumable CTC prefix beam search (cache-aware streaming).  The two searches above, started from a per-utterance beam state
+ * and returning the next one, so that a stream searched chunk by chunk gives bit-identical hypotheses, frames, lengths and scores
+ * to one launch over all of its frames, for ANY cut into chunks: a frame does the same float32 operations in the same order.
+ * State (device arrays, written out of place: state_out must not alias state_in; the same state_in stepped twice gives the same
+ * result).  Per slot s < beam, [B, beam], slot order = the order of the set (ties of the next frame are broken by it):
+ *   node, par, tok, len   i32   the beam's node, its parent node, its last token, its length       fresh stream: 0, -1, -1, 0
+ *   h, hp                 u64   hash of the prefix and of the parent's prefix                       the root hash, 0
+ *   pb, pnb, tot, brank   f32   as above; brank = the rank the slot was kept with (= its score)     slot 0: 0, -inf, 0, 0; else -inf
+ *   lm_state, lm_sum      i32, f32   LM search only (may be NULL otherwise): automaton state, lm(prefix)            1 (<s>), 0
+ * Per utterance, [B]:
+ *   nb            i32   live beams; slots >= nb are not read                                                                     1
+ *   frames_done   i32   frames consumed by earlier steps                                                                         0
+ * state_in NULL, or state_in->node NULL: every stream is fresh (the one-shot search's initial values).  state_out is required.
+ * The prefix tree persists: node_ws is i32 pairs [B, Tcap, beam] (8-byte aligned), owned by the caller, appended to in place; the
+ * utterance's base is b * Tcap * beam pairs.  The extension kept in slot s of frame t of THIS chunk becomes node
+ * 1 + (frames_done + t) * beam + s, stored at pair (frames_done + t) * beam + s, so (node - 1) / beam is the GLOBAL frame of the
+ * token; merging and the output walk nodes that earlier launches wrote.  Replaying a chunk from the same state_in rewrites the same
+ * pairs with the same values; two different continuations of one state need two trees.
+ * logp f32 [B,Tmax,C] and lens i64 [B] describe this chunk.  Capacity: the step consumes min(lens[b], Tmax, Tcap - frames_done[b])
+ * frames and writes frames_done + consumed; it never stores past the tree or the outputs whatever the state holds (frames_done, nb
+ * and len are clamped to their ranges, node ids beyond Tcap * beam are not followed).  lens[b] = 0: the state passes through.
+ * Outputs: the current n-best, chased out of the tree as above, tokens / tok_frame i32 [B,beam,Tcap] (tok_frame: global frames).
+ * Positions at or beyond hyp_len[b,k] are NOT written (padding [B,beam,Tcap] on every chunk would cost more than the search):
+ * slice by hyp_len.  hyp_len, score, n_hyp as above.  All five outputs NULL: the state advances and nothing is chased.
+ * MI_ERR_ARG for what the one-shot entry refuses (with the five outputs all present or all NULL), a null state_out, a state (in
+ * with a non-null node, or out) with a null array (lm_state / lm_sum: in the LM search only), state_out->node == state_in->node,
+ * Tcap < 1, Tcap * beam > 0x3fffffff (node ids are 32-bit). */
+typedef struct mi355x_ctc_beam_stream_state {
+  int* node; int* par; int* tok; int* len; unsigned long long* h; unsigned long long* hp;
+  float* pb; float* pnb; float* tot; float* brank; int* lm_state; float* lm_sum; int* nb; int* frames_done;
+} mi355x_ctc_beam_stream_state;
+int mi355x_ctc_beam_decode_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
+                                  void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold,
+                                  float beta, int Tcap, const mi355x_ctc_beam_stream_state* state_in,
+                                  const mi355x_ctc_beam_stream_state* state_out, void* stream);
+int mi355x_ctc_beam_decode_lm_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
+                                     void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam,
+                                     float threshold, float beta, const void* state_arc_begin, const void* arc_tok,
+                                     const void* arc_logp, const void* arc_next, const void* state_bo, const void* state_bo_next,
+                                     int n_states, int n_arcs, float alpha, float lm_ub, int Tcap,
+                                     const mi355x_ctc_beam_stream_state* state_in,
+                                     const mi355x_ctc_beam_stream_state* state_out, void* stream);
+
 /* SpectrogramAugmentation (nemo/collections/asr/modules/audio_preprocessing.py:443-553; SpecAugment._apply_masks
  * parts/submodules/spectr_augment.py:153-215, SpecCutout.forward :245-261): x[b, f0:f1, t0:t1] = value for n rectangles
  * rects[n][5] = (b, f0, f1, t0, t1) (int32, device memory; clipped to the tensor).  x: f32 [B, F, T], in place. */

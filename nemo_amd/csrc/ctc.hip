@@ -971,10 +971,23 @@ __device__ __forceinline__ float ctc_beam_lm_lookup(const ctc_beam_lm& lm, int s
 }
 // candidate (r, k) goes in front of (wr, wk)
 __device__ __forceinline__ bool ctc_beam_beats(float r, int k, float wr, int wk) { return r > wr || (r == wr && k < wk); }
-// are the prefixes of nodes a and b the same sequence (they have the same length)?
-__device__ __forceinline__ bool ctc_beam_same_prefix(const int2* ws, int a, int b) {
+// the state a resumable search starts from (in.node null: fresh streams) and the one it writes, with the frames the tree holds;
+// nothing in the one-shot search
+struct ctc_beam_stream {
+  mi355x_ctc_beam_stream_state in, out;
+  int Tcap;
+};
+struct ctc_beam_no_stream {};
+template <bool STREAM> struct ctc_beam_stream_of { typedef ctc_beam_no_stream type; };
+template <> struct ctc_beam_stream_of<true> { typedef ctc_beam_stream type; };
+// are the prefixes of nodes a and b the same sequence (they have the same length)?  BOUND (resumable search: the ids come from a
+// state and a tree the caller keeps): an id beyond `lim` is not followed
+template <bool BOUND>
+__device__ __forceinline__ bool ctc_beam_same_prefix(const int2* ws, int a, int b, int lim) {
   while (a != b) {
     if (a <= 0 || b <= 0) return false;
+    if constexpr (BOUND)
+      if (a > lim || b > lim) return false;
     const int2 ea = ws[a - 1], eb = ws[b - 1];
     if (ea.y != eb.y) return false;
     a = ea.x; b = eb.x;
@@ -982,16 +995,22 @@ __device__ __forceinline__ bool ctc_beam_same_prefix(const int2* ws, int a, int 
   return true;
 }
 
-template <bool LM>
+// STREAM: the resumable search (include/mi355x_asr.h).  The beams start from st.in and end in st.out, the tree and the outputs have
+// Tcap frames per utterance, a node's frame is counted from the stream's first frame, and the outputs are not padded.  The frame
+// loop is the one-shot search's: rows are indexed by the frame of the chunk, nodes by the frame of the stream, nothing else differs.
+template <bool LM, bool STREAM>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ logp, const long long* __restrict__ lens, int2* node_ws,
                                                       int* __restrict__ tokens, int* __restrict__ tok_frame, int* __restrict__ hyp_len,
                                                       float* __restrict__ score, int* __restrict__ n_hyp, int Tmax, int C, int blank,
-                                                      int W, float theta, float beta, typename ctc_beam_lm_of<LM>::type lm) {
+                                                      int W, float theta, float beta, typename ctc_beam_lm_of<LM>::type lm,
+                                                      typename ctc_beam_stream_of<STREAM>::type st) {
   extern __shared__ float s_rows[];   // [2][C]: the log-probabilities of this frame and of the next
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int T = (int)max(0ll, min((long long)Tmax, lens ? lens[b] : (long long)Tmax));
+  int T = (int)max(0ll, min((long long)Tmax, lens ? lens[b] : (long long)Tmax));
   const float* lp = logp + (long long)b * Tmax * C;
-  int2* ws = node_ws + (long long)b * Tmax * W;
+  int Tout = Tmax;   // frames per utterance of the tree and of tokens / tok_frame
+  if constexpr (STREAM) Tout = st.Tcap;
+  int2* ws = node_ws + (long long)b * Tout * W;
   const int G = (C + 63) >> 6;
   // the beam of this lane (lanes < nb are live, sorted by rank)
   int node = 0, par = -1, tok = -1, len = 0;
@@ -1000,6 +1019,24 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   int nb = 1;
   int lm_state = 1;   // (LM) the automaton state of the prefix, <s> for the empty one, and lm(prefix)
   float lm_sum = 0.f;
+  int f0 = 0;         // (STREAM) frames of the stream before this chunk
+  if constexpr (STREAM) {
+    if (st.in.node) {   // every value that becomes an address is clamped to its range: a state that is not one of this search's
+      f0 = min(max(st.in.frames_done[b], 0), Tout);   // gives a wrong result, never a store outside the tree or the outputs
+      nb = min(max(st.in.nb[b], 0), W);
+      if (lane < nb) {
+        const int s = b * W + lane;
+        node = st.in.node[s]; par = st.in.par[s]; tok = min(max(st.in.tok[s], -1), C - 1); len = min(max(st.in.len[s], 0), f0);
+        h = st.in.h[s]; hp = st.in.hp[s];
+        pb = st.in.pb[s]; pnb = st.in.pnb[s]; tot = st.in.tot[s]; brank = st.in.brank[s];
+        if constexpr (LM) { lm_state = st.in.lm_state[s]; lm_sum = st.in.lm_sum[s]; }
+      } else {   // a slot without a beam is what the frame loop leaves in one
+        pb = NEGINF; tot = NEGINF; brank = NEGINF;
+      }
+    }
+    T = min(T, Tout - f0);   // (the capacity clamp)
+  }
+  const int node_lim = Tout * W;   // (STREAM) the largest node id the tree can hold
   if (T > 0)
     for (int c = lane; c < C; c += 64) s_rows[c] = lp[c];
   for (int t = 0; t < T; ++t) {
@@ -1024,7 +1061,8 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     int pl = -1;   // the slot of the beam whose extension by `tok` is this beam
     for (int i = 0; i < nb; ++i) {
       const int hl = ctc_rl((int)(unsigned)h, i), hh = ctc_rl((int)(unsigned)(h >> 32), i), li = ctc_rl(len, i), ni = ctc_rl(node, i);
-      if (live && pl < 0 && len == li + 1 && (int)(unsigned)hp == hl && (int)(unsigned)(hp >> 32) == hh && ctc_beam_same_prefix(ws, par, ni))
+      if (live && pl < 0 && len == li + 1 && (int)(unsigned)hp == hl && (int)(unsigned)(hp >> 32) == hh &&
+          ctc_beam_same_prefix<STREAM>(ws, par, ni, node_lim))
         pl = i;
     }
     {
@@ -1147,10 +1185,12 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     unsigned long long n_h = CTC_BEAM_ROOT_HASH, n_hp = 0;
     float n_pb = NEGINF, n_pnb = NEGINF, n_tot = NEGINF;
     if (is_ext) {
-      n_node = 1 + t * W + pos; n_par = node_s; n_tok = c_new; n_len = len_s + 1;
+      int tg = t;   // the frame of the stream (f0 + T <= Tout: the store stays in the tree)
+      if constexpr (STREAM) tg = f0 + t;
+      n_node = 1 + tg * W + pos; n_par = node_s; n_tok = c_new; n_len = len_s + 1;
       n_h = ctc_beam_hash(h_s, c_new); n_hp = h_s;
       n_pnb = e_val; n_tot = e_val;
-      ws[t * W + pos] = make_int2(n_par, n_tok);
+      ws[tg * W + pos] = make_int2(n_par, n_tok);
     } else if (keep) {
       n_node = node_s; n_par = par_s; n_tok = tok_s; n_len = len_s; n_h = h_s; n_hp = hp_s;
       n_pb = spb_s; n_pnb = spnb_s; n_tot = stot_s;
@@ -1169,6 +1209,36 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     }
     __threadfence_block();   // the node stores of this frame are visible to the lanes that chase them
     __syncthreads();
+  }
+  if constexpr (STREAM) {
+    // ---- the next state, out of place; then the n-best so far where it is asked for: no padding, Tcap positions per hypothesis
+    if (lane < W) {
+      const int s = b * W + lane;
+      st.out.node[s] = node; st.out.par[s] = par; st.out.tok[s] = tok; st.out.len[s] = len;
+      st.out.h[s] = h; st.out.hp[s] = hp;
+      st.out.pb[s] = pb; st.out.pnb[s] = pnb; st.out.tot[s] = tot; st.out.brank[s] = brank;
+      if constexpr (LM) { st.out.lm_state[s] = lm_state; st.out.lm_sum[s] = lm_sum; }
+    }
+    if (lane == 0) { st.out.nb[b] = nb; st.out.frames_done[b] = f0 + T; }
+    if (!tokens) return;
+    if (lane < W) {
+      const bool live = lane < nb;
+      hyp_len[b * W + lane] = live ? len : 0;
+      score[b * W + lane] = live ? brank : NEGINF;
+      if (live) {
+        int* tk = tokens + ((long long)b * W + lane) * Tout;
+        int* tf = tok_frame + ((long long)b * W + lane) * Tout;
+        int id = node;
+        for (int p = len - 1; p >= 0 && id > 0 && id <= node_lim; --p) {   // (len <= f0 + T <= Tout)
+          const int2 e = ws[id - 1];
+          tk[p] = e.y;
+          tf[p] = (id - 1) / W;
+          id = e.x;
+        }
+      }
+    }
+    if (lane == 0) n_hyp[b] = nb;
+    return;
   }
   // ---- output: the beams are in order; a lane per hypothesis chases its parents, tokens from position len-1 downward
   int* tk = tokens + (long long)b * W * Tmax;
@@ -1200,18 +1270,47 @@ extern "C" long long mi355x_ctc_beam_workspace_elems(int Tmax, int beam) {
 
 // LDS rule: two rows of log-probabilities (this frame's and the next one's), 8 C bytes <= 64 KB, i.e. C <= 8192, whatever the beam
 // width: the candidates of a frame are streamed against the running top-`beam` in registers and never stored.
-static bool ctc_beam_args_ok(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len, void* score,
-                             void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta) {
-  if (!logp || !lens || !node_ws || !tokens || !tok_frame || !hyp_len || !score || !n_hyp) return false;
+// (Ttree: the frames the tree holds per utterance -- Tmax for the one-shot search, Tcap for the resumable one)
+static bool ctc_beam_shape_ok(const void* logp, const void* lens, void* node_ws, int B, int Tmax, int C, int blank, int beam,
+                              float threshold, float beta, int Ttree) {
+  if (!logp || !lens || !node_ws) return false;
   if (B <= 0 || Tmax <= 0 || C <= 0 || blank < 0 || blank >= C || beam < 1 || beam > CTC_BEAM_MAX) return false;
   if (!(threshold > 0.f) || beta != beta || ((size_t)node_ws & 7)) return false;   // (NaN fails the first compare)
-  if ((long long)Tmax * beam > 0x3fffffffll) return false;   // node ids are 32-bit
+  if (Ttree < 1 || (long long)Ttree * beam > 0x3fffffffll) return false;   // node ids are 32-bit
   return (size_t)C * 8 <= 64 * 1024;
 }
-#define CTC_BEAM_LAUNCH(LM, ...)                                                                                                        \
-  MI_LAUNCH(ctc_beam_kernel<LM>, dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp, (const long long*)lens,    \
-            (int2*)node_ws, (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, blank, beam, threshold, \
-            beta, __VA_ARGS__)
+static bool ctc_beam_args_ok(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len, void* score,
+                             void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta) {
+  if (!tokens || !tok_frame || !hyp_len || !score || !n_hyp) return false;
+  return ctc_beam_shape_ok(logp, lens, node_ws, B, Tmax, C, blank, beam, threshold, beta, Tmax);
+}
+static bool ctc_beam_state_ok(const mi355x_ctc_beam_stream_state* s, bool lm) {
+  return s->node && s->par && s->tok && s->len && s->h && s->hp && s->pb && s->pnb && s->tot && s->brank && s->nb && s->frames_done &&
+         (!lm || (s->lm_state && s->lm_sum));
+}
+// the resumable entries: the five outputs all or none, a whole state_out, a state_in that is null, fresh (node null) or whole
+static bool ctc_beam_stream_args_ok(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
+                                    void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta,
+                                    int Tcap, const mi355x_ctc_beam_stream_state* state_in,
+                                    const mi355x_ctc_beam_stream_state* state_out, bool lm) {
+  const int outs = !!tokens + !!tok_frame + !!hyp_len + !!score + !!n_hyp;
+  if (outs != 0 && outs != 5) return false;
+  if (!state_out || !ctc_beam_state_ok(state_out, lm)) return false;
+  if (state_in && state_in->node && (!ctc_beam_state_ok(state_in, lm) || state_in->node == state_out->node)) return false;
+  return ctc_beam_shape_ok(logp, lens, node_ws, B, Tmax, C, blank, beam, threshold, beta, Tcap);
+}
+static ctc_beam_stream ctc_beam_stream_arg(const mi355x_ctc_beam_stream_state* state_in, const mi355x_ctc_beam_stream_state* state_out,
+                                           int Tcap) {
+  ctc_beam_stream st = {};
+  if (state_in && state_in->node) st.in = *state_in;
+  st.out = *state_out;
+  st.Tcap = Tcap;
+  return st;
+}
+#define CTC_BEAM_LAUNCH(LM, STREAM, ...)                                                                                                \
+  MI_LAUNCH((ctc_beam_kernel<LM, STREAM>), dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp,                  \
+            (const long long*)lens, (int2*)node_ws, (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, \
+            blank, beam, threshold, beta, __VA_ARGS__)
 
 extern "C" int mi355x_ctc_beam_decode(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
                                       void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold,
@@ -1219,7 +1318,7 @@ extern "C" int mi355x_ctc_beam_decode(const void* logp, const void* lens, void* 
   mi_clear_errors();
   if (!ctc_beam_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta))
     return MI_ERR_ARG;
-  CTC_BEAM_LAUNCH(false, ctc_beam_no_lm{});
+  CTC_BEAM_LAUNCH(false, false, ctc_beam_no_lm{}, ctc_beam_no_stream{});
   return mi_check_launch();
 }
 
@@ -1236,7 +1335,39 @@ extern "C" int mi355x_ctc_beam_decode_lm(const void* logp, const void* lens, voi
   if (n_states < 2 || n_arcs < C - 1 || blank != C - 1 || !(alpha >= 0.f) || lm_ub != lm_ub) return MI_ERR_ARG;
   const ctc_beam_lm lm = {(const int*)state_arc_begin, (const int*)arc_tok, (const float*)arc_logp, (const int*)arc_next,
                           (const float*)state_bo, (const int*)state_bo_next, n_states, n_arcs, alpha, lm_ub};
-  CTC_BEAM_LAUNCH(true, lm);
+  CTC_BEAM_LAUNCH(true, false, lm, ctc_beam_no_stream{});
+  return mi_check_launch();
+}
+
+// The two searches, resumable: one chunk from state_in to state_out over the tree the caller keeps (include/mi355x_asr.h).
+extern "C" int mi355x_ctc_beam_decode_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
+                                             void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam,
+                                             float threshold, float beta, int Tcap, const mi355x_ctc_beam_stream_state* state_in,
+                                             const mi355x_ctc_beam_stream_state* state_out, void* stream) {
+  mi_clear_errors();
+  if (!ctc_beam_stream_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
+                               Tcap, state_in, state_out, false))
+    return MI_ERR_ARG;
+  CTC_BEAM_LAUNCH(false, true, ctc_beam_no_lm{}, ctc_beam_stream_arg(state_in, state_out, Tcap));
+  return mi_check_launch();
+}
+
+extern "C" int mi355x_ctc_beam_decode_lm_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
+                                                void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam,
+                                                float threshold, float beta, const void* state_arc_begin, const void* arc_tok,
+                                                const void* arc_logp, const void* arc_next, const void* state_bo,
+                                                const void* state_bo_next, int n_states, int n_arcs, float alpha, float lm_ub,
+                                                int Tcap, const mi355x_ctc_beam_stream_state* state_in,
+                                                const mi355x_ctc_beam_stream_state* state_out, void* stream) {
+  mi_clear_errors();
+  if (!ctc_beam_stream_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
+                               Tcap, state_in, state_out, true))
+    return MI_ERR_ARG;
+  if (!state_arc_begin || !arc_tok || !arc_logp || !arc_next || !state_bo || !state_bo_next) return MI_ERR_ARG;
+  if (n_states < 2 || n_arcs < C - 1 || blank != C - 1 || !(alpha >= 0.f) || lm_ub != lm_ub) return MI_ERR_ARG;
+  const ctc_beam_lm lm = {(const int*)state_arc_begin, (const int*)arc_tok, (const float*)arc_logp, (const int*)arc_next,
+                          (const float*)state_bo, (const int*)state_bo_next, n_states, n_arcs, alpha, lm_ub};
+  CTC_BEAM_LAUNCH(true, true, lm, ctc_beam_stream_arg(state_in, state_out, Tcap));
   return mi_check_launch();
 }
 #undef CTC_BEAM_LAUNCH

@@ -132,6 +132,37 @@ def ctc_beam_results(decoding, log_probs, enc_len, return_hypotheses=False):
     return out
 
 
+def ctc_beam_stream_hypotheses(decoding, log_probs, chunk_len, previous_hypotheses=None):
+    """one chunk of every stream through the resumable beam search of `decoding` (a BeamBatchedCTCDecoder): log_probs [B, T, V+1]
+    and the valid frames of THIS chunk; `previous_hypotheses` = the list this function returned for the previous chunk (None: fresh
+    streams).  -> one Hypothesis per stream: text, y_sequence, score of the best hypothesis over all frames so far, timestamp = the
+    global frame each token entered it, length = the best hypothesis' token count, dec_state = (CTCBeamStreamState, row).  The same
+    streams in the same order are resumed without a copy; any other selection or order of earlier hypotheses goes through
+    `CTCBeamStreamState.gather`.  With the decoding object's `return_best_hypothesis` off, `n_best` holds (text, ids, score) of
+    every hypothesis, best first."""
+    from ..modules import CTCBeamStreamState
+    from ..modules.rnnt_decoding import Hypothesis
+    state = None
+    if previous_hypotheses is not None:
+        pairs = [h.dec_state for h in previous_hypotheses]
+        if len(pairs) != log_probs.shape[0]:
+            raise ValueError(f"previous_hypotheses holds {len(pairs)} streams, the chunk {log_probs.shape[0]}")
+        state = pairs[0][0]
+        if any(s is not state or r != i for i, (s, r) in enumerate(pairs)) or state.B != len(pairs):
+            state = CTCBeamStreamState.gather(pairs)
+    best_only = decoding.return_best_hypothesis
+    hyps, state = decoding.nbest_stream(log_probs, chunk_len, state, best_only=best_only)
+    out = []
+    for b, hs in enumerate(hyps):
+        ids, score, frames = hs[0] if hs else ([], float("-inf"), [])
+        hyp = Hypothesis(score=score, y_sequence=torch.tensor(ids, dtype=torch.long), text=decoding.ids_to_text(ids),
+                         timestamp=frames, length=len(ids), dec_state=(state, b))
+        if not best_only:
+            hyp.n_best = [(decoding.ids_to_text(i), i, s) for i, s, _ in hs]
+        out.append(hyp)
+    return out
+
+
 def ctc_transcribe_beam(model, audio, batch_size=4, return_hypotheses=False, channel_selector=None):
     """`transcribe` over a CTC head whose decoding object is the beam search (`model._ctc_log_probs`, `model._ctc_decoding()` as in
     `ctc_transcribe_timestamps`): one `ctc_beam_results` entry per input, in input order"""
@@ -478,16 +509,19 @@ class EncDecCTCModel(nn.Module):
         """`ASRModuleMixin.conformer_stream_step` for CTC models: one chunk through the encoder with caches
         (ConformerEncoder.cache_aware_stream_step), the decoder's log-softmax, and the per-frame arg-max of every utterance's valid
         frames appended to `previous_pred_out`.  -> (greedy_predictions: list of i64 [n_b] per utterance, texts (None unless
-        return_transcription), cache_last_channel_next, cache_last_time_next, cache_last_channel_next_len, best_hyp = None)
+        return_transcription), cache_last_channel_next, cache_last_time_next, cache_last_channel_next_len, best_hyp)
+        best_hyp is None under the greedy strategies; under `beam_batch` see `_ctc_stream_step`
         [+ (log_probs, encoded_len) with return_log_probs; encoded_len counts the frames of all chunks so far]."""
         return self._ctc_stream_step(self.decoder, self.wer, processed_signal, processed_signal_length, cache_last_channel,
                                      cache_last_time, cache_last_channel_len, keep_all_outputs, previous_pred_out,
-                                     drop_extra_pre_encoded, return_transcription, return_log_probs)
+                                     drop_extra_pre_encoded, return_transcription, return_log_probs, previous_hypotheses)
 
     def _ctc_stream_step(self, decoder, wer, processed_signal, processed_signal_length, cache_last_channel, cache_last_time,
                          cache_last_channel_len, keep_all_outputs, previous_pred_out, drop_extra_pre_encoded, return_transcription,
-                         return_log_probs):
-        """the streaming step over a given CTC head (`decoder`, with `wer` for the text): the hybrid model's auxiliary head runs it too"""
+                         return_log_probs, previous_hypotheses=None):
+        """the streaming step over a given CTC head (`decoder`, with `wer` for the text): the hybrid model's auxiliary head runs it too.
+        Under `beam_batch` the head's beam search is resumed over this chunk (`ctc_beam_stream_hypotheses`): best_hyp is then a list
+        of Hypothesis to pass back as `previous_hypotheses`, and the texts are the best beam hypotheses'."""
         if not hasattr(self.encoder, "cache_aware_stream_step"):
             raise NotImplementedError(f"{type(self.encoder).__name__} has no cache-aware streaming")
         if return_transcription and wer is None:
@@ -497,6 +531,9 @@ class EncDecCTCModel(nn.Module):
             cache_last_channel=cache_last_channel, cache_last_time=cache_last_time, cache_last_channel_len=cache_last_channel_len,
             keep_all_outputs=keep_all_outputs, drop_extra_pre_encoded=drop_extra_pre_encoded)
         log_probs = decoder(encoder_output=encoded)
+        best_hyp = None
+        if wer is not None and _is_beam(wer.decoding):   # (this chunk's frames: encoded_len before the earlier chunks are added in)
+            best_hyp = ctc_beam_stream_hypotheses(wer.decoding, log_probs, encoded_len, previous_hypotheses)
         preds = log_probs.argmax(dim=-1).cpu()
         enc_len = encoded_len.cpu().clone()
         blank = decoder.num_classes_with_blank - 1
@@ -508,10 +545,12 @@ class EncDecCTCModel(nn.Module):
                 cur = torch.cat((prev, cur), dim=-1)
                 enc_len[b] += prev.numel()
             greedy.append(cur)
-            if return_transcription:   # ctc_decoder_predictions_tensor: merge repeats, drop blanks
+            if return_transcription and best_hyp is not None:
+                texts.append(best_hyp[b].text)
+            elif return_transcription:   # ctc_decoder_predictions_tensor: merge repeats, drop blanks
                 ids = [int(t) for t in torch.unique_consecutive(cur).tolist() if int(t) != blank]
                 texts.append(wer.decoding.ids_to_text(ids))
-        result = [greedy, texts, ch_next, t_next, len_next, None]
+        result = [greedy, texts, ch_next, t_next, len_next, best_hyp]
         if return_log_probs:
             result += [log_probs, enc_len.to(log_probs.device)]
         return tuple(result)

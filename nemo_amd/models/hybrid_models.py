@@ -253,11 +253,13 @@ class EncDecHybridRNNTCTCModel(EncDecRNNTModel):
                               previous_pred_out=None, drop_extra_pre_encoded=None, return_transcription=True,
                               return_log_probs=False):
         """one chunk of every stream through the encoder and the head `cur_decoder` names.  'ctc': EncDecCTCModel's step over
-        `ctc_decoder` (state in `previous_pred_out`).  'rnnt': rnnt_conformer_stream_step (state in `previous_hypotheses`)."""
+        `ctc_decoder` (state in `previous_pred_out`; under `beam_batch` the beam search's in `previous_hypotheses`).  'rnnt':
+        rnnt_conformer_stream_step (state in `previous_hypotheses`)."""
         if self.cur_decoder == "ctc":
             return self._ctc_stream_step(self.ctc_decoder, self.ctc_wer, processed_signal, processed_signal_length,
                                          cache_last_channel, cache_last_time, cache_last_channel_len, keep_all_outputs,
-                                         previous_pred_out, drop_extra_pre_encoded, return_transcription, return_log_probs)
+                                         previous_pred_out, drop_extra_pre_encoded, return_transcription, return_log_probs,
+                                         previous_hypotheses)
         return rnnt_conformer_stream_step(self, processed_signal, processed_signal_length, cache_last_channel, cache_last_time,
                                           cache_last_channel_len, keep_all_outputs, previous_hypotheses, previous_pred_out,
                                           drop_extra_pre_encoded, return_transcription, return_log_probs)

@@ -4,8 +4,8 @@ from .conformer_encoder import ConformerEncoder  # noqa: F401
 from .squeezeformer_encoder import SqueezeformerEncoder  # noqa: F401
 from .conv_asr import ConvASRDecoder  # noqa: F401
 from .ctc import CTCLoss  # noqa: F401
-from .ctc_decoding import (BeamBatchedCTCDecoder, CTCAligner, GreedyCTCDecoder, WER, ctc_decoder_from_config,  # noqa: F401
-                           ctc_offsets, word_error_rate)
+from .ctc_decoding import (BeamBatchedCTCDecoder, CTCAligner, CTCBeamStreamState, GreedyCTCDecoder, WER,  # noqa: F401
+                           ctc_decoder_from_config, ctc_offsets, word_error_rate)
 from .ngram_lm import NGramLM  # noqa: F401
 from .rnnt_loss import RNNTLoss, RNNTLossNumba  # noqa: F401
 from .tdt_loss import TDTLoss, TDTLossNumba  # noqa: F401

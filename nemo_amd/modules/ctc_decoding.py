@@ -107,6 +107,115 @@ class GreedyCTCDecoder(_CTCText):
         return [self.ids_to_text(tokens[b, : int(out_len[b])].tolist()) for b in range(tokens.shape[0])]
 
 
+class CTCBeamStreamState:
+    """The beam search of a batch of B streams between two chunks (`mi355x_ctc_beam_stream_state`, include/mi355x_asr.h): the beams
+    of every stream, the prefix tree they point into, and the buffers the n-best is written to.
+      h64    i64 [2, B, W]   h, hp: the hashes of each beam's prefix and of its parent's prefix
+      beams  i32 [10, B, W]  node, par, tok, len, lm_state, then (float32 bits) pb, pnb, tot, brank, lm_sum; `arrays()` names them
+      utt    i32 [2, B]      nb (live beams), frames_done
+      tree   i32 [B, Tcap, W, 2]   (parent node, token) of node 1 + frame * W + slot; append-only, SHARED by the states of a stream
+      tokens, tok_frame  i32 [B, W, Tcap]   the n-best of the last emitting step, valid up to hyp_len; allocated once, reused by
+                             every step (copy what has to outlive the next one)
+    `lm`: the state of an LM-fused search (lm_state / lm_sum are meaningful).  `bound`: an upper bound of the frames consumed -- the
+    sum of the T of the steps taken, kept on the host, so that capacity never needs a device read.
+    A step never writes the beam arrays of the state it starts from; it appends to the tree.  Stepping one state twice with the
+    same chunk rewrites the same nodes with the same values; two DIFFERENT continuations of one state need a `gather` copy each."""
+    INT_FIELDS, FLOAT_FIELDS = ("node", "par", "tok", "len", "lm_state"), ("pb", "pnb", "tot", "brank", "lm_sum")
+    ROOT_HASH = 0x243F6A8885A308D3
+    MAX_NODES = 0x3FFFFFFF   # capacity * W: node ids are 32-bit
+
+    def __init__(self, h64, beams, utt, tree, tokens, tok_frame, lm, bound):
+        self.h64, self.beams, self.utt, self.tree, self.tokens, self.tok_frame = h64, beams, utt, tree, tokens, tok_frame
+        self.B, self.W, self.lm, self.bound = int(beams.shape[1]), int(beams.shape[2]), bool(lm), int(bound)
+
+    @property
+    def capacity(self) -> int:
+        return int(self.tree.shape[1])
+
+    @property
+    def device(self):
+        return self.beams.device
+
+    @classmethod
+    def _check_capacity(cls, capacity, W):
+        if capacity < 1 or capacity * W > cls.MAX_NODES:
+            raise ValueError(f"CTC beam stream state: capacity {capacity} frames x {W} beams is outside 1..{cls.MAX_NODES} nodes "
+                             "(node ids are 32-bit)")
+
+    @staticmethod
+    def _buffers(B, W, capacity, device):
+        i32 = dict(dtype=torch.int32, device=device)
+        return torch.zeros(B, capacity, W, 2, **i32), torch.empty(B, W, capacity, **i32), torch.empty(B, W, capacity, **i32)
+
+    @classmethod
+    def fresh(cls, B, W, device, capacity: int = 64, lm: bool = False):
+        """B streams that have seen nothing, with room for `capacity` frames (it grows by doubling: `reserve`)"""
+        B, W, capacity = int(B), int(W), int(capacity)
+        if B < 1 or not 1 <= W <= 64:
+            raise ValueError(f"CTC beam stream state: B = {B}, W = {W} (B >= 1, 1 <= W <= 64)")
+        cls._check_capacity(capacity, W)
+        h64 = torch.zeros(2, B, W, dtype=torch.int64, device=device)
+        h64[0] = cls.ROOT_HASH
+        ints = torch.tensor([0, -1, -1, 0, 1], dtype=torch.int32, device=device)
+        flts = torch.tensor([float("-inf")] * 4 + [0.0], dtype=torch.float32, device=device)
+        beams = torch.cat((ints, flts.view(torch.int32))).view(10, 1, 1).repeat(1, B, W)
+        beams[5:9:2, :, 0] = 0   # slot 0, the empty prefix: pb = tot = 0
+        beams[8, :, 0] = 0       # and its rank
+        utt = torch.zeros(2, B, dtype=torch.int32, device=device)
+        utt[0] = 1
+        return cls(h64, beams, utt, *cls._buffers(B, W, capacity, device), lm=lm, bound=0)
+
+    def arrays(self):
+        """name -> [B, W] (nb, frames_done: [B]) views of the arrays the search carries (lm_state / lm_sum only for an LM search)"""
+        out = {"h": self.h64[0], "hp": self.h64[1]}
+        out.update({n: self.beams[i] for i, n in enumerate(self.INT_FIELDS)})
+        out.update({n: self.beams[5 + i].view(torch.float32) for i, n in enumerate(self.FLOAT_FIELDS)})
+        if not self.lm:
+            del out["lm_state"], out["lm_sum"]
+        out.update(nb=self.utt[0], frames_done=self.utt[1])
+        return out
+
+    def reserve(self, T: int):
+        """room for T more frames: while bound + T exceeds the capacity it doubles -- a new tree with the frames of the old one
+        copied in (node ids do not depend on the capacity) and new output buffers"""
+        need, cap = self.bound + int(T), self.capacity
+        if need <= cap:
+            return self
+        while cap < need:
+            cap *= 2
+        cap = max(need, min(cap, self.MAX_NODES // self.W))   # (the last doubling stops at what node ids can name)
+        self._check_capacity(cap, self.W)
+        old = self.tree
+        self.tree, self.tokens, self.tok_frame = self._buffers(self.B, self.W, cap, self.device)
+        self.tree[:, : old.shape[1]] = old
+        return self
+
+    def next(self, T: int):
+        """the state a step over T frames writes: new beam arrays (uninitialised), this state's tree and buffers"""
+        return CTCBeamStreamState(torch.empty_like(self.h64), torch.empty_like(self.beams), torch.empty_like(self.utt), self.tree,
+                                  self.tokens, self.tok_frame, self.lm, self.bound + int(T))
+
+    @classmethod
+    def gather(cls, pairs):
+        """a new state of len(pairs) streams: row i is stream `row` of `state` for the i-th (state, row) -- for a server that drops
+        finished streams or regroups them.  Beams and trees are copied; the new state shares nothing with the old ones."""
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError("CTC beam stream state: gather of no streams")
+        first = pairs[0][0]
+        for s, r in pairs:
+            if s.W != first.W or s.lm != first.lm or s.device != first.device:
+                raise ValueError("CTC beam stream state: gather over states of different beam width, LM-ness or device")
+            if not 0 <= int(r) < s.B:
+                raise ValueError(f"CTC beam stream state: row {r} of a state of {s.B} streams")
+        cap = max(s.capacity for s, _ in pairs)
+        tree, tokens, tok_frame = cls._buffers(len(pairs), first.W, cap, first.device)
+        for i, (s, r) in enumerate(pairs):
+            tree[i, : s.capacity] = s.tree[int(r)]
+        pick = lambda name: torch.stack([getattr(s, name)[:, int(r)] for s, r in pairs], dim=1).contiguous()
+        return cls(pick("h64"), pick("beams"), pick("utt"), tree, tokens, tok_frame, first.lm, max(s.bound for s, _ in pairs))
+
+
 class BeamBatchedCTCDecoder(_CTCText):
     """CTC prefix beam search on the device (`mi355x_ctc_beam_decode`, with `ngram_lm` `mi355x_ctc_beam_decode_lm`): the `beam_batch`
     strategy.  `beam_size` hypotheses per utterance (1..64), `beam_threshold`: a class is looked at in a frame only if its
@@ -154,6 +263,33 @@ class BeamBatchedCTCDecoder(_CTCText):
         tokens, _, hyp_len, score, n_hyp = (t.cpu() for t in self.decode_ids(log_probs, lengths))
         return [[(tokens[b, k, : int(hyp_len[b, k])].tolist(), float(score[b, k])) for k in range(int(n_hyp[b]))]
                 for b in range(tokens.shape[0])]
+
+    @torch.no_grad()
+    def decode_stream(self, log_probs: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                      state: Optional[CTCBeamStreamState] = None, emit: bool = True):
+        """one chunk of the resumable search (`mi355x_ctc_beam_decode_stream` / `_lm_stream`): log_probs [B, T, V+1] and lengths
+        [B] of THIS chunk (0: the stream has ended, its state passes through), `state` what the previous chunk returned (None: fresh
+        streams) -> (the n-best of all frames so far, or None with emit=False; the next state).  The n-best is `decode_ids`'
+        tuple with tokens / tok_frame i32 [B, W, capacity] in the state's buffers: NOT padded, valid up to hyp_len, overwritten by
+        the next step; tok_frame counts from the stream's first frame.  Any cut of a stream into chunks gives the bits of
+        `decode_ids` over all of it."""
+        _check_log_probs(log_probs)
+        lp = log_probs.to(torch.float32).contiguous()
+        lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
+        return ops.ctc_beam_decode_stream(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, state,
+                                          lm=self.ngram_lm, alpha=self.ngram_lm_alpha, emit=emit)
+
+    def nbest_stream(self, log_probs, lengths=None, state=None, best_only: bool = False):
+        """`decode_stream` to host lists: per stream the (token ids, score, global frame of each token) of its hypotheses so far,
+        best first (best_only: the first one alone), and the next state.  The D2H copy is the hypotheses up to the longest one."""
+        (tokens, tok_frame, hyp_len, score, n_hyp), nxt = self.decode_stream(log_probs, lengths, state, emit=True)
+        hyp_len, score, n_hyp = hyp_len.cpu(), score.cpu(), n_hyp.cpu()
+        K = 1 if best_only else int(n_hyp.max())
+        L = int(hyp_len[:, :K].max()) if K else 0
+        tokens, tok_frame = tokens[:, :K, :L].cpu(), tok_frame[:, :K, :L].cpu()
+        out = [[(tokens[b, k, : int(hyp_len[b, k])].tolist(), float(score[b, k]), tok_frame[b, k, : int(hyp_len[b, k])].tolist())
+                for k in range(min(K, int(n_hyp[b])))] for b in range(tokens.shape[0])]
+        return out, nxt
 
     def __call__(self, log_probs, lengths=None):
         texts = [[self.ids_to_text(ids) for ids, _ in hyps] for hyps in self.nbest(log_probs, lengths)]

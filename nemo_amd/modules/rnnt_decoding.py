@@ -56,6 +56,7 @@ class Hypothesis:  # parts/utils/rnnt_utils.py:35-110 (the fields greedy decodin
     frame_confidence: Optional[List[float]] = None   # CTC: one value per frame of the utterance
     token_confidence: Optional[List[float]] = None   # one value per label of y_sequence
     word_confidence: Optional[List[float]] = None    # one value per word of the text
+    n_best: Optional[list] = None   # streaming CTC beam search with return_best_hypothesis off: (text, ids, score), best first
 
 
 class GreedyBatchedRNNTInfer:

@@ -529,6 +529,58 @@ def _ctc_beam(logp, lens, blank, beam_size, beam_threshold, beam_beta, lm, alpha
     return tokens, tok_frame, hyp_len, score, n_hyp
 
 
+class _CTCBeamStateC(C.Structure):   # mi355x_ctc_beam_stream_state
+    _fields_ = [(n, C.c_void_p) for n in ("node", "par", "tok", "len", "h", "hp", "pb", "pnb", "tot", "brank", "lm_state", "lm_sum",
+                                           "nb", "frames_done")]
+
+    @classmethod
+    def of(cls, state):
+        a = state.arrays()
+        return cls(**{n: (_ptr(a[n]) if n in a else None) for n, _ in cls._fields_})
+
+
+def ctc_beam_decode_stream(logp, lens, blank, beam_size, beam_threshold, beam_beta, state, lm=None, alpha=0.0, emit=True):
+    """one chunk of the resumable CTC prefix beam search (mi355x_ctc_beam_decode_stream; with `lm`, an NGramLM, and `alpha`
+    mi355x_ctc_beam_decode_lm_stream): logp f32 [B,T,C] contiguous and lens i64 [B] (None: T) of THIS chunk, `state` the
+    `modules.CTCBeamStreamState` the previous chunk returned (None: fresh streams) -> ((tokens, tok_frame, hyp_len, score, n_hyp) of
+    all frames so far, or None with emit=False; the next state).  tokens / tok_frame are the state's buffers [B, W, capacity]: valid
+    up to hyp_len, not padded, rewritten by the next emitting step; tok_frame counts from the stream's first frame.  The input
+    state's beams are not written (its tree is appended to, and grown here so that the kernel's capacity clamp never acts).  Any cut
+    into chunks gives the bits of `ctc_beam_decode` / `ctc_beam_decode_lm` over the whole sequence."""
+    from .modules.ctc_decoding import CTCBeamStreamState
+    B, T, C_ = logp.shape
+    W = int(beam_size)
+    if lm is not None:
+        from .modules.ngram_lm import NGramLM
+        if not isinstance(lm, NGramLM):
+            raise TypeError(f"ctc_beam_decode_stream: `lm` must be an NGramLM, got {type(lm).__name__}")
+        if lm.vocab_size != C_ - 1:
+            raise ValueError(f"ctc_beam_decode_stream: the LM has {lm.vocab_size} labels, the log-probabilities {C_} classes "
+                             f"(labels + the blank)")
+    if state is None:
+        state = CTCBeamStreamState.fresh(B, W, logp.device, lm=lm is not None)
+    if state.B != B or state.W != W or state.lm != (lm is not None):
+        raise ValueError(f"ctc_beam_decode_stream: the state is of {state.B} streams, {state.W} beams, "
+                         f"{'an' if state.lm else 'no'} LM; the call of {B}, {W}, {'an' if lm is not None else 'no'} LM")
+    if lens is None:
+        lens = torch.full((B,), T, dtype=torch.int64, device=logp.device)
+    state.reserve(T)
+    nxt = state.next(T)
+    i32, f32 = (dict(dtype=d, device=logp.device) for d in (torch.int32, torch.float32))
+    outs = (state.tokens, state.tok_frame, torch.empty(B, W, **i32), torch.empty(B, W, **f32), torch.empty(B, **i32)) if emit else None
+    s_in, s_out = _CTCBeamStateC.of(state), _CTCBeamStateC.of(nxt)
+    args = (_ptr(logp), _ptr(lens), _ptr(state.tree), *((_ptr(t) for t in outs) if emit else (None,) * 5), B, T, C_, int(blank), W,
+            float(beam_threshold), float(beam_beta))
+    tail = (state.capacity, C.byref(s_in), C.byref(s_out), _stream())
+    if lm is None:
+        check(lib.mi355x_ctc_beam_decode_stream(*args, *tail), "ctc_beam_decode_stream")
+    else:
+        tables = lm.to(logp.device)
+        check(lib.mi355x_ctc_beam_decode_lm_stream(*args, *(_ptr(t) for t in tables), lm.num_states, lm.num_arcs, float(alpha),
+                                                   float(lm.lm_ub), *tail), "ctc_beam_decode_lm_stream")
+    return outs, nxt
+
+
 def specaug_rects(u_tw, u_ts, u_fw, u_fs, length, rects, B, nt, nf, F, T, time_width, freq_width):
     """mask rectangles of SpecAugment's vectorised path from its four uniform draws (one launch instead of ~40 tensor ops)"""
     frac = isinstance(time_width, float)

@@ -12,13 +12,17 @@ that drift of the box hits all of them alike:
   * mi355x_ctc_greedy_decode, mi355x_ctc_greedy_decode_ts and mi355x_ctc_beam_decode of every library given with `--lib name=path`
     (e.g. a build of the parent commit), alternating with the in-tree library's: the spread between builds of entry points a
     change does not touch.
+  * with `--stream CHUNK` the resumable entries (mi355x_ctc_beam_decode_stream, with --lm also mi355x_ctc_beam_decode_lm_stream)
+    over the same T frames cut into chunks of CHUNK frames, one candidate = the whole utterance: every step carries the state
+    through device arrays and appends to a tree of T frames; `emit=all` chases the n-best out on every chunk, `emit=last` on the
+    last one only.  Next to the one-shot time, the difference is launches + state load and store + the chases.
 Input: log-softmax of 1.5 * N(0,1) with +5 on the class of a random path (blank with probability 0.6), the generator of the tests --
 peaked like a trained model's output, so that the threshold prunes; lengths = T.  The launches of a candidate per round are sized
 from one timed launch so that a round of it takes about `--round-ms`.  Reported per candidate: median, min and max of the
 per-round means, in microseconds per launch.
 
     python tools/ctc_beam_bench.py [--shapes 32,501,129 32,501,1025] [--beams 4 16 64] [--thresholds 20 inf] [--rounds 7]
-                                   [--lm ORDER] [--alpha 0.5] [--lib parent=PATH ...] [--json OUT]
+                                   [--lm ORDER] [--alpha 0.5] [--stream CHUNK] [--lib parent=PATH ...] [--json OUT]
 """
 import argparse
 import ctypes
@@ -87,7 +91,7 @@ def make_ngram_lm(V, order):
         return NGramLM.from_arpa(os.path.join(d, "lm.arpa"), V)
 
 
-def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, alpha=0.5):
+def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, alpha=0.5, chunk=0):
     from nemo_amd import _lib
     lib = _lib.lib
     logp = make_logp(B, T, C)
@@ -119,6 +123,31 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, 
             assert rc == 0, rc
         return fn
 
+    chunks = [logp[:, t:t + chunk].contiguous() for t in range(0, T, chunk)] if chunk else []
+    chunk_lens = {n: torch.full((B,), n, dtype=torch.int64, device=dev) for n in {c.shape[1] for c in chunks}}
+
+    def streamed(W, th, emit_all, a=None):
+        """the utterances in chunks through the resumable entry: two states written in turn, a tree of T frames"""
+        from nemo_amd.modules import CTCBeamStreamState
+        from nemo_amd.ops import _CTCBeamStateC
+        st = [CTCBeamStreamState.fresh(B, W, dev, capacity=T, lm=a is not None) for _ in range(2)]
+        cs = [_CTCBeamStateC.of(x) for x in st]
+        outs = (p(st[0].tokens), p(st[0].tok_frame), p(hyp_len), p(score), p(n_hyp))
+
+        def fn():
+            for i, c in enumerate(chunks):
+                n = c.shape[1]
+                o = outs if emit_all or i == len(chunks) - 1 else (None,) * 5
+                head = (p(c), p(chunk_lens[n]), p(st[0].tree), *o, B, n, C, C - 1, W, th, 0.0)
+                tail = (T, ctypes.byref(cs[(i + 1) & 1]) if i else None, ctypes.byref(cs[i & 1]), stream)
+                if a is None:
+                    rc = lib.mi355x_ctc_beam_decode_stream(*head, *tail)
+                else:
+                    rc = lib.mi355x_ctc_beam_decode_lm_stream(*head, *tables, lm.num_states, lm.num_arcs, a, lm.lm_ub, *tail)
+                assert rc == 0, rc
+        fn._keep = st
+        return fn
+
     def greedy(l, ts):
         def fn():
             if ts:
@@ -139,6 +168,12 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, 
             if lm:
                 cands[f"beam+lm W={W} threshold={th} alpha={alpha}"] = beam_lm(W, th, alpha)
                 cands[f"beam+lm W={W} threshold={th} alpha=0"] = beam_lm(W, th, 0.0)
+            if chunk:
+                for emit_all in (True, False):
+                    tag = f"W={W} threshold={th} chunk={chunk} emit={'all' if emit_all else 'last'}"
+                    cands[f"stream {tag}"] = streamed(W, th, emit_all)
+                    if lm:
+                        cands[f"stream+lm {tag} alpha={alpha}"] = streamed(W, th, emit_all, alpha)
     row = dict(shape=dict(B=B, T=T, C=C), **rounds(cands, n_rounds, round_ms))
     if lm:
         row["lm"] = dict(order=lm.order, states=lm.num_states, arcs=lm.num_arcs, lm_ub=lm.lm_ub)
@@ -167,6 +202,7 @@ def main():
     ap.add_argument("--round-ms", type=float, default=50.0)
     ap.add_argument("--lm", type=int, default=0, metavar="ORDER", help="also time the search with an n-gram model of this order fused")
     ap.add_argument("--alpha", type=float, default=0.5, help="the fusion weight of the --lm runs")
+    ap.add_argument("--stream", type=int, default=0, metavar="CHUNK", help="also time the resumable search over chunks of CHUNK frames")
     ap.add_argument("--lib", nargs="*", default=[], help="name=path of further builds of the library")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -174,7 +210,7 @@ def main():
     out = dict(device=torch.cuda.get_device_name(0), rounds=args.rounds, round_ms=args.round_ms, shapes=[])
     for s in args.shapes:
         B, T, C = (int(x) for x in s.split(","))
-        row = one_shape(B, T, C, args.beams, args.thresholds, libs, args.rounds, args.round_ms, args.lm, args.alpha)
+        row = one_shape(B, T, C, args.beams, args.thresholds, libs, args.rounds, args.round_ms, args.lm, args.alpha, args.stream)
         out["shapes"].append(row)
         print(json.dumps(row), flush=True)
     if args.json:

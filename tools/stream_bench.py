@@ -12,8 +12,13 @@ geometry (prediction hidden 640, joint hidden 640, vocabulary 1024, max_symbols 
 heads the same 14 frames are also decoded as 14 one-frame chunks (`head_ms_14x1`): everything paid per chunk -- the projection
 GEMM, the other launches and the prediction step the kernel reruns at entry -- is in that figure 14 times instead of once, so the
 difference bounds the cost of the rerun from above; it does not isolate it.
+`--decoder ctc_beam [--beam-size 4 16 64] [--classes 129 1025] [--lm ORDER]`: the CTC head with the resumable prefix beam search
+behind it (ConvASRDecoder + mi355x_ctc_beam_decode_stream, with --lm mi355x_ctc_beam_decode_lm_stream and the trigram of the tests'
+generator at alpha 0.5), stepped from the state a stream has after eight chunks, with the n-best chased out on every step and, as
+`head_ms_no_emit`, with the state advanced only.  One row per (classes, beam size) under `heads`: median, min and max of 7 rounds.
 
     python tools/stream_bench.py [--batch 1 16 64] [--steps 50] [--warmup 10] [--layers 17] [--decoder none] [--json OUT]
+                                 [--beam-size 4 16 64] [--classes 129 1025] [--lm ORDER]
 """
 import argparse
 import json
@@ -62,6 +67,45 @@ def build_head(kind, d_model=512):
         tokens, times, out_len, nxt = infer.decode_ids_stream(enc, n, state)
         return tokens, nxt
     return step
+
+
+def build_beam_head(C, W, lm_order, d_model=512):
+    """-> step(encoded, encoded_len, state, emit) for the CTC head over C classes with the resumable beam search of width W"""
+    from nemo_amd.modules import BeamBatchedCTCDecoder, ConvASRDecoder
+    torch.manual_seed(1)
+    dec = ConvASRDecoder(feat_in=d_model, num_classes=C - 1, compute_dtype=torch.bfloat16).to(dev).eval()
+    with torch.no_grad():
+        dec.decoder_layers[0].weight.mul_(8.0)   # (random weights give nearly flat rows: peaked ones, so that the threshold prunes)
+    lm = None
+    if lm_order:
+        from ctc_beam_bench import make_ngram_lm
+        lm = make_ngram_lm(C - 1, lm_order)
+    search = BeamBatchedCTCDecoder(blank_id=C - 1, beam_size=W, ngram_lm=lm, ngram_lm_alpha=0.5 if lm else 0.0)
+    return lambda enc, n, state=None, emit=True: search.decode_stream(dec(encoder_output=enc), n, state, emit=emit)
+
+
+def beam_head_setting(head, enc_out, enc_len, steps, warmup, n_rounds=7):
+    import statistics
+    from torch.profiler import ProfilerActivity, profile
+    with torch.no_grad():
+        state = None
+        for _ in range(8):   # a stream in mid-flight: the tree holds eight chunks
+            _, state = head(enc_out, enc_len, state)
+        row = {}
+        for key, emit in (("head_ms_per_step", True), ("head_ms_no_emit", False)):
+            fn = lambda: head(enc_out, enc_len, state, emit)   # noqa: E731  (out of place: every call is the same step)
+            for _ in range(warmup):
+                fn()
+            torch.cuda.synchronize()
+            ms = [timed(fn, steps) for _ in range(n_rounds)]
+            row[key] = round(statistics.median(ms), 3)
+            row[key + "_range"] = [round(min(ms), 3), round(max(ms), 3)]
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            head(enc_out, enc_len, state)
+            torch.cuda.synchronize()
+        row["head_launches"] = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+        row["chunk_frames"] = int(enc_out.shape[2])
+    return row
 
 
 def head_setting(head, kind, B, enc_out, enc_len, steps, warmup):
@@ -126,7 +170,10 @@ def one_setting(enc, B, steps, warmup, head=None, kind="none"):
     torch.cuda.synchronize()
     ms = timed(step, steps)
     head_row = {}
-    if head is not None:
+    if kind == "ctc_beam":   # `head`: [(settings, step)], one per (classes, beam size)
+        res = step()
+        head_row = dict(heads=[dict(cfg, **beam_head_setting(h, res[0].detach(), res[1].detach(), steps, warmup)) for cfg, h in head])
+    elif head is not None:
         res = step()
         head_row = head_setting(head, kind, B, res[0].detach(), res[1].detach(), steps, warmup)
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
@@ -155,7 +202,9 @@ def one_setting(enc, B, steps, warmup, head=None, kind="none"):
     ms_off = timed(offline, 3)
     row = dict(batch=B, ms_per_step=round(ms, 3), launches_per_step=launches, rtf=round(ms / 1120.0, 5),
                stream_20s_ms=round(ms_stream, 2), offline_20s_ms=round(ms_off, 2))
-    if head_row:
+    if kind == "ctc_beam":
+        row.update(decoder=kind, **head_row)
+    elif head_row:
         row.update(decoder=kind, **head_row)
         row["rtf_with_head"] = round((ms + head_row["head_ms_per_step"]) / 1120.0, 5)
     return row
@@ -167,11 +216,18 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--layers", type=int, default=17)
-    ap.add_argument("--decoder", choices=["none", "ctc", "rnnt", "tdt"], default="none")
+    ap.add_argument("--decoder", choices=["none", "ctc", "rnnt", "tdt", "ctc_beam"], default="none")
+    ap.add_argument("--beam-size", type=int, nargs="+", default=[4, 16, 64])
+    ap.add_argument("--classes", type=int, nargs="+", default=[129, 1025])
+    ap.add_argument("--lm", type=int, default=0, metavar="ORDER")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     enc = build(args.layers)
-    head = build_head(args.decoder) if args.decoder != "none" else None
+    if args.decoder == "ctc_beam":
+        head = [(dict(classes=C, beam_size=W, lm_order=args.lm), build_beam_head(C, W, args.lm)) for C in args.classes
+                for W in args.beam_size]
+    else:
+        head = build_head(args.decoder) if args.decoder != "none" else None
     rows = []
     for B in args.batch:
         r = one_setting(enc, B, args.steps, args.warmup, head, args.decoder)

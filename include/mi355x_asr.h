@@ -742,6 +742,56 @@ int mi355x_ctc_beam_decode_lm_stream(const void* logp, const void* lens, void* n
                                      const mi355x_ctc_beam_stream_state* state_in,
                                      const mi355x_ctc_beam_stream_state* state_out, void* stream);
 
+/* ---- the search with one or two fusion models, and phrase boosting (context biasing).  A fusion model is a back-off automaton of
+ * the six tables above with its weight `alpha` >= 0, the upper bound `ub` of a look-up's value (lm_ub above) and, optionally, a
+ * seventh table:
+ *   state_final f32 [S]   what alpha multiplies and the OUTPUT adds to a hypothesis that ends in state s (NULL: nothing)
+ * With models m1 (and m2) the search above changes in the rank only:
+ *   rank = ((tot + beta * len) + alpha1 * m1(prefix)) + alpha2 * m2(prefix),   float32, in that association, each product rounded
+ * before it is added; m(prefix) is the running float32 sum of the look-ups as lm(prefix) is above.  Each model has its own state
+ * and sum per beam.  At output -- the end of the one-shot search, every emitting step of the resumable one -- a hypothesis' score is
+ *   (rank + alpha1 * state_final1[state1]) + alpha2 * state_final2[state2]     (a term only where the table is given)
+ * and the n-best is ordered by that score, descending, ties by the hypothesis' slot in the search order, ascending.  The state a
+ * resumable step writes holds the search's order and ranks, not the final ones, so any cut into chunks gives the bits of one launch.
+ * An n-gram model: the six tables, state_final NULL.  One n-gram model alone gives the bits of mi355x_ctc_beam_decode_lm.
+ * A boosting tree (modules/boosting_tree.py builds it) is the Aho-Corasick automaton of a set P of key phrases (non-empty token
+ * sequences) in the same six tables: trie children are the arcs, the failure link is the back-off.  With context_score cs > 0 and
+ * depth_scaling ds > 0 the k-th token of a phrase is worth ts(k) = cs (k = 1) or cs * ds (k > 1); part(m) = ts(1) + .. + ts(m),
+ * full(p) = part(|p|).  For a prefix y:
+ *   complete(y) = the sum of full(p) over every occurrence of a phrase p of P as a contiguous run of y (every end position;
+ *                 overlapping and nested occurrences all count)
+ *   pending(y)  = part(m), m = the length of the longest suffix of y that is a prefix of a phrase (a whole phrase counts), 0 if none
+ *   inside the search   boost(y) = complete(y) + pending(y)          returned   boost_final(y) = complete(y)
+ * so a phrase is paid for token by token while it is being spelled, the payment is taken back when the spelling fails, and a
+ * phrase begun and not finished is not paid for in the returned score.  In the tables: the arc into trie node n carries
+ * ts(depth n) + out(n), out(n) = the sum of full over the phrases that end at n or at a node of n's failure chain; the back-off
+ * weight of n is part(depth fail(n)) - part(depth n); the root (state 0) has V arcs, a label that starts no phrase has value 0 and
+ * next state 0; state 1 (the state the search starts in) is an arc-less alias of the root with back-off 0;
+ * state_final[s] = -part(depth s).  Arc values are positive: `ub` is the bound that keeps the early-outs of the search exact.
+ * MI_ERR_ARG for what mi355x_ctc_beam_decode refuses, blank != C-1, n_models outside 1..2, a null `models`, and per model a null
+ * table (state_final may be null), n_states < 2, n_arcs < C-1, alpha < 0 or NaN, a NaN ub. */
+typedef struct mi355x_ctc_beam_fusion {
+  const void* state_arc_begin; const void* arc_tok; const void* arc_logp; const void* arc_next; const void* state_bo;
+  const void* state_bo_next; const void* state_final;
+  int n_states, n_arcs;
+  float alpha, ub;
+} mi355x_ctc_beam_fusion;
+int mi355x_ctc_beam_decode_fused(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
+                                 void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta,
+                                 const mi355x_ctc_beam_fusion* models, int n_models, void* stream);
+/* The resumable form.  The state: `beams` as above (lm_state / lm_sum are the first model's and required), then the second model's
+ * per-beam arrays [B, beam] (fresh stream: 1, 0), required with n_models = 2 and not read otherwise.  MI_ERR_ARG for what the
+ * resumable entries and the one-shot fused entry refuse and for a missing fs_state / fs_sum with two models. */
+typedef struct mi355x_ctc_beam_fused_state {
+  mi355x_ctc_beam_stream_state beams;
+  int* fs_state; float* fs_sum;
+} mi355x_ctc_beam_fused_state;
+int mi355x_ctc_beam_decode_fused_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
+                                        void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam,
+                                        float threshold, float beta, const mi355x_ctc_beam_fusion* models, int n_models, int Tcap,
+                                        const mi355x_ctc_beam_fused_state* state_in, const mi355x_ctc_beam_fused_state* state_out,
+                                        void* stream);
+
 /* SpectrogramAugmentation (nemo/collections/asr/modules/audio_preprocessing.py:443-553; SpecAugment._apply_masks
  * parts/submodules/spectr_augment.py:153-215, SpecCutout.forward :245-261): x[b, f0:f1, t0:t1] = value for n rectangles
  * rects[n][5] = (b, f0, f1, t0, t1) (int32, device memory; clipped to the tensor).  x: f32 [B, F, T], in place. */

@@ -132,6 +132,9 @@ SIGNATURES = {
     "mi355x_ctc_beam_decode_stream": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp],
     "mi355x_ctc_beam_decode_lm_stream": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, i32,
                                          i32, f32, f32, i32, vp, vp, vp],
+    # (..., models: mi355x_ctc_beam_fusion[n_models], n_models, [Tcap, state_in, state_out: mi355x_ctc_beam_fused_state,] stream)
+    "mi355x_ctc_beam_decode_fused": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, i32, vp],
+    "mi355x_ctc_beam_decode_fused_stream": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, i32, i32, vp, vp, vp],
     "mi355x_fill_rects": [vp, vp, i32, i32, i32, i32, f32, vp],
     "mi355x_specaug_rects": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp],
     "mi355x_add2_colsum": [vp, vp, vp, i64, i64, i32, vp, vp, i64, vp],

@@ -942,8 +942,17 @@ struct ctc_beam_lm {
   float alpha, ub;
 };
 struct ctc_beam_no_lm {};
-template <bool LM> struct ctc_beam_lm_of { typedef ctc_beam_no_lm type; };
-template <> struct ctc_beam_lm_of<true> { typedef ctc_beam_lm type; };
+// FUSED searches (mi355x_ctc_beam_decode_fused): the first model with its nullable `state_final` table (fin) and, FUSED = 2, a second
+// model (m2, fin2) walked alongside it
+struct ctc_beam_fused : ctc_beam_lm {
+  const float* fin;
+  ctc_beam_lm m2;
+  const float* fin2;
+};
+template <bool LM, int FUSED> struct ctc_beam_lm_of { typedef ctc_beam_no_lm type; };
+template <> struct ctc_beam_lm_of<true, 0> { typedef ctc_beam_lm type; };
+template <> struct ctc_beam_lm_of<true, 1> { typedef ctc_beam_fused type; };
+template <> struct ctc_beam_lm_of<true, 2> { typedef ctc_beam_fused type; };
 __device__ __forceinline__ float ctc_beam_alpha_lm(float alpha, float lm) {
   float al = alpha * lm;
   asm volatile("" : "+v"(al));   // rounded on its own, like beta * len
@@ -978,8 +987,15 @@ struct ctc_beam_stream {
   int Tcap;
 };
 struct ctc_beam_no_stream {};
-template <bool STREAM> struct ctc_beam_stream_of { typedef ctc_beam_no_stream type; };
-template <> struct ctc_beam_stream_of<true> { typedef ctc_beam_stream type; };
+// with the second model's per-beam arrays (FUSED = 2; mi355x_ctc_beam_fused_state)
+struct ctc_beam_stream2 : ctc_beam_stream {
+  const int* in_fs_state; const float* in_fs_sum;
+  int* out_fs_state; float* out_fs_sum;
+};
+template <bool STREAM, int FUSED> struct ctc_beam_stream_of { typedef ctc_beam_no_stream type; };
+template <> struct ctc_beam_stream_of<true, 0> { typedef ctc_beam_stream type; };
+template <> struct ctc_beam_stream_of<true, 1> { typedef ctc_beam_stream type; };
+template <> struct ctc_beam_stream_of<true, 2> { typedef ctc_beam_stream2 type; };
 // are the prefixes of nodes a and b the same sequence (they have the same length)?  BOUND (resumable search: the ids come from a
 // state and a tree the caller keeps): an id beyond `lim` is not followed
 template <bool BOUND>
@@ -998,12 +1014,21 @@ __device__ __forceinline__ bool ctc_beam_same_prefix(const int2* ws, int a, int 
 // STREAM: the resumable search (include/mi355x_asr.h).  The beams start from st.in and end in st.out, the tree and the outputs have
 // Tcap frames per utterance, a node's frame is counted from the stream's first frame, and the outputs are not padded.  The frame
 // loop is the one-shot search's: rows are indexed by the frame of the chunk, nodes by the frame of the stream, nothing else differs.
-template <bool LM, bool STREAM>
+// FUSED (mi355x_ctc_beam_decode_fused; 0: the four searches above, untouched): 1 = one fusion model, 2 = two, each with its own state
+// register, running sum, alpha and upper bound (`fs_state`, `fs_sum` for the second: two more registers in the end-of-frame shuffle).
+// The rank adds the second model's rounded product behind the first's; every early-out adds both bounds to the candidate's side in
+// that association, so it stays exact for the same reason (monotone rounding, alpha >= 0, look-up <= ub).  At output a model's
+// `state_final` table (null: none) adds alpha * state_final[state] to each hypothesis' score, the hypotheses are re-ordered inside
+// the wave by (that score descending, slot ascending) -- a rank count over readlanes and one ds_permute, no LDS -- and chased out in
+// that order.  The state a resumable step writes holds the search's order and ranks.
+template <bool LM, bool STREAM, int FUSED = 0>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ logp, const long long* __restrict__ lens, int2* node_ws,
                                                       int* __restrict__ tokens, int* __restrict__ tok_frame, int* __restrict__ hyp_len,
                                                       float* __restrict__ score, int* __restrict__ n_hyp, int Tmax, int C, int blank,
-                                                      int W, float theta, float beta, typename ctc_beam_lm_of<LM>::type lm,
-                                                      typename ctc_beam_stream_of<STREAM>::type st) {
+                                                      int W, float theta, float beta, typename ctc_beam_lm_of<LM, FUSED>::type lm,
+                                                      typename ctc_beam_stream_of<STREAM, FUSED>::type st) {
+  static_assert(FUSED == 0 || LM, "a fused search has a first model");
+  constexpr bool F2 = FUSED == 2;
   extern __shared__ float s_rows[];   // [2][C]: the log-probabilities of this frame and of the next
   const int b = blockIdx.x, lane = threadIdx.x;
   int T = (int)max(0ll, min((long long)Tmax, lens ? lens[b] : (long long)Tmax));
@@ -1019,6 +1044,8 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   int nb = 1;
   int lm_state = 1;   // (LM) the automaton state of the prefix, <s> for the empty one, and lm(prefix)
   float lm_sum = 0.f;
+  int fs_state = 1;   // (F2) the same of the second model
+  float fs_sum = 0.f;
   int f0 = 0;         // (STREAM) frames of the stream before this chunk
   if constexpr (STREAM) {
     if (st.in.node) {   // every value that becomes an address is clamped to its range: a state that is not one of this search's
@@ -1030,6 +1057,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         h = st.in.h[s]; hp = st.in.hp[s];
         pb = st.in.pb[s]; pnb = st.in.pnb[s]; tot = st.in.tot[s]; brank = st.in.brank[s];
         if constexpr (LM) { lm_state = st.in.lm_state[s]; lm_sum = st.in.lm_sum[s]; }
+        if constexpr (F2) { fs_state = st.in_fs_state[s]; fs_sum = st.in_fs_sum[s]; }
       } else {   // a slot without a beam is what the frame loop leaves in one
         pb = NEGINF; tot = NEGINF; brank = NEGINF;
       }
@@ -1079,6 +1107,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     if (live && stot != NEGINF) {
       e_rank = ctc_beam_rank(stot, beta, len); e_key = lane;
       if constexpr (LM) e_rank += ctc_beam_alpha_lm(lm.alpha, lm_sum);
+      if constexpr (F2) e_rank += ctc_beam_alpha_lm(lm.m2.alpha, fs_sum);
     }
     {
       int pos = 0;
@@ -1098,8 +1127,14 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       lm_top = ctc_beam_alpha_lm(lm.alpha, lm_sum + lm.ub);
       lm_top_max = wave_max(live ? lm_top : NEGINF);
     }
+    float fs_top = 0.f, fs_top_max = 0.f;   // (F2) the second model's
+    if constexpr (F2) {
+      fs_top = ctc_beam_alpha_lm(lm.m2.alpha, fs_sum + lm.m2.ub);
+      fs_top_max = wave_max(live ? fs_top : NEGINF);
+    }
     unsigned long long beams;
-    if constexpr (LM) beams = __ballot(live && !(ctc_beam_rank(tot + mx, beta, len + 1) + lm_top < wr));
+    if constexpr (F2) beams = __ballot(live && !((ctc_beam_rank(tot + mx, beta, len + 1) + lm_top) + fs_top < wr));
+    else if constexpr (LM) beams = __ballot(live && !(ctc_beam_rank(tot + mx, beta, len + 1) + lm_top < wr));
     else beams = __ballot(live && !(ctc_beam_rank(tot + mx, beta, len + 1) < wr));
     const float tmax = wave_max(live ? tot : NEGINF), blmax = wave_max(live ? ctc_beam_bonus(beta, len + 1) : NEGINF);
     unsigned long long groups[2] = {0ull, 0ull};   // (G <= 128: the launcher's LDS rule)
@@ -1107,7 +1142,8 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       const int c = g * 64 + lane;
       const float v = c < C ? row[c] : NEGINF;
       bool in;
-      if constexpr (LM) in = c < C && c != blank && v >= lo && !(((tmax + v) + blmax) + lm_top_max < wr);
+      if constexpr (F2) in = c < C && c != blank && v >= lo && !((((tmax + v) + blmax) + lm_top_max) + fs_top_max < wr);
+      else if constexpr (LM) in = c < C && c != blank && v >= lo && !(((tmax + v) + blmax) + lm_top_max < wr);
       else in = c < C && c != blank && v >= lo && !((tmax + v) + blmax < wr);
       if (__ballot(in)) groups[g >> 6] |= 1ull << (g & 63);
     }
@@ -1115,9 +1151,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       const int i = __ffsll((long long)bm) - 1;
       const int tok_i = ctc_rl(tok, i), len_i = ctc_rl(len, i);
       const float pb_i = ctc_rlf(pb, i), tot_i = ctc_rlf(tot, i);
-      int lms_i = 0;
-      float lmsum_i = 0.f, lm_top_i = 0.f;
-      if constexpr (LM) {
+      int lms_i = 0, fss_i = 0;
+      float lmsum_i = 0.f, lm_top_i = 0.f, fssum_i = 0.f, fs_top_i = 0.f;
+      if constexpr (F2) {
+        lms_i = ctc_rl(lm_state, i); lmsum_i = ctc_rlf(lm_sum, i); lm_top_i = ctc_rlf(lm_top, i);
+        fss_i = ctc_rl(fs_state, i); fssum_i = ctc_rlf(fs_sum, i); fs_top_i = ctc_rlf(fs_top, i);
+        if ((ctc_beam_rank(tot_i + mx, beta, len_i + 1) + lm_top_i) + fs_top_i < wr) continue;   // (the bar has risen)
+      } else if constexpr (LM) {
         lms_i = ctc_rl(lm_state, i); lmsum_i = ctc_rlf(lm_sum, i); lm_top_i = ctc_rlf(lm_top, i);
         if (ctc_beam_rank(tot_i + mx, beta, len_i + 1) + lm_top_i < wr) continue;   // (the bar has risen)
       } else {
@@ -1134,7 +1174,14 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         const float val = ((c == tok_i) ? pb_i : tot_i) + v;
         float rank = ctc_beam_rank(val, beta, len_i + 1);
         const int key = W + i * C + c;
-        if constexpr (LM) {   // the bound without a look-up first; the lanes it leaves walk the tables for their exact rank
+        if constexpr (F2) {   // both bounds first; the lanes they leave walk both models' tables
+          ok = ok && val != NEGINF && ctc_beam_beats((rank + lm_top_i) + fs_top_i, key, wr, wk);
+          if (ok) {
+            int next;
+            rank += ctc_beam_alpha_lm(lm.alpha, lmsum_i + ctc_beam_lm_lookup(lm, lms_i, c, next));
+            rank += ctc_beam_alpha_lm(lm.m2.alpha, fssum_i + ctc_beam_lm_lookup(lm.m2, fss_i, c, next));
+          }
+        } else if constexpr (LM) {   // the bound without a look-up first; the lanes it leaves walk the tables for their exact rank
           ok = ok && val != NEGINF && ctc_beam_beats(rank + lm_top_i, key, wr, wk);
           if (ok) {
             int next;
@@ -1180,6 +1227,19 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         n_lm_state = lms_s; n_lm_sum = lmsum_s;
       }
     }
+    int n_fs_state = 1;
+    float n_fs_sum = 0.f;
+    if constexpr (F2) {
+      const int fss_s = __shfl(fs_state, src, 64);
+      const float fssum_s = __shfl(fs_sum, src, 64);
+      if (is_ext) {
+        int next = 0;
+        n_fs_sum = fssum_s + ctc_beam_lm_lookup(lm.m2, fss_s, c_new, next);
+        n_fs_state = next;
+      } else if (keep) {
+        n_fs_state = fss_s; n_fs_sum = fssum_s;
+      }
+    }
     const int pos = lane;
     int n_node = 0, n_par = -1, n_tok = -1, n_len = 0;
     unsigned long long n_h = CTC_BEAM_ROOT_HASH, n_hp = 0;
@@ -1198,6 +1258,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     node = n_node; par = n_par; tok = n_tok; len = n_len; h = n_h; hp = n_hp;
     pb = n_pb; pnb = n_pnb; tot = n_tot;
     if constexpr (LM) { lm_state = n_lm_state; lm_sum = n_lm_sum; }
+    if constexpr (F2) { fs_state = n_fs_state; fs_sum = n_fs_sum; }
     brank = keep ? e_rank : NEGINF;
     nb = __popcll(__ballot(keep));
     // ---- the next row
@@ -1210,6 +1271,23 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     __threadfence_block();   // the node stores of this frame are visible to the lanes that chase them
     __syncthreads();
   }
+  // ---- (FUSED) the final term and the order of the output: lane l holds the hypothesis of output place l in o_*
+  int o_node = node, o_len = len;
+  float o_score = brank;
+  if constexpr (FUSED > 0) {
+    const bool live = lane < nb;
+    float sc = NEGINF;
+    if (live) {
+      sc = brank;
+      if (lm.fin) sc += ctc_beam_alpha_lm(lm.alpha, lm.fin[min(max(lm_state, 0), lm.n_states - 1)]);
+      if constexpr (F2)
+        if (lm.fin2) sc += ctc_beam_alpha_lm(lm.m2.alpha, lm.fin2[min(max(fs_state, 0), lm.m2.n_states - 1)]);
+    }
+    int pos = 0;
+    for (int j = 0; j < nb; ++j) pos += ctc_beam_beats(ctc_rlf(sc, j), j, sc, lane) ? 1 : 0;
+    if (!live) pos = lane;   // (the live lanes take the places 0 .. nb-1: a permutation)
+    o_node = ctc_push(node, pos); o_len = ctc_push(len, pos); o_score = ctc_pushf(sc, pos);
+  }
   if constexpr (STREAM) {
     // ---- the next state, out of place; then the n-best so far where it is asked for: no padding, Tcap positions per hypothesis
     if (lane < W) {
@@ -1218,18 +1296,19 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       st.out.h[s] = h; st.out.hp[s] = hp;
       st.out.pb[s] = pb; st.out.pnb[s] = pnb; st.out.tot[s] = tot; st.out.brank[s] = brank;
       if constexpr (LM) { st.out.lm_state[s] = lm_state; st.out.lm_sum[s] = lm_sum; }
+      if constexpr (F2) { st.out_fs_state[s] = fs_state; st.out_fs_sum[s] = fs_sum; }
     }
     if (lane == 0) { st.out.nb[b] = nb; st.out.frames_done[b] = f0 + T; }
     if (!tokens) return;
     if (lane < W) {
       const bool live = lane < nb;
-      hyp_len[b * W + lane] = live ? len : 0;
-      score[b * W + lane] = live ? brank : NEGINF;
+      hyp_len[b * W + lane] = live ? o_len : 0;
+      score[b * W + lane] = live ? o_score : NEGINF;
       if (live) {
         int* tk = tokens + ((long long)b * W + lane) * Tout;
         int* tf = tok_frame + ((long long)b * W + lane) * Tout;
-        int id = node;
-        for (int p = len - 1; p >= 0 && id > 0 && id <= node_lim; --p) {   // (len <= f0 + T <= Tout)
+        int id = o_node;
+        for (int p = o_len - 1; p >= 0 && id > 0 && id <= node_lim; --p) {   // (len <= f0 + T <= Tout)
           const int2 e = ws[id - 1];
           tk[p] = e.y;
           tf[p] = (id - 1) / W;
@@ -1244,16 +1323,16 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   int* tk = tokens + (long long)b * W * Tmax;
   int* tf = tok_frame + (long long)b * W * Tmax;
   for (int j = 0; j < W; ++j) {   // padding, by the whole wave
-    const int lj = j < nb ? ctc_rl(len, j) : 0;
+    const int lj = j < nb ? ctc_rl(o_len, j) : 0;
     for (int p = lj + lane; p < Tmax; p += 64) { tk[(long long)j * Tmax + p] = -1; tf[(long long)j * Tmax + p] = -1; }
   }
   if (lane < W) {
     const bool live = lane < nb;
-    hyp_len[b * W + lane] = live ? len : 0;
-    score[b * W + lane] = live ? brank : NEGINF;
+    hyp_len[b * W + lane] = live ? o_len : 0;
+    score[b * W + lane] = live ? o_score : NEGINF;
     if (live) {
-      int id = node;
-      for (int p = len - 1; p >= 0 && id > 0; --p) {
+      int id = o_node;
+      for (int p = o_len - 1; p >= 0 && id > 0; --p) {
         const int2 e = ws[id - 1];
         tk[(long long)lane * Tmax + p] = e.y;
         tf[(long long)lane * Tmax + p] = (id - 1) / W;
@@ -1308,7 +1387,7 @@ static ctc_beam_stream ctc_beam_stream_arg(const mi355x_ctc_beam_stream_state* s
   return st;
 }
 #define CTC_BEAM_LAUNCH(LM, STREAM, ...)                                                                                                \
-  MI_LAUNCH((ctc_beam_kernel<LM, STREAM>), dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp,                  \
+  MI_LAUNCH((ctc_beam_kernel<LM, STREAM, 0>), dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp,                  \
             (const long long*)lens, (int2*)node_ws, (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, \
             blank, beam, threshold, beta, __VA_ARGS__)
 
@@ -1371,3 +1450,74 @@ extern "C" int mi355x_ctc_beam_decode_lm_stream(const void* logp, const void* le
   return mi_check_launch();
 }
 #undef CTC_BEAM_LAUNCH
+
+// The search with one or two fusion models, each an n-gram model or a boosting tree (a table set with `state_final`), and the final
+// term at output (include/mi355x_asr.h).  New instantiations: the four kernels above are not touched by them.
+static bool ctc_beam_fusion_ok(const mi355x_ctc_beam_fusion* m, int n_models, int C, int blank) {
+  if (!m || n_models < 1 || n_models > 2 || blank != C - 1) return false;
+  for (int i = 0; i < n_models; ++i) {
+    if (!m[i].state_arc_begin || !m[i].arc_tok || !m[i].arc_logp || !m[i].arc_next || !m[i].state_bo || !m[i].state_bo_next) return false;
+    if (m[i].n_states < 2 || m[i].n_arcs < C - 1 || !(m[i].alpha >= 0.f) || m[i].ub != m[i].ub) return false;
+  }
+  return true;
+}
+static ctc_beam_lm ctc_beam_fusion_tables(const mi355x_ctc_beam_fusion& m) {
+  return {(const int*)m.state_arc_begin, (const int*)m.arc_tok, (const float*)m.arc_logp, (const int*)m.arc_next,
+          (const float*)m.state_bo, (const int*)m.state_bo_next, m.n_states, m.n_arcs, m.alpha, m.ub};
+}
+static ctc_beam_fused ctc_beam_fused_arg(const mi355x_ctc_beam_fusion* m, int n_models) {
+  ctc_beam_fused f = {};
+  static_cast<ctc_beam_lm&>(f) = ctc_beam_fusion_tables(m[0]);
+  f.fin = (const float*)m[0].state_final;
+  if (n_models == 2) {
+    f.m2 = ctc_beam_fusion_tables(m[1]);
+    f.fin2 = (const float*)m[1].state_final;
+  }
+  return f;
+}
+#define CTC_BEAM_FUSED_LAUNCH(STREAM, FUSED, ...)                                                                                        \
+  MI_LAUNCH((ctc_beam_kernel<true, STREAM, FUSED>), dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp,         \
+            (const long long*)lens, (int2*)node_ws, (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, \
+            blank, beam, threshold, beta, __VA_ARGS__)
+
+extern "C" int mi355x_ctc_beam_decode_fused(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
+                                            void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam,
+                                            float threshold, float beta, const mi355x_ctc_beam_fusion* models, int n_models,
+                                            void* stream) {
+  mi_clear_errors();
+  if (!ctc_beam_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta))
+    return MI_ERR_ARG;
+  if (!ctc_beam_fusion_ok(models, n_models, C, blank)) return MI_ERR_ARG;
+  const ctc_beam_fused f = ctc_beam_fused_arg(models, n_models);
+  if (n_models == 2) { CTC_BEAM_FUSED_LAUNCH(false, 2, f, ctc_beam_no_stream{}); }
+  else { CTC_BEAM_FUSED_LAUNCH(false, 1, f, ctc_beam_no_stream{}); }
+  return mi_check_launch();
+}
+
+extern "C" int mi355x_ctc_beam_decode_fused_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
+                                                   void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank,
+                                                   int beam, float threshold, float beta, const mi355x_ctc_beam_fusion* models,
+                                                   int n_models, int Tcap, const mi355x_ctc_beam_fused_state* state_in,
+                                                   const mi355x_ctc_beam_fused_state* state_out, void* stream) {
+  mi_clear_errors();
+  if (!ctc_beam_stream_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
+                               Tcap, state_in ? &state_in->beams : nullptr, state_out ? &state_out->beams : nullptr, true))
+    return MI_ERR_ARG;
+  if (!ctc_beam_fusion_ok(models, n_models, C, blank)) return MI_ERR_ARG;
+  const bool resumed = state_in && state_in->beams.node;
+  if (n_models == 2 && (!state_out->fs_state || !state_out->fs_sum || (resumed && (!state_in->fs_state || !state_in->fs_sum))))
+    return MI_ERR_ARG;
+  const ctc_beam_fused f = ctc_beam_fused_arg(models, n_models);
+  const ctc_beam_stream base = ctc_beam_stream_arg(state_in ? &state_in->beams : nullptr, &state_out->beams, Tcap);
+  if (n_models == 2) {
+    ctc_beam_stream2 st = {};
+    static_cast<ctc_beam_stream&>(st) = base;
+    if (resumed) { st.in_fs_state = state_in->fs_state; st.in_fs_sum = state_in->fs_sum; }
+    st.out_fs_state = state_out->fs_state; st.out_fs_sum = state_out->fs_sum;
+    CTC_BEAM_FUSED_LAUNCH(true, 2, f, st);
+  } else {
+    CTC_BEAM_FUSED_LAUNCH(true, 1, f, base);
+  }
+  return mi_check_launch();
+}
+#undef CTC_BEAM_FUSED_LAUNCH

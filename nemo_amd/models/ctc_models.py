@@ -365,7 +365,7 @@ class EncDecCTCModel(nn.Module):
                 return None
             from ..modules import WER, ctc_decoder_from_config
             # greedy / greedy_batch or beam_batch; beam / pyctcdecode / flashlight / wfst (ctc_decoding.py:231-236) raise in the factory
-            self._wer = WER(ctc_decoder_from_config(self._cfg.get("decoding"), list(vocab), what="CTC"),
+            self._wer = WER(ctc_decoder_from_config(self._cfg.get("decoding"), list(vocab), what="CTC", text_to_ids=self._text_to_ids),
                             use_cer=bool(self._cfg.get("use_cer", False)))
         return self._wer
 

@@ -116,7 +116,8 @@ class EncDecHybridRNNTCTCModel(EncDecRNNTModel):
             if vocab is None:
                 return None
             from ..modules import WER, ctc_decoder_from_config
-            self._ctc_wer = WER(ctc_decoder_from_config(self._cfg["aux_ctc"].get("decoding"), list(vocab), what="aux_ctc"),
+            self._ctc_wer = WER(ctc_decoder_from_config(self._cfg["aux_ctc"].get("decoding"), list(vocab), what="aux_ctc",
+                                                        text_to_ids=self._text_to_ids),
                                 use_cer=bool(self._cfg.get("use_cer", False)))
         return self._ctc_wer
 

@@ -7,6 +7,7 @@ from .ctc import CTCLoss  # noqa: F401
 from .ctc_decoding import (BeamBatchedCTCDecoder, CTCAligner, CTCBeamStreamState, GreedyCTCDecoder, WER,  # noqa: F401
                            ctc_decoder_from_config, ctc_offsets, word_error_rate)
 from .ngram_lm import NGramLM  # noqa: F401
+from .boosting_tree import BoostingTree  # noqa: F401
 from .rnnt_loss import RNNTLoss, RNNTLossNumba  # noqa: F401
 from .tdt_loss import TDTLoss, TDTLossNumba  # noqa: F401
 from .rnnt import RNNTDecoder, RNNTJoint  # noqa: F401

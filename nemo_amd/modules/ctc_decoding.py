@@ -124,8 +124,9 @@ class CTCBeamStreamState:
     ROOT_HASH = 0x243F6A8885A308D3
     MAX_NODES = 0x3FFFFFFF   # capacity * W: node ids are 32-bit
 
-    def __init__(self, h64, beams, utt, tree, tokens, tok_frame, lm, bound):
+    def __init__(self, h64, beams, utt, tree, tokens, tok_frame, lm, bound, fs=None):
         self.h64, self.beams, self.utt, self.tree, self.tokens, self.tok_frame = h64, beams, utt, tree, tokens, tok_frame
+        self.fs = fs   # i32 [2, B, W] or None: fs_state, fs_sum (float32 bits) of a search with a SECOND fusion model
         self.B, self.W, self.lm, self.bound = int(beams.shape[1]), int(beams.shape[2]), bool(lm), int(bound)
 
     @property
@@ -148,8 +149,9 @@ class CTCBeamStreamState:
         return torch.zeros(B, capacity, W, 2, **i32), torch.empty(B, W, capacity, **i32), torch.empty(B, W, capacity, **i32)
 
     @classmethod
-    def fresh(cls, B, W, device, capacity: int = 64, lm: bool = False):
-        """B streams that have seen nothing, with room for `capacity` frames (it grows by doubling: `reserve`)"""
+    def fresh(cls, B, W, device, capacity: int = 64, lm: bool = False, second: bool = False):
+        """B streams that have seen nothing, with room for `capacity` frames (it grows by doubling: `reserve`); `second`: with the
+        per-beam arrays of a second fusion model (`mi355x_ctc_beam_fused_state`)"""
         B, W, capacity = int(B), int(W), int(capacity)
         if B < 1 or not 1 <= W <= 64:
             raise ValueError(f"CTC beam stream state: B = {B}, W = {W} (B >= 1, 1 <= W <= 64)")
@@ -163,7 +165,11 @@ class CTCBeamStreamState:
         beams[8, :, 0] = 0       # and its rank
         utt = torch.zeros(2, B, dtype=torch.int32, device=device)
         utt[0] = 1
-        return cls(h64, beams, utt, *cls._buffers(B, W, capacity, device), lm=lm, bound=0)
+        fs = None
+        if second:
+            fs = torch.zeros(2, B, W, dtype=torch.int32, device=device)
+            fs[0] = 1
+        return cls(h64, beams, utt, *cls._buffers(B, W, capacity, device), lm=lm, bound=0, fs=fs)
 
     def arrays(self):
         """name -> [B, W] (nb, frames_done: [B]) views of the arrays the search carries (lm_state / lm_sum only for an LM search)"""
@@ -173,6 +179,8 @@ class CTCBeamStreamState:
         if not self.lm:
             del out["lm_state"], out["lm_sum"]
         out.update(nb=self.utt[0], frames_done=self.utt[1])
+        if self.fs is not None:
+            out.update(fs_state=self.fs[0], fs_sum=self.fs[1].view(torch.float32))
         return out
 
     def reserve(self, T: int):
@@ -193,7 +201,8 @@ class CTCBeamStreamState:
     def next(self, T: int):
         """the state a step over T frames writes: new beam arrays (uninitialised), this state's tree and buffers"""
         return CTCBeamStreamState(torch.empty_like(self.h64), torch.empty_like(self.beams), torch.empty_like(self.utt), self.tree,
-                                  self.tokens, self.tok_frame, self.lm, self.bound + int(T))
+                                  self.tokens, self.tok_frame, self.lm, self.bound + int(T),
+                                  fs=None if self.fs is None else torch.empty_like(self.fs))
 
     @classmethod
     def gather(cls, pairs):
@@ -204,7 +213,7 @@ class CTCBeamStreamState:
             raise ValueError("CTC beam stream state: gather of no streams")
         first = pairs[0][0]
         for s, r in pairs:
-            if s.W != first.W or s.lm != first.lm or s.device != first.device:
+            if s.W != first.W or s.lm != first.lm or s.device != first.device or (s.fs is None) != (first.fs is None):
                 raise ValueError("CTC beam stream state: gather over states of different beam width, LM-ness or device")
             if not 0 <= int(r) < s.B:
                 raise ValueError(f"CTC beam stream state: row {r} of a state of {s.B} streams")
@@ -213,7 +222,8 @@ class CTCBeamStreamState:
         for i, (s, r) in enumerate(pairs):
             tree[i, : s.capacity] = s.tree[int(r)]
         pick = lambda name: torch.stack([getattr(s, name)[:, int(r)] for s, r in pairs], dim=1).contiguous()
-        return cls(pick("h64"), pick("beams"), pick("utt"), tree, tokens, tok_frame, first.lm, max(s.bound for s, _ in pairs))
+        return cls(pick("h64"), pick("beams"), pick("utt"), tree, tokens, tok_frame, first.lm, max(s.bound for s, _ in pairs),
+                   fs=None if first.fs is None else pick("fs"))
 
 
 class BeamBatchedCTCDecoder(_CTCText):
@@ -222,14 +232,28 @@ class BeamBatchedCTCDecoder(_CTCText):
     log-probability is within that much of the frame's best (inf: every class), `beam_beta`: bonus per token, `ngram_lm`: an `NGramLM`
     over the labels, fused with weight `ngram_lm_alpha` >= 0; the score of a hypothesis is the log-probability of its LABEL SEQUENCE
     (all of its alignments the search kept) + beam_beta * length + ngram_lm_alpha * the LM's log-probability of the sequence.
-    `return_best_hypothesis=False` makes `__call__` return the n-best lists."""
+    `return_best_hypothesis=False` makes `__call__` return the n-best lists.
+    `boosting_tree`: a `BoostingTree` of key phrases, fused with weight `boosting_tree_alpha` >= 0 (alone or beside the LM:
+    `mi355x_ctc_beam_decode_fused`): the search adds boosting_tree_alpha * boost(sequence) to its rank, and the score returned holds
+    the boost of the completed phrases only -- a phrase begun and not finished is not paid for -- with the n-best ordered by it.
+    Without a tree every method calls what it called before."""
 
     confidence_cfg = None   # (the greedy decoder's attribute: confidences are not defined for the beam search)
 
     def __init__(self, vocabulary: Optional[Sequence[str]] = None, blank_id: Optional[int] = None, beam_size: int = 4,
                  return_best_hypothesis: bool = True, beam_threshold: float = 20.0, beam_beta: float = 0.0, ngram_lm=None,
-                 ngram_lm_alpha: float = 0.0):
+                 ngram_lm_alpha: float = 0.0, boosting_tree=None, boosting_tree_alpha: float = 0.0):
         self._set_labels(vocabulary, blank_id)
+        self.boosting_tree, self.boosting_tree_alpha = boosting_tree, float(boosting_tree_alpha)
+        if not self.boosting_tree_alpha >= 0:
+            raise ValueError(f"boosting_tree_alpha must be >= 0; got {boosting_tree_alpha}")
+        if boosting_tree is not None:
+            from .boosting_tree import BoostingTree
+            if not isinstance(boosting_tree, BoostingTree):
+                raise TypeError(f"boosting_tree must be a BoostingTree (BoostingTree.from_phrases), got {type(boosting_tree).__name__}")
+            if boosting_tree.vocab_size != self.blank_id:
+                raise ValueError(f"the boosting tree has {boosting_tree.vocab_size} labels, the decoder {self.blank_id} (blank_id = the "
+                                 "label count)")
         self.beam_size, self.return_best_hypothesis = int(beam_size), bool(return_best_hypothesis)
         self.beam_threshold, self.beam_beta = float(beam_threshold), float(beam_beta)
         self.ngram_lm, self.ngram_lm_alpha = ngram_lm, float(ngram_lm_alpha)
@@ -253,10 +277,18 @@ class BeamBatchedCTCDecoder(_CTCText):
         _check_log_probs(log_probs)
         lp = log_probs.to(torch.float32).contiguous()
         lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
+        if self.boosting_tree is not None:
+            return ops.ctc_beam_decode_fused(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta,
+                                             self._fusion_models())
         if self.ngram_lm is not None:
             return ops.ctc_beam_decode_lm(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, self.ngram_lm,
                                           self.ngram_lm_alpha)
         return ops.ctc_beam_decode(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta)
+
+    def _fusion_models(self):
+        """the (model, alpha) list of the fused entries: the LM, where there is one, then the tree"""
+        lm = [(self.ngram_lm, self.ngram_lm_alpha)] if self.ngram_lm is not None else []
+        return lm + [(self.boosting_tree, self.boosting_tree_alpha)]
 
     def nbest(self, log_probs, lengths=None):
         """per utterance the list of (token ids, score), best first: the D2H copy is the folded hypotheses, W * T integers an utterance"""
@@ -276,6 +308,9 @@ class BeamBatchedCTCDecoder(_CTCText):
         _check_log_probs(log_probs)
         lp = log_probs.to(torch.float32).contiguous()
         lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
+        if self.boosting_tree is not None:
+            return ops.ctc_beam_decode_fused_stream(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, state,
+                                                    self._fusion_models(), emit=emit)
         return ops.ctc_beam_decode_stream(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, state,
                                           lm=self.ngram_lm, alpha=self.ngram_lm_alpha, emit=emit)
 
@@ -328,11 +363,59 @@ def _ngram_lm_from_config(beam, vocabulary, what):
     return NGramLM.from_arpa(arpa, len(vocabulary), token_offset=offset, vocabulary=list(vocabulary) if offset is None else None)
 
 
-def ctc_decoder_from_config(decoding_cfg, vocabulary=None, what: str = "CTC"):
+_BOOST_REFUSED = {"unk_score": 0.0, "final_eos_score": 0.0, "score_per_phrase": 0.0}   # the reference's keys that are not provided
+
+
+def _boosting_tree_from_config(beam, vocabulary, what, text_to_ids):
+    """the boosting tree of a `beam` sub-section (None without one): `boosting_tree` = a BoostingTree, or {key_phrases_list: [...],
+    key_phrases_file: a text file with one phrase per line, context_score (1.0), depth_scaling (2.0)}; the phrases are tokenised with
+    `text_to_ids` (the model's own: its tokenizer, or its character parser).  `unk_score`, `final_eos_score` and `score_per_phrase`
+    of the reference are refused by name where they are not their defaults; so are a weight without phrases, a phrase that tokenises
+    to nothing and a file that is not there."""
+    alpha = float(beam.get("boosting_tree_alpha") or 0.0)
+    if alpha < 0:
+        raise ValueError(f"{what} decoding: `beam.boosting_tree_alpha` must be >= 0; got {alpha}")
+    section = beam.get("boosting_tree")
+    from .boosting_tree import BoostingTree
+    if isinstance(section, BoostingTree):
+        return section, alpha
+    section = dict(section or {})
+    for key, default in _BOOST_REFUSED.items():
+        if section.get(key) is not None and float(section[key]) != default:
+            raise NotImplementedError(f"{what} decoding: `beam.boosting_tree.{key}` = {section[key]!r} (only the default {default} is "
+                                      "provided)")
+    phrases = [str(p) for p in (section.get("key_phrases_list") or [])]
+    path = section.get("key_phrases_file")
+    if path is not None and str(path):
+        if not os.path.isfile(str(path)):
+            raise FileNotFoundError(f"{what} decoding: `beam.boosting_tree.key_phrases_file` = {path!r} is not a file")
+        with open(str(path), encoding="utf-8") as f:
+            phrases += [line.strip() for line in f if line.strip()]
+    if not phrases:
+        if alpha != 0.0:
+            raise ValueError(f"{what} decoding: `beam.boosting_tree_alpha` != 0 without key phrases (`beam.boosting_tree."
+                             "key_phrases_list` / `key_phrases_file`): there is nothing to boost")
+        return None, alpha
+    if vocabulary is None:   # (the section is only being checked)
+        return None, alpha
+    if text_to_ids is None:
+        raise ValueError(f"{what} decoding: `beam.boosting_tree` needs the model's text_to_ids to tokenise its phrases")
+    ids = []
+    for p in phrases:
+        t = [int(i) for i in text_to_ids(p)]
+        if not t:
+            raise ValueError(f"{what} decoding: the key phrase {p!r} tokenises to nothing")
+        ids.append(t)
+    return BoostingTree.from_phrases(ids, len(vocabulary), context_score=float(section.get("context_score", 1.0)),
+                                     depth_scaling=float(section.get("depth_scaling", 2.0))), alpha
+
+
+def ctc_decoder_from_config(decoding_cfg, vocabulary=None, what: str = "CTC", text_to_ids=None):
     """The one place that reads a CTC head's `decoding` section (`what` names the head in messages): checks it and, with a
     vocabulary, returns its decoding object -- GreedyCTCDecoder for `greedy` / `greedy_batch`, BeamBatchedCTCDecoder for
     `beam_batch` (its `beam` sub-section: beam_size, return_best_hypothesis, beam_threshold, beam_beta, ngram_lm_arpa,
-    ngram_lm_alpha, ngram_lm_token_offset).  Everything else the reference knows (beam = pyctcdecode / KenLM, flashlight, wfst:
+    ngram_lm_alpha, ngram_lm_token_offset, boosting_tree, boosting_tree_alpha: `_boosting_tree_from_config`, whose phrases
+    `text_to_ids` tokenises).  Everything else the reference knows (beam = pyctcdecode / KenLM, flashlight, wfst:
     ctc_decoding.py:231-236), its keys for KenLM / .nemo language models, and an LM weight without an LM raise NotImplementedError."""
     dcfg = dict(decoding_cfg or {})
     strategy = str(dcfg.get("strategy", "greedy_batch"))
@@ -348,12 +431,13 @@ def ctc_decoder_from_config(decoding_cfg, vocabulary=None, what: str = "CTC"):
     if confidence_from(dcfg.get("confidence_cfg")) is not None:
         raise NotImplementedError(f"{what} decoding: `confidence_cfg` with strategy 'beam_batch' (confidences come from the greedy search)")
     lm = _ngram_lm_from_config(beam, vocabulary, what)
+    tree, tree_alpha = _boosting_tree_from_config(beam, vocabulary, what, text_to_ids)
     if vocabulary is None:
         return None
     return BeamBatchedCTCDecoder(vocabulary=list(vocabulary), beam_size=beam.get("beam_size", 4),
                                  return_best_hypothesis=beam.get("return_best_hypothesis", True),
                                  beam_threshold=beam.get("beam_threshold", 20.0), beam_beta=beam.get("beam_beta", 0.0),
-                                 ngram_lm=lm, ngram_lm_alpha=alpha)
+                                 ngram_lm=lm, ngram_lm_alpha=alpha, boosting_tree=tree, boosting_tree_alpha=tree_alpha)
 
 
 def ctc_offsets(tokens: Sequence[str], starts: Sequence[int], ends: Sequence[int], word_pieces: bool = False):

@@ -523,7 +523,7 @@ def _ctc_beam(logp, lens, blank, beam_size, beam_threshold, beam_beta, lm, alpha
     if lm is None:
         check(lib.mi355x_ctc_beam_decode(*args, _stream()), "ctc_beam_decode")
     else:
-        tables = lm.to(logp.device)   # (cached on the LM: they outlive the launch)
+        tables = lm.to(logp.device)[:6]   # (cached on the LM: they outlive the launch; a BoostingTree's seventh table is not this entry's)
         check(lib.mi355x_ctc_beam_decode_lm(*args, *(_ptr(t) for t in tables), lm.num_states, lm.num_arcs, float(alpha),
                                             float(lm.lm_ub), _stream()), "ctc_beam_decode_lm")
     return tokens, tok_frame, hyp_len, score, n_hyp
@@ -575,9 +575,102 @@ def ctc_beam_decode_stream(logp, lens, blank, beam_size, beam_threshold, beam_be
     if lm is None:
         check(lib.mi355x_ctc_beam_decode_stream(*args, *tail), "ctc_beam_decode_stream")
     else:
-        tables = lm.to(logp.device)
+        tables = lm.to(logp.device)[:6]
         check(lib.mi355x_ctc_beam_decode_lm_stream(*args, *(_ptr(t) for t in tables), lm.num_states, lm.num_arcs, float(alpha),
                                                    float(lm.lm_ub), *tail), "ctc_beam_decode_lm_stream")
+    return outs, nxt
+
+
+class _CTCBeamFusionC(C.Structure):   # mi355x_ctc_beam_fusion
+    _fields_ = ([(n, C.c_void_p) for n in ("state_arc_begin", "arc_tok", "arc_logp", "arc_next", "state_bo", "state_bo_next",
+                                            "state_final")] +
+                [("n_states", C.c_int), ("n_arcs", C.c_int), ("alpha", C.c_float), ("ub", C.c_float)])
+
+
+class _CTCBeamFusedStateC(C.Structure):   # mi355x_ctc_beam_fused_state
+    _fields_ = [("beams", _CTCBeamStateC), ("fs_state", C.c_void_p), ("fs_sum", C.c_void_p)]
+
+    @classmethod
+    def of(cls, state):
+        a = state.arrays()
+        return cls(beams=_CTCBeamStateC.of(state), fs_state=_ptr(a["fs_state"]) if "fs_state" in a else None,
+                   fs_sum=_ptr(a["fs_sum"]) if "fs_sum" in a else None)
+
+
+def _ctc_beam_fusion_check(what, models, logp):
+    """`models` = [(NGramLM | BoostingTree, alpha), ...], one or two, over the labels of `logp`"""
+    from .modules.ngram_lm import NGramLM
+    models = list(models) if models is not None else []
+    if not 1 <= len(models) <= 2:
+        raise ValueError(f"{what}: `models` must hold one or two (model, alpha) pairs, got {len(models)}")
+    for i, pair in enumerate(models):
+        if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and isinstance(pair[0], NGramLM)):
+            got = type(pair[0]).__name__ if isinstance(pair, (tuple, list)) and len(pair) else type(pair).__name__
+            raise TypeError(f"{what}: `models` holds (NGramLM | BoostingTree, alpha) pairs, got {got}")
+        if pair[0].vocab_size != logp.shape[2] - 1:
+            raise ValueError(f"{what}: model {i} has {pair[0].vocab_size} labels, the log-probabilities {logp.shape[2]} classes "
+                             f"(labels + the blank)")
+    return models
+
+
+def _ctc_beam_fusion_array(models, logp):
+    """the `mi355x_ctc_beam_fusion` array of checked `models` and the tensors it points into"""
+    arr, keep = (_CTCBeamFusionC * len(models))(), []
+    for i, (m, alpha) in enumerate(models):
+        tables = m.to(logp.device)   # (cached on the model: they outlive the launch)
+        keep.append(tables)
+        arr[i] = _CTCBeamFusionC(*(_ptr(t) for t in tables[:6]), _ptr(tables[6]) if len(tables) > 6 else None, m.num_states,
+                                 m.num_arcs, float(alpha), float(m.lm_ub))
+    return arr, keep
+
+
+def ctc_beam_decode_fused(logp, lens, blank, beam_size, beam_threshold, beam_beta, models):
+    """`ctc_beam_decode` with one or two fusion models (mi355x_ctc_beam_decode_fused): `models` is a list of (NGramLM | BoostingTree,
+    alpha), not loose tensors.  The search ranks by ((tot + beam_beta * len) + alpha1 * m1(prefix)) + alpha2 * m2(prefix); the score
+    returned adds each BoostingTree's final term (the boost of a phrase begun and not finished is taken back) and the n-best is
+    ordered by it.  Same outputs as `ctc_beam_decode`."""
+    arr, keep = _ctc_beam_fusion_array(_ctc_beam_fusion_check("ctc_beam_decode_fused", models, logp), logp)
+    B, T, C_ = logp.shape
+    W = int(beam_size)
+    if lens is None:
+        lens = torch.full((B,), T, dtype=torch.int64, device=logp.device)
+    i32, f32 = (dict(dtype=d, device=logp.device) for d in (torch.int32, torch.float32))
+    ws = torch.empty(B * max(2, int(lib.mi355x_ctc_beam_workspace_elems(T, W))), **i32)   # (a fresh allocation: 8-byte aligned)
+    Wa = max(W, 0)
+    tokens, tok_frame = torch.empty(B, Wa, T, **i32), torch.empty(B, Wa, T, **i32)
+    hyp_len, score, n_hyp = torch.empty(B, Wa, **i32), torch.empty(B, Wa, **f32), torch.empty(B, **i32)
+    check(lib.mi355x_ctc_beam_decode_fused(_ptr(logp), _ptr(lens), _ptr(ws), _ptr(tokens), _ptr(tok_frame), _ptr(hyp_len), _ptr(score),
+                                           _ptr(n_hyp), B, T, C_, int(blank), W, float(beam_threshold), float(beam_beta),
+                                           C.cast(arr, C.c_void_p), len(arr), _stream()), "ctc_beam_decode_fused")
+    return tokens, tok_frame, hyp_len, score, n_hyp
+
+
+def ctc_beam_decode_fused_stream(logp, lens, blank, beam_size, beam_threshold, beam_beta, state, models, emit=True):
+    """one chunk of the resumable `ctc_beam_decode_fused` (mi355x_ctc_beam_decode_fused_stream): `ctc_beam_decode_stream`'s
+    arguments and results with `models` as in `ctc_beam_decode_fused`.  The state holds the search's order and ranks; the emitted
+    n-best carries the final terms.  Any cut into chunks gives the bits of `ctc_beam_decode_fused` over the whole sequence."""
+    from .modules.ctc_decoding import CTCBeamStreamState
+    models = _ctc_beam_fusion_check("ctc_beam_decode_fused_stream", models, logp)
+    B, T, C_ = logp.shape
+    W, two = int(beam_size), len(models) == 2
+    if state is None:
+        state = CTCBeamStreamState.fresh(B, W, logp.device, lm=True, second=two)
+    if state.B != B or state.W != W or not state.lm or (state.fs is not None) != two:
+        raise ValueError(f"ctc_beam_decode_fused_stream: the state is of {state.B} streams, {state.W} beams, "
+                         f"{int(state.lm) + (state.fs is not None)} fusion models; the call of {B}, {W}, {len(models)}")
+    arr, keep = _ctc_beam_fusion_array(models, logp)
+    if lens is None:
+        lens = torch.full((B,), T, dtype=torch.int64, device=logp.device)
+    state.reserve(T)
+    nxt = state.next(T)
+    i32, f32 = (dict(dtype=d, device=logp.device) for d in (torch.int32, torch.float32))
+    outs = (state.tokens, state.tok_frame, torch.empty(B, W, **i32), torch.empty(B, W, **f32), torch.empty(B, **i32)) if emit else None
+    s_in, s_out = _CTCBeamFusedStateC.of(state), _CTCBeamFusedStateC.of(nxt)
+    check(lib.mi355x_ctc_beam_decode_fused_stream(_ptr(logp), _ptr(lens), _ptr(state.tree),
+                                                  *((_ptr(t) for t in outs) if emit else (None,) * 5), B, T, C_, int(blank), W,
+                                                  float(beam_threshold), float(beam_beta), C.cast(arr, C.c_void_p), len(arr),
+                                                  state.capacity, C.byref(s_in), C.byref(s_out), _stream()),
+          "ctc_beam_decode_fused_stream")
     return outs, nxt
 
 

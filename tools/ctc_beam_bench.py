@@ -16,13 +16,17 @@ that drift of the box hits all of them alike:
     over the same T frames cut into chunks of CHUNK frames, one candidate = the whole utterance: every step carries the state
     through device arrays and appends to a tree of T frames; `emit=all` chases the n-best out on every chunk, `emit=last` on the
     last one only.  Next to the one-shot time, the difference is launches + state load and store + the chases.
+  * with `--boost N` mi355x_ctc_beam_decode_fused with a boosting tree of N key phrases (runs of 2..4 tokens cut from the arg-max
+    paths of the input itself, so that they are begun and completed) at `--boost-alpha`, alone and, with --lm, beside the n-gram
+    model (two fusion models); with --lm and --lib also mi355x_ctc_beam_decode_lm of the other builds.
 Input: log-softmax of 1.5 * N(0,1) with +5 on the class of a random path (blank with probability 0.6), the generator of the tests --
 peaked like a trained model's output, so that the threshold prunes; lengths = T.  The launches of a candidate per round are sized
 from one timed launch so that a round of it takes about `--round-ms`.  Reported per candidate: median, min and max of the
 per-round means, in microseconds per launch.
 
     python tools/ctc_beam_bench.py [--shapes 32,501,129 32,501,1025] [--beams 4 16 64] [--thresholds 20 inf] [--rounds 7]
-                                   [--lm ORDER] [--alpha 0.5] [--stream CHUNK] [--lib parent=PATH ...] [--json OUT]
+                                   [--lm ORDER] [--alpha 0.5] [--stream CHUNK] [--boost N] [--boost-alpha 1.0]
+                                   [--lib parent=PATH ...] [--json OUT]
 """
 import argparse
 import ctypes
@@ -38,12 +42,13 @@ import torch  # noqa: E402
 dev = "cuda"
 GREEDY = ("mi355x_ctc_greedy_decode", "mi355x_ctc_greedy_decode_ts")
 BEAM = "mi355x_ctc_beam_decode"
+BEAM_LM = "mi355x_ctc_beam_decode_lm"
 
 
 def load(path):
     from nemo_amd import _lib
     lib = ctypes.CDLL(path)
-    for name in GREEDY + (BEAM,):
+    for name in GREEDY + (BEAM, BEAM_LM):
         getattr(lib, name).argtypes = _lib.SIGNATURES[name]
         getattr(lib, name).restype = ctypes.c_int
     return lib
@@ -91,7 +96,32 @@ def make_ngram_lm(V, order):
         return NGramLM.from_arpa(os.path.join(d, "lm.arpa"), V)
 
 
-def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, alpha=0.5, chunk=0):
+def make_boosting_tree(logp, n_phrases, seed=0):
+    """n_phrases runs of 2..4 tokens from the collapsed arg-max paths of the input, as a BoostingTree"""
+    from nemo_amd.modules import BoostingTree
+    C = logp.shape[2]
+    g = torch.Generator().manual_seed(seed)
+    paths = []
+    for row in logp.argmax(-1).cpu().tolist():
+        ids, prev = [], None
+        for c in row:
+            if c != prev and c != C - 1:
+                ids.append(c)
+            prev = c
+        paths.append(ids)
+    paths = [x for x in paths if len(x) >= 4]
+    phrases, tries = [], 0
+    while len(phrases) < n_phrases and tries < 100 * n_phrases:
+        tries += 1
+        ids = paths[int(torch.randint(len(paths), (1,), generator=g))]
+        n = int(torch.randint(2, 5, (1,), generator=g))
+        a = int(torch.randint(0, len(ids) - n + 1, (1,), generator=g))
+        if tuple(ids[a:a + n]) not in phrases:
+            phrases.append(tuple(ids[a:a + n]))
+    return BoostingTree.from_phrases(phrases, C - 1)
+
+
+def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, alpha=0.5, chunk=0, boost=0, boost_alpha=1.0):
     from nemo_amd import _lib
     lib = _lib.lib
     logp = make_logp(B, T, C)
@@ -114,13 +144,27 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, 
         return fn
 
     lm = make_ngram_lm(C - 1, lm_order) if lm_order else None
-    tables = [p(t) for t in lm.to(dev)] if lm else None
+    tables = [p(t) for t in lm.to(dev)[:6]] if lm else None
 
-    def beam_lm(W, th, a):
+    def beam_lm(W, th, a, l=lib):
         def fn():
-            rc = lib.mi355x_ctc_beam_decode_lm(p(logp), p(lens), p(ws), p(tokens), p(frames), p(hyp_len), p(score), p(n_hyp), B, T, C,
+            rc = l.mi355x_ctc_beam_decode_lm(p(logp), p(lens), p(ws), p(tokens), p(frames), p(hyp_len), p(score), p(n_hyp), B, T, C,
                                                C - 1, W, th, 0.0, *tables, lm.num_states, lm.num_arcs, a, lm.lm_ub, stream)
             assert rc == 0, rc
+        return fn
+
+    tree = make_boosting_tree(logp, boost) if boost else None
+
+    def beam_fused(W, th, models):
+        """mi355x_ctc_beam_decode_fused with `models` = [(NGramLM | BoostingTree, alpha), ...]"""
+        from nemo_amd.ops import _ctc_beam_fusion_array
+        arr, keep = _ctc_beam_fusion_array(models, logp)
+
+        def fn():
+            rc = lib.mi355x_ctc_beam_decode_fused(p(logp), p(lens), p(ws), p(tokens), p(frames), p(hyp_len), p(score), p(n_hyp), B, T, C,
+                                                  C - 1, W, th, 0.0, ctypes.cast(arr, ctypes.c_void_p), len(arr), stream)
+            assert rc == 0, rc
+        fn._keep = (arr, keep)
         return fn
 
     chunks = [logp[:, t:t + chunk].contiguous() for t in range(0, T, chunk)] if chunk else []
@@ -168,6 +212,13 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, 
             if lm:
                 cands[f"beam+lm W={W} threshold={th} alpha={alpha}"] = beam_lm(W, th, alpha)
                 cands[f"beam+lm W={W} threshold={th} alpha=0"] = beam_lm(W, th, 0.0)
+                for name, l in libs.items():
+                    cands[f"beam+lm[{name}] W={W} threshold={th} alpha={alpha}"] = beam_lm(W, th, alpha, l)
+            if tree:
+                cands[f"beam+boost W={W} threshold={th} alpha={boost_alpha}"] = beam_fused(W, th, [(tree, boost_alpha)])
+                if lm:
+                    cands[f"beam+lm+boost W={W} threshold={th} alpha={alpha},{boost_alpha}"] = beam_fused(W, th, [(lm, alpha),
+                                                                                                               (tree, boost_alpha)])
             if chunk:
                 for emit_all in (True, False):
                     tag = f"W={W} threshold={th} chunk={chunk} emit={'all' if emit_all else 'last'}"
@@ -184,6 +235,14 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, 
         beam_lm(Wmax, thresholds[0], alpha)()
         torch.cuda.synchronize()
         row["best_changed_by_lm"] = f"{sum(int(l0[b, 0]) != int(hyp_len[b, 0]) or not torch.equal(t0[b, 0], tokens[b, 0]) for b in range(B))}/{B}"
+    if tree:
+        row["boost"] = dict(phrases=len(tree.phrases), states=tree.num_states, arcs=tree.num_arcs, ub=tree.lm_ub)
+        beam(Wmax, thresholds[0])()
+        torch.cuda.synchronize()
+        t0, l0 = tokens.clone(), hyp_len.clone()
+        beam_fused(Wmax, thresholds[0], [(tree, boost_alpha)])()
+        torch.cuda.synchronize()
+        row["best_changed_by_boost"] = f"{sum(int(l0[b, 0]) != int(hyp_len[b, 0]) or not torch.equal(t0[b, 0], tokens[b, 0]) for b in range(B))}/{B}"
     # what the search found at the widest setting: hypotheses per utterance and how often the best one differs from the greedy one
     beam(Wmax, thresholds[0])(); greedy(lib, False)()
     torch.cuda.synchronize()
@@ -203,6 +262,8 @@ def main():
     ap.add_argument("--lm", type=int, default=0, metavar="ORDER", help="also time the search with an n-gram model of this order fused")
     ap.add_argument("--alpha", type=float, default=0.5, help="the fusion weight of the --lm runs")
     ap.add_argument("--stream", type=int, default=0, metavar="CHUNK", help="also time the resumable search over chunks of CHUNK frames")
+    ap.add_argument("--boost", type=int, default=0, metavar="N", help="also time the search with a boosting tree of N key phrases")
+    ap.add_argument("--boost-alpha", type=float, default=1.0, help="the weight of the --boost runs")
     ap.add_argument("--lib", nargs="*", default=[], help="name=path of further builds of the library")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -210,7 +271,8 @@ def main():
     out = dict(device=torch.cuda.get_device_name(0), rounds=args.rounds, round_ms=args.round_ms, shapes=[])
     for s in args.shapes:
         B, T, C = (int(x) for x in s.split(","))
-        row = one_shape(B, T, C, args.beams, args.thresholds, libs, args.rounds, args.round_ms, args.lm, args.alpha, args.stream)
+        row = one_shape(B, T, C, args.beams, args.thresholds, libs, args.rounds, args.round_ms, args.lm, args.alpha, args.stream, args.boost,
+                        args.boost_alpha)
         out["shapes"].append(row)
         print(json.dumps(row), flush=True)
     if args.json:

@@ -877,8 +877,8 @@ extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const voi
 }
 
 // ------------------------------------------------------------------------------------------------ CTC prefix beam search
-// The classic CTC prefix beam search (the `beam_batch` strategy), with or without shallow fusion of a token-level back-off n-gram
-// language model (the LM flag of the kernel template: one search, two instantiations), ONE launch per batch, one wave per utterance,
+// The classic CTC prefix beam search (the `beam_batch` strategy), with or without shallow fusion of token-level back-off automata
+// (ctc_beam_kernel<NM, STREAM, FINAL>: one search, eight instantiations), ONE launch per batch, one wave per utterance,
 // a lane per beam: the whole search state of an utterance lives in the registers of its wave, so the frame loop has no workgroup
 // barrier, and nothing of size [B, T, C] leaves the device.  include/mi355x_asr.h states the search; in short, per frame:
 //   token pruning   c is considered iff lp[t,c] >= max_c lp[t,c] - threshold (float32 subtract and compare)
@@ -886,7 +886,6 @@ extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const voi
 //   extensions      ext(i,c).pnb = (c == last_i ? pb_i : tot_i) + lp[c] ; where the prefix of ext(i,c) is the prefix of a beam j of
 //                   the current set, the value is added (log-add-exp) to stay(j).pnb instead: the two are ONE candidate
 //   selection       the `beam` candidates of the largest rank = tot + beta * len, tot = logaddexp(pb, pnb) > -inf
-//                   (LM: rank = (tot + beta * len) + alpha * lm(prefix); nothing else of the search changes)
 // A beam is a node of a prefix tree.  Node 0 is the empty prefix; the extension kept in slot s of frame t becomes node
 // 1 + t*beam + s and stores (parent node, token) at node_ws[t*beam + s], so the frame a token was created in is (node - 1) / beam.
 // Which beam an extension would duplicate: a beam carries a 64-bit hash of its prefix and of its parent's prefix; equal hash and
@@ -903,15 +902,26 @@ extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const voi
 // Ties: candidates are ordered by (rank descending, key ascending), key = i for stay(i) and beam + i*C + c for ext(i,c), i the slot
 // of the beam in the sorted set of the previous frame; the order is total, so selection and output order are deterministic.
 // Arithmetic: plain float32, logaddexp(a,b) = max + log1pf(expf(-|a-b|)); beta * len is rounded on its own (no fused multiply-add).
-// Language model (LM instantiation): the back-off automaton of include/mi355x_asr.h in six global arrays, small and shared by every
-// wave, so they stay in L2; LDS holds what it held.  A beam carries its automaton state and lm(prefix) (`lm_state`, `lm_sum`: two
-// more registers that travel with it in the end-of-frame shuffle).  lm(prefix . c) = lm_sum + look-up(lm_state, c), and a look-up
-// <= lm_ub, so every early-out keeps its form with alpha * (lm_sum + lm_ub) added to the side of the candidate: rounding is monotone,
+// Fusion models (NM of the kernel template = their number, 0 .. 2: an n-gram language model, a boosting tree, or both): each is the
+// back-off automaton of include/mi355x_asr.h in six global arrays, small and shared by every wave, so they stay in L2; LDS holds
+// what it held.  A beam carries, per model, its automaton state and m(prefix) (`m_state[k]`, `m_sum[k]`: registers that travel with
+// it in the end-of-frame shuffle; k is a constant everywhere, `CTC_BEAM_EACH_MODEL`, so they stay registers), and
+//   rank = ((tot + beta * len) + alpha_0 * m_0(prefix)) + alpha_1 * m_1(prefix)     each product rounded on its own; nothing else of
+// the search changes.  m(prefix . c) = m_sum + look-up(m_state, c), and a look-up <= ub, so every early-out keeps its form with
+// alpha_k * (m_sum[k] + ub_k) added to the side of the candidate in the same association (`ctc_beam_bound`): rounding is monotone,
 // alpha >= 0, the bar only rises.  In the streamed loop that bound, which needs no look-up, is tested first and only the lanes that
 // pass it walk the tables (a binary search in the arcs of the state, a direct index at state 0); the ballot sees exact ranks.  The
-// running top-W stays (rank, key, value): a kept extension repeats its one look-up at the end of the frame -- same inputs, same
-// value -- to get its lm_sum and next state.  Every chase is bounded (back-off chain: n_states steps, binary search: 32) and every
+// running top-W stays (rank, key, value): a kept extension repeats its look-ups at the end of the frame -- same inputs, same
+// values -- to get its sums and next states.  Every chase is bounded (back-off chain: n_states steps, binary search: 32) and every
 // index is clamped to its table, so tables that are not what the loader checks give a wrong score, never a hang or a stray load.
+// At output a model's `state_final` table (fin; null: none) adds alpha * fin[state] to each hypothesis' score, the hypotheses are
+// re-ordered inside the wave by (that score descending, slot ascending) -- a rank count over readlanes and one ds_permute, no LDS;
+// the identity where no model has the table -- and chased out in that order.  FINAL compiles that in; the launcher leaves it out
+// for one model without the table (the n-gram search): it runs once per launch, but the values it keeps alive change the register
+// and SGPR-spill choices inside the frame loop, measured at 2.4 to 4.3 % of that search (profiles/ctc_beam_unify.md).
+// STREAM: the resumable search.  The beams start from st.in and end in st.out (which hold the search's order and ranks), the tree
+// and the outputs have Tcap frames per utterance, a node's frame is counted from the stream's first frame, and the outputs are not
+// padded.  The frame loop is the one-shot search's: rows are indexed by the frame of the chunk, nodes by the frame of the stream.
 #define CTC_BEAM_MAX 64
 #define CTC_BEAM_ROOT_HASH 0x243F6A8885A308D3ull
 __device__ __forceinline__ float ctc_lae(float a, float b) {
@@ -935,24 +945,22 @@ __device__ __forceinline__ float ctc_pushf(float v, int dst) { return __int_as_f
 // lane l <- lane l-1 over the whole wave (DPP wave_shr:1); lane 0 keeps its value
 __device__ __forceinline__ int ctc_up1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ float ctc_up1f(float v) { return __int_as_float(ctc_up1(__float_as_int(v))); }
-// the six tables of the back-off automaton with the fusion weight and the upper bound of a look-up; nothing where LM is off
+// one value of T per fusion model in a kernel parameter: v[0 .. NM-1]; an empty record at NM = 0 (device code has no zero-length
+// arrays)
+template <class T, int NM> struct ctc_beam_per_model { T v[NM]; };
+template <class T> struct ctc_beam_per_model<T, 0> {};
+// a fusion model: the six tables of the back-off automaton, the fusion weight, the upper bound of a look-up and the nullable
+// `state_final` table
 struct ctc_beam_lm {
   const int* arc_begin; const int* arc_tok; const float* arc_logp; const int* arc_next; const float* bo; const int* bo_next;
   int n_states, n_arcs;
   float alpha, ub;
-};
-struct ctc_beam_no_lm {};
-// FUSED searches (mi355x_ctc_beam_decode_fused): the first model with its nullable `state_final` table (fin) and, FUSED = 2, a second
-// model (m2, fin2) walked alongside it
-struct ctc_beam_fused : ctc_beam_lm {
   const float* fin;
-  ctc_beam_lm m2;
-  const float* fin2;
 };
-template <bool LM, int FUSED> struct ctc_beam_lm_of { typedef ctc_beam_no_lm type; };
-template <> struct ctc_beam_lm_of<true, 0> { typedef ctc_beam_lm type; };
-template <> struct ctc_beam_lm_of<true, 1> { typedef ctc_beam_fused type; };
-template <> struct ctc_beam_lm_of<true, 2> { typedef ctc_beam_fused type; };
+// the models of a kernel.  The kernels with the output's final terms take room for two whatever NM (the second slot is not read at
+// NM = 1): where the stream record lands in the argument block decides how its scalar loads are grouped and which SGPRs spill, and
+// the resumable one-model kernel measured 0.6 to 0.9 % slower behind a one-model record (profiles/ctc_beam_unify.md)
+template <int NM, bool FINAL> using ctc_beam_models = ctc_beam_per_model<ctc_beam_lm, (FINAL ? 2 : NM)>;
 __device__ __forceinline__ float ctc_beam_alpha_lm(float alpha, float lm) {
   float al = alpha * lm;
   asm volatile("" : "+v"(al));   // rounded on its own, like beta * len
@@ -980,22 +988,38 @@ __device__ __forceinline__ float ctc_beam_lm_lookup(const ctc_beam_lm& lm, int s
 }
 // candidate (r, k) goes in front of (wr, wk)
 __device__ __forceinline__ bool ctc_beam_beats(float r, int k, float wr, int wk) { return r > wr || (r == wr && k < wk); }
-// the state a resumable search starts from (in.node null: fresh streams) and the one it writes, with the frames the tree holds;
-// nothing in the one-shot search
-struct ctc_beam_stream {
+// the loop over the models, unrolled by the preprocessor: the body once per model k < NM (<= 2), in model order, with k a constant
+// expression, so that the per-model registers and records are indexed by constants from the first pass on and the code is what
+// the same steps written out by hand per model compile to
+#define CTC_BEAM_EACH_MODEL(NM, k, ...)                              \
+  do {                                                               \
+    if constexpr ((NM) > 0) { constexpr int k = 0; __VA_ARGS__ }     \
+    if constexpr ((NM) > 1) { constexpr int k = 1; __VA_ARGS__ }     \
+  } while (0)
+// what no extension of a beam can rank above: `base` with the models' bounds added in model order, ((base + top_0) + top_1)
+template <int NM>
+__device__ __forceinline__ float ctc_beam_bound(float base, const float (&top)[NM > 0 ? NM : 1]) {
+  CTC_BEAM_EACH_MODEL(NM, k, { base += top[k]; });
+  return base;
+}
+// the state a resumable search starts from (in.node null: fresh streams) and the one it writes, with the frames the tree holds and
+// one (state, sum) pointer pair in each per model, `model<k>()`: the first model's are where the C struct has them, lm_state and
+// lm_sum of in / out, the pairs of the models behind it follow (fs_state / fs_sum of mi355x_ctc_beam_fused_state); nothing in the
+// one-shot search
+struct ctc_beam_model_state {
+  const int* in_state; const float* in_sum;
+  int* out_state; float* out_sum;
+};
+template <int NM, bool STREAM> struct ctc_beam_stream {};
+template <int NM> struct ctc_beam_stream<NM, true> {
   mi355x_ctc_beam_stream_state in, out;
   int Tcap;
+  ctc_beam_per_model<ctc_beam_model_state, (NM > 1 ? NM - 1 : 0)> more;
+  template <int k> __device__ __forceinline__ ctc_beam_model_state model() const {
+    if constexpr (k == 0) return {in.lm_state, in.lm_sum, out.lm_state, out.lm_sum};
+    else return more.v[k - 1];
+  }
 };
-struct ctc_beam_no_stream {};
-// with the second model's per-beam arrays (FUSED = 2; mi355x_ctc_beam_fused_state)
-struct ctc_beam_stream2 : ctc_beam_stream {
-  const int* in_fs_state; const float* in_fs_sum;
-  int* out_fs_state; float* out_fs_sum;
-};
-template <bool STREAM, int FUSED> struct ctc_beam_stream_of { typedef ctc_beam_no_stream type; };
-template <> struct ctc_beam_stream_of<true, 0> { typedef ctc_beam_stream type; };
-template <> struct ctc_beam_stream_of<true, 1> { typedef ctc_beam_stream type; };
-template <> struct ctc_beam_stream_of<true, 2> { typedef ctc_beam_stream2 type; };
 // are the prefixes of nodes a and b the same sequence (they have the same length)?  BOUND (resumable search: the ids come from a
 // state and a tree the caller keeps): an id beyond `lim` is not followed
 template <bool BOUND>
@@ -1011,24 +1035,15 @@ __device__ __forceinline__ bool ctc_beam_same_prefix(const int2* ws, int a, int 
   return true;
 }
 
-// STREAM: the resumable search (include/mi355x_asr.h).  The beams start from st.in and end in st.out, the tree and the outputs have
-// Tcap frames per utterance, a node's frame is counted from the stream's first frame, and the outputs are not padded.  The frame
-// loop is the one-shot search's: rows are indexed by the frame of the chunk, nodes by the frame of the stream, nothing else differs.
-// FUSED (mi355x_ctc_beam_decode_fused; 0: the four searches above, untouched): 1 = one fusion model, 2 = two, each with its own state
-// register, running sum, alpha and upper bound (`fs_state`, `fs_sum` for the second: two more registers in the end-of-frame shuffle).
-// The rank adds the second model's rounded product behind the first's; every early-out adds both bounds to the candidate's side in
-// that association, so it stays exact for the same reason (monotone rounding, alpha >= 0, look-up <= ub).  At output a model's
-// `state_final` table (null: none) adds alpha * state_final[state] to each hypothesis' score, the hypotheses are re-ordered inside
-// the wave by (that score descending, slot ascending) -- a rank count over readlanes and one ds_permute, no LDS -- and chased out in
-// that order.  The state a resumable step writes holds the search's order and ranks.
-template <bool LM, bool STREAM, int FUSED = 0>
+template <int NM, bool STREAM, bool FINAL>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ logp, const long long* __restrict__ lens, int2* node_ws,
                                                       int* __restrict__ tokens, int* __restrict__ tok_frame, int* __restrict__ hyp_len,
                                                       float* __restrict__ score, int* __restrict__ n_hyp, int Tmax, int C, int blank,
-                                                      int W, float theta, float beta, typename ctc_beam_lm_of<LM, FUSED>::type lm,
-                                                      typename ctc_beam_stream_of<STREAM, FUSED>::type st) {
-  static_assert(FUSED == 0 || LM, "a fused search has a first model");
-  constexpr bool F2 = FUSED == 2;
+                                                      int W, float theta, float beta, ctc_beam_models<NM, FINAL> lm,
+                                                      ctc_beam_stream<NM, STREAM> st) {
+  static_assert(NM >= 0 && NM <= 2, "at most two fusion models");
+  static_assert(NM > 0 || !FINAL, "a final term is a model's");
+  constexpr int NR = NM > 0 ? NM : 1;   // (per-model registers: an array of one that nothing touches at NM = 0)
   extern __shared__ float s_rows[];   // [2][C]: the log-probabilities of this frame and of the next
   const int b = blockIdx.x, lane = threadIdx.x;
   int T = (int)max(0ll, min((long long)Tmax, lens ? lens[b] : (long long)Tmax));
@@ -1042,10 +1057,9 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   unsigned long long h = CTC_BEAM_ROOT_HASH, hp = 0;
   float pb = lane == 0 ? 0.f : NEGINF, pnb = NEGINF, tot = pb, brank = pb;
   int nb = 1;
-  int lm_state = 1;   // (LM) the automaton state of the prefix, <s> for the empty one, and lm(prefix)
-  float lm_sum = 0.f;
-  int fs_state = 1;   // (F2) the same of the second model
-  float fs_sum = 0.f;
+  int m_state[NR];    // per model: the automaton state of the prefix, <s> for the empty one, and m(prefix)
+  float m_sum[NR];
+  CTC_BEAM_EACH_MODEL(NM, k, { m_state[k] = 1; m_sum[k] = 0.f; });
   int f0 = 0;         // (STREAM) frames of the stream before this chunk
   if constexpr (STREAM) {
     if (st.in.node) {   // every value that becomes an address is clamped to its range: a state that is not one of this search's
@@ -1056,8 +1070,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         node = st.in.node[s]; par = st.in.par[s]; tok = min(max(st.in.tok[s], -1), C - 1); len = min(max(st.in.len[s], 0), f0);
         h = st.in.h[s]; hp = st.in.hp[s];
         pb = st.in.pb[s]; pnb = st.in.pnb[s]; tot = st.in.tot[s]; brank = st.in.brank[s];
-        if constexpr (LM) { lm_state = st.in.lm_state[s]; lm_sum = st.in.lm_sum[s]; }
-        if constexpr (F2) { fs_state = st.in_fs_state[s]; fs_sum = st.in_fs_sum[s]; }
+        CTC_BEAM_EACH_MODEL(NM, k, { m_state[k] = st.template model<k>().in_state[s]; m_sum[k] = st.template model<k>().in_sum[s]; });
       } else {   // a slot without a beam is what the frame loop leaves in one
         pb = NEGINF; tot = NEGINF; brank = NEGINF;
       }
@@ -1106,8 +1119,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     int e_key = 0x7fffffff - lane;
     if (live && stot != NEGINF) {
       e_rank = ctc_beam_rank(stot, beta, len); e_key = lane;
-      if constexpr (LM) e_rank += ctc_beam_alpha_lm(lm.alpha, lm_sum);
-      if constexpr (F2) e_rank += ctc_beam_alpha_lm(lm.m2.alpha, fs_sum);
+      CTC_BEAM_EACH_MODEL(NM, k, { e_rank += ctc_beam_alpha_lm(lm.v[k].alpha, m_sum[k]); });
     }
     {
       int pos = 0;
@@ -1121,48 +1133,31 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     // ---- extensions, streamed.  The bar only rises, and float32 rounding is monotone, so what cannot beat the bar of the stays is
     // out for the whole frame: a beam whose best possible extension (tot_i + mx) ranks below it, and a class whose extension of the
     // best possible beam (the largest tot, the largest bonus) does -- a group of 64 classes with no other class is never read again.
-    // (LM) what alpha * lm of an extension of this beam cannot exceed
-    float lm_top = 0.f, lm_top_max = 0.f;
-    if constexpr (LM) {
-      lm_top = ctc_beam_alpha_lm(lm.alpha, lm_sum + lm.ub);
-      lm_top_max = wave_max(live ? lm_top : NEGINF);
-    }
-    float fs_top = 0.f, fs_top_max = 0.f;   // (F2) the second model's
-    if constexpr (F2) {
-      fs_top = ctc_beam_alpha_lm(lm.m2.alpha, fs_sum + lm.m2.ub);
-      fs_top_max = wave_max(live ? fs_top : NEGINF);
-    }
-    unsigned long long beams;
-    if constexpr (F2) beams = __ballot(live && !((ctc_beam_rank(tot + mx, beta, len + 1) + lm_top) + fs_top < wr));
-    else if constexpr (LM) beams = __ballot(live && !(ctc_beam_rank(tot + mx, beta, len + 1) + lm_top < wr));
-    else beams = __ballot(live && !(ctc_beam_rank(tot + mx, beta, len + 1) < wr));
+    // per model, what alpha * m of an extension of this beam cannot exceed
+    float m_top[NR], m_top_max[NR];
+    CTC_BEAM_EACH_MODEL(NM, k, {
+      m_top[k] = ctc_beam_alpha_lm(lm.v[k].alpha, m_sum[k] + lm.v[k].ub);
+      m_top_max[k] = wave_max(live ? m_top[k] : NEGINF);
+    });
+    const unsigned long long beams = __ballot(live && !(ctc_beam_bound<NM>(ctc_beam_rank(tot + mx, beta, len + 1), m_top) < wr));
     const float tmax = wave_max(live ? tot : NEGINF), blmax = wave_max(live ? ctc_beam_bonus(beta, len + 1) : NEGINF);
     unsigned long long groups[2] = {0ull, 0ull};   // (G <= 128: the launcher's LDS rule)
     for (int g = 0; g < G; ++g) {
       const int c = g * 64 + lane;
       const float v = c < C ? row[c] : NEGINF;
-      bool in;
-      if constexpr (F2) in = c < C && c != blank && v >= lo && !((((tmax + v) + blmax) + lm_top_max) + fs_top_max < wr);
-      else if constexpr (LM) in = c < C && c != blank && v >= lo && !(((tmax + v) + blmax) + lm_top_max < wr);
-      else in = c < C && c != blank && v >= lo && !((tmax + v) + blmax < wr);
+      const bool in = c < C && c != blank && v >= lo && !(ctc_beam_bound<NM>((tmax + v) + blmax, m_top_max) < wr);
       if (__ballot(in)) groups[g >> 6] |= 1ull << (g & 63);
     }
     for (unsigned long long bm = beams; bm; bm &= bm - 1) {
       const int i = __ffsll((long long)bm) - 1;
       const int tok_i = ctc_rl(tok, i), len_i = ctc_rl(len, i);
       const float pb_i = ctc_rlf(pb, i), tot_i = ctc_rlf(tot, i);
-      int lms_i = 0, fss_i = 0;
-      float lmsum_i = 0.f, lm_top_i = 0.f, fssum_i = 0.f, fs_top_i = 0.f;
-      if constexpr (F2) {
-        lms_i = ctc_rl(lm_state, i); lmsum_i = ctc_rlf(lm_sum, i); lm_top_i = ctc_rlf(lm_top, i);
-        fss_i = ctc_rl(fs_state, i); fssum_i = ctc_rlf(fs_sum, i); fs_top_i = ctc_rlf(fs_top, i);
-        if ((ctc_beam_rank(tot_i + mx, beta, len_i + 1) + lm_top_i) + fs_top_i < wr) continue;   // (the bar has risen)
-      } else if constexpr (LM) {
-        lms_i = ctc_rl(lm_state, i); lmsum_i = ctc_rlf(lm_sum, i); lm_top_i = ctc_rlf(lm_top, i);
-        if (ctc_beam_rank(tot_i + mx, beta, len_i + 1) + lm_top_i < wr) continue;   // (the bar has risen)
-      } else {
-        if (ctc_beam_rank(tot_i + mx, beta, len_i + 1) < wr) continue;   // (the bar has risen)
-      }
+      int m_state_i[NR];
+      float m_sum_i[NR], m_top_i[NR];
+      CTC_BEAM_EACH_MODEL(NM, k, {
+        m_state_i[k] = ctc_rl(m_state[k], i); m_sum_i[k] = ctc_rlf(m_sum[k], i); m_top_i[k] = ctc_rlf(m_top[k], i);
+      });
+      if (ctc_beam_bound<NM>(ctc_beam_rank(tot_i + mx, beta, len_i + 1), m_top_i) < wr) continue;   // (the bar has risen)
       const unsigned long long kids = __ballot(live && pl == i);
       for (int hw = 0; hw < 2; ++hw)
       for (unsigned long long gm = groups[hw]; gm; gm &= gm - 1) {
@@ -1174,18 +1169,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         const float val = ((c == tok_i) ? pb_i : tot_i) + v;
         float rank = ctc_beam_rank(val, beta, len_i + 1);
         const int key = W + i * C + c;
-        if constexpr (F2) {   // both bounds first; the lanes they leave walk both models' tables
-          ok = ok && val != NEGINF && ctc_beam_beats((rank + lm_top_i) + fs_top_i, key, wr, wk);
+        if constexpr (NM > 0) {   // the bounds, without a look-up, first; the lanes they leave walk the tables for their exact rank
+          ok = ok && val != NEGINF && ctc_beam_beats(ctc_beam_bound<NM>(rank, m_top_i), key, wr, wk);
           if (ok) {
             int next;
-            rank += ctc_beam_alpha_lm(lm.alpha, lmsum_i + ctc_beam_lm_lookup(lm, lms_i, c, next));
-            rank += ctc_beam_alpha_lm(lm.m2.alpha, fssum_i + ctc_beam_lm_lookup(lm.m2, fss_i, c, next));
-          }
-        } else if constexpr (LM) {   // the bound without a look-up first; the lanes it leaves walk the tables for their exact rank
-          ok = ok && val != NEGINF && ctc_beam_beats(rank + lm_top_i, key, wr, wk);
-          if (ok) {
-            int next;
-            rank += ctc_beam_alpha_lm(lm.alpha, lmsum_i + ctc_beam_lm_lookup(lm, lms_i, c, next));
+            CTC_BEAM_EACH_MODEL(NM, k, {
+              rank += ctc_beam_alpha_lm(lm.v[k].alpha, m_sum_i[k] + ctc_beam_lm_lookup(lm.v[k], m_state_i[k], c, next));
+            });
           }
         }
         for (unsigned long long m = __ballot(ok && val != NEGINF && ctc_beam_beats(rank, key, wr, wk)); m; m &= m - 1) {
@@ -1214,32 +1204,20 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     const unsigned long long hp_s = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(hp >> 32), src, 64) << 32) |
                                     (unsigned)__shfl((int)(unsigned)hp, src, 64);
     const float spb_s = __shfl(spb, src, 64), spnb_s = __shfl(spnb, src, 64), stot_s = __shfl(stot, src, 64);
-    int n_lm_state = 1;
-    float n_lm_sum = 0.f;
-    if constexpr (LM) {
-      const int lms_s = __shfl(lm_state, src, 64);
-      const float lmsum_s = __shfl(lm_sum, src, 64);
+    int n_m_state[NR];
+    float n_m_sum[NR];
+    CTC_BEAM_EACH_MODEL(NM, k, {
+      n_m_state[k] = 1; n_m_sum[k] = 0.f;
+      const int m_state_s = __shfl(m_state[k], src, 64);
+      const float m_sum_s = __shfl(m_sum[k], src, 64);
       if (is_ext) {   // the look-up that ranked it, once more: its value and the state behind it
         int next = 0;
-        n_lm_sum = lmsum_s + ctc_beam_lm_lookup(lm, lms_s, c_new, next);
-        n_lm_state = next;
+        n_m_sum[k] = m_sum_s + ctc_beam_lm_lookup(lm.v[k], m_state_s, c_new, next);
+        n_m_state[k] = next;
       } else if (keep) {
-        n_lm_state = lms_s; n_lm_sum = lmsum_s;
+        n_m_state[k] = m_state_s; n_m_sum[k] = m_sum_s;
       }
-    }
-    int n_fs_state = 1;
-    float n_fs_sum = 0.f;
-    if constexpr (F2) {
-      const int fss_s = __shfl(fs_state, src, 64);
-      const float fssum_s = __shfl(fs_sum, src, 64);
-      if (is_ext) {
-        int next = 0;
-        n_fs_sum = fssum_s + ctc_beam_lm_lookup(lm.m2, fss_s, c_new, next);
-        n_fs_state = next;
-      } else if (keep) {
-        n_fs_state = fss_s; n_fs_sum = fssum_s;
-      }
-    }
+    });
     const int pos = lane;
     int n_node = 0, n_par = -1, n_tok = -1, n_len = 0;
     unsigned long long n_h = CTC_BEAM_ROOT_HASH, n_hp = 0;
@@ -1257,8 +1235,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     }
     node = n_node; par = n_par; tok = n_tok; len = n_len; h = n_h; hp = n_hp;
     pb = n_pb; pnb = n_pnb; tot = n_tot;
-    if constexpr (LM) { lm_state = n_lm_state; lm_sum = n_lm_sum; }
-    if constexpr (F2) { fs_state = n_fs_state; fs_sum = n_fs_sum; }
+    CTC_BEAM_EACH_MODEL(NM, k, { m_state[k] = n_m_state[k]; m_sum[k] = n_m_sum[k]; });
     brank = keep ? e_rank : NEGINF;
     nb = __popcll(__ballot(keep));
     // ---- the next row
@@ -1271,17 +1248,18 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     __threadfence_block();   // the node stores of this frame are visible to the lanes that chase them
     __syncthreads();
   }
-  // ---- (FUSED) the final term and the order of the output: lane l holds the hypothesis of output place l in o_*
+  // ---- (FINAL: a model has a `state_final` table; without one what follows is the identity) the final terms and the order of the
+  // output: lane l holds the hypothesis of output place l in o_*
   int o_node = node, o_len = len;
   float o_score = brank;
-  if constexpr (FUSED > 0) {
+  if constexpr (FINAL) {
     const bool live = lane < nb;
     float sc = NEGINF;
     if (live) {
       sc = brank;
-      if (lm.fin) sc += ctc_beam_alpha_lm(lm.alpha, lm.fin[min(max(lm_state, 0), lm.n_states - 1)]);
-      if constexpr (F2)
-        if (lm.fin2) sc += ctc_beam_alpha_lm(lm.m2.alpha, lm.fin2[min(max(fs_state, 0), lm.m2.n_states - 1)]);
+      CTC_BEAM_EACH_MODEL(NM, k, {
+        if (lm.v[k].fin) sc += ctc_beam_alpha_lm(lm.v[k].alpha, lm.v[k].fin[min(max(m_state[k], 0), lm.v[k].n_states - 1)]);
+      });
     }
     int pos = 0;
     for (int j = 0; j < nb; ++j) pos += ctc_beam_beats(ctc_rlf(sc, j), j, sc, lane) ? 1 : 0;
@@ -1295,8 +1273,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       st.out.node[s] = node; st.out.par[s] = par; st.out.tok[s] = tok; st.out.len[s] = len;
       st.out.h[s] = h; st.out.hp[s] = hp;
       st.out.pb[s] = pb; st.out.pnb[s] = pnb; st.out.tot[s] = tot; st.out.brank[s] = brank;
-      if constexpr (LM) { st.out.lm_state[s] = lm_state; st.out.lm_sum[s] = lm_sum; }
-      if constexpr (F2) { st.out_fs_state[s] = fs_state; st.out_fs_sum[s] = fs_sum; }
+      CTC_BEAM_EACH_MODEL(NM, k, { st.template model<k>().out_state[s] = m_state[k]; st.template model<k>().out_sum[s] = m_sum[k]; });
     }
     if (lane == 0) { st.out.nb[b] = nb; st.out.frames_done[b] = f0 + T; }
     if (!tokens) return;
@@ -1358,64 +1335,110 @@ static bool ctc_beam_shape_ok(const void* logp, const void* lens, void* node_ws,
   if (Ttree < 1 || (long long)Ttree * beam > 0x3fffffffll) return false;   // node ids are 32-bit
   return (size_t)C * 8 <= 64 * 1024;
 }
-static bool ctc_beam_args_ok(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len, void* score,
-                             void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta) {
-  if (!tokens || !tok_frame || !hyp_len || !score || !n_hyp) return false;
-  return ctc_beam_shape_ok(logp, lens, node_ws, B, Tmax, C, blank, beam, threshold, beta, Tmax);
+// State 0's arc index is the label, so a search with a model needs the blank as the last class: n_arcs >= C - 1 labels.
+static bool ctc_beam_model_ok(const mi355x_ctc_beam_fusion& m, int C) {
+  if (!m.state_arc_begin || !m.arc_tok || !m.arc_logp || !m.arc_next || !m.state_bo || !m.state_bo_next) return false;
+  return m.n_states >= 2 && m.n_arcs >= C - 1 && m.alpha >= 0.f && m.ub == m.ub;   // (a NaN fails its compare)
 }
-static bool ctc_beam_state_ok(const mi355x_ctc_beam_stream_state* s, bool lm) {
-  return s->node && s->par && s->tok && s->len && s->h && s->hp && s->pb && s->pnb && s->tot && s->brank && s->nb && s->frames_done &&
-         (!lm || (s->lm_state && s->lm_sum));
+// a state of the resumable search with n_models models is whole: the first model's arrays are beams.lm_*, the second's fs_*
+static bool ctc_beam_state_ok(const mi355x_ctc_beam_fused_state* s, int n_models) {
+  const mi355x_ctc_beam_stream_state& b = s->beams;
+  return b.node && b.par && b.tok && b.len && b.h && b.hp && b.pb && b.pnb && b.tot && b.brank && b.nb && b.frames_done &&
+         (n_models < 1 || (b.lm_state && b.lm_sum)) && (n_models < 2 || (s->fs_state && s->fs_sum));
 }
-// the resumable entries: the five outputs all or none, a whole state_out, a state_in that is null, fresh (node null) or whole
-static bool ctc_beam_stream_args_ok(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
-                                    void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta,
-                                    int Tcap, const mi355x_ctc_beam_stream_state* state_in,
-                                    const mi355x_ctc_beam_stream_state* state_out, bool lm) {
+template <int NM, bool FINAL>
+static ctc_beam_models<NM, FINAL> ctc_beam_models_arg(const mi355x_ctc_beam_fusion* m) {
+  ctc_beam_models<NM, FINAL> r = {};
+  CTC_BEAM_EACH_MODEL(NM, k, {
+    r.v[k] = {(const int*)m[k].state_arc_begin, (const int*)m[k].arc_tok, (const float*)m[k].arc_logp, (const int*)m[k].arc_next,
+              (const float*)m[k].state_bo, (const int*)m[k].state_bo_next, m[k].n_states, m[k].n_arcs, m[k].alpha, m[k].ub,
+              (const float*)m[k].state_final};
+  });
+  return r;
+}
+template <int NM, bool STREAM>
+static ctc_beam_stream<NM, STREAM> ctc_beam_stream_arg(const mi355x_ctc_beam_fused_state* in, const mi355x_ctc_beam_fused_state* out,
+                                                       int Tcap) {
+  ctc_beam_stream<NM, STREAM> r = {};
+  if constexpr (STREAM) {
+    const mi355x_ctc_beam_fused_state fresh = {};   // (in null, or in->beams.node null: fresh streams, nothing of `in` is read)
+    const mi355x_ctc_beam_fused_state& i = in && in->beams.node ? *in : fresh;
+    r.in = i.beams; r.out = out->beams; r.Tcap = Tcap;
+    if constexpr (NM > 1) r.more.v[0] = {i.fs_state, i.fs_sum, out->fs_state, out->fs_sum};
+  }
+  return r;
+}
+
+// Every entry of the search: 0 to 2 fusion models, and the resumable search where state_out is given (the one-shot search has no
+// states, and its tree holds Tmax frames).  The resumable search takes its five outputs all or none, a whole state_out, and a
+// state_in that is null, fresh (node null) or whole.
+static int ctc_beam_launch(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len, void* score,
+                           void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta,
+                           const mi355x_ctc_beam_fusion* models, int n_models, int Tcap, const mi355x_ctc_beam_fused_state* state_in,
+                           const mi355x_ctc_beam_fused_state* state_out, void* stream) {
+  mi_clear_errors();
+  const bool streamed = state_out != nullptr;
   const int outs = !!tokens + !!tok_frame + !!hyp_len + !!score + !!n_hyp;
-  if (outs != 0 && outs != 5) return false;
-  if (!state_out || !ctc_beam_state_ok(state_out, lm)) return false;
-  if (state_in && state_in->node && (!ctc_beam_state_ok(state_in, lm) || state_in->node == state_out->node)) return false;
-  return ctc_beam_shape_ok(logp, lens, node_ws, B, Tmax, C, blank, beam, threshold, beta, Tcap);
-}
-static ctc_beam_stream ctc_beam_stream_arg(const mi355x_ctc_beam_stream_state* state_in, const mi355x_ctc_beam_stream_state* state_out,
-                                           int Tcap) {
-  ctc_beam_stream st = {};
-  if (state_in && state_in->node) st.in = *state_in;
-  st.out = *state_out;
-  st.Tcap = Tcap;
-  return st;
-}
-#define CTC_BEAM_LAUNCH(LM, STREAM, ...)                                                                                                \
-  MI_LAUNCH((ctc_beam_kernel<LM, STREAM, 0>), dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp,                  \
+  if (outs != 5 && !(streamed && outs == 0)) return MI_ERR_ARG;
+  if (n_models < 0 || n_models > 2 || (n_models && (!models || blank != C - 1))) return MI_ERR_ARG;
+  for (int k = 0; k < n_models; ++k)
+    if (!ctc_beam_model_ok(models[k], C)) return MI_ERR_ARG;
+  if (streamed) {
+    if (!ctc_beam_state_ok(state_out, n_models)) return MI_ERR_ARG;
+    if (state_in && state_in->beams.node && (!ctc_beam_state_ok(state_in, n_models) || state_in->beams.node == state_out->beams.node))
+      return MI_ERR_ARG;
+  }
+  if (!ctc_beam_shape_ok(logp, lens, node_ws, B, Tmax, C, blank, beam, threshold, beta, streamed ? Tcap : Tmax)) return MI_ERR_ARG;
+  // the output's final terms and re-ordering are compiled in where a model can bring a `state_final` table: with two models always,
+  // with one where it has the table (an n-gram model has none, and the code's mere presence costs its search 2.4 to 4.3 %)
+  const bool final = n_models == 2 || (n_models == 1 && models[0].state_final);
+#define CTC_BEAM_LAUNCH(NM, STREAM, FINAL)                                                                                             \
+  MI_LAUNCH((ctc_beam_kernel<NM, STREAM, FINAL>), dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp,           \
             (const long long*)lens, (int2*)node_ws, (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, \
-            blank, beam, threshold, beta, __VA_ARGS__)
+            blank, beam, threshold, beta, (ctc_beam_models_arg<NM, FINAL>(models)), (ctc_beam_stream_arg<NM, STREAM>(state_in, state_out, Tcap)))
+  switch (4 * n_models + 2 * streamed + final) {
+    case 0: CTC_BEAM_LAUNCH(0, false, false); break;
+    case 2: CTC_BEAM_LAUNCH(0, true, false); break;
+    case 4: CTC_BEAM_LAUNCH(1, false, false); break;
+    case 5: CTC_BEAM_LAUNCH(1, false, true); break;
+    case 6: CTC_BEAM_LAUNCH(1, true, false); break;
+    case 7: CTC_BEAM_LAUNCH(1, true, true); break;
+    case 9: CTC_BEAM_LAUNCH(2, false, true); break;
+    default: CTC_BEAM_LAUNCH(2, true, true); break;
+  }
+#undef CTC_BEAM_LAUNCH
+  return mi_check_launch();
+}
+// what an entry refuses before the launcher sees it: the launcher takes no model for the plain search, a null state_out for the
+// one-shot one
+static int ctc_beam_refused() {
+  mi_clear_errors();
+  return MI_ERR_ARG;
+}
+// a state of the entries without a second model, as the launcher takes it (null: fresh streams)
+static mi355x_ctc_beam_fused_state ctc_beam_state_arg(const mi355x_ctc_beam_stream_state* s) {
+  mi355x_ctc_beam_fused_state f = {};
+  if (s) f.beams = *s;
+  return f;
+}
 
 extern "C" int mi355x_ctc_beam_decode(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
                                       void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold,
                                       float beta, void* stream) {
-  mi_clear_errors();
-  if (!ctc_beam_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta))
-    return MI_ERR_ARG;
-  CTC_BEAM_LAUNCH(false, false, ctc_beam_no_lm{}, ctc_beam_no_stream{});
-  return mi_check_launch();
+  return ctc_beam_launch(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
+                         nullptr, 0, 0, nullptr, nullptr, stream);
 }
 
-// The same search with the n-gram model fused.  State 0's arc index is the label, so the blank has to be the last class.
+// The same search with the n-gram model fused: one fusion model without a `state_final` table.
 extern "C" int mi355x_ctc_beam_decode_lm(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len,
                                          void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold,
                                          float beta, const void* state_arc_begin, const void* arc_tok, const void* arc_logp,
                                          const void* arc_next, const void* state_bo, const void* state_bo_next, int n_states,
                                          int n_arcs, float alpha, float lm_ub, void* stream) {
-  mi_clear_errors();
-  if (!ctc_beam_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta))
-    return MI_ERR_ARG;
-  if (!state_arc_begin || !arc_tok || !arc_logp || !arc_next || !state_bo || !state_bo_next) return MI_ERR_ARG;
-  if (n_states < 2 || n_arcs < C - 1 || blank != C - 1 || !(alpha >= 0.f) || lm_ub != lm_ub) return MI_ERR_ARG;
-  const ctc_beam_lm lm = {(const int*)state_arc_begin, (const int*)arc_tok, (const float*)arc_logp, (const int*)arc_next,
-                          (const float*)state_bo, (const int*)state_bo_next, n_states, n_arcs, alpha, lm_ub};
-  CTC_BEAM_LAUNCH(true, false, lm, ctc_beam_no_stream{});
-  return mi_check_launch();
+  const mi355x_ctc_beam_fusion m = {state_arc_begin, arc_tok, arc_logp, arc_next, state_bo, state_bo_next, nullptr, n_states, n_arcs,
+                                    alpha, lm_ub};
+  return ctc_beam_launch(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta, &m, 1,
+                         0, nullptr, nullptr, stream);
 }
 
 // The two searches, resumable: one chunk from state_in to state_out over the tree the caller keeps (include/mi355x_asr.h).
@@ -1423,12 +1446,10 @@ extern "C" int mi355x_ctc_beam_decode_stream(const void* logp, const void* lens,
                                              void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam,
                                              float threshold, float beta, int Tcap, const mi355x_ctc_beam_stream_state* state_in,
                                              const mi355x_ctc_beam_stream_state* state_out, void* stream) {
-  mi_clear_errors();
-  if (!ctc_beam_stream_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
-                               Tcap, state_in, state_out, false))
-    return MI_ERR_ARG;
-  CTC_BEAM_LAUNCH(false, true, ctc_beam_no_lm{}, ctc_beam_stream_arg(state_in, state_out, Tcap));
-  return mi_check_launch();
+  if (!state_out) return ctc_beam_refused();
+  const mi355x_ctc_beam_fused_state in = ctc_beam_state_arg(state_in), out = ctc_beam_state_arg(state_out);
+  return ctc_beam_launch(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
+                         nullptr, 0, Tcap, &in, &out, stream);
 }
 
 extern "C" int mi355x_ctc_beam_decode_lm_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
@@ -1438,60 +1459,23 @@ extern "C" int mi355x_ctc_beam_decode_lm_stream(const void* logp, const void* le
                                                 const void* state_bo_next, int n_states, int n_arcs, float alpha, float lm_ub,
                                                 int Tcap, const mi355x_ctc_beam_stream_state* state_in,
                                                 const mi355x_ctc_beam_stream_state* state_out, void* stream) {
-  mi_clear_errors();
-  if (!ctc_beam_stream_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
-                               Tcap, state_in, state_out, true))
-    return MI_ERR_ARG;
-  if (!state_arc_begin || !arc_tok || !arc_logp || !arc_next || !state_bo || !state_bo_next) return MI_ERR_ARG;
-  if (n_states < 2 || n_arcs < C - 1 || blank != C - 1 || !(alpha >= 0.f) || lm_ub != lm_ub) return MI_ERR_ARG;
-  const ctc_beam_lm lm = {(const int*)state_arc_begin, (const int*)arc_tok, (const float*)arc_logp, (const int*)arc_next,
-                          (const float*)state_bo, (const int*)state_bo_next, n_states, n_arcs, alpha, lm_ub};
-  CTC_BEAM_LAUNCH(true, true, lm, ctc_beam_stream_arg(state_in, state_out, Tcap));
-  return mi_check_launch();
+  if (!state_out) return ctc_beam_refused();
+  const mi355x_ctc_beam_fusion m = {state_arc_begin, arc_tok, arc_logp, arc_next, state_bo, state_bo_next, nullptr, n_states, n_arcs,
+                                    alpha, lm_ub};
+  const mi355x_ctc_beam_fused_state in = ctc_beam_state_arg(state_in), out = ctc_beam_state_arg(state_out);
+  return ctc_beam_launch(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta, &m, 1,
+                         Tcap, &in, &out, stream);
 }
-#undef CTC_BEAM_LAUNCH
 
 // The search with one or two fusion models, each an n-gram model or a boosting tree (a table set with `state_final`), and the final
-// term at output (include/mi355x_asr.h).  New instantiations: the four kernels above are not touched by them.
-static bool ctc_beam_fusion_ok(const mi355x_ctc_beam_fusion* m, int n_models, int C, int blank) {
-  if (!m || n_models < 1 || n_models > 2 || blank != C - 1) return false;
-  for (int i = 0; i < n_models; ++i) {
-    if (!m[i].state_arc_begin || !m[i].arc_tok || !m[i].arc_logp || !m[i].arc_next || !m[i].state_bo || !m[i].state_bo_next) return false;
-    if (m[i].n_states < 2 || m[i].n_arcs < C - 1 || !(m[i].alpha >= 0.f) || m[i].ub != m[i].ub) return false;
-  }
-  return true;
-}
-static ctc_beam_lm ctc_beam_fusion_tables(const mi355x_ctc_beam_fusion& m) {
-  return {(const int*)m.state_arc_begin, (const int*)m.arc_tok, (const float*)m.arc_logp, (const int*)m.arc_next,
-          (const float*)m.state_bo, (const int*)m.state_bo_next, m.n_states, m.n_arcs, m.alpha, m.ub};
-}
-static ctc_beam_fused ctc_beam_fused_arg(const mi355x_ctc_beam_fusion* m, int n_models) {
-  ctc_beam_fused f = {};
-  static_cast<ctc_beam_lm&>(f) = ctc_beam_fusion_tables(m[0]);
-  f.fin = (const float*)m[0].state_final;
-  if (n_models == 2) {
-    f.m2 = ctc_beam_fusion_tables(m[1]);
-    f.fin2 = (const float*)m[1].state_final;
-  }
-  return f;
-}
-#define CTC_BEAM_FUSED_LAUNCH(STREAM, FUSED, ...)                                                                                        \
-  MI_LAUNCH((ctc_beam_kernel<true, STREAM, FUSED>), dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp,         \
-            (const long long*)lens, (int2*)node_ws, (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, \
-            blank, beam, threshold, beta, __VA_ARGS__)
-
+// term at output (include/mi355x_asr.h).
 extern "C" int mi355x_ctc_beam_decode_fused(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
                                             void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam,
                                             float threshold, float beta, const mi355x_ctc_beam_fusion* models, int n_models,
                                             void* stream) {
-  mi_clear_errors();
-  if (!ctc_beam_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta))
-    return MI_ERR_ARG;
-  if (!ctc_beam_fusion_ok(models, n_models, C, blank)) return MI_ERR_ARG;
-  const ctc_beam_fused f = ctc_beam_fused_arg(models, n_models);
-  if (n_models == 2) { CTC_BEAM_FUSED_LAUNCH(false, 2, f, ctc_beam_no_stream{}); }
-  else { CTC_BEAM_FUSED_LAUNCH(false, 1, f, ctc_beam_no_stream{}); }
-  return mi_check_launch();
+  if (!models || n_models < 1) return ctc_beam_refused();
+  return ctc_beam_launch(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
+                         models, n_models, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int mi355x_ctc_beam_decode_fused_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
@@ -1499,25 +1483,7 @@ extern "C" int mi355x_ctc_beam_decode_fused_stream(const void* logp, const void*
                                                    int beam, float threshold, float beta, const mi355x_ctc_beam_fusion* models,
                                                    int n_models, int Tcap, const mi355x_ctc_beam_fused_state* state_in,
                                                    const mi355x_ctc_beam_fused_state* state_out, void* stream) {
-  mi_clear_errors();
-  if (!ctc_beam_stream_args_ok(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
-                               Tcap, state_in ? &state_in->beams : nullptr, state_out ? &state_out->beams : nullptr, true))
-    return MI_ERR_ARG;
-  if (!ctc_beam_fusion_ok(models, n_models, C, blank)) return MI_ERR_ARG;
-  const bool resumed = state_in && state_in->beams.node;
-  if (n_models == 2 && (!state_out->fs_state || !state_out->fs_sum || (resumed && (!state_in->fs_state || !state_in->fs_sum))))
-    return MI_ERR_ARG;
-  const ctc_beam_fused f = ctc_beam_fused_arg(models, n_models);
-  const ctc_beam_stream base = ctc_beam_stream_arg(state_in ? &state_in->beams : nullptr, &state_out->beams, Tcap);
-  if (n_models == 2) {
-    ctc_beam_stream2 st = {};
-    static_cast<ctc_beam_stream&>(st) = base;
-    if (resumed) { st.in_fs_state = state_in->fs_state; st.in_fs_sum = state_in->fs_sum; }
-    st.out_fs_state = state_out->fs_state; st.out_fs_sum = state_out->fs_sum;
-    CTC_BEAM_FUSED_LAUNCH(true, 2, f, st);
-  } else {
-    CTC_BEAM_FUSED_LAUNCH(true, 1, f, base);
-  }
-  return mi_check_launch();
+  if (!models || n_models < 1 || !state_out) return ctc_beam_refused();
+  return ctc_beam_launch(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
+                         models, n_models, Tcap, state_in, state_out, stream);
 }
-#undef CTC_BEAM_FUSED_LAUNCH

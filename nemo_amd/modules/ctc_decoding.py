@@ -227,7 +227,7 @@ class CTCBeamStreamState:
 
 
 class BeamBatchedCTCDecoder(_CTCText):
-    """CTC prefix beam search on the device (`mi355x_ctc_beam_decode`, with `ngram_lm` `mi355x_ctc_beam_decode_lm`): the `beam_batch`
+    """CTC prefix beam search on the device (`mi355x_ctc_beam_decode`, with `ngram_lm` `mi355x_ctc_beam_decode_fused`): the `beam_batch`
     strategy.  `beam_size` hypotheses per utterance (1..64), `beam_threshold`: a class is looked at in a frame only if its
     log-probability is within that much of the frame's best (inf: every class), `beam_beta`: bonus per token, `ngram_lm`: an `NGramLM`
     over the labels, fused with weight `ngram_lm_alpha` >= 0; the score of a hypothesis is the log-probability of its LABEL SEQUENCE
@@ -236,7 +236,7 @@ class BeamBatchedCTCDecoder(_CTCText):
     `boosting_tree`: a `BoostingTree` of key phrases, fused with weight `boosting_tree_alpha` >= 0 (alone or beside the LM:
     `mi355x_ctc_beam_decode_fused`): the search adds boosting_tree_alpha * boost(sequence) to its rank, and the score returned holds
     the boost of the completed phrases only -- a phrase begun and not finished is not paid for -- with the n-best ordered by it.
-    Without a tree every method calls what it called before."""
+    Every method makes one call with the models there are (`_fusion_models`): none, the LM, the tree, or both."""
 
     confidence_cfg = None   # (the greedy decoder's attribute: confidences are not defined for the beam search)
 
@@ -277,18 +277,13 @@ class BeamBatchedCTCDecoder(_CTCText):
         _check_log_probs(log_probs)
         lp = log_probs.to(torch.float32).contiguous()
         lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
-        if self.boosting_tree is not None:
-            return ops.ctc_beam_decode_fused(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta,
-                                             self._fusion_models())
-        if self.ngram_lm is not None:
-            return ops.ctc_beam_decode_lm(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, self.ngram_lm,
-                                          self.ngram_lm_alpha)
-        return ops.ctc_beam_decode(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta)
+        what, models = ops._ctc_beam_checked(self._fusion_models(), self.boosting_tree is not None, lp, "")
+        return ops._ctc_beam_search(what, lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, models)
 
     def _fusion_models(self):
-        """the (model, alpha) list of the fused entries: the LM, where there is one, then the tree"""
+        """the (model, alpha) list of the search: the LM, where there is one, then the tree, where there is one"""
         lm = [(self.ngram_lm, self.ngram_lm_alpha)] if self.ngram_lm is not None else []
-        return lm + [(self.boosting_tree, self.boosting_tree_alpha)]
+        return lm + ([(self.boosting_tree, self.boosting_tree_alpha)] if self.boosting_tree is not None else [])
 
     def nbest(self, log_probs, lengths=None):
         """per utterance the list of (token ids, score), best first: the D2H copy is the folded hypotheses, W * T integers an utterance"""
@@ -299,7 +294,7 @@ class BeamBatchedCTCDecoder(_CTCText):
     @torch.no_grad()
     def decode_stream(self, log_probs: torch.Tensor, lengths: Optional[torch.Tensor] = None,
                       state: Optional[CTCBeamStreamState] = None, emit: bool = True):
-        """one chunk of the resumable search (`mi355x_ctc_beam_decode_stream` / `_lm_stream`): log_probs [B, T, V+1] and lengths
+        """one chunk of the resumable search (`mi355x_ctc_beam_decode_stream` / `_fused_stream`): log_probs [B, T, V+1] and lengths
         [B] of THIS chunk (0: the stream has ended, its state passes through), `state` what the previous chunk returned (None: fresh
         streams) -> (the n-best of all frames so far, or None with emit=False; the next state).  The n-best is `decode_ids`'
         tuple with tokens / tok_frame i32 [B, W, capacity] in the state's buffers: NOT padded, valid up to hyp_len, overwritten by
@@ -308,11 +303,9 @@ class BeamBatchedCTCDecoder(_CTCText):
         _check_log_probs(log_probs)
         lp = log_probs.to(torch.float32).contiguous()
         lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
-        if self.boosting_tree is not None:
-            return ops.ctc_beam_decode_fused_stream(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, state,
-                                                    self._fusion_models(), emit=emit)
-        return ops.ctc_beam_decode_stream(lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, state,
-                                          lm=self.ngram_lm, alpha=self.ngram_lm_alpha, emit=emit)
+        what, models = ops._ctc_beam_checked(self._fusion_models(), self.boosting_tree is not None, lp, "_stream")
+        return ops._ctc_beam_search_stream(what, lp, lens, self.blank_id, self.beam_size, self.beam_threshold, self.beam_beta, state,
+                                           models, emit)
 
     def nbest_stream(self, log_probs, lengths=None, state=None, best_only: bool = False):
         """`decode_stream` to host lists: per stream the (token ids, score, global frame of each token) of its hypotheses so far,

@@ -487,48 +487,6 @@ def ctc_align(logp, targets, in_len, tgt_len, blank):
     return path, tok_start[:, :U], tok_end[:, :U], score
 
 
-def ctc_beam_decode(logp, lens, blank, beam_size, beam_threshold=20.0, beam_beta=0.0):
-    """CTC prefix beam search (mi355x_ctc_beam_decode; `ctc_beam_decode_lm` fuses an n-gram model): logp f32 [B,T,C] contiguous, lens
-    i64 [B] (None: T for every utterance) -> (tokens i32 [B,W,T]: hypotheses best first, -1 padded; tok_frame i32 [B,W,T]: the frame
-    each token was created in; hyp_len i32 [B,W]; score f32 [B,W]: tot + beam_beta * len, -inf for absent hypotheses; n_hyp i32 [B]).
-    The node workspace (2 * T * W integers per utterance) is allocated here and dropped."""
-    return _ctc_beam(logp, lens, blank, beam_size, beam_threshold, beam_beta, None, 0.0)
-
-
-def ctc_beam_decode_lm(logp, lens, blank, beam_size, beam_threshold, beam_beta, lm, alpha):
-    """`ctc_beam_decode` with shallow fusion of an n-gram model (mi355x_ctc_beam_decode_lm): the hypotheses are ranked by
-    (tot + beam_beta * len) + alpha * lm(prefix), which is also the score returned.  `lm` is an `NGramLM` (modules/ngram_lm.py), not
-    loose tensors: only tables its loader built and checked reach the kernel.  alpha = 0 gives the bits of `ctc_beam_decode`."""
-    from .modules.ngram_lm import NGramLM
-    if not isinstance(lm, NGramLM):
-        raise TypeError(f"ctc_beam_decode_lm: `lm` must be an NGramLM, got {type(lm).__name__}")
-    if lm.vocab_size != logp.shape[2] - 1:
-        raise ValueError(f"ctc_beam_decode_lm: the LM has {lm.vocab_size} labels, the log-probabilities {logp.shape[2]} classes "
-                         f"(labels + the blank)")
-    return _ctc_beam(logp, lens, blank, beam_size, beam_threshold, beam_beta, lm, alpha)
-
-
-def _ctc_beam(logp, lens, blank, beam_size, beam_threshold, beam_beta, lm, alpha):
-    B, T, C_ = logp.shape
-    W = int(beam_size)
-    if lens is None:
-        lens = torch.full((B,), T, dtype=torch.int64, device=logp.device)
-    i32, f32 = (dict(dtype=d, device=logp.device) for d in (torch.int32, torch.float32))
-    ws = torch.empty(B * max(2, int(lib.mi355x_ctc_beam_workspace_elems(T, W))), **i32)   # (a fresh allocation: 8-byte aligned)
-    Wa = max(W, 0)   # (a width the entry refuses still reaches it, for its ValueError)
-    tokens, tok_frame = torch.empty(B, Wa, T, **i32), torch.empty(B, Wa, T, **i32)
-    hyp_len, score, n_hyp = torch.empty(B, Wa, **i32), torch.empty(B, Wa, **f32), torch.empty(B, **i32)
-    args = (_ptr(logp), _ptr(lens), _ptr(ws), _ptr(tokens), _ptr(tok_frame), _ptr(hyp_len), _ptr(score), _ptr(n_hyp), B, T, C_,
-            int(blank), W, float(beam_threshold), float(beam_beta))
-    if lm is None:
-        check(lib.mi355x_ctc_beam_decode(*args, _stream()), "ctc_beam_decode")
-    else:
-        tables = lm.to(logp.device)[:6]   # (cached on the LM: they outlive the launch; a BoostingTree's seventh table is not this entry's)
-        check(lib.mi355x_ctc_beam_decode_lm(*args, *(_ptr(t) for t in tables), lm.num_states, lm.num_arcs, float(alpha),
-                                            float(lm.lm_ub), _stream()), "ctc_beam_decode_lm")
-    return tokens, tok_frame, hyp_len, score, n_hyp
-
-
 class _CTCBeamStateC(C.Structure):   # mi355x_ctc_beam_stream_state
     _fields_ = [(n, C.c_void_p) for n in ("node", "par", "tok", "len", "h", "hp", "pb", "pnb", "tot", "brank", "lm_state", "lm_sum",
                                            "nb", "frames_done")]
@@ -537,48 +495,6 @@ class _CTCBeamStateC(C.Structure):   # mi355x_ctc_beam_stream_state
     def of(cls, state):
         a = state.arrays()
         return cls(**{n: (_ptr(a[n]) if n in a else None) for n, _ in cls._fields_})
-
-
-def ctc_beam_decode_stream(logp, lens, blank, beam_size, beam_threshold, beam_beta, state, lm=None, alpha=0.0, emit=True):
-    """one chunk of the resumable CTC prefix beam search (mi355x_ctc_beam_decode_stream; with `lm`, an NGramLM, and `alpha`
-    mi355x_ctc_beam_decode_lm_stream): logp f32 [B,T,C] contiguous and lens i64 [B] (None: T) of THIS chunk, `state` the
-    `modules.CTCBeamStreamState` the previous chunk returned (None: fresh streams) -> ((tokens, tok_frame, hyp_len, score, n_hyp) of
-    all frames so far, or None with emit=False; the next state).  tokens / tok_frame are the state's buffers [B, W, capacity]: valid
-    up to hyp_len, not padded, rewritten by the next emitting step; tok_frame counts from the stream's first frame.  The input
-    state's beams are not written (its tree is appended to, and grown here so that the kernel's capacity clamp never acts).  Any cut
-    into chunks gives the bits of `ctc_beam_decode` / `ctc_beam_decode_lm` over the whole sequence."""
-    from .modules.ctc_decoding import CTCBeamStreamState
-    B, T, C_ = logp.shape
-    W = int(beam_size)
-    if lm is not None:
-        from .modules.ngram_lm import NGramLM
-        if not isinstance(lm, NGramLM):
-            raise TypeError(f"ctc_beam_decode_stream: `lm` must be an NGramLM, got {type(lm).__name__}")
-        if lm.vocab_size != C_ - 1:
-            raise ValueError(f"ctc_beam_decode_stream: the LM has {lm.vocab_size} labels, the log-probabilities {C_} classes "
-                             f"(labels + the blank)")
-    if state is None:
-        state = CTCBeamStreamState.fresh(B, W, logp.device, lm=lm is not None)
-    if state.B != B or state.W != W or state.lm != (lm is not None):
-        raise ValueError(f"ctc_beam_decode_stream: the state is of {state.B} streams, {state.W} beams, "
-                         f"{'an' if state.lm else 'no'} LM; the call of {B}, {W}, {'an' if lm is not None else 'no'} LM")
-    if lens is None:
-        lens = torch.full((B,), T, dtype=torch.int64, device=logp.device)
-    state.reserve(T)
-    nxt = state.next(T)
-    i32, f32 = (dict(dtype=d, device=logp.device) for d in (torch.int32, torch.float32))
-    outs = (state.tokens, state.tok_frame, torch.empty(B, W, **i32), torch.empty(B, W, **f32), torch.empty(B, **i32)) if emit else None
-    s_in, s_out = _CTCBeamStateC.of(state), _CTCBeamStateC.of(nxt)
-    args = (_ptr(logp), _ptr(lens), _ptr(state.tree), *((_ptr(t) for t in outs) if emit else (None,) * 5), B, T, C_, int(blank), W,
-            float(beam_threshold), float(beam_beta))
-    tail = (state.capacity, C.byref(s_in), C.byref(s_out), _stream())
-    if lm is None:
-        check(lib.mi355x_ctc_beam_decode_stream(*args, *tail), "ctc_beam_decode_stream")
-    else:
-        tables = lm.to(logp.device)[:6]
-        check(lib.mi355x_ctc_beam_decode_lm_stream(*args, *(_ptr(t) for t in tables), lm.num_states, lm.num_arcs, float(alpha),
-                                                   float(lm.lm_ub), *tail), "ctc_beam_decode_lm_stream")
-    return outs, nxt
 
 
 class _CTCBeamFusionC(C.Structure):   # mi355x_ctc_beam_fusion
@@ -597,6 +513,16 @@ class _CTCBeamFusedStateC(C.Structure):   # mi355x_ctc_beam_fused_state
                    fs_sum=_ptr(a["fs_sum"]) if "fs_sum" in a else None)
 
 
+def _ctc_beam_lm_check(what, lm, logp):
+    """`lm` of the entries that take one n-gram model: an NGramLM over the labels of `logp`"""
+    from .modules.ngram_lm import NGramLM
+    if not isinstance(lm, NGramLM):
+        raise TypeError(f"{what}: `lm` must be an NGramLM, got {type(lm).__name__}")
+    if lm.vocab_size != logp.shape[2] - 1:
+        raise ValueError(f"{what}: the LM has {lm.vocab_size} labels, the log-probabilities {logp.shape[2]} classes "
+                         f"(labels + the blank)")
+
+
 def _ctc_beam_fusion_check(what, models, logp):
     """`models` = [(NGramLM | BoostingTree, alpha), ...], one or two, over the labels of `logp`"""
     from .modules.ngram_lm import NGramLM
@@ -613,6 +539,16 @@ def _ctc_beam_fusion_check(what, models, logp):
     return models
 
 
+class _CTCBeamSixTables:
+    """a model as the entries that take one n-gram model pass it on: its six tables, without a BoostingTree's `state_final`"""
+
+    def __init__(self, model):
+        self.model, self.num_states, self.num_arcs, self.lm_ub = model, model.num_states, model.num_arcs, model.lm_ub
+
+    def to(self, device):
+        return self.model.to(device)[:6]
+
+
 def _ctc_beam_fusion_array(models, logp):
     """the `mi355x_ctc_beam_fusion` array of checked `models` and the tensors it points into"""
     arr, keep = (_CTCBeamFusionC * len(models))(), []
@@ -624,54 +560,114 @@ def _ctc_beam_fusion_array(models, logp):
     return arr, keep
 
 
-def ctc_beam_decode_fused(logp, lens, blank, beam_size, beam_threshold, beam_beta, models):
-    """`ctc_beam_decode` with one or two fusion models (mi355x_ctc_beam_decode_fused): `models` is a list of (NGramLM | BoostingTree,
-    alpha), not loose tensors.  The search ranks by ((tot + beam_beta * len) + alpha1 * m1(prefix)) + alpha2 * m2(prefix); the score
-    returned adds each BoostingTree's final term (the boost of a phrase begun and not finished is taken back) and the n-best is
-    ordered by it.  Same outputs as `ctc_beam_decode`."""
-    arr, keep = _ctc_beam_fusion_array(_ctc_beam_fusion_check("ctc_beam_decode_fused", models, logp), logp)
+def _ctc_beam_checked(models, fused, logp, suffix):
+    """the models of a call as its public entry checks and passes them on, and that entry's name for messages (`suffix`: '' or
+    '_stream').  `fused`: the entries that take (NGramLM | BoostingTree, alpha) pairs; else the ones that take no model or one n-gram
+    model, of which six tables reach the kernel"""
+    if fused:
+        what = "ctc_beam_decode_fused" + suffix
+        return what, _ctc_beam_fusion_check(what, models, logp)
+    what = "ctc_beam_decode" + (suffix if suffix or not models else "_lm")
+    for lm, _ in models:
+        _ctc_beam_lm_check(what, lm, logp)
+    return what, [(_CTCBeamSixTables(lm), alpha) for lm, alpha in models]
+
+
+def _ctc_beam_search(what, logp, lens, blank, beam_size, beam_threshold, beam_beta, models):
+    """the one-shot search behind every public entry: `models` = [(NGramLM | BoostingTree, alpha), ...], checked by the caller, none
+    (mi355x_ctc_beam_decode) to two (mi355x_ctc_beam_decode_fused); `what` names the caller where the library refuses the arguments"""
     B, T, C_ = logp.shape
     W = int(beam_size)
     if lens is None:
         lens = torch.full((B,), T, dtype=torch.int64, device=logp.device)
     i32, f32 = (dict(dtype=d, device=logp.device) for d in (torch.int32, torch.float32))
     ws = torch.empty(B * max(2, int(lib.mi355x_ctc_beam_workspace_elems(T, W))), **i32)   # (a fresh allocation: 8-byte aligned)
-    Wa = max(W, 0)
+    Wa = max(W, 0)   # (a width the entry refuses still reaches it, for its ValueError)
     tokens, tok_frame = torch.empty(B, Wa, T, **i32), torch.empty(B, Wa, T, **i32)
     hyp_len, score, n_hyp = torch.empty(B, Wa, **i32), torch.empty(B, Wa, **f32), torch.empty(B, **i32)
-    check(lib.mi355x_ctc_beam_decode_fused(_ptr(logp), _ptr(lens), _ptr(ws), _ptr(tokens), _ptr(tok_frame), _ptr(hyp_len), _ptr(score),
-                                           _ptr(n_hyp), B, T, C_, int(blank), W, float(beam_threshold), float(beam_beta),
-                                           C.cast(arr, C.c_void_p), len(arr), _stream()), "ctc_beam_decode_fused")
+    arr, keep = _ctc_beam_fusion_array(models, logp)
+    entry, fusion = ((lib.mi355x_ctc_beam_decode_fused, (C.cast(arr, C.c_void_p), len(arr))) if models else
+                     (lib.mi355x_ctc_beam_decode, ()))
+    check(entry(_ptr(logp), _ptr(lens), _ptr(ws), _ptr(tokens), _ptr(tok_frame), _ptr(hyp_len), _ptr(score), _ptr(n_hyp), B, T, C_,
+                int(blank), W, float(beam_threshold), float(beam_beta), *fusion, _stream()), what)
     return tokens, tok_frame, hyp_len, score, n_hyp
 
 
-def ctc_beam_decode_fused_stream(logp, lens, blank, beam_size, beam_threshold, beam_beta, state, models, emit=True):
-    """one chunk of the resumable `ctc_beam_decode_fused` (mi355x_ctc_beam_decode_fused_stream): `ctc_beam_decode_stream`'s
-    arguments and results with `models` as in `ctc_beam_decode_fused`.  The state holds the search's order and ranks; the emitted
-    n-best carries the final terms.  Any cut into chunks gives the bits of `ctc_beam_decode_fused` over the whole sequence."""
+def _ctc_beam_search_stream(what, logp, lens, blank, beam_size, beam_threshold, beam_beta, state, models, emit):
+    """one chunk of the resumable search behind every public entry (mi355x_ctc_beam_decode_stream without a model, else
+    mi355x_ctc_beam_decode_fused_stream): `_ctc_beam_search`'s arguments, `state` a CTCBeamStreamState of this batch, width and model
+    count (None: fresh streams) -> (the n-best so far in the state's buffers, or None with emit=False; the next state)"""
     from .modules.ctc_decoding import CTCBeamStreamState
-    models = _ctc_beam_fusion_check("ctc_beam_decode_fused_stream", models, logp)
     B, T, C_ = logp.shape
-    W, two = int(beam_size), len(models) == 2
+    W = int(beam_size)
     if state is None:
-        state = CTCBeamStreamState.fresh(B, W, logp.device, lm=True, second=two)
-    if state.B != B or state.W != W or not state.lm or (state.fs is not None) != two:
-        raise ValueError(f"ctc_beam_decode_fused_stream: the state is of {state.B} streams, {state.W} beams, "
+        state = CTCBeamStreamState.fresh(B, W, logp.device, lm=len(models) >= 1, second=len(models) == 2)
+    if state.B != B or state.W != W or int(state.lm) + (state.fs is not None) != len(models):
+        raise ValueError(f"{what}: the state is of {state.B} streams, {state.W} beams, "
                          f"{int(state.lm) + (state.fs is not None)} fusion models; the call of {B}, {W}, {len(models)}")
-    arr, keep = _ctc_beam_fusion_array(models, logp)
     if lens is None:
         lens = torch.full((B,), T, dtype=torch.int64, device=logp.device)
     state.reserve(T)
     nxt = state.next(T)
     i32, f32 = (dict(dtype=d, device=logp.device) for d in (torch.int32, torch.float32))
     outs = (state.tokens, state.tok_frame, torch.empty(B, W, **i32), torch.empty(B, W, **f32), torch.empty(B, **i32)) if emit else None
-    s_in, s_out = _CTCBeamFusedStateC.of(state), _CTCBeamFusedStateC.of(nxt)
-    check(lib.mi355x_ctc_beam_decode_fused_stream(_ptr(logp), _ptr(lens), _ptr(state.tree),
-                                                  *((_ptr(t) for t in outs) if emit else (None,) * 5), B, T, C_, int(blank), W,
-                                                  float(beam_threshold), float(beam_beta), C.cast(arr, C.c_void_p), len(arr),
-                                                  state.capacity, C.byref(s_in), C.byref(s_out), _stream()),
-          "ctc_beam_decode_fused_stream")
+    arr, keep = _ctc_beam_fusion_array(models, logp)
+    entry, fusion = ((lib.mi355x_ctc_beam_decode_fused_stream, (C.cast(arr, C.c_void_p), len(arr))) if models else
+                     (lib.mi355x_ctc_beam_decode_stream, ()))
+    s_in, s_out = _CTCBeamFusedStateC.of(state), _CTCBeamFusedStateC.of(nxt)   # (the model-less entry's state is its first member)
+    check(entry(_ptr(logp), _ptr(lens), _ptr(state.tree), *((_ptr(t) for t in outs) if emit else (None,) * 5), B, T, C_, int(blank), W,
+                float(beam_threshold), float(beam_beta), *fusion, state.capacity, C.byref(s_in), C.byref(s_out), _stream()), what)
     return outs, nxt
+
+
+def ctc_beam_decode(logp, lens, blank, beam_size, beam_threshold=20.0, beam_beta=0.0):
+    """CTC prefix beam search (mi355x_ctc_beam_decode; `ctc_beam_decode_lm` fuses an n-gram model): logp f32 [B,T,C] contiguous, lens
+    i64 [B] (None: T for every utterance) -> (tokens i32 [B,W,T]: hypotheses best first, -1 padded; tok_frame i32 [B,W,T]: the frame
+    each token was created in; hyp_len i32 [B,W]; score f32 [B,W]: tot + beam_beta * len, -inf for absent hypotheses; n_hyp i32 [B]).
+    The node workspace (2 * T * W integers per utterance) is allocated here and dropped."""
+    return _ctc_beam_search("ctc_beam_decode", logp, lens, blank, beam_size, beam_threshold, beam_beta, [])
+
+
+def ctc_beam_decode_lm(logp, lens, blank, beam_size, beam_threshold, beam_beta, lm, alpha):
+    """`ctc_beam_decode` with shallow fusion of an n-gram model (the search of mi355x_ctc_beam_decode_lm): the hypotheses are ranked by
+    (tot + beam_beta * len) + alpha * lm(prefix), which is also the score returned.  `lm` is an `NGramLM` (modules/ngram_lm.py), not
+    loose tensors: only tables its loader built and checked reach the kernel (a BoostingTree's seventh table is not this entry's).
+    alpha = 0 gives the bits of `ctc_beam_decode`."""
+    what, models = _ctc_beam_checked([(lm, alpha)], False, logp, "")
+    return _ctc_beam_search(what, logp, lens, blank, beam_size, beam_threshold, beam_beta, models)
+
+
+def ctc_beam_decode_stream(logp, lens, blank, beam_size, beam_threshold, beam_beta, state, lm=None, alpha=0.0, emit=True):
+    """one chunk of the resumable CTC prefix beam search (mi355x_ctc_beam_decode_stream; with `lm`, an NGramLM, and `alpha` the search
+    of mi355x_ctc_beam_decode_lm_stream): logp f32 [B,T,C] contiguous and lens i64 [B] (None: T) of THIS chunk, `state` the
+    `modules.CTCBeamStreamState` the previous chunk returned (None: fresh streams) -> ((tokens, tok_frame, hyp_len, score, n_hyp) of
+    all frames so far, or None with emit=False; the next state).  tokens / tok_frame are the state's buffers [B, W, capacity]: valid
+    up to hyp_len, not padded, rewritten by the next emitting step; tok_frame counts from the stream's first frame.  The input
+    state's beams are not written (its tree is appended to, and grown here so that the kernel's capacity clamp never acts).  Any cut
+    into chunks gives the bits of `ctc_beam_decode` / `ctc_beam_decode_lm` over the whole sequence."""
+    what, models = _ctc_beam_checked([] if lm is None else [(lm, alpha)], False, logp, "_stream")
+    if state is not None and (state.B != logp.shape[0] or state.W != int(beam_size) or state.lm != (lm is not None)):
+        raise ValueError(f"ctc_beam_decode_stream: the state is of {state.B} streams, {state.W} beams, "
+                         f"{'an' if state.lm else 'no'} LM; the call of {logp.shape[0]}, {int(beam_size)}, "
+                         f"{'an' if lm is not None else 'no'} LM")
+    return _ctc_beam_search_stream(what, logp, lens, blank, beam_size, beam_threshold, beam_beta, state, models, emit)
+
+
+def ctc_beam_decode_fused(logp, lens, blank, beam_size, beam_threshold, beam_beta, models):
+    """`ctc_beam_decode` with one or two fusion models (mi355x_ctc_beam_decode_fused): `models` is a list of (NGramLM | BoostingTree,
+    alpha), not loose tensors.  The search ranks by ((tot + beam_beta * len) + alpha1 * m1(prefix)) + alpha2 * m2(prefix); the score
+    returned adds each BoostingTree's final term (the boost of a phrase begun and not finished is taken back) and the n-best is
+    ordered by it.  Same outputs as `ctc_beam_decode`."""
+    what, models = _ctc_beam_checked(models, True, logp, "")
+    return _ctc_beam_search(what, logp, lens, blank, beam_size, beam_threshold, beam_beta, models)
+
+
+def ctc_beam_decode_fused_stream(logp, lens, blank, beam_size, beam_threshold, beam_beta, state, models, emit=True):
+    """one chunk of the resumable `ctc_beam_decode_fused` (mi355x_ctc_beam_decode_fused_stream): `ctc_beam_decode_stream`'s
+    arguments and results with `models` as in `ctc_beam_decode_fused`.  The state holds the search's order and ranks; the emitted
+    n-best carries the final terms.  Any cut into chunks gives the bits of `ctc_beam_decode_fused` over the whole sequence."""
+    what, models = _ctc_beam_checked(models, True, logp, "_stream")
+    return _ctc_beam_search_stream(what, logp, lens, blank, beam_size, beam_threshold, beam_beta, state, models, emit)
 
 
 def specaug_rects(u_tw, u_ts, u_fw, u_fs, length, rects, B, nt, nf, F, T, time_width, freq_width):

@@ -362,6 +362,33 @@ def test_any_chunking_gives_the_one_shot_bits_and_one_final_state(shape):
     _same(_host(out), want, (shape, "sparse"))
 
 
+def test_one_ngram_model_streams_the_same_through_both_entries():
+    """the streamed form of the one-model equivalence: `ctc_beam_decode_stream` with an LM and `ctc_beam_decode_fused_stream` with
+    that LM alone, over the same chunks (T = 70 in tens of 7, the n-best asked for on the last one), give the same n-best and write
+    the same state, byte for byte"""
+    from nemo_amd import ops
+    T, C, W, alpha = 70, 70, 8, 0.5
+    lp, lm = _stream_logp(T, C), _device_lm(C - 1, 3)
+    ends = {}
+    for via in ("lm", "fused"):
+        state = None
+        for t0 in range(0, T, 7):
+            args = (lp[:, t0:t0 + 7].contiguous(), None, C - 1, W, INF, 0.0, state)
+            last = t0 + 7 == T
+            if via == "lm":
+                out, state = ops.ctc_beam_decode_stream(*args, lm=lm, alpha=alpha, emit=last)
+            else:
+                out, state = ops.ctc_beam_decode_fused_stream(*args, [(lm, alpha)], emit=last)
+            assert (out is None) == (not last)
+        ends[via] = (_host(out), _state_bits(state))
+    (a, sa), (b, sb) = ends["lm"], ends["fused"]
+    assert a[4].tolist() == [W] * len(STREAM_SEEDS)   # (full sets: every slot of the state is a beam)
+    _same(b, a, "fused against lm")
+    assert set(sa) == set(sb) and {"lm_state", "lm_sum"} <= set(sa)
+    for name in sa:
+        assert sa[name].tobytes() == sb[name].tobytes(), name
+
+
 # ------------------------------------------------------------------------------------------------ 5. bad arguments
 def test_bad_arguments_raise():
     from nemo_amd import ops

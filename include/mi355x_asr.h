@@ -365,6 +365,36 @@ int mi355x_relpos_flash_bwd_dkv(const void* qu, const void* qv, const void* qkv,
                                 int B, int H, int T, int dk, int Tp, float scale, unsigned drop_key, unsigned drop_threshold,
                                 float drop_scale, const void* row_offsets, void* stream);
 
+/* SAVED PROBABILITIES (head width 64, padded rows): the forward already holds every probability in registers; exported once, the
+ * two backward kernels need not rebuild S = Qu K^T, the positional band, the rel_shift and the exponentials.
+ * mi355x_relpos_flash_fwd_p = mi355x_relpos_flash_fwd (ctx, ctx_lo, lse bit-identical) that also writes
+ *   probs bf16 [(b*H+h)][query block it][key tile kt][lane][16]: the 32 x 32 un-normalised probabilities
+ *     p~ = exp2((s - mref) * scale * log2 e) of queries 32*it .. +31 against keys 32*kt .. +31 before dropout, in the register order
+ *     of the kernel: lane = (query & 31) + 32 * ((key >> 2) & 1), register r = (key & 3) + 4 * ((key & 31) >> 3); masked keys 0;
+ *     both block indices run to NT4 = 4 * ceil(T / 128); key tiles kt >= ceil(len[b] / 32) are not written;
+ *   mref f32 [(b*H+h)][kt][32 * NT4]: the raw-score reference point of query i in that step (the running maximum moves lazily
+ *     and per query, so it travels with the tile).  P[i,j] = p~ * exp(mref * scale - lse).
+ * probs_elems / mref_elems = capacities in elements, >= mi355x_relpos_probs_elems / mi355x_relpos_mref_elems (B, H, T).
+ * The _p backward entry points produce what mi355x_relpos_flash_bwd_dq / _dkv produce, from probs and mref (one extra bf16 rounding
+ * of each probability).  All three return MI_ERR_ARG for dk != 64, a row_offsets table or a short buffer. */
+long long mi355x_relpos_probs_elems(int B, int H, int T);
+long long mi355x_relpos_mref_elems(int B, int H, int T);
+int mi355x_relpos_flash_fwd_p(const void* qkv, long long ldq, const void* pos, long long ldp, const void* bias_u, const void* bias_v,
+                              const void* len, void* ctx, void* ctx_lo, long long ldo, void* lse, void* probs, long long probs_elems,
+                              void* mref, long long mref_elems, int B, int H, int T, int dk, int Tp, float scale, unsigned drop_key,
+                              unsigned drop_threshold, float drop_scale, const void* row_offsets, void* stream);
+int mi355x_relpos_flash_bwd_dq_p(const void* probs, long long probs_elems, const void* mref, long long mref_elems, const void* qkv,
+                                 long long ldq, const void* pos, long long ldp, const void* len, const void* dO, const void* lse,
+                                 const void* delta, void* dqu, void* dqv, void* ds_out, void* dq_out, long long ld_dq,
+                                 void* bias_grads, void* cs_scratch, long long cs_scratch_elems, int B, int H, int T, int dk,
+                                 long long ds_elems, float scale, unsigned drop_key, unsigned drop_threshold, float drop_scale,
+                                 const void* row_offsets, void* stream);
+int mi355x_relpos_flash_bwd_dkv_p(const void* probs, long long probs_elems, const void* mref, long long mref_elems, const void* qu,
+                                  const void* qkv, long long ldq, const void* len, const void* dO, const void* lse,
+                                  const void* delta, void* dqkv, long long ldd, int B, int H, int T, int dk, float scale,
+                                  unsigned drop_key, unsigned drop_threshold, float drop_scale, const void* row_offsets,
+                                  void* stream);
+
 /* dpos f32 [2T-1, ldd] += gradient w.r.t. pos = linear_pos(pos_emb) (multi_head_attention.py:296-300 backward), summed over
  * the batch: dpos[c, h, :] += sum_{b,i} dS[b,h,i,c-(T-1)+i] * qv[b,i,h,:], from the blocks written by
  * mi355x_relpos_flash_bwd_dq (ds_out).  partial (optional): f32 scratch of >= mi355x_relpos_dpos_partial_elems(B,H,T)

@@ -149,6 +149,14 @@ SIGNATURES = {
     "mi355x_relpos_flash_bwd_dkv": [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, u32, u32, f32, vp, vp],
     "mi355x_relpos_flash_bwd_dpos": [vp, vp, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, i64, vp, vp],
     "mi355x_relpos_ds_elems": [i32, i32, i32],
+    "mi355x_relpos_probs_elems": [i32, i32, i32],
+    "mi355x_relpos_mref_elems": [i32, i32, i32],
+    "mi355x_relpos_flash_fwd_p": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, f32, u32,
+                                  u32, f32, vp, vp],
+    "mi355x_relpos_flash_bwd_dq_p": [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i32, i32,
+                                     i32, i32, i64, f32, u32, u32, f32, vp, vp],
+    "mi355x_relpos_flash_bwd_dkv_p": [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u32, u32, f32,
+                                      vp, vp],
     "mi355x_relpos_dpos_partial_elems": [i32, i32, i32],
     "mi355x_dwconv_fwd": [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp],
     "mi355x_dwconv_fwd_ctx": [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp],
@@ -236,6 +244,8 @@ def _load():
         fn.restype = i32
     lib.mi355x_asr_version.restype = C.c_char_p
     lib.mi355x_relpos_ds_elems.restype = i64
+    lib.mi355x_relpos_probs_elems.restype = i64
+    lib.mi355x_relpos_mref_elems.restype = i64
     lib.mi355x_relpos_dpos_partial_elems.restype = i64
     lib.mi355x_ctc_beam_workspace_elems.restype = i64
     lib.mi355x_asr_version.argtypes = []

@@ -180,7 +180,12 @@ __device__ __forceinline__ void load_q(const bf16_t* qrow, const float* bias, bf
   }
 }
 
-template <int ADK>
+// EXPORT (saved-probabilities backward, see the *_p entry points): every key step also writes the lane's 16 un-normalised
+// probabilities p~ = exp2(s c2 - m_run c2) (before dropout, bf16, <= 2^8 by the lazy re-scaling bound) in the lane's own register
+// order -- 32 contiguous bytes per lane, 2 KiB per wave step -- to p_out[(b,h)][query block of 32][key tile][lane][16], and the
+// reference point m_run of that step to mref_out[(b,h)][key tile][query] (the re-scale is lazy and per query, so the reference
+// travels with the tile).  Both grids are padded to whole 128-query workgroups: NT4 = 4 * gridDim.x blocks each way.
+template <int ADK, bool EXPORT = false>
 __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_fwd_kernel(const bf16_t* __restrict__ qkv, long long ldq,
                                                                   const bf16_t* __restrict__ pos, long long ldp,
                                                                   const float* __restrict__ bias_u, const float* __restrict__ bias_v,
@@ -188,7 +193,9 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_fwd_kerne
                                                                   bf16_t* __restrict__ ctx_lo, long long ldo,
                                                                   float* __restrict__ lse, int B, int H, int T,
                                                                   int Tp, float scale, DropCfg drop,
-                                                                  const long long* __restrict__ cu) {
+                                                                  const long long* __restrict__ cu,
+                                                                  bf16_t* __restrict__ p_out = nullptr,
+                                                                  float* __restrict__ mref_out = nullptr) {
   drop_resolve(drop);
   constexpr int NKK = ADK / 16, NDT = ADK / 32, NCH = ADK / 8;
   __shared__ __attribute__((aligned(16))) bf16_t s_k2[2][ABK * ADK];   // 2 x 4 KiB (double-buffered)
@@ -326,6 +333,24 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_fwd_kerne
     for (int r = 0; r < 16; ++r) { s[r] = __builtin_amdgcn_exp2f(fmaf(s[r], c2, -mc)); rs += s[r]; }
     rs += __shfl_xor(rs, 32, 64);
     l_run += rs;
+    if constexpr (EXPORT) {
+      const long long nt4 = 4LL * gridDim.x, bh = (long long)b * H + h;
+      // wave-uniform 64-bit bases + 32-bit lane offsets.  The offsets are re-derived from the thread index in every step behind an
+      // empty asm: hoisted out of the loop they would be four more registers live across it (170 instead of 166 VGPRs; 168 is
+      // what a third workgroup per CU needs)
+      uint32_t po = threadIdx.x, mo = threadIdx.x;
+      asm volatile("" : "+v"(po));
+      po = (po & 63u) * 32u;
+      char* pblk = reinterpret_cast<char*>(p_out + ((bh * nt4 + (blockIdx.x * 4 + wave)) * nt4 + kt) * 1024) + po;
+      const u32x4 w0 = {pack_bf2(s[0], s[1]), pack_bf2(s[2], s[3]), pack_bf2(s[4], s[5]), pack_bf2(s[6], s[7])};
+      const u32x4 w1 = {pack_bf2(s[8], s[9]), pack_bf2(s[10], s[11]), pack_bf2(s[12], s[13]), pack_bf2(s[14], s[15])};
+      *reinterpret_cast<u32x4*>(pblk) = w0;
+      *reinterpret_cast<u32x4*>(pblk + 16) = w1;
+      asm volatile("" : "+v"(mo));
+      mo = (mo & 31u) * 4u;
+      if (lh == 0)
+        *reinterpret_cast<float*>(reinterpret_cast<char*>(mref_out + (bh * nt4 + kt) * (nt4 * 32) + i0_blk + wave * 32) + mo) = m_run;
+    }
     // ---- dropout on the probabilities (the 1/(1-p) scale is folded into the final normalisation)
     if (drop.threshold != 0u) {
       const uint32_t bj0 = (uint32_t)(j0 >> 2);
@@ -481,8 +506,22 @@ __device__ __forceinline__ void load_rows(const bf16_t* rowp, bf16x8 (&out)[NKK]
   }
 }
 
+// per-lane state of the "given probabilities" backward kernels (empty for the recomputing instantiations)
+template <bool GP> struct GivenP {};
+template <> struct GivenP<true> {
+  const bf16_t* pin;    // this lane's / wave's exported probabilities
+  const float* mref;    // reference points of this lane's query
+  long long mstride;    // mref elements per key tile / probs elements per query block
+  u32x4 np0, np1;       // dQ: the next step's 16 probabilities
+  float nmr;            // the next step's reference point
+};
+
 // dQu / dQv for one 128-query tile (lane = query, same structure as the forward)
-template <int ADK>
+// GP ("given probabilities"): P is not recomputed -- the lane loads the 32 bytes of p~ the forward exported for its (query, key
+// tile) one step ahead and scales them by exp2(mref c2 - lse log2 e).  S, the band product G, the G -> LDS -> shifted-read skew
+// and the per-element exp2 go; Qu / Qv are not read at all (the band is still staged: dQv is a product with it).  The launcher
+// passes probs / mref in the places of qu_g / qv_g.
+template <int ADK, bool GP = false>
 __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dq_kernel(
     const bf16_t* __restrict__ qu_g, const bf16_t* __restrict__ qv_g, const bf16_t* __restrict__ qkv, long long ldq,
     const bf16_t* __restrict__ pos, long long ldp, const long long* __restrict__ len, const bf16_t* __restrict__ dO,
@@ -492,6 +531,10 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dq_ke
     const long long* __restrict__ cu) {
   drop_resolve(drop);
   constexpr int NKK = ADK / 16, NDT = ADK / 32, NCH = ADK / 8;
+  // GP: Qu / Qv are not read, and their two parameters carry the exported probabilities (bf16) and reference points (f32) instead --
+  // the parameter list, and with it every instruction of the recomputing instantiation, stays what it was
+  const bf16_t* const p_in = qu_g;
+  const float* const mref_in = reinterpret_cast<const float*>(qv_g);
   __shared__ __attribute__((aligned(16))) bf16_t s_k2[2][ABK * ADK];       // double-buffered (read until the end of a step)
   __shared__ __attribute__((aligned(16))) bf16_t s_v[ABK * ADK];           // read in the first MFMA block only
   __shared__ __attribute__((aligned(16))) bf16_t s_p[APRING * 32 * ADK];   // positional band: ring of 32-row blocks (see forward)
@@ -525,14 +568,19 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dq_ke
   const bf16_t* pbase = pos + h * ADK;
 
   bf16x8 qu[NKK], qv[NKK], dof[NKK];
-  load_rows<NKK>(qu_g + rowi * d + h * ADK, qu, i < Tr, lh);
-  load_rows<NKK>(qv_g + rowi * d + h * ADK, qv, i < Tr, lh);
+  if constexpr (!GP) {
+    load_rows<NKK>(qu_g + rowi * d + h * ADK, qu, i < Tr, lh);
+    load_rows<NKK>(qv_g + rowi * d + h * ADK, qv, i < Tr, lh);
+  }
   load_rows<NKK>(dO + rowi * d + h * ADK, dof, i < Tr, lh);
   float lse_i = qvalid ? lse[((long long)b * H + h) * T + i] : 1e30f;  // padded query: exp(. - 1e30) = 0
   float dlt_i = qvalid ? delta[((long long)b * H + h) * T + i] : 0.f;
   // (the compiler must wait for these register loads HERE, not at their first use inside the loop: see the dK/dV kernel)
 #pragma unroll
-  for (int kk = 0; kk < NKK; ++kk) { asm volatile("" : "+v"(qu[kk])); asm volatile("" : "+v"(qv[kk])); asm volatile("" : "+v"(dof[kk])); }
+  for (int kk = 0; kk < NKK; ++kk) {
+    if constexpr (!GP) { asm volatile("" : "+v"(qu[kk])); asm volatile("" : "+v"(qv[kk])); }
+    asm volatile("" : "+v"(dof[kk]));
+  }
   asm volatile("" : "+v"(lse_i), "+v"(dlt_i));
 
   f32x16 dqu[NDT], dqv[NDT];
@@ -562,10 +610,38 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dq_ke
     stage_rows<ADK>(vbase, ldq, 0, Trc, s_v, ABK * NCH);
     stage_rows<ADK>(pbase, ldp, c0, P - 1, s_p, ABAND * NCH);
   }
+  // GP: this lane's exported probabilities (two 16-byte halves) and reference point of the NEXT step, loaded into registers
+  // one step ahead (the step's own `vmcnt(0)` covers them; the empty asm below keeps the compiler's wait at that place)
+  // (all of it lives in a struct that is empty without GP: the recomputing instantiation compiles to what it was)
+  GivenP<GP> gp;
+  if constexpr (GP) {
+    const long long nt4 = 4LL * gridDim.x, bh = (long long)b * H + h;
+    gp.pin = p_in + ((bh * nt4 + (blockIdx.x * 4 + wave)) * nt4) * 1024 + lane * 16;
+    gp.mref = mref_in + (bh * nt4) * (nt4 * 32) + i;
+    gp.mstride = nt4 * 32;
+    gp.np0 = gp.np1 = (u32x4){0u, 0u, 0u, 0u};
+    gp.nmr = 0.f;
+    if (nkt > 0) {
+      gp.np0 = *reinterpret_cast<const u32x4*>(gp.pin);
+      gp.np1 = *reinterpret_cast<const u32x4*>(gp.pin + 8);
+      gp.nmr = *gp.mref;
+    }
+  }
   for (int kt = 0; kt < nkt; ++kt) {
     const int j0 = kt * ABK;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // tile kt has landed; every wave is done with step kt-1
+    u32x4 cp0, cp1;
+    float cmr;
+    if constexpr (GP) {
+      cp0 = gp.np0; cp1 = gp.np1; cmr = gp.nmr;
+      asm volatile("" : "+v"(cp0), "+v"(cp1), "+v"(cmr));
+      if (kt + 1 < nkt) {
+        gp.np0 = *reinterpret_cast<const u32x4*>(gp.pin + (long long)(kt + 1) * 1024);
+        gp.np1 = *reinterpret_cast<const u32x4*>(gp.pin + (long long)(kt + 1) * 1024 + 8);
+        gp.nmr = gp.mref[(long long)(kt + 1) * gp.mstride];
+      }
+    }
     if (kt + 1 < nkt) {
       stage_rows<ADK>(kbase, ldq, j0 + ABK, Trc, s_k2[(kt + 1) & 1], ABK * NCH);
       stage_rows<ADK>(pbase, ldp, c0 + 32 * (kt + 5), P - 1, s_p + ((kt + 5) % APRING) * (32 * ADK), 32 * NCH);
@@ -574,30 +650,50 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dq_ke
     const int slot0 = (kt + 3 - wave) % APRING, slot1 = (kt + 4 - wave) % APRING;  // this wave's two band blocks
 
     f32x16 acc_s, acc_g[2], acc_dp;
+    if constexpr (GP) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { acc_s[r] = 0.f; acc_g[0][r] = 0.f; acc_g[1][r] = 0.f; acc_dp[r] = 0.f; }
+      for (int r = 0; r < 16; ++r) acc_dp[r] = 0.f;
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { acc_s[r] = 0.f; acc_g[0][r] = 0.f; acc_g[1][r] = 0.f; acc_dp[r] = 0.f; }
+    }
 #pragma unroll
     for (int kk = 0; kk < NKK; ++kk) {
-      const bf16x8 kf = *reinterpret_cast<const bf16x8*>(s_k + a_off<ADK>(q, kk * 2 + lh));
-      acc_s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qu[kk], acc_s, 0, 0, 0);
+      if constexpr (!GP) {
+        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(s_k + a_off<ADK>(q, kk * 2 + lh));
+        acc_s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qu[kk], acc_s, 0, 0, 0);
+      }
       const bf16x8 vf = *reinterpret_cast<const bf16x8*>(s_v + a_off<ADK>(q, kk * 2 + lh));
       acc_dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[kk], acc_dp, 0, 0, 0);  // dP^T[key][query] = V . dO^T
+      if constexpr (!GP) {
 #pragma unroll
-      for (int gt = 0; gt < 2; ++gt) {
-        const bf16x8 pf = *reinterpret_cast<const bf16x8*>(s_p + a_off<ADK>((gt ? slot1 : slot0) * 32 + q, kk * 2 + lh));
-        acc_g[gt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, qv[kk], acc_g[gt], 0, 0, 0);
+        for (int gt = 0; gt < 2; ++gt) {
+          const bf16x8 pf = *reinterpret_cast<const bf16x8*>(s_p + a_off<ADK>((gt ? slot1 : slot0) * 32 + q, kk * 2 + lh));
+          acc_g[gt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, qv[kk], acc_g[gt], 0, 0, 0);
+        }
       }
     }
     if (kt + 1 < nkt) {  // (block-uniform)
       __syncthreads();   // every wave has its V fragments
       stage_rows<ADK>(vbase, ldq, j0 + ABK, Trc, s_v, ABK * NCH);
     }
+    float ds[16];
+    if constexpr (GP) {
+      // P[i, j] = p~ * exp2(mref c2 - lse log2 e): masked keys were exported as 0, padded queries carry lse_i = +1e30 -> factor 0
+      const float fac = __builtin_amdgcn_exp2f(fmaf(cmr, c2, -lse2));
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        ds[2 * w] = __uint_as_float(cp0[w] << 16) * fac;
+        ds[2 * w + 1] = __uint_as_float(cp0[w] & 0xffff0000u) * fac;
+        ds[8 + 2 * w] = __uint_as_float(cp1[w] << 16) * fac;
+        ds[8 + 2 * w + 1] = __uint_as_float(cp1[w] & 0xffff0000u) * fac;
+      }
+    } else {
 #pragma unroll
     for (int gt = 0; gt < 2; ++gt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) sg[q * SG_LD + 32 * gt + (r & 3) + 8 * (r >> 2) + 4 * lh] = acc_g[gt][r];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    float ds[16];
     if (j0 + ABK <= L) {  // every key valid; padded queries carry lse_i = +1e30 -> P = 0 without a mask
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -613,6 +709,7 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dq_ke
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
     // dS = P * (dropmask * dP - delta) * scale
     if (drop.threshold != 0u) {
       const uint32_t bj0 = (uint32_t)(j0 >> 2);
@@ -779,22 +876,34 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dq_ke
 
 // dK / dV for one 128-key tile (lane = key): S = Qu K^T, G = Qv P^T with the rel_shift resolved by a lane rotation
 // (bd[query rho][key q] = G[rho][31 + q - rho]: a compile-time shift per register), dV^T += dO^T Pd, dK^T += Qu^T dS.
-template <int ADK>
+// GP ("given probabilities"): each wave stages the 2 KiB block the forward exported for (query tile of the step, its key tile) by
+// LDS-DMA one step ahead and every lane picks its 16 (query row, own key) values out of it with 16-bit reads; S, G, the lane
+// rotation and the per-element exp go, and with them the K registers, the Qv tile and the whole positional band (33 KiB of LDS).
+// The launcher passes probs / mref in the places of pos / qv_g.
+template <int ADK, bool GP = false>
 __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dkv_kernel(
     const bf16_t* __restrict__ qu_g, const bf16_t* __restrict__ qv_g, const bf16_t* __restrict__ qkv, long long ldq,
     const bf16_t* __restrict__ pos, long long ldp, const long long* __restrict__ len, const bf16_t* __restrict__ dO,
     const float* __restrict__ lse, const float* __restrict__ delta, bf16_t* __restrict__ dqkv, long long ldd, int B, int H,
     int T, int Tp, int d, float scale, DropCfg drop, const long long* __restrict__ cu) {
   drop_resolve(drop);
+  // GP: neither the positional table nor Qv is read, and their two parameters carry the exported probabilities (bf16) and reference
+  // points (f32) instead -- the parameter list of the recomputing instantiation stays what it was
+  const bf16_t* const p_in = pos;
+  const float* const mref_in = reinterpret_cast<const float*>(qv_g);
   // staging (double-buffered query tiles + the positional band as a ring of 32-row blocks, see the forward kernel) and the
   // output transposition tile share one buffer: the latter is only used after the loop
   constexpr int NKK = ADK / 16, NDT = ADK / 32, NCH = ADK / 8;
-  constexpr int STAGE_BYTES = 2 * 3 * 32 * ADK * 2 + APRING * 32 * ADK * 2 + 2 * 2 * 32 * 4;  // 24 + 24 + 0.5 KiB (ADK = 64)
+  constexpr int NQ = GP ? 2 : 3;                                          // staged query-side tiles: qu | (qv) | dO
+  constexpr int Q_BYTES = 2 * NQ * 32 * ADK * 2;
+  constexpr int P_BYTES = GP ? 2 * 4 * 2048 : APRING * 32 * ADK * 2;     // GP: [2][wave] exported blocks instead of the band
+  constexpr int STAGE_BYTES = Q_BYTES + P_BYTES + 2 * 2 * 32 * 4 + (GP ? 4 * 32 * 4 : 0);  // 24 + 24 + 0.5 KiB (ADK = 64); GP: 33 KiB
   constexpr int OUT_BYTES = 4 * 32 * SG_LD * 4;
   __shared__ __attribute__((aligned(16))) char s_raw[STAGE_BYTES > OUT_BYTES ? STAGE_BYTES : OUT_BYTES];
-  bf16_t* const s_q3 = reinterpret_cast<bf16_t*>(s_raw);                                 // [2][qu | qv | dO][32 * ADK]
-  bf16_t* const s_p = reinterpret_cast<bf16_t*>(s_raw + 2 * 3 * 32 * ADK * 2);          // [APRING * 32][ADK]
-  float* const s_ld = reinterpret_cast<float*>(s_raw + 2 * 3 * 32 * ADK * 2 + APRING * 32 * ADK * 2);  // [2][lse | delta][32]
+  bf16_t* const s_q3 = reinterpret_cast<bf16_t*>(s_raw);                  // [2][qu | qv | dO][32 * ADK]
+  bf16_t* const s_p = reinterpret_cast<bf16_t*>(s_raw + Q_BYTES);         // [APRING * 32][ADK]; GP: [2][4 waves][1024]
+  float* const s_ld = reinterpret_cast<float*>(s_raw + Q_BYTES + P_BYTES);  // [2][lse | delta][32]
+  float* const s_fac = s_ld + 2 * 64;                                     // GP: [4 waves][32] per-query factors of the step
 
   const int b = blockIdx.z, h = blockIdx.y;
   const int j0_blk = blockIdx.x * ABQ;
@@ -817,13 +926,16 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dkv_k
   const float dscale = drop.threshold != 0u ? drop.scale : 1.f;  // folded, with `scale`, into the accumulators at the end
 
   bf16x8 kf[NKK], vf[NKK];
-  load_rows<NKK>(kbase + rowj * ldq, kf, j < Tr, lh);
+  if constexpr (!GP) load_rows<NKK>(kbase + rowj * ldq, kf, j < Tr, lh);
   load_rows<NKK>(kbase + (ldq / 3) + rowj * ldq, vf, j < Tr, lh);
 
   // (the compiler must wait for these register loads HERE: inside the loop its `s_waitcnt vmcnt(0)` at their first use would
   //  also wait, every step, for the prefetch it knows nothing about)
 #pragma unroll
-  for (int kk = 0; kk < NKK; ++kk) { asm volatile("" : "+v"(kf[kk])); asm volatile("" : "+v"(vf[kk])); }
+  for (int kk = 0; kk < NKK; ++kk) {
+    if constexpr (!GP) asm volatile("" : "+v"(kf[kk]));
+    asm volatile("" : "+v"(vf[kk]));
+  }
   f32x16 dk_acc[NDT], dv_acc[NDT];
 #pragma unroll
   for (int t = 0; t < NDT; ++t)
@@ -838,11 +950,28 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dkv_k
   // needs ONE new block at the low end.  Query tiles (Qu, Qv, dO) and their lse / delta (wave 0: lanes 0-31 | 32-63, 4 bytes
   // each) are double-buffered.
   const int cb0 = T - 1 + j0_blk - 31;
+  // GP: the wave's exported block of query tile qt, [forward lane = query + 32 * ((key >> 2) & 1)][16 registers], lands as 128
+  // sixteen-byte chunks; the chunks of the upper forward lanes are placed 4 chunks (16 banks) off so that the 16-bit reads below
+  // (one query row, 32 keys per half-wave) do not meet in a bank.  mref of the step's 32 queries comes by a register load.
+  GivenP<GP> gp;
+  if constexpr (GP) {
+    const long long nt4 = 4LL * gridDim.x, bh = (long long)b * H + h, ktw = blockIdx.x * 4 + wave;
+    gp.pin = p_in + (bh * nt4 * nt4 + ktw) * 1024;                        // + qt * nt4 * 1024 per step
+    gp.mref = mref_in + (bh * nt4 + ktw) * (nt4 * 32) + (lane & 31);      // + qt * 32 per step
+    gp.mstride = nt4 * 1024;
+    gp.nmr = 0.f;
+  }
   auto stage_q = [&](int i0, int buf) {
-    bf16_t* dst = s_q3 + buf * (3 * 32 * ADK);
+    bf16_t* dst = s_q3 + buf * (NQ * 32 * ADK);
     stage_rows<ADK>(qub, d, i0, Trc, dst, 32 * NCH);
-    stage_rows<ADK>(qvb, d, i0, Trc, dst + 32 * ADK, 32 * NCH);
-    stage_rows<ADK>(dob, d, i0, Trc, dst + 2 * 32 * ADK, 32 * NCH);
+    if constexpr (!GP) stage_rows<ADK>(qvb, d, i0, Trc, dst + 32 * ADK, 32 * NCH);
+    stage_rows<ADK>(dob, d, i0, Trc, dst + (NQ - 1) * 32 * ADK, 32 * NCH);
+    if constexpr (GP) {
+      const bf16_t* blk = gp.pin + (long long)(i0 >> 5) * gp.mstride;
+      bf16_t* pd_ = s_p + (buf * 4 + wave) * 1024;
+      dma16(blk + lane * 8, pd_);
+      dma16(blk + (64 + (lane ^ 4)) * 8, pd_ + 512);
+    }
     if (wave == 0) {
       int ii = i0 + (lane & 31);
       ii = ii < T ? ii : T - 1;  // (rows >= len are never used: p = 0 there)
@@ -851,39 +980,74 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dkv_k
   };
   if (nqt > 0) {
     stage_q(0, 0);
-    stage_rows<ADK>(pbase, ldp, cb0, P - 1, s_p, ABAND * NCH);
+    if constexpr (GP) gp.nmr = *gp.mref;
+    else stage_rows<ADK>(pbase, ldp, cb0, P - 1, s_p, ABAND * NCH);
   }
+  // GP: bf16 index of (query row 0, this lane's key) in the staged block, for registers whose query row has bit 1 clear / set
+  const int klh = (q >> 2) & 1, kel = (q & 3) + 4 * ((q >> 3) & 1);
+  const int pofA = (64 * klh + (q >> 4) + 8 * lh + 4 * klh) * 8 + kel, pofB = (64 * klh + (q >> 4) + 8 * lh - 4 * klh) * 8 + kel;
   for (int qt = 0; qt < nqt; ++qt) {
     const int i0 = qt * 32;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // tile qt has landed; every wave is done with step qt-1
+    float cmr;
+    if constexpr (GP) {
+      cmr = gp.nmr;
+      asm volatile("" : "+v"(cmr));
+      if (qt + 1 < nqt) gp.nmr = gp.mref[(qt + 1) * 32];
+    }
     if (qt + 1 < nqt) {
       stage_q(i0 + 32, (qt + 1) & 1);
-      stage_rows<ADK>(pbase, ldp, cb0 - 32 * (qt + 1), P - 1, s_p + ((6 * 1024 - (qt + 1)) % APRING) * (32 * ADK), 32 * NCH);
+      if constexpr (!GP)
+        stage_rows<ADK>(pbase, ldp, cb0 - 32 * (qt + 1), P - 1, s_p + ((6 * 1024 - (qt + 1)) % APRING) * (32 * ADK), 32 * NCH);
     }
-    const bf16_t* s_qu = s_q3 + (qt & 1) * (3 * 32 * ADK);
+    const bf16_t* s_qu = s_q3 + (qt & 1) * (NQ * 32 * ADK);
     const bf16_t* s_qv = s_qu + 32 * ADK;
-    const bf16_t* s_do = s_qu + 2 * 32 * ADK;
+    const bf16_t* s_do = s_qu + (NQ - 1) * 32 * ADK;
     const float* s_lse = s_ld + (qt & 1) * 64;
     const float* s_dlt = s_lse + 32;
     const int slot0 = (6 * 1024 - qt + wave) % APRING, slot1 = (6 * 1024 - qt + wave + 1) % APRING;  // band blocks wave, wave + 1
 
     f32x16 acc_s, acc_g[2], acc_dp;
+    if constexpr (GP) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { acc_s[r] = 0.f; acc_g[0][r] = 0.f; acc_g[1][r] = 0.f; acc_dp[r] = 0.f; }
+      for (int r = 0; r < 16; ++r) acc_dp[r] = 0.f;
+    } else {
 #pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) {
-      const bf16x8 quf = *reinterpret_cast<const bf16x8*>(s_qu + a_off<ADK>(q, kk * 2 + lh));
-      acc_s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(quf, kf[kk], acc_s, 0, 0, 0);     // S[query][key]
-      const bf16x8 dof = *reinterpret_cast<const bf16x8*>(s_do + a_off<ADK>(q, kk * 2 + lh));
-      acc_dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vf[kk], acc_dp, 0, 0, 0);   // dP[query][key]
-      const bf16x8 qvf = *reinterpret_cast<const bf16x8*>(s_qv + a_off<ADK>(q, kk * 2 + lh));
+      for (int r = 0; r < 16; ++r) { acc_s[r] = 0.f; acc_g[0][r] = 0.f; acc_g[1][r] = 0.f; acc_dp[r] = 0.f; }
+    }
+    float fac4[16];
+    if constexpr (GP) {
+      // per-query factor exp2(mref c2 - lse log2 e) of the step's 32 queries: one v_exp per lane, handed round through the wave's
+      // own 128 bytes of LDS (a wave's LDS operations complete in order)
+      float* fw = s_fac + wave * 32;
+      fw[lane & 31] = __builtin_amdgcn_exp2f((cmr * scale - s_lse[lane & 31]) * 1.4426950408889634f);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-        const bf16x8 pf = *reinterpret_cast<const bf16x8*>(s_p + a_off<ADK>((ct ? slot1 : slot0) * 32 + q, kk * 2 + lh));
-        acc_g[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qvf, pf, acc_g[ct], 0, 0, 0);  // G[query][c_local]
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(fw + 8 * g + 4 * lh);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) fac4[4 * g + e] = t[e];
       }
     }
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk) {
+      if constexpr (!GP) {
+        const bf16x8 quf = *reinterpret_cast<const bf16x8*>(s_qu + a_off<ADK>(q, kk * 2 + lh));
+        acc_s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(quf, kf[kk], acc_s, 0, 0, 0);     // S[query][key]
+      }
+      const bf16x8 dof = *reinterpret_cast<const bf16x8*>(s_do + a_off<ADK>(q, kk * 2 + lh));
+      acc_dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vf[kk], acc_dp, 0, 0, 0);   // dP[query][key]
+      if constexpr (!GP) {
+        const bf16x8 qvf = *reinterpret_cast<const bf16x8*>(s_qv + a_off<ADK>(q, kk * 2 + lh));
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+          const bf16x8 pf = *reinterpret_cast<const bf16x8*>(s_p + a_off<ADK>((ct ? slot1 : slot0) * 32 + q, kk * 2 + lh));
+          acc_g[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qvf, pf, acc_g[ct], 0, 0, 0);  // G[query][c_local]
+        }
+      }
+    }
+    const bf16_t* s_pw = s_p + ((qt & 1) * 4 + wave) * 1024;   // (GP) this wave's exported block
     float pd[16], ds[16];
     uint32_t w4[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};  // keep iff w >= threshold (threshold 0: dropout off)
 #pragma unroll
@@ -896,13 +1060,22 @@ __global__ __launch_bounds__(256, ADK == 64 ? 2 : 1) void relpos_flash_bwd_dkv_k
         for (int c = 0; c < 4; ++c) w4[c] = __umul24(adrop_y(seed + c * (2u * ADROP_G)), klane);
       }
       const int rho = (r & 3) + 8 * (r >> 2) + 4 * lh;  // query row of this register
-      const int sl = 31 + q - rho;                      // column of G that holds c(i, j)
-      const float g0 = __shfl(acc_g[0][r], lh * 32 + (sl & 31), 64);
-      const float g1 = __shfl(acc_g[1][r], lh * 32 + (sl & 31), 64);
-      const float bd = sl < 32 ? g0 : g1;
+      float bd = 0.f;
+      if constexpr (!GP) {
+        const int sl = 31 + q - rho;                      // column of G that holds c(i, j)
+        const float g0 = __shfl(acc_g[0][r], lh * 32 + (sl & 31), 64);
+        const float g1 = __shfl(acc_g[1][r], lh * 32 + (sl & 31), 64);
+        bd = sl < 32 ? g0 : g1;
+      }
       const int ii = i0 + rho;
       const bool ok = kvalid && ii < L;
-      const float p = ok ? __expf((acc_s[r] + bd) * scale - s_lse[rho]) : 0.f;
+      float p;
+      if constexpr (GP) {
+        const uint32_t pt = s_pw[((r & 2) ? pofB : pofA) + (2 * (r & 3) + 16 * (r >> 2)) * 8];
+        p = ok ? __uint_as_float(pt << 16) * fac4[r] : 0.f;   // (a select: blocks of key tiles beyond the utterance are never written)
+      } else {
+        p = ok ? __expf((acc_s[r] + bd) * scale - s_lse[rho]) : 0.f;
+      }
       const bool keep = w4[r & 3] >= drop.threshold;
       pd[r] = keep ? p : 0.f;
       ds[r] = p * fmaf(keep ? acc_dp[r] : 0.f, dscale, -s_dlt[rho]);  // (x scale: applied to dK at the end)
@@ -1308,5 +1481,86 @@ extern "C" int mi355x_relpos_flash_bwd_dpos(const void* qv, const void* ds, cons
               (float*)dpos, ldd, (bf16_t*)dpos_cast, H, T, nz)
   if (dk == 64) { DPOS_LAUNCH(64); } else { DPOS_LAUNCH(128); }
 #undef DPOS_LAUNCH
+  return mi_check_launch();
+}
+
+// ---- saved-probabilities variants (head width 64, padded rows only): the forward also exports its un-normalised probabilities
+// and their reference points, the two backward kernels take them instead of recomputing S, the positional band and the exponentials
+extern "C" long long mi355x_relpos_probs_elems(int B, int H, int T) {
+  const long long nt4 = 4LL * ((T + ABQ - 1) / ABQ);   // 32-row blocks each way, padded to whole 128-row workgroups
+  return (long long)B * H * nt4 * nt4 * 1024;
+}
+extern "C" long long mi355x_relpos_mref_elems(int B, int H, int T) { return mi355x_relpos_probs_elems(B, H, T) / 32; }
+
+static bool probs_args_ok(const void* probs, long long probs_elems, const void* mref, long long mref_elems, int B, int H, int T,
+                          int dk, const void* row_offsets) {
+  if (dk != 64 || row_offsets || !probs || !mref || B <= 0 || H <= 0 || T <= 0) return false;
+  if (((uintptr_t)probs & 15) || ((uintptr_t)mref & 3)) return false;
+  return probs_elems >= mi355x_relpos_probs_elems(B, H, T) && mref_elems >= mi355x_relpos_mref_elems(B, H, T);
+}
+
+extern "C" int mi355x_relpos_flash_fwd_p(const void* qkv, long long ldq, const void* pos, long long ldp, const void* bias_u,
+                                         const void* bias_v, const void* len, void* ctx, void* ctx_lo, long long ldo, void* lse,
+                                         void* probs, long long probs_elems, void* mref, long long mref_elems, int B, int H, int T,
+                                         int dk, int Tp, float scale, unsigned drop_key, unsigned drop_threshold, float drop_scale,
+                                         const void* row_offsets, void* stream) {
+  mi_clear_errors();
+  if (!qkv || !pos || !bias_u || !bias_v || !len || !ctx || B <= 0 || H <= 0 || T <= 0) return MI_ERR_ARG;
+  if (!probs_args_ok(probs, probs_elems, mref, mref_elems, B, H, T, dk, row_offsets)) return MI_ERR_ARG;
+  if ((ldq % 24) || (ldp & 7) || (ldo & 7) || ((uintptr_t)qkv & 15) || ((uintptr_t)pos & 15) || ((uintptr_t)ctx & 15) ||
+      ((uintptr_t)ctx_lo & 15))
+    return MI_ERR_ARG;
+  DropCfg dc = mi_drop(drop_key, drop_threshold, drop_scale);
+  dim3 grid((T + ABQ - 1) / ABQ, H, B);
+  MI_LAUNCH((relpos_flash_fwd_kernel<64, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv, ldq,
+            (const bf16_t*)pos, ldp, (const float*)bias_u, (const float*)bias_v, (const long long*)len, (bf16_t*)ctx,
+            (bf16_t*)ctx_lo, ldo, (float*)lse, B, H, T, Tp, scale, dc, (const long long*)nullptr, (bf16_t*)probs, (float*)mref);
+  return mi_check_launch();
+}
+
+// (takes neither qu nor qv: with P given, dQ needs K, V, dO and the band only)
+extern "C" int mi355x_relpos_flash_bwd_dq_p(const void* probs, long long probs_elems, const void* mref, long long mref_elems,
+                                            const void* qkv, long long ldq, const void* pos, long long ldp, const void* len,
+                                            const void* dO, const void* lse, const void* delta, void* dqu, void* dqv, void* ds_out,
+                                            void* dq_out, long long ld_dq, void* bias_grads, void* cs_scratch,
+                                            long long cs_scratch_elems, int B, int H, int T, int dk, long long ds_elems, float scale,
+                                            unsigned drop_key, unsigned drop_threshold, float drop_scale, const void* row_offsets,
+                                            void* stream) {
+  mi_clear_errors();
+  if (!qkv || !pos || !len || !dO || !lse || !delta || B <= 0 || H <= 0 || T <= 0) return MI_ERR_ARG;
+  if (!probs_args_ok(probs, probs_elems, mref, mref_elems, B, H, T, dk, row_offsets)) return MI_ERR_ARG;
+  if ((ldq % 24) || (ldp & 7)) return MI_ERR_ARG;
+  if (!dq_out && (!dqu || !dqv)) return MI_ERR_ARG;
+  const long long cs_need = (long long)B * ((T + ABQ - 1) / ABQ) * 2 * H * dk;
+  if (dq_out && ((ld_dq & 7) || ((uintptr_t)dq_out & 15) || (bias_grads && (!cs_scratch || cs_scratch_elems < cs_need))))
+    return MI_ERR_ARG;
+  if (ds_out && (((uintptr_t)ds_out & 15) || ds_elems < mi355x_relpos_ds_elems(B, H, T))) return MI_ERR_ARG;
+  DropCfg dc = mi_drop(drop_key, drop_threshold, drop_scale);
+  dim3 grid((T + ABQ - 1) / ABQ, H, B);
+  MI_LAUNCH((relpos_flash_bwd_dq_kernel<64, true>), grid, dim3(256), 0, (hipStream_t)stream, /* qu_g: */ (const bf16_t*)probs,
+            /* qv_g: */ (const bf16_t*)mref, (const bf16_t*)qkv, ldq, (const bf16_t*)pos, ldp, (const long long*)len,
+            (const bf16_t*)dO, (const float*)lse, (const float*)delta, (bf16_t*)dqu, (bf16_t*)dqv, (bf16_t*)ds_out, (bf16_t*)dq_out,
+            ld_dq, bias_grads ? (float*)cs_scratch : nullptr, B, H, T, H * 64, scale, dc, (const long long*)nullptr);
+  if (dq_out && bias_grads)
+    MI_LAUNCH((partials_reduce_kernel<float>), dim3((2 * H * dk + 255) / 256, 8), dim3(256), 0, (hipStream_t)stream,
+              (const float*)cs_scratch, (int)(B * ((T + ABQ - 1) / ABQ)), 2 * H * dk, (float*)bias_grads);
+  return mi_check_launch();
+}
+
+extern "C" int mi355x_relpos_flash_bwd_dkv_p(const void* probs, long long probs_elems, const void* mref, long long mref_elems,
+                                             const void* qu, const void* qkv, long long ldq, const void* len, const void* dO,
+                                             const void* lse, const void* delta, void* dqkv, long long ldd, int B, int H, int T,
+                                             int dk, float scale, unsigned drop_key, unsigned drop_threshold, float drop_scale,
+                                             const void* row_offsets, void* stream) {
+  mi_clear_errors();
+  if (!qu || !qkv || !len || !dO || !lse || !delta || !dqkv || B <= 0 || H <= 0 || T <= 0) return MI_ERR_ARG;
+  if (!probs_args_ok(probs, probs_elems, mref, mref_elems, B, H, T, dk, row_offsets)) return MI_ERR_ARG;
+  if ((ldq % 24) || (ldd % 24)) return MI_ERR_ARG;
+  DropCfg dc = mi_drop(drop_key, drop_threshold, drop_scale);
+  dim3 grid((T + ABQ - 1) / ABQ, H, B);
+  MI_LAUNCH((relpos_flash_bwd_dkv_kernel<64, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qu,
+            /* qv_g: */ (const bf16_t*)mref, (const bf16_t*)qkv, ldq, /* pos: */ (const bf16_t*)probs, 0LL, (const long long*)len,
+            (const bf16_t*)dO, (const float*)lse, (const float*)delta, (bf16_t*)dqkv, ldd, B, H, T, T, H * 64, scale, dc,
+            (const long long*)nullptr);
   return mi_check_launch();
 }

@@ -201,6 +201,8 @@ class _AttnCore(NamedTuple):
     s: Any = None        # softmax output; pd = s after attention dropout (s itself without dropout)
     pd: Any = None
     lse: Any = None      # log-sum-exp [B, H, T]
+    probs: Any = None    # fused path, flash_save_probs: the forward's un-normalised probabilities (bf16 blocks) and the
+    mref: Any = None     # reference points they were taken against -- the backward kernels scale them instead of recomputing
 
 
 class _ConvCore(NamedTuple):
@@ -423,6 +425,9 @@ class ConformerEncoder(EngineModule):
         self.fuse_layer_boundary_norms = os.environ.get("MI355X_LN2", "1") != "0"
         self.fuse_boundary_bwd = os.environ.get("MI355X_LN2_BWD", "1") != "0"  # ... and their backwards (mi355x_layernorm2_bwd)
         self.flash_delta_residual = os.environ.get("MI355X_FLASH_DELTA_LO", "1") != "0"  # (A/B switch of the delta fix)
+        # fused attention (d_k' = 64, padded rows): the forward exports its probabilities (T' x T' bf16 per head, 134 MB per layer at
+        # B = 32, T' = 501) and dQ / dK/dV read them back instead of recomputing S, the positional band and the exponentials
+        self.flash_save_probs = os.environ.get("MI355X_ATTN_SAVE_P", "1") != "0"
         self.wgrad_side_stream = os.environ.get("MI355X_WGRAD_STREAM", "1") != "0"
         self._wg_stream = None
         self._wgrad_join_per_layer = True
@@ -807,7 +812,7 @@ class ConformerEncoder(EngineModule):
         return (tuple(mel.shape), self._cdt(), str(mel.device), self._flatp.generation, self._syncbn_world(),
                 self.grad_ready_hook is not None, self._wgrad_join_per_layer, self.wgrad_side_stream, self.wgrad_grouped,
                 self.dpos_side_stream, self.sub_wgrad_side_stream, self.conv2_implicit, self.ln_cast_fuse, self.fuse_bn_dwconv_bwd, self.fuse_glu_dwconv_bwd, self.fuse_glu_dwconv_fwd, self.tap_reduce_side, self.pad_tile_skip,
-                self.use_flash_attention, self.flash_delta_residual, self.syncbn_profile is not None, self.graph_tape, self.swish_g, self.dropout, self.dropout_att, self.dropout_emb, self.dropout_pre_encoder,
+                self.use_flash_attention, self.flash_delta_residual, self.flash_save_probs, self.syncbn_profile is not None, self.graph_tape, self.swish_g, self.dropout, self.dropout_att, self.dropout_emb, self.dropout_pre_encoder,
                 self.wgrad_defer, self.graph_bwd_live, self.posproj_side, self.wgrad_layers, self._ctx)
 
     def _auto_begin(self, gs, mode):
@@ -1578,6 +1583,12 @@ class ConformerEncoder(EngineModule):
             # (kept whenever activations are saved for a backward -- also for an eval-mode / frozen encoder that is
             #  differentiated through: delta from the rounded O alone put a 36 % error on layer-0 q / k gradients)
             ctx_lo = self._new(ctx.shape[0], dA, dtype=cdt, device=dev) if (self._saving and self.flash_delta_residual) else None
+            if self._saving and self.flash_save_probs and dk == 64 and cu is None:
+                probs = self._new(ops.lib.mi355x_relpos_probs_elems(B, H, T), dtype=cdt, device=dev)
+                mref = self._new(ops.lib.mi355x_relpos_mref_elems(B, H, T), dtype=torch.float32, device=dev)
+                ops.relpos_flash_fwd_p(qkv, 3 * dA, p, dA, bias_u, bias_v, lens, ctx, dA, lse, probs, mref, B, H, T, dk, Tp, scale,
+                                       d_att, ctx_lo=ctx_lo)
+                return ctx, _AttnCore(ctx_lo=ctx_lo, lse=lse, probs=probs, mref=mref)
             ops.relpos_flash_fwd(qkv, 3 * dA, p, dA, bias_u, bias_v, lens, ctx, dA, lse, B, H, T, dk, Tp, scale, d_att,
                                  ctx_lo=ctx_lo, cu=cu)
             return ctx, _AttnCore(ctx_lo=ctx_lo, lse=lse)
@@ -1648,13 +1659,21 @@ class ConformerEncoder(EngineModule):
             side_pos = self.dpos_side_stream and self.wgrad_side_stream
             n_ds = ops.lib.mi355x_relpos_ds_elems(B, H, T)
             dS = (self._new(n_ds, dtype=cdt, device=dev) if side_pos else self._buf("dS", (n_ds,), cdt, dev))
-            ops.relpos_flash_bwd_dq(qu, qv, qkv, 3 * dA, p, dA, lens, dctx, lse, dlt, dqu, dqv, B, H, T, dk, scale, d_att,
-                                    ds_out=dS, dq_out=dqkv if fuse_dq else None, ld_dq=3 * dA, bias_grads=bias_grads, cu=cu)
+            probs, mref = saved.probs, saved.mref
+            if probs is not None:
+                ops.relpos_flash_bwd_dq_p(probs, mref, qkv, 3 * dA, p, dA, lens, dctx, lse, dlt, dqu, dqv, B, H, T, dk, scale, d_att,
+                                          ds_out=dS, dq_out=dqkv if fuse_dq else None, ld_dq=3 * dA, bias_grads=bias_grads)
+            else:
+                ops.relpos_flash_bwd_dq(qu, qv, qkv, 3 * dA, p, dA, lens, dctx, lse, dlt, dqu, dqv, B, H, T, dk, scale, d_att,
+                                        ds_out=dS, dq_out=dqkv if fuse_dq else None, ld_dq=3 * dA, bias_grads=bias_grads, cu=cu)
             if side_pos:
                 with self._wgrad_scope(qv, dS):
                     ops.relpos_flash_bwd_dpos(qv, dS, lens, dp, B, H, T, dk, dpos_cast=dp_cast, cu=cu)
-            ops.relpos_flash_bwd_dkv(qu, qv, qkv, 3 * dA, p, dA, lens, dctx, lse, dlt, dqkv, 3 * dA, B, H, T, dk, Tp, scale, d_att,
-                                     cu=cu)
+            if probs is not None:
+                ops.relpos_flash_bwd_dkv_p(probs, mref, qu, qkv, 3 * dA, lens, dctx, lse, dlt, dqkv, 3 * dA, B, H, T, dk, scale, d_att)
+            else:
+                ops.relpos_flash_bwd_dkv(qu, qv, qkv, 3 * dA, p, dA, lens, dctx, lse, dlt, dqkv, 3 * dA, B, H, T, dk, Tp, scale,
+                                         d_att, cu=cu)
             if not side_pos:
                 ops.relpos_flash_bwd_dpos(qv, dS, lens, dp, B, H, T, dk, dpos_cast=dp_cast, cu=cu)
             return dqkv, dqu, dqv

@@ -761,6 +761,36 @@ def relpos_flash_bwd_dkv(qu, qv, qkv, ldq, pos, ldp, lens, dO, lse, delta, dqkv,
                                           drop.scale, _ptr(cu), _stream()), "relpos_flash_bwd_dkv")
 
 
+def relpos_flash_fwd_p(qkv, ldq, pos, ldp, bias_u, bias_v, lens, ctx, ldo, lse, probs, mref, B, H, T, dk, Tp, scale,
+                       drop: Dropout = NO_DROP, ctx_lo=None):
+    """relpos_flash_fwd that also exports its un-normalised probabilities (`probs`: bf16, >= mi355x_relpos_probs_elems) and
+    their per-step reference points (`mref`: f32, >= mi355x_relpos_mref_elems) for the *_p backward kernels; d_k = 64, padded rows"""
+    check(lib.mi355x_relpos_flash_fwd_p(_ptr(qkv), ldq, _ptr(pos), ldp, _ptr(bias_u), _ptr(bias_v), _ptr(lens), _ptr(ctx),
+                                        _ptr(ctx_lo), ldo, _ptr(lse), _ptr(probs), probs.numel(), _ptr(mref), mref.numel(), B, H, T,
+                                        dk, Tp, scale, drop.key, drop.threshold, drop.scale, None, _stream()), "relpos_flash_fwd_p")
+
+
+def relpos_flash_bwd_dq_p(probs, mref, qkv, ldq, pos, ldp, lens, dO, lse, delta, dqu, dqv, B, H, T, dk, scale,
+                          drop: Dropout = NO_DROP, ds_out=None, dq_out=None, ld_dq=0, bias_grads=None):
+    """relpos_flash_bwd_dq on the probabilities relpos_flash_fwd_p exported (same outputs; needs neither qu nor qv)"""
+    sc, n = None, 0
+    if bias_grads is not None:
+        n = B * ((T + 127) // 128) * 2 * H * dk
+        sc = _scratch("relpos_flash_bwd_dq", n, qkv.device)
+    check(lib.mi355x_relpos_flash_bwd_dq_p(_ptr(probs), probs.numel(), _ptr(mref), mref.numel(), _ptr(qkv), ldq, _ptr(pos), ldp,
+                                           _ptr(lens), _ptr(dO), _ptr(lse), _ptr(delta), _ptr(dqu), _ptr(dqv), _ptr(ds_out),
+                                           _ptr(dq_out), ld_dq, _ptr(bias_grads), _ptr(sc), n, B, H, T, dk,
+                                           0 if ds_out is None else ds_out.numel(), scale, drop.key, drop.threshold, drop.scale,
+                                           None, _stream()), "relpos_flash_bwd_dq_p")
+
+
+def relpos_flash_bwd_dkv_p(probs, mref, qu, qkv, ldq, lens, dO, lse, delta, dqkv, ldd, B, H, T, dk, scale, drop: Dropout = NO_DROP):
+    """relpos_flash_bwd_dkv on the probabilities relpos_flash_fwd_p exported"""
+    check(lib.mi355x_relpos_flash_bwd_dkv_p(_ptr(probs), probs.numel(), _ptr(mref), mref.numel(), _ptr(qu), _ptr(qkv), ldq,
+                                            _ptr(lens), _ptr(dO), _ptr(lse), _ptr(delta), _ptr(dqkv), ldd, B, H, T, dk, scale,
+                                            drop.key, drop.threshold, drop.scale, None, _stream()), "relpos_flash_bwd_dkv_p")
+
+
 def relpos_flash_bwd_dpos(qv, ds, lens, dpos, B, H, T, dk, dpos_cast=None, cu=None):
     """`dpos_cast` (bf16, shape of dpos): the GEMM-operand copy of the updated gradient, written by the reduction stage"""
     n = lib.mi355x_relpos_dpos_partial_elems(B, H, T)

@@ -822,6 +822,65 @@ int mi355x_ctc_beam_decode_fused_stream(const void* logp, const void* lens, void
                                         const mi355x_ctc_beam_fused_state* state_in, const mi355x_ctc_beam_fused_state* state_out,
                                         void* stream);
 
+/* ---- committing the stable prefix of a stream, and the search over what is left.  The resumable search above keeps every frame of
+ * a stream in its tree.  mi355x_ctc_beam_commit takes the tokens that every live hypothesis shares out of the tree, makes the node
+ * they end in the new root and drops every tree frame that no live hypothesis needs any more, so the tree of a stream that never
+ * ends stays small.  It does integer work only: the float32 fields of a beam are copied as their bits.
+ * The window of a stream (device arrays, all zero for a stream that was never committed):
+ *   tok_base     i32 [B]         tokens committed so far
+ *   frame_base   i32 [B]         global frames the stream had consumed at its last commit
+ *   kept         i32 [B]         tree frames that survived the last commit
+ *   frame_map    i32 [B, Tcap]   the global frame of each of the first `kept` tree frames
+ * With fd = frames_done of the state, G = frame_base + fd - kept is the number of global frames consumed, and tree frame i is
+ * global frame frame_map[i] if i < kept, else i - kept + frame_base.  A node's creation frame is that of its tree frame.
+ * Per stream, with S = stable_frames (negative: never force):
+ *  1. Forced pruning (S >= 0 only).  cut = G - S.  old(X) of a beam X is the deepest node of its chain (its own node, its parent,
+ *     ... ) whose global creation frame is < cut, the root (node 0) if there is none.  X survives iff old(X) == old(slot 0); slot 0
+ *     always does.  The survivors keep their order and every field bit for bit (pb, pnb, tot, brank, h, hp, len, tok, the models'
+ *     states and sums); nb' is their number; the slots behind them get what the search leaves in an empty slot (node 0, par -1,
+ *     tok -1, len 0, the root hash, 0, -inf four times, model state 1 and sum 0).  Identity is BY NODE, not by token sequence: a
+ *     beam that spells the same old prefix under another node (the prefix fell out of the set and came back) is dropped.
+ *  2. Common ancestor.  A is the deepest node on every survivor's chain (the root if none).  The tokens on the path root -> A and
+ *     their global frames are written to com_tokens / com_frames [B, Tcap], positions 0 .. n_com[b]-1, in order.
+ *  3. Re-rooting, and compaction in frame space.  Exactly the tree frames that hold a strict descendant of A on a survivor's chain
+ *     stay, in order, renumbered 0 .. kept'-1.  Their `beam` pairs go to tree_out with the parent renumbered: A becomes 0, a node
+ *     of a kept frame its new id 1 + new frame * beam + slot, anything else 0; a pair of a kept frame that is on no survivor's
+ *     chain is written (0, -1).  The beams' node and par are renumbered the same way; a beam that IS A gets node 0 and par -1.
+ *     frames_done' = kept', frame_base' = G, tok_base' = tok_base + n_com, frame_map' is composed from the old map.  len stays the
+ *     GLOBAL length: the rank uses beta * len and keeps its bits.
+ * After a forced commit every kept frame is younger than the cut, so kept' <= S: the memory of a stream is bounded.  With S < 0
+ * the commit changes no result: committed tokens followed by the tail that mi355x_ctc_beam_decode_window_stream returns are the
+ * hypotheses, frames, lengths and scores of the uncommitted search, bit for bit.
+ * Out of place: state_out, window_out and tree_out are written, nothing of the input is; the same input committed twice gives the
+ * same result.  workspace: i32, B * mi355x_ctc_beam_commit_workspace_elems(Tcap, beam).  n_models (0..2) says which model arrays
+ * of the states are copied (lm_state / lm_sum from 1, fs_state / fs_sum at 2).
+ * Whatever the state and the tree hold, nothing is stored outside the arrays given and every walk ends: frames_done, nb and kept
+ * are clamped to their ranges (tok_base and frame_base to 0 .. 0x3fffffff, here and in the search below, so that no sum of
+ * theirs overflows), a node id outside the frames that are done is the root, and a parent is followed only into an earlier frame.  A state that is not one of this search's gives a wrong answer.
+ * MI_ERR_ARG for a null argument or array (model arrays as n_models asks), B < 1, beam outside 1..64, Tcap < 1,
+ * Tcap * beam > 0x3fffffff, n_models outside 0..2, trees that are not 8-byte aligned, and aliasing of input and output (the
+ * states' node arrays, the trees, the windows' frame_map or kept arrays). */
+typedef struct mi355x_ctc_beam_window {
+  int* tok_base; int* frame_base; int* kept; int* frame_map;
+} mi355x_ctc_beam_window;
+long long mi355x_ctc_beam_commit_workspace_elems(int Tcap, int beam);
+int mi355x_ctc_beam_commit(const mi355x_ctc_beam_fused_state* state_in, const mi355x_ctc_beam_window* window_in, const void* tree_in,
+                           const mi355x_ctc_beam_fused_state* state_out, const mi355x_ctc_beam_window* window_out, void* tree_out,
+                           void* com_tokens, void* com_frames, void* n_com, void* workspace, int B, int beam, int Tcap,
+                           int n_models, int stable_frames, void* stream);
+/* mi355x_ctc_beam_decode_fused_stream (n_models 0..2; `models` may be NULL at 0) over a committed stream: `window` (required, read
+ * only) is the record mi355x_ctc_beam_commit wrote with the state and the tree.  Three things differ, none inside a frame:
+ *   len of state_in is clamped to tok_base + clamp(len - tok_base, 0, frames_done)
+ *   the outputs hold the TAIL of each hypothesis, the tokens behind the committed ones: positions 0 .. len - tok_base - 1 are
+ *   written and hyp_len = len - tok_base (score and n_hyp as ever)
+ *   tok_frame is the global frame, through the window's map
+ * MI_ERR_ARG for what mi355x_ctc_beam_decode_fused_stream refuses (but n_models = 0) and a null window or window array. */
+int mi355x_ctc_beam_decode_window_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
+                                         void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank, int beam,
+                                         float threshold, float beta, const mi355x_ctc_beam_fusion* models, int n_models, int Tcap,
+                                         const mi355x_ctc_beam_fused_state* state_in, const mi355x_ctc_beam_fused_state* state_out,
+                                         const mi355x_ctc_beam_window* window, void* stream);
+
 /* SpectrogramAugmentation (nemo/collections/asr/modules/audio_preprocessing.py:443-553; SpecAugment._apply_masks
  * parts/submodules/spectr_augment.py:153-215, SpecCutout.forward :245-261): x[b, f0:f1, t0:t1] = value for n rectangles
  * rects[n][5] = (b, f0, f1, t0, t1) (int32, device memory; clipped to the tensor).  x: f32 [B, F, T], in place. */

@@ -135,6 +135,13 @@ SIGNATURES = {
     # (..., models: mi355x_ctc_beam_fusion[n_models], n_models, [Tcap, state_in, state_out: mi355x_ctc_beam_fused_state,] stream)
     "mi355x_ctc_beam_decode_fused": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, i32, vp],
     "mi355x_ctc_beam_decode_fused_stream": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, i32, i32, vp, vp, vp],
+    # (..., state_out, window: pointer to mi355x_ctc_beam_window, stream)
+    "mi355x_ctc_beam_decode_window_stream": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, i32, i32, vp, vp, vp,
+                                             vp],
+    # (state_in, window_in, tree_in, state_out, window_out, tree_out, com_tokens, com_frames, n_com, workspace, B, beam, Tcap,
+    #  n_models, stable_frames, stream)
+    "mi355x_ctc_beam_commit": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "mi355x_ctc_beam_commit_workspace_elems": [i32, i32],
     "mi355x_fill_rects": [vp, vp, i32, i32, i32, i32, f32, vp],
     "mi355x_specaug_rects": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp],
     "mi355x_add2_colsum": [vp, vp, vp, i64, i64, i32, vp, vp, i64, vp],
@@ -248,6 +255,7 @@ def _load():
     lib.mi355x_relpos_mref_elems.restype = i64
     lib.mi355x_relpos_dpos_partial_elems.restype = i64
     lib.mi355x_ctc_beam_workspace_elems.restype = i64
+    lib.mi355x_ctc_beam_commit_workspace_elems.restype = i64
     lib.mi355x_asr_version.argtypes = []
     lib.mi355x_tape_destroy.restype = None
     lib.mi355x_mailbox_destroy.restype = None

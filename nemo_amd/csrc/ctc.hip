@@ -9,6 +9,7 @@
 // Replaces on the reference path: torch.nn.functional.ctc_loss forward+backward called by
 //   nemo/collections/asr/losses/ctc.py:68-82 (CTCLoss(blank=V, reduction='none', zero_infinity=True) + mean_batch).
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 #include "mi355x_asr.h"
 
@@ -924,6 +925,9 @@ extern "C" int mi355x_ctc_align(const void* logp, const void* targets, const voi
 // padded.  The frame loop is the one-shot search's: rows are indexed by the frame of the chunk, nodes by the frame of the stream.
 #define CTC_BEAM_MAX 64
 #define CTC_BEAM_ROOT_HASH 0x243F6A8885A308D3ull
+// the bases of a window (tokens committed, frames consumed) are clamped to 0 .. this, so that no sum with a frame count (<= Tcap,
+// itself <= 0x3fffffff) leaves the int range whatever a window holds
+#define CTC_BEAM_BASE_MAX 0x3fffffff
 __device__ __forceinline__ float ctc_lae(float a, float b) {
   const float m = fmaxf(a, b);
   return (m == NEGINF) ? NEGINF : m + log1pf(expf(-fabsf(a - b)));
@@ -1020,6 +1024,13 @@ template <int NM> struct ctc_beam_stream<NM, true> {
     else return more.v[k - 1];
   }
 };
+// the window of a committed stream (mi355x_ctc_beam_window, read-only): behind the stream record, in a record of its own type, so
+// that the kernels without a window keep the argument block they had
+template <int NM> struct ctc_beam_stream_win : ctc_beam_stream<NM, true> {
+  const int* tok_base; const int* frame_base; const int* kept; const int* frame_map;
+};
+template <int NM, bool STREAM, bool WIN>
+using ctc_beam_stream_arg_t = std::conditional_t<WIN, ctc_beam_stream_win<NM>, ctc_beam_stream<NM, STREAM>>;
 // are the prefixes of nodes a and b the same sequence (they have the same length)?  BOUND (resumable search: the ids come from a
 // state and a tree the caller keeps): an id beyond `lim` is not followed
 template <bool BOUND>
@@ -1035,13 +1046,14 @@ __device__ __forceinline__ bool ctc_beam_same_prefix(const int2* ws, int a, int 
   return true;
 }
 
-template <int NM, bool STREAM, bool FINAL>
+template <int NM, bool STREAM, bool FINAL, bool WIN = false>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ logp, const long long* __restrict__ lens, int2* node_ws,
                                                       int* __restrict__ tokens, int* __restrict__ tok_frame, int* __restrict__ hyp_len,
                                                       float* __restrict__ score, int* __restrict__ n_hyp, int Tmax, int C, int blank,
                                                       int W, float theta, float beta, ctc_beam_models<NM, FINAL> lm,
-                                                      ctc_beam_stream<NM, STREAM> st) {
+                                                      ctc_beam_stream_arg_t<NM, STREAM, WIN> st) {
   static_assert(NM >= 0 && NM <= 2, "at most two fusion models");
+  static_assert(STREAM || !WIN, "a window is a stream's");
   static_assert(NM > 0 || !FINAL, "a final term is a model's");
   constexpr int NR = NM > 0 ? NM : 1;   // (per-model registers: an array of one that nothing touches at NM = 0)
   extern __shared__ float s_rows[];   // [2][C]: the log-probabilities of this frame and of the next
@@ -1067,7 +1079,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       nb = min(max(st.in.nb[b], 0), W);
       if (lane < nb) {
         const int s = b * W + lane;
-        node = st.in.node[s]; par = st.in.par[s]; tok = min(max(st.in.tok[s], -1), C - 1); len = min(max(st.in.len[s], 0), f0);
+        node = st.in.node[s]; par = st.in.par[s]; tok = min(max(st.in.tok[s], -1), C - 1);
+        if constexpr (WIN) {   // len is the GLOBAL length (the rank's beta * len keeps its bits); the tree holds its tail
+          const int tb = min(max(st.tok_base[b], 0), CTC_BEAM_BASE_MAX);
+          len = tb + min(max(max(st.in.len[s], 0) - tb, 0), f0);
+        } else {
+          len = min(max(st.in.len[s], 0), f0);
+        }
         h = st.in.h[s]; hp = st.in.hp[s];
         pb = st.in.pb[s]; pnb = st.in.pnb[s]; tot = st.in.tot[s]; brank = st.in.brank[s];
         CTC_BEAM_EACH_MODEL(NM, k, { m_state[k] = st.template model<k>().in_state[s]; m_sum[k] = st.template model<k>().in_sum[s]; });
@@ -1277,6 +1295,15 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     }
     if (lane == 0) { st.out.nb[b] = nb; st.out.frames_done[b] = f0 + T; }
     if (!tokens) return;
+    // (WIN) the tail only: the tokens behind the committed ones, and a tree frame's global frame through the window -- read here,
+    // behind the frame loop, so that nothing of it is alive in the loop
+    int w_kept = 0, w_base = 0;
+    const int* w_map = nullptr;
+    if constexpr (WIN) {
+      if (st.in.node) o_len = min(max(o_len - min(max(st.tok_base[b], 0), CTC_BEAM_BASE_MAX), 0), Tout);
+      w_kept = min(max(st.kept[b], 0), Tout); w_base = min(max(st.frame_base[b], 0), CTC_BEAM_BASE_MAX);
+      w_map = st.frame_map + (long long)b * Tout;
+    }
     if (lane < W) {
       const bool live = lane < nb;
       hyp_len[b * W + lane] = live ? o_len : 0;
@@ -1288,7 +1315,9 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         for (int p = o_len - 1; p >= 0 && id > 0 && id <= node_lim; --p) {   // (len <= f0 + T <= Tout)
           const int2 e = ws[id - 1];
           tk[p] = e.y;
-          tf[p] = (id - 1) / W;
+          int fr = (id - 1) / W;
+          if constexpr (WIN) fr = fr < w_kept ? w_map[fr] : fr - w_kept + w_base;
+          tf[p] = fr;
           id = e.x;
         }
       }
@@ -1356,28 +1385,32 @@ static ctc_beam_models<NM, FINAL> ctc_beam_models_arg(const mi355x_ctc_beam_fusi
   });
   return r;
 }
-template <int NM, bool STREAM>
-static ctc_beam_stream<NM, STREAM> ctc_beam_stream_arg(const mi355x_ctc_beam_fused_state* in, const mi355x_ctc_beam_fused_state* out,
-                                                       int Tcap) {
-  ctc_beam_stream<NM, STREAM> r = {};
+template <int NM, bool STREAM, bool WIN>
+static ctc_beam_stream_arg_t<NM, STREAM, WIN> ctc_beam_stream_arg(const mi355x_ctc_beam_fused_state* in,
+                                                                  const mi355x_ctc_beam_fused_state* out, int Tcap,
+                                                                  const mi355x_ctc_beam_window* win) {
+  ctc_beam_stream_arg_t<NM, STREAM, WIN> r = {};
   if constexpr (STREAM) {
     const mi355x_ctc_beam_fused_state fresh = {};   // (in null, or in->beams.node null: fresh streams, nothing of `in` is read)
     const mi355x_ctc_beam_fused_state& i = in && in->beams.node ? *in : fresh;
     r.in = i.beams; r.out = out->beams; r.Tcap = Tcap;
     if constexpr (NM > 1) r.more.v[0] = {i.fs_state, i.fs_sum, out->fs_state, out->fs_sum};
+    if constexpr (WIN) { r.tok_base = win->tok_base; r.frame_base = win->frame_base; r.kept = win->kept; r.frame_map = win->frame_map; }
   }
   return r;
 }
 
 // Every entry of the search: 0 to 2 fusion models, and the resumable search where state_out is given (the one-shot search has no
 // states, and its tree holds Tmax frames).  The resumable search takes its five outputs all or none, a whole state_out, and a
-// state_in that is null, fresh (node null) or whole.
+// state_in that is null, fresh (node null) or whole; with `win` (a whole window record) it is the search of a committed stream.
+// The window is a template flag, not a null check at run time: the kernels of the entries without one are the code they were.
 static int ctc_beam_launch(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame, void* hyp_len, void* score,
                            void* n_hyp, int B, int Tmax, int C, int blank, int beam, float threshold, float beta,
                            const mi355x_ctc_beam_fusion* models, int n_models, int Tcap, const mi355x_ctc_beam_fused_state* state_in,
-                           const mi355x_ctc_beam_fused_state* state_out, void* stream) {
+                           const mi355x_ctc_beam_fused_state* state_out, void* stream, const mi355x_ctc_beam_window* win = nullptr) {
   mi_clear_errors();
   const bool streamed = state_out != nullptr;
+  if (win && (!streamed || !win->tok_base || !win->frame_base || !win->kept || !win->frame_map)) return MI_ERR_ARG;
   const int outs = !!tokens + !!tok_frame + !!hyp_len + !!score + !!n_hyp;
   if (outs != 5 && !(streamed && outs == 0)) return MI_ERR_ARG;
   if (n_models < 0 || n_models > 2 || (n_models && (!models || blank != C - 1))) return MI_ERR_ARG;
@@ -1392,10 +1425,20 @@ static int ctc_beam_launch(const void* logp, const void* lens, void* node_ws, vo
   // the output's final terms and re-ordering are compiled in where a model can bring a `state_final` table: with two models always,
   // with one where it has the table (an n-gram model has none, and the code's mere presence costs its search 2.4 to 4.3 %)
   const bool final = n_models == 2 || (n_models == 1 && models[0].state_final);
-#define CTC_BEAM_LAUNCH(NM, STREAM, FINAL)                                                                                             \
-  MI_LAUNCH((ctc_beam_kernel<NM, STREAM, FINAL>), dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp,           \
+#define CTC_BEAM_LAUNCH_W(NM, STREAM, FINAL, WIN)                                                                                      \
+  MI_LAUNCH((ctc_beam_kernel<NM, STREAM, FINAL, WIN>), dim3(B), dim3(64), (size_t)C * 8, (hipStream_t)stream, (const float*)logp,      \
             (const long long*)lens, (int2*)node_ws, (int*)tokens, (int*)tok_frame, (int*)hyp_len, (float*)score, (int*)n_hyp, Tmax, C, \
-            blank, beam, threshold, beta, (ctc_beam_models_arg<NM, FINAL>(models)), (ctc_beam_stream_arg<NM, STREAM>(state_in, state_out, Tcap)))
+            blank, beam, threshold, beta, (ctc_beam_models_arg<NM, FINAL>(models)),                                                    \
+            (ctc_beam_stream_arg<NM, STREAM, WIN>(state_in, state_out, Tcap, win)))
+#define CTC_BEAM_LAUNCH(NM, STREAM, FINAL) CTC_BEAM_LAUNCH_W(NM, STREAM, FINAL, false)
+  if (win) {
+    switch (2 * n_models + final) {
+      case 0: CTC_BEAM_LAUNCH_W(0, true, false, true); break;
+      case 2: CTC_BEAM_LAUNCH_W(1, true, false, true); break;
+      case 3: CTC_BEAM_LAUNCH_W(1, true, true, true); break;
+      default: CTC_BEAM_LAUNCH_W(2, true, true, true); break;
+    }
+  } else
   switch (4 * n_models + 2 * streamed + final) {
     case 0: CTC_BEAM_LAUNCH(0, false, false); break;
     case 2: CTC_BEAM_LAUNCH(0, true, false); break;
@@ -1407,6 +1450,7 @@ static int ctc_beam_launch(const void* logp, const void* lens, void* node_ws, vo
     default: CTC_BEAM_LAUNCH(2, true, true); break;
   }
 #undef CTC_BEAM_LAUNCH
+#undef CTC_BEAM_LAUNCH_W
   return mi_check_launch();
 }
 // what an entry refuses before the launcher sees it: the launcher takes no model for the plain search, a null state_out for the
@@ -1486,4 +1530,216 @@ extern "C" int mi355x_ctc_beam_decode_fused_stream(const void* logp, const void*
   if (!models || n_models < 1 || !state_out) return ctc_beam_refused();
   return ctc_beam_launch(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
                          models, n_models, Tcap, state_in, state_out, stream);
+}
+
+// The resumable search of a committed stream: 0 to 2 models, the tree and the state as mi355x_ctc_beam_commit left them, and the
+// window it wrote (include/mi355x_asr.h).
+extern "C" int mi355x_ctc_beam_decode_window_stream(const void* logp, const void* lens, void* node_ws, void* tokens, void* tok_frame,
+                                                    void* hyp_len, void* score, void* n_hyp, int B, int Tmax, int C, int blank,
+                                                    int beam, float threshold, float beta, const mi355x_ctc_beam_fusion* models,
+                                                    int n_models, int Tcap, const mi355x_ctc_beam_fused_state* state_in,
+                                                    const mi355x_ctc_beam_fused_state* state_out,
+                                                    const mi355x_ctc_beam_window* window, void* stream) {
+  if (!state_out || !window) return ctc_beam_refused();
+  return ctc_beam_launch(logp, lens, node_ws, tokens, tok_frame, hyp_len, score, n_hyp, B, Tmax, C, blank, beam, threshold, beta,
+                         models, n_models, Tcap, state_in, state_out, stream, window);
+}
+
+// ------------------------------------------------------------------------------------------------ committing a stream's stable prefix
+// mi355x_ctc_beam_commit (include/mi355x_asr.h states it): a wave per stream, a lane per beam, integers only -- the float32 fields
+// of a beam travel as their bits.  Out of place: (state, window, tree) -> (state', window', tree').  In order:
+//   forced pruning   (stable_frames >= 0) a lane walks its chain down to the first node created before the cut: old(X); the beams
+//                    whose old is slot 0's survive and close ranks (a ballot and a count)
+//   common ancestor  every surviving lane holds a node of its chain, at first its own; while they differ the lanes above the
+//                    smallest id step to their parent -- a parent's id is below its child's, so the ancestor is never stepped over
+//   kept frames      the lanes walk from their node to the ancestor and flag the frames they pass in the frame table [Tcap]; a
+//                    ballot scan turns the flags into new frame numbers and composes the new frame map
+//   the new tree     the kept frames are filled with (0, -1), then the lanes walk once more and store their nodes with both ids
+//                    renumbered (lanes that share a node store the same pair)
+//   committed path   lane 0 walks from the ancestor to the root into the chain buffer [2 Tcap]; the wave turns it round
+// A parent is followed only into an EARLIER frame of the frames the state says are done, so a chain has at most Tcap nodes and
+// every walk ends, whatever the tree holds; frames_done, nb and kept are clamped as the search clamps them, tok_base and
+// frame_base to 0 .. CTC_BEAM_BASE_MAX.
+#define CTC_NEGINF_BITS ((int)0xff800000)
+__device__ __forceinline__ int ctc_wave_min_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int ctc_wave_max_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// the parent of node id (0 < id <= lim): followed only into an earlier frame, else the root
+__device__ __forceinline__ int ctc_commit_parent(const int2* ws, int id, int W) {
+  const int p = ws[id - 1].x;
+  return (p > 0 && (p - 1) / W < (id - 1) / W) ? p : 0;
+}
+// the new id of node p: the ancestor is the new root, a node of a kept frame moves with its frame, anything else is the root
+__device__ __forceinline__ int ctc_commit_remap(const int* ftab, int p, int A, int lim, int W) {
+  if (p == A || p <= 0 || p > lim) return 0;
+  const int f = ftab[(p - 1) / W];
+  return f < 0 ? 0 : 1 + f * W + (p - 1) % W;
+}
+
+template <int NM>
+__global__ __launch_bounds__(64) void ctc_beam_commit_kernel(mi355x_ctc_beam_fused_state in, mi355x_ctc_beam_window win,
+                                                             const int2* __restrict__ tree_in, mi355x_ctc_beam_fused_state out,
+                                                             mi355x_ctc_beam_window wout, int2* __restrict__ tree_out,
+                                                             int* __restrict__ com_tokens, int* __restrict__ com_frames,
+                                                             int* __restrict__ n_com, int* __restrict__ wsp, int W, int Tcap,
+                                                             int S) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int fd = min(max(in.beams.frames_done[b], 0), Tcap);
+  const int nb = min(max(in.beams.nb[b], 0), W);
+  const int kept = min(max(win.kept[b], 0), fd);
+  const int fbase = min(max(win.frame_base[b], 0), CTC_BEAM_BASE_MAX), tbase = min(max(win.tok_base[b], 0), CTC_BEAM_BASE_MAX);
+  const int G = fbase + fd - kept;   // (0 <= G < 2^31, and S >= 0 below: no sum here overflows)
+  const int lim = fd * W;   // the largest id of a node of a frame that is done
+  const int2* ws = tree_in + (long long)b * Tcap * W;
+  int2* wo = tree_out + (long long)b * Tcap * W;
+  const int* fmap = win.frame_map + (long long)b * Tcap;
+  int* fmap_o = wout.frame_map + (long long)b * Tcap;
+  int* ftab = wsp + (long long)b * 3 * Tcap;   // [Tcap]: flag, then new number, of a tree frame
+  int* chain = ftab + Tcap;                    // [2 Tcap]: (token, global frame) from the ancestor down to the root
+#define CTC_GF(i) ((i) < kept ? fmap[(i)] : (i) - kept + fbase)
+  const bool live = lane < nb;
+  const int s = b * W + lane;
+  int node = 0, par = -1;
+  if (live) {
+    node = in.beams.node[s]; par = in.beams.par[s];
+    if (node <= 0 || node > lim) node = 0;
+  }
+  // ---- forced pruning
+  bool surv = live;
+  if (S >= 0) {
+    const int cut = G - S;
+    int id = node;
+    while (id > 0 && CTC_GF((id - 1) / W) >= cut) id = ctc_commit_parent(ws, id, W);
+    surv = live && id == ctc_rl(id, 0);
+  }
+  const unsigned long long smask = __ballot(surv);
+  const int nb2 = __popcll(smask);
+  const int slot = __popcll(smask & ((1ull << lane) - 1ull));
+  // ---- the common ancestor
+  int cur = node;
+  int A = 0;
+  if (nb2 > 0) {
+    int mn = ctc_wave_min_i(surv ? cur : 0x7fffffff), mx = ctc_wave_max_i(surv ? cur : -1);
+    for (long long it = 0; mn != mx && it <= (long long)Tcap * W; ++it) {
+      if (surv && cur > mn) cur = ctc_commit_parent(ws, cur, W);
+      mn = ctc_wave_min_i(surv ? cur : 0x7fffffff); mx = ctc_wave_max_i(surv ? cur : -1);
+    }
+    A = mn == mx ? mn : 0;
+  }
+  // ---- the frames that stay: those with a strict descendant of A on a survivor's chain
+  for (int i = lane; i < fd; i += 64) ftab[i] = 0;
+  __threadfence_block();
+  __syncthreads();
+  if (surv)
+    for (int id = node; id > 0 && id != A; id = ctc_commit_parent(ws, id, W)) ftab[(id - 1) / W] = 1;
+  __threadfence_block();
+  __syncthreads();
+  int kept2 = 0;
+  for (int i0 = 0; i0 < fd; i0 += 64) {
+    const int i = i0 + lane;
+    const bool k = i < fd && ftab[i] != 0;
+    const unsigned long long m = __ballot(k);
+    const int idx = kept2 + __popcll(m & ((1ull << lane) - 1ull));
+    if (i < fd) ftab[i] = k ? idx : -1;
+    if (k) fmap_o[idx] = CTC_GF(i);
+    kept2 += __popcll(m);
+  }
+  // ---- the new tree
+  for (int j = lane; j < kept2 * W; j += 64) wo[j] = make_int2(0, -1);
+  __threadfence_block();
+  __syncthreads();
+  if (surv)
+    for (int id = node; id > 0 && id != A;) {
+      const int p = ctc_commit_parent(ws, id, W);
+      const int to = ctc_commit_remap(ftab, id, A, lim, W);   // (> 0: the walk above flagged its frame)
+      if (to > 0) wo[to - 1] = make_int2(ctc_commit_remap(ftab, p, A, lim, W), ws[id - 1].y);
+      id = p;
+    }
+  // ---- the committed tokens: root to A
+  int n = 0;
+  if (lane == 0)
+    for (int id = A; id > 0 && n < Tcap; id = ctc_commit_parent(ws, id, W)) {
+      chain[2 * n] = ws[id - 1].y; chain[2 * n + 1] = CTC_GF((id - 1) / W);
+      ++n;
+    }
+  n = ctc_rl(n, 0);
+  __threadfence_block();
+  __syncthreads();
+  for (int p = lane; p < n; p += 64) {
+    com_tokens[(long long)b * Tcap + p] = chain[2 * (n - 1 - p)];
+    com_frames[(long long)b * Tcap + p] = chain[2 * (n - 1 - p) + 1];
+  }
+#undef CTC_GF
+  // ---- the beams: the survivors in their order, bit for bit, with their two ids renumbered; behind them what the search leaves
+  // in an empty slot
+  if (surv) {
+    const int d = b * W + slot;
+    out.beams.node[d] = ctc_commit_remap(ftab, node, A, lim, W);
+    out.beams.par[d] = node == A ? -1 : ctc_commit_remap(ftab, par, A, lim, W);
+    out.beams.tok[d] = in.beams.tok[s]; out.beams.len[d] = in.beams.len[s];
+    out.beams.h[d] = in.beams.h[s]; out.beams.hp[d] = in.beams.hp[s];
+    int* const fo[4] = {(int*)out.beams.pb, (int*)out.beams.pnb, (int*)out.beams.tot, (int*)out.beams.brank};
+    const int* const fi[4] = {(const int*)in.beams.pb, (const int*)in.beams.pnb, (const int*)in.beams.tot, (const int*)in.beams.brank};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) fo[k][d] = fi[k][s];
+    if constexpr (NM > 0) { out.beams.lm_state[d] = in.beams.lm_state[s]; ((int*)out.beams.lm_sum)[d] = ((const int*)in.beams.lm_sum)[s]; }
+    if constexpr (NM > 1) { out.fs_state[d] = in.fs_state[s]; ((int*)out.fs_sum)[d] = ((const int*)in.fs_sum)[s]; }
+  }
+  if (lane >= nb2 && lane < W) {
+    const int d = b * W + lane;
+    out.beams.node[d] = 0; out.beams.par[d] = -1; out.beams.tok[d] = -1; out.beams.len[d] = 0;
+    out.beams.h[d] = CTC_BEAM_ROOT_HASH; out.beams.hp[d] = 0;
+    ((int*)out.beams.pb)[d] = CTC_NEGINF_BITS; ((int*)out.beams.pnb)[d] = CTC_NEGINF_BITS;
+    ((int*)out.beams.tot)[d] = CTC_NEGINF_BITS; ((int*)out.beams.brank)[d] = CTC_NEGINF_BITS;
+    if constexpr (NM > 0) { out.beams.lm_state[d] = 1; ((int*)out.beams.lm_sum)[d] = 0; }
+    if constexpr (NM > 1) { out.fs_state[d] = 1; ((int*)out.fs_sum)[d] = 0; }
+  }
+  if (lane == 0) {
+    out.beams.nb[b] = nb2; out.beams.frames_done[b] = kept2;
+    wout.tok_base[b] = tbase + n; wout.frame_base[b] = G; wout.kept[b] = kept2;
+    n_com[b] = n;
+  }
+}
+
+// i32 elements of workspace per stream: the frame table [Tcap] and the chain buffer [2 Tcap]
+extern "C" long long mi355x_ctc_beam_commit_workspace_elems(int Tcap, int beam) {
+  return (Tcap <= 0 || beam < 1 || beam > CTC_BEAM_MAX) ? 0 : 3ll * Tcap;
+}
+
+static bool ctc_beam_window_ok(const mi355x_ctc_beam_window* w) { return w && w->tok_base && w->frame_base && w->kept && w->frame_map; }
+
+extern "C" int mi355x_ctc_beam_commit(const mi355x_ctc_beam_fused_state* state_in, const mi355x_ctc_beam_window* window_in,
+                                      const void* tree_in, const mi355x_ctc_beam_fused_state* state_out,
+                                      const mi355x_ctc_beam_window* window_out, void* tree_out, void* com_tokens, void* com_frames,
+                                      void* n_com, void* workspace, int B, int beam, int Tcap, int n_models, int stable_frames,
+                                      void* stream) {
+  mi_clear_errors();
+  if (!state_in || !state_out || !tree_in || !tree_out || !com_tokens || !com_frames || !n_com || !workspace) return MI_ERR_ARG;
+  if (B <= 0 || beam < 1 || beam > CTC_BEAM_MAX || Tcap < 1 || (long long)Tcap * beam > 0x3fffffffll) return MI_ERR_ARG;
+  if (n_models < 0 || n_models > 2 || !ctc_beam_state_ok(state_in, n_models) || !ctc_beam_state_ok(state_out, n_models))
+    return MI_ERR_ARG;
+  if (!ctc_beam_window_ok(window_in) || !ctc_beam_window_ok(window_out)) return MI_ERR_ARG;
+  if (((size_t)tree_in & 7) || ((size_t)tree_out & 7)) return MI_ERR_ARG;
+  // out of place: no array of the result is one of the input
+  if (state_in->beams.node == state_out->beams.node || tree_in == tree_out || window_in->frame_map == window_out->frame_map ||
+      window_in->kept == window_out->kept)
+    return MI_ERR_ARG;
+  const int S = stable_frames < 0 ? -1 : stable_frames;
+#define CTC_COMMIT_LAUNCH(NM)                                                                                                          \
+  MI_LAUNCH((ctc_beam_commit_kernel<NM>), dim3(B), dim3(64), 0, (hipStream_t)stream, *state_in, *window_in, (const int2*)tree_in,      \
+            *state_out, *window_out, (int2*)tree_out, (int*)com_tokens, (int*)com_frames, (int*)n_com, (int*)workspace, beam, Tcap, S)
+  switch (n_models) {
+    case 0: CTC_COMMIT_LAUNCH(0); break;
+    case 1: CTC_COMMIT_LAUNCH(1); break;
+    default: CTC_COMMIT_LAUNCH(2); break;
+  }
+#undef CTC_COMMIT_LAUNCH
+  return mi_check_launch();
 }

@@ -139,7 +139,9 @@ def ctc_beam_stream_hypotheses(decoding, log_probs, chunk_len, previous_hypothes
     global frame each token entered it, length = the best hypothesis' token count, dec_state = (CTCBeamStreamState, row).  The same
     streams in the same order are resumed without a copy; any other selection or order of earlier hypotheses goes through
     `CTCBeamStreamState.gather`.  With the decoding object's `return_best_hypothesis` off, `n_best` holds (text, ids, score) of
-    every hypothesis, best first."""
+    every hypothesis, best first.  With the decoding object's `stream_commit_every` = N the state is committed after every N-th
+    step (`commit_stream`, forced with its `stream_stable_frames`), and `stable_length` counts the leading tokens of y_sequence
+    that are committed: they are in every later hypothesis of the stream."""
     from ..modules import CTCBeamStreamState
     from ..modules.rnnt_decoding import Hypothesis
     state = None
@@ -152,11 +154,18 @@ def ctc_beam_stream_hypotheses(decoding, log_probs, chunk_len, previous_hypothes
             state = CTCBeamStreamState.gather(pairs)
     best_only = decoding.return_best_hypothesis
     hyps, state = decoding.nbest_stream(log_probs, chunk_len, state, best_only=best_only)
+    every = getattr(decoding, "stream_commit_every", None)
+    before = state.committed
+    if every and state.steps % every == 0:
+        _, state = decoding.commit_stream(state, decoding.stream_stable_frames)
     out = []
     for b, hs in enumerate(hyps):
         ids, score, frames = hs[0] if hs else ([], float("-inf"), [])
+        # (a forced commit keeps the best beam of the SEARCH order; where a boosting tree's final term put another one first, this
+        # hypothesis may leave the newly committed text, and what was committed before it is what is final in it)
+        done = state.committed[b][0] if list(state.committed[b][0]) == ids[: len(state.committed[b][0])] else before[b][0]
         hyp = Hypothesis(score=score, y_sequence=torch.tensor(ids, dtype=torch.long), text=decoding.ids_to_text(ids),
-                         timestamp=frames, length=len(ids), dec_state=(state, b))
+                         timestamp=frames, length=len(ids), dec_state=(state, b), stable_length=len(done))
         if not best_only:
             hyp.n_best = [(decoding.ids_to_text(i), i, s) for i, s, _ in hs]
         out.append(hyp)

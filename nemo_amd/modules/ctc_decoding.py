@@ -119,15 +119,39 @@ class CTCBeamStreamState:
     `lm`: the state of an LM-fused search (lm_state / lm_sum are meaningful).  `bound`: an upper bound of the frames consumed -- the
     sum of the T of the steps taken, kept on the host, so that capacity never needs a device read.
     A step never writes the beam arrays of the state it starts from; it appends to the tree.  Stepping one state twice with the
-    same chunk rewrites the same nodes with the same values; two DIFFERENT continuations of one state need a `gather` copy each."""
+    same chunk rewrites the same nodes with the same values; two DIFFERENT continuations of one state need a `gather` copy each.
+    A COMMITTED state (`ops.ctc_beam_commit`, `mi355x_ctc_beam_window`) also carries
+      win        i32 [4, B]       tok_base, frame_base, kept of the window, and the token count of the last commit
+      frame_map  i32 [B, Tcap]    the global frame of the first `kept` tree frames
+      committed  per stream (token ids, global frames): the tokens taken out of the tree so far, on the host
+    (`win` is None for a state that was never committed; its window is all zero).  Its tree is its own, re-rooted and compacted;
+    its `bound` is the largest `kept` of its streams, so its capacity follows the window, not the stream's length, and the n-best
+    buffers hold the TAIL of each hypothesis behind the committed tokens."""
     INT_FIELDS, FLOAT_FIELDS = ("node", "par", "tok", "len", "lm_state"), ("pb", "pnb", "tot", "brank", "lm_sum")
     ROOT_HASH = 0x243F6A8885A308D3
     MAX_NODES = 0x3FFFFFFF   # capacity * W: node ids are 32-bit
 
-    def __init__(self, h64, beams, utt, tree, tokens, tok_frame, lm, bound, fs=None):
+    def __init__(self, h64, beams, utt, tree, tokens, tok_frame, lm, bound, fs=None, win=None, frame_map=None, committed=None,
+                 steps=0):
         self.h64, self.beams, self.utt, self.tree, self.tokens, self.tok_frame = h64, beams, utt, tree, tokens, tok_frame
         self.fs = fs   # i32 [2, B, W] or None: fs_state, fs_sum (float32 bits) of a search with a SECOND fusion model
         self.B, self.W, self.lm, self.bound = int(beams.shape[1]), int(beams.shape[2]), bool(lm), int(bound)
+        self.win, self.frame_map = win, frame_map
+        self.committed = list(committed) if committed is not None else [((), ())] * self.B
+        self.steps = int(steps)   # the steps taken so far (host): what `stream_commit_every` counts
+
+    @property
+    def n_models(self) -> int:
+        return int(self.lm) + (self.fs is not None)
+
+    def window_arrays(self):
+        """name -> the arrays of `mi355x_ctc_beam_window`; of a state that was never committed new all-zero ones (the state is left
+        as it is)"""
+        win, frame_map = self.win, self.frame_map
+        if win is None:
+            i32 = dict(dtype=torch.int32, device=self.device)
+            win, frame_map = torch.zeros(4, self.B, **i32), torch.zeros(self.B, self.capacity, **i32)
+        return dict(tok_base=win[0], frame_base=win[1], kept=win[2], frame_map=frame_map)
 
     @property
     def capacity(self) -> int:
@@ -196,18 +220,23 @@ class CTCBeamStreamState:
         old = self.tree
         self.tree, self.tokens, self.tok_frame = self._buffers(self.B, self.W, cap, self.device)
         self.tree[:, : old.shape[1]] = old
+        if self.frame_map is not None:
+            old, self.frame_map = self.frame_map, torch.zeros(self.B, cap, dtype=torch.int32, device=self.device)
+            self.frame_map[:, : old.shape[1]] = old
         return self
 
     def next(self, T: int):
         """the state a step over T frames writes: new beam arrays (uninitialised), this state's tree and buffers"""
         return CTCBeamStreamState(torch.empty_like(self.h64), torch.empty_like(self.beams), torch.empty_like(self.utt), self.tree,
                                   self.tokens, self.tok_frame, self.lm, self.bound + int(T),
-                                  fs=None if self.fs is None else torch.empty_like(self.fs))
+                                  fs=None if self.fs is None else torch.empty_like(self.fs), win=self.win, frame_map=self.frame_map,
+                                  committed=self.committed, steps=self.steps + 1)
 
     @classmethod
     def gather(cls, pairs):
         """a new state of len(pairs) streams: row i is stream `row` of `state` for the i-th (state, row) -- for a server that drops
-        finished streams or regroups them.  Beams and trees are copied; the new state shares nothing with the old ones."""
+        finished streams or regroups them.  Beams, trees and windows are copied; the new state shares nothing with the old ones.
+        Committed and uncommitted streams mix: an uncommitted stream has the all-zero window."""
         pairs = list(pairs)
         if not pairs:
             raise ValueError("CTC beam stream state: gather of no streams")
@@ -222,8 +251,29 @@ class CTCBeamStreamState:
         for i, (s, r) in enumerate(pairs):
             tree[i, : s.capacity] = s.tree[int(r)]
         pick = lambda name: torch.stack([getattr(s, name)[:, int(r)] for s, r in pairs], dim=1).contiguous()
+        win = frame_map = None
+        if any(s.win is not None for s, _ in pairs):
+            i32 = dict(dtype=torch.int32, device=first.device)
+            win, frame_map = torch.zeros(4, len(pairs), **i32), torch.zeros(len(pairs), cap, **i32)
+            for i, (s, r) in enumerate(pairs):
+                if s.win is not None:
+                    win[:, i], frame_map[i, : s.capacity] = s.win[:, int(r)], s.frame_map[int(r)]
         return cls(pick("h64"), pick("beams"), pick("utt"), tree, tokens, tok_frame, first.lm, max(s.bound for s, _ in pairs),
-                   fs=None if first.fs is None else pick("fs"))
+                   fs=None if first.fs is None else pick("fs"), win=win, frame_map=frame_map,
+                   committed=[s.committed[int(r)] for s, r in pairs], steps=max(s.steps for s, _ in pairs))
+
+
+def _stream_commit_keys(every, stable, what="BeamBatchedCTCDecoder"):
+    """`stream_commit_every` (chunks, >= 1, or None) and `stream_stable_frames` (frames, >= 0, or None; only with the former)"""
+    every = None if every is None else int(every)
+    stable = None if stable is None else int(stable)
+    if every is not None and every < 1:
+        raise ValueError(f"{what}: `stream_commit_every` must be None or >= 1 chunks; got {every}")
+    if stable is not None and stable < 0:
+        raise ValueError(f"{what}: `stream_stable_frames` must be None or >= 0 frames; got {stable}")
+    if stable is not None and every is None:
+        raise ValueError(f"{what}: `stream_stable_frames` without `stream_commit_every` (nothing would ever be committed)")
+    return every, stable
 
 
 class BeamBatchedCTCDecoder(_CTCText):
@@ -236,14 +286,18 @@ class BeamBatchedCTCDecoder(_CTCText):
     `boosting_tree`: a `BoostingTree` of key phrases, fused with weight `boosting_tree_alpha` >= 0 (alone or beside the LM:
     `mi355x_ctc_beam_decode_fused`): the search adds boosting_tree_alpha * boost(sequence) to its rank, and the score returned holds
     the boost of the completed phrases only -- a phrase begun and not finished is not paid for -- with the n-best ordered by it.
-    Every method makes one call with the models there are (`_fusion_models`): none, the LM, the tree, or both."""
+    Every method makes one call with the models there are (`_fusion_models`): none, the LM, the tree, or both.
+    `stream_commit_every` = N (None: never): the streaming step of the models commits the state after every N-th chunk
+    (`commit_stream`), with `stream_stable_frames` = S (None: the exact commit) as the age beyond which a partial result is final."""
 
     confidence_cfg = None   # (the greedy decoder's attribute: confidences are not defined for the beam search)
 
     def __init__(self, vocabulary: Optional[Sequence[str]] = None, blank_id: Optional[int] = None, beam_size: int = 4,
                  return_best_hypothesis: bool = True, beam_threshold: float = 20.0, beam_beta: float = 0.0, ngram_lm=None,
-                 ngram_lm_alpha: float = 0.0, boosting_tree=None, boosting_tree_alpha: float = 0.0):
+                 ngram_lm_alpha: float = 0.0, boosting_tree=None, boosting_tree_alpha: float = 0.0,
+                 stream_commit_every: Optional[int] = None, stream_stable_frames: Optional[int] = None):
         self._set_labels(vocabulary, blank_id)
+        self.stream_commit_every, self.stream_stable_frames = _stream_commit_keys(stream_commit_every, stream_stable_frames)
         self.boosting_tree, self.boosting_tree_alpha = boosting_tree, float(boosting_tree_alpha)
         if not self.boosting_tree_alpha >= 0:
             raise ValueError(f"boosting_tree_alpha must be >= 0; got {boosting_tree_alpha}")
@@ -299,7 +353,9 @@ class BeamBatchedCTCDecoder(_CTCText):
         streams) -> (the n-best of all frames so far, or None with emit=False; the next state).  The n-best is `decode_ids`'
         tuple with tokens / tok_frame i32 [B, W, capacity] in the state's buffers: NOT padded, valid up to hyp_len, overwritten by
         the next step; tok_frame counts from the stream's first frame.  Any cut of a stream into chunks gives the bits of
-        `decode_ids` over all of it."""
+        `decode_ids` over all of it.  Of a COMMITTED state (`commit_stream`) the buffers hold the TAIL of each hypothesis -- the
+        tokens behind `state.committed`, hyp_len their number -- with global frames and the whole hypothesis' score; `nbest_stream`
+        puts the two together."""
         _check_log_probs(log_probs)
         lp = log_probs.to(torch.float32).contiguous()
         lens = lengths.to(torch.int64).contiguous() if lengths is not None else None
@@ -309,15 +365,31 @@ class BeamBatchedCTCDecoder(_CTCText):
 
     def nbest_stream(self, log_probs, lengths=None, state=None, best_only: bool = False):
         """`decode_stream` to host lists: per stream the (token ids, score, global frame of each token) of its hypotheses so far,
-        best first (best_only: the first one alone), and the next state.  The D2H copy is the hypotheses up to the longest one."""
+        best first (best_only: the first one alone), and the next state.  The D2H copy is the hypotheses up to the longest one; of a
+        committed state their tails, in front of which the committed tokens the state keeps on the host are put: the hypotheses
+        are whole either way."""
         (tokens, tok_frame, hyp_len, score, n_hyp), nxt = self.decode_stream(log_probs, lengths, state, emit=True)
         hyp_len, score, n_hyp = hyp_len.cpu(), score.cpu(), n_hyp.cpu()
         K = 1 if best_only else int(n_hyp.max())
         L = int(hyp_len[:, :K].max()) if K else 0
         tokens, tok_frame = tokens[:, :K, :L].cpu(), tok_frame[:, :K, :L].cpu()
-        out = [[(tokens[b, k, : int(hyp_len[b, k])].tolist(), float(score[b, k]), tok_frame[b, k, : int(hyp_len[b, k])].tolist())
+        done = [(list(ids), list(frames)) for ids, frames in nxt.committed]
+        out = [[(done[b][0] + tokens[b, k, : int(hyp_len[b, k])].tolist(), float(score[b, k]),
+                 done[b][1] + tok_frame[b, k, : int(hyp_len[b, k])].tolist())
                 for k in range(min(K, int(n_hyp[b])))] for b in range(tokens.shape[0])]
         return out, nxt
+
+    def commit_stream(self, state: CTCBeamStreamState, stable_frames: Optional[int] = None):
+        """commit what the live hypotheses of every stream agree on (`ops.ctc_beam_commit`): -> (per stream the NEWLY committed
+        (token ids, global frames), the next state), whose tree holds only what is still open.  stable_frames None: the exact
+        commit -- every later result is what it would have been.  stable_frames = S: partial-result stabilisation -- the beams that
+        differ from the best one in anything older than S frames are dropped first, so the text older than S frames is final and
+        the tree holds at most S frames.  A dropped beam is identified by its node: one that spells the same old text under another
+        node goes too.  The beam that always survives is the best one of the SEARCH order.  With a boosting tree the n-best is
+        ordered by the scores with the final terms, so the hypothesis shown first at the step of a forced commit can be a beam that
+        commit drops: that one hypothesis may leave the newly committed text (the models' `stable_length` then counts what was
+        committed before it); every later n-best starts with all that is committed."""
+        return ops.ctc_beam_commit(state, stable_frames)
 
     def __call__(self, log_probs, lengths=None):
         texts = [[self.ids_to_text(ids) for ids, _ in hyps] for hyps in self.nbest(log_probs, lengths)]
@@ -408,8 +480,9 @@ def ctc_decoder_from_config(decoding_cfg, vocabulary=None, what: str = "CTC", te
     vocabulary, returns its decoding object -- GreedyCTCDecoder for `greedy` / `greedy_batch`, BeamBatchedCTCDecoder for
     `beam_batch` (its `beam` sub-section: beam_size, return_best_hypothesis, beam_threshold, beam_beta, ngram_lm_arpa,
     ngram_lm_alpha, ngram_lm_token_offset, boosting_tree, boosting_tree_alpha: `_boosting_tree_from_config`, whose phrases
-    `text_to_ids` tokenises).  Everything else the reference knows (beam = pyctcdecode / KenLM, flashlight, wfst:
-    ctc_decoding.py:231-236), its keys for KenLM / .nemo language models, and an LM weight without an LM raise NotImplementedError."""
+    `text_to_ids` tokenises; stream_commit_every, stream_stable_frames: `_stream_commit_keys`, both None by default).
+    Everything else the reference knows (beam = pyctcdecode / KenLM, flashlight, wfst: ctc_decoding.py:231-236), its keys for
+    KenLM / .nemo language models, and an LM weight without an LM raise NotImplementedError."""
     dcfg = dict(decoding_cfg or {})
     strategy = str(dcfg.get("strategy", "greedy_batch"))
     if strategy in ("greedy", "greedy_batch"):
@@ -425,12 +498,14 @@ def ctc_decoder_from_config(decoding_cfg, vocabulary=None, what: str = "CTC", te
         raise NotImplementedError(f"{what} decoding: `confidence_cfg` with strategy 'beam_batch' (confidences come from the greedy search)")
     lm = _ngram_lm_from_config(beam, vocabulary, what)
     tree, tree_alpha = _boosting_tree_from_config(beam, vocabulary, what, text_to_ids)
+    every, stable = _stream_commit_keys(beam.get("stream_commit_every"), beam.get("stream_stable_frames"), f"{what} decoding")
     if vocabulary is None:
         return None
     return BeamBatchedCTCDecoder(vocabulary=list(vocabulary), beam_size=beam.get("beam_size", 4),
                                  return_best_hypothesis=beam.get("return_best_hypothesis", True),
                                  beam_threshold=beam.get("beam_threshold", 20.0), beam_beta=beam.get("beam_beta", 0.0),
-                                 ngram_lm=lm, ngram_lm_alpha=alpha, boosting_tree=tree, boosting_tree_alpha=tree_alpha)
+                                 ngram_lm=lm, ngram_lm_alpha=alpha, boosting_tree=tree, boosting_tree_alpha=tree_alpha,
+                                 stream_commit_every=every, stream_stable_frames=stable)
 
 
 def ctc_offsets(tokens: Sequence[str], starts: Sequence[int], ends: Sequence[int], word_pieces: bool = False):

@@ -57,6 +57,7 @@ class Hypothesis:  # parts/utils/rnnt_utils.py:35-110 (the fields greedy decodin
     token_confidence: Optional[List[float]] = None   # one value per label of y_sequence
     word_confidence: Optional[List[float]] = None    # one value per word of the text
     n_best: Optional[list] = None   # streaming CTC beam search with return_best_hypothesis off: (text, ids, score), best first
+    stable_length: int = 0   # streaming CTC beam search: the leading tokens of y_sequence that are committed (final); monotone
 
 
 class GreedyBatchedRNNTInfer:

@@ -513,6 +513,17 @@ class _CTCBeamFusedStateC(C.Structure):   # mi355x_ctc_beam_fused_state
                    fs_sum=_ptr(a["fs_sum"]) if "fs_sum" in a else None)
 
 
+class _CTCBeamWindowC(C.Structure):   # mi355x_ctc_beam_window
+    _fields_ = [(n, C.c_void_p) for n in ("tok_base", "frame_base", "kept", "frame_map")]
+
+    @classmethod
+    def of(cls, state):
+        a = state.window_arrays()
+        w = cls(**{n: _ptr(t) for n, t in a.items()})
+        w.keep = a   # (an uncommitted state's all-zero window lives as long as the record)
+        return w
+
+
 def _ctc_beam_lm_check(what, lm, logp):
     """`lm` of the entries that take one n-gram model: an NGramLM over the labels of `logp`"""
     from .modules.ngram_lm import NGramLM
@@ -595,7 +606,8 @@ def _ctc_beam_search(what, logp, lens, blank, beam_size, beam_threshold, beam_be
 
 def _ctc_beam_search_stream(what, logp, lens, blank, beam_size, beam_threshold, beam_beta, state, models, emit):
     """one chunk of the resumable search behind every public entry (mi355x_ctc_beam_decode_stream without a model, else
-    mi355x_ctc_beam_decode_fused_stream): `_ctc_beam_search`'s arguments, `state` a CTCBeamStreamState of this batch, width and model
+    mi355x_ctc_beam_decode_fused_stream; from a committed state mi355x_ctc_beam_decode_window_stream, whose n-best holds the tails
+    behind `state.committed`): `_ctc_beam_search`'s arguments, `state` a CTCBeamStreamState of this batch, width and model
     count (None: fresh streams) -> (the n-best so far in the state's buffers, or None with emit=False; the next state)"""
     from .modules.ctc_decoding import CTCBeamStreamState
     B, T, C_ = logp.shape
@@ -614,10 +626,54 @@ def _ctc_beam_search_stream(what, logp, lens, blank, beam_size, beam_threshold, 
     arr, keep = _ctc_beam_fusion_array(models, logp)
     entry, fusion = ((lib.mi355x_ctc_beam_decode_fused_stream, (C.cast(arr, C.c_void_p), len(arr))) if models else
                      (lib.mi355x_ctc_beam_decode_stream, ()))
+    window = ()
+    if state.win is not None:   # a committed state: the search that reads its window (the outputs hold the tails)
+        entry, fusion = lib.mi355x_ctc_beam_decode_window_stream, (C.cast(arr, C.c_void_p) if models else None, len(arr))
+        win = _CTCBeamWindowC.of(state)
+        window = (C.byref(win),)
     s_in, s_out = _CTCBeamFusedStateC.of(state), _CTCBeamFusedStateC.of(nxt)   # (the model-less entry's state is its first member)
     check(entry(_ptr(logp), _ptr(lens), _ptr(state.tree), *((_ptr(t) for t in outs) if emit else (None,) * 5), B, T, C_, int(blank), W,
-                float(beam_threshold), float(beam_beta), *fusion, state.capacity, C.byref(s_in), C.byref(s_out), _stream()), what)
+                float(beam_threshold), float(beam_beta), *fusion, state.capacity, C.byref(s_in), C.byref(s_out), *window, _stream()),
+          what)
     return outs, nxt
+
+
+def ctc_beam_commit(state, stable_frames=None):
+    """commit the stable prefix of every stream of `state` (a `modules.CTCBeamStreamState`; mi355x_ctc_beam_commit, which
+    include/mi355x_asr.h states): the tokens every live hypothesis shares leave the tree, which is re-rooted and compacted into a
+    new tree of the same capacity.  `stable_frames` = S >= 0 forces it: only the beams that agree with the best one on everything
+    older than S frames survive, and at most S frames stay in the tree.  None: the exact commit, which changes no result.
+    -> ([(token ids, global frames)] newly committed per stream, the committed state).  Out of place: `state` stays what it was.
+    One D2H copy of [4, B] integers (the window and the counts, from which the new state's host `bound` is taken) and one of the
+    new tokens."""
+    from .modules.ctc_decoding import CTCBeamStreamState
+    S = -1 if stable_frames is None else int(stable_frames)
+    if S < -1:
+        raise ValueError(f"ctc_beam_commit: stable_frames must be None or >= 0; got {stable_frames}")
+    B, W, cap, dev_ = state.B, state.W, state.capacity, state.device
+    i32 = dict(dtype=torch.int32, device=dev_)
+    out = CTCBeamStreamState(torch.empty_like(state.h64), torch.empty_like(state.beams), torch.empty_like(state.utt),
+                             torch.empty_like(state.tree),   # (only the frames the commit keeps, then the search's, are ever read)
+                             state.tokens, state.tok_frame, state.lm, 0, fs=None if state.fs is None else torch.empty_like(state.fs),
+                             win=torch.empty(4, B, **i32), frame_map=torch.empty(B, cap, **i32), steps=state.steps)
+    com = torch.empty(2, B, cap, **i32)
+    ws = torch.empty(B * max(1, int(lib.mi355x_ctc_beam_commit_workspace_elems(cap, W))), **i32)
+    s_in, s_out = _CTCBeamFusedStateC.of(state), _CTCBeamFusedStateC.of(out)
+    w_in, w_out = _CTCBeamWindowC.of(state), _CTCBeamWindowC.of(out)
+    check(lib.mi355x_ctc_beam_commit(C.byref(s_in), C.byref(w_in), _ptr(state.tree), C.byref(s_out), C.byref(w_out), _ptr(out.tree),
+                                     _ptr(com[0]), _ptr(com[1]), _ptr(out.win[3]), _ptr(ws), B, W, cap, state.n_models, S, _stream()),
+          "ctc_beam_commit")
+    head = out.win.cpu()
+    out.bound = int(head[2].max())
+    n_max = int(head[3].max())
+    new = com[:, :, :n_max].cpu() if n_max else None
+    fresh, out.committed = [], []
+    for b in range(B):
+        n = int(head[3, b])
+        ids, frames = (tuple(new[0, b, :n].tolist()), tuple(new[1, b, :n].tolist())) if n else ((), ())
+        fresh.append((list(ids), list(frames)))
+        out.committed.append((tuple(state.committed[b][0]) + ids, tuple(state.committed[b][1]) + frames))
+    return fresh, out
 
 
 def ctc_beam_decode(logp, lens, blank, beam_size, beam_threshold=20.0, beam_beta=0.0):

@@ -19,6 +19,13 @@ that drift of the box hits all of them alike:
   * with `--boost N` mi355x_ctc_beam_decode_fused with a boosting tree of N key phrases (runs of 2..4 tokens cut from the arg-max
     paths of the input itself, so that they are begun and completed) at `--boost-alpha`, alone and, with --lm, beside the n-gram
     model (two fusion models); with --lm and --lib also mi355x_ctc_beam_decode_lm of the other builds.
+  * with --stream and --lib also the resumable entries of the other builds, alternating with the in-tree library's.
+  * with `--commit` (instead of all of the above; profiles/ctc_beam_commit.md is made with it) mi355x_ctc_beam_commit alone, on the
+    states that `--commit-windows` frames of the stream leave, exact and forced with `--stable-frames`; and the whole stream through
+    the decoding object (`nbest_stream`: search, chase and the D2H copy of the n-best) in chunks of --stream frames (14 if not
+    given), without a commit and with `commit_stream` after every `--commit-every`-th chunk: wall time per step (host lists
+    included) at the head (steps 3 to 8) and at the tail (the six steps before the last) of the stream, the D2H bytes of those
+    steps, between device events the step's search alone and what chasing the n-best out adds, and the capacity the tree ended with.
 Input: log-softmax of 1.5 * N(0,1) with +5 on the class of a random path (blank with probability 0.6), the generator of the tests --
 peaked like a trained model's output, so that the threshold prunes; lengths = T.  The launches of a candidate per round are sized
 from one timed launch so that a round of it takes about `--round-ms`.  Reported per candidate: median, min and max of the
@@ -27,6 +34,7 @@ per-round means, in microseconds per launch.
     python tools/ctc_beam_bench.py [--shapes 32,501,129 32,501,1025] [--beams 4 16 64] [--thresholds 20 inf] [--rounds 7]
                                    [--lm ORDER] [--alpha 0.5] [--stream CHUNK] [--boost N] [--boost-alpha 1.0]
                                    [--lib parent=PATH ...] [--json OUT]
+                                   [--commit [--commit-windows 28 280] [--stable-frames 28] [--commit-every 2]]
 """
 import argparse
 import ctypes
@@ -35,6 +43,7 @@ import os
 import statistics
 import sys
 import tempfile
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
@@ -43,12 +52,13 @@ dev = "cuda"
 GREEDY = ("mi355x_ctc_greedy_decode", "mi355x_ctc_greedy_decode_ts")
 BEAM = "mi355x_ctc_beam_decode"
 BEAM_LM = "mi355x_ctc_beam_decode_lm"
+STREAMED = ("mi355x_ctc_beam_decode_stream", "mi355x_ctc_beam_decode_lm_stream")
 
 
 def load(path):
     from nemo_amd import _lib
     lib = ctypes.CDLL(path)
-    for name in GREEDY + (BEAM, BEAM_LM):
+    for name in GREEDY + (BEAM, BEAM_LM) + STREAMED:
         getattr(lib, name).argtypes = _lib.SIGNATURES[name]
         getattr(lib, name).restype = ctypes.c_int
     return lib
@@ -170,8 +180,8 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, 
     chunks = [logp[:, t:t + chunk].contiguous() for t in range(0, T, chunk)] if chunk else []
     chunk_lens = {n: torch.full((B,), n, dtype=torch.int64, device=dev) for n in {c.shape[1] for c in chunks}}
 
-    def streamed(W, th, emit_all, a=None):
-        """the utterances in chunks through the resumable entry: two states written in turn, a tree of T frames"""
+    def streamed(W, th, emit_all, a=None, lib=lib):
+        """the utterances in chunks through the resumable entry (of `lib`): two states written in turn, a tree of T frames"""
         from nemo_amd.modules import CTCBeamStreamState
         from nemo_amd.ops import _CTCBeamStateC
         st = [CTCBeamStreamState.fresh(B, W, dev, capacity=T, lm=a is not None) for _ in range(2)]
@@ -223,8 +233,12 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, 
                 for emit_all in (True, False):
                     tag = f"W={W} threshold={th} chunk={chunk} emit={'all' if emit_all else 'last'}"
                     cands[f"stream {tag}"] = streamed(W, th, emit_all)
+                    for name, l in libs.items():
+                        cands[f"stream[{name}] {tag}"] = streamed(W, th, emit_all, lib=l)
                     if lm:
                         cands[f"stream+lm {tag} alpha={alpha}"] = streamed(W, th, emit_all, alpha)
+                        for name, l in libs.items():
+                            cands[f"stream+lm[{name}] {tag} alpha={alpha}"] = streamed(W, th, emit_all, alpha, lib=l)
     row = dict(shape=dict(B=B, T=T, C=C), **rounds(cands, n_rounds, round_ms))
     if lm:
         row["lm"] = dict(order=lm.order, states=lm.num_states, arcs=lm.num_arcs, lm_ub=lm.lm_ub)
@@ -252,6 +266,85 @@ def one_shape(B, T, C, beams, thresholds, libs, n_rounds, round_ms, lm_order=0, 
     return row
 
 
+def commit_shape(B, T, C, beams, n_rounds, round_ms, chunk, windows, stable, every):
+    """--commit: the kernel alone on the states of `windows` frames, and the stream with and without commits"""
+    from nemo_amd import _lib, ops
+    from nemo_amd.modules import BeamBatchedCTCDecoder, CTCBeamStreamState
+    from nemo_amd.ops import _CTCBeamFusedStateC, _CTCBeamWindowC
+    lib = _lib.lib
+    logp = make_logp(B, T, C)
+    stream = torch.cuda.current_stream().cuda_stream
+    p = lambda t: t.data_ptr()   # noqa: E731
+    i32 = dict(dtype=torch.int32, device=dev)
+    row, cands, notes = dict(shape=dict(B=B, T=T, C=C)), {}, {}
+    for W in beams:
+        for n in windows:
+            n = min(n, T)
+            _, st = ops.ctc_beam_decode_stream(logp[:, :n].contiguous(), None, C - 1, W, 20.0, 0.0,
+                                               CTCBeamStreamState.fresh(B, W, dev, capacity=n), emit=False)
+            for S in (-1, stable):
+                out = CTCBeamStreamState.fresh(B, W, dev, capacity=n)
+                out.win, out.frame_map = torch.zeros(4, B, **i32), torch.zeros(B, n, **i32)
+                com, ws = torch.empty(2, B, n, **i32), torch.empty(B * int(lib.mi355x_ctc_beam_commit_workspace_elems(n, W)), **i32)
+                args = (_CTCBeamFusedStateC.of(st), _CTCBeamWindowC.of(st), _CTCBeamFusedStateC.of(out), _CTCBeamWindowC.of(out))
+
+                def fn(st=st, out=out, com=com, ws=ws, args=args, W=W, n=n, S=S):
+                    rc = lib.mi355x_ctc_beam_commit(ctypes.byref(args[0]), ctypes.byref(args[1]), p(st.tree), ctypes.byref(args[2]),
+                                                    ctypes.byref(args[3]), p(out.tree), p(com[0]), p(com[1]), p(out.win[3]), p(ws), B, W,
+                                                    n, 0, S, stream)
+                    assert rc == 0, rc
+                key = f"commit W={W} window={n} {'exact' if S < 0 else f'stable={S}'}"
+                cands[key] = fn
+                fn()
+                torch.cuda.synchronize()
+                notes[key] = dict(kept_max=int(out.win[2].max()), committed_mean=float(out.win[3].float().mean()),
+                                  nb_mean=float(out.utt[0].float().mean()))
+    row.update(rounds(cands, n_rounds, round_ms))
+    for k, v in notes.items():
+        row[k].update(v)
+    # the whole stream through the decoding object
+    chunks = [logp[:, t:t + chunk].contiguous() for t in range(0, T, chunk)]
+    for W in beams:
+        dec = BeamBatchedCTCDecoder(vocabulary=[str(i) for i in range(C - 1)], beam_size=W, return_best_hypothesis=False)
+        for tag, commit in (("plain", False), (f"commit_every={every} stable={stable}", True)):
+            per_round = []
+            for r in range(n_rounds + 1):   # (round 0: warm-up)
+                state, steps, d2h, search, chase = None, [], [], [], []
+                for i, c in enumerate(chunks):
+                    # on the device alone (a step is out of place, so it can be repeated): the search of this step without and
+                    # with the n-best chased out
+                    quiet = timed(lambda: dec.decode_stream(c, None, state, emit=False), 3)
+                    search.append(quiet)
+                    chase.append(timed(lambda: dec.decode_stream(c, None, state, emit=True), 3) - quiet)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    hyps, state = dec.nbest_stream(c, None, state)
+                    # what nbest_stream copied: two [B, K, L] slices (L: the longest tail) and hyp_len, score, n_hyp
+                    tail = max(len(ids) - len(state.committed[b][0]) for b, h in enumerate(hyps) for ids, _, _ in h)
+                    nbytes = 2 * 4 * B * max(len(h) for h in hyps) * tail + 4 * B * (2 * W + 1)
+                    if commit and (i + 1) % every == 0:
+                        new, state = dec.commit_stream(state, stable)
+                        nbytes += 4 * 4 * B + 2 * 4 * B * max(len(x[0]) for x in new)
+                    torch.cuda.synchronize()
+                    steps.append((time.perf_counter() - t0) * 1e6)
+                    d2h.append(nbytes)
+                if r:
+                    per_round.append(dict(total_ms=sum(steps) / 1e3, head_us=statistics.mean(steps[2:8]), tail_us=statistics.mean(steps[-7:-1]),
+                                          d2h_head=statistics.mean(d2h[2:8]), d2h_tail=statistics.mean(d2h[-7:-1]),
+                                          search_head=statistics.mean(search[2:8]), search_tail=statistics.mean(search[-7:-1]),
+                                          chase_head=statistics.mean(chase[2:8]), chase_tail=statistics.mean(chase[-7:-1])))
+            med = lambda k: round(statistics.median(x[k] for x in per_round), 1)   # noqa: E731
+            row[f"stream W={W} chunk={chunk} {tag}"] = dict(
+                total_ms=med("total_ms"), total_ms_min=round(min(x["total_ms"] for x in per_round), 1),
+                total_ms_max=round(max(x["total_ms"] for x in per_round), 1), step_us_head=med("head_us"), step_us_tail=med("tail_us"),
+                d2h_bytes_head=med("d2h_head"), d2h_bytes_tail=med("d2h_tail"), capacity=state.capacity,
+                search_us_head=med("search_head"), search_us_tail=med("search_tail"), chase_us_head=med("chase_head"),
+                chase_us_tail=med("chase_tail"),
+                chase_us_tail_range=[round(f(x["chase_tail"] for x in per_round), 1) for f in (min, max)],
+                committed_mean=statistics.mean(len(x[0]) for x in state.committed))
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=["32,501,129", "32,501,1025"])
@@ -264,6 +357,10 @@ def main():
     ap.add_argument("--stream", type=int, default=0, metavar="CHUNK", help="also time the resumable search over chunks of CHUNK frames")
     ap.add_argument("--boost", type=int, default=0, metavar="N", help="also time the search with a boosting tree of N key phrases")
     ap.add_argument("--boost-alpha", type=float, default=1.0, help="the weight of the --boost runs")
+    ap.add_argument("--commit", action="store_true", help="time mi355x_ctc_beam_commit and the stream with and without commits")
+    ap.add_argument("--commit-windows", nargs="+", type=int, default=[28, 280], help="frames in the tree when the commit is timed")
+    ap.add_argument("--stable-frames", type=int, default=28)
+    ap.add_argument("--commit-every", type=int, default=2)
     ap.add_argument("--lib", nargs="*", default=[], help="name=path of further builds of the library")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -271,6 +368,12 @@ def main():
     out = dict(device=torch.cuda.get_device_name(0), rounds=args.rounds, round_ms=args.round_ms, shapes=[])
     for s in args.shapes:
         B, T, C = (int(x) for x in s.split(","))
+        if args.commit:
+            row = commit_shape(B, T, C, args.beams, args.rounds, args.round_ms, args.stream or 14, args.commit_windows, args.stable_frames,
+                               args.commit_every)
+            out["shapes"].append(row)
+            print(json.dumps(row), flush=True)
+            continue
         row = one_shape(B, T, C, args.beams, args.thresholds, libs, args.rounds, args.round_ms, args.lm, args.alpha, args.stream, args.boost,
                         args.boost_alpha)
         out["shapes"].append(row)

@@ -1029,6 +1029,45 @@ int mi355x_tdt_greedy_decode_stream_conf(const void* enc_proj, int f_dtype, long
                                          const mi355x_rnnt_stream_state* state_out, void* tok_conf, int method, int norm,
                                          float alpha, float k0, float k1, float k2, void* stream);
 
+/* ---- the greedy searches with shallow fusion: one or two fusion models, the automata of mi355x_ctc_beam_fusion above (an n-gram
+ * model: six tables; a boosting tree: the six and state_final).  ONE entry for the four searches: the arguments of
+ * mi355x_tdt_greedy_decode (D = 0 with durations NULL: the RNN-T search), then the models and the two states (both NULL: the
+ * one-shot search; state_out given: the resumable search, state_in NULL = fresh streams).  The tables cover the labels 0 .. V1-2,
+ * so blank == V1-1 is required.  `ub` is not read: this search has no early-outs.
+ * Each stream keeps one automaton state per model; a fresh stream starts every model in state 1.  One step on frame t with the
+ * label logits lg[0 .. V1):
+ *   mi = the arg-max of lg (first maximum), as in the searches above.  mi == blank: the step is theirs -- the models never turn a
+ *   blank into a label.  Otherwise the emitted label is the arg-max over v != blank (first maximum) of
+ *     rank_v = ((lg[v] - lg[mi]) + alpha_0 * look_0(state_0, v)) + alpha_1 * look_1(state_1, v)
+ *   in float32, in that association, each product rounded before it is added; look_m(s, v) is the look-up of model m from state s
+ *   (ln p(v | s) of an n-gram model, the boost increment of a tree).  Every model then moves to the state behind the emitted label.
+ *   TDT: the duration stays the arg-max of the duration logits; max_symbols, the jumps, skip and zero_run are unchanged.
+ * Score: per emitted label k the running score gains (((lg[k] - lg[mi]) - log se) + alpha_0 * l_0) + alpha_1 * l_1, se = the sum of
+ * exp(lg[v] - lg[mi]) over the V1 labels and l_m = look_m(state_m, k).  The `score` output is the running score with
+ * alpha_m * state_final_m[state_m] added in model order wherever that table is given: the boost of a phrase that was begun and not
+ * finished is taken back, as in the CTC search.  The stream state carries the running score WITHOUT those terms, so any cut into
+ * chunks gives the bits of one launch -- tokens, frames, lengths, score, h / c and every field of the state -- and with every
+ * alpha = 0 all of them are the bits of the entries without models.  Parity with the reference's fused scores is not claimed: this
+ * paragraph is the rule.
+ * State: the resumable search's, and m_state i32 [B, 2], the automaton state of model m in column m (fresh stream: 1; column 1 is
+ * neither read nor written with one model).  score, h_out / c_out as in the one-shot entries, optional in both forms.
+ * MI_ERR_ARG for what the siblings refuse, n_models outside 1..2, a null `models`, per model a null table (state_final may be
+ * null), n_states < 2, n_arcs < V1-1, alpha < 0 or NaN; blank != V1-1; a state with a null m_state; state_in without state_out;
+ * aliased states. */
+typedef struct mi355x_rnnt_fused_state {
+  mi355x_rnnt_stream_state s;
+  int* m_state;
+} mi355x_rnnt_fused_state;
+int mi355x_transducer_greedy_decode_fused(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
+                                          const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
+                                          const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+                                          const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
+                                          int H, int V1, int D, const int* durations, int blank, int max_symbols, void* tokens,
+                                          void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out,
+                                          const mi355x_ctc_beam_fusion* models, int n_models,
+                                          const mi355x_rnnt_fused_state* state_in, const mi355x_rnnt_fused_state* state_out,
+                                          void* stream);
+
 /* ---- cache-aware streaming inference (ConformerEncoder.cache_aware_stream_step; the `update_cache` paths of
  * RelPositionMultiHeadAttention and CausalConv1D).  Caches are f32 in the reference's layouts; in bf16 compute they hold the
  * bf16-rounded operands widened to f32, so a streamed chunk reads the same operand values as the offline forward.

@@ -231,6 +231,10 @@ SIGNATURES = {
     "mi355x_tdt_greedy_decode_stream_conf": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32,
                                              i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32,
                                              vp],
+    # mi355x_tdt_greedy_decode's arguments, then (models: mi355x_ctc_beam_fusion[n_models], n_models, state_in, state_out: pointers
+    # to mi355x_rnnt_fused_state, stream)
+    "mi355x_transducer_greedy_decode_fused": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32,
+                                              i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp],
     "mi355x_stream_cache_assemble": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi355x_stream_attn": [vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "mi355x_stream_dwconv": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],

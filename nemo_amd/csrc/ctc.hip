@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "ctc_beam_fusion.h"
 #include "mi355x_asr.h"
 
 #define NEGINF (-INFINITY)
@@ -953,43 +954,11 @@ __device__ __forceinline__ float ctc_up1f(float v) { return __int_as_float(ctc_u
 // arrays)
 template <class T, int NM> struct ctc_beam_per_model { T v[NM]; };
 template <class T> struct ctc_beam_per_model<T, 0> {};
-// a fusion model: the six tables of the back-off automaton, the fusion weight, the upper bound of a look-up and the nullable
-// `state_final` table
-struct ctc_beam_lm {
-  const int* arc_begin; const int* arc_tok; const float* arc_logp; const int* arc_next; const float* bo; const int* bo_next;
-  int n_states, n_arcs;
-  float alpha, ub;
-  const float* fin;
-};
+// (a fusion model, `ctc_beam_lm`, with `ctc_beam_alpha_lm` and `ctc_beam_lm_lookup`: ctc_beam_fusion.h)
 // the models of a kernel.  The kernels with the output's final terms take room for two whatever NM (the second slot is not read at
 // NM = 1): where the stream record lands in the argument block decides how its scalar loads are grouped and which SGPRs spill, and
 // the resumable one-model kernel measured 0.6 to 0.9 % slower behind a one-model record (profiles/ctc_beam_unify.md)
 template <int NM, bool FINAL> using ctc_beam_models = ctc_beam_per_model<ctc_beam_lm, (FINAL ? 2 : NM)>;
-__device__ __forceinline__ float ctc_beam_alpha_lm(float alpha, float lm) {
-  float al = alpha * lm;
-  asm volatile("" : "+v"(al));   // rounded on its own, like beta * len
-  return al;
-}
-// ln p(c | state s) and the state behind it: while c is not among the arcs of s, add the back-off of s and go to its suffix state
-__device__ __forceinline__ float ctc_beam_lm_lookup(const ctc_beam_lm& lm, int s, int c, int& next) {
-  float acc = 0.f;
-  for (int n = 0; n < lm.n_states; ++n) {
-    s = min(max(s, 0), lm.n_states - 1);
-    if (s == 0) break;
-    int lo = min(max(lm.arc_begin[s], 0), lm.n_arcs);
-    const int end = min(max(lm.arc_begin[s + 1], lo), lm.n_arcs);
-    int hi = end;
-    for (int k = 0; k < 32 && lo < hi; ++k) {
-      const int mid = (lo + hi) >> 1;
-      if (lm.arc_tok[mid] < c) lo = mid + 1; else hi = mid;
-    }
-    if (lo < end && lm.arc_tok[lo] == c) { next = lm.arc_next[lo]; return acc + lm.arc_logp[lo]; }
-    acc += lm.bo[s];
-    s = lm.bo_next[s];
-  }
-  next = lm.arc_next[c];   // state 0: the arc index is the label (0 <= c < C-1 <= n_arcs)
-  return acc + lm.arc_logp[c];
-}
 // candidate (r, k) goes in front of (wr, wk)
 __device__ __forceinline__ bool ctc_beam_beats(float r, int k, float wr, int wk) { return r > wr || (r == wr && k < wk); }
 // the loop over the models, unrolled by the preprocessor: the body once per model k < NM (<= 2), in model order, with k a constant

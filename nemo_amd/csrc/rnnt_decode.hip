@@ -26,6 +26,7 @@
 // chunks takes the same decisions with the same arithmetic as one launch over the whole sequence: tokens, frame indices,
 // lengths, score and final state are bit-identical.  The one-shot entry points are the fresh-state case.
 #include "common.h"
+#include "ctc_beam_fusion.h"
 #include "mi355x_asr.h"
 #include "tdt.h"
 
@@ -74,14 +75,30 @@ struct RnntDecP {
 struct RnntDecPC : RnntDecP {
   float* tok_conf; MiConf conf;
 };
-template <bool CONF> struct RnntDecArg { typedef RnntDecP t; };
-template <> struct RnntDecArg<true> { typedef RnntDecPC t; };
+// the parameter block of the NM > 0 instantiations (the fused search): the first one, the fusion models (room for two whatever
+// NM; the second slot is not read at NM = 1) and the per-stream automaton states [B, 2] to start from (null: fresh streams, every
+// model in state 1) and to write (null: none)
+struct RnntDecPF : RnntDecP {
+  ctc_beam_lm lm[2];
+  const int* ms_in; int* ms_out;
+};
+template <bool CONF, int NM = 0> struct RnntDecArg { typedef RnntDecP t; };
+template <> struct RnntDecArg<true, 0> { typedef RnntDecPC t; };
+template <> struct RnntDecArg<false, 1> { typedef RnntDecPF t; };
+template <> struct RnntDecArg<false, 2> { typedef RnntDecPF t; };
 
 // STREAM = false is the one-shot search: the state code folds away at compile time and the instantiation is the kernel the
 // one-shot entry points have always launched.  CONF = false likewise: the sums of the confidence measure, their two block
 // reductions and the store in `emit` exist in the CONF = true instantiations alone (the *_conf entry points).
-template <typename WT, bool TDT, bool STREAM, bool CONF>
-__global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDecArg<CONF>::t p) {
+//
+// NM = the number of fusion models (mi355x_transducer_greedy_decode_fused; STREAM = true, CONF = false only: a one-shot call is a
+// fresh stream with no state to write).  NM = 0 is the search without models: everything below that names a model sits behind
+// `if constexpr (NM > 0)` and those instantiations are the kernels they were.  With models a step whose arg-max is a label picks
+// the label by rank_v = ((lg[v] - lg[mi]) + alpha_0 * look_0(state_0, v)) + alpha_1 * look_1(state_1, v) over v != blank (a blank
+// arg-max stays a blank: the models never turn a blank into a label); the states are uniform over the workgroup.
+template <typename WT, bool TDT, bool STREAM, bool CONF, int NM = 0>
+__global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDecArg<CONF, NM>::t p) {
+  static_assert(NM == 0 || (STREAM && !CONF && NM <= 2), "the fused search is the resumable one, without confidences");
   extern __shared__ __attribute__((aligned(16))) float rd_smem[];
   const int H = p.H, J = p.J, V1 = p.V1;
   float* x = rd_smem;            // [H] embedding of the last emitted label
@@ -102,6 +119,17 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
   const bool resume = STREAM && p.sin.h != nullptr;
   int last = p.blank, frames_done = 0, skip = 0, same = 0;
   float score = 0.f;
+  // NM > 0: the automaton state of every model (fresh: 1), and what the look-ups of the step's winner gave: its label logit
+  // relative to the arg-max, and per model the value and the state behind it (joint_step sets them, emit uses them)
+  int m_state[NM > 0 ? NM : 1], f_next[NM > 0 ? NM : 1];
+  float f_look[NM > 0 ? NM : 1], f_d = 0.f;
+  if constexpr (NM > 0) {
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      m_state[k] = p.ms_in ? __builtin_amdgcn_readfirstlane(p.ms_in[(long long)b * 2 + k]) : 1;
+      f_next[k] = 1; f_look[k] = 0.f;
+    }
+  }
   if (resume) {
     last = p.sin.last[b]; score = p.sin.score[b]; frames_done = p.sin.frames_done[b];
     if (TDT) { skip = max(p.sin.skip[b], 0); same = p.sin.zero_run[b]; }
@@ -181,8 +209,46 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
     __syncthreads();   // (red_v is re-used by block_sum)
     se = block_sum(se, red_v);
     if (sums) { cA = block_sum(sa, red_v); cB = block_sum(sb, red_v); }
+    int kf = mi;
+    if constexpr (NM > 0) {
+      if (mi != p.blank) {   // (uniform)
+        // every lane ranks its labels with the models (bounded, clamped look-ups; the tables come from L2), then the block arg-max
+        float rv = -INFINITY; int ri = 0x7fffffff;
+        for (int v = tid; v < V1; v += RD_THREADS) {
+          if (v == p.blank) continue;
+          float r = lg[v] - mv;
+#pragma unroll
+          for (int k = 0; k < NM; ++k) {
+            int nx;
+            r += ctc_beam_alpha_lm(p.lm[k].alpha, ctc_beam_lm_lookup(p.lm[k], m_state[k], v, nx));
+          }
+          if (r > rv) { rv = r; ri = v; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const float ov = __shfl_xor(rv, o, 64); const int oi = __shfl_xor(ri, o, 64);
+          if (ov > rv || (ov == rv && oi < ri)) { rv = ov; ri = oi; }
+        }
+        __syncthreads();   // (red_v was read by block_sum)
+        if (lane == 0) { red_v[wave] = rv; red_i[wave] = ri; }
+        __syncthreads();
+        float wv = red_v[0]; int wi = red_i[0];
+#pragma unroll
+        for (int w = 1; w < RD_WAVES; ++w) if (red_v[w] > wv || (red_v[w] == wv && red_i[w] < wi)) { wv = red_v[w]; wi = red_i[w]; }
+        // the winner's look-ups again, by every thread at one address: values and states stay uniform (no rank is a number, e.g.
+        // NaN logits: the arg-max itself)
+        kf = __builtin_amdgcn_readfirstlane((wi < 0 || wi >= V1 || wi == p.blank) ? mi : wi);
+        f_d = lg[kf] - mv;
+#pragma unroll
+        for (int k = 0; k < NM; ++k) {
+          int nx = 0;
+          f_look[k] = ctc_beam_lm_lookup(p.lm[k], m_state[k], kf, nx);
+          f_next[k] = __builtin_amdgcn_readfirstlane(nx);
+        }
+      }
+    }
     if (tid == 0) {
-      s_k = mi;
+      s_k = kf;
       if (TDT) {   // first maximum wins, as for the labels
         int di = 0;
         for (int i = 1; i < p.dur.D; ++i) if (lg[V1 + i] > lg[V1 + di]) di = i;
@@ -211,7 +277,15 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
     // reference's search computes on CPU tensors.  On CUDA tensors its `_joint_step(log_normalize=None)` skips the
     // log-softmax and sums raw maximum logits instead (rnnt_greedy_decoding.py:257-259, 965): scores then differ by the
     // summed log-partition terms; the token ids, time stamps and lengths are the same either way.
-    score += -logf(se);   // log-prob of the arg-max label = mv - (mv + log se)
+    if constexpr (NM > 0) {
+      // the label's log-prob (lg[k] - lg[mi]) - log se, then the models' terms in model order, each product rounded on its own
+      float gain = f_d - logf(se);
+#pragma unroll
+      for (int m = 0; m < NM; ++m) { gain += ctc_beam_alpha_lm(p.lm[m].alpha, f_look[m]); m_state[m] = f_next[m]; }
+      score += gain;
+    } else {
+      score += -logf(se);   // log-prob of the arg-max label = mv - (mv + log se)
+    }
     for (int i = tid; i < H; i += RD_THREADS) { h[i] = hn[i]; c[i] = cn[i]; x[i] = p.emb[(long long)k * H + i]; }
     __syncthreads();
     pred_step(false);
@@ -251,7 +325,25 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
       }
     }
   }
-  if (tid == 0) { p.out_len[b] = n < p.max_out ? n : p.max_out; if (p.score) p.score[b] = score; }
+  if constexpr (NM > 0) {
+    // the `score` output takes back what a phrase begun and not finished was paid; the stream state keeps the running score
+    if (tid == 0) {
+      p.out_len[b] = n < p.max_out ? n : p.max_out;
+      if (p.score) {
+        float sc = score;
+#pragma unroll
+        for (int k = 0; k < NM; ++k)
+          if (p.lm[k].fin) sc += ctc_beam_alpha_lm(p.lm[k].alpha, p.lm[k].fin[min(max(m_state[k], 0), p.lm[k].n_states - 1)]);
+        p.score[b] = sc;
+      }
+      if (p.ms_out) {
+#pragma unroll
+        for (int k = 0; k < NM; ++k) p.ms_out[(long long)b * 2 + k] = m_state[k];
+      }
+    }
+  } else {
+    if (tid == 0) { p.out_len[b] = n < p.max_out ? n : p.max_out; if (p.score) p.score[b] = score; }
+  }
   for (int i = tid + n; i < p.max_out; i += RD_THREADS) {   // pad (also when nothing was emitted)
     p.tokens[(long long)b * p.max_out + i] = -1;
     if (p.times) p.times[(long long)b * p.max_out + i] = -1;
@@ -267,13 +359,19 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
   }
 }
 
+// what the fused entry adds to a launch: the checked models and the per-stream automaton states [B, 2] (null: fresh / none)
+struct RnntFusedArg {
+  const mi355x_ctc_beam_fusion* models; int n_models;
+  const int* ms_in; int* ms_out;
+};
+
 static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
                               const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh,
                               const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out, long long ld_out,
                               const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, const TdtDur* dur, int blank,
                               int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out,
                               void* c_out, const mi355x_rnnt_stream_state* sin, const mi355x_rnnt_stream_state* sout,
-                              void* tok_conf, const MiConf* conf, void* stream) {
+                              void* tok_conf, const MiConf* conf, void* stream, const RnntFusedArg* fused = nullptr) {
   if (!enc_proj || !emb || !w_ih || !w_hh || !b_ih || !b_hh || !w_pred || !w_out || !tokens || !out_len) return MI_ERR_ARG;
   if (B <= 0 || T <= 0 || J <= 0 || H <= 0 || V1 <= 1 || max_out <= 0 || blank < 0 || blank >= V1) return MI_ERR_ARG;
   if ((H & 3) || (J & 3) || (ld_ih & 3) || (ld_hh & 3) || (ld_pred & 3) || (ld_out & 3) || (!h_out != !c_out)) return MI_ERR_ARG;
@@ -305,6 +403,29 @@ static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, 
   const size_t shm = (size_t)(9 * H + 2 * J + V1 + D + 4) * sizeof(float);
   if (shm > 160 * 1024 - 256) return MI_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
+  if (fused) {   // the NM > 0 instantiations: the resumable kernel, from fresh streams and without a state to write in a one-shot call
+    RnntDecPF pf;
+    static_cast<RnntDecP&>(pf) = p;
+    for (int k = 0; k < 2; ++k) {
+      const mi355x_ctc_beam_fusion& m = fused->models[k < fused->n_models ? k : 0];
+      pf.lm[k] = {(const int*)m.state_arc_begin, (const int*)m.arc_tok, (const float*)m.arc_logp, (const int*)m.arc_next,
+                  (const float*)m.state_bo, (const int*)m.state_bo_next, m.n_states, m.n_arcs, m.alpha, m.ub,
+                  (const float*)m.state_final};
+    }
+    pf.ms_in = fused->ms_in; pf.ms_out = fused->ms_out;
+#define RD_LAUNCH_F(WT, TDT, NM)                                                                                                          \
+  hipFuncSetAttribute((const void*)rnnt_greedy_kernel<WT, TDT, true, false, NM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
+  MI_LAUNCH((rnnt_greedy_kernel<WT, TDT, true, false, NM>), dim3(B), dim3(RD_THREADS), shm, s, pf)
+#define RD_LAUNCH_F_NM(WT, TDT) \
+  if (fused->n_models == 1) { RD_LAUNCH_F(WT, TDT, 1); } else { RD_LAUNCH_F(WT, TDT, 2); }
+#define RD_LAUNCH_F_WT(WT) \
+  if (dur) { RD_LAUNCH_F_NM(WT, true) } else { RD_LAUNCH_F_NM(WT, false) }
+    if (w_dtype == MI_DT_F32) { RD_LAUNCH_F_WT(float) } else { RD_LAUNCH_F_WT(bf16_t) }
+#undef RD_LAUNCH_F_WT
+#undef RD_LAUNCH_F_NM
+#undef RD_LAUNCH_F
+    return mi_check_launch();
+  }
 #define RD_LAUNCH(WT, TDT, STREAM, CONF)                                                                                              \
   hipFuncSetAttribute((const void*)rnnt_greedy_kernel<WT, TDT, STREAM, CONF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
   MI_LAUNCH((rnnt_greedy_kernel<WT, TDT, STREAM, CONF>), dim3(B), dim3(RD_THREADS), shm, s, (typename RnntDecArg<CONF>::t)p)
@@ -435,4 +556,32 @@ extern "C" int mi355x_tdt_greedy_decode_stream_conf(
   return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
                             w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len,
                             nullptr, max_out, nullptr, nullptr, state_in, state_out, tok_conf, &q, stream);
+}
+
+// ---- the greedy searches with one or two fusion models (n-gram models, boosting trees: the automata of mi355x_ctc_beam_fusion).
+// One entry for RNN-T (D = 0, durations null) and TDT, one-shot (both states null) and resumable.
+extern "C" int mi355x_transducer_greedy_decode_fused(
+    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
+    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
+    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D, const int* durations,
+    int blank, int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out,
+    const mi355x_ctc_beam_fusion* models, int n_models, const mi355x_rnnt_fused_state* state_in,
+    const mi355x_rnnt_fused_state* state_out, void* stream) {
+  mi_clear_errors();
+  TdtDur dur;
+  const bool tdt = D != 0 || durations;
+  if (tdt && (!durations || tdt_durations(D, durations, &dur))) return MI_ERR_ARG;
+  if (!models || n_models < 1 || n_models > 2 || V1 < 2 || blank != V1 - 1) return MI_ERR_ARG;
+  for (int k = 0; k < n_models; ++k) {   // the tables cover the labels 0 .. V1-2 (state 0's arc index is the label)
+    const mi355x_ctc_beam_fusion& m = models[k];
+    if (!m.state_arc_begin || !m.arc_tok || !m.arc_logp || !m.arc_next || !m.state_bo || !m.state_bo_next) return MI_ERR_ARG;
+    if (m.n_states < 2 || m.n_arcs < V1 - 1 || !(m.alpha >= 0.f)) return MI_ERR_ARG;   // (a NaN fails its compare)
+  }
+  if ((state_in && !state_in->m_state) || (state_out && !state_out->m_state)) return MI_ERR_ARG;
+  if (state_in && (!state_out || state_in->m_state == state_out->m_state)) return MI_ERR_ARG;   // resumable: out of place
+  const RnntFusedArg fz = {models, n_models, state_in ? state_in->m_state : nullptr, state_out ? state_out->m_state : nullptr};
+  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, tdt ? &dur : nullptr, blank, max_symbols, tokens, times,
+                            out_len, score, max_out, h_out, c_out, state_in ? &state_in->s : nullptr,
+                            state_out ? &state_out->s : nullptr, nullptr, nullptr, stream, &fz);
 }

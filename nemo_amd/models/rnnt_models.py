@@ -123,7 +123,12 @@ class EncDecRNNTModel(EncDecCTCModel):
             strategy = dcfg.get("strategy", "greedy_batch")
             if strategy not in ("greedy", "greedy_batch"):
                 raise NotImplementedError(f"transducer decoding strategy '{strategy}' (implemented: greedy, greedy_batch)")
-            ms = dict(dcfg.get("greedy") or {}).get("max_symbols", 10)
+            greedy = dict(dcfg.get("greedy") or {})
+            ms = greedy.get("max_symbols", 10)
+            # shallow fusion (`greedy.ngram_lm_arpa`, `greedy.boosting_tree`): None without those keys, and nothing changes
+            from ..modules.rnnt_decoding import transducer_fusion_from_config
+            fusion = transducer_fusion_from_config(greedy, list(vocab) if vocab is not None else list(self.tokenizer.vocab),
+                                                   self._text_to_ids)
             # TDT: `decoding.model_type: tdt` with `decoding.durations`; a joint with duration outputs decodes as TDT with the
             # loss's durations when the decoding section does not say otherwise
             tdt_loss = isinstance(self.loss, TDTLoss)
@@ -132,8 +137,25 @@ class EncDecRNNTModel(EncDecCTCModel):
             self._decoding = RNNTDecoding(self.decoder, self.joint, vocabulary=list(vocab) if vocab is not None else None,
                                           max_symbols=ms, tokenizer=self.tokenizer if vocab is None else None,
                                           model_type=model_type, durations=list(durations) if durations else None,
-                                          confidence_cfg=dcfg.get("confidence_cfg"))
+                                          confidence_cfg=dcfg.get("confidence_cfg"), fusion_models=fusion)
         return self._decoding
+
+    def change_decoding_strategy(self, decoding_cfg=None, verbose: bool = True):
+        """rnnt_models.py:340-380: rebuilds the decoding object (and the WER over it) from `decoding_cfg` (kept when None)"""
+        if decoding_cfg is not None:
+            strategy = dict(decoding_cfg).get("strategy", "greedy_batch")
+            if strategy not in ("greedy", "greedy_batch"):
+                raise NotImplementedError(f"transducer decoding strategy '{strategy}' (implemented: greedy, greedy_batch)")
+            self._cfg["decoding"] = dict(decoding_cfg)
+        self._decoding = None
+        self._wer = None
+
+    def _text_to_ids(self, text: str):
+        """EncDecCTCModel._text_to_ids for a model whose labels are in its config (the transducer decoder holds no vocabulary)"""
+        if self.tokenizer is not None:
+            return self.tokenizer.text_to_ids(text)
+        from ..data.text import make_parser
+        return make_parser(labels=list(self._cfg["labels"]), do_normalize=False)(text)
 
     @property
     def wer(self):

@@ -12,5 +12,6 @@ from .rnnt_loss import RNNTLoss, RNNTLossNumba  # noqa: F401
 from .tdt_loss import TDTLoss, TDTLossNumba  # noqa: F401
 from .rnnt import RNNTDecoder, RNNTJoint  # noqa: F401
 from .rnnt_decoding import GreedyBatchedRNNTInfer, GreedyBatchedTDTInfer, RNNTDecoding, RNNTWER, Hypothesis  # noqa: F401
+from .rnnt_decoding import transducer_fusion_from_config  # noqa: F401
 from .confidence import (ConfidenceConfig, ConfidenceMethodConfig, aggregate, confidence_from,  # noqa: F401
                          word_confidence)

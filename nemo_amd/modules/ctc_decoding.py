@@ -403,25 +403,26 @@ class BeamBatchedCTCDecoder(_CTCText):
 _LM_KEYS = ("ngram_lm_model", "kenlm_path")
 
 
-def _ngram_lm_from_config(beam, vocabulary, what):
+def _ngram_lm_from_config(beam, vocabulary, what, sec="beam"):
     """the LM of a `beam` sub-section (None without one): `ngram_lm_arpa` = the path of an ARPA text file or an NGramLM,
     `ngram_lm_token_offset` (100; None: the file's words are the vocabulary's strings).  KenLM binaries and `.nemo` LM archives are
-    not read: the reference's keys for them are refused by name."""
+    not read: the reference's keys for them are refused by name.  `sec` names the sub-section in messages (the transducer
+    heads read `greedy`)."""
     for key in _LM_KEYS:
         if beam.get(key):
-            raise NotImplementedError(f"{what} decoding: `beam.{key}` (KenLM binaries and .nemo LM archives are not read here; give "
-                                      "an ARPA text file under `beam.ngram_lm_arpa`)")
+            raise NotImplementedError(f"{what} decoding: `{sec}.{key}` (KenLM binaries and .nemo LM archives are not read here; give "
+                                      f"an ARPA text file under `{sec}.ngram_lm_arpa`)")
     arpa = beam.get("ngram_lm_arpa")
     if arpa is None or (isinstance(arpa, str) and not arpa):
         if float(beam.get("ngram_lm_alpha") or 0.0) != 0.0:
-            raise NotImplementedError(f"{what} decoding: `beam.ngram_lm_alpha` != 0 without `beam.ngram_lm_arpa` (there is no language "
+            raise NotImplementedError(f"{what} decoding: `{sec}.ngram_lm_alpha` != 0 without `{sec}.ngram_lm_arpa` (there is no language "
                                       "model to weigh)")
         return None
     from .ngram_lm import NGramLM
     if isinstance(arpa, NGramLM):
         return arpa
     if not os.path.isfile(str(arpa)):
-        raise FileNotFoundError(f"{what} decoding: `beam.ngram_lm_arpa` = {arpa!r} is not a file")
+        raise FileNotFoundError(f"{what} decoding: `{sec}.ngram_lm_arpa` = {arpa!r} is not a file")
     if vocabulary is None:   # (the section is only being checked)
         return None
     offset = beam.get("ngram_lm_token_offset", 100)
@@ -431,15 +432,15 @@ def _ngram_lm_from_config(beam, vocabulary, what):
 _BOOST_REFUSED = {"unk_score": 0.0, "final_eos_score": 0.0, "score_per_phrase": 0.0}   # the reference's keys that are not provided
 
 
-def _boosting_tree_from_config(beam, vocabulary, what, text_to_ids):
+def _boosting_tree_from_config(beam, vocabulary, what, text_to_ids, sec="beam"):
     """the boosting tree of a `beam` sub-section (None without one): `boosting_tree` = a BoostingTree, or {key_phrases_list: [...],
     key_phrases_file: a text file with one phrase per line, context_score (1.0), depth_scaling (2.0)}; the phrases are tokenised with
     `text_to_ids` (the model's own: its tokenizer, or its character parser).  `unk_score`, `final_eos_score` and `score_per_phrase`
     of the reference are refused by name where they are not their defaults; so are a weight without phrases, a phrase that tokenises
-    to nothing and a file that is not there."""
+    to nothing and a file that is not there.  `sec` names the sub-section in messages."""
     alpha = float(beam.get("boosting_tree_alpha") or 0.0)
     if alpha < 0:
-        raise ValueError(f"{what} decoding: `beam.boosting_tree_alpha` must be >= 0; got {alpha}")
+        raise ValueError(f"{what} decoding: `{sec}.boosting_tree_alpha` must be >= 0; got {alpha}")
     section = beam.get("boosting_tree")
     from .boosting_tree import BoostingTree
     if isinstance(section, BoostingTree):
@@ -447,24 +448,24 @@ def _boosting_tree_from_config(beam, vocabulary, what, text_to_ids):
     section = dict(section or {})
     for key, default in _BOOST_REFUSED.items():
         if section.get(key) is not None and float(section[key]) != default:
-            raise NotImplementedError(f"{what} decoding: `beam.boosting_tree.{key}` = {section[key]!r} (only the default {default} is "
+            raise NotImplementedError(f"{what} decoding: `{sec}.boosting_tree.{key}` = {section[key]!r} (only the default {default} is "
                                       "provided)")
     phrases = [str(p) for p in (section.get("key_phrases_list") or [])]
     path = section.get("key_phrases_file")
     if path is not None and str(path):
         if not os.path.isfile(str(path)):
-            raise FileNotFoundError(f"{what} decoding: `beam.boosting_tree.key_phrases_file` = {path!r} is not a file")
+            raise FileNotFoundError(f"{what} decoding: `{sec}.boosting_tree.key_phrases_file` = {path!r} is not a file")
         with open(str(path), encoding="utf-8") as f:
             phrases += [line.strip() for line in f if line.strip()]
     if not phrases:
         if alpha != 0.0:
-            raise ValueError(f"{what} decoding: `beam.boosting_tree_alpha` != 0 without key phrases (`beam.boosting_tree."
+            raise ValueError(f"{what} decoding: `{sec}.boosting_tree_alpha` != 0 without key phrases (`{sec}.boosting_tree."
                              "key_phrases_list` / `key_phrases_file`): there is nothing to boost")
         return None, alpha
     if vocabulary is None:   # (the section is only being checked)
         return None, alpha
     if text_to_ids is None:
-        raise ValueError(f"{what} decoding: `beam.boosting_tree` needs the model's text_to_ids to tokenise its phrases")
+        raise ValueError(f"{what} decoding: `{sec}.boosting_tree` needs the model's text_to_ids to tokenise its phrases")
     ids = []
     for p in phrases:
         t = [int(i) for i in text_to_ids(p)]

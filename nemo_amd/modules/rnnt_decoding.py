@@ -32,11 +32,19 @@ a label, computed inside the search from the logits it already holds.  `Hypothes
 (streaming: appended chunk by chunk) whenever token OR word confidence is preserved, since `RNNTDecoding` folds the words'
 `word_confidence` from it.  Blank steps are not kept, so
 `preserve_frame_confidence` (and `preserve_alignments`) stay unavailable.
+
+Shallow fusion (`fusion_models=[(NGramLM | BoostingTree, alpha), ...]`, one or two; `decoding.greedy.ngram_lm_arpa` /
+`decoding.greedy.boosting_tree` in a model's config): the search runs through `mi355x_transducer_greedy_decode_fused`, whose rule
+include/mi355x_asr.h states -- a step whose arg-max is a label emits the label that ranks highest with the models' look-ups added,
+a blank stays a blank, and the score of a hypothesis carries the models' terms, a phrase begun and not finished taken back.  The
+stream state is an `ops.RNNTFusedStreamState` (one automaton state per model and stream) and a streaming `Hypothesis.score` is the
+kernel's `score` output, so it equals the one-shot score.  Without models every call is exactly what it was.  Together with token
+or word confidence it is refused (the measure belongs to the unfused distribution).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -60,11 +68,25 @@ class Hypothesis:  # parts/utils/rnnt_utils.py:35-110 (the fields greedy decodin
     stable_length: int = 0   # streaming CTC beam search: the leading tokens of y_sequence that are committed (final); monotone
 
 
+class FusedChunk(NamedTuple):
+    """what `decode_ids_stream` returns with `fusion_models`: the plain search's four results under their names, and `score`"""
+    tokens: torch.Tensor    # i32 [B, N], -1 padded: this chunk's labels
+    frames: torch.Tensor    # i32 [B, N]: their GLOBAL frame indices
+    lengths: torch.Tensor   # i32 [B]
+    state: object           # ops.RNNTFusedStreamState: the next state (its `score` is the running score)
+    score: torch.Tensor     # f32 [B]: the stream's score so far, the models' final terms included
+
+
 class GreedyBatchedRNNTInfer:
     def __init__(self, decoder_model, joint_model, blank_index: int, max_symbols_per_step: Optional[int] = None,
-                 preserve_alignments: bool = False, preserve_frame_confidence: bool = False, confidence_cfg=None, **unused):
+                 preserve_alignments: bool = False, preserve_frame_confidence: bool = False, confidence_cfg=None,
+                 fusion_models=None, **unused):
         from .confidence import confidence_from
         self.confidence_cfg = confidence_from(confidence_cfg)   # None: no confidence, the search is what it was
+        self.fusion_models = list(fusion_models) if fusion_models else None   # None: no fusion, the search is what it was
+        if self.fusion_models is not None and self.confidence_cfg is not None and self.confidence_cfg.wants_tokens:
+            raise NotImplementedError("`fusion_models` together with a `confidence_cfg` that preserves token or word confidence: the "
+                                      "fused search computes no confidences")
         if preserve_alignments or preserve_frame_confidence or (self.confidence_cfg is not None
                                                                 and self.confidence_cfg.preserve_frame_confidence):
             # the search keeps the steps that emitted a label: per-step blank confidences / alignments are not stored
@@ -120,8 +142,12 @@ class GreedyBatchedRNNTInfer:
                    with_confidence: bool = False):
         """encoder_output [B, D, T] (device) -> (tokens i32 [B, N] -1 padded, frame indices, lengths i32 [B], scores f32 [B]
         [, (h, c)][, tok_conf f32 [B, N] 0.0 padded: with_confidence, needs a `confidence_cfg`])"""
+        self._no_fused_confidence(with_confidence)
         f, args = self._project(encoder_output)
         lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        if self.fusion_models is not None:
+            out = self._search_fused(f, lens, *args)
+            return out if with_state else out[:4]
         if with_confidence:
             return self._search_conf(f, lens, *args, method=self._method(args), with_state=with_state)
         return self._search(f, lens, *args, with_state=with_state)
@@ -135,13 +161,29 @@ class GreedyBatchedRNNTInfer:
     def _search_stream_conf(self, *args, method, state=None):
         return ops.rnnt_greedy_decode_stream_conf(*args, method, state=state)
 
+    def _search_fused(self, *args, state=None):
+        """the search with `fusion_models` -> (tokens, frame indices, lengths, score, (h, c) | the next state)"""
+        return ops.transducer_greedy_decode_fused(*args, self.fusion_models, state=state)
+
+    def _no_fused_confidence(self, with_confidence):
+        if with_confidence and self.fusion_models is not None:
+            raise NotImplementedError("`with_confidence` together with `fusion_models`: the fused search computes no confidences")
+
     @torch.no_grad()
     def decode_ids_stream(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, state=None, with_confidence: bool = False):
         """one chunk of every stream: encoder_output [B, D, T_chunk], encoded_lengths = this chunk's frames per stream, `state` the
         ops.RNNTStreamState of the previous chunk (None: fresh streams) -> (tokens, GLOBAL frame indices, lengths of this chunk's
-        labels, the next state[, tok_conf of this chunk's labels: with_confidence])"""
+        labels, the next state[, tok_conf of this chunk's labels: with_confidence]).  With `fusion_models`: a `FusedChunk`, the
+        same four under their names (the state an ops.RNNTFusedStreamState) and `score`, the stream's score so far with the
+        models' final terms; `with_confidence` is refused"""
+        self._no_fused_confidence(with_confidence)
         f, args = self._project(encoder_output)
         lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        if self.fusion_models is not None:
+            if state is None:
+                state = ops.RNNTFusedStreamState.fresh(f.shape[0], args[0].shape[1], self._blank_index, f.device)
+            tokens, times, out_len, score, nxt = self._search_fused(f, lens, *args, state=state)
+            return FusedChunk(tokens, times, out_len, nxt, score)
         if with_confidence:
             return self._search_stream_conf(f, lens, *args, method=self._method(args), state=state)
         return self._search_stream(f, lens, *args, state=state)
@@ -151,7 +193,8 @@ class GreedyBatchedRNNTInfer:
         chunk is resumed from (`forward(chunk, lengths, partial_hypotheses=decoder.fresh_hypotheses(B))`)"""
         dec = self.decoder
         device = device if device is not None else dec.prediction["embed"].weight.device
-        st = ops.RNNTStreamState.fresh(batch_size, dec.pred_hidden, self._blank_index, device)
+        state_cls = ops.RNNTFusedStreamState if self.fusion_models is not None else ops.RNNTStreamState
+        st = state_cls.fresh(batch_size, dec.pred_hidden, self._blank_index, device)
         return [Hypothesis(score=0.0, y_sequence=torch.zeros(0, dtype=torch.long), timestamp=[], dec_state=st.select(b), length=0,
                            last_token=st.select(b).last, token_confidence=[] if self._with_confidence else None)
                 for b in range(batch_size)]
@@ -179,9 +222,18 @@ class GreedyBatchedRNNTInfer:
         if any(h is None or not isinstance(h.dec_state, ops.RNNTStreamState) for h in partial_hypotheses):
             raise ValueError("`partial_hypotheses` must carry a stream state in `dec_state`: hypotheses this decoder returned for "
                              "earlier chunks, or `fresh_hypotheses(batch_size)` for the first chunk of a stream")
-        state = ops.RNNTStreamState.stack([h.dec_state for h in partial_hypotheses])
-        tokens, times, out_len, nxt, *tc = self.decode_ids_stream(encoder_output, encoded_lengths, state, with_confidence=conf)
-        tokens, times, out_len, score = tokens.cpu(), times.cpu(), out_len.cpu(), nxt.score.cpu()   # the only D2H copies
+        fused = self.fusion_models is not None
+        if fused and any(not isinstance(h.dec_state, ops.RNNTFusedStreamState) for h in partial_hypotheses):
+            raise ValueError("`partial_hypotheses` of a decoder with `fusion_models` must carry the fused stream state: hypotheses "
+                             "this decoder returned for earlier chunks, or `fresh_hypotheses(batch_size)`")
+        state = (ops.RNNTFusedStreamState if fused else ops.RNNTStreamState).stack([h.dec_state for h in partial_hypotheses])
+        if fused:   # the kernel's `score` output carries the models' final terms; the state keeps the running score
+            chunk = self.decode_ids_stream(encoder_output, encoded_lengths, state)
+            tokens, times, out_len, nxt, score, tc = chunk.tokens, chunk.frames, chunk.lengths, chunk.state, chunk.score, ()
+        else:
+            tokens, times, out_len, nxt, *tc = self.decode_ids_stream(encoder_output, encoded_lengths, state, with_confidence=conf)
+            score = nxt.score
+        tokens, times, out_len, score = tokens.cpu(), times.cpu(), out_len.cpu(), score.cpu()   # the only D2H copies
         tc = tc[0].cpu() if conf else None
         lens = encoded_lengths.cpu()
         hyps = []
@@ -214,6 +266,9 @@ class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
         if getattr(joint_model, "_num_extra_outputs", len(self.durations)) != len(self.durations):
             raise ValueError(f"the joint has {joint_model._num_extra_outputs} extra outputs for {len(self.durations)} durations")
 
+    def _search_fused(self, *args, state=None):
+        return ops.transducer_greedy_decode_fused(*args, self.fusion_models, durations=self.durations, state=state)
+
     def _search(self, *args, with_state=False):
         return ops.tdt_greedy_decode(*args[:16], self.durations, args[16], with_state=with_state)
 
@@ -227,12 +282,32 @@ class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
         return ops.tdt_greedy_decode_stream_conf(*args[:16], self.durations, args[16], method, state=state)
 
 
+def transducer_fusion_from_config(greedy, vocabulary=None, text_to_ids=None, what: str = "transducer"):
+    """The fusion models of a transducer head's `decoding.greedy` sub-section, read by the CTC head's readers (modules/
+    ctc_decoding.py) under the section name `greedy`: ngram_lm_arpa, ngram_lm_alpha, ngram_lm_token_offset, boosting_tree
+    {key_phrases_list, key_phrases_file, context_score, depth_scaling}, boosting_tree_alpha, with the same refusals
+    (`ngram_lm_model` / `kenlm_path` by name, a weight without a model, a missing file, a phrase that tokenises to nothing, the
+    three tree keys that are not provided).  `vocabulary`: the labels, in id order (None: the section is only checked);
+    `text_to_ids` tokenises the phrases.  -> [(NGramLM, alpha)][(BoostingTree, alpha)], the LM first, or None without the keys."""
+    from .ctc_decoding import _boosting_tree_from_config, _ngram_lm_from_config
+    greedy = dict(greedy or {})
+    alpha = float(greedy.get("ngram_lm_alpha") or 0.0)
+    if alpha < 0:
+        raise ValueError(f"{what} decoding: `greedy.ngram_lm_alpha` must be >= 0; got {alpha}")
+    lm = _ngram_lm_from_config(greedy, vocabulary, what, sec="greedy")
+    tree, tree_alpha = _boosting_tree_from_config(greedy, vocabulary, what, text_to_ids, sec="greedy")
+    models = ([(lm, alpha)] if lm is not None else []) + ([(tree, tree_alpha)] if tree is not None else [])
+    return models or None
+
+
 class RNNTDecoding:
     """`strategy: greedy_batch` of AbstractRNNTDecoding (rnnt_decoding.py:216-330) for a character / word-piece vocabulary;
-    blank id = len(vocabulary) (rnnt_decoding.py:1170)."""
+    blank id = len(vocabulary) (rnnt_decoding.py:1170).  `fusion_models` (None: the search without models): what
+    `transducer_fusion_from_config` reads from `decoding.greedy`."""
 
     def __init__(self, decoder, joint, vocabulary: Optional[Sequence[str]] = None, max_symbols: Optional[int] = 10,
-                 tokenizer=None, model_type: str = "rnnt", durations: Optional[Sequence[int]] = None, confidence_cfg=None):
+                 tokenizer=None, model_type: str = "rnnt", durations: Optional[Sequence[int]] = None, confidence_cfg=None,
+                 fusion_models=None):
         from .confidence import confidence_from
         self.vocabulary = list(vocabulary) if vocabulary is not None else None
         self.tokenizer = tokenizer
@@ -242,10 +317,10 @@ class RNNTDecoding:
             if not durations:
                 raise ValueError("decoding with model_type 'tdt' needs `durations`")
             self.decoding = GreedyBatchedTDTInfer(decoder, joint, self.blank_id, durations, max_symbols_per_step=max_symbols,
-                                                  confidence_cfg=self.confidence_cfg)
+                                                  confidence_cfg=self.confidence_cfg, fusion_models=fusion_models)
         elif model_type == "rnnt":
             self.decoding = GreedyBatchedRNNTInfer(decoder, joint, self.blank_id, max_symbols_per_step=max_symbols,
-                                                   confidence_cfg=self.confidence_cfg)
+                                                   confidence_cfg=self.confidence_cfg, fusion_models=fusion_models)
         else:
             raise NotImplementedError(f"transducer decoding model_type '{model_type}' (implemented: rnnt, tdt)")
 

@@ -1204,6 +1204,99 @@ def tdt_greedy_decode_stream_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_
                                  ld_out, b_out, blank, durations, max_symbols, state, max_out, method=method)
 
 
+class _FusedStreamStateC(C.Structure):   # mi355x_rnnt_fused_state
+    _fields_ = [("s", _StreamStateC), ("m_state", C.c_void_p)]
+
+
+class RNNTFusedStreamState(RNNTStreamState):
+    """the state of the fused greedy search (mi355x_rnnt_fused_state): RNNTStreamState and m_state i32 [B, 2], the automaton state
+    of fusion model m in column m (fresh stream: 1; column 1 stays 1 with one model).  `score` is the running score without the
+    models' final terms."""
+    __slots__ = ("m_state",)
+    _base = RNNTStreamState.__slots__
+
+    def __init__(self, h, c, last, score, frames_done, skip, zero_run, m_state):
+        super().__init__(h, c, last, score, frames_done, skip, zero_run)
+        self.m_state = m_state
+
+    @classmethod
+    def empty(cls, B, H, device):
+        return cls(*RNNTStreamState.empty(B, H, device).tensors(), torch.ones(B, 2, dtype=torch.int32, device=device))
+
+    @classmethod
+    def fresh(cls, B, H, blank, device):
+        return cls(*RNNTStreamState.fresh(B, H, blank, device).tensors(), torch.ones(B, 2, dtype=torch.int32, device=device))
+
+    def tensors(self):
+        return tuple(getattr(self, n) for n in self._base + self.__slots__)
+
+    def select(self, b):
+        return RNNTFusedStreamState(*(t[b:b + 1] for t in self.tensors()))
+
+    def _c(self, B, H):
+        m = self.m_state
+        if tuple(m.shape) != (B, 2) or m.dtype != torch.int32 or not m.is_contiguous():
+            raise ValueError(f"stream state `m_state`: expected contiguous torch.int32 {(B, 2)}, got {m.dtype} {tuple(m.shape)}")
+        return _FusedStreamStateC(RNNTStreamState(*self.tensors()[:len(self._base)])._c(B, H), _ptr(m))
+
+
+def _transducer_fusion_check(what, models, V1):
+    """`models` = [(NGramLM | BoostingTree, alpha), ...], one or two, over the V1 - 1 labels of the joint"""
+    from .modules.ngram_lm import NGramLM
+    models = list(models) if models is not None else []
+    if not 1 <= len(models) <= 2:
+        raise ValueError(f"{what}: `models` must hold one or two (model, alpha) pairs, got {len(models)}")
+    for i, pair in enumerate(models):
+        if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and isinstance(pair[0], NGramLM)):
+            got = type(pair[0]).__name__ if isinstance(pair, (tuple, list)) and len(pair) else type(pair).__name__
+            raise TypeError(f"{what}: `models` holds (NGramLM | BoostingTree, alpha) pairs, got {got}")
+        if pair[0].vocab_size != V1 - 1:
+            raise ValueError(f"{what}: model {i} has {pair[0].vocab_size} labels, the joint {V1} classes (labels + the blank)")
+    return models
+
+
+def transducer_greedy_decode_fused(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                                   b_out, blank, max_symbols, models, durations=None, state=None, max_out=None):
+    """the greedy transducer search with shallow fusion (mi355x_transducer_greedy_decode_fused, which include/mi355x_asr.h states):
+    rnnt_greedy_decode's arguments, `models` = a list of one or two (NGramLM | BoostingTree, alpha) as in `ctc_beam_decode_fused`,
+    `durations` for the TDT search.  A step whose arg-max is a label emits the label that ranks highest with the models' look-ups
+    added; a blank stays a blank.  `state` None: the one-shot search -> (tokens, frame indices, lengths, score, (h, c)).  `state` an
+    RNNTFusedStreamState (`fresh` for the first chunk): one chunk of the resumable search, enc_len = this chunk's frames ->
+    (tokens, GLOBAL frame indices, lengths of this chunk's labels, score, the next RNNTFusedStreamState).  `score` is the score
+    of the stream so far with each BoostingTree's final term (a phrase begun and not finished is not paid for); the state's own
+    `score` is the running one.  Any cut into chunks gives the bits of one launch; every alpha = 0 the bits of the searches
+    without models."""
+    what = "transducer_greedy_decode_fused"
+    B, T, J = enc_proj.shape
+    V1, H = emb.shape
+    models = _transducer_fusion_check(what, models, V1)
+    if state is not None and not isinstance(state, RNNTFusedStreamState):
+        raise TypeError(f"{what}: `state` must be an RNNTFusedStreamState, got {type(state).__name__}")
+    if max_out is None:
+        max_out = T * max_symbols if max_symbols > 0 else 4 * T
+    dev = enc_proj.device
+    tokens = torch.empty(B, max_out, dtype=torch.int32, device=dev)
+    times = torch.empty(B, max_out, dtype=torch.int32, device=dev)
+    out_len = torch.empty(B, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    h = c = nxt = s_in = s_out = None
+    if state is None:
+        h, c = (torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(2))
+    else:
+        nxt = RNNTFusedStreamState.empty(B, H, dev)
+        if durations is None:   # (not written by the RNN-T search)
+            nxt.skip.zero_(); nxt.zero_run.zero_()
+        s_in, s_out = state._c(B, H), nxt._c(B, H)
+    arr, keep = _ctc_beam_fusion_array(models, enc_proj)
+    D, dur = _tdt_durations(durations) if durations is not None else (0, None)
+    check(lib.mi355x_transducer_greedy_decode_fused(
+        _ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih, _ptr(w_hh), ld_hh, _ptr(b_ih),
+        _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out), ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1, D, dur, blank,
+        max_symbols, _ptr(tokens), _ptr(times), _ptr(out_len), _ptr(score), max_out, _ptr(h), _ptr(c), C.cast(arr, C.c_void_p),
+        len(arr), C.byref(s_in) if s_in is not None else None, C.byref(s_out) if s_out is not None else None, _stream()), what)
+    return tokens, times, out_len, score, ((h, c) if state is None else nxt)
+
+
 def row_scale(x, vec, rows, cols):
     check(lib.mi355x_row_scale(_ptr(x), _ptr(vec), rows, cols, _stream()), "row_scale")
 

@@ -17,8 +17,18 @@ behind it (ConvASRDecoder + mi355x_ctc_beam_decode_stream, with --lm mi355x_ctc_
 generator at alpha 0.5), stepped from the state a stream has after eight chunks, with the n-best chased out on every step and, as
 `head_ms_no_emit`, with the state advanced only.  One row per (classes, beam size) under `heads`: median, min and max of 7 rounds.
 
+`--decoder {rnnt,tdt} --head-only FRAMES [FRAMES ...] [--lm ORDER] [--boost P]`: no encoder; the transducer head alone on random
+encoder output of FRAMES frames per stream (14 = the streaming step, 250 = 20 s offline), the plain search against the search with
+shallow fusion (mi355x_transducer_greedy_decode_fused: --lm, the n-gram model of the tests' generator at alpha 0.5; --boost, a tree
+of P three-label phrases taken from the plain search's own output on this input, at alpha 2.0), resumed from the state after one
+chunk.  The two are timed in alternating rounds of one process: median, min and max of 7 rounds each, and the labels emitted.
+What is timed is the head's step (`decode_ids_stream`): the encoder-projection GEMM with its cast, the same on both sides, and
+the search.  The difference of the two times is the fused kernel's; their ratio understates its relative cost by that share.
+The heads' weights are the modules' initialisation times 4 (the tests' scale), so that the joint emits labels and the models are
+consulted: a flat joint, as `--decoder rnnt` without --head-only builds it, emits blanks only.
+
     python tools/stream_bench.py [--batch 1 16 64] [--steps 50] [--warmup 10] [--layers 17] [--decoder none] [--json OUT]
-                                 [--beam-size 4 16 64] [--classes 129 1025] [--lm ORDER]
+                                 [--beam-size 4 16 64] [--classes 129 1025] [--lm ORDER] [--boost P] [--head-only FRAMES ...]
 """
 import argparse
 import json
@@ -44,7 +54,7 @@ def build(n_layers):
     return enc
 
 
-def build_head(kind, d_model=512):
+def build_head(kind, d_model=512, fusion_models=None, scale=1.0):
     """-> step(encoded [B, D, T], encoded_len) for the head `kind`, weights random (the step's cost does not depend on them much:
     the transducer search emits what a random joint emits, bounded by max_symbols = 10 per frame)"""
     from nemo_amd.modules import ConvASRDecoder, GreedyBatchedRNNTInfer, GreedyBatchedTDTInfer, RNNTDecoder, RNNTJoint
@@ -58,15 +68,57 @@ def build_head(kind, d_model=512):
     joint = RNNTJoint(jointnet={"encoder_hidden": d_model, "pred_hidden": 640, "joint_hidden": 640, "activation": "relu", "dropout": 0.0},
                       num_classes=V, num_extra_outputs=len(durations) if kind == "tdt" else 0, compute_dtype=torch.bfloat16)
     with torch.no_grad():
+        for p in list(pred.parameters()) + list(joint.parameters()):   # (scale 1: a nearly flat joint, which the blank bias decides)
+            p.mul_(scale)
         joint.joint_net[-1].bias[V] += 2.0   # (a blank now and then, as a trained model has)
     pred, joint = pred.to(dev).eval(), joint.to(dev).eval()
-    infer = (GreedyBatchedTDTInfer(pred, joint, V, durations, max_symbols_per_step=10) if kind == "tdt"
-             else GreedyBatchedRNNTInfer(pred, joint, V, max_symbols_per_step=10))
+    infer = (GreedyBatchedTDTInfer(pred, joint, V, durations, max_symbols_per_step=10, fusion_models=fusion_models) if kind == "tdt"
+             else GreedyBatchedRNNTInfer(pred, joint, V, max_symbols_per_step=10, fusion_models=fusion_models))
 
-    def step(enc, n, state=None):
-        tokens, times, out_len, nxt = infer.decode_ids_stream(enc, n, state)
-        return tokens, nxt
+    def step(enc, n, state=None, lengths=False):
+        tokens, times, out_len, nxt, *_ = infer.decode_ids_stream(enc, n, state)
+        return ((tokens, out_len) if lengths else tokens), nxt
     return step
+
+
+def fused_head_setting(kind, lm_order, n_phrases, B, frames, steps, warmup, n_rounds=7, d_model=512):
+    """the transducer head alone on `frames` frames per stream: the plain search against the fused one, alternating rounds"""
+    import statistics
+    V = 1024
+    g = torch.Generator(device=dev).manual_seed(2)
+    enc_out = torch.randn(B, d_model, frames, device=dev, generator=g)
+    enc_len = torch.full((B,), frames, dtype=torch.int64, device=dev)
+    plain = build_head(kind, d_model, scale=4.0)   # (the tests' scale: a joint that emits labels, so that the models are consulted)
+    with torch.no_grad():
+        (tokens, out_len), p_state = plain(enc_out, enc_len, lengths=True)
+    models = []
+    if lm_order:
+        from ctc_beam_bench import make_ngram_lm
+        models.append((make_ngram_lm(V, lm_order), 0.5))
+    if n_phrases:   # runs of three labels the plain search emits on this input: phrases that are walked, completed and broken off
+        from nemo_amd.modules import BoostingTree
+        tokens, out_len = tokens.cpu(), out_len.cpu()
+        runs = [tuple(tokens[b, i:i + 3].tolist()) for b in range(B) for i in range(0, int(out_len[b]) - 2, 3)]
+        runs = list(dict.fromkeys(runs))[:n_phrases]
+        models.append((BoostingTree.from_phrases(runs, V), 2.0))
+    fused = build_head(kind, d_model, fusion_models=models, scale=4.0)   # (the same seed: the same weights)
+    row = dict(decoder=kind, batch=B, frames=frames, lm_order=lm_order, phrases=len(models[-1][0].phrases) if n_phrases else 0)
+    with torch.no_grad():
+        (_, f_len), f_state = fused(enc_out, enc_len, lengths=True)
+        row["labels_plain"], row["labels_fused"] = int(out_len.sum()), int(f_len.sum())
+        fns = dict(plain=lambda: plain(enc_out, enc_len, p_state), fused=lambda: fused(enc_out, enc_len, f_state))
+        for fn in fns.values():
+            for _ in range(warmup):
+                fn()
+        torch.cuda.synchronize()
+        ms = dict(plain=[], fused=[])
+        for _ in range(n_rounds):
+            for name, fn in fns.items():
+                ms[name].append(timed(fn, steps))
+    for name, v in ms.items():
+        row[name + "_ms"] = round(statistics.median(v), 3)
+        row[name + "_ms_range"] = [round(min(v), 3), round(max(v), 3)]
+    return row
 
 
 def build_beam_head(C, W, lm_order, d_model=512):
@@ -220,8 +272,22 @@ def main():
     ap.add_argument("--beam-size", type=int, nargs="+", default=[4, 16, 64])
     ap.add_argument("--classes", type=int, nargs="+", default=[129, 1025])
     ap.add_argument("--lm", type=int, default=0, metavar="ORDER")
+    ap.add_argument("--boost", type=int, default=0, metavar="P")
+    ap.add_argument("--head-only", type=int, nargs="+", default=None, metavar="FRAMES")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    if args.head_only:
+        if args.decoder not in ("rnnt", "tdt") or not (args.lm or args.boost):
+            ap.error("--head-only compares the transducer heads with and without fusion: --decoder rnnt|tdt and --lm and / or --boost")
+        rows = []
+        for B in args.batch:
+            for frames in args.head_only:
+                rows.append(fused_head_setting(args.decoder, args.lm, args.boost, B, frames, args.steps, args.warmup))
+                print(json.dumps(rows[-1]), flush=True)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(rows, f, indent=1)
+        return
     enc = build(args.layers)
     if args.decoder == "ctc_beam":
         head = [(dict(classes=C, beam_size=W, lm_order=args.lm), build_beam_head(C, W, args.lm)) for C in args.classes

@@ -64,7 +64,7 @@ struct PackEntry {
   const float* src; void* dst;
   int rows, cols, nr2, nc2;
   long long sr1, sr2, sc1, sc2, pitch;
-  long long tile_begin;  // prefix sum of 32x32 tiles
+  long long tile_begin;  // prefix sum of 64x64 tiles (PK_T)
 };
 #define PK_T 64  // tile edge; tile_begin counts 64x64 tiles
 __global__ __launch_bounds__(256) void pack_kernel(const PackEntry* __restrict__ tab, int n_entries, int out_dt) {
@@ -147,8 +147,9 @@ static int adamw_launch(void* params, const void* grads, void* exp_avg, void* ex
                         float ema_decay, void* stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || n <= 0 || (n & 3) || step < 1) return MI_ERR_ARG;
   if (ema && !(ema_decay >= 0.f && ema_decay <= 1.f)) return MI_ERR_ARG;
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  // in double, rounded once: in float 1 - beta2^step cancels (beta2 = 0.999, steps 2 - 5: the step size tens of ulps off)
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   long long nb = ((n >> 2) + 255) / 256;
   if (nb > 8192) nb = 8192;
   MI_LAUNCH(adamw_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (float*)params, (const float*)grads,

@@ -922,13 +922,10 @@ int mi355x_rnnt_loss_ex(const void* acts, long long ld_acts, const void* labels,
  * [V1, H] (row `blank` zero); one LSTM layer, torch gate order i, f, g, o: w_ih / w_hh [4H, H], w_pred [J, H], w_out [V1, J] in w_dtype
  * with row pitches ld_*; biases f32.  tokens / times i32 [B, max_out] (-1 padded; times optional), out_len i32 [B], score f32 [B]
  * (optional: sum of the emitted labels' log-probabilities), h_out / c_out f32 [B, H] (optional, both or neither: the final state).
- * max_symbols <= 0: unlimited.  H, J and the pitches multiples of 4. */
-int mi355x_rnnt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                              const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                              const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out,
-                              long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int blank,
-                              int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out,
-                              void* c_out, void* stream);
+ * max_symbols <= 0: unlimited.  H, J and the pitches multiples of 4.
+ * Every form of the search -- this one, TDT, resumable, with confidences, with fusion models -- is one call of
+ * mi355x_transducer_greedy_decode with a mi355x_transducer_greedy_desc; both are declared below, after the paragraphs that state
+ * each form. */
 
 /* ---- Token-and-Duration Transducer (TDT) loss: the objective of the reference's TDTLossNumba (rnnt_pytorch.py -> GPUTDT,
  * gpu_rnnt.py).  acts f32 [B,T,U1,V1+D] = joint LOGITS with row pitch ld_acts >= V1+D: V1 label logits (blank among them), then D
@@ -943,20 +940,14 @@ int mi355x_tdt_loss_ex(const void* acts, long long ld_acts, const void* labels, 
                        int T, int U1, int V1, int D, const int* durations, int blank, float sigma, float grad_scale, void* costs,
                        void* grads, int grads_dtype, long long ld_grads, void* workspace, long long workspace_elems, void* stream);
 
-/* ---- greedy TDT decoding on the device: mi355x_rnnt_greedy_decode's arguments plus the duration set; w_out [V1+D, J], b_out
- * [V1+D].  Per utterance: t = 0; while t < enc_len[b]: k = argmax of the V1 label logits, d = durations[argmax of the D duration
- * logits] (first maximum wins for both); blank -> t += max(d, 1); else emit (k, t), commit the state, t += d, where the
- * max_symbols-th consecutive label of duration 0 (max_symbols > 0) is moved on by one frame.  At most max_out labels. */
-int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                             const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                             const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out,
-                             long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D,
-                             const int* durations, int blank, int max_symbols, void* tokens, void* times, void* out_len,
-                             void* score, int max_out, void* h_out, void* c_out, void* stream);
+/* ---- greedy TDT decoding on the device (the descriptor's D and durations given): the RNN-T search's fields plus the duration set;
+ * w_out [V1+D, J], b_out [V1+D].  Per utterance: t = 0; while t < enc_len[b]: k = argmax of the V1 label logits, d = durations[argmax
+ * of the D duration logits] (first maximum wins for both); blank -> t += max(d, 1); else emit (k, t), commit the state, t += d, where
+ * the max_symbols-th consecutive label of duration 0 (max_symbols > 0) is moved on by one frame.  At most max_out labels. */
 
-/* ---- resumable greedy search (streaming transducer decoding: the reference's `partial_hypotheses`).  The searches above, started
- * from a per-stream decoder state and returning the next one, so that a stream decoded chunk by chunk gives bit-identical tokens,
- * frame indices, lengths, score and final state to one launch over the whole sequence, for ANY cut into chunks.
+/* ---- resumable greedy search (streaming transducer decoding: the reference's `partial_hypotheses`; the descriptor's state_out
+ * given).  The searches above, started from a per-stream decoder state and returning the next one, so that a stream decoded
+ * chunk by chunk gives bit-identical tokens, frame indices, lengths, score and final state to one launch over the whole sequence, for ANY cut into chunks.
  * State (device arrays, written out of place: state_out must not alias state_in):
  *   h, c          f32 [B, H]  committed LSTM state                                              fresh stream: 0
  *   last          i32 [B]     last emitted label (blank = the zero embedding row)                             blank
@@ -971,68 +962,28 @@ int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, c
  * indices.  max_symbols counts per frame, so the RNN-T search carries no counter; max_symbols <= 0 bounds each CHUNK by max_out.
  * With max_symbols > 0 give max_out >= T * max_symbols: as in the one-shot search, labels beyond max_out are counted and scored but
  * not stored, and here they would also enter the carried state (last, h, c), which then contradicts what the caller received.
- * T >= 1 as for the one-shot entries: a step in which no stream has a frame is not a launch (keep the state).  The one-shot entry
- * points launch their own instantiation of the kernel template, compiled without the state code. */
+ * T >= 1 as for the one-shot search: a step in which no stream has a frame is not a launch (keep the state).  A one-shot call
+ * (both states NULL, no models) launches its own instantiation of the kernel template, compiled without the state code. */
 typedef struct mi355x_rnnt_stream_state {
   float* h; float* c; int* last; float* score; int* frames_done; int* skip; int* zero_run;
 } mi355x_rnnt_stream_state;
-int mi355x_rnnt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                     const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                     const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-                                     const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
-                                     int H, int V1, int blank, int max_symbols, void* tokens, void* times, void* out_len,
-                                     int max_out, const mi355x_rnnt_stream_state* state_in,
-                                     const mi355x_rnnt_stream_state* state_out, void* stream);
-int mi355x_tdt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                    const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                    const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out,
-                                    long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D,
-                                    const int* durations, int blank, int max_symbols, void* tokens, void* times, void* out_len,
-                                    int max_out, const mi355x_rnnt_stream_state* state_in,
-                                    const mi355x_rnnt_stream_state* state_out, void* stream);
 
-/* ---- the four searches above with the confidence of every emitted label: their sibling's arguments, then tok_conf f32
+/* ---- the searches above with the confidence of every emitted label (the descriptor's `conf` given): tok_conf f32
  * [B, max_out] (0.0 padded) and the measure (MI355X_CONF_*, k0..k2 for V = V1).  tok_conf[b, n] = the confidence of the step that
  * emitted label n, over the V1 label logits of that step (blank included; TDT: the duration logits take no part); blank steps are
  * not kept.  The sums ride in the pass that computes the step's log-sum-exp, relative to the maximum logit.  Everything else the
- * siblings write is bit-identical to theirs, and a stream cut into any chunks gives bit-identical tok_conf to one launch: the value
- * belongs to a label, so the stream state carries nothing new.  These launch their own instantiations of the kernel template; the
- * siblings launch the code they always have.  MI_ERR_ARG also for a null tok_conf, alpha <= 0, unknown enum values. */
-int mi355x_rnnt_greedy_decode_conf(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                   const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                   const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out,
-                                   long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int blank,
-                                   int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out,
-                                   void* c_out, void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2,
-                                   void* stream);
-int mi355x_tdt_greedy_decode_conf(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                  const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                  const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out,
-                                  long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D,
-                                  const int* durations, int blank, int max_symbols, void* tokens, void* times, void* out_len,
-                                  void* score, int max_out, void* h_out, void* c_out, void* tok_conf, int method, int norm,
-                                  float alpha, float k0, float k1, float k2, void* stream);
-int mi355x_rnnt_greedy_decode_stream_conf(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                          const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                          const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-                                          const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
-                                          int H, int V1, int blank, int max_symbols, void* tokens, void* times, void* out_len,
-                                          int max_out, const mi355x_rnnt_stream_state* state_in,
-                                          const mi355x_rnnt_stream_state* state_out, void* tok_conf, int method, int norm,
-                                          float alpha, float k0, float k1, float k2, void* stream);
-int mi355x_tdt_greedy_decode_stream_conf(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                         const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                         const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-                                         const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
-                                         int H, int V1, int D, const int* durations, int blank, int max_symbols, void* tokens,
-                                         void* times, void* out_len, int max_out, const mi355x_rnnt_stream_state* state_in,
-                                         const mi355x_rnnt_stream_state* state_out, void* tok_conf, int method, int norm,
-                                         float alpha, float k0, float k1, float k2, void* stream);
+ * search writes is bit-identical to what it writes without a measure, and a stream cut into any chunks gives bit-identical tok_conf
+ * to one launch: the value belongs to a label, so the stream state carries nothing new.  These launch their own instantiations of
+ * the kernel template; a call without a measure launches the code it always has.  MI_ERR_ARG also for a null tok_conf,
+ * alpha <= 0, unknown enum values. */
+typedef struct mi355x_transducer_conf {
+  int method, norm;   /* MI355X_CONF_*, MI355X_CONF_NORM_* */
+  float alpha, k0, k1, k2;
+} mi355x_transducer_conf;
 
-/* ---- the greedy searches with shallow fusion: one or two fusion models, the automata of mi355x_ctc_beam_fusion above (an n-gram
- * model: six tables; a boosting tree: the six and state_final).  ONE entry for the four searches: the arguments of
- * mi355x_tdt_greedy_decode (D = 0 with durations NULL: the RNN-T search), then the models and the two states (both NULL: the
- * one-shot search; state_out given: the resumable search, state_in NULL = fresh streams).  The tables cover the labels 0 .. V1-2,
+/* ---- the greedy searches with shallow fusion (the descriptor's `models` given): one or two fusion models, the automata of
+ * mi355x_ctc_beam_fusion above (an n-gram model: six tables; a boosting tree: the six and state_final), for RNN-T and TDT, one-shot
+ * (both states NULL) and resumable (state_out given, state_in NULL = fresh streams).  The tables cover the labels 0 .. V1-2,
  * so blank == V1-1 is required.  `ub` is not read: this search has no early-outs.
  * Each stream keeps one automaton state per model; a fresh stream starts every model in state 1.  One step on frame t with the
  * label logits lg[0 .. V1):
@@ -1047,26 +998,47 @@ int mi355x_tdt_greedy_decode_stream_conf(const void* enc_proj, int f_dtype, long
  * alpha_m * state_final_m[state_m] added in model order wherever that table is given: the boost of a phrase that was begun and not
  * finished is taken back, as in the CTC search.  The stream state carries the running score WITHOUT those terms, so any cut into
  * chunks gives the bits of one launch -- tokens, frames, lengths, score, h / c and every field of the state -- and with every
- * alpha = 0 all of them are the bits of the entries without models.  Parity with the reference's fused scores is not claimed: this
+ * alpha = 0 all of them are the bits of the search without models.  Parity with the reference's fused scores is not claimed: this
  * paragraph is the rule.
- * State: the resumable search's, and m_state i32 [B, 2], the automaton state of model m in column m (fresh stream: 1; column 1 is
- * neither read nor written with one model).  score, h_out / c_out as in the one-shot entries, optional in both forms.
- * MI_ERR_ARG for what the siblings refuse, n_models outside 1..2, a null `models`, per model a null table (state_final may be
- * null), n_states < 2, n_arcs < V1-1, alpha < 0 or NaN; blank != V1-1; a state with a null m_state; state_in without state_out;
- * aliased states. */
-typedef struct mi355x_rnnt_fused_state {
-  mi355x_rnnt_stream_state s;
-  int* m_state;
-} mi355x_rnnt_fused_state;
-int mi355x_transducer_greedy_decode_fused(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                          const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                          const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-                                          const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
-                                          int H, int V1, int D, const int* durations, int blank, int max_symbols, void* tokens,
-                                          void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out,
-                                          const mi355x_ctc_beam_fusion* models, int n_models,
-                                          const mi355x_rnnt_fused_state* state_in, const mi355x_rnnt_fused_state* state_out,
-                                          void* stream);
+ * State: the resumable search's, and m_state_in / m_state_out i32 [B, 2], the automaton state of model m in column m (fresh
+ * stream: 1; column 1 is neither read nor written with one model); m_state_in is read with state_in, m_state_out written with
+ * state_out.  score, h_out / c_out as in the one-shot search, optional in both forms.
+ * MI_ERR_ARG for what the search without models refuses, n_models outside 1..2, a null `models`, per model a null table
+ * (state_final may be null), n_states < 2, n_arcs < V1-1, alpha < 0 or NaN; blank != V1-1; a state given with a null m_state_*;
+ * state_in without state_out; aliased states. */
+
+/* ---- the descriptor of a greedy search and its one entry.  A group that is absent selects the search without it:
+ *   TDT         D == 0 and durations NULL: the RNN-T search.  Anything else must be a valid duration set (host array, as for
+ *               mi355x_tdt_loss_ex).
+ *   resumable   state_in and state_out NULL: the one-shot search.  state_out alone: fresh streams.  state_in without state_out:
+ *               MI_ERR_ARG.
+ *   confidence  conf NULL: none, and tok_conf is ignored.
+ *   fusion      models NULL and n_models == 0: none, and m_state_* are ignored.  Anything else is a fusion request.
+ * Confidences together with fusion models are refused with MI_ERR_ARG before anything is launched: the kernel template has no
+ * such instantiation.  times, score and the pair h_out / c_out are optional in every form.  A NULL descriptor is MI_ERR_ARG.
+ * The nine entries this one replaced (named here without the mi355x_ prefix), as descriptor settings:
+ *   former entry                          TDT           states                    conf  models  passed as NULL
+ *   rnnt_greedy_decode                    -             -                         -     -       -
+ *   tdt_greedy_decode                     D, durations  -                         -     -       -
+ *   {rnnt,tdt}_greedy_decode_stream       as above      state_out (+ state_in)    -     -       score, h_out, c_out
+ *   {rnnt,tdt}_greedy_decode_conf         as above      -                         set   -       -
+ *   {rnnt,tdt}_greedy_decode_stream_conf  as above      state_out (+ state_in)    set   -       score, h_out, c_out
+ *   transducer_greedy_decode_fused        either        none, or as above         -     1..2    -                    */
+typedef struct mi355x_transducer_greedy_desc {
+  const void* enc_proj; const void* enc_len;                                           /* input (enc_len i64 [B])        */
+  const void* emb; const void* w_ih; const void* w_hh; const void* w_pred; const void* w_out;   /* weights               */
+  const void* b_ih; const void* b_hh; const void* b_pred; const void* b_out;
+  const int* durations;                                                                /* TDT: host array [D]            */
+  void* tokens; void* times; void* out_len; void* score; void* h_out; void* c_out;     /* outputs                        */
+  const mi355x_rnnt_stream_state* state_in; const mi355x_rnnt_stream_state* state_out; /* resumable                      */
+  const mi355x_transducer_conf* conf; void* tok_conf;                                  /* confidence                     */
+  const mi355x_ctc_beam_fusion* models; const int* m_state_in; int* m_state_out;       /* fusion: models[n_models]       */
+  long long ldf, ld_ih, ld_hh, ld_pred, ld_out;
+  int f_dtype, w_dtype;
+  int B, T, J, H, V1, blank, max_symbols, max_out;
+  int D, n_models;
+} mi355x_transducer_greedy_desc;
+int mi355x_transducer_greedy_decode(const mi355x_transducer_greedy_desc* d, void* stream);
 
 /* ---- cache-aware streaming inference (ConformerEncoder.cache_aware_stream_step; the `update_cache` paths of
  * RelPositionMultiHeadAttention and CausalConv1D).  Caches are f32 in the reference's layouts; in bf16 compute they hold the

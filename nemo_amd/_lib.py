@@ -65,6 +65,22 @@ class PackEntry(C.Structure):
     ]
 
 
+class TransducerConf(C.Structure):
+    """mirror of `mi355x_transducer_conf`"""
+    _fields_ = [("method", i32), ("norm", i32), ("alpha", f32), ("k0", f32), ("k1", f32), ("k2", f32)]
+
+
+class TransducerGreedyDesc(C.Structure):
+    """mirror of `mi355x_transducer_greedy_desc`; state_in / state_out point to mi355x_rnnt_stream_state, conf to a TransducerConf,
+    models to mi355x_ctc_beam_fusion[n_models], durations to int[D] on the host"""
+    _fields_ = (
+        [(n, vp) for n in ("enc_proj", "enc_len", "emb", "w_ih", "w_hh", "w_pred", "w_out", "b_ih", "b_hh", "b_pred", "b_out",
+                           "durations", "tokens", "times", "out_len", "score", "h_out", "c_out", "state_in", "state_out", "conf",
+                           "tok_conf", "models", "m_state_in", "m_state_out")]
+        + [(n, i64) for n in ("ldf", "ld_ih", "ld_hh", "ld_pred", "ld_out")]
+        + [(n, i32) for n in ("f_dtype", "w_dtype", "B", "T", "J", "H", "V1", "blank", "max_symbols", "max_out", "D", "n_models")])
+
+
 # name -> argtypes (return type is always int, except the version string)
 SIGNATURES = {
     "mi355x_gemm": [C.POINTER(GemmDesc), vp],
@@ -191,8 +207,7 @@ SIGNATURES = {
     "mi355x_fill_f32": [vp, i64, f32, vp],
     "mi355x_rnnt_workspace_elems": [i32, i32, i32, vp],
     "mi355x_rnnt_loss": [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, i64, vp],
-    "mi355x_rnnt_greedy_decode": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32,
-                                  i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp],
+    "mi355x_transducer_greedy_decode": [C.POINTER(TransducerGreedyDesc), vp],
     "mi355x_dwconv_config": [i32],
     "mi355x_ctc_config": [i32],
     "mi355x_ctc_align_config": [i32],
@@ -215,26 +230,6 @@ SIGNATURES = {
     "mi355x_rnnt_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
     "mi355x_tdt_workspace_elems": [i32, i32, i32, i32, vp],
     "mi355x_tdt_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
-    "mi355x_tdt_greedy_decode": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32,
-                                 i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp],
-    "mi355x_rnnt_greedy_decode_stream": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32,
-                                         i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp],
-    "mi355x_tdt_greedy_decode_stream": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32,
-                                        i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp],
-    # the *_conf searches: their sibling's arguments with (tok_conf, method, norm, alpha, k0, k1, k2) in front of the stream
-    "mi355x_rnnt_greedy_decode_conf": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32,
-                                       i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp],
-    "mi355x_tdt_greedy_decode_conf": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32,
-                                      i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp],
-    "mi355x_rnnt_greedy_decode_stream_conf": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32,
-                                              i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp],
-    "mi355x_tdt_greedy_decode_stream_conf": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32,
-                                             i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32,
-                                             vp],
-    # mi355x_tdt_greedy_decode's arguments, then (models: mi355x_ctc_beam_fusion[n_models], n_models, state_in, state_out: pointers
-    # to mi355x_rnnt_fused_state, stream)
-    "mi355x_transducer_greedy_decode_fused": [vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32,
-                                              i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp],
     "mi355x_stream_cache_assemble": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi355x_stream_attn": [vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "mi355x_stream_dwconv": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],

@@ -15,11 +15,11 @@
 // Outputs are integer token ids and frame indices: bit-exact against the oracle restatement (oracle/transducer_ref.py
 // greedy_decode) and the reference-run fixture (tests/golden/ref_rnnt_greedy.json).
 //
-// Token-and-Duration Transducer (mi355x_tdt_greedy_decode, the TDT instance of the same kernel): the output layer has V1 + D rows,
+// Token-and-Duration Transducer (a descriptor with a duration set: the TDT instance of the same kernel): the output layer has V1 + D rows,
 // label arg-max over the first V1 logits, duration arg-max over the last D, and the frame index advances by the predicted
 // duration (a blank by at least one frame; a run of max_symbols labels predicted with duration 0 is moved on by one frame).
 //
-// Resumable search (mi355x_rnnt_greedy_decode_stream / mi355x_tdt_greedy_decode_stream): the same kernel started from a per-stream
+// Resumable search (a descriptor with state_out; mi355x_transducer_greedy_decode is the one entry): the same kernel started from a per-stream
 // decoder state (committed h / c, last label, running score, frames consumed so far; TDT: frames already jumped over and the
 // run of zero-duration labels) and writing the next one, out of place.  hn / cn / gp are NOT carried: they are rebuilt from
 // (h, c, emb[last]) by one prediction step at entry -- the very step `emit` ran after the last label -- so a stream cut into any
@@ -91,7 +91,7 @@ template <> struct RnntDecArg<false, 2> { typedef RnntDecPF t; };
 // one-shot entry points have always launched.  CONF = false likewise: the sums of the confidence measure, their two block
 // reductions and the store in `emit` exist in the CONF = true instantiations alone (the *_conf entry points).
 //
-// NM = the number of fusion models (mi355x_transducer_greedy_decode_fused; STREAM = true, CONF = false only: a one-shot call is a
+// NM = the number of fusion models (a descriptor with `models`; STREAM = true, CONF = false only: a one-shot call is a
 // fresh stream with no state to write).  NM = 0 is the search without models: everything below that names a model sits behind
 // `if constexpr (NM > 0)` and those instantiations are the kernels they were.  With models a step whose arg-max is a label picks
 // the label by rank_v = ((lg[v] - lg[mi]) + alpha_0 * look_0(state_0, v)) + alpha_1 * look_1(state_1, v) over v != blank (a blank
@@ -359,229 +359,93 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
   }
 }
 
-// what the fused entry adds to a launch: the checked models and the per-stream automaton states [B, 2] (null: fresh / none)
-struct RnntFusedArg {
-  const mi355x_ctc_beam_fusion* models; int n_models;
-  const int* ms_in; int* ms_out;
-};
-
-static int greedy_decode_impl(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                              const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh,
-                              const void* w_pred, long long ld_pred, const void* b_pred, const void* w_out, long long ld_out,
-                              const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, const TdtDur* dur, int blank,
-                              int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out,
-                              void* c_out, const mi355x_rnnt_stream_state* sin, const mi355x_rnnt_stream_state* sout,
-                              void* tok_conf, const MiConf* conf, void* stream, const RnntFusedArg* fused = nullptr) {
-  if (!enc_proj || !emb || !w_ih || !w_hh || !b_ih || !b_hh || !w_pred || !w_out || !tokens || !out_len) return MI_ERR_ARG;
-  if (B <= 0 || T <= 0 || J <= 0 || H <= 0 || V1 <= 1 || max_out <= 0 || blank < 0 || blank >= V1) return MI_ERR_ARG;
-  if ((H & 3) || (J & 3) || (ld_ih & 3) || (ld_hh & 3) || (ld_pred & 3) || (ld_out & 3) || (!h_out != !c_out)) return MI_ERR_ARG;
-  if ((f_dtype != MI_DT_F32 && f_dtype != MI_DT_BF16) || (w_dtype != MI_DT_F32 && w_dtype != MI_DT_BF16)) return MI_ERR_ARG;
-  RnntDecPC p;
-  p.f = enc_proj; p.f_dt = f_dtype; p.ldf = ldf; p.enc_len = (const long long*)enc_len; p.emb = (const float*)emb;
-  p.w_ih = w_ih; p.w_hh = w_hh; p.w_pred = w_pred; p.w_out = w_out;
-  p.ld_ih = ld_ih; p.ld_hh = ld_hh; p.ld_pred = ld_pred; p.ld_out = ld_out;
-  p.b_ih = (const float*)b_ih; p.b_hh = (const float*)b_hh; p.b_pred = (const float*)b_pred; p.b_out = (const float*)b_out;
-  p.tokens = (int*)tokens; p.times = (int*)times; p.out_len = (int*)out_len; p.score = (float*)score;
-  p.h_out = (float*)h_out; p.c_out = (float*)c_out;
-  p.B = B; p.T = T; p.J = J; p.H = H; p.V1 = V1; p.blank = blank; p.max_symbols = max_symbols; p.max_out = max_out;
+// ---- the one entry of the greedy searches (include/mi355x_asr.h states the descriptor): RNN-T or TDT, one-shot or resumable, with
+// the confidence of every emitted label or with one or two fusion models.  Every check is here; nothing is launched after a refusal.
+static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, hipStream_t s) {
+  if (!d) return MI_ERR_ARG;
+  if (!d->enc_proj || !d->emb || !d->w_ih || !d->w_hh || !d->b_ih || !d->b_hh || !d->w_pred || !d->w_out || !d->tokens || !d->out_len)
+    return MI_ERR_ARG;
+  const int B = d->B, H = d->H, J = d->J, V1 = d->V1;
+  if (B <= 0 || d->T <= 0 || J <= 0 || H <= 0 || V1 <= 1 || d->max_out <= 0 || d->blank < 0 || d->blank >= V1) return MI_ERR_ARG;
+  if ((H & 3) || (J & 3) || (d->ld_ih & 3) || (d->ld_hh & 3) || (d->ld_pred & 3) || (d->ld_out & 3) || (!d->h_out != !d->c_out))
+    return MI_ERR_ARG;
+  if ((d->f_dtype != MI_DT_F32 && d->f_dtype != MI_DT_BF16) || (d->w_dtype != MI_DT_F32 && d->w_dtype != MI_DT_BF16)) return MI_ERR_ARG;
+  RnntDecPF p;   // the widest block; the base and the confidence block are cut from it below
+  p.f = d->enc_proj; p.f_dt = d->f_dtype; p.ldf = d->ldf; p.enc_len = (const long long*)d->enc_len; p.emb = (const float*)d->emb;
+  p.w_ih = d->w_ih; p.w_hh = d->w_hh; p.w_pred = d->w_pred; p.w_out = d->w_out;
+  p.ld_ih = d->ld_ih; p.ld_hh = d->ld_hh; p.ld_pred = d->ld_pred; p.ld_out = d->ld_out;
+  p.b_ih = (const float*)d->b_ih; p.b_hh = (const float*)d->b_hh; p.b_pred = (const float*)d->b_pred; p.b_out = (const float*)d->b_out;
+  p.tokens = (int*)d->tokens; p.times = (int*)d->times; p.out_len = (int*)d->out_len; p.score = (float*)d->score;
+  p.h_out = (float*)d->h_out; p.c_out = (float*)d->c_out;
+  p.B = B; p.T = d->T; p.J = J; p.H = H; p.V1 = V1; p.blank = d->blank; p.max_symbols = d->max_symbols; p.max_out = d->max_out;
+  const bool tdt = d->D != 0 || d->durations;   // D == 0 with no durations: the RNN-T search
   p.dur = {};
-  if (dur) p.dur = *dur;
-  p.tok_conf = (float*)tok_conf; p.conf = {};
-  if (conf) {   // the *_conf entry points: a measure over the V1 label logits and somewhere to write it
-    if (!tok_conf || !mi_conf_valid(V1, conf->method, conf->norm, conf->alpha)) return MI_ERR_ARG;
-    p.conf = *conf;
-  }
+  if (tdt && tdt_durations(d->D, d->durations, &p.dur)) return MI_ERR_ARG;
+  const bool fused = d->models || d->n_models != 0;
+  if (d->conf && (fused || !d->tok_conf || !mi_conf_valid(V1, d->conf->method, d->conf->norm, d->conf->alpha)))
+    return MI_ERR_ARG;   // (no instantiation has both the confidence sums and the models)
+  if (d->state_in && !d->state_out) return MI_ERR_ARG;
   p.sin = {}; p.sout = {};
   for (int io = 0; io < 2; ++io) {   // a state is given whole (skip / zero_run: TDT only) or not at all
-    const mi355x_rnnt_stream_state* st = io ? sout : sin;
+    const mi355x_rnnt_stream_state* st = io ? d->state_out : d->state_in;
     if (!st) continue;
-    if (!st->h || !st->c || !st->last || !st->score || !st->frames_done || (dur && (!st->skip || !st->zero_run))) return MI_ERR_ARG;
+    if (!st->h || !st->c || !st->last || !st->score || !st->frames_done || (tdt && (!st->skip || !st->zero_run))) return MI_ERR_ARG;
     (io ? p.sout : p.sin) = *st;
   }
   if (p.sin.h && p.sout.h && (p.sin.h == p.sout.h || p.sin.c == p.sout.c)) return MI_ERR_ARG;   // out of place
-  const int D = p.dur.D;
-  const size_t shm = (size_t)(9 * H + 2 * J + V1 + D + 4) * sizeof(float);
-  if (shm > 160 * 1024 - 256) return MI_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (fused) {   // the NM > 0 instantiations: the resumable kernel, from fresh streams and without a state to write in a one-shot call
-    RnntDecPF pf;
-    static_cast<RnntDecP&>(pf) = p;
-    for (int k = 0; k < 2; ++k) {
-      const mi355x_ctc_beam_fusion& m = fused->models[k < fused->n_models ? k : 0];
-      pf.lm[k] = {(const int*)m.state_arc_begin, (const int*)m.arc_tok, (const float*)m.arc_logp, (const int*)m.arc_next,
-                  (const float*)m.state_bo, (const int*)m.state_bo_next, m.n_states, m.n_arcs, m.alpha, m.ub,
-                  (const float*)m.state_final};
+  p.ms_in = nullptr; p.ms_out = nullptr;
+  if (fused) {
+    if (!d->models || d->n_models < 1 || d->n_models > 2 || d->blank != V1 - 1) return MI_ERR_ARG;
+    for (int k = 0; k < d->n_models; ++k) {   // the tables cover the labels 0 .. V1-2 (state 0's arc index is the label)
+      const mi355x_ctc_beam_fusion& m = d->models[k];
+      if (!m.state_arc_begin || !m.arc_tok || !m.arc_logp || !m.arc_next || !m.state_bo || !m.state_bo_next) return MI_ERR_ARG;
+      if (m.n_states < 2 || m.n_arcs < V1 - 1 || !(m.alpha >= 0.f)) return MI_ERR_ARG;   // (a NaN fails its compare)
     }
-    pf.ms_in = fused->ms_in; pf.ms_out = fused->ms_out;
-#define RD_LAUNCH_F(WT, TDT, NM)                                                                                                          \
-  hipFuncSetAttribute((const void*)rnnt_greedy_kernel<WT, TDT, true, false, NM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-  MI_LAUNCH((rnnt_greedy_kernel<WT, TDT, true, false, NM>), dim3(B), dim3(RD_THREADS), shm, s, pf)
-#define RD_LAUNCH_F_NM(WT, TDT) \
-  if (fused->n_models == 1) { RD_LAUNCH_F(WT, TDT, 1); } else { RD_LAUNCH_F(WT, TDT, 2); }
-#define RD_LAUNCH_F_WT(WT) \
-  if (dur) { RD_LAUNCH_F_NM(WT, true) } else { RD_LAUNCH_F_NM(WT, false) }
-    if (w_dtype == MI_DT_F32) { RD_LAUNCH_F_WT(float) } else { RD_LAUNCH_F_WT(bf16_t) }
-#undef RD_LAUNCH_F_WT
-#undef RD_LAUNCH_F_NM
-#undef RD_LAUNCH_F
-    return mi_check_launch();
+    if ((d->state_in && !d->m_state_in) || (d->state_out && !d->m_state_out)) return MI_ERR_ARG;
+    if (d->state_in && d->m_state_in == d->m_state_out) return MI_ERR_ARG;   // out of place
+    for (int k = 0; k < 2; ++k) {   // (room for two whatever n_models: the second slot repeats the first and is not read)
+      const mi355x_ctc_beam_fusion& m = d->models[k < d->n_models ? k : 0];
+      p.lm[k] = {(const int*)m.state_arc_begin, (const int*)m.arc_tok, (const float*)m.arc_logp, (const int*)m.arc_next,
+                 (const float*)m.state_bo, (const int*)m.state_bo_next, m.n_states, m.n_arcs, m.alpha, m.ub,
+                 (const float*)m.state_final};
+    }
+    if (d->state_in) p.ms_in = d->m_state_in;
+    if (d->state_out) p.ms_out = d->m_state_out;
   }
-#define RD_LAUNCH(WT, TDT, STREAM, CONF)                                                                                              \
-  hipFuncSetAttribute((const void*)rnnt_greedy_kernel<WT, TDT, STREAM, CONF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-  MI_LAUNCH((rnnt_greedy_kernel<WT, TDT, STREAM, CONF>), dim3(B), dim3(RD_THREADS), shm, s, (typename RnntDecArg<CONF>::t)p)
-#define RD_LAUNCH_C(WT, CONF)                                                                        \
-  if (sout) { if (dur) { RD_LAUNCH(WT, true, true, CONF); } else { RD_LAUNCH(WT, false, true, CONF); } }   \
-  else { if (dur) { RD_LAUNCH(WT, true, false, CONF); } else { RD_LAUNCH(WT, false, false, CONF); } }
-#define RD_LAUNCH_WT(WT) \
-  if (conf) { RD_LAUNCH_C(WT, true) } else { RD_LAUNCH_C(WT, false) }
-  if (w_dtype == MI_DT_F32) { RD_LAUNCH_WT(float) } else { RD_LAUNCH_WT(bf16_t) }
-#undef RD_LAUNCH_WT
-#undef RD_LAUNCH_C
-#undef RD_LAUNCH
-  return mi_check_launch();
-}
+  const size_t shm = (size_t)(9 * H + 2 * J + V1 + p.dur.D + 4) * sizeof(float);
+  if (shm > 160 * 1024 - 256) return MI_ERR_ARG;
 
-extern "C" int mi355x_rnnt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                         const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                         const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-                                         const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
-                                         int H, int V1, int blank, int max_symbols, void* tokens, void* times, void* out_len,
-                                         void* score, int max_out, void* h_out, void* c_out, void* stream) {
-  mi_clear_errors();
-  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len, score,
-                            max_out, h_out, c_out, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-extern "C" int mi355x_tdt_greedy_decode(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                        const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh, const void* b_ih,
-                                        const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-                                        const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J,
-                                        int H, int V1, int D, const int* durations, int blank, int max_symbols, void* tokens,
-                                        void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out,
-                                        void* stream) {
-  mi_clear_errors();
-  TdtDur dur;
-  if (tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
-  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len, score,
-                            max_out, h_out, c_out, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-// ---- resumable search: the same launch from / to a per-stream decoder state (state_in NULL = fresh streams; state_out required)
-extern "C" int mi355x_rnnt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                                const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh,
-                                                const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred,
-                                                const void* b_pred, const void* w_out, long long ld_out, const void* b_out,
-                                                int w_dtype, int B, int T, int J, int H, int V1, int blank, int max_symbols,
-                                                void* tokens, void* times, void* out_len, int max_out,
-                                                const mi355x_rnnt_stream_state* state_in,
-                                                const mi355x_rnnt_stream_state* state_out, void* stream) {
-  mi_clear_errors();
-  if (!state_out) return MI_ERR_ARG;
-  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len,
-                            nullptr, max_out, nullptr, nullptr, state_in, state_out, nullptr, nullptr, stream);
-}
-
-extern "C" int mi355x_tdt_greedy_decode_stream(const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb,
-                                               const void* w_ih, long long ld_ih, const void* w_hh, long long ld_hh,
-                                               const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred,
-                                               const void* b_pred, const void* w_out, long long ld_out, const void* b_out,
-                                               int w_dtype, int B, int T, int J, int H, int V1, int D, const int* durations,
-                                               int blank, int max_symbols, void* tokens, void* times, void* out_len, int max_out,
-                                               const mi355x_rnnt_stream_state* state_in,
-                                               const mi355x_rnnt_stream_state* state_out, void* stream) {
-  mi_clear_errors();
-  TdtDur dur;
-  if (!state_out || tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
-  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len,
-                            nullptr, max_out, nullptr, nullptr, state_in, state_out, nullptr, nullptr, stream);
-}
-
-// ---- the four searches with the confidence of every emitted label (tok_conf f32 [B, max_out], 0.0 padded): the CONF = true
-// instantiations.  Everything else they write is what their siblings write.
-extern "C" int mi355x_rnnt_greedy_decode_conf(
-    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
-    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int blank, int max_symbols, void* tokens,
-    void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out, void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2, void* stream) {
-  mi_clear_errors();
-  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)V1};
-  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len, score,
-                            max_out, h_out, c_out, nullptr, nullptr, tok_conf, &q, stream);
-}
-
-extern "C" int mi355x_tdt_greedy_decode_conf(
-    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
-    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D, const int* durations, int blank,
-    int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out,
-    void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2, void* stream) {
-  mi_clear_errors();
-  TdtDur dur;
-  if (tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
-  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)V1};
-  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len, score,
-                            max_out, h_out, c_out, nullptr, nullptr, tok_conf, &q, stream);
-}
-
-extern "C" int mi355x_rnnt_greedy_decode_stream_conf(
-    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
-    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int blank, int max_symbols, void* tokens,
-    void* times, void* out_len, int max_out, const mi355x_rnnt_stream_state* state_in, const mi355x_rnnt_stream_state* state_out,
-    void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2, void* stream) {
-  mi_clear_errors();
-  if (!state_out) return MI_ERR_ARG;
-  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)V1};
-  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, nullptr, blank, max_symbols, tokens, times, out_len,
-                            nullptr, max_out, nullptr, nullptr, state_in, state_out, tok_conf, &q, stream);
-}
-
-extern "C" int mi355x_tdt_greedy_decode_stream_conf(
-    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
-    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D, const int* durations, int blank,
-    int max_symbols, void* tokens, void* times, void* out_len, int max_out, const mi355x_rnnt_stream_state* state_in,
-    const mi355x_rnnt_stream_state* state_out, void* tok_conf, int method, int norm, float alpha, float k0, float k1, float k2, void* stream) {
-  mi_clear_errors();
-  TdtDur dur;
-  if (!state_out || tdt_durations(D, durations, &dur)) return MI_ERR_ARG;
-  const MiConf q = {method, norm, alpha, k0, k1, k2, (float)V1};
-  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, &dur, blank, max_symbols, tokens, times, out_len,
-                            nullptr, max_out, nullptr, nullptr, state_in, state_out, tok_conf, &q, stream);
-}
-
-// ---- the greedy searches with one or two fusion models (n-gram models, boosting trees: the automata of mi355x_ctc_beam_fusion).
-// One entry for RNN-T (D = 0, durations null) and TDT, one-shot (both states null) and resumable.
-extern "C" int mi355x_transducer_greedy_decode_fused(
-    const void* enc_proj, int f_dtype, long long ldf, const void* enc_len, const void* emb, const void* w_ih, long long ld_ih,
-    const void* w_hh, long long ld_hh, const void* b_ih, const void* b_hh, const void* w_pred, long long ld_pred, const void* b_pred,
-    const void* w_out, long long ld_out, const void* b_out, int w_dtype, int B, int T, int J, int H, int V1, int D, const int* durations,
-    int blank, int max_symbols, void* tokens, void* times, void* out_len, void* score, int max_out, void* h_out, void* c_out,
-    const mi355x_ctc_beam_fusion* models, int n_models, const mi355x_rnnt_fused_state* state_in,
-    const mi355x_rnnt_fused_state* state_out, void* stream) {
-  mi_clear_errors();
-  TdtDur dur;
-  const bool tdt = D != 0 || durations;
-  if (tdt && (!durations || tdt_durations(D, durations, &dur))) return MI_ERR_ARG;
-  if (!models || n_models < 1 || n_models > 2 || V1 < 2 || blank != V1 - 1) return MI_ERR_ARG;
-  for (int k = 0; k < n_models; ++k) {   // the tables cover the labels 0 .. V1-2 (state 0's arc index is the label)
-    const mi355x_ctc_beam_fusion& m = models[k];
-    if (!m.state_arc_begin || !m.arc_tok || !m.arc_logp || !m.arc_next || !m.state_bo || !m.state_bo_next) return MI_ERR_ARG;
-    if (m.n_states < 2 || m.n_arcs < V1 - 1 || !(m.alpha >= 0.f)) return MI_ERR_ARG;   // (a NaN fails its compare)
+  // The 24 instantiations, [weights][TDT][mode]: the one-shot and the resumable kernel, each plain and with confidences, and the
+  // resumable kernel with one and with two models (a fused one-shot call is a fresh stream with no state to write).
+  enum { RD_ONESHOT = 0, RD_STREAM = 2, RD_FUSED = 3 };   // + 1: with confidences / + n_models
+#define RD_ROW(WT, TDT)                                                                                                          \
+  {(const void*)rnnt_greedy_kernel<WT, TDT, false, false>, (const void*)rnnt_greedy_kernel<WT, TDT, false, true>,                \
+   (const void*)rnnt_greedy_kernel<WT, TDT, true, false>, (const void*)rnnt_greedy_kernel<WT, TDT, true, true>,                  \
+   (const void*)rnnt_greedy_kernel<WT, TDT, true, false, 1>, (const void*)rnnt_greedy_kernel<WT, TDT, true, false, 2>}
+  static const void* const kernels[2][2][6] = {{RD_ROW(float, false), RD_ROW(float, true)},
+                                               {RD_ROW(bf16_t, false), RD_ROW(bf16_t, true)}};
+#undef RD_ROW
+  const int mode = fused ? RD_FUSED + d->n_models : (d->state_out ? RD_STREAM : RD_ONESHOT) + (d->conf ? 1 : 0);
+  const void* fn = kernels[d->w_dtype == MI_DT_BF16][tdt][mode];
+  hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  // the three parameter blocks are the three signatures
+  auto issue = [&](auto kernel, const auto& block) { MI_LAUNCH(kernel, dim3(B), dim3(RD_THREADS), shm, s, block); };
+  if (fused) {
+    issue((void (*)(RnntDecPF))fn, p);
+  } else if (d->conf) {
+    RnntDecPC pc;
+    static_cast<RnntDecP&>(pc) = p;
+    pc.tok_conf = (float*)d->tok_conf;
+    pc.conf = {d->conf->method, d->conf->norm, d->conf->alpha, d->conf->k0, d->conf->k1, d->conf->k2, (float)V1};
+    issue((void (*)(RnntDecPC))fn, pc);
+  } else {
+    issue((void (*)(RnntDecP))fn, static_cast<const RnntDecP&>(p));
   }
-  if ((state_in && !state_in->m_state) || (state_out && !state_out->m_state)) return MI_ERR_ARG;
-  if (state_in && (!state_out || state_in->m_state == state_out->m_state)) return MI_ERR_ARG;   // resumable: out of place
-  const RnntFusedArg fz = {models, n_models, state_in ? state_in->m_state : nullptr, state_out ? state_out->m_state : nullptr};
-  return greedy_decode_impl(enc_proj, f_dtype, ldf, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                            w_out, ld_out, b_out, w_dtype, B, T, J, H, V1, tdt ? &dur : nullptr, blank, max_symbols, tokens, times,
-                            out_len, score, max_out, h_out, c_out, state_in ? &state_in->s : nullptr,
-                            state_out ? &state_out->s : nullptr, nullptr, nullptr, stream, &fz);
+  return MI_OK;
+}
+
+extern "C" int mi355x_transducer_greedy_decode(const mi355x_transducer_greedy_desc* d, void* stream) {
+  mi_clear_errors();
+  const int rc = greedy_decode_impl(d, (hipStream_t)stream);
+  return rc != MI_OK ? rc : mi_check_launch();
 }

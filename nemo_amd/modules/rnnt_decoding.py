@@ -7,7 +7,7 @@ Mirrors the pieces of the reference a training run touches (names, argument mean
   * `WER` for transducers (metrics/wer.py:210-356: `update(predictions = encoder output, predictions_lengths, targets,
     targets_lengths)` decodes, then accumulates edit distance / reference words).
 The reference's search is a Python loop over frames with a device -> host sync per inner iteration; here the whole batch is ONE
-launch (`mi355x_rnnt_greedy_decode`, csrc/rnnt_decode.hip): the encoder projection is a GEMM, a workgroup per utterance runs the
+launch (`mi355x_transducer_greedy_decode`, csrc/rnnt_decode.hip): the encoder projection is a GEMM, a workgroup per utterance runs the
 LSTM / joint / arg-max recurrence out of LDS, and only the token ids leave the device -- when text is asked for.
 
 Four documented differences to the reference's search (token ids / time stamps / lengths are bit-identical to it, tests/test_rnnt_decoding.py):
@@ -22,19 +22,19 @@ Four documented differences to the reference's search (token ids / time stamps /
 Streaming: `forward(..., partial_hypotheses=hyps)` (the first chunk: `hyps = decoder.fresh_hypotheses(B)`; without
 `partial_hypotheses` the call is the one-shot search it has always been) resumes every stream from the decoder state its hypothesis carries
 (`Hypothesis.dec_state`, an `ops.RNNTStreamState` of batch 1 on the device: committed LSTM state, last label, running score, frames
-done, and for TDT the frames a duration already jumped over) through the resumable search (`mi355x_rnnt_greedy_decode_stream` /
-`mi355x_tdt_greedy_decode_stream`); the returned hypotheses cover the whole stream so far and are new objects.  Over the same
+done, and for TDT the frames a duration already jumped over) through the resumable search (the same entry with a
+state to write); the returned hypotheses cover the whole stream so far and are new objects.  Over the same
 encoder-projection values, any cut into chunks gives bit-identical hypotheses to one call over the concatenation.
 
 Confidence (`confidence_cfg`, modules/confidence.py): with token or word confidence asked for the search runs through the `_conf`
-entry points (`mi355x_rnnt_greedy_decode_conf` and its siblings): the measure of the label distribution of every step that emitted
+functions of `ops` (the same entry with a measure in the descriptor): the measure of the label distribution of every step that emitted
 a label, computed inside the search from the logits it already holds.  `Hypothesis.token_confidence` has one value per label
 (streaming: appended chunk by chunk) whenever token OR word confidence is preserved, since `RNNTDecoding` folds the words'
 `word_confidence` from it.  Blank steps are not kept, so
 `preserve_frame_confidence` (and `preserve_alignments`) stay unavailable.
 
 Shallow fusion (`fusion_models=[(NGramLM | BoostingTree, alpha), ...]`, one or two; `decoding.greedy.ngram_lm_arpa` /
-`decoding.greedy.boosting_tree` in a model's config): the search runs through `mi355x_transducer_greedy_decode_fused`, whose rule
+`decoding.greedy.boosting_tree` in a model's config): the search runs through `ops.transducer_greedy_decode_fused`, whose rule
 include/mi355x_asr.h states -- a step whose arg-max is a label emits the label that ranks highest with the models' look-ups added,
 a blank stays a blank, and the score of a hypothesis carries the models' terms, a phrase begun and not finished taken back.  The
 stream state is an `ops.RNNTFusedStreamState` (one automaton state per model and stream) and a streaming `Hypothesis.score` is the
@@ -255,8 +255,8 @@ class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
     Token-and-Duration Transducer, whose joint appends one logit per duration behind the V+1 label logits.  Per utterance the
     label is the arg-max of the label logits, the duration the arg-max of the duration logits; a blank moves on by
     max(duration, 1) frames, a label by its duration, and the `max_symbols`-th consecutive label of duration 0 by one frame.
-    One launch for the batch (`mi355x_tdt_greedy_decode`; streaming: `mi355x_tdt_greedy_decode_stream`, a duration that jumps past
-    the end of a chunk is taken off the next one)."""
+    One launch for the batch (`mi355x_transducer_greedy_decode` with the duration set; streaming: a duration that jumps past the end
+    of a chunk is taken off the next one)."""
 
     def __init__(self, decoder_model, joint_model, blank_index: int, durations, max_symbols_per_step: Optional[int] = None,
                  **kw):

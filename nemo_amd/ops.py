@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import ConvGather, GemmDesc, PackEntry, RowMap, check, lib
+from ._lib import ConvGather, GemmDesc, PackEntry, RowMap, TransducerConf, TransducerGreedyDesc, check, lib
 
 F32, BF16 = 0, 1
 EPI_STORE, EPI_SWISH_DROP, EPI_RESID, EPI_DSWISH, EPI_RELU_MASK, EPI_MUL_POS, EPI_SWISH_DROP_G, EPI_DSWISH_G = range(8)
@@ -1009,51 +1009,84 @@ def rnnt_loss(acts, labels, act_lens, label_lens, blank, grads=None, fastemit_la
                              clamp=clamp, grad_scale=grad_scale)
 
 
-def _greedy_decode(tdt, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
-                   blank, durations, max_symbols, max_out, with_state, method=None):
-    """the one-shot searches: buffers, argument tuple and the entry point of (RNN-T | TDT) x (plain | `method` given: the _conf form)"""
+def _greedy_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
+                   blank, durations, max_symbols, max_out, *, with_state=False, stream=None, state=None, method=None, models=None):
+    """every greedy transducer search: the outputs, the descriptor and the one entry (mi355x_transducer_greedy_decode).  `durations`
+    given: TDT.  `stream` = the state class of the resumable search (None: one-shot), `state` = the state to start from (None: fresh
+    streams).  `method` = the confidence measure, `models` = the checked fusion models.  -> (tokens, times, out_len), then whatever
+    was asked for, in this order: score (every search but the resumable one without models), (h, c) (`with_state`), the next state
+    (`stream`), tok_conf (`method`)."""
+    if state is not None and not isinstance(state, stream):
+        raise TypeError(f"{what}: `state` must be an {stream.__name__}, got {type(state).__name__}")
     B, T, J = enc_proj.shape
     V1, H = emb.shape
     if max_out is None:
         max_out = T * max_symbols if max_symbols > 0 else 4 * T
     dev = enc_proj.device
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
     tokens = torch.empty(B, max_out, dtype=torch.int32, device=dev)
     times = torch.empty(B, max_out, dtype=torch.int32, device=dev)
     out_len = torch.empty(B, dtype=torch.int32, device=dev)
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    h = torch.empty(B, H, dtype=torch.float32, device=dev) if with_state else None
-    c = torch.empty(B, H, dtype=torch.float32, device=dev) if with_state else None
-    head = (_ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih, _ptr(w_hh), ld_hh,
-            _ptr(b_ih), _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out), ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1)
-    if tdt:
-        head += _tdt_durations(durations)
-    tail = (blank, max_symbols, _ptr(tokens), _ptr(times), _ptr(out_len), _ptr(score), max_out, _ptr(h), _ptr(c))
-    name = ("tdt" if tdt else "rnnt") + "_greedy_decode" + ("_conf" if method is not None else "")
-    extra = ()
-    if method is not None:   # the _conf entries: the confidence of every emitted label
-        tok_conf = torch.empty(B, max_out, dtype=torch.float32, device=dev)
-        tail += (_ptr(tok_conf), *method)
-        extra = (tok_conf,)
-    check(getattr(lib, "mi355x_" + name)(*head, *tail, _stream()), name)
-    return (tokens, times, out_len, score) + (((h, c),) if with_state else ()) + extra
+    d = TransducerGreedyDesc(
+        enc_proj=_ptr(enc_proj), f_dtype=dt(enc_proj), ldf=enc_proj.stride(1), enc_len=_ptr(enc_len), emb=_ptr(emb),
+        w_ih=_ptr(w_ih), ld_ih=ld_ih, w_hh=_ptr(w_hh), ld_hh=ld_hh, w_pred=_ptr(w_pred), ld_pred=ld_pred, w_out=_ptr(w_out),
+        ld_out=ld_out, w_dtype=dt(w_ih), b_ih=_ptr(b_ih), b_hh=_ptr(b_hh), b_pred=_ptr(b_pred), b_out=_ptr(b_out),
+        B=B, T=T, J=J, H=H, V1=V1, blank=blank, max_symbols=max_symbols, max_out=max_out,
+        tokens=_ptr(tokens), times=_ptr(times), out_len=_ptr(out_len))
+    out = (tokens, times, out_len)
+    keep = []   # what the descriptor points to on the host, alive until the call returns
+    if durations is not None:
+        d.D, dur = _tdt_durations(durations)
+        d.durations = C.addressof(dur)
+        keep.append(dur)
+    if stream is None or models is not None:
+        score = f32(B)
+        d.score = _ptr(score)
+        out += (score,)
+    if with_state:
+        h, c = f32(B, H), f32(B, H)
+        d.h_out, d.c_out = _ptr(h), _ptr(c)
+        out += ((h, c),)
+    if stream is not None:
+        nxt = stream.empty(B, H, dev)
+        if durations is None:   # (not written by the RNN-T search)
+            nxt.skip.zero_(); nxt.zero_run.zero_()
+        for field, st in (("state_in", state), ("state_out", nxt)):
+            if st is not None:
+                keep.append(st._c(B, H))
+                setattr(d, field, C.addressof(keep[-1]))
+                if models is not None:
+                    setattr(d, "m_" + field, _ptr(st.m_state))
+        out += (nxt,)
+    if method is not None:   # the confidence of every emitted label
+        tok_conf = f32(B, max_out)
+        keep.append(TransducerConf(*method))
+        d.conf, d.tok_conf = C.addressof(keep[-1]), _ptr(tok_conf)
+        out += (tok_conf,)
+    if models is not None:
+        arr, tables = _ctc_beam_fusion_array(models, enc_proj)
+        keep += [arr, tables]
+        d.models, d.n_models = C.addressof(arr), len(arr)
+    check(lib.mi355x_transducer_greedy_decode(C.byref(d), _stream()), what)
+    return out
 
 
 def rnnt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
                        blank, max_symbols, max_out=None, with_state=False):
-    """greedy transducer search of a whole batch in one launch (mi355x_rnnt_greedy_decode).  enc_proj [B, T, J] = joint.enc(encoder
-    output); weights fp32 or bf16 (all four the same dtype).  -> (tokens i32 [B, max_out] -1 padded, frame indices likewise,
+    """greedy transducer search of a whole batch in one launch (mi355x_transducer_greedy_decode).  enc_proj [B, T, J] = joint.enc(
+    encoder output); weights fp32 or bf16 (all four the same dtype).  -> (tokens i32 [B, max_out] -1 padded, frame indices likewise,
     lengths i32 [B], score f32 [B][, (h, c) f32 [B, H]])"""
-    return _greedy_decode(False, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                          b_out, blank, None, max_symbols, max_out, with_state)
+    return _greedy_search("rnnt_greedy_decode", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                          w_out, ld_out, b_out, blank, None, max_symbols, max_out, with_state=with_state)
 
 
 def rnnt_greedy_decode_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
                             b_out, blank, max_symbols, method, max_out=None, with_state=False):
-    """rnnt_greedy_decode plus the confidence of every emitted label (mi355x_rnnt_greedy_decode_conf): `method` = (method, norm,
-    alpha, k0, k1, k2) for V = V1 (modules.confidence.ConfidenceMethodConfig.kernel_args) -> rnnt_greedy_decode's tuple with
-    tok_conf f32 [B, max_out] (0.0 padded) appended"""
-    return _greedy_decode(False, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                          b_out, blank, None, max_symbols, max_out, with_state, method=method)
+    """rnnt_greedy_decode plus the confidence of every emitted label (mi355x_transducer_greedy_decode with a measure): `method` =
+    (method, norm, alpha, k0, k1, k2) for V = V1 (modules.confidence.ConfidenceMethodConfig.kernel_args) -> rnnt_greedy_decode's
+    tuple with tok_conf f32 [B, max_out] (0.0 padded) appended"""
+    return _greedy_search("rnnt_greedy_decode_conf", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred,
+                          b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, with_state=with_state, method=method)
 
 
 def _tdt_durations(durations):
@@ -1080,17 +1113,18 @@ def tdt_loss(acts, labels, act_lens, label_lens, blank, durations, grads=None, s
 
 def tdt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
                       blank, durations, max_symbols, max_out=None, with_state=False):
-    """greedy TDT search of a whole batch in one launch (mi355x_tdt_greedy_decode): as rnnt_greedy_decode, with w_out / b_out
-    holding V1 + len(durations) rows (label logits, then duration logits); frames advance by the predicted duration"""
-    return _greedy_decode(True, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                          b_out, blank, durations, max_symbols, max_out, with_state)
+    """greedy TDT search of a whole batch in one launch (mi355x_transducer_greedy_decode with a duration set): as rnnt_greedy_decode,
+    with w_out / b_out holding V1 + len(durations) rows (label logits, then duration logits); frames advance by the predicted duration"""
+    return _greedy_search("tdt_greedy_decode", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                          w_out, ld_out, b_out, blank, durations, max_symbols, max_out, with_state=with_state)
 
 
 def tdt_greedy_decode_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
                            b_out, blank, durations, max_symbols, method, max_out=None, with_state=False):
-    """tdt_greedy_decode plus the confidence of every emitted label over the V1 label logits (mi355x_tdt_greedy_decode_conf)"""
-    return _greedy_decode(True, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                          b_out, blank, durations, max_symbols, max_out, with_state, method=method)
+    """tdt_greedy_decode plus the confidence of every emitted label over the V1 label logits (mi355x_transducer_greedy_decode with
+    a duration set and a measure)"""
+    return _greedy_search("tdt_greedy_decode_conf", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred,
+                          b_pred, w_out, ld_out, b_out, blank, durations, max_symbols, max_out, with_state=with_state, method=method)
 
 
 class _StreamStateC(C.Structure):   # mi355x_rnnt_stream_state
@@ -1140,78 +1174,47 @@ class RNNTStreamState:
         return _StreamStateC(*(_ptr(t) for t in self.tensors()))
 
 
-def _greedy_decode_stream(tdt, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                          b_out, blank, durations, max_symbols, state, max_out, method=None):
-    B, T, J = enc_proj.shape
-    V1, H = emb.shape
-    if max_out is None:
-        max_out = T * max_symbols if max_symbols > 0 else 4 * T
-    dev = enc_proj.device
-    tokens = torch.empty(B, max_out, dtype=torch.int32, device=dev)
-    times = torch.empty(B, max_out, dtype=torch.int32, device=dev)
-    out_len = torch.empty(B, dtype=torch.int32, device=dev)
-    nxt = RNNTStreamState.empty(B, H, dev)
-    if not tdt:   # (not written by the RNN-T search)
-        nxt.skip.zero_(); nxt.zero_run.zero_()
-    s_in = state._c(B, H) if state is not None else None
-    s_out = nxt._c(B, H)
-    head = (_ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih, _ptr(w_hh), ld_hh,
-            _ptr(b_ih), _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out), ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1)
-    if tdt:
-        head += _tdt_durations(durations)
-    tail = (blank, max_symbols, _ptr(tokens), _ptr(times), _ptr(out_len), max_out, C.byref(s_in) if s_in is not None else None,
-            C.byref(s_out))
-    name = ("tdt" if tdt else "rnnt") + "_greedy_decode_stream" + ("_conf" if method is not None else "")
-    extra = ()
-    if method is not None:   # the _conf entries: the chunk's labels with their confidences
-        tok_conf = torch.empty(B, max_out, dtype=torch.float32, device=dev)
-        tail += (_ptr(tok_conf), *method)
-        extra = (tok_conf,)
-    check(getattr(lib, "mi355x_" + name)(*head, *tail, _stream()), name)
-    return (tokens, times, out_len, nxt) + extra
-
-
 def rnnt_greedy_decode_stream(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
                               b_out, blank, max_symbols, state=None, max_out=None):
-    """one chunk of the resumable greedy transducer search (mi355x_rnnt_greedy_decode_stream): rnnt_greedy_decode's arguments, with
-    enc_len = the frames of this chunk per stream, and `state` = the RNNTStreamState the previous chunk returned (None: fresh
-    streams).  -> (tokens, global frame indices, lengths of THIS chunk's labels, the next RNNTStreamState; its `score` is the
+    """one chunk of the resumable greedy transducer search (mi355x_transducer_greedy_decode with a state to write):
+    rnnt_greedy_decode's arguments, with enc_len = the frames of this chunk per stream, and `state` = the RNNTStreamState the
+    previous chunk returned (None: fresh streams).  -> (tokens, global frame indices, lengths of THIS chunk's labels, the next RNNTStreamState; its `score` is the
     stream's running score).  Any cut of a stream into chunks gives bit-identical results to one launch over all of it."""
-    return _greedy_decode_stream(False, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
-                                 ld_out, b_out, blank, None, max_symbols, state, max_out)
+    return _greedy_search("rnnt_greedy_decode_stream", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred,
+                          b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, stream=RNNTStreamState, state=state)
 
 
 def tdt_greedy_decode_stream(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
                              b_out, blank, durations, max_symbols, state=None, max_out=None):
-    """one chunk of the resumable greedy TDT search (mi355x_tdt_greedy_decode_stream): as rnnt_greedy_decode_stream; a duration
-    that jumps past the chunk's end is carried in the state (`skip`) and taken off the next chunk(s)"""
-    return _greedy_decode_stream(True, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
-                                 ld_out, b_out, blank, durations, max_symbols, state, max_out)
+    """one chunk of the resumable greedy TDT search (mi355x_transducer_greedy_decode with a duration set and a state to write): as
+    rnnt_greedy_decode_stream; a duration that jumps past the chunk's end is carried in the state (`skip`) and taken off the next
+    chunk(s)"""
+    return _greedy_search("tdt_greedy_decode_stream", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred,
+                          b_pred, w_out, ld_out, b_out, blank, durations, max_symbols, max_out, stream=RNNTStreamState, state=state)
 
 
 def rnnt_greedy_decode_stream_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
                                    b_out, blank, max_symbols, method, state=None, max_out=None):
-    """rnnt_greedy_decode_stream plus the confidence of this chunk's labels (mi355x_rnnt_greedy_decode_stream_conf) -> (tokens,
-    global frame indices, lengths, next state, tok_conf f32 [B, max_out] 0.0 padded); bit-identical to one launch for any cut"""
-    return _greedy_decode_stream(False, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
-                                 ld_out, b_out, blank, None, max_symbols, state, max_out, method=method)
+    """rnnt_greedy_decode_stream plus the confidence of this chunk's labels (mi355x_transducer_greedy_decode with a state to write
+    and a measure) -> (tokens, global frame indices, lengths, next state, tok_conf f32 [B, max_out] 0.0 padded); bit-identical to one launch for any cut"""
+    return _greedy_search("rnnt_greedy_decode_stream_conf", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred,
+                          ld_pred, b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, stream=RNNTStreamState,
+                          state=state, method=method)
 
 
 def tdt_greedy_decode_stream_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
                                   b_out, blank, durations, max_symbols, method, state=None, max_out=None):
-    """tdt_greedy_decode_stream plus the confidence of this chunk's labels (mi355x_tdt_greedy_decode_stream_conf)"""
-    return _greedy_decode_stream(True, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
-                                 ld_out, b_out, blank, durations, max_symbols, state, max_out, method=method)
-
-
-class _FusedStreamStateC(C.Structure):   # mi355x_rnnt_fused_state
-    _fields_ = [("s", _StreamStateC), ("m_state", C.c_void_p)]
+    """tdt_greedy_decode_stream plus the confidence of this chunk's labels (mi355x_transducer_greedy_decode with a duration set, a
+    state to write and a measure)"""
+    return _greedy_search("tdt_greedy_decode_stream_conf", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred,
+                          ld_pred, b_pred, w_out, ld_out, b_out, blank, durations, max_symbols, max_out, stream=RNNTStreamState,
+                          state=state, method=method)
 
 
 class RNNTFusedStreamState(RNNTStreamState):
-    """the state of the fused greedy search (mi355x_rnnt_fused_state): RNNTStreamState and m_state i32 [B, 2], the automaton state
-    of fusion model m in column m (fresh stream: 1; column 1 stays 1 with one model).  `score` is the running score without the
-    models' final terms."""
+    """the state of the fused greedy search (the descriptor's states and m_state_in / m_state_out): RNNTStreamState and m_state i32
+    [B, 2], the automaton state of fusion model m in column m (fresh stream: 1; column 1 stays 1 with one model).  `score` is the
+    running score without the models' final terms."""
     __slots__ = ("m_state",)
     _base = RNNTStreamState.__slots__
 
@@ -1237,7 +1240,7 @@ class RNNTFusedStreamState(RNNTStreamState):
         m = self.m_state
         if tuple(m.shape) != (B, 2) or m.dtype != torch.int32 or not m.is_contiguous():
             raise ValueError(f"stream state `m_state`: expected contiguous torch.int32 {(B, 2)}, got {m.dtype} {tuple(m.shape)}")
-        return _FusedStreamStateC(RNNTStreamState(*self.tensors()[:len(self._base)])._c(B, H), _ptr(m))
+        return RNNTStreamState(*self.tensors()[:len(self._base)])._c(B, H)   # (m_state travels beside it in the descriptor)
 
 
 def _transducer_fusion_check(what, models, V1):
@@ -1257,7 +1260,7 @@ def _transducer_fusion_check(what, models, V1):
 
 def transducer_greedy_decode_fused(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
                                    b_out, blank, max_symbols, models, durations=None, state=None, max_out=None):
-    """the greedy transducer search with shallow fusion (mi355x_transducer_greedy_decode_fused, which include/mi355x_asr.h states):
+    """the greedy transducer search with shallow fusion (mi355x_transducer_greedy_decode with models, which include/mi355x_asr.h states):
     rnnt_greedy_decode's arguments, `models` = a list of one or two (NGramLM | BoostingTree, alpha) as in `ctc_beam_decode_fused`,
     `durations` for the TDT search.  A step whose arg-max is a label emits the label that ranks highest with the models' look-ups
     added; a blank stays a blank.  `state` None: the one-shot search -> (tokens, frame indices, lengths, score, (h, c)).  `state` an
@@ -1267,34 +1270,10 @@ def transducer_greedy_decode_fused(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld
     `score` is the running one.  Any cut into chunks gives the bits of one launch; every alpha = 0 the bits of the searches
     without models."""
     what = "transducer_greedy_decode_fused"
-    B, T, J = enc_proj.shape
-    V1, H = emb.shape
-    models = _transducer_fusion_check(what, models, V1)
-    if state is not None and not isinstance(state, RNNTFusedStreamState):
-        raise TypeError(f"{what}: `state` must be an RNNTFusedStreamState, got {type(state).__name__}")
-    if max_out is None:
-        max_out = T * max_symbols if max_symbols > 0 else 4 * T
-    dev = enc_proj.device
-    tokens = torch.empty(B, max_out, dtype=torch.int32, device=dev)
-    times = torch.empty(B, max_out, dtype=torch.int32, device=dev)
-    out_len = torch.empty(B, dtype=torch.int32, device=dev)
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    h = c = nxt = s_in = s_out = None
-    if state is None:
-        h, c = (torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(2))
-    else:
-        nxt = RNNTFusedStreamState.empty(B, H, dev)
-        if durations is None:   # (not written by the RNN-T search)
-            nxt.skip.zero_(); nxt.zero_run.zero_()
-        s_in, s_out = state._c(B, H), nxt._c(B, H)
-    arr, keep = _ctc_beam_fusion_array(models, enc_proj)
-    D, dur = _tdt_durations(durations) if durations is not None else (0, None)
-    check(lib.mi355x_transducer_greedy_decode_fused(
-        _ptr(enc_proj), dt(enc_proj), enc_proj.stride(1), _ptr(enc_len), _ptr(emb), _ptr(w_ih), ld_ih, _ptr(w_hh), ld_hh, _ptr(b_ih),
-        _ptr(b_hh), _ptr(w_pred), ld_pred, _ptr(b_pred), _ptr(w_out), ld_out, _ptr(b_out), dt(w_ih), B, T, J, H, V1, D, dur, blank,
-        max_symbols, _ptr(tokens), _ptr(times), _ptr(out_len), _ptr(score), max_out, _ptr(h), _ptr(c), C.cast(arr, C.c_void_p),
-        len(arr), C.byref(s_in) if s_in is not None else None, C.byref(s_out) if s_out is not None else None, _stream()), what)
-    return tokens, times, out_len, score, ((h, c) if state is None else nxt)
+    return _greedy_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                          b_out, blank, durations, max_symbols, max_out, with_state=state is None,
+                          stream=None if state is None else RNNTFusedStreamState, state=state,
+                          models=_transducer_fusion_check(what, models, emb.shape[0]))
 
 
 def row_scale(x, vec, rows, cols):

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY -- float64 restatement of the greedy transducer search with shallow fusion
-(mi355x_transducer_greedy_decode_fused; include/mi355x_asr.h states the rule), built on tests/stream_decode_oracle.py: its prediction
+(mi355x_transducer_greedy_decode with models; include/mi355x_asr.h states the rule), built on tests/stream_decode_oracle.py: its prediction
 step and state, its chunking, with every tensor widened to float64.
 
 The models share nothing with the tables the device walks:

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY -- CPU restatement of the RESUMABLE greedy transducer search (csrc/rnnt_decode.hip:
-mi355x_rnnt_greedy_decode_stream / mi355x_tdt_greedy_decode_stream), fp32 torch, utterance by utterance.
+mi355x_transducer_greedy_decode with a state to write, RNN-T and TDT), fp32 torch, utterance by utterance.
 
 Written from oracle/transducer_ref.greedy_decode and tests/tdt_oracle.tdt_greedy_decode plus the per-stream decoder state:
     h, c          committed LSTM state                                   fresh: 0

@@ -28,7 +28,13 @@ def test_library_exports_every_declared_symbol():
 
 def test_struct_layouts_match_the_header():
     """compile a tiny C program against the header and compare sizeof/offsetof with the ctypes mirrors"""
-    from nemo_amd._lib import GemmDesc, PackEntry
+    from nemo_amd._lib import GemmDesc, PackEntry, TransducerConf, TransducerGreedyDesc
+    # the descriptor of the greedy transducer search and its measure: sizeof and the offsetof of EVERY field, under the mirror's names
+    # (a wrong mirror is a wrong pointer on the device)
+    whole = (("mi355x_transducer_greedy_desc", TransducerGreedyDesc), ("mi355x_transducer_conf", TransducerConf))
+    whole_src = "".join(
+        f'  printf("%zu\\n", sizeof({cname}));\n' + "".join(f'  printf("%zu\\n", offsetof({cname}, {f[0]}));\n' for f in mirror._fields_)
+        for cname, mirror in whole)
     src = r'''
 #include <stdio.h>
 #include <stddef.h>
@@ -39,7 +45,7 @@ int main(){
          offsetof(mi355x_gemm_desc, row_len), offsetof(mi355x_gemm_desc, colsum_out));
   printf("%zu\n", offsetof(mi355x_gemm_desc, colsum_stride));
   printf("%zu %zu\n", sizeof(mi355x_pack_entry), offsetof(mi355x_pack_entry, tile_begin));
-  return 0; }'''
+''' + whole_src + "  return 0; }"
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         c = os.path.join(tmp, "t.c")
@@ -52,7 +58,10 @@ int main(){
     assert vals[:7] == [ctypes.sizeof(G), G.c_col_stride.offset, G.bias.offset, G.aux_in.offset, G.drop_key.offset,
                         G.row_len.offset, G.colsum_out.offset]
     assert vals[7] == G.colsum_stride.offset
-    assert vals[8:] == [ctypes.sizeof(PackEntry), PackEntry.tile_begin.offset]
+    assert vals[8:10] == [ctypes.sizeof(PackEntry), PackEntry.tile_begin.offset]
+    want = [v for _, m in whole for v in [ctypes.sizeof(m)] + [getattr(m, f[0]).offset for f in m._fields_]]
+    assert len(TransducerGreedyDesc._fields_) == 42 and len(TransducerConf._fields_) == 6   # as many as the header's structs have
+    assert vals[10:] == want
 
 
 def test_invalid_arguments_are_rejected_without_a_gpu():

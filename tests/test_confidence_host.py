@@ -132,9 +132,9 @@ def test_the_new_entry_points_are_declared():
     from nemo_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "mi355x_asr.h")).read()
     declared = set(re.findall(r"\bint (mi355x_[a-z0-9_]+)\s*\(", hdr))
-    for name in ("mi355x_ctc_greedy_decode_conf", "mi355x_rnnt_greedy_decode_conf", "mi355x_tdt_greedy_decode_conf",
-                 "mi355x_rnnt_greedy_decode_stream_conf", "mi355x_tdt_greedy_decode_stream_conf"):
+    for name in ("mi355x_ctc_greedy_decode_conf", "mi355x_transducer_greedy_decode"):   # (the transducer searches: one entry)
         assert name in declared and name in _lib.EXPORTED_SYMBOLS and hasattr(_lib.lib, name), name
+    assert "mi355x_transducer_greedy_desc" in hdr and "mi355x_transducer_conf" in hdr
     for macro, value in (("MI355X_CONF_MAX_PROB", 0), ("MI355X_CONF_GIBBS", 1), ("MI355X_CONF_TSALLIS", 2), ("MI355X_CONF_RENYI", 3),
                          ("MI355X_CONF_NORM_LIN", 0), ("MI355X_CONF_NORM_EXP", 1), ("MI355X_CONF_AGG_MEAN", 0),
                          ("MI355X_CONF_AGG_MIN", 1), ("MI355X_CONF_AGG_MAX", 2), ("MI355X_CONF_AGG_PROD", 3)):
@@ -161,17 +161,21 @@ def test_invalid_confidence_arguments_of_the_searches_are_rejected_before_any_la
     from nemo_amd import _lib
     from nemo_amd.ops import _StreamStateC
     one, B, T, J, H, V1 = 1, 2, 8, 32, 32, 49   # non-null stand-ins and valid sizes: only the confidence arguments are wrong
-    head = (one, 0, J, one, one, one, H, one, H, one, one, one, H, one, one, J, one, 0, B, T, J, H, V1)
     dur = (C.c_int * 5)(0, 1, 2, 3, 4)
     state = _StreamStateC(*([one] * 7))
-    fn = getattr(_lib.lib, f"mi355x_{entry.replace('_stream', '')}_greedy_decode{'_stream' if 'stream' in entry else ''}_conf")
 
-    def call(tok_conf=one, method=2, norm=1, alpha=0.33):
-        mid = (5, dur) if entry.startswith("tdt") else ()
-        if "stream" in entry:
-            tail = (V1 - 1, 10, one, one, one, 80, None, C.byref(state))
+    def call(tok_conf=one, method=2, norm=1, alpha=0.33):   # `entry` as descriptor settings of the one entry
+        q = _lib.TransducerConf(method, norm, alpha, 1.0, 1.0, 0.0)
+        d = _lib.TransducerGreedyDesc(
+            enc_proj=one, f_dtype=0, ldf=J, enc_len=one, emb=one, w_ih=one, ld_ih=H, w_hh=one, ld_hh=H, b_ih=one, b_hh=one, w_pred=one,
+            ld_pred=H, b_pred=one, w_out=one, ld_out=J, b_out=one, w_dtype=0, B=B, T=T, J=J, H=H, V1=V1, blank=V1 - 1, max_symbols=10,
+            tokens=one, times=one, out_len=one, max_out=80, conf=C.addressof(q), tok_conf=tok_conf)
+        if entry.startswith("tdt"):
+            d.D, d.durations = 5, C.addressof(dur)
+        if "stream" in entry:   # fresh streams; no score / h / c, as the resumable searches are called
+            d.state_out = C.addressof(state)
         else:
-            tail = (V1 - 1, 10, one, one, one, one, 80, None, None)
-        return fn(*head, *mid, *tail, tok_conf, method, norm, alpha, 1.0, 1.0, 0.0, None)
+            d.score = one
+        return _lib.lib.mi355x_transducer_greedy_decode(C.byref(d), None)
     for kw in (dict(tok_conf=None), dict(alpha=0.0), dict(alpha=-1.0), dict(method=4), dict(method=-1), dict(norm=2), dict(norm=-1)):
         assert call(**kw) == 1, kw

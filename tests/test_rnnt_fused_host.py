@@ -1,6 +1,6 @@
 """CPU: the restatement of the fused greedy transducer search (tests/rnnt_fused_oracle.py) against the unfused restatement and
 against itself, the input conditions of the GPU cases (tests/test_rnnt_fused_gpu.py), the `decoding.greedy` keys and their
-refusals, the stream state with the model states, and the argument checks of mi355x_transducer_greedy_decode_fused."""
+refusals, the stream state with the model states, and the argument checks of mi355x_transducer_greedy_decode."""
 import ctypes as C
 import os
 import re
@@ -270,16 +270,39 @@ def test_op_refuses_wrong_model_lists():
         call([(tree, 1.0)], state=ops.RNNTStreamState.fresh(1, 4, 4, "cpu"))
 
 
+_P = 4096   # non-null: the argument checks return MI_ERR_ARG (1) before anything is launched, the pointers are never followed
+_V1 = 9
+
+
+def _stream_state(**kw):
+    from nemo_amd.ops import _StreamStateC
+    return _StreamStateC(**dict(dict(h=_P, c=_P + 64, last=_P, score=_P, frames_done=_P, skip=_P, zero_run=_P), **kw))
+
+
+def _greedy_rc(s_in=None, s_out=None, conf=None, **kw):
+    """the return code of mi355x_transducer_greedy_decode for a descriptor that is valid (B=2, T=4, J=H=8, V1=9: the RNN-T one-shot
+    search without models) but for the fields given; s_in / s_out = mi355x_rnnt_stream_state, conf = a TransducerConf"""
+    from nemo_amd import _lib
+    d = _lib.TransducerGreedyDesc(
+        enc_proj=_P, f_dtype=0, ldf=8, emb=_P, w_ih=_P, ld_ih=8, w_hh=_P, ld_hh=8, b_ih=_P, b_hh=_P, w_pred=_P, ld_pred=8, b_pred=_P,
+        w_out=_P, ld_out=8, b_out=_P, w_dtype=0, B=2, T=4, J=8, H=8, V1=_V1, blank=_V1 - 1, max_symbols=2, tokens=_P, out_len=_P,
+        max_out=8)
+    for field, obj in (("state_in", s_in), ("state_out", s_out), ("conf", conf)):
+        if obj is not None:
+            setattr(d, field, C.addressof(obj))
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return _lib.lib.mi355x_transducer_greedy_decode(C.byref(d), None)
+
+
 def test_fused_entry_is_exported_declared_and_checks_its_arguments():
     from nemo_amd import _lib
-    name = "mi355x_transducer_greedy_decode_fused"
+    name = "mi355x_transducer_greedy_decode"
     hdr = open(os.path.join(ROOT, "include", "mi355x_asr.h")).read()
-    assert name in set(re.findall(r"\b(mi355x_[a-z0-9_]+)\s*\(", hdr)) and "mi355x_rnnt_fused_state" in hdr
+    assert name in set(re.findall(r"\b(mi355x_[a-z0-9_]+)\s*\(", hdr)) and "mi355x_transducer_greedy_desc" in hdr
     assert name in _lib.EXPORTED_SYMBOLS and hasattr(C.CDLL(_lib.LIB_PATH), name)
-    assert len(_lib.SIGNATURES[name]) == len(_lib.SIGNATURES["mi355x_tdt_greedy_decode"]) + 4
-    from nemo_amd.ops import _CTCBeamFusionC, _FusedStreamStateC, _StreamStateC
-    p = 4096   # non-null: the argument checks return MI_ERR_ARG (1) before anything is launched, the pointers are never followed
-    V1 = 9
+    from nemo_amd.ops import _CTCBeamFusionC
+    p, V1 = _P, _V1
     dur = (C.c_int * 3)(0, 1, 2)
 
     def model(**kw):
@@ -287,22 +310,21 @@ def test_fused_entry_is_exported_declared_and_checks_its_arguments():
                       n_states=4, n_arcs=V1 - 1, alpha=1.0, ub=0.0), **kw)
         return _CTCBeamFusionC(**a)
 
-    def state(m_state=p, **kw):
-        s = dict(dict(h=p, c=p + 64, last=p, score=p, frames_done=p, skip=p, zero_run=p), **kw)
-        return _FusedStreamStateC(_StreamStateC(**s), m_state)
+    def state(m_state=p, **kw):   # a stream state and the automaton states that go with it
+        return _stream_state(**kw), m_state
 
-    def rc(models=(model(),), n_models=None, s_in=None, s_out=None, **kw):
-        a = dict(dict(f=p, emb=p, w=p, b=p, tokens=p, out_len=p, B=2, T=4, J=8, H=8, V1=V1, D=0, dur=None, blank=V1 - 1, max_out=8), **kw)
+    def rc(models=(model(),), n_models=None, s_in=None, s_out=None, w=p, b=p, dur=None, **kw):
         arr = (_CTCBeamFusionC * max(1, len(models)))(*models) if models is not None else None
-        return _lib.lib.mi355x_transducer_greedy_decode_fused(
-            a["f"], 0, 8, None, a["emb"], a["w"], 8, a["w"], 8, a["b"], a["b"], a["w"], 8, a["b"], a["w"], 8, a["b"], 0, a["B"], a["T"],
-            a["J"], a["H"], a["V1"], a["D"], a["dur"], a["blank"], 2, a["tokens"], None, a["out_len"], None, a["max_out"], None, None,
-            C.cast(arr, C.c_void_p) if arr is not None else None, len(models) if n_models is None and models is not None else (n_models or 0),
-            C.byref(s_in) if s_in is not None else None, C.byref(s_out) if s_out is not None else None, None)
+        s_in, m_in = s_in or (None, None)
+        s_out, m_out = s_out or (None, None)
+        return _greedy_rc(s_in, s_out, w_ih=w, w_hh=w, w_pred=w, w_out=w, b_ih=b, b_hh=b, b_pred=b, b_out=b,
+                          durations=C.addressof(dur) if dur is not None else None, models=C.addressof(arr) if arr is not None else None,
+                          n_models=len(models) if n_models is None and models is not None else (n_models or 0),
+                          m_state_in=m_in, m_state_out=m_out, **kw)
 
-    # what the siblings refuse
-    for bad in (dict(f=None), dict(emb=None), dict(w=None), dict(tokens=None), dict(out_len=None), dict(B=0), dict(T=0), dict(H=6),
-                dict(J=6), dict(max_out=0), dict(D=3, dur=None), dict(D=1, dur=dur), dict(D=0, dur=dur)):
+    # what the search without models refuses
+    for bad in (dict(enc_proj=None), dict(emb=None), dict(w=None), dict(tokens=None), dict(out_len=None), dict(B=0), dict(T=0),
+                dict(H=6), dict(J=6), dict(max_out=0), dict(D=3, dur=None), dict(D=1, dur=dur), dict(D=0, dur=dur)):
         assert rc(**bad) == 1, bad
     # the models
     assert rc(models=None, n_models=1) == 1
@@ -320,3 +342,15 @@ def test_fused_entry_is_exported_declared_and_checks_its_arguments():
     assert rc(s_in=state(), s_out=state(m_state=p, h=p + 128, c=p + 192)) == 1         # aliased model states
     assert rc(s_in=state(), s_out=state(m_state=p + 256)) == 1                         # aliased h / c
     assert rc(s_out=state(h=None)) == 1 and rc(D=3, dur=dur, s_out=state(skip=None)) == 1
+
+
+def test_descriptor_entry_refuses_what_no_former_entry_could_be_asked():
+    from nemo_amd import _lib
+    from nemo_amd.ops import _CTCBeamFusionC
+    assert _lib.lib.mi355x_transducer_greedy_decode(None, None) == 1                   # no descriptor
+    # a state to start from and none to write, without models
+    assert _greedy_rc(s_in=_stream_state()) == 1
+    # confidences together with models: the kernel template has no such instantiation
+    arr = (_CTCBeamFusionC * 1)(_CTCBeamFusionC(state_arc_begin=_P, arc_tok=_P, arc_logp=_P, arc_next=_P, state_bo=_P, state_bo_next=_P,
+                                                state_final=None, n_states=4, n_arcs=_V1 - 1, alpha=1.0, ub=0.0))
+    assert _greedy_rc(conf=_lib.TransducerConf(2, 1, 0.33, 1.0, 1.0, 0.0), tok_conf=_P, models=C.addressof(arr), n_models=1) == 1

@@ -157,12 +157,18 @@ def test_tdt_abi_rejects_bad_arguments_without_a_gpu():
     assert lib.mi355x_tdt_loss_ex(*a) == 1
     a = list(args(dur(0, 1, 2), 3)); a[15] = fake; a[16] = 0; a[17] = 10       # gradient pitch < V1 + D
     assert lib.mi355x_tdt_loss_ex(*a) == 1
-    g = [fake, 0, 16, fake, fake, fake, 16, fake, 16, fake, fake, fake, 16, fake, fake, 16, fake, 0, 2, 4, 16, 16, 9, 3, dur(0, 1, 2),
-         8, 10, fake, fake, fake, fake, 40, None, None, None]
-    assert lib.mi355x_tdt_greedy_decode(*g[:24], dur(1, 2, 3), *g[25:]) == 1
-    assert lib.mi355x_tdt_greedy_decode(*g[:23], 9, dur(*range(9)), *g[25:]) == 1
-    g2 = list(g); g2[25] = 9                                                   # blank outside the V1 label logits
-    assert lib.mi355x_tdt_greedy_decode(*g2) == 1
+
+    def greedy(durs=dur(0, 1, 2), **kw):   # the TDT search through the descriptor entry; valid but for what a case overrides
+        d = _lib.TransducerGreedyDesc(
+            enc_proj=16, f_dtype=0, ldf=16, enc_len=16, emb=16, w_ih=16, ld_ih=16, w_hh=16, ld_hh=16, b_ih=16, b_hh=16, w_pred=16,
+            ld_pred=16, b_pred=16, w_out=16, ld_out=16, b_out=16, w_dtype=0, B=2, T=4, J=16, H=16, V1=9, D=len(durs),
+            durations=ctypes.addressof(durs), blank=8, max_symbols=10, tokens=16, times=16, out_len=16, score=16, max_out=40)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return lib.mi355x_transducer_greedy_decode(ctypes.byref(d), None)
+    assert greedy(dur(1, 2, 3)) == 1                                           # durations not starting at 0
+    assert greedy(dur(*range(9))) == 1                                         # nine durations
+    assert greedy(blank=9) == 1                                                # blank outside the V1 label logits
 
 
 def test_rnnt_abi_rejects_the_same_bad_arguments_without_a_gpu():

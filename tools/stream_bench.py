@@ -7,7 +7,7 @@ with 256 channels, LayerNorm conv module, [70, 13]: 112 mel frames = 1.12 s of a
 
 `--decoder {none,ctc,rnnt,tdt}` adds the head's step behind the encoder step and reports it separately (`head_ms_per_step`,
 `head_launches`): ctc = ConvASRDecoder + per-frame arg-max; rnnt / tdt = the encoder projection GEMM + the resumable greedy search
-(mi355x_rnnt_greedy_decode_stream / mi355x_tdt_greedy_decode_stream) from a carried decoder state, at the recipe's transducer
+(ops.rnnt_greedy_decode_stream / ops.tdt_greedy_decode_stream) from a carried decoder state, at the recipe's transducer
 geometry (prediction hidden 640, joint hidden 640, vocabulary 1024, max_symbols 10), bf16 weight images.  For the transducer
 heads the same 14 frames are also decoded as 14 one-frame chunks (`head_ms_14x1`): everything paid per chunk -- the projection
 GEMM, the other launches and the prediction step the kernel reruns at entry -- is in that figure 14 times instead of once, so the
@@ -19,7 +19,7 @@ generator at alpha 0.5), stepped from the state a stream has after eight chunks,
 
 `--decoder {rnnt,tdt} --head-only FRAMES [FRAMES ...] [--lm ORDER] [--boost P]`: no encoder; the transducer head alone on random
 encoder output of FRAMES frames per stream (14 = the streaming step, 250 = 20 s offline), the plain search against the search with
-shallow fusion (mi355x_transducer_greedy_decode_fused: --lm, the n-gram model of the tests' generator at alpha 0.5; --boost, a tree
+shallow fusion (ops.transducer_greedy_decode_fused: --lm, the n-gram model of the tests' generator at alpha 0.5; --boost, a tree
 of P three-label phrases taken from the plain search's own output on this input, at alpha 2.0), resumed from the state after one
 chunk.  The two are timed in alternating rounds of one process: median, min and max of 7 rounds each, and the labels emitted.
 What is timed is the head's step (`decode_ids_stream`): the encoder-projection GEMM with its cast, the same on both sides, and

@@ -1040,6 +1040,37 @@ typedef struct mi355x_transducer_greedy_desc {
 } mi355x_transducer_greedy_desc;
 int mi355x_transducer_greedy_decode(const mi355x_transducer_greedy_desc* d, void* stream);
 
+/* ---- the greedy searches for a prediction network of L = 1 + n_upper LSTM layers, L in 1..4: every form the descriptor above
+ * states (RNN-T and TDT, one-shot and resumable, with confidences, with one or two fusion models, fp32 masters and bf16 images).
+ * The descriptor keeps describing layer 0; the struct below adds layers 1 .. n_upper, all [4H, H] in the descriptor's w_dtype with
+ * f32 biases.  THE RULE -- one prediction step on the input x = emb[last] with the committed state h[l], c[l], l = 0 .. L-1:
+ *     z     = ((W_hh[l] . h[l] + b_hh[l]) + W_ih[l] . in_l) + b_ih[l]      in_0 = x, in_l = hn[l-1];  torch gate order i, f, g, o
+ *     cn[l] = sigmoid(f) * c[l] + sigmoid(i) * tanh(g)
+ *     hn[l] = sigmoid(o) * tanh(cn[l])
+ *     gp    = W_pred . hn[L-1] + b_pred
+ * in float32, in that association (every dot product a sum over lane-strided 4-vectors reduced across a wave; the layers run
+ * in a chain from the bottom, an upper layer's two products in one pass over its rows).  Eval mode: no dropout between layers.
+ * Emitting a label commits EVERY layer (h[l] <- hn[l], c[l] <- cn[l]) and runs the next step; a blank start-of-sequence input
+ * skips layer 0's W_ih product alone.  Everything else is the one-layer search's: the arg-max rules, TDT durations and max_symbols,
+ * score, confidence sums, fusion ranks, skip / zero_run / frames_done.
+ * With n_upper > 0 every LSTM state is [L, B, H] (torch's LSTM state layout): h / c of both mi355x_rnnt_stream_state and h_out /
+ * c_out.  The resumable form keeps its contract: any cut into chunks gives the bits of one launch -- tokens, frames, lengths,
+ * score, every state field and tok_conf.
+ * upper NULL or n_upper == 0: the entry above, with the same checks, the same kernels and the same bits ([B, H] states).
+ * MI_ERR_ARG, before anything is launched: everything the entry above refuses; n_upper outside 0..3; in a used slot a null table
+ * or a pitch that is not a multiple of 4; an LDS need of 4 * (5H + 4LH + 2J + V1 + D + 4) bytes above 160 KiB - 256 (x [H], then
+ * h, c, hn, cn of every layer, the gates [4H], two [J] vectors and the logits; L = 1 is the 9H + ... of the one-layer search).
+ * The deep kernels are instantiations of their own, all of them the resumable kernel (a one-shot call is a fresh stream with
+ * no state to write); the one-layer calls launch the code they always have. */
+typedef struct mi355x_transducer_lstm_layers {   /* layers 1 .. n_upper of the prediction network */
+  int n_upper;                                    /* L - 1: 0 .. 3 */
+  const void* w_ih[3]; const void* w_hh[3];       /* [4H, H] in the descriptor's w_dtype */
+  const void* b_ih[3]; const void* b_hh[3];       /* f32 [4H] */
+  long long ld_ih[3], ld_hh[3];                   /* row pitches, multiples of 4 */
+} mi355x_transducer_lstm_layers;
+int mi355x_transducer_greedy_decode_layers(const mi355x_transducer_greedy_desc* d, const mi355x_transducer_lstm_layers* upper,
+                                           void* stream);
+
 /* ---- cache-aware streaming inference (ConformerEncoder.cache_aware_stream_step; the `update_cache` paths of
  * RelPositionMultiHeadAttention and CausalConv1D).  Caches are f32 in the reference's layouts; in bf16 compute they hold the
  * bf16-rounded operands widened to f32, so a streamed chunk reads the same operand values as the offline forward.

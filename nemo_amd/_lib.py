@@ -81,6 +81,12 @@ class TransducerGreedyDesc(C.Structure):
         + [(n, i32) for n in ("f_dtype", "w_dtype", "B", "T", "J", "H", "V1", "blank", "max_symbols", "max_out", "D", "n_models")])
 
 
+class TransducerLstmLayers(C.Structure):
+    """mirror of `mi355x_transducer_lstm_layers`: layers 1 .. n_upper of the prediction network (slot l = layer l + 1)"""
+    _fields_ = [("n_upper", i32), ("w_ih", vp * 3), ("w_hh", vp * 3), ("b_ih", vp * 3), ("b_hh", vp * 3), ("ld_ih", i64 * 3),
+                ("ld_hh", i64 * 3)]
+
+
 # name -> argtypes (return type is always int, except the version string)
 SIGNATURES = {
     "mi355x_gemm": [C.POINTER(GemmDesc), vp],
@@ -208,6 +214,7 @@ SIGNATURES = {
     "mi355x_rnnt_workspace_elems": [i32, i32, i32, vp],
     "mi355x_rnnt_loss": [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, i64, vp],
     "mi355x_transducer_greedy_decode": [C.POINTER(TransducerGreedyDesc), vp],
+    "mi355x_transducer_greedy_decode_layers": [C.POINTER(TransducerGreedyDesc), C.POINTER(TransducerLstmLayers), vp],
     "mi355x_dwconv_config": [i32],
     "mi355x_ctc_config": [i32],
     "mi355x_ctc_align_config": [i32],

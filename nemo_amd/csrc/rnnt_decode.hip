@@ -25,6 +25,20 @@
 // (h, c, emb[last]) by one prediction step at entry -- the very step `emit` ran after the last label -- so a stream cut into any
 // chunks takes the same decisions with the same arithmetic as one launch over the whole sequence: tokens, frame indices,
 // lengths, score and final state are bit-identical.  The one-shot entry points are the fresh-state case.
+//
+// Prediction networks of L = 1 + n_upper LSTM layers (mi355x_transducer_greedy_decode_layers, L <= 4).  THE RULE: one prediction step on
+// the input x = emb[last] with the committed state h[l], c[l], l = 0 .. L-1, is, layer by layer from the bottom,
+//     z     = ((W_hh[l] . h[l] + b_hh[l]) + W_ih[l] . in_l) + b_ih[l]         in_0 = x, in_l = hn[l-1]   (torch gate order i, f, g, o)
+//     cn[l] = sigmoid(f) * c[l] + sigmoid(i) * tanh(g),   hn[l] = sigmoid(o) * tanh(cn[l]),   gp = W_pred . hn[L-1] + b_pred
+// in float32 and in that association: every dot product is a wave's sum over lane-strided 4-vectors, the recurrent product with
+// its bias first, then the input product, then the input bias.  No dropout between layers (eval mode).  Emitting a label commits
+// EVERY layer (h[l] <- hn[l], c[l] <- cn[l]) and runs the next step; a blank start-of-sequence input skips layer 0's W_ih product
+// alone.  Layer 0 is the code of the one-layer search; an upper layer computes both of its products in ONE pass over the rows (two
+// accumulators per row, so the loads of both matrices are in flight together and the layer costs one barrier less); the layers
+// run in a chain, the recurrent products are not hoisted in front of it (that would need 4H more floats of LDS per layer for no
+// fewer bytes read).  LDS holds h, c, hn, cn of every layer; all states on the device are [L, B, H] (torch's LSTM state layout).
+// The arg-max rules, TDT durations, max_symbols, score, confidence sums, fusion ranks and skip / zero_run / frames_done are those
+// of the one-layer search, and so is the resumable contract: any cut into chunks gives the bits of one launch.
 #include "common.h"
 #include "ctc_beam_fusion.h"
 #include "mi355x_asr.h"
@@ -57,6 +71,43 @@ __device__ __forceinline__ void rd_gemv(const WT* __restrict__ W, long long ldw,
   }
 }
 
+// out[r] = ((sum_k Wh[r, k] * vh[k] + bh[r]) + sum_k Wi[r, k] * vi[k]) + bi[r]: the two products of an upper LSTM layer in one pass over
+// the rows (rd_gemv<false> on Wh followed by rd_gemv<true> on Wi gives these bits; here nothing waits between them)
+template <typename WT>
+__device__ __forceinline__ void rd_gemv2(const WT* __restrict__ Wh, long long ldh, const float* vh, const WT* __restrict__ Wi,
+                                         long long ldi, const float* vi, int R, int K, const float* bh, const float* bi, float* out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int r = wave; r < R; r += RD_WAVES) {
+    const WT* wh = Wh + (long long)r * ldh;
+    const WT* wi = Wi + (long long)r * ldi;
+    float a = 0.f, e = 0.f;
+    for (int k = lane * 4; k < K; k += 256) {
+      float x[4], u[4];
+      rd_ld4<WT>(wh + k, x);
+      rd_ld4<WT>(wi + k, u);
+      const float4 y = *reinterpret_cast<const float4*>(vh + k);
+      const float4 w = *reinterpret_cast<const float4*>(vi + k);
+      a += x[0] * y.x + x[1] * y.y + x[2] * y.z + x[3] * y.w;
+      e += u[0] * w.x + u[1] * w.y + u[2] * w.z + u[3] * w.w;
+    }
+    a = wave_sum(a);
+    e = wave_sum(e);
+    if (lane == 0) out[r] = ((0.f + a + bh[r]) + e) + bi[r];
+  }
+}
+
+// the LSTM cell of an upper layer on the gate pre-activations z [4H] (i, f, g, o) and the committed cell state c: cn, hn.  Layer 0
+// has the same loop inside the kernel: the one-layer instantiations are held to the instructions they have always had.
+__device__ __forceinline__ void rd_lstm_cell(const float* z, const float* c, float* hn, float* cn, int H) {
+  for (int j = threadIdx.x; j < H; j += RD_THREADS) {
+    const float ig = 1.f / (1.f + expf(-z[j])), fg = 1.f / (1.f + expf(-z[H + j]));
+    const float gg = tanhf(z[2 * H + j]), og = 1.f / (1.f + expf(-z[3 * H + j]));
+    const float cc = fg * c[j] + ig * gg;
+    cn[j] = cc;
+    hn[j] = og * tanhf(cc);
+  }
+}
+
 struct RnntDecP {
   const void* f; int f_dt; long long ldf;   // encoder projection [B, T, J] (rows of pitch ldf)
   const long long* enc_len;
@@ -82,10 +133,20 @@ struct RnntDecPF : RnntDecP {
   ctc_beam_lm lm[2];
   const int* ms_in; int* ms_out;
 };
-template <bool CONF, int NM = 0> struct RnntDecArg { typedef RnntDecP t; };
+// layers 1 .. n of the prediction network (mi355x_transducer_lstm_layers with typed pointers), and the parameter blocks of the DEEP
+// instantiations: each of the three above (untouched) with the upper layers behind it, by value
+struct RnntUpper {
+  int n;
+  const void *w_ih[3], *w_hh[3];
+  const float *b_ih[3], *b_hh[3];
+  long long ld_ih[3], ld_hh[3];
+};
+template <typename Base> struct RnntDecDeep : Base { RnntUpper up; };
+template <bool CONF, int NM = 0, bool DEEP = false> struct RnntDecArg { typedef RnntDecP t; };
 template <> struct RnntDecArg<true, 0> { typedef RnntDecPC t; };
 template <> struct RnntDecArg<false, 1> { typedef RnntDecPF t; };
 template <> struct RnntDecArg<false, 2> { typedef RnntDecPF t; };
+template <bool CONF, int NM> struct RnntDecArg<CONF, NM, true> { typedef RnntDecDeep<typename RnntDecArg<CONF, NM>::t> t; };
 
 // STREAM = false is the one-shot search: the state code folds away at compile time and the instantiation is the kernel the
 // one-shot entry points have always launched.  CONF = false likewise: the sums of the confidence measure, their two block
@@ -96,9 +157,14 @@ template <> struct RnntDecArg<false, 2> { typedef RnntDecPF t; };
 // `if constexpr (NM > 0)` and those instantiations are the kernels they were.  With models a step whose arg-max is a label picks
 // the label by rank_v = ((lg[v] - lg[mi]) + alpha_0 * look_0(state_0, v)) + alpha_1 * look_1(state_1, v) over v != blank (a blank
 // arg-max stays a blank: the models never turn a blank into a label); the states are uniform over the workgroup.
-template <typename WT, bool TDT, bool STREAM, bool CONF, int NM = 0>
-__global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDecArg<CONF, NM>::t p) {
+//
+// DEEP = a prediction network of L = 1 + p.up.n layers (the rule is at the top of this file; STREAM = true only, for the reason
+// NM > 0 gives).  LDS then holds the block (h, c, hn, cn) of every layer, layer 0's where it always was and layer l's 4 * l * H floats
+// behind it, and the state arrays are [L, B, H].  DEEP = false: none of it exists and the instantiations are the kernels they were.
+template <typename WT, bool TDT, bool STREAM, bool CONF, int NM = 0, bool DEEP = false>
+__global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDecArg<CONF, NM, DEEP>::t p) {
   static_assert(NM == 0 || (STREAM && !CONF && NM <= 2), "the fused search is the resumable one, without confidences");
+  static_assert(!DEEP || STREAM, "the deep search is the resumable one (a one-shot call: a fresh stream, no state to write)");
   extern __shared__ __attribute__((aligned(16))) float rd_smem[];
   const int H = p.H, J = p.J, V1 = p.V1;
   float* x = rd_smem;            // [H] embedding of the last emitted label
@@ -107,6 +173,11 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
   float* hn = c + H;             // state after consuming `last` (committed when the next label is emitted)
   float* cn = hn + H;
   float* z = cn + H;             // [4H] gate pre-activations
+  int L = 1;                     // LSTM layers (uniform)
+  if constexpr (DEEP) {          // (h, c, hn, cn) of the upper layers sit between layer 0's and z
+    L = 1 + min(max(p.up.n, 0), 3);
+    z = h + 4 * L * H;
+  }
   float* gp = z + 4 * H;         // [J] prediction projection of hn
   float* a = gp + J;             // [J] relu(f_t + gp)
   float* lg = a + J;             // [V1] logits (TDT: [V1 + D], the duration logits behind the label logits)
@@ -134,11 +205,22 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
     last = p.sin.last[b]; score = p.sin.score[b]; frames_done = p.sin.frames_done[b];
     if (TDT) { skip = max(p.sin.skip[b], 0); same = p.sin.zero_run[b]; }
     if (last < 0 || last >= V1) last = p.blank;   // (a label outside the embedding table is never read)
-    for (int i = tid; i < H; i += RD_THREADS) {
-      h[i] = p.sin.h[(long long)b * H + i]; c[i] = p.sin.c[(long long)b * H + i]; x[i] = p.emb[(long long)last * H + i];
+    if constexpr (DEEP) {
+      for (int l = 0; l < L; ++l)
+        for (int i = tid; i < H; i += RD_THREADS) {
+          h[l * 4 * H + i] = p.sin.h[((long long)l * p.B + b) * H + i]; c[l * 4 * H + i] = p.sin.c[((long long)l * p.B + b) * H + i];
+        }
+      for (int i = tid; i < H; i += RD_THREADS) x[i] = p.emb[(long long)last * H + i];
+    } else {
+      for (int i = tid; i < H; i += RD_THREADS) {
+        h[i] = p.sin.h[(long long)b * H + i]; c[i] = p.sin.c[(long long)b * H + i]; x[i] = p.emb[(long long)last * H + i];
+      }
     }
   } else {
     for (int i = tid; i < H; i += RD_THREADS) { h[i] = 0.f; c[i] = 0.f; x[i] = 0.f; }
+    if constexpr (DEEP)
+      for (int l = 1; l < L; ++l)
+        for (int i = tid; i < H; i += RD_THREADS) { h[l * 4 * H + i] = 0.f; c[l * 4 * H + i] = 0.f; }
   }
   __syncthreads();
 
@@ -157,7 +239,23 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
       hn[j] = og * tanhf(cc);
     }
     __syncthreads();
-    rd_gemv<WT, false>((const WT*)p.w_pred, p.ld_pred, hn, J, H, p.b_pred, gp);
+    const float* top = hn;   // hn of the last layer
+    if constexpr (DEEP) {
+      // (constant indices into the parameter block: the pointers come from scalar loads, no private copy of the tables)
+#pragma unroll
+      for (int l = 0; l < 3; ++l) {
+        if (l + 1 < L) {   // (uniform)
+          float* hl = h + (l + 1) * 4 * H;   // this layer's h, c, hn, cn; its input: hn of the layer below, 2H in front of hl
+          rd_gemv2<WT>((const WT*)p.up.w_hh[l], p.up.ld_hh[l], hl, (const WT*)p.up.w_ih[l], p.up.ld_ih[l], hl - 2 * H, 4 * H, H,
+                       p.up.b_hh[l], p.up.b_ih[l], z);
+          __syncthreads();
+          rd_lstm_cell(z, hl + H, hl + 2 * H, hl + 3 * H, H);
+          __syncthreads();
+          top = hl + 2 * H;
+        }
+      }
+    }
+    rd_gemv<WT, false>((const WT*)p.w_pred, p.ld_pred, top, J, H, p.b_pred, gp);
     __syncthreads();
   };
   // `last` = blank is the zero embedding row (blank_as_pad); a chunk with no frame to look at takes no decision and needs no step
@@ -287,6 +385,9 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
       score += -logf(se);   // log-prob of the arg-max label = mv - (mv + log se)
     }
     for (int i = tid; i < H; i += RD_THREADS) { h[i] = hn[i]; c[i] = cn[i]; x[i] = p.emb[(long long)k * H + i]; }
+    if constexpr (DEEP)
+      for (int l = 1; l < L; ++l)
+        for (int i = tid; i < H; i += RD_THREADS) { h[l * 4 * H + i] = hn[l * 4 * H + i]; c[l * 4 * H + i] = cn[l * 4 * H + i]; }
     __syncthreads();
     pred_step(false);
   };
@@ -349,9 +450,20 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
     if (p.times) p.times[(long long)b * p.max_out + i] = -1;
     if constexpr (CONF) p.tok_conf[(long long)b * p.max_out + i] = 0.f;
   }
-  if (p.h_out) for (int i = tid; i < H; i += RD_THREADS) { p.h_out[(long long)b * H + i] = h[i]; p.c_out[(long long)b * H + i] = c[i]; }
+  if constexpr (DEEP) {   // [L, B, H]
+    for (int l = 0; l < L; ++l)
+      for (int i = tid; i < H; i += RD_THREADS) {
+        const long long o = ((long long)l * p.B + b) * H + i;
+        const float hv = h[l * 4 * H + i], cv = c[l * 4 * H + i];
+        if (p.h_out) { p.h_out[o] = hv; p.c_out[o] = cv; }
+        if (p.sout.h) { p.sout.h[o] = hv; p.sout.c[o] = cv; }
+      }
+  } else {
+    if (p.h_out) for (int i = tid; i < H; i += RD_THREADS) { p.h_out[(long long)b * H + i] = h[i]; p.c_out[(long long)b * H + i] = c[i]; }
+  }
   if (STREAM && p.sout.h) {
-    for (int i = tid; i < H; i += RD_THREADS) { p.sout.h[(long long)b * H + i] = h[i]; p.sout.c[(long long)b * H + i] = c[i]; }
+    if constexpr (!DEEP)
+      for (int i = tid; i < H; i += RD_THREADS) { p.sout.h[(long long)b * H + i] = h[i]; p.sout.c[(long long)b * H + i] = c[i]; }
     if (tid == 0) {
       p.sout.last[b] = last; p.sout.score[b] = score; p.sout.frames_done[b] = frames_done + len;
       if (TDT) { p.sout.skip[b] = skip; p.sout.zero_run[b] = same; }
@@ -359,9 +471,22 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
   }
 }
 
+// The 16 DEEP instantiations, [weights][TDT][plain, with confidences, one model, two models], all of them the resumable kernel: a
+// one-shot call is a fresh stream with no state to write.  The block is the one the shallow kernel of the same form takes, with
+// the upper layers behind it.
+template <typename Block>
+static void greedy_issue_deep(const void* fn, const Block& block, const RnntUpper& up, int B, size_t shm, hipStream_t s) {
+  RnntDecDeep<Block> q;
+  static_cast<Block&>(q) = block;
+  q.up = up;
+  MI_LAUNCH((void (*)(RnntDecDeep<Block>))fn, dim3(B), dim3(RD_THREADS), shm, s, q);
+}
+
 // ---- the one entry of the greedy searches (include/mi355x_asr.h states the descriptor): RNN-T or TDT, one-shot or resumable, with
 // the confidence of every emitted label or with one or two fusion models.  Every check is here; nothing is launched after a refusal.
-static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, hipStream_t s) {
+// `upper` (mi355x_transducer_greedy_decode_layers): layers 1 .. n_upper of the prediction network; null or n_upper == 0 is the call
+// without it, down to the kernel launched.
+static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, const mi355x_transducer_lstm_layers* upper, hipStream_t s) {
   if (!d) return MI_ERR_ARG;
   if (!d->enc_proj || !d->emb || !d->w_ih || !d->w_hh || !d->b_ih || !d->b_hh || !d->w_pred || !d->w_out || !d->tokens || !d->out_len)
     return MI_ERR_ARG;
@@ -412,8 +537,42 @@ static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, hipStream_
     if (d->state_in) p.ms_in = d->m_state_in;
     if (d->state_out) p.ms_out = d->m_state_out;
   }
-  const size_t shm = (size_t)(9 * H + 2 * J + V1 + p.dur.D + 4) * sizeof(float);
+  RnntUpper up = {};
+  if (upper) {
+    if (upper->n_upper < 0 || upper->n_upper > 3) return MI_ERR_ARG;
+    up.n = upper->n_upper;
+    for (int l = 0; l < up.n; ++l) {
+      if (!upper->w_ih[l] || !upper->w_hh[l] || !upper->b_ih[l] || !upper->b_hh[l] || (upper->ld_ih[l] & 3) || (upper->ld_hh[l] & 3))
+        return MI_ERR_ARG;
+      up.w_ih[l] = upper->w_ih[l]; up.w_hh[l] = upper->w_hh[l]; up.ld_ih[l] = upper->ld_ih[l]; up.ld_hh[l] = upper->ld_hh[l];
+      up.b_ih[l] = (const float*)upper->b_ih[l]; up.b_hh[l] = (const float*)upper->b_hh[l];
+    }
+  }
+  // x [H], (h, c, hn, cn) [4H] per layer, z [4H], gp and a [J], lg [V1 + D], and 4 floats of slack (one layer: 9H + ...)
+  const size_t shm = ((size_t)5 * H + (size_t)4 * (1 + up.n) * H + (size_t)2 * J + V1 + p.dur.D + 4) * sizeof(float);
   if (shm > 160 * 1024 - 256) return MI_ERR_ARG;
+
+  if (up.n > 0) {
+#define RD_ROW(WT, TDT)                                                                                                          \
+  {(const void*)rnnt_greedy_kernel<WT, TDT, true, false, 0, true>, (const void*)rnnt_greedy_kernel<WT, TDT, true, true, 0, true>, \
+   (const void*)rnnt_greedy_kernel<WT, TDT, true, false, 1, true>, (const void*)rnnt_greedy_kernel<WT, TDT, true, false, 2, true>}
+    static const void* const deep[2][2][4] = {{RD_ROW(float, false), RD_ROW(float, true)}, {RD_ROW(bf16_t, false), RD_ROW(bf16_t, true)}};
+#undef RD_ROW
+    const void* fn = deep[d->w_dtype == MI_DT_BF16][tdt][fused ? 1 + d->n_models : (d->conf ? 1 : 0)];
+    hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    if (fused) {
+      greedy_issue_deep<RnntDecPF>(fn, p, up, B, shm, s);
+    } else if (d->conf) {
+      RnntDecPC pc;
+      static_cast<RnntDecP&>(pc) = p;
+      pc.tok_conf = (float*)d->tok_conf;
+      pc.conf = {d->conf->method, d->conf->norm, d->conf->alpha, d->conf->k0, d->conf->k1, d->conf->k2, (float)V1};
+      greedy_issue_deep<RnntDecPC>(fn, pc, up, B, shm, s);
+    } else {
+      greedy_issue_deep<RnntDecP>(fn, p, up, B, shm, s);
+    }
+    return MI_OK;
+  }
 
   // The 24 instantiations, [weights][TDT][mode]: the one-shot and the resumable kernel, each plain and with confidences, and the
   // resumable kernel with one and with two models (a fused one-shot call is a fresh stream with no state to write).
@@ -446,6 +605,13 @@ static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, hipStream_
 
 extern "C" int mi355x_transducer_greedy_decode(const mi355x_transducer_greedy_desc* d, void* stream) {
   mi_clear_errors();
-  const int rc = greedy_decode_impl(d, (hipStream_t)stream);
+  const int rc = greedy_decode_impl(d, nullptr, (hipStream_t)stream);
+  return rc != MI_OK ? rc : mi_check_launch();
+}
+
+extern "C" int mi355x_transducer_greedy_decode_layers(const mi355x_transducer_greedy_desc* d, const mi355x_transducer_lstm_layers* upper,
+                                                      void* stream) {
+  mi_clear_errors();
+  const int rc = greedy_decode_impl(d, upper, (hipStream_t)stream);
   return rc != MI_OK ? rc : mi_check_launch();
 }

@@ -58,7 +58,7 @@ class Hypothesis:  # parts/utils/rnnt_utils.py:35-110 (the fields greedy decodin
     y_sequence: torch.Tensor
     timestamp: List[int] = field(default_factory=list)
     text: Optional[str] = None
-    dec_state: Optional[object] = None   # one-shot search: the final (h, c); streaming: ops.RNNTStreamState of this stream (batch 1, device)
+    dec_state: Optional[object] = None   # one-shot search: the final (h, c) ([H] each; L > 1 layers: [L, H]); streaming: ops.RNNTStreamState of this stream (batch 1, device)
     length: int = 0
     last_token: Optional[torch.Tensor] = None   # i32 [1] on the device (= dec_state.last); blank before the first label
     frame_confidence: Optional[List[float]] = None   # CTC: one value per frame of the utterance
@@ -93,8 +93,10 @@ class GreedyBatchedRNNTInfer:
             raise NotImplementedError("alignments / frame confidences are not produced by the on-device search")
         if max_symbols_per_step is not None and max_symbols_per_step <= 0:
             raise ValueError(f"Expected max_symbols_per_step > 0 (or None), got {max_symbols_per_step}")  # rnnt_greedy_decoding.py:187
-        if getattr(decoder_model, "pred_rnn_layers", 1) != 1:
-            raise NotImplementedError("on-device greedy search: one LSTM layer in the prediction network (the recipe's pred_rnn_layers)")
+        self.pred_layers = int(getattr(decoder_model, "pred_rnn_layers", 1))
+        if not 1 <= self.pred_layers <= 4:
+            raise NotImplementedError(f"on-device greedy search: at most 4 LSTM layers in the prediction network, got pred_rnn_layers = "
+                                      f"{self.pred_layers}")
         self.decoder, self.joint = decoder_model, joint_model
         self._blank_index = int(blank_index)
         self.max_symbols = max_symbols_per_step
@@ -129,6 +131,24 @@ class GreedyBatchedRNNTInfer:
                 self._blank_index, self.max_symbols or 0)
         return f.view(B, T, J), args
 
+    def _upper(self, device):
+        """layers 1 .. L-1 of the prediction network as the searches' `upper_layers` (None with one layer): the bf16 images and
+        their pitches in bf16 compute, else the fp32 masters; the biases are fp32 either way"""
+        if self.pred_layers == 1:
+            return None
+        dec = self.decoder
+        lstm, H = dec.prediction["dec_rnn"].lstm, dec.pred_hidden
+        cdt = self.joint._cdt()
+        Wd = dec._plan(cdt, device)[0] if cdt == torch.bfloat16 else None
+        upper = []
+        for l in range(1, self.pred_layers):
+            b_ih, b_hh = getattr(lstm, f"bias_ih_l{l}"), getattr(lstm, f"bias_hh_l{l}")
+            if Wd is not None:
+                upper.append((Wd[f"l{l}.wih"], Wd.pitch(f"l{l}.wih"), Wd[f"l{l}.whh"], Wd.pitch(f"l{l}.whh"), b_ih, b_hh))
+            else:
+                upper.append((getattr(lstm, f"weight_ih_l{l}"), H, getattr(lstm, f"weight_hh_l{l}"), H, b_ih, b_hh))
+        return upper
+
     @property
     def _with_confidence(self) -> bool:
         return self.confidence_cfg is not None and self.confidence_cfg.wants_tokens
@@ -145,25 +165,26 @@ class GreedyBatchedRNNTInfer:
         self._no_fused_confidence(with_confidence)
         f, args = self._project(encoder_output)
         lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        up = self._upper(f.device)
         if self.fusion_models is not None:
-            out = self._search_fused(f, lens, *args)
+            out = self._search_fused(f, lens, *args, upper_layers=up)
             return out if with_state else out[:4]
         if with_confidence:
-            return self._search_conf(f, lens, *args, method=self._method(args), with_state=with_state)
-        return self._search(f, lens, *args, with_state=with_state)
+            return self._search_conf(f, lens, *args, method=self._method(args), with_state=with_state, upper_layers=up)
+        return self._search(f, lens, *args, with_state=with_state, upper_layers=up)
 
     _search = staticmethod(ops.rnnt_greedy_decode)
     _search_stream = staticmethod(ops.rnnt_greedy_decode_stream)
 
-    def _search_conf(self, *args, method, with_state=False):
-        return ops.rnnt_greedy_decode_conf(*args, method, with_state=with_state)
+    def _search_conf(self, *args, method, **kw):
+        return ops.rnnt_greedy_decode_conf(*args, method, **kw)
 
-    def _search_stream_conf(self, *args, method, state=None):
-        return ops.rnnt_greedy_decode_stream_conf(*args, method, state=state)
+    def _search_stream_conf(self, *args, method, **kw):
+        return ops.rnnt_greedy_decode_stream_conf(*args, method, **kw)
 
-    def _search_fused(self, *args, state=None):
+    def _search_fused(self, *args, **kw):
         """the search with `fusion_models` -> (tokens, frame indices, lengths, score, (h, c) | the next state)"""
-        return ops.transducer_greedy_decode_fused(*args, self.fusion_models, state=state)
+        return ops.transducer_greedy_decode_fused(*args, self.fusion_models, **kw)
 
     def _no_fused_confidence(self, with_confidence):
         if with_confidence and self.fusion_models is not None:
@@ -179,14 +200,15 @@ class GreedyBatchedRNNTInfer:
         self._no_fused_confidence(with_confidence)
         f, args = self._project(encoder_output)
         lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        up = self._upper(f.device)
         if self.fusion_models is not None:
             if state is None:
-                state = ops.RNNTFusedStreamState.fresh(f.shape[0], args[0].shape[1], self._blank_index, f.device)
-            tokens, times, out_len, score, nxt = self._search_fused(f, lens, *args, state=state)
+                state = ops.RNNTFusedStreamState.fresh(f.shape[0], args[0].shape[1], self._blank_index, f.device, layers=self.pred_layers)
+            tokens, times, out_len, score, nxt = self._search_fused(f, lens, *args, state=state, upper_layers=up)
             return FusedChunk(tokens, times, out_len, nxt, score)
         if with_confidence:
-            return self._search_stream_conf(f, lens, *args, method=self._method(args), state=state)
-        return self._search_stream(f, lens, *args, state=state)
+            return self._search_stream_conf(f, lens, *args, method=self._method(args), state=state, upper_layers=up)
+        return self._search_stream(f, lens, *args, state=state, upper_layers=up)
 
     def fresh_hypotheses(self, batch_size: int, device=None):
         """empty hypotheses of `batch_size` streams that have seen nothing, carrying a fresh decoder state: what a stream's FIRST
@@ -194,7 +216,7 @@ class GreedyBatchedRNNTInfer:
         dec = self.decoder
         device = device if device is not None else dec.prediction["embed"].weight.device
         state_cls = ops.RNNTFusedStreamState if self.fusion_models is not None else ops.RNNTStreamState
-        st = state_cls.fresh(batch_size, dec.pred_hidden, self._blank_index, device)
+        st = state_cls.fresh(batch_size, dec.pred_hidden, self._blank_index, device, layers=self.pred_layers)
         return [Hypothesis(score=0.0, y_sequence=torch.zeros(0, dtype=torch.long), timestamp=[], dec_state=st.select(b), length=0,
                            last_token=st.select(b).last, token_confidence=[] if self._with_confidence else None)
                 for b in range(batch_size)]
@@ -214,7 +236,7 @@ class GreedyBatchedRNNTInfer:
             for b in range(B):
                 n = int(out_len[b])
                 hyps.append(Hypothesis(score=float(score[b]), y_sequence=tokens[b, :n].to(torch.long), timestamp=times[b, :n].tolist(),
-                                       dec_state=(h[b], c[b]), length=int(encoded_lengths[b]),
+                                       dec_state=(h[b], c[b]) if h.dim() == 2 else (h[:, b], c[:, b]), length=int(encoded_lengths[b]),
                                        token_confidence=tc[b, :n].tolist() if conf else None))
             return (hyps,)
         if len(partial_hypotheses) != B:
@@ -266,20 +288,20 @@ class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
         if getattr(joint_model, "_num_extra_outputs", len(self.durations)) != len(self.durations):
             raise ValueError(f"the joint has {joint_model._num_extra_outputs} extra outputs for {len(self.durations)} durations")
 
-    def _search_fused(self, *args, state=None):
-        return ops.transducer_greedy_decode_fused(*args, self.fusion_models, durations=self.durations, state=state)
+    def _search_fused(self, *args, **kw):
+        return ops.transducer_greedy_decode_fused(*args, self.fusion_models, durations=self.durations, **kw)
 
-    def _search(self, *args, with_state=False):
-        return ops.tdt_greedy_decode(*args[:16], self.durations, args[16], with_state=with_state)
+    def _search(self, *args, **kw):
+        return ops.tdt_greedy_decode(*args[:16], self.durations, args[16], **kw)
 
-    def _search_stream(self, *args, state=None):
-        return ops.tdt_greedy_decode_stream(*args[:16], self.durations, args[16], state=state)
+    def _search_stream(self, *args, **kw):
+        return ops.tdt_greedy_decode_stream(*args[:16], self.durations, args[16], **kw)
 
-    def _search_conf(self, *args, method, with_state=False):
-        return ops.tdt_greedy_decode_conf(*args[:16], self.durations, args[16], method, with_state=with_state)
+    def _search_conf(self, *args, method, **kw):
+        return ops.tdt_greedy_decode_conf(*args[:16], self.durations, args[16], method, **kw)
 
-    def _search_stream_conf(self, *args, method, state=None):
-        return ops.tdt_greedy_decode_stream_conf(*args[:16], self.durations, args[16], method, state=state)
+    def _search_stream_conf(self, *args, method, **kw):
+        return ops.tdt_greedy_decode_stream_conf(*args[:16], self.durations, args[16], method, **kw)
 
 
 def transducer_fusion_from_config(greedy, vocabulary=None, text_to_ids=None, what: str = "transducer"):

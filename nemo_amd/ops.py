@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import ConvGather, GemmDesc, PackEntry, RowMap, TransducerConf, TransducerGreedyDesc, check, lib
+from ._lib import ConvGather, GemmDesc, PackEntry, RowMap, TransducerConf, TransducerGreedyDesc, TransducerLstmLayers, check, lib
 
 F32, BF16 = 0, 1
 EPI_STORE, EPI_SWISH_DROP, EPI_RESID, EPI_DSWISH, EPI_RELU_MASK, EPI_MUL_POS, EPI_SWISH_DROP_G, EPI_DSWISH_G = range(8)
@@ -1010,12 +1010,19 @@ def rnnt_loss(acts, labels, act_lens, label_lens, blank, grads=None, fastemit_la
 
 
 def _greedy_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
-                   blank, durations, max_symbols, max_out, *, with_state=False, stream=None, state=None, method=None, models=None):
+                   blank, durations, max_symbols, max_out, *, with_state=False, stream=None, state=None, method=None, models=None,
+                   upper_layers=None):
     """every greedy transducer search: the outputs, the descriptor and the one entry (mi355x_transducer_greedy_decode).  `durations`
     given: TDT.  `stream` = the state class of the resumable search (None: one-shot), `state` = the state to start from (None: fresh
     streams).  `method` = the confidence measure, `models` = the checked fusion models.  -> (tokens, times, out_len), then whatever
     was asked for, in this order: score (every search but the resumable one without models), (h, c) (`with_state`), the next state
-    (`stream`), tok_conf (`method`)."""
+    (`stream`), tok_conf (`method`).  `upper_layers` = [(w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh), ...] for layers 1 .. L-1 of the
+    prediction network (mi355x_transducer_greedy_decode_layers; weights in w_ih's dtype, biases fp32): every LSTM state is then
+    [L, B, H].  None or empty: the one-layer search, as ever."""
+    upper_layers = list(upper_layers) if upper_layers else []
+    L = 1 + len(upper_layers)
+    if L > 4:
+        raise ValueError(f"{what}: at most 4 LSTM layers in the prediction network (3 `upper_layers`), got {L}")
     if state is not None and not isinstance(state, stream):
         raise TypeError(f"{what}: `state` must be an {stream.__name__}, got {type(state).__name__}")
     B, T, J = enc_proj.shape
@@ -1044,16 +1051,16 @@ def _greedy_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih,
         d.score = _ptr(score)
         out += (score,)
     if with_state:
-        h, c = f32(B, H), f32(B, H)
+        h, c = (f32(B, H), f32(B, H)) if L == 1 else (f32(L, B, H), f32(L, B, H))
         d.h_out, d.c_out = _ptr(h), _ptr(c)
         out += ((h, c),)
     if stream is not None:
-        nxt = stream.empty(B, H, dev)
+        nxt = stream.empty(B, H, dev, layers=L)
         if durations is None:   # (not written by the RNN-T search)
             nxt.skip.zero_(); nxt.zero_run.zero_()
         for field, st in (("state_in", state), ("state_out", nxt)):
             if st is not None:
-                keep.append(st._c(B, H))
+                keep.append(st._c(B, H, layers=L))
                 setattr(d, field, C.addressof(keep[-1]))
                 if models is not None:
                     setattr(d, "m_" + field, _ptr(st.m_state))
@@ -1067,26 +1074,39 @@ def _greedy_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih,
         arr, tables = _ctc_beam_fusion_array(models, enc_proj)
         keep += [arr, tables]
         d.models, d.n_models = C.addressof(arr), len(arr)
-    check(lib.mi355x_transducer_greedy_decode(C.byref(d), _stream()), what)
+    if L == 1:
+        check(lib.mi355x_transducer_greedy_decode(C.byref(d), _stream()), what)
+        return out
+    up = TransducerLstmLayers(n_upper=L - 1)
+    for l, (u_ih, uld_ih, u_hh, uld_hh, ub_ih, ub_hh) in enumerate(upper_layers):
+        if dt(u_ih) != d.w_dtype or dt(u_hh) != d.w_dtype or ub_ih.dtype != torch.float32 or ub_hh.dtype != torch.float32:
+            raise ValueError(f"{what}: layer {l + 1} of the prediction network: weights in the dtype of layer 0, biases fp32")
+        if (min(uld_ih, uld_hh) < H or u_ih.numel() < (4 * H - 1) * uld_ih + H or u_hh.numel() < (4 * H - 1) * uld_hh + H
+                or min(ub_ih.numel(), ub_hh.numel()) < 4 * H):
+            raise ValueError(f"{what}: layer {l + 1} of the prediction network: weights [4H, H], biases [4H] for H = {H}")
+        up.w_ih[l], up.w_hh[l], up.b_ih[l], up.b_hh[l] = _ptr(u_ih), _ptr(u_hh), _ptr(ub_ih), _ptr(ub_hh)
+        up.ld_ih[l], up.ld_hh[l] = uld_ih, uld_hh
+    check(lib.mi355x_transducer_greedy_decode_layers(C.byref(d), C.byref(up), _stream()), what)
     return out
 
 
 def rnnt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
-                       blank, max_symbols, max_out=None, with_state=False):
+                       blank, max_symbols, max_out=None, with_state=False, *, upper_layers=None):
     """greedy transducer search of a whole batch in one launch (mi355x_transducer_greedy_decode).  enc_proj [B, T, J] = joint.enc(
     encoder output); weights fp32 or bf16 (all four the same dtype).  -> (tokens i32 [B, max_out] -1 padded, frame indices likewise,
     lengths i32 [B], score f32 [B][, (h, c) f32 [B, H]])"""
     return _greedy_search("rnnt_greedy_decode", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                          w_out, ld_out, b_out, blank, None, max_symbols, max_out, with_state=with_state)
+                          w_out, ld_out, b_out, blank, None, max_symbols, max_out, with_state=with_state, upper_layers=upper_layers)
 
 
 def rnnt_greedy_decode_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                            b_out, blank, max_symbols, method, max_out=None, with_state=False):
+                            b_out, blank, max_symbols, method, max_out=None, with_state=False, *, upper_layers=None):
     """rnnt_greedy_decode plus the confidence of every emitted label (mi355x_transducer_greedy_decode with a measure): `method` =
     (method, norm, alpha, k0, k1, k2) for V = V1 (modules.confidence.ConfidenceMethodConfig.kernel_args) -> rnnt_greedy_decode's
     tuple with tok_conf f32 [B, max_out] (0.0 padded) appended"""
     return _greedy_search("rnnt_greedy_decode_conf", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred,
-                          b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, with_state=with_state, method=method)
+                          b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, with_state=with_state, method=method,
+                          upper_layers=upper_layers)
 
 
 def _tdt_durations(durations):
@@ -1112,19 +1132,21 @@ def tdt_loss(acts, labels, act_lens, label_lens, blank, durations, grads=None, s
 
 
 def tdt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
-                      blank, durations, max_symbols, max_out=None, with_state=False):
+                      blank, durations, max_symbols, max_out=None, with_state=False, *, upper_layers=None):
     """greedy TDT search of a whole batch in one launch (mi355x_transducer_greedy_decode with a duration set): as rnnt_greedy_decode,
     with w_out / b_out holding V1 + len(durations) rows (label logits, then duration logits); frames advance by the predicted duration"""
     return _greedy_search("tdt_greedy_decode", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
-                          w_out, ld_out, b_out, blank, durations, max_symbols, max_out, with_state=with_state)
+                          w_out, ld_out, b_out, blank, durations, max_symbols, max_out, with_state=with_state,
+                          upper_layers=upper_layers)
 
 
 def tdt_greedy_decode_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                           b_out, blank, durations, max_symbols, method, max_out=None, with_state=False):
+                           b_out, blank, durations, max_symbols, method, max_out=None, with_state=False, *, upper_layers=None):
     """tdt_greedy_decode plus the confidence of every emitted label over the V1 label logits (mi355x_transducer_greedy_decode with
     a duration set and a measure)"""
     return _greedy_search("tdt_greedy_decode_conf", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred,
-                          b_pred, w_out, ld_out, b_out, blank, durations, max_symbols, max_out, with_state=with_state, method=method)
+                          b_pred, w_out, ld_out, b_out, blank, durations, max_symbols, max_out, with_state=with_state, method=method,
+                          upper_layers=upper_layers)
 
 
 class _StreamStateC(C.Structure):   # mi355x_rnnt_stream_state
@@ -1134,39 +1156,50 @@ class _StreamStateC(C.Structure):   # mi355x_rnnt_stream_state
 class RNNTStreamState:
     """decoder state of a batch of streams between two chunks of the resumable greedy search (mi355x_rnnt_stream_state): h, c f32
     [B, H] (committed LSTM state), last i32 [B] (last emitted label), score f32 [B] (running log-probability), frames_done i32 [B],
-    skip / zero_run i32 [B] (TDT; zeros and unused for RNN-T).  All on the device; every step returns a new object."""
+    skip / zero_run i32 [B] (TDT; zeros and unused for RNN-T).  All on the device; every step returns a new object.  A prediction
+    network of `layers` = L > 1 LSTM layers: h, c are [L, B, H] (torch's LSTM state layout, the batch on dimension 1)."""
     __slots__ = ("h", "c", "last", "score", "frames_done", "skip", "zero_run")
 
     def __init__(self, h, c, last, score, frames_done, skip, zero_run):
         self.h, self.c, self.last, self.score, self.frames_done, self.skip, self.zero_run = h, c, last, score, frames_done, skip, zero_run
 
-    @classmethod
-    def empty(cls, B, H, device):
-        i32 = lambda: torch.empty(B, dtype=torch.int32, device=device)
-        return cls(torch.empty(B, H, dtype=torch.float32, device=device), torch.empty(B, H, dtype=torch.float32, device=device),
-                   i32(), torch.empty(B, dtype=torch.float32, device=device), i32(), i32(), i32())
+    @staticmethod
+    def _hc_shape(B, H, layers):
+        return (B, H) if layers == 1 else (layers, B, H)
 
     @classmethod
-    def fresh(cls, B, H, blank, device):
+    def empty(cls, B, H, device, layers=1):
+        i32 = lambda: torch.empty(B, dtype=torch.int32, device=device)
+        hc = lambda: torch.empty(cls._hc_shape(B, H, layers), dtype=torch.float32, device=device)
+        return cls(hc(), hc(), i32(), torch.empty(B, dtype=torch.float32, device=device), i32(), i32(), i32())
+
+    @classmethod
+    def fresh(cls, B, H, blank, device, layers=1):
         """the state of B streams that have seen nothing (what a null state_in means to the kernel)"""
         z = lambda: torch.zeros(B, dtype=torch.int32, device=device)
-        return cls(torch.zeros(B, H, dtype=torch.float32, device=device), torch.zeros(B, H, dtype=torch.float32, device=device),
-                   torch.full((B,), int(blank), dtype=torch.int32, device=device), torch.zeros(B, dtype=torch.float32, device=device),
-                   z(), z(), z())
+        hc = lambda: torch.zeros(cls._hc_shape(B, H, layers), dtype=torch.float32, device=device)
+        return cls(hc(), hc(), torch.full((B,), int(blank), dtype=torch.int32, device=device),
+                   torch.zeros(B, dtype=torch.float32, device=device), z(), z(), z())
 
     def tensors(self):
         return tuple(getattr(self, n) for n in self.__slots__)
 
+    @staticmethod
+    def _pick(t, b):
+        """stream b of a state tensor as a batch of one: the batch is dimension 1 of a layered h / c, dimension 0 of the others"""
+        return t[:, b:b + 1].contiguous() if t.dim() == 3 else t[b:b + 1]
+
     def select(self, b):
-        """the state of stream b as a batch of one (views)"""
-        return RNNTStreamState(*(t[b:b + 1] for t in self.tensors()))
+        """the state of stream b as a batch of one (views; a layered h / c: a copy, so that it stays contiguous)"""
+        return RNNTStreamState(*(self._pick(t, b) for t in self.tensors()))
 
     @classmethod
     def stack(cls, states):
-        return cls(*(torch.cat(ts, dim=0).contiguous() for ts in zip(*(s.tensors() for s in states))))
+        return cls(*(torch.cat(ts, dim=1 if ts[0].dim() == 3 else 0).contiguous() for ts in zip(*(s.tensors() for s in states))))
 
-    def _c(self, B, H):
-        want = ((B, H), (B, H), (B,), (B,), (B,), (B,), (B,))
+    def _c(self, B, H, layers=1):
+        hc = self._hc_shape(B, H, layers)
+        want = (hc, hc, (B,), (B,), (B,), (B,), (B,))
         dts = (torch.float32, torch.float32, torch.int32, torch.float32, torch.int32, torch.int32, torch.int32)
         for n, t, shp, d in zip(self.__slots__, self.tensors(), want, dts):
             if tuple(t.shape) != shp or t.dtype != d or not t.is_contiguous():
@@ -1175,40 +1208,42 @@ class RNNTStreamState:
 
 
 def rnnt_greedy_decode_stream(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                              b_out, blank, max_symbols, state=None, max_out=None):
+                              b_out, blank, max_symbols, state=None, max_out=None, *, upper_layers=None):
     """one chunk of the resumable greedy transducer search (mi355x_transducer_greedy_decode with a state to write):
     rnnt_greedy_decode's arguments, with enc_len = the frames of this chunk per stream, and `state` = the RNNTStreamState the
     previous chunk returned (None: fresh streams).  -> (tokens, global frame indices, lengths of THIS chunk's labels, the next RNNTStreamState; its `score` is the
     stream's running score).  Any cut of a stream into chunks gives bit-identical results to one launch over all of it."""
     return _greedy_search("rnnt_greedy_decode_stream", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred,
-                          b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, stream=RNNTStreamState, state=state)
+                          b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, stream=RNNTStreamState, state=state,
+                          upper_layers=upper_layers)
 
 
 def tdt_greedy_decode_stream(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                             b_out, blank, durations, max_symbols, state=None, max_out=None):
+                             b_out, blank, durations, max_symbols, state=None, max_out=None, *, upper_layers=None):
     """one chunk of the resumable greedy TDT search (mi355x_transducer_greedy_decode with a duration set and a state to write): as
     rnnt_greedy_decode_stream; a duration that jumps past the chunk's end is carried in the state (`skip`) and taken off the next
     chunk(s)"""
     return _greedy_search("tdt_greedy_decode_stream", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred,
-                          b_pred, w_out, ld_out, b_out, blank, durations, max_symbols, max_out, stream=RNNTStreamState, state=state)
+                          b_pred, w_out, ld_out, b_out, blank, durations, max_symbols, max_out, stream=RNNTStreamState, state=state,
+                          upper_layers=upper_layers)
 
 
 def rnnt_greedy_decode_stream_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                                   b_out, blank, max_symbols, method, state=None, max_out=None):
+                                   b_out, blank, max_symbols, method, state=None, max_out=None, *, upper_layers=None):
     """rnnt_greedy_decode_stream plus the confidence of this chunk's labels (mi355x_transducer_greedy_decode with a state to write
     and a measure) -> (tokens, global frame indices, lengths, next state, tok_conf f32 [B, max_out] 0.0 padded); bit-identical to one launch for any cut"""
     return _greedy_search("rnnt_greedy_decode_stream_conf", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred,
                           ld_pred, b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, stream=RNNTStreamState,
-                          state=state, method=method)
+                          state=state, method=method, upper_layers=upper_layers)
 
 
 def tdt_greedy_decode_stream_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                                  b_out, blank, durations, max_symbols, method, state=None, max_out=None):
+                                  b_out, blank, durations, max_symbols, method, state=None, max_out=None, *, upper_layers=None):
     """tdt_greedy_decode_stream plus the confidence of this chunk's labels (mi355x_transducer_greedy_decode with a duration set, a
     state to write and a measure)"""
     return _greedy_search("tdt_greedy_decode_stream_conf", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred,
                           ld_pred, b_pred, w_out, ld_out, b_out, blank, durations, max_symbols, max_out, stream=RNNTStreamState,
-                          state=state, method=method)
+                          state=state, method=method, upper_layers=upper_layers)
 
 
 class RNNTFusedStreamState(RNNTStreamState):
@@ -1223,24 +1258,24 @@ class RNNTFusedStreamState(RNNTStreamState):
         self.m_state = m_state
 
     @classmethod
-    def empty(cls, B, H, device):
-        return cls(*RNNTStreamState.empty(B, H, device).tensors(), torch.ones(B, 2, dtype=torch.int32, device=device))
+    def empty(cls, B, H, device, layers=1):
+        return cls(*RNNTStreamState.empty(B, H, device, layers).tensors(), torch.ones(B, 2, dtype=torch.int32, device=device))
 
     @classmethod
-    def fresh(cls, B, H, blank, device):
-        return cls(*RNNTStreamState.fresh(B, H, blank, device).tensors(), torch.ones(B, 2, dtype=torch.int32, device=device))
+    def fresh(cls, B, H, blank, device, layers=1):
+        return cls(*RNNTStreamState.fresh(B, H, blank, device, layers).tensors(), torch.ones(B, 2, dtype=torch.int32, device=device))
 
     def tensors(self):
         return tuple(getattr(self, n) for n in self._base + self.__slots__)
 
     def select(self, b):
-        return RNNTFusedStreamState(*(t[b:b + 1] for t in self.tensors()))
+        return RNNTFusedStreamState(*(self._pick(t, b) for t in self.tensors()))
 
-    def _c(self, B, H):
+    def _c(self, B, H, layers=1):
         m = self.m_state
         if tuple(m.shape) != (B, 2) or m.dtype != torch.int32 or not m.is_contiguous():
             raise ValueError(f"stream state `m_state`: expected contiguous torch.int32 {(B, 2)}, got {m.dtype} {tuple(m.shape)}")
-        return RNNTStreamState(*self.tensors()[:len(self._base)])._c(B, H)   # (m_state travels beside it in the descriptor)
+        return RNNTStreamState(*self.tensors()[:len(self._base)])._c(B, H, layers)   # (m_state travels beside it in the descriptor)
 
 
 def _transducer_fusion_check(what, models, V1):
@@ -1259,7 +1294,7 @@ def _transducer_fusion_check(what, models, V1):
 
 
 def transducer_greedy_decode_fused(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
-                                   b_out, blank, max_symbols, models, durations=None, state=None, max_out=None):
+                                   b_out, blank, max_symbols, models, durations=None, state=None, max_out=None, *, upper_layers=None):
     """the greedy transducer search with shallow fusion (mi355x_transducer_greedy_decode with models, which include/mi355x_asr.h states):
     rnnt_greedy_decode's arguments, `models` = a list of one or two (NGramLM | BoostingTree, alpha) as in `ctc_beam_decode_fused`,
     `durations` for the TDT search.  A step whose arg-max is a label emits the label that ranks highest with the models' look-ups
@@ -1273,7 +1308,7 @@ def transducer_greedy_decode_fused(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld
     return _greedy_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
                           b_out, blank, durations, max_symbols, max_out, with_state=state is None,
                           stream=None if state is None else RNNTFusedStreamState, state=state,
-                          models=_transducer_fusion_check(what, models, emb.shape[0]))
+                          models=_transducer_fusion_check(what, models, emb.shape[0]), upper_layers=upper_layers)
 
 
 def row_scale(x, vec, rows, cols):

@@ -27,8 +27,15 @@ the search.  The difference of the two times is the fused kernel's; their ratio 
 The heads' weights are the modules' initialisation times 4 (the tests' scale), so that the joint emits labels and the models are
 consulted: a flat joint, as `--decoder rnnt` without --head-only builds it, emits blanks only.
 
+`--pred-layers N [N ...]` (default 1; 1..4): the LSTM layers of the transducer heads' prediction network.  With --head-only and
+neither --lm nor --boost the head is timed once per layer count on the same input, the counts alternating in the rounds of one
+process: per count the median, min and max of 7 rounds, the labels emitted, and the time relative to the first count.  The heads
+share the seed, not the hypotheses: every count is another network, so the labels differ and are reported.  Everywhere else the
+first count is the one that is built.
+
     python tools/stream_bench.py [--batch 1 16 64] [--steps 50] [--warmup 10] [--layers 17] [--decoder none] [--json OUT]
                                  [--beam-size 4 16 64] [--classes 129 1025] [--lm ORDER] [--boost P] [--head-only FRAMES ...]
+                                 [--pred-layers N ...]
 """
 import argparse
 import json
@@ -54,7 +61,7 @@ def build(n_layers):
     return enc
 
 
-def build_head(kind, d_model=512, fusion_models=None, scale=1.0):
+def build_head(kind, d_model=512, fusion_models=None, scale=1.0, pred_layers=1):
     """-> step(encoded [B, D, T], encoded_len) for the head `kind`, weights random (the step's cost does not depend on them much:
     the transducer search emits what a random joint emits, bounded by max_symbols = 10 per frame)"""
     from nemo_amd.modules import ConvASRDecoder, GreedyBatchedRNNTInfer, GreedyBatchedTDTInfer, RNNTDecoder, RNNTJoint
@@ -64,7 +71,8 @@ def build_head(kind, d_model=512, fusion_models=None, scale=1.0):
         dec = ConvASRDecoder(feat_in=d_model, num_classes=V, compute_dtype=torch.bfloat16).to(dev).eval()
         return lambda enc, n, state=None: (dec(encoder_output=enc).argmax(-1), None)
     durations = [0, 1, 2, 3, 4]
-    pred = RNNTDecoder(prednet={"pred_hidden": 640, "pred_rnn_layers": 1, "dropout": 0.0}, vocab_size=V, compute_dtype=torch.bfloat16)
+    pred = RNNTDecoder(prednet={"pred_hidden": 640, "pred_rnn_layers": pred_layers, "dropout": 0.0}, vocab_size=V,
+                       compute_dtype=torch.bfloat16)
     joint = RNNTJoint(jointnet={"encoder_hidden": d_model, "pred_hidden": 640, "joint_hidden": 640, "activation": "relu", "dropout": 0.0},
                       num_classes=V, num_extra_outputs=len(durations) if kind == "tdt" else 0, compute_dtype=torch.bfloat16)
     with torch.no_grad():
@@ -81,14 +89,45 @@ def build_head(kind, d_model=512, fusion_models=None, scale=1.0):
     return step
 
 
-def fused_head_setting(kind, lm_order, n_phrases, B, frames, steps, warmup, n_rounds=7, d_model=512):
+def layers_head_setting(kind, layer_counts, B, frames, steps, warmup, n_rounds=7, d_model=512):
+    """the transducer head alone on `frames` frames per stream, once per count of prediction-network layers, alternating rounds"""
+    import statistics
+    g = torch.Generator(device=dev).manual_seed(2)
+    enc_out = torch.randn(B, d_model, frames, device=dev, generator=g)
+    enc_len = torch.full((B,), frames, dtype=torch.int64, device=dev)
+    row = dict(decoder=kind, batch=B, frames=frames, layers=[])
+    with torch.no_grad():
+        fns, labels = {}, {}
+        for L in layer_counts:
+            head = build_head(kind, d_model, scale=4.0, pred_layers=L)
+            (_, out_len), state = head(enc_out, enc_len, lengths=True)
+            labels[L] = int(out_len.sum())
+            fns[L] = lambda head=head, state=state: head(enc_out, enc_len, state)
+        for fn in fns.values():
+            for _ in range(warmup):
+                fn()
+        torch.cuda.synchronize()
+        ms = {L: [] for L in fns}
+        for _ in range(n_rounds):
+            for L, fn in fns.items():
+                ms[L].append(timed(fn, steps))
+    first = statistics.median(ms[layer_counts[0]])
+    for L, v in ms.items():
+        med = statistics.median(v)
+        row["layers"].append(dict(pred_layers=L, labels=labels[L], ms=round(med, 3), ms_range=[round(min(v), 3), round(max(v), 3)],
+                                  ratio=round(med / first, 3)))
+    return row
+
+
+def fused_head_setting(kind, lm_order, n_phrases, B, frames, steps, warmup, n_rounds=7, d_model=512, pred_layers=1):
     """the transducer head alone on `frames` frames per stream: the plain search against the fused one, alternating rounds"""
     import statistics
     V = 1024
     g = torch.Generator(device=dev).manual_seed(2)
     enc_out = torch.randn(B, d_model, frames, device=dev, generator=g)
     enc_len = torch.full((B,), frames, dtype=torch.int64, device=dev)
-    plain = build_head(kind, d_model, scale=4.0)   # (the tests' scale: a joint that emits labels, so that the models are consulted)
+    # (the tests' scale: a joint that emits labels, so that the models are consulted)
+    plain = build_head(kind, d_model, scale=4.0, pred_layers=pred_layers)
     with torch.no_grad():
         (tokens, out_len), p_state = plain(enc_out, enc_len, lengths=True)
     models = []
@@ -101,8 +140,9 @@ def fused_head_setting(kind, lm_order, n_phrases, B, frames, steps, warmup, n_ro
         runs = [tuple(tokens[b, i:i + 3].tolist()) for b in range(B) for i in range(0, int(out_len[b]) - 2, 3)]
         runs = list(dict.fromkeys(runs))[:n_phrases]
         models.append((BoostingTree.from_phrases(runs, V), 2.0))
-    fused = build_head(kind, d_model, fusion_models=models, scale=4.0)   # (the same seed: the same weights)
-    row = dict(decoder=kind, batch=B, frames=frames, lm_order=lm_order, phrases=len(models[-1][0].phrases) if n_phrases else 0)
+    fused = build_head(kind, d_model, fusion_models=models, scale=4.0, pred_layers=pred_layers)   # (the same seed: the same weights)
+    row = dict(decoder=kind, batch=B, frames=frames, lm_order=lm_order, phrases=len(models[-1][0].phrases) if n_phrases else 0,
+               pred_layers=pred_layers)
     with torch.no_grad():
         (_, f_len), f_state = fused(enc_out, enc_len, lengths=True)
         row["labels_plain"], row["labels_fused"] = int(out_len.sum()), int(f_len.sum())
@@ -274,15 +314,21 @@ def main():
     ap.add_argument("--lm", type=int, default=0, metavar="ORDER")
     ap.add_argument("--boost", type=int, default=0, metavar="P")
     ap.add_argument("--head-only", type=int, nargs="+", default=None, metavar="FRAMES")
+    ap.add_argument("--pred-layers", type=int, nargs="+", default=[1], metavar="N", choices=[1, 2, 3, 4])
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     if args.head_only:
-        if args.decoder not in ("rnnt", "tdt") or not (args.lm or args.boost):
-            ap.error("--head-only compares the transducer heads with and without fusion: --decoder rnnt|tdt and --lm and / or --boost")
+        if args.decoder not in ("rnnt", "tdt"):
+            ap.error("--head-only times the transducer heads: --decoder rnnt|tdt (with --lm and / or --boost: with and without "
+                     "fusion; without them: per --pred-layers count)")
         rows = []
         for B in args.batch:
             for frames in args.head_only:
-                rows.append(fused_head_setting(args.decoder, args.lm, args.boost, B, frames, args.steps, args.warmup))
+                if args.lm or args.boost:
+                    rows.append(fused_head_setting(args.decoder, args.lm, args.boost, B, frames, args.steps, args.warmup,
+                                                   pred_layers=args.pred_layers[0]))
+                else:
+                    rows.append(layers_head_setting(args.decoder, args.pred_layers, B, frames, args.steps, args.warmup))
                 print(json.dumps(rows[-1]), flush=True)
         if args.json:
             with open(args.json, "w") as f:
@@ -293,7 +339,7 @@ def main():
         head = [(dict(classes=C, beam_size=W, lm_order=args.lm), build_beam_head(C, W, args.lm)) for C in args.classes
                 for W in args.beam_size]
     else:
-        head = build_head(args.decoder) if args.decoder != "none" else None
+        head = build_head(args.decoder, pred_layers=args.pred_layers[0]) if args.decoder != "none" else None
     rows = []
     for B in args.batch:
         r = one_setting(enc, B, args.steps, args.warmup, head, args.decoder)

@@ -1071,6 +1071,62 @@ typedef struct mi355x_transducer_lstm_layers {   /* layers 1 .. n_upper of the p
 int mi355x_transducer_greedy_decode_layers(const mi355x_transducer_greedy_desc* d, const mi355x_transducer_lstm_layers* upper,
                                            void* stream);
 
+/* ---- beam search of the transducer heads on the device (`strategy: malsd_batch`: batched, alignment-length synchronous, with
+ * merging of equal hypotheses), RNN-T and TDT, one-shot, one LSTM layer.  ONE launch for the batch.  Parity with the reference's
+ * numbers is not claimed: THE RULE below is the contract.  Weights, inputs and geometry are those of the greedy descriptor.
+ * Per utterance with len = enc_len[b] valid frames a beam of W = `beam` slots is kept.  A hypothesis holds: its token sequence with
+ * the frame of each token; its frame t; score, the sum of log-probabilities; the LSTM state (h, c) after consuming its last label;
+ * the prediction projection gp = W_pred . h + b_pred of that state; sym, the labels emitted at frame t (TDT: the current run of
+ * labels of duration 0).  Start: slot 0 is live with the empty sequence, t = 0, score 0, sym 0 and the state of one prediction step
+ * from (h, c) = 0 on the zero (start-of-sequence) input; the other slots are empty.  len == 0: one empty hypothesis, score 0.
+ * One step, repeated while any hypothesis has t < len, at most len + max_out times (then the search stops as it stands):
+ *   1. joint, for every live hypothesis with t < len: lg = W_out . relu(enc_proj[t] + gp) + b_out; lp[v] = lg[v] - lse(lg[0:V1]);
+ *      TDT: ld[i] = lg[V1+i] - lse(lg[V1:V1+D]); lse(x) = max x + log(sum exp(x - max x)).
+ *   2. candidates.  RNN-T: blank (score + lp[blank], t + 1, same tokens, sym = 0); every label v != blank (score + lp[v], t,
+ *      tokens + v at frame t, sym + 1).  TDT: for every label v and duration index i the candidate score + (lp[v] + ld[i]); a blank
+ *      advances t by max(d_i, 1), sym = 0; a label by d_i with sym = (d_i == 0 ? sym + 1 : 0), and a label whose new sym reaches
+ *      max_symbols (> 0) with d_i == 0 advances by 1, sym = 0 (the greedy kernel's rule).  A hypothesis with sym == max_symbols
+ *      (RNN-T, max_symbols > 0) or with max_out tokens offers its blank candidate(s) only.  A finished hypothesis (t >= len)
+ *      offers itself, unchanged.
+ *   3. select: the W best candidates by score.  Ties: the lower parent slot, then blank before labels, then the lower label id,
+ *      then the lower duration index.  Candidates whose score is -inf or NaN rank last and are not kept.  The k-th best becomes
+ *      the new slot k.
+ *   4. merge: selected hypotheses with equal token sequences and equal t become one: the best-ranked slot survives with its
+ *      frames and state, its score = logaddexp(score, other) = max + log1p(exp(min - max)) over the others in rank order; their
+ *      slots are emptied.  Equality is of the sequences themselves (length and a rolling hash screen; a match is confirmed by
+ *      walking both sequences in the prefix tree).
+ *   5. advance: a surviving label-extended hypothesis runs the prediction step on emb[v] and its parent's (h, c):
+ *      z = ((W_hh . h + b_hh) + W_ih . emb[v]) + b_ih (torch gate order i, f, g, o), c' = sigmoid(f) c + sigmoid(i) tanh(g),
+ *      h' = sigmoid(o) tanh(c'), gp' = W_pred . h' + b_pred.  A blank-extended or finished one copies its parent's.
+ * At the end the hypotheses are ordered by score, best first, then by slot.  Scores are not length-normalised.  beam = 1 takes the
+ * decisions of the greedy search (its score also counts the blanks).
+ * Precision: fp32 weights: every product float32 on float32 operands.  bf16 weight images: the activation operands of the four
+ * contractions (h, emb[v], h' and relu(enc_proj + gp)) are rounded to bf16, round to nearest even; accumulation, biases, cell,
+ * softmaxes and scores stay float32.
+ * Outputs: tokens / times i32 [B, beam, max_out] (-1 padded), out_len i32 [B, beam], score f32 [B, beam] (-inf for empty ranks),
+ * n_hyp i32 [B].  workspace: at least mi355x_transducer_beam_workspace_bytes(B, T, H, J, beam, max_out) bytes, 16-byte aligned (the
+ * beam's states in two halves and the prefix tree; -1 for arguments the search refuses).
+ * MI_ERR_ARG, before anything is launched: a NULL descriptor or array (enc_len may be NULL: every utterance has T frames); beam
+ * outside 1..16; B, T, H, J, max_out < 1; V1 < 2 or >= 131071; blank outside [0, V1); H, J or a weight pitch not a multiple of 8
+ * (bf16) / 4 (fp32), or a pitch below its row; a weight pointer or the workspace not 16-byte aligned; unknown dtypes; an invalid
+ * duration set (D == 0 and durations NULL: RNN-T); a short workspace; an LDS need above 152 KiB: the larger of three [16, H + pad]
+ * operand tiles and one [16, J + pad] tile with the float32 logits [16, V1 + D] behind it. */
+typedef struct mi355x_transducer_beam_desc {
+  const void* enc_proj; const void* enc_len;                                           /* input (enc_len i64 [B])        */
+  const void* emb; const void* w_ih; const void* w_hh; const void* w_pred; const void* w_out;   /* weights               */
+  const void* b_ih; const void* b_hh; const void* b_pred; const void* b_out;
+  const int* durations;                                                                /* TDT: host array [D]            */
+  void* tokens; void* times; void* out_len; void* score; void* n_hyp;                  /* outputs                        */
+  void* workspace;
+  long long workspace_bytes;
+  long long ldf, ld_ih, ld_hh, ld_pred, ld_out;
+  int f_dtype, w_dtype;
+  int B, T, J, H, V1, blank, max_symbols, max_out;
+  int D, beam;
+} mi355x_transducer_beam_desc;
+long long mi355x_transducer_beam_workspace_bytes(int B, int T, int H, int J, int beam, int max_out);
+int mi355x_transducer_beam_decode(const mi355x_transducer_beam_desc* d, void* stream);
+
 /* ---- cache-aware streaming inference (ConformerEncoder.cache_aware_stream_step; the `update_cache` paths of
  * RelPositionMultiHeadAttention and CausalConv1D).  Caches are f32 in the reference's layouts; in bf16 compute they hold the
  * bf16-rounded operands widened to f32, so a streamed chunk reads the same operand values as the offline forward.

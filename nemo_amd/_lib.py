@@ -81,6 +81,15 @@ class TransducerGreedyDesc(C.Structure):
         + [(n, i32) for n in ("f_dtype", "w_dtype", "B", "T", "J", "H", "V1", "blank", "max_symbols", "max_out", "D", "n_models")])
 
 
+class TransducerBeamDesc(C.Structure):
+    """mirror of `mi355x_transducer_beam_desc`; durations points to int[D] on the host"""
+    _fields_ = (
+        [(n, vp) for n in ("enc_proj", "enc_len", "emb", "w_ih", "w_hh", "w_pred", "w_out", "b_ih", "b_hh", "b_pred", "b_out",
+                           "durations", "tokens", "times", "out_len", "score", "n_hyp", "workspace")]
+        + [(n, i64) for n in ("workspace_bytes", "ldf", "ld_ih", "ld_hh", "ld_pred", "ld_out")]
+        + [(n, i32) for n in ("f_dtype", "w_dtype", "B", "T", "J", "H", "V1", "blank", "max_symbols", "max_out", "D", "beam")])
+
+
 class TransducerLstmLayers(C.Structure):
     """mirror of `mi355x_transducer_lstm_layers`: layers 1 .. n_upper of the prediction network (slot l = layer l + 1)"""
     _fields_ = [("n_upper", i32), ("w_ih", vp * 3), ("w_hh", vp * 3), ("b_ih", vp * 3), ("b_hh", vp * 3), ("ld_ih", i64 * 3),
@@ -215,6 +224,8 @@ SIGNATURES = {
     "mi355x_rnnt_loss": [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, i64, vp],
     "mi355x_transducer_greedy_decode": [C.POINTER(TransducerGreedyDesc), vp],
     "mi355x_transducer_greedy_decode_layers": [C.POINTER(TransducerGreedyDesc), C.POINTER(TransducerLstmLayers), vp],
+    "mi355x_transducer_beam_decode": [C.POINTER(TransducerBeamDesc), vp],
+    "mi355x_transducer_beam_workspace_bytes": [i32, i32, i32, i32, i32, i32],
     "mi355x_dwconv_config": [i32],
     "mi355x_ctc_config": [i32],
     "mi355x_ctc_align_config": [i32],
@@ -262,6 +273,7 @@ def _load():
     lib.mi355x_relpos_dpos_partial_elems.restype = i64
     lib.mi355x_ctc_beam_workspace_elems.restype = i64
     lib.mi355x_ctc_beam_commit_workspace_elems.restype = i64
+    lib.mi355x_transducer_beam_workspace_bytes.restype = i64
     lib.mi355x_asr_version.argtypes = []
     lib.mi355x_tape_destroy.restype = None
     lib.mi355x_mailbox_destroy.restype = None

@@ -19,7 +19,6 @@ from .ctc_models import (_is_beam, ctc_align_audio, ctc_fill_confidence, ctc_tra
                          frame_stride_s)
 from .rnnt_models import EncDecRNNTModel, fastconformer_tdt_config, fastconformer_transducer_config, rnnt_conformer_stream_step
 
-_GREEDY = ("greedy", "greedy_batch")
 
 
 def _check_ctc_strategy(dcfg):
@@ -132,9 +131,8 @@ class EncDecHybridRNNTCTCModel(EncDecRNNTModel):
         does the same for the auxiliary head (`aux_ctc.decoding`)"""
         if decoder_type is None or decoder_type == "rnnt":
             if decoding_cfg is not None:
-                strategy = dict(decoding_cfg).get("strategy", "greedy_batch")
-                if strategy not in _GREEDY:
-                    raise NotImplementedError(f"transducer decoding strategy '{strategy}' (implemented: greedy, greedy_batch)")
+                from ..modules.rnnt_decoding import transducer_beam_from_config
+                transducer_beam_from_config(decoding_cfg)   # (refuses what is not implemented, by name)
                 self._cfg["decoding"] = dict(decoding_cfg)
             self._decoding = None
             self._wer = None

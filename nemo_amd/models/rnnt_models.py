@@ -4,7 +4,8 @@ encoder / decoder (prediction network) / joint / loss (rnnt_models.py:50-120), `
 output), `training_step` (:692-760: decoder -> joint, fused with the loss when `joint.fuse_loss_wer`), and the optimizer /
 data-parallel machinery shared with the CTC model (`fit_step`, bucketed gradient exchange over the flat buffers of encoder,
 prediction network and joint), greedy batched decoding + WER on the device (`decoding`, `wer`, `validation_pass`, `transcribe`:
-rnnt_models.py:92-110, 245-330, 790-850; modules/rnnt_decoding.py).  Beam search is outside this path."""
+rnnt_models.py:92-110, 245-330, 790-850; modules/rnnt_decoding.py).  `decoding.strategy: malsd_batch` selects the on-device beam
+search (csrc/rnnt_beam.hip); the reference's other beam strategies are refused."""
 from __future__ import annotations
 
 import copy
@@ -120,9 +121,8 @@ class EncDecRNNTModel(EncDecCTCModel):
                 return None
             from ..modules import RNNTDecoding
             dcfg = dict(self._cfg.get("decoding") or {})
-            strategy = dcfg.get("strategy", "greedy_batch")
-            if strategy not in ("greedy", "greedy_batch"):
-                raise NotImplementedError(f"transducer decoding strategy '{strategy}' (implemented: greedy, greedy_batch)")
+            from ..modules.rnnt_decoding import transducer_beam_from_config
+            beam = transducer_beam_from_config(dcfg)   # None: the greedy strategies; malsd_batch: the beam decoders' arguments
             greedy = dict(dcfg.get("greedy") or {})
             ms = greedy.get("max_symbols", 10)
             # shallow fusion (`greedy.ngram_lm_arpa`, `greedy.boosting_tree`): None without those keys, and nothing changes
@@ -137,15 +137,14 @@ class EncDecRNNTModel(EncDecCTCModel):
             self._decoding = RNNTDecoding(self.decoder, self.joint, vocabulary=list(vocab) if vocab is not None else None,
                                           max_symbols=ms, tokenizer=self.tokenizer if vocab is None else None,
                                           model_type=model_type, durations=list(durations) if durations else None,
-                                          confidence_cfg=dcfg.get("confidence_cfg"), fusion_models=fusion)
+                                          confidence_cfg=dcfg.get("confidence_cfg"), fusion_models=fusion, beam=beam)
         return self._decoding
 
     def change_decoding_strategy(self, decoding_cfg=None, verbose: bool = True):
         """rnnt_models.py:340-380: rebuilds the decoding object (and the WER over it) from `decoding_cfg` (kept when None)"""
         if decoding_cfg is not None:
-            strategy = dict(decoding_cfg).get("strategy", "greedy_batch")
-            if strategy not in ("greedy", "greedy_batch"):
-                raise NotImplementedError(f"transducer decoding strategy '{strategy}' (implemented: greedy, greedy_batch)")
+            from ..modules.rnnt_decoding import transducer_beam_from_config
+            transducer_beam_from_config(decoding_cfg)   # (refuses what is not implemented, by name)
             self._cfg["decoding"] = dict(decoding_cfg)
         self._decoding = None
         self._wer = None
@@ -336,6 +335,8 @@ def rnnt_conformer_stream_step(model, processed_signal, processed_signal_length=
         raise NotImplementedError(f"{type(model.encoder).__name__} has no cache-aware streaming")
     if model.decoding is None:
         raise RuntimeError("conformer_stream_step needs a vocabulary (`labels` or a tokenizer)")
+    if getattr(model.decoding.decoding, "beam_size", None) is not None:   # strategy malsd_batch is one-shot: refused by name
+        model.decoding.decoding.fresh_hypotheses(0)
     encoded, encoded_len, ch_next, t_next, len_next = model.encoder.cache_aware_stream_step(
         processed_signal=processed_signal, processed_signal_length=processed_signal_length, cache_last_channel=cache_last_channel,
         cache_last_time=cache_last_time, cache_last_channel_len=cache_last_channel_len, keep_all_outputs=keep_all_outputs,

@@ -40,6 +40,13 @@ a blank stays a blank, and the score of a hypothesis carries the models' terms, 
 stream state is an `ops.RNNTFusedStreamState` (one automaton state per model and stream) and a streaming `Hypothesis.score` is the
 kernel's `score` output, so it equals the one-shot score.  Without models every call is exactly what it was.  Together with token
 or word confidence it is refused (the measure belongs to the unfused distribution).
+
+Beam search (`decoding: {strategy: malsd_batch, beam: {beam_size, return_best_hypothesis, max_symbols_per_step, score_norm}}`):
+`BeamBatchedRNNTInfer` / `BeamBatchedTDTInfer` run `ops.transducer_beam_decode` (csrc/rnnt_beam.hip), one launch for the batch,
+whose rule include/mi355x_asr.h states; parity with the reference's `malsd_batch` numbers is not claimed.  The hypotheses carry
+`y_sequence`, `timestamp` and `score` (the sum of log-probabilities, blanks included, merged paths added; not length-normalised)
+and, with `return_best_hypothesis: false`, `n_best`.  One-shot, one LSTM layer, beam_size <= 16; everything else is refused by
+name (`transducer_beam_from_config`).
 """
 from __future__ import annotations
 
@@ -304,6 +311,104 @@ class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
         return ops.tdt_greedy_decode_stream_conf(*args[:16], self.durations, args[16], method, **kw)
 
 
+class BeamBatchedRNNTInfer(GreedyBatchedRNNTInfer):
+    """`strategy: malsd_batch` for an RNN-T head: `forward(encoder_output [B, D, T], encoded_lengths)` -> a 1-tuple holding the
+    best `Hypothesis` of every utterance (y_sequence, timestamp, score); with `return_best_hypothesis=False` each also carries
+    `n_best`, the list of all kept hypotheses as `Hypothesis` objects, best first"""
+    durations = None
+
+    def __init__(self, decoder_model, joint_model, blank_index: int, beam_size: int = 4, max_symbols_per_step: Optional[int] = 10,
+                 return_best_hypothesis: bool = True, score_norm: bool = False, preserve_alignments: bool = False,
+                 confidence_cfg=None, **unused):
+        from .confidence import confidence_from
+        conf = confidence_from(confidence_cfg)
+        if conf is not None and (conf.wants_tokens or conf.preserve_frame_confidence):
+            raise NotImplementedError("strategy 'malsd_batch' with a `confidence_cfg` that preserves confidences: the beam search "
+                                      "computes none")
+        if preserve_alignments:
+            raise NotImplementedError("strategy 'malsd_batch' with `preserve_alignments`: the beam search keeps no alignments")
+        if score_norm:
+            raise NotImplementedError("strategy 'malsd_batch' with `score_norm: true`: scores are not length-normalised")
+        if not 1 <= int(beam_size) <= 16:
+            if int(beam_size) < 1:
+                raise ValueError(f"`beam_size` must be >= 1; got {beam_size}")
+            raise NotImplementedError(f"strategy 'malsd_batch' with `beam_size` = {beam_size}: the on-device beam holds at most 16")
+        if int(getattr(decoder_model, "pred_rnn_layers", 1)) != 1:
+            raise NotImplementedError(f"strategy 'malsd_batch' with `pred_rnn_layers` = {decoder_model.pred_rnn_layers}: the beam "
+                                      "search runs one LSTM layer")
+        super().__init__(decoder_model, joint_model, blank_index, max_symbols_per_step=max_symbols_per_step)
+        self.beam_size, self.return_best_hypothesis = int(beam_size), bool(return_best_hypothesis)
+
+    @torch.no_grad()
+    def decode_ids(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor):
+        """encoder_output [B, D, T] (device) -> (tokens i32 [B, W, N] -1 padded, frame indices, lengths i32 [B, W], scores f32
+        [B, W] best first, n_hyp i32 [B])"""
+        f, args = self._project(encoder_output)
+        lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        return ops.transducer_beam_decode(f, lens, *args, self.beam_size, durations=self.durations)
+
+    def fresh_hypotheses(self, batch_size: int, device=None):
+        raise NotImplementedError("strategy 'malsd_batch' with `partial_hypotheses` (rnnt_conformer_stream_step): the beam search is "
+                                  "one-shot")
+
+    def forward(self, encoder_output: torch.Tensor, encoded_lengths: torch.Tensor, partial_hypotheses=None):
+        if partial_hypotheses is not None:
+            self.fresh_hypotheses(0)
+        tokens, times, out_len, score, n_hyp = (t.cpu() for t in self.decode_ids(encoder_output, encoded_lengths))
+        hyps = []
+        for b in range(encoder_output.shape[0]):
+            nb = [Hypothesis(score=float(score[b, k]), y_sequence=tokens[b, k, :int(out_len[b, k])].to(torch.long),
+                             timestamp=times[b, k, :int(out_len[b, k])].tolist(), length=int(encoded_lengths[b]))
+                  for k in range(int(n_hyp[b]))]
+            if not self.return_best_hypothesis:
+                nb[0].n_best = list(nb)
+            hyps.append(nb[0])
+        return (hyps,)
+
+    __call__ = forward
+
+
+class BeamBatchedTDTInfer(BeamBatchedRNNTInfer):
+    """`strategy: malsd_batch` for a TDT head: a candidate per (label, duration), frames advance by the duration"""
+
+    def __init__(self, decoder_model, joint_model, blank_index: int, durations, **kw):
+        super().__init__(decoder_model, joint_model, blank_index, **kw)
+        from .tdt_loss import check_durations
+        self.durations = check_durations(list(durations))
+        if getattr(joint_model, "_num_extra_outputs", len(self.durations)) != len(self.durations):
+            raise ValueError(f"the joint has {joint_model._num_extra_outputs} extra outputs for {len(self.durations)} durations")
+
+
+_BEAM_KEYS = ("beam_size", "return_best_hypothesis", "max_symbols_per_step", "score_norm")
+
+
+def transducer_beam_from_config(decoding_cfg, what: str = "transducer"):
+    """The transducer head's `decoding` section -> None for the greedy strategies, or for `strategy: malsd_batch` the keyword
+    arguments of the beam decoders read from its `beam` sub-section (beam_size 4, return_best_hypothesis true,
+    max_symbols_per_step 10, score_norm false).  Every other strategy, and under malsd_batch `allow_cuda_graphs`, `ngram_lm_*` /
+    `boosting_tree*`, `preserve_alignments` and any key this search does not know, is refused by name."""
+    dcfg = dict(decoding_cfg or {})
+    strategy = dcfg.get("strategy", "greedy_batch")
+    if strategy in ("greedy", "greedy_batch"):
+        return None
+    if strategy != "malsd_batch":
+        raise NotImplementedError(f"{what} decoding strategy '{strategy}' (implemented: greedy, greedy_batch, malsd_batch)")
+    beam = dict(dcfg.get("beam") or {})
+    if dcfg.get("preserve_alignments") or beam.get("preserve_alignments"):
+        raise NotImplementedError(f"{what} decoding: strategy 'malsd_batch' with `preserve_alignments`")
+    for key, value in beam.items():
+        if key in _BEAM_KEYS:
+            continue
+        if key == "allow_cuda_graphs" and not value:
+            continue
+        if (key.startswith("ngram_lm") or key.startswith("boosting_tree")) and not value:
+            continue
+        raise NotImplementedError(f"{what} decoding: strategy 'malsd_batch' with `beam.{key}`")
+    return dict(beam_size=int(beam.get("beam_size", 4)), return_best_hypothesis=bool(beam.get("return_best_hypothesis", True)),
+                max_symbols_per_step=beam.get("max_symbols_per_step", 10), score_norm=bool(beam.get("score_norm", False)),
+                preserve_alignments=False)
+
+
 def transducer_fusion_from_config(greedy, vocabulary=None, text_to_ids=None, what: str = "transducer"):
     """The fusion models of a transducer head's `decoding.greedy` sub-section, read by the CTC head's readers (modules/
     ctc_decoding.py) under the section name `greedy`: ngram_lm_arpa, ngram_lm_alpha, ngram_lm_token_offset, boosting_tree
@@ -329,13 +434,23 @@ class RNNTDecoding:
 
     def __init__(self, decoder, joint, vocabulary: Optional[Sequence[str]] = None, max_symbols: Optional[int] = 10,
                  tokenizer=None, model_type: str = "rnnt", durations: Optional[Sequence[int]] = None, confidence_cfg=None,
-                 fusion_models=None):
+                 fusion_models=None, beam=None):
         from .confidence import confidence_from
         self.vocabulary = list(vocabulary) if vocabulary is not None else None
         self.tokenizer = tokenizer
         self.blank_id = decoder.blank_idx
         self.confidence_cfg = confidence_from(confidence_cfg)
-        if model_type == "tdt":   # rnnt_decoding.py: `model_type: tdt` with the duration set of the joint's extra outputs
+        if model_type not in ("rnnt", "tdt"):
+            raise NotImplementedError(f"transducer decoding model_type '{model_type}' (implemented: rnnt, tdt)")
+        if model_type == "tdt" and not durations:
+            raise ValueError("decoding with model_type 'tdt' needs `durations`")
+        if beam is not None:   # strategy malsd_batch: the keyword arguments `transducer_beam_from_config` read
+            if fusion_models:
+                raise NotImplementedError("strategy 'malsd_batch' with fusion models (`ngram_lm_*` / `boosting_tree`)")
+            beam = dict(beam, confidence_cfg=self.confidence_cfg)
+            self.decoding = (BeamBatchedTDTInfer(decoder, joint, self.blank_id, durations, **beam) if model_type == "tdt"
+                             else BeamBatchedRNNTInfer(decoder, joint, self.blank_id, **beam))
+        elif model_type == "tdt":   # rnnt_decoding.py: `model_type: tdt` with the duration set of the joint's extra outputs
             if not durations:
                 raise ValueError("decoding with model_type 'tdt' needs `durations`")
             self.decoding = GreedyBatchedTDTInfer(decoder, joint, self.blank_id, durations, max_symbols_per_step=max_symbols,
@@ -362,6 +477,8 @@ class RNNTDecoding:
         words = self.confidence_cfg is not None and self.confidence_cfg.preserve_word_confidence
         for h in hyps:
             h.text = self.ids_to_text(h.y_sequence.tolist())
+            for alt in h.n_best or ():   # beam search with return_best_hypothesis off
+                alt.text = self.ids_to_text(alt.y_sequence.tolist())
             if words:
                 h.word_confidence = self.word_confidence(h.y_sequence.tolist(), h.token_confidence)
         return hyps

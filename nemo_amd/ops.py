@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import ConvGather, GemmDesc, PackEntry, RowMap, TransducerConf, TransducerGreedyDesc, TransducerLstmLayers, check, lib
+from ._lib import ConvGather, GemmDesc, PackEntry, RowMap, TransducerBeamDesc, TransducerConf, TransducerGreedyDesc, TransducerLstmLayers, check, lib
 
 F32, BF16 = 0, 1
 EPI_STORE, EPI_SWISH_DROP, EPI_RESID, EPI_DSWISH, EPI_RELU_MASK, EPI_MUL_POS, EPI_SWISH_DROP_G, EPI_DSWISH_G = range(8)
@@ -1112,6 +1112,40 @@ def rnnt_greedy_decode_conf(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_
 def _tdt_durations(durations):
     d = [int(x) for x in durations]
     return len(d), (C.c_int * len(d))(*d)
+
+
+def transducer_beam_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
+                           blank, max_symbols, beam_size, durations=None, max_out=None):
+    """beam search of a transducer head for a whole batch in one launch (mi355x_transducer_beam_decode; include/mi355x_asr.h states
+    the rule): the arguments of rnnt_greedy_decode (`durations` given: TDT, w_out / b_out with V1 + len(durations) rows), one LSTM
+    layer, beam_size in 1..16.  -> (tokens i32 [B, beam, max_out] -1 padded, frame indices likewise, lengths i32 [B, beam], score
+    f32 [B, beam] best first and -inf in the empty ranks, n_hyp i32 [B])"""
+    B, T, J = enc_proj.shape
+    V1, H = emb.shape
+    W = int(beam_size)
+    if max_out is None:
+        max_out = T * max_symbols if max_symbols > 0 else 4 * T
+    dev = enc_proj.device
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    tokens, times, out_len, n_hyp = i32(B, W, max_out), i32(B, W, max_out), i32(B, W), i32(B)
+    score = torch.empty(B, W, dtype=torch.float32, device=dev)
+    nbytes = lib.mi355x_transducer_beam_workspace_bytes(B, T, H, J, W, max_out)
+    if nbytes < 0:
+        raise ValueError(f"transducer_beam_decode: beam_size in 1..16 and positive sizes; got beam_size = {W}, B, T, H, J, max_out = "
+                         f"{(B, T, H, J, max_out)}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    d = TransducerBeamDesc(
+        enc_proj=_ptr(enc_proj), f_dtype=dt(enc_proj), ldf=enc_proj.stride(1), enc_len=_ptr(enc_len), emb=_ptr(emb),
+        w_ih=_ptr(w_ih), ld_ih=ld_ih, w_hh=_ptr(w_hh), ld_hh=ld_hh, w_pred=_ptr(w_pred), ld_pred=ld_pred, w_out=_ptr(w_out),
+        ld_out=ld_out, w_dtype=dt(w_ih), b_ih=_ptr(b_ih), b_hh=_ptr(b_hh), b_pred=_ptr(b_pred), b_out=_ptr(b_out),
+        B=B, T=T, J=J, H=H, V1=V1, blank=blank, max_symbols=max_symbols, max_out=max_out, beam=W,
+        tokens=_ptr(tokens), times=_ptr(times), out_len=_ptr(out_len), score=_ptr(score), n_hyp=_ptr(n_hyp),
+        workspace=_ptr(ws), workspace_bytes=nbytes)
+    if durations is not None:
+        d.D, dur = _tdt_durations(durations)
+        d.durations = C.addressof(dur)
+    check(lib.mi355x_transducer_beam_decode(C.byref(d), _stream()), "transducer_beam_decode")
+    return tokens, times, out_len, score, n_hyp
 
 
 def tdt_loss_pitched(acts, ld_acts, B, T, U1, V1, durations, labels, act_lens, label_lens, blank, grads=None, ld_grads=0,

@@ -1127,6 +1127,71 @@ typedef struct mi355x_transducer_beam_desc {
 long long mi355x_transducer_beam_workspace_bytes(int B, int T, int H, int J, int beam, int max_out);
 int mi355x_transducer_beam_decode(const mi355x_transducer_beam_desc* d, void* stream);
 
+/* ---- the stateless prediction network (`StatelessTransducerDecoder` / `StatelessNet`): training forward and backward, the
+ * prediction tables of the search and the greedy search (csrc/stateless.hip).  The StatelessNet rule below was written from memory
+ * of the reference, which was not at hand: parity with the reference's numbers is not claimed.  THE RULE is the contract.
+ * E = pred_hidden, C = context_size in 1..4, V1 = vocabulary + 1, blank = V1 - 1 in the modules (any row here).  Embedding tables
+ * emb_i f32 [V1, e_i], i = 0 .. C-1 with i = 0 the MOST RECENT label: e_i = E / 2 / C (integer divisions) for i > 0, e_0 = E -
+ * (C - 1) * (E / 2 / C); off_i = e_0 + .. + e_{i-1}.  Row `blank` of every table is zero and stays zero (the padding row: it gets
+ * no gradient).  A label id outside [0, V1) is treated as blank.
+ * Training forward (mi355x_stateless_pred_fwd): targets i64 [B, U]; position u of s = [blank, y_0, .., y_{U-1}] (U1 = U + 1):
+ *     g[b, u, off_i : off_i + e_i] = emb_i[s[u - i]]   for u - i >= 0, else 0
+ * then the counter-based dropout bits of the library on element index (b * U1 + u) * E + column (drop_threshold 0: none).  out
+ * [B, U1, E] in `dtype` (f32: a copy, exact; bf16: rounded to nearest even), 16-byte aligned; B * U1 * E < 2^32.  emb / demb:
+ * HOST arrays of C device pointers.
+ * Training backward (mi355x_stateless_embed_bwd): dg [B, U1, E] in `dtype`, the same dropout triple as the forward;
+ *     d emb_i[v] = sum over (b, u) with s[u - i] == v, v != blank, of mask * dg[b, u, off_i : off_i + e_i]
+ * accumulated in float32 in ascending (b, u) order by one wave per row: no atomics, two runs give the same bits.  accumulate == 0:
+ * every row of demb_i is WRITTEN (unused rows and the blank row: 0; no memset is needed); != 0: the sum is added to what is there
+ * (the blank row is left alone).
+ * Prediction tables (mi355x_stateless_tables): tables f32 [C, V1, J], P_i = emb_i . W_pred[:, off_i : off_i + e_i]^T with w_pred
+ * [J, E] in w_dtype (row pitch ld_pred >= E) -- MFMA tiles with K = e_i, K tails zero in both operands; row `blank` of every P_i is
+ * written as zero.  fp32 masters: float32 products; bf16 images: emb_i is rounded to bf16 as the other operand, sums float32.
+ * One search step of a stream with context (c_0, .., c_{C-1}) (all `blank` at the start) on frame t:
+ *     gp = (..((P_0[c_0] + P_1[c_1]) + P_2[c_2]) ..) + b_pred          lg = W_out . relu(enc_proj[t] + gp) + b_out
+ * in float32 (bf16 images: relu(enc_proj + gp) is rounded to bf16 as the MFMA operand; tables, biases, soft-max and score stay
+ * float32).  Everything behind that is mi355x_transducer_greedy_decode's rule: first arg-max over lg[0:V1]; a blank moves to the
+ * next frame, a label is emitted at frame t and shifts into the context (c_i <- c_{i-1}, c_0 <- v); max_symbols labels per frame
+ * (<= 0: unlimited, the stream ends once max_out labels are out; > 0: labels beyond max_out are counted and scored, not stored);
+ * score = the sum of the emitted labels' log-probabilities; TDT (D, durations): the duration is the first arg-max of the D duration
+ * logits, a blank advances by max(d, 1), a label by d, the max_symbols-th consecutive label of duration 0 by one frame, at most
+ * max_out labels.
+ * mi355x_stateless_greedy_decode: ONE launch for the batch, a workgroup per 16 streams (the rows of one MFMA tile, so W_out is read
+ * once per step for 16 streams); a stream's results do not depend on which streams share its workgroup.  enc_proj [B, T, J]
+ * (f_dtype, row pitch ldf), enc_len i64 [B] (NULL: T frames each), w_out [V1 + D, J] in w_dtype (row pitch ld_out), b_pred f32 [J],
+ * b_out f32 [V1 + D]; tokens / times i32 [B, max_out] (-1 padded; times and score optional), out_len i32 [B], score f32 [B].
+ * Resumable: state_out given (state_out alone: fresh streams; state_in without state_out: MI_ERR_ARG; written out of place, no
+ * array of state_out may alias its counterpart).  Per stream: ctx i32 [B, C] (fresh: blank), score f32 [B] (0), frames_done i32 [B]
+ * (0; added to every frame index written), sym i32 [B] (TDT: the current run of labels of duration 0; RNN-T: 0), skip i32 [B] (TDT:
+ * frames of this chunk an earlier duration already jumped over).  enc_len[b] = the frames of THIS chunk; tokens / times / out_len
+ * hold this chunk's labels.  Any cut of a stream into chunks gives the bits of one launch: tokens, frames, lengths and score.
+ * MI_ERR_ARG, before anything is launched: a NULL descriptor or required array; C outside 1..4 (and E / 2 / C == 0 with C > 1);
+ * B, T, J, max_out < 1; U < 0; V1 < 2; blank outside [0, V1); unknown dtypes; J or ld_out not a multiple of 8 (bf16) / 4 (fp32),
+ * ldf not a multiple of 4, a pitch below its row; enc_proj, tables, b_pred, w_out, out / dg not 16-byte aligned; an invalid duration
+ * set (D == 0 and durations NULL: RNN-T); a state that is not given whole; an LDS need above 152 KiB: the [16, J + pad] operand
+ * tile with the float32 logits [16, (V1 + D) | 1] behind it. */
+int mi355x_stateless_pred_fwd(const void* targets, const void* const* emb, void* out, int dtype, int B, int U, int E, int C, int V1,
+                              int blank, unsigned drop_key, unsigned drop_threshold, float drop_scale, void* stream);
+int mi355x_stateless_embed_bwd(const void* targets, const void* dg, int dtype, void* const* demb, int accumulate, int B, int U, int E,
+                               int C, int V1, int blank, unsigned drop_key, unsigned drop_threshold, float drop_scale, void* stream);
+int mi355x_stateless_tables(const void* const* emb, const void* w_pred, long long ld_pred, int w_dtype, void* tables, int E, int C,
+                            int V1, int J, int blank, void* stream);
+typedef struct mi355x_stateless_stream_state {
+  int* ctx; float* score; int* frames_done; int* sym; int* skip;
+} mi355x_stateless_stream_state;
+typedef struct mi355x_stateless_greedy_desc {
+  const void* enc_proj; const void* enc_len;                                           /* input (enc_len i64 [B])        */
+  const void* tables; const void* b_pred; const void* w_out; const void* b_out;        /* tables f32 [C, V1, J]          */
+  const int* durations;                                                                /* TDT: host array [D]            */
+  void* tokens; void* times; void* out_len; void* score;                               /* outputs                        */
+  const mi355x_stateless_stream_state* state_in; const mi355x_stateless_stream_state* state_out;   /* resumable          */
+  long long ldf, ld_out;
+  int f_dtype, w_dtype;
+  int B, T, J, V1, C, blank, max_symbols, max_out;
+  int D;
+} mi355x_stateless_greedy_desc;
+int mi355x_stateless_greedy_decode(const mi355x_stateless_greedy_desc* d, void* stream);
+
 /* ---- cache-aware streaming inference (ConformerEncoder.cache_aware_stream_step; the `update_cache` paths of
  * RelPositionMultiHeadAttention and CausalConv1D).  Caches are f32 in the reference's layouts; in bf16 compute they hold the
  * bf16-rounded operands widened to f32, so a streamed chunk reads the same operand values as the offline forward.

@@ -90,6 +90,16 @@ class TransducerBeamDesc(C.Structure):
         + [(n, i32) for n in ("f_dtype", "w_dtype", "B", "T", "J", "H", "V1", "blank", "max_symbols", "max_out", "D", "beam")])
 
 
+class StatelessGreedyDesc(C.Structure):
+    """mirror of `mi355x_stateless_greedy_desc`; state_in / state_out point to mi355x_stateless_stream_state, durations to int[D] on
+    the host"""
+    _fields_ = (
+        [(n, vp) for n in ("enc_proj", "enc_len", "tables", "b_pred", "w_out", "b_out", "durations", "tokens", "times", "out_len",
+                           "score", "state_in", "state_out")]
+        + [(n, i64) for n in ("ldf", "ld_out")]
+        + [(n, i32) for n in ("f_dtype", "w_dtype", "B", "T", "J", "V1", "C", "blank", "max_symbols", "max_out", "D")])
+
+
 class TransducerLstmLayers(C.Structure):
     """mirror of `mi355x_transducer_lstm_layers`: layers 1 .. n_upper of the prediction network (slot l = layer l + 1)"""
     _fields_ = [("n_upper", i32), ("w_ih", vp * 3), ("w_hh", vp * 3), ("b_ih", vp * 3), ("b_hh", vp * 3), ("ld_ih", i64 * 3),
@@ -226,6 +236,11 @@ SIGNATURES = {
     "mi355x_transducer_greedy_decode_layers": [C.POINTER(TransducerGreedyDesc), C.POINTER(TransducerLstmLayers), vp],
     "mi355x_transducer_beam_decode": [C.POINTER(TransducerBeamDesc), vp],
     "mi355x_transducer_beam_workspace_bytes": [i32, i32, i32, i32, i32, i32],
+    # (targets, emb / demb: host array of C device pointers, ...)
+    "mi355x_stateless_pred_fwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, u32, u32, f32, vp],
+    "mi355x_stateless_embed_bwd": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, u32, u32, f32, vp],
+    "mi355x_stateless_tables": [vp, vp, i64, i32, vp, i32, i32, i32, i32, i32, vp],
+    "mi355x_stateless_greedy_decode": [C.POINTER(StatelessGreedyDesc), vp],
     "mi355x_dwconv_config": [i32],
     "mi355x_ctc_config": [i32],
     "mi355x_ctc_align_config": [i32],

@@ -167,6 +167,8 @@ TARGET_ALIASES = {
     "nemo.collections.asr.losses.rnnt.RNNTLoss": "nemo_amd.modules.RNNTLoss",
     "nemo.collections.asr.modules.RNNTDecoder": "nemo_amd.modules.RNNTDecoder",
     "nemo.collections.asr.modules.RNNTJoint": "nemo_amd.modules.RNNTJoint",
+    "nemo.collections.asr.modules.StatelessTransducerDecoder": "nemo_amd.modules.StatelessTransducerDecoder",
+    "nemo.collections.asr.modules.rnnt.StatelessTransducerDecoder": "nemo_amd.modules.StatelessTransducerDecoder",
     "nemo.collections.asr.models.EncDecRNNTModel": "nemo_amd.models.EncDecRNNTModel",
     "nemo.collections.asr.models.EncDecRNNTBPEModel": "nemo_amd.models.EncDecRNNTModel",
     "nemo.collections.asr.models.EncDecHybridRNNTCTCModel": "nemo_amd.models.EncDecHybridRNNTCTCModel",

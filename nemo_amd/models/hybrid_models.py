@@ -275,12 +275,13 @@ class EncDecHybridRNNTCTCModel(EncDecRNNTModel):
 
 def fastconformer_hybrid_config(size: str = "large", vocab_size: int = 1024, ctc_loss_weight: float = 0.3, durations=None,
                                 streaming: bool = False, att_context_size=None, spec_augment: bool = False,
-                                **encoder_overrides) -> Dict[str, Any]:
+                                stateless_context=None, **encoder_overrides) -> Dict[str, Any]:
     """model section of examples/asr/conf/fastconformer/hybrid_transducer_ctc/fastconformer_hybrid_transducer_ctc_bpe.yaml: the
     FastConformer-Transducer model plus `aux_ctc` (ctc_loss_weight 0.3, a ConvASRDecoder on the encoder output, greedy CTC
     decoding); `durations` makes the transducer head a TDT (fastconformer_hybrid_tdt_ctc_bpe.yaml).  `streaming=True` gives the
     encoder of hybrid_cache_aware_streaming/fastconformer_hybrid_transducer_ctc_bpe_streaming.yaml: chunked_limited attention with
-    `att_context_size` ([70, 13] = 1.12 s chunks), causal convolutions (LayerNorm in the conv module) and causal down-sampling."""
+    `att_context_size` ([70, 13] = 1.12 s chunks), causal convolutions (LayerNorm in the conv module) and causal down-sampling.
+    `stateless_context`: as in fastconformer_transducer_config."""
     if att_context_size is not None and not streaming:
         encoder_overrides["att_context_size"] = list(att_context_size)
     if streaming:
@@ -289,9 +290,11 @@ def fastconformer_hybrid_config(size: str = "large", vocab_size: int = 1024, ctc
         enc.update(encoder_overrides)
         encoder_overrides = enc
     if durations:
-        cfg = fastconformer_tdt_config(size, vocab_size=vocab_size, durations=durations, spec_augment=spec_augment, **encoder_overrides)
+        cfg = fastconformer_tdt_config(size, vocab_size=vocab_size, durations=durations, spec_augment=spec_augment,
+                                       stateless_context=stateless_context, **encoder_overrides)
     else:
-        cfg = fastconformer_transducer_config(size, vocab_size=vocab_size, spec_augment=spec_augment, **encoder_overrides)
+        cfg = fastconformer_transducer_config(size, vocab_size=vocab_size, spec_augment=spec_augment,
+                                              stateless_context=stateless_context, **encoder_overrides)
     cfg["aux_ctc"] = dict(ctc_loss_weight=ctc_loss_weight, use_cer=False, ctc_reduction="mean_batch",
                           decoder=dict(_target_="nemo.collections.asr.modules.ConvASRDecoder", feat_in=None, num_classes=vocab_size,
                                        vocabulary=None),

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import copy
 import os
-from typing import Any, Dict
+from typing import Any, Dict, Optional
 
 import torch
 
@@ -350,11 +350,12 @@ def rnnt_conformer_stream_step(model, processed_signal, processed_signal_length=
 
 
 def fastconformer_transducer_config(size: str = "large", vocab_size: int = 1024, spec_augment: bool = False,
-                                    **encoder_overrides) -> Dict[str, Any]:
+                                    stateless_context: Optional[int] = None, **encoder_overrides) -> Dict[str, Any]:
     """model section of examples/asr/conf/fastconformer/fast-conformer_transducer_bpe.yaml (sizes of its table: Large = 17
     layers, d_model 512, 8 heads; x8 'dw_striding' sub-sampling with 256 channels, depthwise kernel 9; prediction network
     one 640-wide LSTM layer, joint 640, both with dropout 0.2; fused joint + loss in sub-batches of 4); tokenizer replaced by
-    an explicit vocabulary size."""
+    an explicit vocabulary size.  `stateless_context` = C (None: the LSTM above) replaces the prediction network by the stateless
+    one, `decoder._target_: StatelessTransducerDecoder` with `context_size: C` (modules/stateless.py)."""
     sizes = {"small": (176, 4, 16), "medium": (256, 4, 16), "large": (512, 8, 17)}
     d_model, n_heads, n_layers = sizes[size]
     enc = dict(feat_in=80, feat_out=-1, n_layers=n_layers, d_model=d_model, subsampling="dw_striding", subsampling_factor=8,
@@ -363,7 +364,7 @@ def fastconformer_transducer_config(size: str = "large", vocab_size: int = 1024,
                pos_emb_max_len=5000, conv_kernel_size=9, conv_norm_type="batch_norm", conv_context_size=None, dropout=0.1,
                dropout_pre_encoder=0.1, dropout_emb=0.0, dropout_att=0.1, stochastic_depth_drop_prob=0.0)
     enc.update(encoder_overrides)
-    return {
+    cfg = {
         "sample_rate": 16000, "rnnt_reduction": "mean_batch",
         "model_defaults": dict(enc_hidden=enc["d_model"], pred_hidden=640, joint_hidden=640),
         "preprocessor": dict(sample_rate=16000, normalize="per_feature", window_size=0.025, window_stride=0.01, window="hann",
@@ -379,14 +380,21 @@ def fastconformer_transducer_config(size: str = "large", vocab_size: int = 1024,
         "optim": dict(name="adamw", lr=5.0, betas=[0.9, 0.98], weight_decay=1e-3,
                       sched=dict(name="NoamAnnealing", d_model=d_model, warmup_steps=10000, warmup_ratio=None, min_lr=1e-6)),
     }
+    if stateless_context is not None:
+        cfg["decoder"] = dict(_target_="nemo.collections.asr.modules.StatelessTransducerDecoder", normalization_mode=None,
+                              random_state_sampling=False, blank_as_pad=True, vocab_size=vocab_size,
+                              context_size=int(stateless_context), prednet=dict(pred_hidden=640, dropout=0.2))
+    return cfg
 
 
 def fastconformer_tdt_config(size: str = "large", vocab_size: int = 1024, durations=(0, 1, 2, 3, 4), sigma: float = 0.02,
-                             omega: float = 0.1, spec_augment: bool = False, **encoder_overrides) -> Dict[str, Any]:
+                             omega: float = 0.1, spec_augment: bool = False, stateless_context: Optional[int] = None,
+                             **encoder_overrides) -> Dict[str, Any]:
     """model section of examples/asr/conf/fastconformer/fast-conformer_tdt_bpe.yaml (the Parakeet-TDT recipe): the
     FastConformer-Transducer model with the Token-and-Duration Transducer objective -- the joint appends one logit per duration
     (joint.num_extra_outputs), loss_name tdt with tdt_kwargs {durations, sigma, omega}, greedy TDT decoding."""
-    cfg = fastconformer_transducer_config(size, vocab_size=vocab_size, spec_augment=spec_augment, **encoder_overrides)
+    cfg = fastconformer_transducer_config(size, vocab_size=vocab_size, spec_augment=spec_augment, stateless_context=stateless_context,
+                                          **encoder_overrides)
     durations = [int(d) for d in durations]
     cfg["model_defaults"]["tdt_durations"] = list(durations)
     cfg["model_defaults"]["num_tdt_durations"] = len(durations)

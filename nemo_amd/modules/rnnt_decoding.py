@@ -47,6 +47,13 @@ whose rule include/mi355x_asr.h states; parity with the reference's `malsd_batch
 `y_sequence`, `timestamp` and `score` (the sum of log-probabilities, blanks included, merged paths added; not length-normalised)
 and, with `return_best_hypothesis: false`, `n_best`.  One-shot, one LSTM layer, beam_size <= 16; everything else is refused by
 name (`transducer_beam_from_config`).
+
+Stateless prediction network (`modules.StatelessTransducerDecoder` as `decoder_model`): the greedy decoders search with
+`ops.stateless_greedy_decode` (csrc/stateless.hip; 16 streams per workgroup as the rows of one MFMA tile) over the decoder's
+prediction tables, which are rebuilt only when the weights moved (`StatelessTransducerDecoder.search_tables`).  One-shot and
+`partial_hypotheses` (an `ops.StatelessStreamState` in `Hypothesis.dec_state`; a one-shot hypothesis carries no `dec_state`), RNN-T
+and TDT.  With a stateless decoder `fusion_models`, a `confidence_cfg` that preserves anything and `strategy: malsd_batch` are
+refused by name.
 """
 from __future__ import annotations
 
@@ -100,6 +107,13 @@ class GreedyBatchedRNNTInfer:
             raise NotImplementedError("alignments / frame confidences are not produced by the on-device search")
         if max_symbols_per_step is not None and max_symbols_per_step <= 0:
             raise ValueError(f"Expected max_symbols_per_step > 0 (or None), got {max_symbols_per_step}")  # rnnt_greedy_decoding.py:187
+        from .stateless import StatelessTransducerDecoder
+        self.stateless = isinstance(decoder_model, StatelessTransducerDecoder)
+        if self.stateless and self.fusion_models is not None:
+            raise NotImplementedError("`fusion_models` with a StatelessTransducerDecoder: the stateless search takes no fusion models")
+        if self.stateless and self.confidence_cfg is not None and self.confidence_cfg.wants_tokens:
+            raise NotImplementedError("a `confidence_cfg` that preserves confidences with a StatelessTransducerDecoder: the stateless "
+                                      "search computes none")
         self.pred_layers = int(getattr(decoder_model, "pred_rnn_layers", 1))
         if not 1 <= self.pred_layers <= 4:
             raise NotImplementedError(f"on-device greedy search: at most 4 LSTM layers in the prediction network, got pred_rnn_layers = "
@@ -114,29 +128,49 @@ class GreedyBatchedRNNTInfer:
             raise ValueError(f"`encoder_output` must be [B, D, T]; got shape {tuple(encoder_output.shape)}")
         dec, jnt = self.decoder, self.joint
         dev = encoder_output.device
-        B, D, T = encoder_output.shape
         cdt = jnt._cdt()
+        out = jnt.joint_net[-1]
+        # the GEMM operand images the training step keeps up to date (both plans before the projection, as ever)
+        Wj = jnt._plan(cdt, dev)[0] if cdt == torch.bfloat16 else None
+        Wd = dec._plan(cdt, dev)[0] if Wj is not None and not self.stateless else None
+        f = self._enc_proj(encoder_output, cdt, Wj)
+        J = jnt.joint_hidden
+        w_out, ld_out = (Wj["out.w"], Wj.pitch("out.w")) if Wj is not None else (out.weight, J)
+        if self.stateless:   # the search's arguments: the prediction tables, and W_out as the bf16 image or the fp32 master
+            return f, (dec.search_tables(jnt, dev), jnt.pred.bias, w_out, ld_out, out.bias, self._blank_index, self.max_symbols or 0)
         lstm = dec.prediction["dec_rnn"].lstm
         emb = dec.prediction["embed"].weight
-        out = jnt.joint_net[-1]
-        xe32 = encoder_output.transpose(1, 2).contiguous().view(B * T, D).float()
+        if Wj is not None:
+            w = (Wd["l0.wih"], Wd.pitch("l0.wih"), Wd["l0.whh"], Wd.pitch("l0.whh"), Wj["pred.w"], Wj.pitch("pred.w"))
+        else:
+            H = dec.pred_hidden
+            w = (lstm.weight_ih_l0, H, lstm.weight_hh_l0, H, jnt.pred.weight, H)
+        args = (emb, w[0], w[1], w[2], w[3], lstm.bias_ih_l0, lstm.bias_hh_l0, w[4], w[5], jnt.pred.bias, w_out, ld_out, out.bias,
+                self._blank_index, self.max_symbols or 0)
+        return f, args
+
+    def _enc_proj(self, encoder_output, cdt, Wj=None):
+        """encoder_output [B, D, T] -> joint.enc of it, [B, T, J] in the compute dtype (`Wj`: the joint's bf16 plan, if at hand)"""
+        jnt = self.joint
+        dev = encoder_output.device
+        B, D, T = encoder_output.shape
         J = jnt.joint_hidden
-        if cdt == torch.bfloat16:   # the GEMM operand images the training step keeps up to date
-            Wj, Wd = jnt._plan(cdt, dev)[0], dec._plan(cdt, dev)[0]
+        xe32 = encoder_output.transpose(1, 2).contiguous().view(B * T, D).float()
+        f = torch.empty(B * T, J, dtype=cdt, device=dev)
+        if cdt == torch.bfloat16:
+            Wj = Wj if Wj is not None else jnt._plan(cdt, dev)[0]
             xe = torch.empty(B * T, D, dtype=cdt, device=dev)
             ops.drop_scale_cast(xe32, xe, B * T * D, 1.0)
-            f = torch.empty(B * T, J, dtype=cdt, device=dev)
             ops.gemm(xe, Wj["enc.w"], f, B * T, J, D, D, Wj.pitch("enc.w"), J, bias=jnt.enc.bias)
-            w = (Wd["l0.wih"], Wd.pitch("l0.wih"), Wd["l0.whh"], Wd.pitch("l0.whh"), Wj["pred.w"], Wj.pitch("pred.w"), Wj["out.w"],
-                 Wj.pitch("out.w"))
         else:
-            f = torch.empty(B * T, J, dtype=torch.float32, device=dev)
             ops.gemm(xe32, jnt.enc.weight, f, B * T, J, D, D, D, J, bias=jnt.enc.bias)
-            H = dec.pred_hidden
-            w = (lstm.weight_ih_l0, H, lstm.weight_hh_l0, H, jnt.pred.weight, H, out.weight, J)
-        args = (emb, w[0], w[1], w[2], w[3], lstm.bias_ih_l0, lstm.bias_hh_l0, w[4], w[5], jnt.pred.bias, w[6], w[7], out.bias,
-                self._blank_index, self.max_symbols or 0)
-        return f.view(B, T, J), args
+        return f.view(B, T, J)
+
+    def _stateless_search(self, encoder_output, encoded_lengths, state=None, stream=False):
+        """the search with a stateless decoder -> (tokens, frame indices, lengths, score[, the next ops.StatelessStreamState])"""
+        f, args = self._project(encoder_output)
+        lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        return ops.stateless_greedy_decode(f, lens, *args, durations=getattr(self, "durations", None), state=state, stream=stream)
 
     def _upper(self, device):
         """layers 1 .. L-1 of the prediction network as the searches' `upper_layers` (None with one layer): the bf16 images and
@@ -170,6 +204,9 @@ class GreedyBatchedRNNTInfer:
         """encoder_output [B, D, T] (device) -> (tokens i32 [B, N] -1 padded, frame indices, lengths i32 [B], scores f32 [B]
         [, (h, c)][, tok_conf f32 [B, N] 0.0 padded: with_confidence, needs a `confidence_cfg`])"""
         self._no_fused_confidence(with_confidence)
+        if self.stateless:   # (no recurrent state: `with_state` appends None)
+            self._no_stateless_confidence(with_confidence)
+            return self._stateless_search(encoder_output, encoded_lengths) + ((None,) if with_state else ())
         f, args = self._project(encoder_output)
         lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
         up = self._upper(f.device)
@@ -193,6 +230,18 @@ class GreedyBatchedRNNTInfer:
         """the search with `fusion_models` -> (tokens, frame indices, lengths, score, (h, c) | the next state)"""
         return ops.transducer_greedy_decode_fused(*args, self.fusion_models, **kw)
 
+    @staticmethod
+    def _no_stateless_confidence(with_confidence):
+        if with_confidence:
+            raise NotImplementedError("`with_confidence` with a StatelessTransducerDecoder: the stateless search computes no confidences")
+
+    @property
+    def _state_cls(self):
+        """the stream state `partial_hypotheses` carry with this decoder"""
+        if self.stateless:
+            return ops.StatelessStreamState
+        return ops.RNNTFusedStreamState if self.fusion_models is not None else ops.RNNTStreamState
+
     def _no_fused_confidence(self, with_confidence):
         if with_confidence and self.fusion_models is not None:
             raise NotImplementedError("`with_confidence` together with `fusion_models`: the fused search computes no confidences")
@@ -205,6 +254,10 @@ class GreedyBatchedRNNTInfer:
         same four under their names (the state an ops.RNNTFusedStreamState) and `score`, the stream's score so far with the
         models' final terms; `with_confidence` is refused"""
         self._no_fused_confidence(with_confidence)
+        if self.stateless:
+            self._no_stateless_confidence(with_confidence)
+            tokens, times, out_len, _, nxt = self._stateless_search(encoder_output, encoded_lengths, state=state, stream=True)
+            return tokens, times, out_len, nxt
         f, args = self._project(encoder_output)
         lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
         up = self._upper(f.device)
@@ -221,9 +274,12 @@ class GreedyBatchedRNNTInfer:
         """empty hypotheses of `batch_size` streams that have seen nothing, carrying a fresh decoder state: what a stream's FIRST
         chunk is resumed from (`forward(chunk, lengths, partial_hypotheses=decoder.fresh_hypotheses(B))`)"""
         dec = self.decoder
-        device = device if device is not None else dec.prediction["embed"].weight.device
-        state_cls = ops.RNNTFusedStreamState if self.fusion_models is not None else ops.RNNTStreamState
-        st = state_cls.fresh(batch_size, dec.pred_hidden, self._blank_index, device, layers=self.pred_layers)
+        if self.stateless:
+            device = device if device is not None else next(dec.parameters()).device
+            st = ops.StatelessStreamState.fresh(batch_size, dec.context_size, self._blank_index, device)
+        else:
+            device = device if device is not None else dec.prediction["embed"].weight.device
+            st = self._state_cls.fresh(batch_size, dec.pred_hidden, self._blank_index, device, layers=self.pred_layers)
         return [Hypothesis(score=0.0, y_sequence=torch.zeros(0, dtype=torch.long), timestamp=[], dec_state=st.select(b), length=0,
                            last_token=st.select(b).last, token_confidence=[] if self._with_confidence else None)
                 for b in range(batch_size)]
@@ -235,27 +291,30 @@ class GreedyBatchedRNNTInfer:
         B = encoder_output.shape[0]
         conf = self._with_confidence
         if partial_hypotheses is None:
-            tokens, times, out_len, score, (h, c), *tc = self.decode_ids(encoder_output, encoded_lengths, with_state=True,
-                                                                         with_confidence=conf)
+            tokens, times, out_len, score, hc, *tc = self.decode_ids(encoder_output, encoded_lengths, with_state=True,
+                                                                     with_confidence=conf)
+            h, c = hc if hc is not None else (None, None)   # (a stateless decoder has no recurrent state)
             tokens, times, out_len, score = tokens.cpu(), times.cpu(), out_len.cpu(), score.cpu()   # the only D2H copies
             tc = tc[0].cpu() if conf else None
             hyps = []
             for b in range(B):
                 n = int(out_len[b])
                 hyps.append(Hypothesis(score=float(score[b]), y_sequence=tokens[b, :n].to(torch.long), timestamp=times[b, :n].tolist(),
-                                       dec_state=(h[b], c[b]) if h.dim() == 2 else (h[:, b], c[:, b]), length=int(encoded_lengths[b]),
+                                       dec_state=None if h is None else (h[b], c[b]) if h.dim() == 2 else (h[:, b], c[:, b]),
+                                       length=int(encoded_lengths[b]),
                                        token_confidence=tc[b, :n].tolist() if conf else None))
             return (hyps,)
         if len(partial_hypotheses) != B:
             raise ValueError(f"{len(partial_hypotheses)} partial hypotheses for a batch of {B}")
-        if any(h is None or not isinstance(h.dec_state, ops.RNNTStreamState) for h in partial_hypotheses):
+        if any(h is None or not isinstance(h.dec_state, ops.StatelessStreamState if self.stateless else ops.RNNTStreamState)
+               for h in partial_hypotheses):
             raise ValueError("`partial_hypotheses` must carry a stream state in `dec_state`: hypotheses this decoder returned for "
                              "earlier chunks, or `fresh_hypotheses(batch_size)` for the first chunk of a stream")
         fused = self.fusion_models is not None
         if fused and any(not isinstance(h.dec_state, ops.RNNTFusedStreamState) for h in partial_hypotheses):
             raise ValueError("`partial_hypotheses` of a decoder with `fusion_models` must carry the fused stream state: hypotheses "
                              "this decoder returned for earlier chunks, or `fresh_hypotheses(batch_size)`")
-        state = (ops.RNNTFusedStreamState if fused else ops.RNNTStreamState).stack([h.dec_state for h in partial_hypotheses])
+        state = self._state_cls.stack([h.dec_state for h in partial_hypotheses])
         if fused:   # the kernel's `score` output carries the models' final terms; the state keeps the running score
             chunk = self.decode_ids_stream(encoder_output, encoded_lengths, state)
             tokens, times, out_len, nxt, score, tc = chunk.tokens, chunk.frames, chunk.lengths, chunk.state, chunk.score, ()
@@ -333,6 +392,10 @@ class BeamBatchedRNNTInfer(GreedyBatchedRNNTInfer):
             if int(beam_size) < 1:
                 raise ValueError(f"`beam_size` must be >= 1; got {beam_size}")
             raise NotImplementedError(f"strategy 'malsd_batch' with `beam_size` = {beam_size}: the on-device beam holds at most 16")
+        from .stateless import StatelessTransducerDecoder
+        if isinstance(decoder_model, StatelessTransducerDecoder):
+            raise NotImplementedError("strategy 'malsd_batch' with a StatelessTransducerDecoder: the beam search runs an LSTM "
+                                      "prediction network")
         if int(getattr(decoder_model, "pred_rnn_layers", 1)) != 1:
             raise NotImplementedError(f"strategy 'malsd_batch' with `pred_rnn_layers` = {decoder_model.pred_rnn_layers}: the beam "
                                       "search runs one LSTM layer")

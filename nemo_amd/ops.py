@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import ConvGather, GemmDesc, PackEntry, RowMap, TransducerBeamDesc, TransducerConf, TransducerGreedyDesc, TransducerLstmLayers, check, lib
+from ._lib import ConvGather, GemmDesc, PackEntry, RowMap, StatelessGreedyDesc, TransducerBeamDesc, TransducerConf, TransducerGreedyDesc, TransducerLstmLayers, check, lib
 
 F32, BF16 = 0, 1
 EPI_STORE, EPI_SWISH_DROP, EPI_RESID, EPI_DSWISH, EPI_RELU_MASK, EPI_MUL_POS, EPI_SWISH_DROP_G, EPI_DSWISH_G = range(8)
@@ -1397,3 +1397,153 @@ def stream_dwconv(x, cache, w, bias, y, cache_next, B, Tq, d, k):
     """causal depthwise conv whose k - 1 left taps come from cache [B, d, k-1] f32; cache_next = last k - 1 frames of cat(cache, x)"""
     check(lib.mi355x_stream_dwconv(_ptr(x), _ptr(cache), _ptr(w), _ptr(bias), _ptr(y), _ptr(cache_next), dt(x), B, Tq, d, k,
                                    _stream()), "stream_dwconv")
+
+
+# ---------------------------------------------------------------- stateless prediction network (csrc/stateless.hip)
+def stateless_widths(E, C):
+    """the slice widths [e_0, .., e_{C-1}] of the stateless network's concatenation (e_0, the most recent label's, is the widest)"""
+    if not 1 <= C <= 4 or (C > 1 and E // 2 // C < 1):
+        raise ValueError(f"stateless prediction network: context_size in 1..4 with E // 2 // C >= 1; got E = {E}, C = {C}")
+    w = E // 2 // C
+    return [E - (C - 1) * w] + [w] * (C - 1)
+
+
+def _stateless_tabs(what, tabs, E):
+    C_ = len(tabs)
+    widths = stateless_widths(E, C_)
+    V1 = tabs[0].shape[0]
+    for t, e in zip(tabs, widths):
+        if t.dtype != torch.float32 or tuple(t.shape) != (V1, e) or not t.is_contiguous():
+            raise ValueError(f"{what}: tables are contiguous f32 [V1, e_i] with widths {widths}; got {tuple(t.shape)} {t.dtype}")
+    return (C.c_void_p * C_)(*(_ptr(t) for t in tabs)), C_, V1
+
+
+def stateless_pred_fwd(targets, embs, blank, out_dtype=torch.float32, drop: Dropout = NO_DROP):
+    """training forward of the stateless prediction network (mi355x_stateless_pred_fwd): targets i64 [B, U], embs = the C tables
+    f32 [V1, e_i] (i = 0: the most recent label) -> g [B, U + 1, E] in out_dtype"""
+    B, U = targets.shape
+    E = sum(t.shape[1] for t in embs)
+    arr, C_, V1 = _stateless_tabs("stateless_pred_fwd", embs, E)
+    out = torch.empty(B, U + 1, E, dtype=out_dtype, device=targets.device)
+    check(lib.mi355x_stateless_pred_fwd(_ptr(targets), arr, _ptr(out), dt(out), B, U, E, C_, V1, blank, drop.key, drop.threshold,
+                                        drop.scale, _stream()), "stateless_pred_fwd")
+    return out
+
+
+def stateless_embed_bwd(targets, dg, dembs, blank, accumulate=False, drop: Dropout = NO_DROP):
+    """embedding gradients of the stateless prediction network (mi355x_stateless_embed_bwd): dg [B, U + 1, E] (f32 or bf16,
+    contiguous) -> dembs (the C gradient tables f32 [V1, e_i]) written, or added to with `accumulate`.  No atomics: two runs give
+    the same bits."""
+    B, U = targets.shape
+    E = dg.shape[2]
+    if tuple(dg.shape) != (B, U + 1, E) or not dg.is_contiguous():
+        raise ValueError(f"stateless_embed_bwd: dg must be contiguous [B, U + 1, E]; got {tuple(dg.shape)}")
+    arr, C_, V1 = _stateless_tabs("stateless_embed_bwd", dembs, E)
+    check(lib.mi355x_stateless_embed_bwd(_ptr(targets), _ptr(dg), dt(dg), arr, int(bool(accumulate)), B, U, E, C_, V1, blank,
+                                         drop.key, drop.threshold, drop.scale, _stream()), "stateless_embed_bwd")
+
+
+def stateless_tables(embs, w_pred, ld_pred, blank, out=None):
+    """the prediction tables of the stateless search (mi355x_stateless_tables): P_i = emb_i . w_pred[:, off_i : off_i + e_i]^T for
+    w_pred [J, E] (fp32 masters or a bf16 image of row pitch ld_pred) -> f32 [C, V1, J]"""
+    E = sum(t.shape[1] for t in embs)
+    arr, C_, V1 = _stateless_tabs("stateless_tables", embs, E)
+    J = w_pred.shape[0]
+    if out is None:
+        out = torch.empty(C_, V1, J, dtype=torch.float32, device=w_pred.device)
+    check(lib.mi355x_stateless_tables(arr, _ptr(w_pred), ld_pred, dt(w_pred), _ptr(out), E, C_, V1, J, blank, _stream()),
+          "stateless_tables")
+    return out
+
+
+class _StatelessStateC(C.Structure):   # mi355x_stateless_stream_state
+    _fields_ = [(n, C.c_void_p) for n in ("ctx", "score", "frames_done", "sym", "skip")]
+
+
+class StatelessStreamState:
+    """state of a batch of streams between two chunks of the stateless greedy search (mi355x_stateless_stream_state): ctx i32 [B, C]
+    (the last C labels, column 0 the most recent), score f32 [B], frames_done / sym / skip i32 [B].  All on the device; every step
+    returns a new object."""
+    __slots__ = ("ctx", "score", "frames_done", "sym", "skip")
+    _dtypes = (torch.int32, torch.float32, torch.int32, torch.int32, torch.int32)
+
+    def __init__(self, ctx, score, frames_done, sym, skip):
+        self.ctx, self.score, self.frames_done, self.sym, self.skip = ctx, score, frames_done, sym, skip
+
+    @classmethod
+    def empty(cls, B, C_, device):
+        return cls(*(torch.empty((B, C_) if i == 0 else (B,), dtype=d, device=device) for i, d in enumerate(cls._dtypes)))
+
+    @classmethod
+    def fresh(cls, B, C_, blank, device):
+        """the state of B streams that have seen nothing (what a null state_in means to the kernel)"""
+        st = cls(*(torch.zeros((B, C_) if i == 0 else (B,), dtype=d, device=device) for i, d in enumerate(cls._dtypes)))
+        st.ctx.fill_(int(blank))
+        return st
+
+    @property
+    def last(self):
+        return self.ctx[:, 0]
+
+    def tensors(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def select(self, b):
+        """the state of stream b as a batch of one (views)"""
+        return StatelessStreamState(*(t[b:b + 1] for t in self.tensors()))
+
+    @classmethod
+    def stack(cls, states):
+        return cls(*(torch.cat(ts, dim=0).contiguous() for ts in zip(*(s.tensors() for s in states))))
+
+    def _c(self, B, C_):
+        for n, t, d in zip(self.__slots__, self.tensors(), self._dtypes):
+            shp = (B, C_) if n == "ctx" else (B,)
+            if tuple(t.shape) != shp or t.dtype != d or not t.is_contiguous():
+                raise ValueError(f"stream state `{n}`: expected contiguous {d} {shp}, got {t.dtype} {tuple(t.shape)}")
+        return _StatelessStateC(*(_ptr(t) for t in self.tensors()))
+
+
+def stateless_greedy_decode(enc_proj, enc_len, tables, b_pred, w_out, ld_out, b_out, blank, max_symbols, durations=None, max_out=None,
+                            state=None, stream=False):
+    """greedy search of a transducer with a stateless prediction network, the whole batch in one launch (mi355x_stateless_greedy_
+    decode): enc_proj [B, T, J], tables f32 [C, V1, J] (stateless_tables), w_out [V1 (+ D), J] fp32 or bf16, `durations` given: TDT.
+    -> (tokens i32 [B, max_out] -1 padded, frame indices likewise, lengths i32 [B], score f32 [B]); with `stream` (or a `state`, the
+    StatelessStreamState of the previous chunk; None: fresh streams) the next StatelessStreamState is appended, enc_len holds this
+    chunk's frames, the frame indices are global and the score is the stream's running score.  Any cut into chunks gives the bits
+    of one launch."""
+    if state is not None and not isinstance(state, StatelessStreamState):
+        raise TypeError(f"stateless_greedy_decode: `state` must be a StatelessStreamState, got {type(state).__name__}")
+    B, T, J = enc_proj.shape
+    C_, V1 = tables.shape[0], tables.shape[1]
+    if tables.dtype != torch.float32 or tables.shape[2] != J or not tables.is_contiguous():
+        raise ValueError(f"stateless_greedy_decode: tables must be contiguous f32 [C, V1, J = {J}]; got {tuple(tables.shape)}")
+    if enc_proj.stride(2) != 1 or enc_proj.stride(0) != T * enc_proj.stride(1):   # (a slice along T: the kernel walks rows b * T + t)
+        raise ValueError(f"stateless_greedy_decode: enc_proj rows must follow each other at one pitch; got strides {enc_proj.stride()}")
+    if max_out is None:
+        max_out = T * max_symbols if max_symbols > 0 else 4 * T
+    dev = enc_proj.device
+    tokens = torch.empty(B, max_out, dtype=torch.int32, device=dev)
+    times = torch.empty(B, max_out, dtype=torch.int32, device=dev)
+    out_len = torch.empty(B, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    d = StatelessGreedyDesc(
+        enc_proj=_ptr(enc_proj), f_dtype=dt(enc_proj), ldf=enc_proj.stride(1), enc_len=_ptr(enc_len), tables=_ptr(tables),
+        b_pred=_ptr(b_pred), w_out=_ptr(w_out), ld_out=ld_out, w_dtype=dt(w_out), b_out=_ptr(b_out), B=B, T=T, J=J, V1=V1, C=C_,
+        blank=blank, max_symbols=max_symbols, max_out=max_out, tokens=_ptr(tokens), times=_ptr(times), out_len=_ptr(out_len),
+        score=_ptr(score))
+    out = (tokens, times, out_len, score)
+    keep = []
+    if durations is not None:
+        d.D, dur = _tdt_durations(durations)
+        d.durations = C.addressof(dur)
+        keep.append(dur)
+    if stream or state is not None:
+        nxt = StatelessStreamState.empty(B, C_, dev)
+        for field, st in (("state_in", state), ("state_out", nxt)):
+            if st is not None:
+                keep.append(st._c(B, C_))
+                setattr(d, field, C.addressof(keep[-1]))
+        out += (nxt,)
+    check(lib.mi355x_stateless_greedy_decode(C.byref(d), _stream()), "stateless_greedy_decode")
+    return out

@@ -17,6 +17,8 @@ behind it (ConvASRDecoder + mi355x_ctc_beam_decode_stream, with --lm mi355x_ctc_
 generator at alpha 0.5), stepped from the state a stream has after eight chunks, with the n-best chased out on every step and, as
 `head_ms_no_emit`, with the state advanced only.  One row per (classes, beam size) under `heads`: median, min and max of 7 rounds.
 
+`--stateless C` (with --decoder rnnt|tdt): the head's prediction network is the stateless one with a context of C labels; with
+--head-only it is timed NEXT to the LSTM head(s), alternating rounds in one process (listed as pred_layers 0).
 `--decoder {rnnt,tdt} --head-only FRAMES [FRAMES ...] [--lm ORDER] [--boost P]`: no encoder; the transducer head alone on random
 encoder output of FRAMES frames per stream (14 = the streaming step, 250 = 20 s offline), the plain search against the search with
 shallow fusion (ops.transducer_greedy_decode_fused: --lm, the n-gram model of the tests' generator at alpha 0.5; --boost, a tree
@@ -61,18 +63,23 @@ def build(n_layers):
     return enc
 
 
-def build_head(kind, d_model=512, fusion_models=None, scale=1.0, pred_layers=1):
+def build_head(kind, d_model=512, fusion_models=None, scale=1.0, pred_layers=1, stateless=0):
     """-> step(encoded [B, D, T], encoded_len) for the head `kind`, weights random (the step's cost does not depend on them much:
     the transducer search emits what a random joint emits, bounded by max_symbols = 10 per frame)"""
-    from nemo_amd.modules import ConvASRDecoder, GreedyBatchedRNNTInfer, GreedyBatchedTDTInfer, RNNTDecoder, RNNTJoint
+    from nemo_amd.modules import (ConvASRDecoder, GreedyBatchedRNNTInfer, GreedyBatchedTDTInfer, RNNTDecoder, RNNTJoint,
+                                  StatelessTransducerDecoder)
     torch.manual_seed(1)
     V = 1024
     if kind == "ctc":
         dec = ConvASRDecoder(feat_in=d_model, num_classes=V, compute_dtype=torch.bfloat16).to(dev).eval()
         return lambda enc, n, state=None: (dec(encoder_output=enc).argmax(-1), None)
     durations = [0, 1, 2, 3, 4]
-    pred = RNNTDecoder(prednet={"pred_hidden": 640, "pred_rnn_layers": pred_layers, "dropout": 0.0}, vocab_size=V,
-                       compute_dtype=torch.bfloat16)
+    if stateless:   # the stateless prediction network with a context of `stateless` labels
+        pred = StatelessTransducerDecoder(prednet={"pred_hidden": 640, "dropout": 0.0}, vocab_size=V, context_size=stateless,
+                                          compute_dtype=torch.bfloat16)
+    else:
+        pred = RNNTDecoder(prednet={"pred_hidden": 640, "pred_rnn_layers": pred_layers, "dropout": 0.0}, vocab_size=V,
+                           compute_dtype=torch.bfloat16)
     joint = RNNTJoint(jointnet={"encoder_hidden": d_model, "pred_hidden": 640, "joint_hidden": 640, "activation": "relu", "dropout": 0.0},
                       num_classes=V, num_extra_outputs=len(durations) if kind == "tdt" else 0, compute_dtype=torch.bfloat16)
     with torch.no_grad():
@@ -89,9 +96,11 @@ def build_head(kind, d_model=512, fusion_models=None, scale=1.0, pred_layers=1):
     return step
 
 
-def layers_head_setting(kind, layer_counts, B, frames, steps, warmup, n_rounds=7, d_model=512):
-    """the transducer head alone on `frames` frames per stream, once per count of prediction-network layers, alternating rounds"""
+def layers_head_setting(kind, layer_counts, B, frames, steps, warmup, n_rounds=7, d_model=512, stateless=0):
+    """the transducer head alone on `frames` frames per stream, once per count of prediction-network layers, alternating rounds;
+    `stateless` = C: also the stateless prediction network with a context of C labels (listed as pred_layers 0), in the same rounds"""
     import statistics
+    layer_counts = list(layer_counts) + ([0] if stateless else [])
     g = torch.Generator(device=dev).manual_seed(2)
     enc_out = torch.randn(B, d_model, frames, device=dev, generator=g)
     enc_len = torch.full((B,), frames, dtype=torch.int64, device=dev)
@@ -99,7 +108,7 @@ def layers_head_setting(kind, layer_counts, B, frames, steps, warmup, n_rounds=7
     with torch.no_grad():
         fns, labels = {}, {}
         for L in layer_counts:
-            head = build_head(kind, d_model, scale=4.0, pred_layers=L)
+            head = build_head(kind, d_model, scale=4.0, pred_layers=L or 1, stateless=0 if L else stateless)
             (_, out_len), state = head(enc_out, enc_len, lengths=True)
             labels[L] = int(out_len.sum())
             fns[L] = lambda head=head, state=state: head(enc_out, enc_len, state)
@@ -315,8 +324,11 @@ def main():
     ap.add_argument("--boost", type=int, default=0, metavar="P")
     ap.add_argument("--head-only", type=int, nargs="+", default=None, metavar="FRAMES")
     ap.add_argument("--pred-layers", type=int, nargs="+", default=[1], metavar="N", choices=[1, 2, 3, 4])
+    ap.add_argument("--stateless", type=int, default=0, metavar="C", choices=[0, 1, 2, 3, 4])
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    if args.stateless and (args.decoder not in ("rnnt", "tdt") or args.lm or args.boost):
+        ap.error("--stateless C: the stateless prediction network of --decoder rnnt|tdt (no --lm / --boost)")
     if args.head_only:
         if args.decoder not in ("rnnt", "tdt"):
             ap.error("--head-only times the transducer heads: --decoder rnnt|tdt (with --lm and / or --boost: with and without "
@@ -328,7 +340,8 @@ def main():
                     rows.append(fused_head_setting(args.decoder, args.lm, args.boost, B, frames, args.steps, args.warmup,
                                                    pred_layers=args.pred_layers[0]))
                 else:
-                    rows.append(layers_head_setting(args.decoder, args.pred_layers, B, frames, args.steps, args.warmup))
+                    rows.append(layers_head_setting(args.decoder, args.pred_layers, B, frames, args.steps, args.warmup,
+                                                    stateless=args.stateless))
                 print(json.dumps(rows[-1]), flush=True)
         if args.json:
             with open(args.json, "w") as f:
@@ -339,7 +352,7 @@ def main():
         head = [(dict(classes=C, beam_size=W, lm_order=args.lm), build_beam_head(C, W, args.lm)) for C in args.classes
                 for W in args.beam_size]
     else:
-        head = build_head(args.decoder, pred_layers=args.pred_layers[0]) if args.decoder != "none" else None
+        head = build_head(args.decoder, pred_layers=args.pred_layers[0], stateless=args.stateless) if args.decoder != "none" else None
     rows = []
     for B in args.batch:
         r = one_setting(enc, B, args.steps, args.warmup, head, args.decoder)

@@ -940,6 +940,48 @@ int mi355x_tdt_loss_ex(const void* acts, long long ld_acts, const void* labels, 
                        int T, int U1, int V1, int D, const int* durations, int blank, float sigma, float grad_scale, void* costs,
                        void* grads, int grads_dtype, long long ld_grads, void* workspace, long long workspace_elems, void* stream);
 
+/* ---- forced alignment on the transducer heads: the Viterbi counterpart of the two loss lattices above, its backtrace in the same
+ * launch.  This paragraph is the rule; parity with an outside tool's numbers is not claimed.
+ * Per cell (t, u) of an utterance's own lattice, 0 <= t < T_b, 0 <= u <= U_b: lpb = log-prob of the blank, lpl = log-prob of label
+ * y_u (unused at u = U_b), TDT only: ld[i] = log-prob of duration d_i; each is logit - lse of its own soft-max (labels over [0, V1),
+ * durations over [V1, V1 + D)), lse(x) = max x + log(sum exp(x - max x)).  No sigma and no FastEmit term.
+ *   RNN-T  v[0][0] = 0;  v[t][u] = max(v[t-1][u] + lpb[t-1][u], v[t][u-1] + lpl[t][u-1]);  score = v[T_b-1][U_b] + lpb[T_b-1][U_b].
+ *          Ties go to the blank arc.
+ *   TDT    (the duration set as mi355x_tdt_loss_ex validates it)  a blank arc of duration d_i >= 1 goes (t-d_i, u) -> (t, u) with
+ *          weight lpb + ld[i], a label arc of duration d_i >= 0 goes (t-d_i, u-1) -> (t, u) with weight lpl + ld[i], both taken at the
+ *          source cell; every arc but the last lands inside the lattice (t < T_b).  v[t][u] is the maximum over the arcs that
+ *          arrive; the path ends with a blank arc that lands exactly on (T_b, U_b) -- the loss's rule -- and score is the maximum
+ *          over those.  Ties go to the first maximum in the order: blank arcs by ascending duration index, then label arcs by
+ *          ascending duration index.
+ * Every step is one float32 add, written v + (lp + ld) (RNN-T: v + lp), and one comparison, so a float32 restatement reproduces
+ * score and path bit for bit whatever order the cells are visited in.  An arc whose weight is -inf or NaN is never taken.  T_b = 0
+ * and U_b = 0: score 0.  No path (T_b = 0 < U_b, a duration set that cannot land on T_b, -inf everywhere): score = -inf and every
+ * output of that utterance is -1 -- flagged, not raised, as in mi355x_ctc_align.  T_b = min(T, act_lens[b]), U_b = min(U1 - 1,
+ * label_lens[b]), negative lengths count as 0.
+ *   mi355x_transducer_align_rows   acts f32 joint LOGITS [B, T, U1, V1 (+ D)] with row pitch ld_acts >= V1 + D, as the joint's
+ *       forward stores them for the loss; labels i64 [B, U1-1] (may be NULL for U1 = 1); act_lens, label_lens i64 [B] -> rows f32
+ *       [B, T, U1, R], R = 2 + D floats per cell: lpb, lpl, ld[0..D); padded cells (t >= T_b or u > U_b) are written as -inf, as
+ *       is lpl at u = U_b.  D = 0 (RNN-T) or 2..8.  Called once per sub-batch of the joint -- B, the three per-utterance inputs
+ *       and `rows` are then the sub-batch's -- so the logits of the whole batch never exist at once.
+ *   mi355x_transducer_align        rows as above for the whole batch; durations host array as for mi355x_tdt_loss_ex, (NULL, D = 0)
+ *       = RNN-T ->
+ *         tok_frame i32 [B, U1-1]  the source frame of label u's arc: the frame the greedy search's `times` reports
+ *         tok_dur   i32 [B, U1-1]  that arc's duration (RNN-T: 0)
+ *         score     f32 [B]
+ *       tok_frame and tok_dur are -1 for u >= U_b.  workspace: the backpointers, one byte per cell (0..7 = blank arc of duration
+ *       index i, 8..15 = label arc of duration index i - 8, 0xff = none), diagonal-major [b][t + u][u] with a pitch of
+ *       64 * ceil-to-power-of-two(U1 / 64) bytes; 16-byte aligned, at least mi355x_transducer_align_workspace_bytes(B, T, U1)
+ *       bytes (-1 for sizes the entry refuses).
+ * MI_ERR_ARG before any launch for null pointers, sizes < 1, U1 > 1024, V1 < 2, blank outside [0, V1), ld_acts < V1 + D, D outside
+ * {0, 2..8}, an invalid duration set or D != 0 without durations (or durations with D = 0), a short or misaligned workspace, a largest
+ * duration above 4 together with U1 > 256. */
+long long mi355x_transducer_align_workspace_bytes(int B, int T, int U1);
+int mi355x_transducer_align_rows(const void* acts, long long ld_acts, const void* labels, const void* act_lens,
+                                 const void* label_lens, int B, int T, int U1, int V1, int D, int blank, void* rows, void* stream);
+int mi355x_transducer_align(const void* rows, const void* act_lens, const void* label_lens, const int* durations, int D, int B,
+                            int T, int U1, void* workspace, long long workspace_bytes, void* tok_frame, void* tok_dur, void* score,
+                            void* stream);
+
 /* ---- greedy TDT decoding on the device (the descriptor's D and durations given): the RNN-T search's fields plus the duration set;
  * w_out [V1+D, J], b_out [V1+D].  Per utterance: t = 0; while t < enc_len[b]: k = argmax of the V1 label logits, d = durations[argmax
  * of the D duration logits] (first maximum wins for both); blank -> t += max(d, 1); else emit (k, t), commit the state, t += d, where

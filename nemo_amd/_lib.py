@@ -263,6 +263,11 @@ SIGNATURES = {
     "mi355x_rnnt_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
     "mi355x_tdt_workspace_elems": [i32, i32, i32, i32, vp],
     "mi355x_tdt_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
+    # (acts, ld_acts, labels, act_lens, label_lens, B, T, U1, V1, D, blank, rows, stream)
+    "mi355x_transducer_align_rows": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp],
+    # (rows, act_lens, label_lens, durations: int[D] on the host, D, B, T, U1, workspace, workspace_bytes, tok_frame, tok_dur, score, stream)
+    "mi355x_transducer_align": [vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp],
+    "mi355x_transducer_align_workspace_bytes": [i32, i32, i32],
     "mi355x_stream_cache_assemble": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi355x_stream_attn": [vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "mi355x_stream_dwconv": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
@@ -289,6 +294,7 @@ def _load():
     lib.mi355x_ctc_beam_workspace_elems.restype = i64
     lib.mi355x_ctc_beam_commit_workspace_elems.restype = i64
     lib.mi355x_transducer_beam_workspace_bytes.restype = i64
+    lib.mi355x_transducer_align_workspace_bytes.restype = i64
     lib.mi355x_asr_version.argtypes = []
     lib.mi355x_tape_destroy.restype = None
     lib.mi355x_mailbox_destroy.restype = None

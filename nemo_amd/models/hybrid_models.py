@@ -183,8 +183,14 @@ class EncDecHybridRNNTCTCModel(EncDecRNNTModel):
         return ctc_transcribe_timestamps(self, audio, batch_size, channel_selector)
 
     @torch.no_grad()
-    def align(self, audio, texts, batch_size: int = 4, channel_selector=None):
-        """forced alignment over the auxiliary CTC head, whichever head `cur_decoder` names (ctc_models.ctc_align_audio)"""
+    def align(self, audio, texts, batch_size: int = 4, channel_selector=None, decoder_type: str = "ctc"):
+        """forced alignment, whichever head `cur_decoder` names: over the auxiliary CTC head (decoder_type "ctc", the default:
+        ctc_models.ctc_align_audio) or over the transducer head (decoder_type "rnnt": rnnt_models.transducer_align_audio)"""
+        if decoder_type not in ("ctc", "rnnt"):
+            raise ValueError(f"decoder_type={decoder_type} is not supported. Supported values: [ctc,rnnt]")
+        if decoder_type == "rnnt":
+            from .rnnt_models import transducer_align_audio
+            return transducer_align_audio(self, audio, texts, batch_size, channel_selector)
         return ctc_align_audio(self, audio, texts, batch_size, channel_selector)
 
     # ------------------------------------------------------------------ both heads in one step (hybrid_rnnt_ctc_models.py:420-520)

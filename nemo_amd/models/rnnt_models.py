@@ -15,7 +15,8 @@ from typing import Any, Dict, Optional
 import torch
 
 from ..modules import RNNTLoss, TDTLoss
-from .ctc_models import EncDecCTCModel, _build as _build_ctc
+from .ctc_models import (EncDecCTCModel, _as_list, _audio_batch, _build as _build_ctc, _inference_setup, _with_seconds,
+                         frame_stride_s)
 
 _DEFAULT_TARGETS = {"decoder": "nemo.collections.asr.modules.RNNTDecoder", "joint": "nemo.collections.asr.modules.RNNTJoint"}
 
@@ -272,6 +273,11 @@ class EncDecRNNTModel(EncDecCTCModel):
         """the decoding object behind `transcribe` / `predict_step` (the hybrid model answers with the head `cur_decoder` names)"""
         return self.decoding
 
+    @torch.no_grad()
+    def align(self, audio, texts, batch_size: int = 4, channel_selector=None):
+        """forced alignment of one transcript per input over the transducer head: see `transducer_align_audio`"""
+        return transducer_align_audio(self, audio, texts, batch_size, channel_selector)
+
     def conformer_stream_step(self, *args, **kwargs):
         """Refused on this class.  The greedy transducer decoders do take `partial_hypotheses` now, and the streaming step exists:
         `rnnt_conformer_stream_step(model, ...)` below, which EncDecHybridRNNTCTCModel.conformer_stream_step runs for its
@@ -317,6 +323,54 @@ class EncDecRNNTModel(EncDecCTCModel):
             feat.dither, feat.pad_to = dither, pad_to
             self.train(was_training)
         return out
+
+
+def transducer_align_audio(model, audio, texts, batch_size=4, channel_selector=None):
+    """`align` over a transducer head (RNN-T or TDT): one transcript per input -> ids (`model._text_to_ids`), Viterbi forced
+    alignment over the lattice of the head's own loss on the device (`modules.TransducerAligner`; only [B, U] integers and the
+    scores come back).  -> what `ctc_align_audio` returns, one dict per input, in input order: {'score', 'feasible', 'text',
+    'tokens': [{char, start_offset, end_offset, start, end}], 'words': [{word, ...}]}.  A token starts on the frame it is emitted
+    on; its exclusive end is the next token's start (the utterance's length for the last one), and at least start + 1.  TDT: every
+    token also carries its `duration` and the dict `token_durations`.  A pair that cannot be aligned has feasible = False, score
+    -inf and no segments."""
+    from ..modules import TransducerAligner, ctc_offsets
+    decoding = model.decoding
+    if decoding is None:
+        raise RuntimeError("align() needs a vocabulary (`labels` or a tokenizer)")
+    audio = _as_list(audio)
+    texts = [texts] if isinstance(texts, str) else list(texts)
+    if len(texts) != len(audio):
+        raise ValueError(f"align() takes one transcript per input: {len(audio)} inputs, {len(texts)} transcripts")
+    tdt = isinstance(model.loss, TDTLoss)
+    aligner = TransducerAligner(model.decoder, model.joint, durations=model.loss.durations if tdt else None)
+    vocab = decoding.vocabulary if decoding.vocabulary is not None else list(decoding.tokenizer.vocab)
+    pieces = any(v.startswith("\u2581") for v in vocab)
+    stride, out = frame_stride_s(model), []
+    with _inference_setup(model):
+        for i in range(0, len(audio), batch_size):
+            sig, lens = _audio_batch(model, audio[i:i + batch_size], channel_selector)
+            ids = [list(model._text_to_ids(t)) for t in texts[i:i + batch_size]]
+            tl = torch.tensor([len(x) for x in ids], dtype=torch.int64)
+            tg = torch.zeros(len(ids), max(1, int(tl.max())), dtype=torch.int64)
+            for r, x in enumerate(ids):
+                tg[r, : len(x)] = torch.tensor(x, dtype=torch.int64)
+            encoded, enc_len = model.forward(input_signal=sig, input_signal_length=lens)
+            frame, dur, score = (t.cpu() for t in aligner(encoded, enc_len, tg.to(sig.device), tl.to(sig.device)))
+            for r, x in enumerate(ids):
+                feasible = bool(torch.isfinite(score[r]))
+                n = len(x) if feasible else 0
+                start = frame[r, :n].tolist()
+                nxt = start[1:] + [int(enc_len[r])]
+                last = [max(e, s + 1) - 1 for s, e in zip(start, nxt)]   # (ctc_offsets takes the last frame, inclusive)
+                char, word = ctc_offsets(decoding.ids_to_tokens(x[:n]), start, last, word_pieces=pieces)
+                res = {"score": float(score[r]), "feasible": feasible, "text": texts[i + r],
+                       "tokens": _with_seconds(char, stride), "words": _with_seconds(word, stride)}
+                if tdt:
+                    res["token_durations"] = dur[r, :n].tolist()
+                    for tok, d in zip(res["tokens"], res["token_durations"]):
+                        tok["duration"] = d
+                out.append(res)
+    return out
 
 
 @torch.no_grad()

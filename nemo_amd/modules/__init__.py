@@ -15,5 +15,6 @@ from .stateless import StatelessTransducerDecoder  # noqa: F401
 from .rnnt_decoding import GreedyBatchedRNNTInfer, GreedyBatchedTDTInfer, RNNTDecoding, RNNTWER, Hypothesis  # noqa: F401
 from .rnnt_decoding import transducer_fusion_from_config  # noqa: F401
 from .rnnt_decoding import BeamBatchedRNNTInfer, BeamBatchedTDTInfer, transducer_beam_from_config  # noqa: F401
+from .transducer_align import TransducerAligner  # noqa: F401
 from .confidence import (ConfidenceConfig, ConfidenceMethodConfig, aggregate, confidence_from,  # noqa: F401
                          word_confidence)

@@ -1148,6 +1148,39 @@ def transducer_beam_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_i
     return tokens, times, out_len, score, n_hyp
 
 
+def transducer_align_rows(acts, ld_acts, labels, act_lens, label_lens, B, T, U1, V1, D, blank, rows):
+    """the lattice inputs of `transducer_align` for one sub-batch of the joint (mi355x_transducer_align_rows): acts f32 logits in
+    rows of pitch ld_acts (V1 label logits, then D duration logits; D = 0: RNN-T), labels i64 [B, U1-1] -> fills rows f32
+    [B, T, U1, 2 + D] = (lpb, lpl, ld[0..D)) per cell, -inf in padded cells"""
+    if rows.dtype != torch.float32 or not rows.is_contiguous() or rows.numel() != B * T * U1 * (2 + D):
+        raise ValueError(f"transducer_align_rows: `rows` must be contiguous f32 [B, T, U1, {2 + D}]")
+    check(lib.mi355x_transducer_align_rows(_ptr(acts), ld_acts, _ptr(labels), _ptr(act_lens), _ptr(label_lens), B, T, U1, V1, D,
+                                           blank, _ptr(rows), _stream()), "transducer_align_rows")
+    return rows
+
+
+def transducer_align(rows, act_lens, label_lens, durations=None):
+    """Viterbi forced alignment over a transducer lattice (mi355x_transducer_align; include/mi355x_asr.h states the rule): rows f32
+    [B, T, U1, 2 + D] from `transducer_align_rows`, act_lens / label_lens i64 [B], `durations` given: TDT -> (tok_frame i32
+    [B, U1-1]: the frame each label is emitted on, tok_dur i32 [B, U1-1]: its duration (RNN-T: 0), score f32 [B]); -1 padded; an
+    utterance without a path has score -inf and -1 everywhere"""
+    B, T, U1, R = rows.shape
+    D, dur = _tdt_durations(durations) if durations is not None else (0, None)
+    if R != 2 + D or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError(f"transducer_align: `rows` must be contiguous f32 [B, T, U1, {2 + D}], got {tuple(rows.shape)}")
+    nbytes = lib.mi355x_transducer_align_workspace_bytes(B, T, U1)
+    if nbytes < 0:
+        raise ValueError(f"transducer_align: positive sizes and U1 <= 1024; got B, T, U1 = {(B, T, U1)}")
+    dev = rows.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    Uk = max(U1 - 1, 1)   # (a batch of empty transcripts: the kernel wants a column to point at)
+    tok_frame, tok_dur = (torch.empty(B * Uk, dtype=torch.int32, device=dev) for _ in range(2))
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    check(lib.mi355x_transducer_align(_ptr(rows), _ptr(act_lens), _ptr(label_lens), dur, D, B, T, U1, _ptr(ws), nbytes,
+                                      _ptr(tok_frame), _ptr(tok_dur), _ptr(score), _stream()), "transducer_align")
+    return tok_frame[:B * (U1 - 1)].view(B, U1 - 1), tok_dur[:B * (U1 - 1)].view(B, U1 - 1), score
+
+
 def tdt_loss_pitched(acts, ld_acts, B, T, U1, V1, durations, labels, act_lens, label_lens, blank, grads=None, ld_grads=0,
                      sigma=0.0, grad_scale=1.0):
     """Token-and-Duration Transducer loss (mi355x_tdt_loss_ex): acts f32 logits [.., V1 + D] in rows of pitch ld_acts (V1 label

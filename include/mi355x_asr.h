@@ -940,6 +940,41 @@ int mi355x_tdt_loss_ex(const void* acts, long long ld_acts, const void* labels, 
                        int T, int U1, int V1, int D, const int* durations, int blank, float sigma, float grad_scale, void* costs,
                        void* grads, int grads_dtype, long long ld_grads, void* workspace, long long workspace_elems, void* stream);
 
+/* ---- multi-blank transducer (Xu et al. 2022; the reference's `loss_name: multiblank_rnnt`, MultiblankRNNTLossNumba and
+ * GreedyBatchedMultiblankRNNTInfer): loss and greedy search.  THE RULE below was written from memory of the reference, which could
+ * not be re-read; it is the contract, and parity with the reference's numbers is not claimed.
+ * big_blank_durations (host array) = d_0 < d_1 < ... < d_{nb-1}, integers, 2 <= d_i <= 8, 1 <= nb <= 7.  The joint has N = V + 1 + nb
+ * outputs: labels 0 .. V-1, the standard blank LAST (blank = N - 1), big blank i = output blank - 1 - i.  The prediction network is
+ * the RNN-T one (V + 1 embedding rows; a label never is a blank).
+ * Loss: acts f32 [B,T,U1,N] = joint LOGITS with row pitch ld_acts >= N.  lp(v) = z_v - lse(z[0:N]): ONE softmax over all N logits;
+ * sigma >= 0 is subtracted from every arc.  Arcs out of cell (t, u): label y_{u+1} to (t, u+1); the standard blank to (t+1, u); big
+ * blank i to (t + d_i, u).  A path ends with a blank-like arc that lands exactly on (T_b, U_b).  alpha(0,0) = 0; ll = lse over the
+ * blank-like arcs into (T_b, U_b); costs f32 [B] = -ll.  grads (NULL = loss only) = grad_scale * d cost / d acts, per cell
+ * softmax_v * occ - (the sum of the posteriors of the cell's arcs that carry output v), posterior = exp(alpha(src) + w + beta(dst)
+ * - ll), occ = the sum over all arcs of the cell; in grads_dtype with row pitch ld_grads >= N (bf16: ld_grads % 8 == 0, columns
+ * [N, ld_grads) zero-filled); cells beyond an utterance's (T_b, U_b+1) are zeros.  No FastEmit term and no clamp.  workspace f32,
+ * at least mi355x_multiblank_workspace_elems(B,T,U1,nb) elements.  mi355x_multiblank_loss: the dense form (pitches N, f32 grads).
+ * MI_ERR_ARG before any launch: what mi355x_tdt_loss_ex refuses (null pointers, sizes, U1 > 1024, short pitches, a short
+ * workspace), nb outside 1..7, a duration outside 2..8 or not ascending, blank != N - 1, N < nb + 2, sigma < 0 or NaN.
+ * Greedy search (mi355x_transducer_greedy_decode_multiblank: the descriptor and the set): the RNN-T search with an output layer of V1 + nb rows, w_out [V1 + nb, J],
+ * b_out [V1 + nb], V1 = V + 1 the rows of `emb`, blank == V1 - 1 (the zero embedding row), so the standard blank is row V1 - 1 + nb
+ * and big blank i row V1 - 2 + nb - i.  Per step k = the first arg-max over ALL V1 + nb logits (a row with no number: the blank);
+ * k the blank: t += 1, sym = 0; k big blank i: t += d_i, sym = 0; otherwise emit (k, t), score += lp(k) (the softmax over all
+ * logits), sym += 1, and sym == max_symbols (> 0) moves t on by one frame with sym = 0.  max_symbols <= 0: bounded by max_out.
+ * Resumable: frames jumped past the end of the chunk go out in `skip` and are taken off the next chunk(s) as for TDT; zero_run is
+ * written as 0; skip and zero_run are required in a state.  Any cut into chunks gives the bits of one launch.  Refused with
+ * MI_ERR_ARG before any launch: a descriptor with a TDT duration set, a confidence measure or fusion models; an invalid set;
+ * blank != V1 - 1 (upper LSTM layers have no way in: the entry takes none).  The four multi-blank kernels ([fp32, bf16] x [one-shot, resumable]) are
+ * instantiations of their own; every other call launches the code it always has. */
+int mi355x_multiblank_workspace_elems(int B, int T, int U1, int nb, long long* elems);
+int mi355x_multiblank_loss_ex(const void* acts, long long ld_acts, const void* labels, const void* act_lens, const void* label_lens,
+                              int B, int T, int U1, int N, int nb, const int* big_blank_durations, int blank, float sigma,
+                              float grad_scale, void* costs, void* grads, int grads_dtype, long long ld_grads, void* workspace,
+                              long long workspace_elems, void* stream);
+int mi355x_multiblank_loss(const void* acts, const void* labels, const void* act_lens, const void* label_lens, int B, int T, int U1,
+                           int N, int nb, const int* big_blank_durations, int blank, float sigma, float grad_scale, void* costs,
+                           void* grads, void* workspace, long long workspace_elems, void* stream);
+
 /* ---- forced alignment on the transducer heads: the Viterbi counterpart of the two loss lattices above, its backtrace in the same
  * launch.  This paragraph is the rule; parity with an outside tool's numbers is not claimed.
  * Per cell (t, u) of an utterance's own lattice, 0 <= t < T_b, 0 <= u <= U_b: lpb = log-prob of the blank, lpl = log-prob of label
@@ -1081,6 +1116,10 @@ typedef struct mi355x_transducer_greedy_desc {
   int D, n_models;
 } mi355x_transducer_greedy_desc;
 int mi355x_transducer_greedy_decode(const mi355x_transducer_greedy_desc* d, void* stream);
+/* the multi-blank search (its paragraph is above, with the loss): the descriptor, whose layout stays what it was, and the big-blank
+ * set beside it (host array), as the upper LSTM layers travel beside it in the entry below */
+int mi355x_transducer_greedy_decode_multiblank(const mi355x_transducer_greedy_desc* d, int n_big_blanks, const int* big_blank_durations,
+                                               void* stream);
 
 /* ---- the greedy searches for a prediction network of L = 1 + n_upper LSTM layers, L in 1..4: every form the descriptor above
  * states (RNN-T and TDT, one-shot and resumable, with confidences, with one or two fusion models, fp32 masters and bf16 images).

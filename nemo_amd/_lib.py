@@ -263,6 +263,10 @@ SIGNATURES = {
     "mi355x_rnnt_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
     "mi355x_tdt_workspace_elems": [i32, i32, i32, i32, vp],
     "mi355x_tdt_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
+    "mi355x_multiblank_workspace_elems": [i32, i32, i32, i32, vp],
+    "mi355x_transducer_greedy_decode_multiblank": [C.POINTER(TransducerGreedyDesc), i32, vp, vp],
+    "mi355x_multiblank_loss_ex": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp, i32, i64, vp, i64, vp],
+    "mi355x_multiblank_loss": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp, vp, i64, vp],
     # (acts, ld_acts, labels, act_lens, label_lens, B, T, U1, V1, D, blank, rows, stream)
     "mi355x_transducer_align_rows": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp],
     # (rows, act_lens, label_lens, durations: int[D] on the host, D, B, T, U1, workspace, workspace_bytes, tok_frame, tok_dur, score, stream)

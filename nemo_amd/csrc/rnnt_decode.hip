@@ -42,6 +42,7 @@
 #include "common.h"
 #include "ctc_beam_fusion.h"
 #include "mi355x_asr.h"
+#include "multiblank.h"
 #include "tdt.h"
 
 #define RD_THREADS 512
@@ -161,8 +162,17 @@ template <bool CONF, int NM> struct RnntDecArg<CONF, NM, true> { typedef RnntDec
 // DEEP = a prediction network of L = 1 + p.up.n layers (the rule is at the top of this file; STREAM = true only, for the reason
 // NM > 0 gives).  LDS then holds the block (h, c, hn, cn) of every layer, layer 0's where it always was and layer l's 4 * l * H floats
 // behind it, and the state arrays are [L, B, H].  DEEP = false: none of it exists and the instantiations are the kernels they were.
-template <typename WT, bool TDT, bool STREAM, bool CONF, int NM = 0, bool DEEP = false>
+//
+// MODE = the objective whose search this is: RD_RNNT, RD_TDT (a duration set in p.dur) or RD_MB, the multi-blank transducer (p.dur
+// holds the nb big-blank durations, dur.D = nb).  Multi-blank: the output layer has V1 + nb rows -- labels 0 .. V1-2, row V1-1+nb
+// the standard blank, row V1-2+nb-i big blank i -- ONE arg-max and one log-sum-exp over all of them; a blank moves on by one
+// frame, big blank i by d_i frames, a label is the RNN-T search's.  Plain only (no CONF, no models, one layer).  Everything that
+// names it sits behind `if constexpr (MB)`: the other instantiations are the kernels they were.
+enum { RD_RNNT = 0, RD_TDT = 1, RD_MB = 2 };
+template <typename WT, int MODE, bool STREAM, bool CONF, int NM = 0, bool DEEP = false>
 __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDecArg<CONF, NM, DEEP>::t p) {
+  constexpr bool TDT = MODE == RD_TDT, MB = MODE == RD_MB;
+  static_assert(!MB || (!CONF && NM == 0 && !DEEP), "the multi-blank search is the plain one");
   static_assert(NM == 0 || (STREAM && !CONF && NM <= 2), "the fused search is the resumable one, without confidences");
   static_assert(!DEEP || STREAM, "the deep search is the resumable one (a one-shot call: a fresh stream, no state to write)");
   extern __shared__ __attribute__((aligned(16))) float rd_smem[];
@@ -204,6 +214,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
   if (resume) {
     last = p.sin.last[b]; score = p.sin.score[b]; frames_done = p.sin.frames_done[b];
     if (TDT) { skip = max(p.sin.skip[b], 0); same = p.sin.zero_run[b]; }
+    if constexpr (MB) skip = max(p.sin.skip[b], 0);   // (zero_run stays 0)
     if (last < 0 || last >= V1) last = p.blank;   // (a label outside the embedding table is never read)
     if constexpr (DEEP) {
       for (int l = 0; l < L; ++l)
@@ -274,11 +285,13 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
       a[j] = fmaxf(fv + gp[j], 0.f);
     }
     __syncthreads();
-    rd_gemv<WT, false>((const WT*)p.w_out, p.ld_out, a, TDT ? V1 + p.dur.D : V1, J, p.b_out, lg);
+    rd_gemv<WT, false>((const WT*)p.w_out, p.ld_out, a, (TDT || MB) ? V1 + p.dur.D : V1, J, p.b_out, lg);
     __syncthreads();
     // arg-max (lowest index among equal maxima, like torch.max) and log-sum-exp (score = sum of the emitted labels' log-probs)
+    int NV = V1;   // the logits the arg-max and the softmax run over (multi-blank: all V1 + nb)
+    if constexpr (MB) NV = V1 + p.dur.D;
     float bv = -INFINITY; int bi = 0x7fffffff;
-    for (int v = tid; v < V1; v += RD_THREADS) { const float q = lg[v]; if (q > bv) { bv = q; bi = v; } }
+    for (int v = tid; v < NV; v += RD_THREADS) { const float q = lg[v]; if (q > bv) { bv = q; bi = v; } }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
@@ -293,7 +306,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
     float sa = 0.f, sb = 0.f;
     bool sums = false;   // (uniform)
     if constexpr (CONF) sums = p.conf.method != MI355X_CONF_MAX_PROB;
-    for (int v = tid; v < V1; v += RD_THREADS) {
+    for (int v = tid; v < NV; v += RD_THREADS) {
       const float d = lg[v] - mv;
       se += expf(d);
       if constexpr (CONF) {
@@ -308,6 +321,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
     se = block_sum(se, red_v);
     if (sums) { cA = block_sum(sa, red_v); cB = block_sum(sb, red_v); }
     int kf = mi;
+    if constexpr (MB) kf = (mi < 0 || mi >= NV) ? NV - 1 : mi;   // a row with no number is a blank
     if constexpr (NM > 0) {
       if (mi != p.blank) {   // (uniform)
         // every lane ranks its labels with the models (bounded, clamped look-ups; the tables come from L2), then the block arg-max
@@ -391,7 +405,27 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
     __syncthreads();
     pred_step(false);
   };
-  if constexpr (TDT) {
+  if constexpr (MB) {
+    // the RNN-T loop below with t advancing by a blank-like output's frames; sym counts the labels of frame t
+    const int bo = V1 - 1 + p.dur.D;   // the standard blank's row; rows [V1 - 1, bo) are the big blanks, bo - 1 - i big blank i
+    int t = STREAM ? skip : 0, sym = 0;
+    while (t < len) {
+      if (p.max_symbols > 0 ? sym >= p.max_symbols : n >= p.max_out) { ++t; sym = 0; continue; }
+      const float se = joint_step(t);
+      const int k = s_k;
+      if (k >= V1 - 1) {
+        int d = 1;
+#pragma unroll
+        for (int i = 0; i < MB_MAXNB; ++i) d = (i == bo - 1 - k) ? p.dur.d[i] : d;
+        t += d;
+        sym = 0;
+      } else {
+        emit(k, t, se);
+        ++sym;
+      }
+    }
+    if (STREAM) skip = max(t - len, 0);
+  } else if constexpr (TDT) {
     // t advances by the predicted duration; the output budget bounds the search like max_symbols <= 0 below
     int t = STREAM ? skip : 0;   // frames an earlier chunk's duration already jumped over
     if (!STREAM) same = 0;
@@ -466,11 +500,24 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(typename RnntDe
       for (int i = tid; i < H; i += RD_THREADS) { p.sout.h[(long long)b * H + i] = h[i]; p.sout.c[(long long)b * H + i] = c[i]; }
     if (tid == 0) {
       p.sout.last[b] = last; p.sout.score[b] = score; p.sout.frames_done[b] = frames_done + len;
-      if (TDT) { p.sout.skip[b] = skip; p.sout.zero_run[b] = same; }
+      if (TDT || MB) { p.sout.skip[b] = skip; p.sout.zero_run[b] = same; }
     }
   }
 }
 
+// The 4 multi-blank instantiations, [weights][one-shot, resumable], live in rnnt_decode_mb.hip: that file includes this one with
+// RD_MULTIBLANK_TU defined and the packed fp32 instructions turned off, and holds nothing but them and their launcher.
+void rd_launch_multiblank(const RnntDecP& p, bool bf16, bool resumable, size_t shm, hipStream_t s);
+#ifdef RD_MULTIBLANK_TU
+void rd_launch_multiblank(const RnntDecP& p, bool bf16, bool resumable, size_t shm, hipStream_t s) {
+  static const void* const mbk[2][2] = {
+      {(const void*)rnnt_greedy_kernel<float, RD_MB, false, false>, (const void*)rnnt_greedy_kernel<float, RD_MB, true, false>},
+      {(const void*)rnnt_greedy_kernel<bf16_t, RD_MB, false, false>, (const void*)rnnt_greedy_kernel<bf16_t, RD_MB, true, false>}};
+  const void* fn = mbk[bf16][resumable];
+  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  MI_LAUNCH((void (*)(RnntDecP))fn, dim3(p.B), dim3(RD_THREADS), shm, s, p);
+}
+#else
 // The 16 DEEP instantiations, [weights][TDT][plain, with confidences, one model, two models], all of them the resumable kernel: a
 // one-shot call is a fresh stream with no state to write.  The block is the one the shallow kernel of the same form takes, with
 // the upper layers behind it.
@@ -486,7 +533,8 @@ static void greedy_issue_deep(const void* fn, const Block& block, const RnntUppe
 // the confidence of every emitted label or with one or two fusion models.  Every check is here; nothing is launched after a refusal.
 // `upper` (mi355x_transducer_greedy_decode_layers): layers 1 .. n_upper of the prediction network; null or n_upper == 0 is the call
 // without it, down to the kernel launched.
-static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, const mi355x_transducer_lstm_layers* upper, hipStream_t s) {
+static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, const mi355x_transducer_lstm_layers* upper, hipStream_t s,
+                              bool mb = false, int n_big = 0, const int* big = nullptr) {
   if (!d) return MI_ERR_ARG;
   if (!d->enc_proj || !d->emb || !d->w_ih || !d->w_hh || !d->b_ih || !d->b_hh || !d->w_pred || !d->w_out || !d->tokens || !d->out_len)
     return MI_ERR_ARG;
@@ -507,6 +555,16 @@ static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, const mi35
   p.dur = {};
   if (tdt && tdt_durations(d->D, d->durations, &p.dur)) return MI_ERR_ARG;
   const bool fused = d->models || d->n_models != 0;
+  // multi-blank (mi355x_transducer_greedy_decode_multiblank): the plain search only, a valid set, and the blank of the prediction
+  // network = its last row
+  if (mb) {
+    MbDur bd;
+    if (tdt || fused || d->conf || upper || mb_durations(n_big, big, &bd) ||
+        d->blank != V1 - 1 || V1 < 2)
+      return MI_ERR_ARG;
+    for (int i = 0; i < MB_MAXNB; ++i) p.dur.d[i] = bd.d[i];   // (TDT_MAXD = 8 entries: room for the 7)
+    p.dur.D = bd.nb;
+  }
   if (d->conf && (fused || !d->tok_conf || !mi_conf_valid(V1, d->conf->method, d->conf->norm, d->conf->alpha)))
     return MI_ERR_ARG;   // (no instantiation has both the confidence sums and the models)
   if (d->state_in && !d->state_out) return MI_ERR_ARG;
@@ -514,7 +572,7 @@ static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, const mi35
   for (int io = 0; io < 2; ++io) {   // a state is given whole (skip / zero_run: TDT only) or not at all
     const mi355x_rnnt_stream_state* st = io ? d->state_out : d->state_in;
     if (!st) continue;
-    if (!st->h || !st->c || !st->last || !st->score || !st->frames_done || (tdt && (!st->skip || !st->zero_run))) return MI_ERR_ARG;
+    if (!st->h || !st->c || !st->last || !st->score || !st->frames_done || ((tdt || mb) && (!st->skip || !st->zero_run))) return MI_ERR_ARG;
     (io ? p.sout : p.sin) = *st;
   }
   if (p.sin.h && p.sout.h && (p.sin.h == p.sout.h || p.sin.c == p.sout.c)) return MI_ERR_ARG;   // out of place
@@ -574,6 +632,11 @@ static int greedy_decode_impl(const mi355x_transducer_greedy_desc* d, const mi35
     return MI_OK;
   }
 
+  if (mb) {
+    rd_launch_multiblank(p, d->w_dtype == MI_DT_BF16, d->state_out != nullptr, shm, s);
+    return MI_OK;
+  }
+
   // The 24 instantiations, [weights][TDT][mode]: the one-shot and the resumable kernel, each plain and with confidences, and the
   // resumable kernel with one and with two models (a fused one-shot call is a fresh stream with no state to write).
   enum { RD_ONESHOT = 0, RD_STREAM = 2, RD_FUSED = 3 };   // + 1: with confidences / + n_models
@@ -615,3 +678,11 @@ extern "C" int mi355x_transducer_greedy_decode_layers(const mi355x_transducer_gr
   const int rc = greedy_decode_impl(d, upper, (hipStream_t)stream);
   return rc != MI_OK ? rc : mi_check_launch();
 }
+
+extern "C" int mi355x_transducer_greedy_decode_multiblank(const mi355x_transducer_greedy_desc* d, int n_big_blanks,
+                                                          const int* big_blank_durations, void* stream) {
+  mi_clear_errors();
+  const int rc = greedy_decode_impl(d, nullptr, (hipStream_t)stream, true, n_big_blanks, big_blank_durations);
+  return rc != MI_OK ? rc : mi_check_launch();
+}
+#endif   // RD_MULTIBLANK_TU

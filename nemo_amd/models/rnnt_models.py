@@ -14,7 +14,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
-from ..modules import RNNTLoss, TDTLoss
+from ..modules import MultiblankRNNTLoss, RNNTLoss, TDTLoss
 from .ctc_models import (EncDecCTCModel, _as_list, _audio_batch, _build as _build_ctc, _inference_setup, _with_seconds,
                          frame_stride_s)
 
@@ -56,9 +56,10 @@ class EncDecRNNTModel(EncDecCTCModel):
             raise ValueError("the vocabulary size must be given (`labels`, `joint.num_classes` or `decoder.vocab_size`)")
         lc = dict(cfg.get("loss") or {})
         loss_name = lc.get("loss_name", "default")
-        if loss_name not in ("default", "warprnnt_numba", "tdt"):
-            # losses/rnnt.py:41-100 RNNT_LOSS_RESOLVER: multiblank / pytorch / graph losses are different objectives
-            raise NotImplementedError(f"transducer loss '{loss_name}' (implemented: default = warprnnt_numba semantics, tdt)")
+        if loss_name not in ("default", "warprnnt_numba", "tdt", "multiblank_rnnt"):
+            # losses/rnnt.py:41-100 RNNT_LOSS_RESOLVER: pytorch / graph losses are different objectives
+            raise NotImplementedError(f"transducer loss '{loss_name}' (implemented: default = warprnnt_numba semantics, tdt, "
+                                      "multiblank_rnnt)")
         dec = dict(cfg["decoder"]); dec["vocab_size"] = n_cls
         jnt = dict(cfg["joint"]); jnt["num_classes"] = n_cls
         tdt_kw = None
@@ -68,6 +69,16 @@ class EncDecRNNTModel(EncDecCTCModel):
             if not tdt_kw.get("durations"):
                 raise ValueError("loss_name 'tdt' needs loss.tdt_kwargs.durations")
             jnt["num_extra_outputs"] = len(tdt_kw["durations"])
+        mb_kw = None
+        if loss_name == "multiblank_rnnt":
+            # multi-blank transducer: the joint puts one output per big blank between the labels and the standard blank
+            # (num_extra_outputs), loss blank = vocabulary size + nb; the prediction network is the RNN-T one
+            mb_kw = dict(lc.get("multiblank_rnnt_kwargs") or {})
+            if not mb_kw.get("big_blank_durations"):
+                raise ValueError("loss_name 'multiblank_rnnt' needs loss.multiblank_rnnt_kwargs.big_blank_durations")
+            if self._takes_aux_ctc:
+                raise NotImplementedError("loss_name 'multiblank_rnnt' in a hybrid transducer-CTC model")
+            jnt["num_extra_outputs"] = len(mb_kw["big_blank_durations"])
         jnt["jointnet"] = dict(jnt["jointnet"])
         jnt["jointnet"].setdefault("encoder_hidden", cfg.get("model_defaults", {}).get("enc_hidden", self.encoder._feat_out))
         jnt["jointnet"].setdefault("pred_hidden", dec["prednet"]["pred_hidden"])
@@ -79,7 +90,19 @@ class EncDecRNNTModel(EncDecCTCModel):
         # skip_nan_grad (models/asr_model.py:147-174): handled by the shared fit_step / on_after_backward (EncDecCTCModel)
         self._skip_nan_grad = bool(cfg.get("skip_nan_grad"))
         self.skipped_steps = 0
-        if tdt_kw is not None:
+        if mb_kw is not None:
+            from ..modules.stateless import StatelessTransducerDecoder
+            if isinstance(self.decoder, StatelessTransducerDecoder):
+                raise NotImplementedError("loss_name 'multiblank_rnnt' with a StatelessTransducerDecoder")
+            if int(getattr(self.decoder, "pred_rnn_layers", 1)) != 1:
+                raise NotImplementedError(f"loss_name 'multiblank_rnnt' with `pred_rnn_layers` = {self.decoder.pred_rnn_layers}: the "
+                                          "multi-blank search runs one LSTM layer")
+            self.loss = MultiblankRNNTLoss(blank=n_cls + len(mb_kw["big_blank_durations"]),
+                                           big_blank_durations=list(mb_kw["big_blank_durations"]),
+                                           reduction=cfg.get("rnnt_reduction", "mean_batch"),
+                                           fastemit_lambda=mb_kw.get("fastemit_lambda", 0.0), clamp=mb_kw.get("clamp", -1.0),
+                                           sigma=mb_kw.get("sigma", 0.0))
+        elif tdt_kw is not None:
             self.loss = TDTLoss(blank=n_cls, durations=list(tdt_kw["durations"]), reduction=cfg.get("rnnt_reduction", "mean_batch"),
                                 fastemit_lambda=tdt_kw.get("fastemit_lambda", 0.0), clamp=tdt_kw.get("clamp", -1.0),
                                 sigma=tdt_kw.get("sigma", 0.0), omega=tdt_kw.get("omega", 0.0))
@@ -133,12 +156,15 @@ class EncDecRNNTModel(EncDecCTCModel):
             # TDT: `decoding.model_type: tdt` with `decoding.durations`; a joint with duration outputs decodes as TDT with the
             # loss's durations when the decoding section does not say otherwise
             tdt_loss = isinstance(self.loss, TDTLoss)
-            model_type = dcfg.get("model_type", "tdt" if tdt_loss else "rnnt")
+            mb_loss = isinstance(self.loss, MultiblankRNNTLoss)   # likewise: `model_type: multiblank` with `big_blank_durations`
+            model_type = dcfg.get("model_type", "tdt" if tdt_loss else "multiblank" if mb_loss else "rnnt")
             durations = dcfg.get("durations") or (self.loss.durations if tdt_loss else None)
+            big_blanks = dcfg.get("big_blank_durations") or (self.loss.big_blank_durations if mb_loss else None)
             self._decoding = RNNTDecoding(self.decoder, self.joint, vocabulary=list(vocab) if vocab is not None else None,
                                           max_symbols=ms, tokenizer=self.tokenizer if vocab is None else None,
                                           model_type=model_type, durations=list(durations) if durations else None,
-                                          confidence_cfg=dcfg.get("confidence_cfg"), fusion_models=fusion, beam=beam)
+                                          confidence_cfg=dcfg.get("confidence_cfg"), fusion_models=fusion, beam=beam,
+                                          big_blank_durations=list(big_blanks) if big_blanks else None)
         return self._decoding
 
     def change_decoding_strategy(self, decoding_cfg=None, verbose: bool = True):
@@ -341,6 +367,8 @@ def transducer_align_audio(model, audio, texts, batch_size=4, channel_selector=N
     texts = [texts] if isinstance(texts, str) else list(texts)
     if len(texts) != len(audio):
         raise ValueError(f"align() takes one transcript per input: {len(audio)} inputs, {len(texts)} transcripts")
+    if isinstance(model.loss, MultiblankRNNTLoss):
+        raise NotImplementedError("align() on a multi-blank transducer head: the alignment lattice knows no big blanks")
     tdt = isinstance(model.loss, TDTLoss)
     aligner = TransducerAligner(model.decoder, model.joint, durations=model.loss.durations if tdt else None)
     vocab = decoding.vocabulary if decoding.vocabulary is not None else list(decoding.tokenizer.vocab)
@@ -456,4 +484,21 @@ def fastconformer_tdt_config(size: str = "large", vocab_size: int = 1024, durati
     cfg["loss"] = dict(loss_name="tdt", tdt_kwargs=dict(fastemit_lambda=0.0, clamp=-1.0, durations=list(durations), sigma=sigma,
                                                         omega=omega))
     cfg["decoding"] = dict(strategy="greedy_batch", model_type="tdt", durations=list(durations), greedy=dict(max_symbols=10))
+    return cfg
+
+
+def fastconformer_multiblank_config(size: str = "large", vocab_size: int = 1024, big_blank_durations=(2, 4, 8), sigma: float = 0.05,
+                                    spec_augment: bool = False, **encoder_overrides) -> Dict[str, Any]:
+    """the FastConformer-Transducer model section with the multi-blank transducer objective (Xu et al. 2022; the reference's
+    conformer_multiblank_transducer_bpe.yaml): the joint has one output per big blank (joint.num_extra_outputs), loss_name
+    multiblank_rnnt with multiblank_rnnt_kwargs {big_blank_durations, sigma}, greedy multi-blank decoding."""
+    cfg = fastconformer_transducer_config(size, vocab_size=vocab_size, spec_augment=spec_augment, **encoder_overrides)
+    durations = [int(d) for d in big_blank_durations]
+    cfg["model_defaults"]["big_blank_durations"] = list(durations)
+    cfg["model_defaults"]["num_big_blanks"] = len(durations)
+    cfg["joint"]["num_extra_outputs"] = len(durations)
+    cfg["loss"] = dict(loss_name="multiblank_rnnt", multiblank_rnnt_kwargs=dict(fastemit_lambda=0.0, clamp=-1.0,
+                                                                                 big_blank_durations=list(durations), sigma=sigma))
+    cfg["decoding"] = dict(strategy="greedy_batch", model_type="multiblank", big_blank_durations=list(durations),
+                           greedy=dict(max_symbols=10))
     return cfg

@@ -10,9 +10,11 @@ from .ngram_lm import NGramLM  # noqa: F401
 from .boosting_tree import BoostingTree  # noqa: F401
 from .rnnt_loss import RNNTLoss, RNNTLossNumba  # noqa: F401
 from .tdt_loss import TDTLoss, TDTLossNumba  # noqa: F401
+from .multiblank_loss import MultiblankRNNTLoss, MultiblankRNNTLossNumba  # noqa: F401
 from .rnnt import RNNTDecoder, RNNTJoint  # noqa: F401
 from .stateless import StatelessTransducerDecoder  # noqa: F401
 from .rnnt_decoding import GreedyBatchedRNNTInfer, GreedyBatchedTDTInfer, RNNTDecoding, RNNTWER, Hypothesis  # noqa: F401
+from .rnnt_decoding import GreedyBatchedMultiblankRNNTInfer  # noqa: F401
 from .rnnt_decoding import transducer_fusion_from_config  # noqa: F401
 from .rnnt_decoding import BeamBatchedRNNTInfer, BeamBatchedTDTInfer, transducer_beam_from_config  # noqa: F401
 from .transducer_align import TransducerAligner  # noqa: F401

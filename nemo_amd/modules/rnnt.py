@@ -29,6 +29,7 @@ from ..core import (AcousticEncodedRepresentation, ElementType, EmbeddedTextType
                     LossType, NeuralType, typecheck)
 from ..packing import _pad8
 from .engine import EngineModule, wgrad_tn
+from .multiblank_loss import MultiblankRNNTLoss
 from .tdt_loss import TDTLoss, draw_rnnt_call
 
 
@@ -296,6 +297,7 @@ class RNNTJoint(_TransducerModule):
         if num_extra_outputs < 0 or num_extra_outputs > 8:
             raise ValueError(f"num_extra_outputs (TDT durations) must lie in [0, 8], got {num_extra_outputs}")
         # TDT (num_extra_outputs = number of durations): the output layer appends the duration logits behind the V+1 label logits
+        # (multi-blank: num_extra_outputs = number of big blanks, which sit between the labels and the standard blank, the last row)
         self._num_extra_outputs = int(num_extra_outputs)
         self._num_classes = num_classes + 1 + self._num_extra_outputs
         self._fuse_loss_wer, self._fused_batch_size = fuse_loss_wer, fused_batch_size
@@ -541,8 +543,13 @@ class RNNTJoint(_TransducerModule):
         fe = float(getattr(loss_mod, "fastemit_lambda", 0.0) or 0.0)   # (a TDTLoss holds 0.0 for both)
         cl = float(getattr(loss_mod, "clamp", 0.0) or 0.0)
 
+        mblank = isinstance(loss_mod, MultiblankRNNTLoss)   # multi-blank: one softmax over the whole row, the blank last
+
         def pitched_loss(logits, ld, nb, Ts, Us, lab, el_, tl_, grads, gscale):
             """the loss of one sub-batch: logits and `grads` (None: loss only) in rows of pitch ld"""
+            if mblank:
+                return ops.multiblank_loss_pitched(logits, ld, nb, Ts, Us, V1, loss_mod.big_blank_durations, lab, el_, tl_,
+                                                   loss_mod.blank, grads=grads, ld_grads=ld, sigma=loss_mod.sigma, grad_scale=gscale)
             if tdt and not tdt_as_rnnt:
                 return ops.tdt_loss_pitched(logits, ld, nb, Ts, Us, Vl, loss_mod.durations, lab, el_, tl_, self._vocab_size,
                                             grads=grads, ld_grads=ld, sigma=loss_mod.sigma, grad_scale=gscale)

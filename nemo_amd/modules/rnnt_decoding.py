@@ -370,6 +370,44 @@ class GreedyBatchedTDTInfer(GreedyBatchedRNNTInfer):
         return ops.tdt_greedy_decode_stream_conf(*args[:16], self.durations, args[16], method, **kw)
 
 
+class GreedyBatchedMultiblankRNNTInfer(GreedyBatchedRNNTInfer):
+    """`GreedyBatchedMultiblankRNNTInfer` (rnnt_greedy_decoding.py): greedy search of a multi-blank transducer, whose joint has nb
+    big-blank outputs between the V labels and the standard blank.  `blank_index` = V + nb, the joint's standard blank (the
+    prediction network's blank, the zero embedding row, is V).  One arg-max over all outputs per step: the blank moves on by one
+    frame, big blank i by `big_blank_durations[i]`, a label is the RNN-T search's.  One launch for the batch
+    (`mi355x_transducer_greedy_decode_multiblank`; streaming through `partial_hypotheses`: a big blank that jumps past the end
+    of a chunk is taken off the next one).  The plain search only: fusion models, a `confidence_cfg` that preserves anything, more
+    than one LSTM layer and a StatelessTransducerDecoder are refused by name."""
+
+    def __init__(self, decoder_model, joint_model, blank_index: int, big_blank_durations, max_symbols_per_step: Optional[int] = None,
+                 **kw):
+        from .multiblank_loss import check_big_blank_durations
+        self.big_blank_durations = check_big_blank_durations(big_blank_durations)
+        nb = len(self.big_blank_durations)
+        super().__init__(decoder_model, joint_model, int(blank_index) - nb, max_symbols_per_step=max_symbols_per_step, **kw)
+        if self.fusion_models is not None:
+            raise NotImplementedError("multi-blank decoding with fusion models (`greedy.ngram_lm_*` / `greedy.boosting_tree`)")
+        if self.confidence_cfg is not None and (self.confidence_cfg.wants_tokens or self.confidence_cfg.preserve_frame_confidence):
+            raise NotImplementedError("multi-blank decoding with a `confidence_cfg` that preserves confidences: the multi-blank "
+                                      "search computes none")
+        if self.stateless:
+            raise NotImplementedError("multi-blank decoding with a StatelessTransducerDecoder: the multi-blank search runs an LSTM "
+                                      "prediction network")
+        if self.pred_layers != 1:
+            raise NotImplementedError(f"multi-blank decoding with `pred_rnn_layers` = {self.pred_layers}: the multi-blank search "
+                                      "runs one LSTM layer")
+        if getattr(joint_model, "_num_extra_outputs", nb) != nb:
+            raise ValueError(f"the joint has {joint_model._num_extra_outputs} extra outputs for {nb} big blanks")
+        if self._blank_index != int(getattr(decoder_model, "blank_idx", self._blank_index)):
+            raise ValueError(f"`blank_index` must be the joint's standard blank, vocabulary size + {nb}; got {blank_index}")
+
+    def _search(self, *args, upper_layers=None, **kw):
+        return ops.multiblank_greedy_decode(*args[:16], self.big_blank_durations, args[16], **kw)
+
+    def _search_stream(self, *args, upper_layers=None, **kw):
+        return ops.multiblank_greedy_decode_stream(*args[:16], self.big_blank_durations, args[16], **kw)
+
+
 class BeamBatchedRNNTInfer(GreedyBatchedRNNTInfer):
     """`strategy: malsd_batch` for an RNN-T head: `forward(encoder_output [B, D, T], encoded_lengths)` -> a 1-tuple holding the
     best `Hypothesis` of every utterance (y_sequence, timestamp, score); with `return_best_hypothesis=False` each also carries
@@ -497,17 +535,25 @@ class RNNTDecoding:
 
     def __init__(self, decoder, joint, vocabulary: Optional[Sequence[str]] = None, max_symbols: Optional[int] = 10,
                  tokenizer=None, model_type: str = "rnnt", durations: Optional[Sequence[int]] = None, confidence_cfg=None,
-                 fusion_models=None, beam=None):
+                 fusion_models=None, beam=None, big_blank_durations: Optional[Sequence[int]] = None):
         from .confidence import confidence_from
         self.vocabulary = list(vocabulary) if vocabulary is not None else None
         self.tokenizer = tokenizer
         self.blank_id = decoder.blank_idx
         self.confidence_cfg = confidence_from(confidence_cfg)
-        if model_type not in ("rnnt", "tdt"):
-            raise NotImplementedError(f"transducer decoding model_type '{model_type}' (implemented: rnnt, tdt)")
+        if model_type not in ("rnnt", "tdt", "multiblank"):
+            raise NotImplementedError(f"transducer decoding model_type '{model_type}' (implemented: rnnt, tdt, multiblank)")
         if model_type == "tdt" and not durations:
             raise ValueError("decoding with model_type 'tdt' needs `durations`")
-        if beam is not None:   # strategy malsd_batch: the keyword arguments `transducer_beam_from_config` read
+        if model_type == "multiblank":
+            if not big_blank_durations:
+                raise ValueError("decoding with model_type 'multiblank' needs `big_blank_durations`")
+            if beam is not None:
+                raise NotImplementedError("strategy 'malsd_batch' with a multi-blank model: the beam search knows no big blanks")
+            self.decoding = GreedyBatchedMultiblankRNNTInfer(decoder, joint, self.blank_id + len(big_blank_durations),
+                                                             big_blank_durations, max_symbols_per_step=max_symbols,
+                                                             confidence_cfg=self.confidence_cfg, fusion_models=fusion_models)
+        elif beam is not None:   # strategy malsd_batch: the keyword arguments `transducer_beam_from_config` read
             if fusion_models:
                 raise NotImplementedError("strategy 'malsd_batch' with fusion models (`ngram_lm_*` / `boosting_tree`)")
             beam = dict(beam, confidence_cfg=self.confidence_cfg)

@@ -1011,14 +1011,15 @@ def rnnt_loss(acts, labels, act_lens, label_lens, blank, grads=None, fastemit_la
 
 def _greedy_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
                    blank, durations, max_symbols, max_out, *, with_state=False, stream=None, state=None, method=None, models=None,
-                   upper_layers=None):
+                   upper_layers=None, big_blanks=None):
     """every greedy transducer search: the outputs, the descriptor and the one entry (mi355x_transducer_greedy_decode).  `durations`
     given: TDT.  `stream` = the state class of the resumable search (None: one-shot), `state` = the state to start from (None: fresh
     streams).  `method` = the confidence measure, `models` = the checked fusion models.  -> (tokens, times, out_len), then whatever
     was asked for, in this order: score (every search but the resumable one without models), (h, c) (`with_state`), the next state
     (`stream`), tok_conf (`method`).  `upper_layers` = [(w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh), ...] for layers 1 .. L-1 of the
     prediction network (mi355x_transducer_greedy_decode_layers; weights in w_ih's dtype, biases fp32): every LSTM state is then
-    [L, B, H].  None or empty: the one-layer search, as ever."""
+    [L, B, H].  None or empty: the one-layer search, as ever.  `big_blanks` = the big-blank durations of the multi-blank search
+    (w_out / b_out with V1 + len(big_blanks) rows; the plain search only)."""
     upper_layers = list(upper_layers) if upper_layers else []
     L = 1 + len(upper_layers)
     if L > 4:
@@ -1056,7 +1057,7 @@ def _greedy_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih,
         out += ((h, c),)
     if stream is not None:
         nxt = stream.empty(B, H, dev, layers=L)
-        if durations is None:   # (not written by the RNN-T search)
+        if durations is None and big_blanks is None:   # (not written by the RNN-T search)
             nxt.skip.zero_(); nxt.zero_run.zero_()
         for field, st in (("state_in", state), ("state_out", nxt)):
             if st is not None:
@@ -1074,6 +1075,14 @@ def _greedy_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih,
         arr, tables = _ctc_beam_fusion_array(models, enc_proj)
         keep += [arr, tables]
         d.models, d.n_models = C.addressof(arr), len(arr)
+    if big_blanks is not None:
+        bb = [int(x) for x in big_blanks]
+        if not 1 <= len(bb) <= 7:
+            raise ValueError(f"{what}: between 1 and 7 big blanks, got {len(bb)}")
+        if upper_layers or models is not None or method is not None or durations is not None:
+            raise ValueError(f"{what}: the multi-blank search is the plain one-layer search")
+        check(lib.mi355x_transducer_greedy_decode_multiblank(C.byref(d), len(bb), (C.c_int * len(bb))(*bb), _stream()), what)
+        return out
     if L == 1:
         check(lib.mi355x_transducer_greedy_decode(C.byref(d), _stream()), what)
         return out
@@ -1196,6 +1205,42 @@ def tdt_loss(acts, labels, act_lens, label_lens, blank, durations, grads=None, s
     V1 = W - len(durations)
     return tdt_loss_pitched(acts, W, B, T, U1, V1, durations, labels, act_lens, label_lens, blank, grads=grads, ld_grads=W,
                             sigma=sigma, grad_scale=grad_scale)
+
+
+def multiblank_loss_pitched(acts, ld_acts, B, T, U1, N, big_blank_durations, labels, act_lens, label_lens, blank, grads=None,
+                            ld_grads=0, sigma=0.0, grad_scale=1.0):
+    """multi-blank transducer loss (mi355x_multiblank_loss_ex; include/mi355x_asr.h states the rule): acts f32 logits [.., N] in rows
+    of pitch ld_acts, N = V + 1 + nb with the nb big blanks in front of the standard blank (blank = N - 1); grads (f32 or bf16,
+    optional) rows of pitch ld_grads, pad columns zero-filled -> costs f32 [B]"""
+    nb, dur = _tdt_durations(big_blank_durations)
+    return _transducer_loss("multiblank_loss_ex", acts, ld_acts, labels, act_lens, label_lens, B, T, U1, N,
+                            (nb, dur, blank, sigma, grad_scale), 5 + nb, grads, ld_grads)
+
+
+def multiblank_loss(acts, labels, act_lens, label_lens, blank, big_blank_durations, grads=None, sigma=0.0, grad_scale=1.0):
+    """acts f32 [B,T,U1,N] logits (contiguous); labels i64 [B,U1-1]; returns costs f32 [B]; fills `grads` (f32, same shape)"""
+    B, T, U1, N = acts.shape
+    return multiblank_loss_pitched(acts, N, B, T, U1, N, big_blank_durations, labels, act_lens, label_lens, blank, grads=grads,
+                                   ld_grads=N, sigma=sigma, grad_scale=grad_scale)
+
+
+def multiblank_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                             b_out, blank, big_blank_durations, max_symbols, max_out=None, with_state=False):
+    """greedy multi-blank search of a whole batch in one launch (mi355x_transducer_greedy_decode_multiblank): as
+    rnnt_greedy_decode, with w_out / b_out holding V1 + nb rows (labels, the big blanks, the standard blank last) and `blank` =
+    V1 - 1, the zero embedding row; a big blank moves on by its duration"""
+    return _greedy_search("multiblank_greedy_decode", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred,
+                          b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, with_state=with_state,
+                          big_blanks=big_blank_durations)
+
+
+def multiblank_greedy_decode_stream(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out,
+                                    ld_out, b_out, blank, big_blank_durations, max_symbols, state=None, max_out=None):
+    """one chunk of the resumable multi-blank search: as rnnt_greedy_decode_stream on an RNNTStreamState; a big blank that jumps past
+    the chunk's end is carried in the state (`skip`) and taken off the next chunk(s)"""
+    return _greedy_search("multiblank_greedy_decode_stream", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred,
+                          ld_pred, b_pred, w_out, ld_out, b_out, blank, None, max_symbols, max_out, stream=RNNTStreamState,
+                          state=state, big_blanks=big_blank_durations)
 
 
 def tdt_greedy_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,

@@ -55,7 +55,8 @@ typedef struct mi355x_gemm_desc {
   float alpha;
   int epilogue;
   int atomic;                       /* 1: atomicAdd into f32 C (required for splitk > 1)                         */
-  int splitk;
+  int splitk;                       /* > 1 (more than one slice after clamping to the K-tiles): no bias, and only the epilogues
+                                     * that are linear in the sum (STORE, DSWISH, MUL_POS, DSWISH_G): every slice runs the epilogue */
   const void* aux_in; int aux_in_dtype;
   void* aux_out; int aux_out_dtype;
   long long ldaux;                  /* pitch of aux_in / aux_out (same batch offsets as C)                       */

@@ -3376,6 +3376,9 @@ static int gemm_fill(const mi355x_gemm_desc* d, GemmP* out) {
   if (p.colsum_out && (!p.transA || d->in_dtype != MI_DT_BF16 || p.nb0 != p.batch)) return MI_ERR_ARG;
   p.splitk = splitk_norm(cdiv(p.K, BK), d->splitk, 1, &p.ktiles_per_split);
   if (p.splitk > 1 && !p.atomic) return MI_ERR_ARG;
+  // every K slice runs the whole epilogue and adds its result: a bias or a residual would be added once per slice, Swish and ReLU
+  // would be taken of partial sums.  Only the kinds that are linear in the accumulator can be split
+  if (p.splitk > 1 && (p.bias || p.epi == EPI_RESID || p.epi == EPI_SWISH_DROP || p.epi == EPI_RELU_MASK)) return MI_ERR_ARG;
   {
     // bit 0: 8-column chunks as vectors (f32 rows: two 16-byte accesses, pitch % 4 == 0; bf16 rows: one, pitch % 8 == 0);
     // bit 1: 4-column chunks as vectors (16-byte f32 / 8-byte bf16: pitch % 4 == 0) -- the last columns of a width of 4 modulo 8
@@ -3388,6 +3391,9 @@ static int gemm_fill(const mi355x_gemm_desc* d, GemmP* out) {
     bool ok = base && pitch8(p.ldc, p.c_dt), ok4 = base && !(p.ldc & 3);
     if (p.aux_in) { ok = ok && pitch8(p.ldaux, auxin_dt); ok4 = ok4 && !(p.ldaux & 3); }
     if (p.aux_out) { ok = ok && pitch8(p.ldaux, p.auxout_dt); ok4 = ok4 && !(p.ldaux & 3); }
+    // the full-width tile epilogues (fast_epilogue, v8_round_fast: all behind bit 0) apply the row map for EPI_MUL_POS only -- the
+    // one kind the conv stack combines it with; a mapped launch of another kind keeps to the per-chunk forms, which call crow()
+    if (p.r_on && p.epi != EPI_MUL_POS) ok = false;
     p.vec_ok = (ok ? 1 : 0) | (ok4 ? 2 : 0);
 #ifdef GEMM_ABLATE
     { const char* e = getenv("MI355X_GEMM_DBG"); if (e) p.vec_ok |= atoi(e) << 8; }

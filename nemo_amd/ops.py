@@ -128,40 +128,46 @@ def wgrad_grouped(problems, rows, splitk):
     GEMM_PROFILE.append(("bf16_TN", sum(q[7] * q[8] for q in problems), 1, rows, 1, e0, e1))
 
 
-def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, *, transA=False, transB=False, in_dtype=None, c_dtype=None, batch=1, nb0=0,
-         sA=(0, 0), sB=(0, 0), sC=(0, 0), bias=None, alpha=1.0, epi=EPI_STORE, atomic=False, splitk=1, aux_in=None,
-         aux_out=None, ldaux=0, drop: Dropout = NO_DROP, row_len=None, rows_per_b=1, rows_inner=1,
-         a_off=0, b_off=0, c_off=0, c_col_stride=1, colsum_out=None, colsum_off=0, colsum_stride=0, gather=None,
-         rowmap=None):
-    """C[M,N] = epi(A @ B^T) -- see mi355x_gemm.  A/B/Cm are tensors whose storage holds the (strided) operands;
-    *_off are element offsets into them (head / column slices)."""
+def _addr(t) -> int:
+    """device address of a tensor; an int is taken as the address itself (gemm_desc for mi355x_gemm_plan: nothing dereferences it)"""
+    return t if isinstance(t, int) else _ptr(t)
+
+
+def gemm_desc(A, B, Cm, M, N, K, lda, ldb, ldc, *, transA=False, transB=False, in_dtype=None, c_dtype=None, batch=1, nb0=0,
+              sA=(0, 0), sB=(0, 0), sC=(0, 0), bias=None, alpha=1.0, epi=EPI_STORE, atomic=False, splitk=1, aux_in=None,
+              aux_out=None, ldaux=0, drop: Dropout = NO_DROP, row_len=None, rows_per_b=1, rows_inner=1,
+              a_off=0, b_off=0, c_off=0, c_col_stride=1, colsum_out=None, colsum_off=0, colsum_stride=0, gather=None,
+              rowmap=None, aux_in_dtype=None, aux_out_dtype=None):
+    """The descriptor gemm() launches, for the same arguments.  Tensors may be given as plain addresses (ints) when the descriptor
+    is only planned (gemm_plan); their dtypes are then passed as in_dtype / c_dtype / aux_in_dtype / aux_out_dtype.  The gather /
+    row-map structs the descriptor points to hang on it as `d.keep`."""
     d = GemmDesc()
-    esA, esC = A.element_size(), Cm.element_size()
-    d.A = _ptr(A) + a_off * esA
-    d.B = _ptr(B) + b_off * B.element_size()
-    d.C = _ptr(Cm) + c_off * esC
+    d.in_dtype = dt(A) if in_dtype is None else in_dtype
+    d.c_dtype = dt(Cm) if c_dtype is None else c_dtype
+    esA, esC = (2 if d.in_dtype == BF16 else 4), (2 if d.c_dtype == BF16 else 4)
+    d.A = _addr(A) + a_off * esA
+    d.B = _addr(B) + b_off * esA
+    d.C = _addr(Cm) + c_off * esC
     d.M, d.N, d.K = M, N, K
     d.lda, d.ldb, d.ldc = lda, ldb, ldc
     d.c_col_stride = c_col_stride
     d.transA, d.transB = int(transA), int(transB)
-    d.in_dtype = dt(A) if in_dtype is None else in_dtype
-    d.c_dtype = dt(Cm) if c_dtype is None else c_dtype
     d.batch, d.nb0 = batch, (nb0 if nb0 > 0 else batch)
     d.sA0, d.sA1 = sA
     d.sB0, d.sB1 = sB
     d.sC0, d.sC1 = sC
-    d.bias = _ptr(bias)
+    d.bias = _addr(bias) if bias is not None else 0
     d.alpha = alpha
     d.epilogue, d.atomic, d.splitk = epi, int(atomic), splitk
-    d.aux_in = _ptr(aux_in)
-    d.aux_in_dtype = dt(aux_in) if aux_in is not None else 0
-    d.aux_out = _ptr(aux_out)
-    d.aux_out_dtype = dt(aux_out) if aux_out is not None else 0
+    d.aux_in = _addr(aux_in) if aux_in is not None else 0
+    d.aux_in_dtype = 0 if aux_in is None else (dt(aux_in) if aux_in_dtype is None else aux_in_dtype)
+    d.aux_out = _addr(aux_out) if aux_out is not None else 0
+    d.aux_out_dtype = 0 if aux_out is None else (dt(aux_out) if aux_out_dtype is None else aux_out_dtype)
     d.ldaux = ldaux if ldaux else ldc
     d.drop_key, d.drop_threshold, d.drop_scale = drop.key, drop.threshold, drop.scale
-    d.row_len = _ptr(row_len)
+    d.row_len = _addr(row_len) if row_len is not None else 0
     d.rows_per_b, d.rows_inner = rows_per_b, rows_inner
-    d.colsum_out = (_ptr(colsum_out) + 4 * colsum_off) if colsum_out is not None else 0
+    d.colsum_out = (_addr(colsum_out) + 4 * colsum_off) if colsum_out is not None else 0
     d.colsum_stride = colsum_stride
     keep = []
     if gather is not None:  # dict(nI, nJ, SI, SJ, C, si, sj, taps=[(di, dj), ...]): implicit-GEMM gather of the A operand
@@ -178,6 +184,17 @@ def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, *, transA=False, transB=False, in_dty
         r.nI, r.nJ, r.OI, r.OJ, r.si, r.sj, r.oi, r.oj = (rowmap[k] for k in ("nI", "nJ", "OI", "OJ", "si", "sj", "oi", "oj"))
         keep.append(r)
         d.rowmap = C.cast(C.pointer(r), C.c_void_p)
+    d.keep = keep
+    return d
+
+
+def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, **kw):
+    """C[M,N] = epi(A @ B^T) -- see mi355x_gemm; the keyword arguments are gemm_desc's.  A/B/Cm are tensors whose storage holds
+    the (strided) operands; *_off are element offsets into them (head / column slices).  splitk > 1 needs atomic=True and -- when
+    more than one K slice remains -- no bias and an epilogue that is linear in the sum (STORE, DSWISH, MUL_POS, DSWISH_G): every
+    slice runs the whole epilogue and adds its result."""
+    d = gemm_desc(A, B, Cm, M, N, K, lda, ldb, ldc, **kw)
+    transA, transB, batch = d.transA, d.transB, d.batch
     if GEMM_PROFILE is None:
         check(lib.mi355x_gemm(C.byref(d), _stream()), "gemm")
         return

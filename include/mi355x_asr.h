@@ -1295,6 +1295,37 @@ int mi355x_stream_attn(const void* q, long long ldq, const void* kv, long long l
 int mi355x_stream_dwconv(const void* x, const void* cache, const void* w, const void* bias, void* y, void* cache_next, int dtype,
                          int B, int Tq, int d, int ksize, void* stream);
 
+/* ---- linear adapters (parameter-efficient fine-tuning: ConformerEncoder.add_adapter, modules/adapter.py; csrc/adapter.hip).
+ * THE RULE, for LinearAdapter(in_features = d, dim, activation = 'swish', norm_position = 'pre', dropout = 0) and a row x of the
+ * residual stream (written from the reference's description, parity with its numbers is not claimed):
+ *     n = LayerNorm(x; gamma, beta, eps)      float32 statistics (two-pass mean / variance)
+ *     h = W_down . n                          W_down [dim, d], no bias
+ *     a = h * sigmoid(h)
+ *     y = x + W_up . a                        W_up [d, dim], no bias, zero-initialised
+ * Inside a Conformer layer x is the tensor norm_out reads (after the second feed-forward residual); several enabled adapters apply
+ * in the order they were added.  dtype = MI355X f32: every product is float32 (v_mfma_f32_16x16x4_f32).  dtype = bf16: n, a and the
+ * backward's dy and dh operands are rounded to bf16 (nearest even) and the weights are bf16 images; accumulation, LayerNorm, Swish
+ * and the residual add stay float32.  x, y, dy, dx are ALWAYS f32 rows [M, d] with a pitch (elements, % 4); gamma / beta f32 [d].
+ * Refused (MI_ERR_ARG, before any launch): a null or not 16-byte aligned array, d not a multiple of 8 (bf16) / 4 (f32), d > 1024,
+ * dim outside 8, 16, ... 128, a pitch below its row, a short workspace, an LDS need above 160 KB.  The LDS need is, per wave of 16
+ * rows, 16 * (d' + p) * e + 16 * (dim' + p) * e (+ 16 * dim' * 4 backward), e = bytes per weight element, d' / dim' = d / dim rounded
+ * up to 32 (bf16) / 16 (f32), p = 16 / e; a workgroup takes 4, 2 or 1 waves, whichever fits.  A lane keeps at most four 16-byte
+ * chunks of a row in registers, which is what limits d to 1024; at d = 1024, dim = 128 the backward in f32 needs 81 KB per wave, so
+ * every d <= 1024 with every dim <= 128 fits in both types (d = 1024, dim = 64, bf16: 4 waves, 138 KB forward, 154 KB backward).
+ * forward:  w_down [dim, ld_down], w_up [d, ld_up] in `dtype`; nothing is saved.
+ * backward: recomputes n, h, a from x; dx = dy + LN_bwd((dy . W_up * swish'(h)) . W_down); takes w_down, w_up_t = W_up^T
+ * [dim, ld_up_t] and w_down_t = W_down^T [d, ld_down_t]; ACCUMULATES (+=) into the contiguous f32 buffers d_w_down [dim, d],
+ * d_w_up [d, dim], dgamma [d], dbeta [d] from per-workgroup partials summed in index order: no atomics, two runs give the same bits.
+ * workspace: mi355x_adapter_workspace_bytes(M, d, dim, dtype) bytes (-1 for a refused geometry), contents need no initialisation. */
+long long mi355x_adapter_workspace_bytes(long long M, int d, int dim, int dtype);
+int mi355x_adapter_fwd(const void* x, long long ldx, const void* gamma, const void* beta, const void* w_down, long long ld_down,
+                       const void* w_up, long long ld_up, void* y, long long ldy, long long M, int d, int dim, int dtype, float eps,
+                       void* stream);
+int mi355x_adapter_bwd(const void* x, long long ldx, const void* dy, long long lddy, const void* gamma, const void* beta,
+                       const void* w_down, long long ld_down, const void* w_up_t, long long ld_up_t, const void* w_down_t,
+                       long long ld_down_t, void* dx, long long lddx, void* d_w_down, void* d_w_up, void* dgamma, void* dbeta,
+                       void* workspace, long long workspace_bytes, long long M, int d, int dim, int dtype, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -275,6 +275,13 @@ SIGNATURES = {
     "mi355x_stream_cache_assemble": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi355x_stream_attn": [vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "mi355x_stream_dwconv": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "mi355x_adapter_workspace_bytes": [i64, i32, i32, i32],
+    # (x, ldx, gamma, beta, w_down, ld_down, w_up, ld_up, y, ldy, M, d, dim, dtype, eps, stream)
+    "mi355x_adapter_fwd": [vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, f32, vp],
+    # (x, ldx, dy, lddy, gamma, beta, w_down, ld_down, w_up_t, ld_up_t, w_down_t, ld_down_t, dx, lddx, d_w_down, d_w_up, dgamma, dbeta,
+    #  workspace, workspace_bytes, M, d, dim, dtype, eps, stream)
+    "mi355x_adapter_bwd": [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32,
+                           f32, vp],
 }
 
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["mi355x_asr_version"])
@@ -299,6 +306,7 @@ def _load():
     lib.mi355x_ctc_beam_commit_workspace_elems.restype = i64
     lib.mi355x_transducer_beam_workspace_bytes.restype = i64
     lib.mi355x_transducer_align_workspace_bytes.restype = i64
+    lib.mi355x_adapter_workspace_bytes.restype = i64
     lib.mi355x_asr_version.argtypes = []
     lib.mi355x_tape_destroy.restype = None
     lib.mi355x_mailbox_destroy.restype = None

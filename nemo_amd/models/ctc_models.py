@@ -17,6 +17,7 @@ import torch
 from torch import nn
 
 from ..core import NeuralModule, Serialization, load_nemo, resolve_target, save_nemo
+from ..modules.adapter import AdapterModelMixin
 from ..modules import AudioToMelSpectrogramPreprocessor, ConformerEncoder, ConvASRDecoder, CTCLoss
 from ..optim import CosineAnnealing, FusedAdamW, NoamAnnealing, NoamHoldAnnealing
 from ..parallel import GradSync
@@ -230,7 +231,7 @@ def ctc_align_audio(model, audio, texts, batch_size=4, channel_selector=None):
     return out
 
 
-class EncDecCTCModel(nn.Module):
+class EncDecCTCModel(AdapterModelMixin, nn.Module):
     def __init__(self, cfg: Dict[str, Any], trainer=None):
         super().__init__()
         cfg = copy.deepcopy(dict(cfg))

@@ -25,6 +25,7 @@ from ..core import (AcousticEncodedRepresentation, BoolType, ChannelType, Length
                     typecheck)
 from ..packing import _pad8
 from . import engine
+from .adapter import AdapterHost
 from .engine import EngineModule
 
 INF_VAL = 10000.0
@@ -222,7 +223,7 @@ _AttSaved = _record("_AttSaved", "x y mean rstd qkv p core ctx d_att d_res")
 # conv module: x -> LayerNorm -> y -> pointwise_conv1 -> pw1 -> core (_ConvCore) -> z (rows of the chain: the packed copy under packed
 # rows) -> pointwise_conv2 -> dropout d_res -> + x
 _ConvSaved = _record("_ConvSaved", "x y mean rstd pw1 core z d_res")
-_LayerSaved = _record("_LayerSaved", "ff1 att conv ff2 out")   # (out: _LnSaved of norm_out, x = its input r4)
+_LayerSaved = _record("_LayerSaved", "ff1 att conv ff2 out ad")   # (out: _LnSaved of norm_out, x = its input r4 behind the adapters `ad`)
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -274,7 +275,7 @@ class _GraphSet:
         self.inherited = False  # the decision was taken over from another padded length of the same configuration (no trial)
 
 
-class ConformerEncoder(EngineModule):
+class ConformerEncoder(AdapterHost, EngineModule):
     @property
     def input_types(self):
         return OrderedDict({
@@ -605,6 +606,8 @@ class ConformerEncoder(EngineModule):
     def forward(self, audio_signal, length, cache_last_channel=None, cache_last_time=None, cache_last_channel_len=None,
                 bypass_pre_encode=False):
         if cache_last_channel is not None or cache_last_time is not None:
+            if self.get_enabled_adapters():   # (stream_step has its own layer loop, which applies no adapter)
+                raise NotImplementedError("cache_aware_stream_step with an adapter enabled: cache-aware streaming applies no adapter")
             if cache_last_channel is None or cache_last_time is None or cache_last_channel_len is None:
                 raise ValueError("cache-aware streaming needs cache_last_channel, cache_last_time and cache_last_channel_len")
             if bypass_pre_encode:
@@ -687,6 +690,8 @@ class ConformerEncoder(EngineModule):
                                 bypass_pre_encode=False):
         """one chunk of `processed_signal` [B, F, pre-encode cache + chunk] through the encoder with caches ->
         (outputs [B, D, T'], encoded_lengths, cache_last_channel_next, cache_last_time_next, cache_last_channel_next_len)"""
+        if self.get_enabled_adapters():
+            raise NotImplementedError("cache_aware_stream_step with an adapter enabled")
         if getattr(self, "streaming_cfg", None) is None:
             self.setup_streaming_params()
         if self.training:
@@ -794,6 +799,7 @@ class ConformerEncoder(EngineModule):
             c = L.conv
             p.add_matrix(f"L{i}.conv.pw1", c.pointwise_conv1.weight.data); p.add_matrix(f"L{i}.conv.pw1t", c.pointwise_conv1.weight.data, True)
             p.add_matrix(f"L{i}.conv.pw2", c.pointwise_conv2.weight.data); p.add_matrix(f"L{i}.conv.pw2t", c.pointwise_conv2.weight.data, True)
+        self._declare_adapter_images(p)
 
     # ------------------------------------------------------------------ replayable launch sequences (nemo_amd/graphs.py)
     def _eager_point(self, fn):
@@ -1792,6 +1798,7 @@ class ConformerEncoder(EngineModule):
         conv = _ConvSaved(r2, y3, mean3, rstd3, pw1, ccore, z, d_cres)
         # ---- macaron FFN 2 + output norm
         r4, ff2 = self._ffn_fwd(f"L{i}.ff2", L.feed_forward2, r3, L.norm_feed_forward2, S, W, drop, site + 5, M)
+        r4, ad = self._adapters_fwd(i, L, r4, W, M)   # (no adapter enabled: r4 itself and no launch)
         nxt = self.layers[i + 1] if i + 1 < self.n_layers else None
         if nxt is not None and d == 512 and self.fuse_layer_boundary_norms:
             # norm_out of this layer and norm_feed_forward1 of the next one in one pass over the rows (mi355x_layernorm2_fwd)
@@ -1803,7 +1810,7 @@ class ConformerEncoder(EngineModule):
             S.pre_ln = _PreNorm(yn, mean_n, rstd_n)
         else:
             xo, mean5, rstd5 = self._ln_fwd(L.norm_out, r4, M, d, torch.float32, dev)
-        return xo, _LayerSaved(ff1, att, conv, ff2, _LnSaved(r4, mean5, rstd5))
+        return xo, _LayerSaved(ff1, att, conv, ff2, _LnSaved(r4, mean5, rstd5), ad)
 
     @staticmethod
     def _dp_world():
@@ -2295,9 +2302,11 @@ class ConformerEncoder(EngineModule):
             # every LayerNorm backward also emits the bf16 (scaled, dropped) copy of the new residual gradient that the next
             # sub-block's output GEMMs consume -- one read of the fp32 gradient and one launch less per sub-block
             nc = (0.5, sl.ff2.d_res)
-            df2 = self._cast_buf(nc, M, d, cdt, dev)
+            df2 = self._cast_buf(nc, M, d, cdt, dev) if not sl.ad else None   # (behind adapters the operand is made from their dx)
             ops.layernorm_bwd(dxo, sl.out.x, ln.weight, sl.out.mean, sl.out.rstd, dr, False, ln.weight.grad, ln.bias.grad, M, d,
                               cast_out=df2, cast_scale=0.5, cast_drop=nc[1] if df2 is not None else None)
+        if sl.ad:   # through the adapters to the feed-forward block's own r4; its cast operand is made from the new gradient
+            dr, df2 = self._adapters_bwd(sl.ad, dr, W, M), None
         # ---- FFN 2
         cv = sl.conv
         dr, db = self._ffn_bwd(f"L{i}.ff2", L.feed_forward2, L.norm_feed_forward2, sl.ff2, dr, S, W, M, df=df2, next_cast=(1.0, cv.d_res))
@@ -2344,7 +2353,7 @@ class ConformerEncoder(EngineModule):
         lo = S.layers[i - 1] if i > 0 else None
         if lo is not None and d == 512 and self.fuse_layer_boundary_norms and self.fuse_boundary_bwd:
             dr, df2_lo = self._ffn_bwd(f"L{i}.ff1", L.feed_forward1, L.norm_feed_forward1, sl.ff1, dr, S, W, M, df=df1,
-                                       next_cast=(0.5, lo.ff2.d_res), boundary=(self.layers[i - 1].norm_out, lo.out))
+                                       next_cast=(0.5, lo.ff2.d_res) if not lo.ad else None, boundary=(self.layers[i - 1].norm_out, lo.out))
             S.pre_bwd = _PreBwd(dr, df2_lo)
             return dr
         dr, _ = self._ffn_bwd(f"L{i}.ff1", L.feed_forward1, L.norm_feed_forward1, sl.ff1, dr, S, W, M, df=df1)

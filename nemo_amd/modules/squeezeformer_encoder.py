@@ -133,6 +133,8 @@ _SqLayerSaved = _record("_SqLayerSaved", "att ff1 conv ff2")
 
 
 class SqueezeformerEncoder(ConformerEncoder):
+    adapters_supported = False   # (modules/adapter.py: only the Conformer layer has the adapter point)
+
     def __init__(self, feat_in: int, n_layers: int, d_model: int, feat_out: int = -1, subsampling: str = "dw_striding",
                  subsampling_factor: int = 4, subsampling_conv_channels: int = -1, ff_expansion_factor: int = 4,
                  self_attention_model: str = "rel_pos", n_heads: int = 4, att_context_size=None, xscaling: bool = True,

@@ -1642,3 +1642,29 @@ def stateless_greedy_decode(enc_proj, enc_len, tables, b_pred, w_out, ld_out, b_
         out += (nxt,)
     check(lib.mi355x_stateless_greedy_decode(C.byref(d), _stream()), "stateless_greedy_decode")
     return out
+
+
+# ---------------------------------------------------------------- linear adapters (csrc/adapter.hip; the rule: include/mi355x_asr.h)
+def adapter_workspace_bytes(M, d, dim, dtype) -> int:
+    n = lib.mi355x_adapter_workspace_bytes(M, d, dim, dt(dtype))
+    if n < 0:
+        raise ValueError(f"libmi355x_asr: adapter geometry M={M}, d={d}, dim={dim} is not supported")
+    return n
+
+
+def adapter_fwd(x, gamma, beta, w_down, w_up, y, M, d, dim, eps=1e-5, ldx=None, ldy=None, ld_down=None, ld_up=None):
+    """y [M, d] = x + W_up . swish(W_down . LayerNorm(x)); x, y f32 rows (pitch ldx / ldy), w_down [dim, d] and w_up [d, dim] in the
+    compute dtype (f32 masters or bf16 images, pitches ld_down / ld_up)"""
+    check(lib.mi355x_adapter_fwd(_ptr(x), ldx or d, _ptr(gamma), _ptr(beta), _ptr(w_down), ld_down or d, _ptr(w_up), ld_up or dim,
+                                 _ptr(y), ldy or d, M, d, dim, dt(w_down), eps, _stream()), "adapter_fwd")
+
+
+def adapter_bwd(x, dy, gamma, beta, w_down, w_up_t, w_down_t, dx, d_w_down, d_w_up, dgamma, dbeta, workspace, M, d, dim, eps=1e-5,
+                ldx=None, lddy=None, lddx=None, ld_down=None, ld_up_t=None, ld_down_t=None):
+    """backward of adapter_fwd from x and dy: dx written, the four f32 gradient buffers accumulated (+=); w_up_t [dim, d] and
+    w_down_t [d, dim] are the transposed matrices; `workspace`: adapter_workspace_bytes(...) bytes on the device"""
+    check(lib.mi355x_adapter_bwd(_ptr(x), ldx or d, _ptr(dy), lddy or d, _ptr(gamma), _ptr(beta), _ptr(w_down), ld_down or d,
+                                 _ptr(w_up_t), ld_up_t or d, _ptr(w_down_t), ld_down_t or dim, _ptr(dx), lddx or d, _ptr(d_w_down),
+                                 _ptr(d_w_up), _ptr(dgamma), _ptr(dbeta), _ptr(workspace),
+                                 workspace.numel() * workspace.element_size() if workspace is not None else 0, M, d, dim,
+                                 dt(w_down), eps, _stream()), "adapter_bwd")

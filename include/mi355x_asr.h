@@ -406,6 +406,38 @@ int mi355x_relpos_flash_bwd_dpos(const void* qv, const void* ds, const void* len
                                  void* partial, long long partial_elems, int B, int H, int T, int dk, long long ds_elems,
                                  const void* row_offsets, void* stream);
 
+/* WINDOWED fused rel-pos attention (csrc/attention_ctx.hip): the four kernels above for a LIMITED attention context
+ * (ConformerEncoder att_context_size = [left, right]; rel_pos_local_attn runs as the regular window [w, w]).  Query i sees key j iff
+ *   ctx_style 1 'regular':         -ctx_left <= j - i <= ctx_right, each side only if it is >= 0 (-1 = unlimited);
+ *   ctx_style 2 'chunked_limited': with ctx_right >= 0 and chunk = ctx_right + 1: 0 <= i / chunk - j / chunk <= ctx_left / chunk
+ *                                  (ctx_left < 0: every chunk to the left); with ctx_right < 0 the left-limited regular mask
+ * -- the rule of mi355x_relpos_softmax_fwd_ctx.  A key outside the window is treated exactly like a padded key; a valid query always
+ * sees itself.  Each workgroup walks only the 32-wide tiles its rows can reach, so work and traffic grow with T x window, and any T
+ * runs (the GEMM + softmax path stops at T = 1024).  Arguments, layouts, dropout (same key and (i, j) counter: the mask of the
+ * unlimited run restricted to the window) and outputs are those of the sibling without the suffix, minus row_offsets (padded rows
+ * only; no saved-probabilities form).  ds_out: of every query tile `it` only slots kt_lo .. kt_hi are written, [kt_lo, kt_hi) being the
+ * key tiles the 128-query workgroup of `it` reaches; mi355x_relpos_flash_bwd_dpos_ctx derives the same range from the same window
+ * and reads nothing else, so positions no window reaches receive += 0.
+ * MI_ERR_ARG before any launch: ctx_style outside 1..2 (style 0 belongs to the entries above), ctx_left or ctx_right < -1, dk not
+ * 64 / 128, and the pointer, pitch and alignment conditions of the siblings. */
+int mi355x_relpos_flash_fwd_ctx(const void* qkv, long long ldq, const void* pos, long long ldp, const void* bias_u,
+                                const void* bias_v, const void* len, void* ctx, void* ctx_lo, long long ldo, void* lse, int B, int H,
+                                int T, int dk, int Tp, float scale, unsigned drop_key, unsigned drop_threshold, float drop_scale,
+                                int ctx_style, int ctx_left, int ctx_right, void* stream);
+int mi355x_relpos_flash_bwd_dq_ctx(const void* qu, const void* qv, const void* qkv, long long ldq, const void* pos, long long ldp,
+                                   const void* len, const void* dO, const void* lse, const void* delta, void* dqu, void* dqv,
+                                   void* ds_out, void* dq_out, long long ld_dq, void* bias_grads, void* cs_scratch,
+                                   long long cs_scratch_elems, int B, int H, int T, int dk, long long ds_elems, float scale,
+                                   unsigned drop_key, unsigned drop_threshold, float drop_scale, int ctx_style, int ctx_left,
+                                   int ctx_right, void* stream);
+int mi355x_relpos_flash_bwd_dkv_ctx(const void* qu, const void* qv, const void* qkv, long long ldq, const void* pos, long long ldp,
+                                    const void* len, const void* dO, const void* lse, const void* delta, void* dqkv, long long ldd,
+                                    int B, int H, int T, int dk, int Tp, float scale, unsigned drop_key, unsigned drop_threshold,
+                                    float drop_scale, int ctx_style, int ctx_left, int ctx_right, void* stream);
+int mi355x_relpos_flash_bwd_dpos_ctx(const void* qv, const void* ds, const void* len, void* dpos, long long ldd, void* dpos_cast,
+                                     void* partial, long long partial_elems, int B, int H, int T, int dk, long long ds_elems,
+                                     int ctx_style, int ctx_left, int ctx_right, void* stream);
+
 /* which depthwise-convolution kernels run (tests and A/B): 0 = the LDS-tile kernels (default: faster inside the training step),
  * 1 = the streaming kernel in the forward pass (bf16, k = 31, even d), 2 = in the backward pass too; level < 0 only queries.
  * Returns the previous level.

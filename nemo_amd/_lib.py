@@ -196,6 +196,13 @@ SIGNATURES = {
                                    f32, u32, u32, f32, vp, vp],
     "mi355x_relpos_flash_bwd_dkv": [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, u32, u32, f32, vp, vp],
     "mi355x_relpos_flash_bwd_dpos": [vp, vp, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, i64, vp, vp],
+    "mi355x_relpos_flash_fwd_ctx": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, f32, u32, u32, f32, i32, i32,
+                                    i32, vp],
+    "mi355x_relpos_flash_bwd_dq_ctx": [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32,
+                                       i64, f32, u32, u32, f32, i32, i32, i32, vp],
+    "mi355x_relpos_flash_bwd_dkv_ctx": [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, u32, u32, f32,
+                                        i32, i32, i32, vp],
+    "mi355x_relpos_flash_bwd_dpos_ctx": [vp, vp, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, i64, i32, i32, i32, vp],
     "mi355x_relpos_ds_elems": [i32, i32, i32],
     "mi355x_relpos_probs_elems": [i32, i32, i32],
     "mi355x_relpos_mref_elems": [i32, i32, i32],

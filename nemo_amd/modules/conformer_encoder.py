@@ -204,6 +204,7 @@ class _AttnCore(NamedTuple):
     lse: Any = None      # log-sum-exp [B, H, T]
     probs: Any = None    # fused path, flash_save_probs: the forward's un-normalised probabilities (bf16 blocks) and the
     mref: Any = None     # reference points they were taken against -- the backward kernels scale them instead of recomputing
+    win: Any = None      # windowed fused path: the (style, left, right) of the forward -- the backward runs the same window
 
 
 class _ConvCore(NamedTuple):
@@ -411,6 +412,10 @@ class ConformerEncoder(AdapterHost, EngineModule):
         self.syncbn_profile = None  # a list while bench.py measures the exposed time of the statistics exchanges
         self.use_flash_attention = True  # bf16 + (padded) d_k == 64: fused kernels; otherwise the GEMM + softmax-kernel path
         self.flash_pad_heads = os.environ.get("MI355X_FLASH_PAD_HEADS", "1") != "0"  # d_k < 64 -> heads zero-padded to 64 (_geometry)
+        # limited / local attention context on the windowed fused kernels (csrc/attention_ctx.hip).  None: only where the GEMM +
+        # softmax path cannot run (T' > 1024); True: whenever the compute dtype is bf16 and the (padded) head width is 64 / 128;
+        # False: never.  See _attn_path.
+        self.use_flash_ctx_attention = None
         # PACKED ROWS ("length-aware kernels skipping padded frames"): the row-wise chain of the layers -- LayerNorms,
         # feed-forward / projection / pointwise-conv GEMMs, residuals, every weight gradient -- runs on the sum_b L_b valid frames
         # of a ragged batch instead of on B * T'_max rows; the fused attention addresses utterance b at row_offsets[b]; only the
@@ -592,6 +597,30 @@ class ConformerEncoder(AdapterHost, EngineModule):
 
     def _flash_ok(self):
         return self.use_flash_attention and not self._ctx_limited_any()
+
+    def _flash_heads(self):
+        """are the heads laid out for fused kernels (zero-padded to 64 / 128 lanes, flash_pad_heads)?  The unlimited context, and a
+        limited one that is always sent to the windowed kernels; with use_flash_ctx_attention = None the geometry stays that of
+        the GEMM + softmax path, which serves every T' <= 1024."""
+        return self._flash_ok() or (self.use_flash_ctx_attention is True and self._ctx_limited_any())
+
+    def _attn_path(self, T, cdt, dk):
+        """which attention core runs at T encoder frames, compute dtype cdt and (padded) head width dk: "flash" (unlimited context,
+        csrc/attention.hip), "flash_ctx" (the forward's limited context self._ctx on the windowed kernels, csrc/attention_ctx.hip)
+        or "gemm" (qbias, batched GEMMs and the soft-max kernel, which keeps a row in registers and stops at 1024 frames)."""
+        fusable = cdt == torch.bfloat16 and dk in (64, 128)
+        if self._flash_ok() and fusable:
+            return "flash"
+        if self._ctx[0] != 0 and fusable and (self.use_flash_ctx_attention is True or
+                                              (self.use_flash_ctx_attention is None and T > 1024)):
+            return "flash_ctx"
+        if T > 1024:
+            raise ValueError(
+                f"attention over {T} encoder frames (> 1024) runs on the fused kernels only: they need compute_dtype=torch.bfloat16 "
+                f"and a head width of 64 or 128 (got {cdt}, head width {dk}; use_flash_attention={self.use_flash_attention}, "
+                f"use_flash_ctx_attention={self.use_flash_ctx_attention}, context {list(self._ctx[1:])}; with a limited context "
+                "use_flash_ctx_attention=True pads narrower heads)")
+        return "gemm"
 
     def _pick_ctx(self):
         import random
@@ -819,7 +848,7 @@ class ConformerEncoder(AdapterHost, EngineModule):
                 self.grad_ready_hook is not None, self._wgrad_join_per_layer, self.wgrad_side_stream, self.wgrad_grouped,
                 self.dpos_side_stream, self.sub_wgrad_side_stream, self.conv2_implicit, self.ln_cast_fuse, self.fuse_bn_dwconv_bwd, self.fuse_glu_dwconv_bwd, self.fuse_glu_dwconv_fwd, self.tap_reduce_side, self.pad_tile_skip,
                 self.use_flash_attention, self.flash_delta_residual, self.flash_save_probs, self.syncbn_profile is not None, self.graph_tape, self.swish_g, self.dropout, self.dropout_att, self.dropout_emb, self.dropout_pre_encoder,
-                self.wgrad_defer, self.graph_bwd_live, self.posproj_side, self.wgrad_layers, self._ctx)
+                self.wgrad_defer, self.graph_bwd_live, self.posproj_side, self.wgrad_layers, self._ctx, self.use_flash_ctx_attention)
 
     def _auto_begin(self, gs, mode):
         e0 = torch.cuda.Event(enable_timing=True)
@@ -1498,9 +1527,9 @@ class ConformerEncoder(AdapterHost, EngineModule):
         linear_pos rows, linear_out columns, pos_bias lanes); activations outside the attention block keep width d."""
         dk = self.d_k
         dkp = _pad8(dk) if cdt == torch.bfloat16 else dk
-        if cdt == torch.bfloat16 and self._flash_ok() and self.flash_pad_heads and 64 < dkp < 128:
+        if cdt == torch.bfloat16 and self._flash_heads() and self.flash_pad_heads and 64 < dkp < 128:
             dkp = 128   # ... and heads of 65..127 lanes to the kernels' second width (d_k' = 128: 8 k-steps, one workgroup per CU)
-        if cdt == torch.bfloat16 and self._flash_ok() and self.flash_pad_heads and dkp < 64:
+        if cdt == torch.bfloat16 and self._flash_heads() and self.flash_pad_heads and dkp < 64:
             # round 5: heads narrower than the fused kernels' width (Conformer-Small: 44) are padded up to 64 instead of to the
             # next multiple of 8, so that they take the fused rel-pos attention (csrc/attention.hip, d_k' = 64) instead of
             # materialising the [H, B, T', T'] scores and the [H, B, T', 2T'-1] positional matrix in HBM
@@ -1571,9 +1600,10 @@ class ConformerEncoder(AdapterHost, EngineModule):
         H, cdt, dev, scale = self.n_heads, S.cdt, qkv.device, 1.0 / math.sqrt(self.d_k)
         M, P = B * T, 2 * T - 1
         Tp, Pp = _pad8(T), _pad8(P)
-        flash = self._flash_ok() and cdt == torch.bfloat16 and dk in (64, 128)
+        path = self._attn_path(T, cdt, dk)
+        flash = path == "flash"
         cu = pk.cu if pk is not None else None
-        if pk is not None and not flash:
+        if pk is not None and not flash:   # (the windowed kernels too: padded rows only)
             qkv_p = self._new(M, 3 * dA, dtype=cdt, device=dev)
             ops.rows_unpack(qkv, qkv_p, lens, cu, T, M, 3 * dA)
             ctx_p, saved = self._attn_fwd(S, qkv_p, p, bias_u, bias_v, lens, B, T, dA, dk, d_att)
@@ -1598,6 +1628,13 @@ class ConformerEncoder(AdapterHost, EngineModule):
             ops.relpos_flash_fwd(qkv, 3 * dA, p, dA, bias_u, bias_v, lens, ctx, dA, lse, B, H, T, dk, Tp, scale, d_att,
                                  ctx_lo=ctx_lo, cu=cu)
             return ctx, _AttnCore(ctx_lo=ctx_lo, lse=lse)
+        if path == "flash_ctx":
+            # limited context on the windowed fused kernels: only the key tiles inside the window are visited
+            lse = self._new(B, H, T, dtype=torch.float32, device=dev)
+            ctx_lo = self._new(M, dA, dtype=cdt, device=dev) if (self._saving and self.flash_delta_residual) else None
+            ops.relpos_flash_fwd(qkv, 3 * dA, p, dA, bias_u, bias_v, lens, ctx, dA, lse, B, H, T, dk, Tp, scale, d_att,
+                                 ctx_lo=ctx_lo, ctx=self._ctx)
+            return ctx, _AttnCore(ctx_lo=ctx_lo, lse=lse, win=self._ctx)
         qu = self._new(M, dA, dtype=cdt, device=dev)
         qv = self._new(M, dA, dtype=cdt, device=dev)
         ops.qbias(qkv, 3 * dA, bias_u, bias_v, qu, qv, M, dA)
@@ -1624,21 +1661,29 @@ class ConformerEncoder(AdapterHost, EngineModule):
         dp_cast (compute dtype) = its GEMM-operand copy for the linear_pos weight gradient.  `bias_grads` (fused path only):
         f32 [2 * dA] = pos_bias_u.grad | pos_bias_v.grad in one piece -- then the dQ kernel writes dq = dqu + dqv into the q third
         of dqkv and the bias gradients itself, and (dqkv, None, None) comes back."""
-        qu, qv, s_, pd, lse = saved.qu, saved.qv, saved.s, saved.pd, saved.lse
+        qu, qv, s_, pd, lse, win = saved.qu, saved.qv, saved.s, saved.pd, saved.lse, saved.win
         H, cdt, dev, scale = self.n_heads, S.cdt, qkv.device, 1.0 / math.sqrt(self.d_k)
         M, P = B * T, 2 * T - 1
         Tp, Pp = _pad8(T), _pad8(P)
         cu = pk.cu if pk is not None else None
-        if pk is not None and lse is None:
+        if pk is not None and (lse is None or win is not None):
             # packed rows, un-fused path (fp32 / other head widths): the batched GEMMs stride over a padded grid -- run them on padded
             # copies and hand the valid rows back
             qkv_p = self._new(M, 3 * dA, dtype=cdt, device=dev)
             dctx_p = self._new(M, dA, dtype=cdt, device=dev)
             ops.rows_unpack(qkv, qkv_p, lens, cu, T, M, 3 * dA)
             ops.rows_unpack(dctx, dctx_p, lens, cu, T, M, dA)
-            dqkv_p, dqu_p, dqv_p = self._attn_bwd(S, saved, qkv_p, p, bias_u, bias_v, None, dctx_p, lens, B, T, dA, dk, d_att, dp, dp_cast)
+            ctx_p = None
+            if win is not None:   # the windowed kernels' delta = sum dO * O reads the context rows
+                ctx_p = self._new(M, dA, dtype=cdt, device=dev)
+                ops.rows_unpack(ctx, ctx_p, lens, cu, T, M, dA)
+            dqkv_p, dqu_p, dqv_p = self._attn_bwd(S, saved, qkv_p, p, bias_u, bias_v, ctx_p, dctx_p, lens, B, T, dA, dk, d_att, dp,
+                                                  dp_cast, bias_grads=bias_grads if win is not None else None)
             out = []
             for t_p, w in ((dqkv_p, 3 * dA), (dqu_p, dA), (dqv_p, dA)):
+                if t_p is None:   # (fused dQ epilogue: dq is in dqkv, the bias gradients are written)
+                    out.append(None)
+                    continue
                 t = self._new(pk.Mp, w, dtype=cdt, device=dev)
                 ops.rows_pack(t_p, t, lens, cu, T, M, w)
                 out.append(t)
@@ -1671,17 +1716,18 @@ class ConformerEncoder(AdapterHost, EngineModule):
                                           ds_out=dS, dq_out=dqkv if fuse_dq else None, ld_dq=3 * dA, bias_grads=bias_grads)
             else:
                 ops.relpos_flash_bwd_dq(qu, qv, qkv, 3 * dA, p, dA, lens, dctx, lse, dlt, dqu, dqv, B, H, T, dk, scale, d_att,
-                                        ds_out=dS, dq_out=dqkv if fuse_dq else None, ld_dq=3 * dA, bias_grads=bias_grads, cu=cu)
+                                        ds_out=dS, dq_out=dqkv if fuse_dq else None, ld_dq=3 * dA, bias_grads=bias_grads, cu=cu,
+                                        ctx=win)
             if side_pos:
                 with self._wgrad_scope(qv, dS):
-                    ops.relpos_flash_bwd_dpos(qv, dS, lens, dp, B, H, T, dk, dpos_cast=dp_cast, cu=cu)
+                    ops.relpos_flash_bwd_dpos(qv, dS, lens, dp, B, H, T, dk, dpos_cast=dp_cast, cu=cu, ctx=win)
             if probs is not None:
                 ops.relpos_flash_bwd_dkv_p(probs, mref, qu, qkv, 3 * dA, lens, dctx, lse, dlt, dqkv, 3 * dA, B, H, T, dk, scale, d_att)
             else:
                 ops.relpos_flash_bwd_dkv(qu, qv, qkv, 3 * dA, p, dA, lens, dctx, lse, dlt, dqkv, 3 * dA, B, H, T, dk, Tp, scale,
-                                         d_att, cu=cu)
+                                         d_att, cu=cu, ctx=win)
             if not side_pos:
-                ops.relpos_flash_bwd_dpos(qv, dS, lens, dp, B, H, T, dk, dpos_cast=dp_cast, cu=cu)
+                ops.relpos_flash_bwd_dpos(qv, dS, lens, dp, B, H, T, dk, dpos_cast=dp_cast, cu=cu, ctx=win)
             return dqkv, dqu, dqv
         # dpd[h,b] = dctx_bh @ v_bh^T  -> reuse the f32 score workspace
         dpd = self._buf("ac", (H, B, T, Tp), torch.float32, dev)

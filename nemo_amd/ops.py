@@ -785,11 +785,24 @@ def relpos_softmax_bwd(dpd, s_in, dscore, dbdf, H, B, T, Tp, Pp, scale, drop: Dr
                                         scale, drop.key, drop.threshold, drop.scale, _stream()), "relpos_softmax_bwd")
 
 
-def relpos_flash_fwd(qkv, ldq, pos, ldp, bias_u, bias_v, lens, ctx, ldo, lse, B, H, T, dk, Tp, scale, drop: Dropout = NO_DROP,
-                     ctx_lo=None, cu=None):
+def _no_cu(cu):
+    if cu is not None:
+        raise ValueError("the windowed attention kernels (ctx=...) take padded rows only: cu must be None")
+
+
+def relpos_flash_fwd(qkv, ldq, pos, ldp, bias_u, bias_v, lens, out, ldo, lse, B, H, T, dk, Tp, scale, drop: Dropout = NO_DROP,
+                     ctx_lo=None, cu=None, *, ctx=None):
     """cu (i64 [B+1]): "packed rows" -- the activation matrices hold the valid frames only (include/mi355x_asr.h); the same
-    argument on every fused attention call below"""
-    check(lib.mi355x_relpos_flash_fwd(_ptr(qkv), ldq, _ptr(pos), ldp, _ptr(bias_u), _ptr(bias_v), _ptr(lens), _ptr(ctx),
+    argument on every fused attention call below.  ctx = (style, left, right): a limited attention context (style 1 'regular' /
+    2 'chunked_limited') -- the windowed kernels of csrc/attention_ctx.hip, padded rows only; the same keyword on the three
+    backward calls"""
+    if ctx is not None:
+        _no_cu(cu)
+        check(lib.mi355x_relpos_flash_fwd_ctx(_ptr(qkv), ldq, _ptr(pos), ldp, _ptr(bias_u), _ptr(bias_v), _ptr(lens), _ptr(out),
+                                              _ptr(ctx_lo), ldo, _ptr(lse), B, H, T, dk, Tp, scale, drop.key, drop.threshold,
+                                              drop.scale, int(ctx[0]), int(ctx[1]), int(ctx[2]), _stream()), "relpos_flash_fwd_ctx")
+        return
+    check(lib.mi355x_relpos_flash_fwd(_ptr(qkv), ldq, _ptr(pos), ldp, _ptr(bias_u), _ptr(bias_v), _ptr(lens), _ptr(out),
                                       _ptr(ctx_lo), ldo, _ptr(lse), B, H, T, dk, Tp, scale, drop.key, drop.threshold, drop.scale,
                                       _ptr(cu), _stream()), "relpos_flash_fwd")
 
@@ -814,13 +827,22 @@ def relpos_ds_buffer(B, H, T, device, fill=None):
 
 
 def relpos_flash_bwd_dq(qu, qv, qkv, ldq, pos, ldp, lens, dO, lse, delta, dqu, dqv, B, H, T, dk, scale,
-                        drop: Dropout = NO_DROP, ds_out=None, dq_out=None, ld_dq=0, bias_grads=None, cu=None):
+                        drop: Dropout = NO_DROP, ds_out=None, dq_out=None, ld_dq=0, bias_grads=None, cu=None, *, ctx=None):
     """dqu / dqv: the two gradients separately (may both be None when `dq_out` is given); dq_out: their sum as rows of pitch
     ld_dq; bias_grads f32 [2 * H * dk] += column sums of dQu | dQv (pos_bias_u | pos_bias_v gradients)"""
     sc, n = None, 0
     if bias_grads is not None:
         n = B * ((T + 127) // 128) * 2 * H * dk
         sc = _scratch("relpos_flash_bwd_dq", n, qu.device)
+    if ctx is not None:
+        _no_cu(cu)
+        check(lib.mi355x_relpos_flash_bwd_dq_ctx(_ptr(qu), _ptr(qv), _ptr(qkv), ldq, _ptr(pos), ldp, _ptr(lens), _ptr(dO), _ptr(lse),
+                                                 _ptr(delta), _ptr(dqu), _ptr(dqv), _ptr(ds_out), _ptr(dq_out), ld_dq,
+                                                 _ptr(bias_grads), _ptr(sc), n, B, H, T, dk,
+                                                 0 if ds_out is None else ds_out.numel(), scale, drop.key, drop.threshold,
+                                                 drop.scale, int(ctx[0]), int(ctx[1]), int(ctx[2]), _stream()),
+              "relpos_flash_bwd_dq_ctx")
+        return
     check(lib.mi355x_relpos_flash_bwd_dq(_ptr(qu), _ptr(qv), _ptr(qkv), ldq, _ptr(pos), ldp, _ptr(lens), _ptr(dO), _ptr(lse),
                                          _ptr(delta), _ptr(dqu), _ptr(dqv), _ptr(ds_out), _ptr(dq_out), ld_dq, _ptr(bias_grads),
                                          _ptr(sc), n, B, H, T, dk, 0 if ds_out is None else ds_out.numel(), scale, drop.key,
@@ -828,7 +850,14 @@ def relpos_flash_bwd_dq(qu, qv, qkv, ldq, pos, ldp, lens, dO, lse, delta, dqu, d
 
 
 def relpos_flash_bwd_dkv(qu, qv, qkv, ldq, pos, ldp, lens, dO, lse, delta, dqkv, ldd, B, H, T, dk, Tp, scale,
-                         drop: Dropout = NO_DROP, cu=None):
+                         drop: Dropout = NO_DROP, cu=None, *, ctx=None):
+    if ctx is not None:
+        _no_cu(cu)
+        check(lib.mi355x_relpos_flash_bwd_dkv_ctx(_ptr(qu), _ptr(qv), _ptr(qkv), ldq, _ptr(pos), ldp, _ptr(lens), _ptr(dO),
+                                                  _ptr(lse), _ptr(delta), _ptr(dqkv), ldd, B, H, T, dk, Tp, scale, drop.key,
+                                                  drop.threshold, drop.scale, int(ctx[0]), int(ctx[1]), int(ctx[2]), _stream()),
+              "relpos_flash_bwd_dkv_ctx")
+        return
     check(lib.mi355x_relpos_flash_bwd_dkv(_ptr(qu), _ptr(qv), _ptr(qkv), ldq, _ptr(pos), ldp, _ptr(lens), _ptr(dO), _ptr(lse),
                                           _ptr(delta), _ptr(dqkv), ldd, B, H, T, dk, Tp, scale, drop.key, drop.threshold,
                                           drop.scale, _ptr(cu), _stream()), "relpos_flash_bwd_dkv")
@@ -864,10 +893,16 @@ def relpos_flash_bwd_dkv_p(probs, mref, qu, qkv, ldq, lens, dO, lse, delta, dqkv
                                             drop.key, drop.threshold, drop.scale, None, _stream()), "relpos_flash_bwd_dkv_p")
 
 
-def relpos_flash_bwd_dpos(qv, ds, lens, dpos, B, H, T, dk, dpos_cast=None, cu=None):
+def relpos_flash_bwd_dpos(qv, ds, lens, dpos, B, H, T, dk, dpos_cast=None, cu=None, *, ctx=None):
     """`dpos_cast` (bf16, shape of dpos): the GEMM-operand copy of the updated gradient, written by the reduction stage"""
     n = lib.mi355x_relpos_dpos_partial_elems(B, H, T)
     scratch = _scratch("relpos_flash_bwd_dpos", n, dpos.device)
+    if ctx is not None:
+        _no_cu(cu)
+        check(lib.mi355x_relpos_flash_bwd_dpos_ctx(_ptr(qv), _ptr(ds), _ptr(lens), _ptr(dpos), dpos.shape[-1], _ptr(dpos_cast),
+                                                   _ptr(scratch), n, B, H, T, dk, ds.numel(), int(ctx[0]), int(ctx[1]), int(ctx[2]),
+                                                   _stream()), "relpos_flash_bwd_dpos_ctx")
+        return
     check(lib.mi355x_relpos_flash_bwd_dpos(_ptr(qv), _ptr(ds), _ptr(lens), _ptr(dpos), dpos.shape[-1], _ptr(dpos_cast),
                                            _ptr(scratch), n, B, H, T, dk, ds.numel(), _ptr(cu), _stream()), "relpos_flash_bwd_dpos")
 

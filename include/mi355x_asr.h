@@ -1241,6 +1241,32 @@ typedef struct mi355x_transducer_beam_desc {
 long long mi355x_transducer_beam_workspace_bytes(int B, int T, int H, int J, int beam, int max_out);
 int mi355x_transducer_beam_decode(const mi355x_transducer_beam_desc* d, void* stream);
 
+/* ---- the beam search above with shallow fusion of ONE token-level n-gram model (the back-off automaton of mi355x_ctc_beam_fusion,
+ * six tables, state_final NULL, over the labels 0 .. V1-2, so blank == V1-1).  THE RULE is the one of mi355x_transducer_beam_decode
+ * with one change in step 2 and one more field per hypothesis: its automaton state s.  Start: s = 1, the state behind <s>, as the
+ * CTC search starts.  For a live hypothesis with t < len every LABEL candidate v != blank is scored with
+ *     lpf[v] = lp[v] + alpha * lm(s, v)                  RNN-T: score + lpf[v]         TDT: score + (lpf[v] + ld[i])
+ * float32, in that association, the product rounded before it is added; lm(s, v) is the float32 value of the look-up of
+ * mi355x_ctc_beam_decode_lm: the back-off weights of the chain s, state_bo_next[s], .. summed in chain order from 0 until a state has
+ * an arc for v, then that arc's log-probability added.  Blank candidates and finished hypotheses get no term: the model never
+ * scores a blank.  A label-extended hypothesis takes the state behind the arc, next(s, v); a blank-extended or finished one keeps
+ * its state.  `score` is the one running sum, acoustic and LM terms together; selection, ties, merging and the final order are
+ * those of the plain rule on that sum.  Merged hypotheses have equal token sequences, hence equal states; their logaddexp is over
+ * the sums (the LM parts of two equal sequences differ only by float32 rounding: the same terms were added at different points of
+ * two running sums).  No </s> term, no length normalisation.  Parity with the reference's fused numbers is not claimed.
+ * With alpha == 0 and finite tables every output is BIT-EQUAL to mi355x_transducer_beam_decode's.
+ * The kernel builds the term row-wise: per hypothesis the chain is walked once, the arcs of each state 64 at a time, a bit per
+ * label marking what a longer context already gave; state 0 finishes the rest.  That holds for chains of up to 6 states before
+ * state 0 (models of order <= 7); a longer chain takes the look-up per label, with the same value.  Every chase is bounded and
+ * every index clamped as in the CTC search: tables that break the rules give a wrong score, never a hang or a read out of bounds.
+ * `ub` is not read.  The workspace is the plain search's (mi355x_transducer_beam_workspace_bytes).
+ * MI_ERR_ARG, before anything is launched: everything mi355x_transducer_beam_decode refuses; n_models != 1 or a null `models`; a
+ * null table; a non-null state_final (boosting trees are not taken); n_states < 2; n_arcs < V1-1; blank != V1-1; alpha negative,
+ * NaN or infinite; an LDS need above 152 KiB, where the [16, V1 + D] logits are followed by 16 masks of ceil(V1 / 32) words.
+ * mi355x_transducer_beam_decode launches the code it always has: the model is a template flag of the kernel. */
+int mi355x_transducer_beam_decode_fused(const mi355x_transducer_beam_desc* d, const mi355x_ctc_beam_fusion* models, int n_models,
+                                        void* stream);
+
 /* ---- the stateless prediction network (`StatelessTransducerDecoder` / `StatelessNet`): training forward and backward, the
  * prediction tables of the search and the greedy search (csrc/stateless.hip).  The StatelessNet rule below was written from memory
  * of the reference, which was not at hand: parity with the reference's numbers is not claimed.  THE RULE is the contract.

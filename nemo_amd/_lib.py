@@ -243,6 +243,8 @@ SIGNATURES = {
     "mi355x_transducer_greedy_decode_layers": [C.POINTER(TransducerGreedyDesc), C.POINTER(TransducerLstmLayers), vp],
     "mi355x_transducer_beam_decode": [C.POINTER(TransducerBeamDesc), vp],
     "mi355x_transducer_beam_workspace_bytes": [i32, i32, i32, i32, i32, i32],
+    # (desc, models: mi355x_ctc_beam_fusion[n_models], n_models, stream)
+    "mi355x_transducer_beam_decode_fused": [C.POINTER(TransducerBeamDesc), vp, i32, vp],
     # (targets, emb / demb: host array of C device pointers, ...)
     "mi355x_stateless_pred_fwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, u32, u32, f32, vp],
     "mi355x_stateless_embed_bwd": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, u32, u32, f32, vp],

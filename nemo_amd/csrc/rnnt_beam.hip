@@ -21,9 +21,13 @@
 //   * selection: each wave finds the W best candidates of the rows it owns (W rounds of "best key behind the last one": a strict
 //     total order, so no taken-flags and no sort), wave 0 merges the sorted lists by their heads, a lane per row;
 //   * prefix tree: (parent, token, frame) nodes in the workspace, node 1 + step * W + slot; a lane per hypothesis confirms a hash
-//     match by walking both sequences, and chases its hypothesis out at the end.
-// Ordinary vector stores only, no scratch.
+//     match by walking both sequences, and chases its hypothesis out at the end;
+//   * n-gram LM fusion (mi355x_transducer_beam_decode_fused; the LM instantiations): the wave that owns a row adds the model's
+//     term to the row's label log-probabilities in place, one walk down the back-off chain per row (rb_lm_row), with a bit mask
+//     per row behind the logits; the automaton state travels with the per-slot scalars.
+// Ordinary vector stores and vector LDS atomics only, no scratch.
 #include "common.h"
+#include "ctc_beam_fusion.h"
 #include "mi355x_asr.h"
 #include "rnnt_mma.h"
 #include "tdt.h"
@@ -32,6 +36,9 @@
 #define RB_WAVES 8
 #define RB_M 16        // rows of the MFMA tile = the widest beam
 #define RB_NONE 0x7fffffff
+#define RB_LM_CHAIN 6  // the fused search walks a back-off chain of up to 6 states before state 0 row-wise (an n-gram model of order
+                       // N has chains of at most N - 1: orders up to 7, and files are built with 3 to 6); a longer chain takes
+                       // the per-label look-up
 
 struct RbP {
   const void* f; int f_dt; long long ldf;   // encoder projection [B, T, J] (rows of pitch ldf)
@@ -44,6 +51,7 @@ struct RbP {
   char* ws; long long ws_per_b;              // workspace and its bytes per utterance
   int B, T, J, H, V1, blank, max_symbols, max_out, W;
   TdtDur dur;                                // TDT: duration set (dur.D = 0: RNN-T)
+  ctc_beam_lm lm;                            // the fused search's model (read by the LM instantiations only)
 };
 
 // bytes of workspace per utterance: two halves of W state rows (h [H], c [H], gp [J], float32), then the prefix tree of
@@ -54,7 +62,57 @@ static inline long long rb_ws_per_b(int T, int H, int J, int W, int max_out) {
   return (bytes + 15) & ~15LL;
 }
 
-template <typename WT, bool TDT>
+// lg[0 .. V1-1) += alpha * lm(s, v) for one row, by the wave that owns the row (mi355x_transducer_beam_decode_fused).  The value of
+// label v is the look-up's: the back-off weights of the chain s_0 = s, s_1 = bo_next[s_0], .. summed in chain order until a state
+// has an arc for v, then that arc's log-probability.  A look-up per (row, label) is V1 x depth binary searches of dependent loads;
+// here the chain is walked ONCE per row from s down to state 0, the lanes take the arcs of a state 64 at a time (arc_tok / arc_logp
+// coalesced), add the term in place into the row's log-probabilities and mark the label in the row's bit mask (LDS atomic-or: the
+// returned word says whether a longer context had the label already, which also keeps a table with a repeated arc to one term per
+// label); state 0 is dense (arc index = label) and finishes every label no longer context had.  Cost: V1 + the arcs on the chain.
+// The chain is wave-uniform, so its loads are scalar.  Every index is clamped as ctc_beam_lm_lookup clamps it; a chain that does not
+// reach state 0 within RB_LM_CHAIN states (a model of order > 7, or a table that breaks the rules) takes the look-up per label.
+// The blank (V1 - 1) is never touched.  `msk`: (V1 + 31) / 32 words of this row.
+__device__ __forceinline__ void rb_lm_row(const ctc_beam_lm& lm, int s0, float* lg, unsigned* msk, int V1, int lane) {
+  const int L = V1 - 1;
+  s0 = __builtin_amdgcn_readfirstlane(min(max(s0, 0), lm.n_states - 1));
+  int depth = 0;
+  for (int s = s0; s != 0 && depth <= RB_LM_CHAIN; ++depth) s = __builtin_amdgcn_readfirstlane(min(max(lm.bo_next[s], 0), lm.n_states - 1));
+  if (depth > RB_LM_CHAIN) {   // (uniform)
+    for (int v = lane; v < L; v += 64) {
+      int nx;
+      lg[v] += ctc_beam_alpha_lm(lm.alpha, ctc_beam_lm_lookup(lm, s0, v, nx));
+    }
+    return;
+  }
+  for (int i = lane; i * 32 < V1; i += 64) msk[i] = 0u;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  float acc = 0.f;
+  int s = s0;
+  for (int j = 0; j < depth; ++j) {   // the states before state 0, the longest context first
+    const int lo = __builtin_amdgcn_readfirstlane(min(max(lm.arc_begin[s], 0), lm.n_arcs));
+    const int end = __builtin_amdgcn_readfirstlane(min(max(lm.arc_begin[s + 1], lo), lm.n_arcs));
+    for (int a = lo + lane; a < end; a += 64) {
+      const int tok = lm.arc_tok[a];
+      if (tok < 0 || tok >= L) continue;
+      const unsigned bit = 1u << (tok & 31);
+      if (atomicOr(&msk[tok >> 5], bit) & bit) continue;
+      lg[tok] += ctc_beam_alpha_lm(lm.alpha, acc + lm.arc_logp[a]);
+    }
+    acc += lm.bo[s];
+    s = __builtin_amdgcn_readfirstlane(min(max(lm.bo_next[s], 0), lm.n_states - 1));
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  for (int v = lane; v < L; v += 64)
+    if (!((msk[v >> 5] >> (v & 31)) & 1u)) lg[v] += ctc_beam_alpha_lm(lm.alpha, acc + lm.arc_logp[v]);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// LM: the search of mi355x_transducer_beam_decode_fused (one n-gram model, p.lm); false: mi355x_transducer_beam_decode, whose
+// instantiations hold no instruction of the model's
+template <typename WT, bool TDT, bool LM>
 __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbP p) {
   constexpr int V = RbT<WT>::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char rb_smem[];
@@ -66,10 +124,12 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbP p) {
   WT* hnA = xA + RB_M * ldh;
   WT* aA = reinterpret_cast<WT*>(rb_smem);
   float* lgs = reinterpret_cast<float*>(rb_smem + (((size_t)RB_M * ldj * sizeof(WT) + 15) & ~(size_t)15));
+  unsigned* lmm = reinterpret_cast<unsigned*>(lgs + RB_M * ldl);   // LM: a bit per (row, label) behind the logits, (V1 + 31) / 32 words a row
   // the beam, two generations: [gen][slot]
   __shared__ float s_score[2][RB_M];
   __shared__ int s_live[2][RB_M], s_t[2][RB_M], s_sym[2][RB_M], s_n[2][RB_M], s_node[2][RB_M];
   __shared__ unsigned s_hash[2][RB_M];
+  __shared__ int s_lms[2][RB_M];   // LM: the automaton state of the hypothesis
   // per parent row: its best candidates, best first (score, ordinal = (blank ? 0 : label + 1) * 8 + duration index)
   __shared__ float c_cs[RB_M][RB_M];
   __shared__ int c_ord[RB_M][RB_M], c_cnt[RB_M];
@@ -87,6 +147,7 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbP p) {
   if (tid < 2 * RB_M) {
     const int g = tid >> 4, k = tid & 15;
     s_live[g][k] = (g == 0 && k == 0); s_score[g][k] = 0.f; s_t[g][k] = 0; s_sym[g][k] = 0; s_n[g][k] = 0; s_node[g][k] = 0; s_hash[g][k] = 0u;
+    if constexpr (LM) s_lms[g][k] = 1;   // the state behind <s>
   }
   // the start of the search is a prediction step like any other: slot 0, "extended" from a parent row of zeros (half 1, row 0) by
   // the start-of-sequence input (no label: x = 0)
@@ -232,6 +293,11 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbP p) {
       for (int v = lane; v < V1; v += 64) se += expf(lg[v] - mx);
       const float lse = mx + logf(wave_sum(se));
       for (int v = lane; v < V1; v += 64) lg[v] -= lse;   // lp, in place (each lane reads back its own)
+      if constexpr (LM) {   // lpf over the labels, in place (lanes write each other's labels: LDS is in order within a wave)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        rb_lm_row(p.lm, s_lms[cur][m], lg, lmm + m * ((V1 + 31) >> 5), V1, lane);
+      }
       float ld[TDT_MAXD];
       if constexpr (TDT) {
         float dm = -INFINITY, ds = 0.f;
@@ -353,9 +419,15 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbP p) {
       }
       live = live && first == lane;
       ext = ext && live;
+      int lms = 1;
+      if constexpr (LM) {   // a label moves the model to the state behind it; a blank and a finished hypothesis keep theirs
+        if (lane < RB_M) lms = s_lms[cur][par];
+        if (ext) ctc_beam_lm_lookup(p.lm, lms, tok, lms);
+      }
       if (lane < RB_M) {
         s_live[nx][lane] = live; s_score[nx][lane] = score; s_t[nx][lane] = t; s_sym[nx][lane] = sym; s_n[nx][lane] = n;
         s_node[nx][lane] = node; s_hash[nx][lane] = hash;
+        if constexpr (LM) s_lms[nx][lane] = lms;
         n_par[lane] = par; n_ext[lane] = ext; n_tok[lane] = ext ? tok : -1;
       }
       if (ext && node < n_nodes) { nodes[3LL * node] = pnode; nodes[3LL * node + 1] = tok; nodes[3LL * node + 2] = frame; }
@@ -402,9 +474,10 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbP p) {
 }
 
 // LDS of a launch: the larger of the prediction step's three A tiles and the joint step's A tile with the logits behind it
-static size_t rb_lds_bytes(int wbytes, int V, int H, int J, int N) {
+// (`mask_words`: the fused search's label masks behind the logits, per row)
+static size_t rb_lds_bytes(int wbytes, int V, int H, int J, int N, int mask_words) {
   const size_t pred = (size_t)3 * RB_M * (H + V) * wbytes;
-  const size_t joint = (((size_t)RB_M * (J + V) * wbytes + 15) & ~(size_t)15) + (size_t)RB_M * (N | 1) * sizeof(float);
+  const size_t joint = (((size_t)RB_M * (J + V) * wbytes + 15) & ~(size_t)15) + (size_t)RB_M * ((N | 1) + mask_words) * sizeof(float);
   return pred > joint ? pred : joint;
 }
 
@@ -413,9 +486,11 @@ extern "C" long long mi355x_transducer_beam_workspace_bytes(int B, int T, int H,
   return (long long)B * rb_ws_per_b(T, H, J, beam, max_out);
 }
 
-// every check is here; nothing is launched after a refusal
-static int beam_decode_impl(const mi355x_transducer_beam_desc* d, hipStream_t s) {
+// every check is here; nothing is launched after a refusal.  `fused`: the entry that takes a model (exactly one)
+static int beam_decode_impl(const mi355x_transducer_beam_desc* d, const mi355x_ctc_beam_fusion* models, int n_models, bool fused,
+                            hipStream_t s) {
   if (!d) return MI_ERR_ARG;
+  if (fused && (!models || n_models != 1)) return MI_ERR_ARG;
   if (!d->enc_proj || !d->emb || !d->w_ih || !d->w_hh || !d->b_ih || !d->b_hh || !d->w_pred || !d->b_pred || !d->w_out || !d->b_out)
     return MI_ERR_ARG;
   if (!d->tokens || !d->times || !d->out_len || !d->score || !d->n_hyp || !d->workspace) return MI_ERR_ARG;
@@ -431,11 +506,19 @@ static int beam_decode_impl(const mi355x_transducer_beam_desc* d, hipStream_t s)
   if (((size_t)d->w_ih | (size_t)d->w_hh | (size_t)d->w_pred | (size_t)d->w_out | (size_t)d->workspace) & 15) return MI_ERR_ARG;
   RbP p;
   p.dur = {};
+  p.lm = {};
+  if (fused) {   // an n-gram model over the labels 0 .. V1-2 (state 0's arc index is the label): the blank is the last class
+    const mi355x_ctc_beam_fusion& m = models[0];
+    if (!m.state_arc_begin || !m.arc_tok || !m.arc_logp || !m.arc_next || !m.state_bo || !m.state_bo_next || m.state_final) return MI_ERR_ARG;
+    if (m.n_states < 2 || m.n_arcs < V1 - 1 || !(m.alpha >= 0.f) || !(m.alpha < INFINITY) || d->blank != V1 - 1) return MI_ERR_ARG;
+    p.lm = {(const int*)m.state_arc_begin, (const int*)m.arc_tok, (const float*)m.arc_logp, (const int*)m.arc_next,
+            (const float*)m.state_bo, (const int*)m.state_bo_next, m.n_states, m.n_arcs, m.alpha, m.ub, nullptr};
+  }
   const bool tdt = d->D != 0 || d->durations;
   if (tdt && tdt_durations(d->D, d->durations, &p.dur)) return MI_ERR_ARG;
   p.ws_per_b = rb_ws_per_b(d->T, H, J, W, d->max_out);
   if (d->workspace_bytes < (long long)B * p.ws_per_b) return MI_ERR_ARG;
-  const size_t shm = rb_lds_bytes(bf ? 2 : 4, V, H, J, V1 + p.dur.D);
+  const size_t shm = rb_lds_bytes(bf ? 2 : 4, V, H, J, V1 + p.dur.D, fused ? (V1 + 31) >> 5 : 0);
   if (shm > 160 * 1024 - 8 * 1024) return MI_ERR_ARG;   // (the beam's scalars and candidate lists are static LDS)
   p.f = d->enc_proj; p.f_dt = d->f_dtype; p.ldf = d->ldf; p.enc_len = (const long long*)d->enc_len; p.emb = (const float*)d->emb;
   p.w_ih = d->w_ih; p.w_hh = d->w_hh; p.w_pred = d->w_pred; p.w_out = d->w_out;
@@ -444,9 +527,12 @@ static int beam_decode_impl(const mi355x_transducer_beam_desc* d, hipStream_t s)
   p.tokens = (int*)d->tokens; p.times = (int*)d->times; p.out_len = (int*)d->out_len; p.score = (float*)d->score; p.n_hyp = (int*)d->n_hyp;
   p.ws = (char*)d->workspace;
   p.B = B; p.T = d->T; p.J = J; p.H = H; p.V1 = V1; p.blank = d->blank; p.max_symbols = d->max_symbols; p.max_out = d->max_out; p.W = W;
-  static void (*const kernels[2][2])(RbP) = {{rnnt_beam_kernel<float, false>, rnnt_beam_kernel<float, true>},
-                                            {rnnt_beam_kernel<bf16_t, false>, rnnt_beam_kernel<bf16_t, true>}};
-  auto fn = kernels[bf][tdt];
+  static void (*const kernels[2][2][2])(RbP) = {
+      {{rnnt_beam_kernel<float, false, false>, rnnt_beam_kernel<float, false, true>},
+       {rnnt_beam_kernel<float, true, false>, rnnt_beam_kernel<float, true, true>}},
+      {{rnnt_beam_kernel<bf16_t, false, false>, rnnt_beam_kernel<bf16_t, false, true>},
+       {rnnt_beam_kernel<bf16_t, true, false>, rnnt_beam_kernel<bf16_t, true, true>}}};
+  auto fn = kernels[bf][tdt][fused];
   if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return MI_ERR_LAUNCH;
   MI_LAUNCH(fn, dim3(B), dim3(RB_THREADS), shm, s, p);
   return MI_OK;
@@ -454,6 +540,13 @@ static int beam_decode_impl(const mi355x_transducer_beam_desc* d, hipStream_t s)
 
 extern "C" int mi355x_transducer_beam_decode(const mi355x_transducer_beam_desc* d, void* stream) {
   mi_clear_errors();
-  const int rc = beam_decode_impl(d, (hipStream_t)stream);
+  const int rc = beam_decode_impl(d, nullptr, 0, false, (hipStream_t)stream);
+  return rc != MI_OK ? rc : mi_check_launch();
+}
+
+extern "C" int mi355x_transducer_beam_decode_fused(const mi355x_transducer_beam_desc* d, const mi355x_ctc_beam_fusion* models,
+                                                   int n_models, void* stream) {
+  mi_clear_errors();
+  const int rc = beam_decode_impl(d, models, n_models, true, (hipStream_t)stream);
   return rc != MI_OK ? rc : mi_check_launch();
 }

@@ -146,7 +146,8 @@ class EncDecRNNTModel(EncDecCTCModel):
             from ..modules import RNNTDecoding
             dcfg = dict(self._cfg.get("decoding") or {})
             from ..modules.rnnt_decoding import transducer_beam_from_config
-            beam = transducer_beam_from_config(dcfg)   # None: the greedy strategies; malsd_batch: the beam decoders' arguments
+            # None: the greedy strategies; malsd_batch: the beam decoders' arguments, with the model of `beam.ngram_lm_arpa`
+            beam = transducer_beam_from_config(dcfg, list(vocab) if vocab is not None else list(self.tokenizer.vocab))
             greedy = dict(dcfg.get("greedy") or {})
             ms = greedy.get("max_symbols", 10)
             # shallow fusion (`greedy.ngram_lm_arpa`, `greedy.boosting_tree`): None without those keys, and nothing changes

@@ -47,6 +47,12 @@ whose rule include/mi355x_asr.h states; parity with the reference's `malsd_batch
 `y_sequence`, `timestamp` and `score` (the sum of log-probabilities, blanks included, merged paths added; not length-normalised)
 and, with `return_best_hypothesis: false`, `n_best`.  One-shot, one LSTM layer, beam_size <= 16; everything else is refused by
 name (`transducer_beam_from_config`).
+With `beam: {ngram_lm_arpa, ngram_lm_alpha, ngram_lm_token_offset}` (or `fusion_models=[(NGramLM, alpha)]` on the beam decoders)
+the search is `ops.transducer_beam_decode_fused`: every label candidate gains alpha * ln p(label | the hypothesis' context) of one
+token-level n-gram model, a blank gains nothing, and `score` is the one sum; alpha = 0 gives the bits of the plain search.  The
+term of a hypothesis row is built row-wise in the kernel (one walk down the back-off chain for all labels), not by a look-up per
+label.  `beam.blank_lm_score_mode` / `beam.pruning_mode` are accepted as `no_score` / `late` only (spellings unverified against
+the reference).  A boosting tree, a second model, `beam.ngram_lm_model` and a weight without `ngram_lm_arpa` stay refused by name.
 
 Stateless prediction network (`modules.StatelessTransducerDecoder` as `decoder_model`): the greedy decoders search with
 `ops.stateless_greedy_decode` (csrc/stateless.hip; 16 streams per workgroup as the rows of one MFMA tile) over the decoder's
@@ -416,8 +422,17 @@ class BeamBatchedRNNTInfer(GreedyBatchedRNNTInfer):
 
     def __init__(self, decoder_model, joint_model, blank_index: int, beam_size: int = 4, max_symbols_per_step: Optional[int] = 10,
                  return_best_hypothesis: bool = True, score_norm: bool = False, preserve_alignments: bool = False,
-                 confidence_cfg=None, **unused):
+                 confidence_cfg=None, fusion_models=None, **unused):
+        from .boosting_tree import BoostingTree
         from .confidence import confidence_from
+        fusion_models = list(fusion_models) if fusion_models else None
+        for pair in fusion_models or ():
+            if isinstance(pair, (tuple, list)) and len(pair) and isinstance(pair[0], BoostingTree):
+                raise NotImplementedError("strategy 'malsd_batch' with a BoostingTree in `fusion_models` (`boosting_tree`): the beam "
+                                          "search fuses one n-gram model")
+        if fusion_models is not None and len(fusion_models) != 1:
+            raise NotImplementedError(f"strategy 'malsd_batch' with {len(fusion_models)} fusion models: the beam search fuses one "
+                                      "n-gram model")
         conf = confidence_from(confidence_cfg)
         if conf is not None and (conf.wants_tokens or conf.preserve_frame_confidence):
             raise NotImplementedError("strategy 'malsd_batch' with a `confidence_cfg` that preserves confidences: the beam search "
@@ -437,7 +452,8 @@ class BeamBatchedRNNTInfer(GreedyBatchedRNNTInfer):
         if int(getattr(decoder_model, "pred_rnn_layers", 1)) != 1:
             raise NotImplementedError(f"strategy 'malsd_batch' with `pred_rnn_layers` = {decoder_model.pred_rnn_layers}: the beam "
                                       "search runs one LSTM layer")
-        super().__init__(decoder_model, joint_model, blank_index, max_symbols_per_step=max_symbols_per_step)
+        super().__init__(decoder_model, joint_model, blank_index, max_symbols_per_step=max_symbols_per_step,
+                         fusion_models=fusion_models)
         self.beam_size, self.return_best_hypothesis = int(beam_size), bool(return_best_hypothesis)
 
     @torch.no_grad()
@@ -446,6 +462,8 @@ class BeamBatchedRNNTInfer(GreedyBatchedRNNTInfer):
         [B, W] best first, n_hyp i32 [B])"""
         f, args = self._project(encoder_output)
         lens = encoded_lengths.to(device=encoder_output.device, dtype=torch.int64).contiguous()
+        if self.fusion_models is not None:
+            return ops.transducer_beam_decode_fused(f, lens, *args, self.beam_size, self.fusion_models, durations=self.durations)
         return ops.transducer_beam_decode(f, lens, *args, self.beam_size, durations=self.durations)
 
     def fresh_hypotheses(self, batch_size: int, device=None):
@@ -481,13 +499,22 @@ class BeamBatchedTDTInfer(BeamBatchedRNNTInfer):
 
 
 _BEAM_KEYS = ("beam_size", "return_best_hypothesis", "max_symbols_per_step", "score_norm")
+# the n-gram model of the beam (read by `_ngram_lm_from_config` under the section name `beam`) and the two parameters of the
+# reference's fused beam whose only accepted values are what this search does: a blank gets no LM term, and nothing is pruned
+# before the LM term is added.  (The spellings of the two parameters and of their values were written from memory of the
+# reference and are unverified.)
+_BEAM_LM_KEYS = ("ngram_lm_arpa", "ngram_lm_alpha", "ngram_lm_token_offset")
+_BEAM_LM_MODES = {"blank_lm_score_mode": "no_score", "pruning_mode": "late"}
 
 
-def transducer_beam_from_config(decoding_cfg, what: str = "transducer"):
+def transducer_beam_from_config(decoding_cfg, vocabulary=None, what: str = "transducer"):
     """The transducer head's `decoding` section -> None for the greedy strategies, or for `strategy: malsd_batch` the keyword
     arguments of the beam decoders read from its `beam` sub-section (beam_size 4, return_best_hypothesis true,
-    max_symbols_per_step 10, score_norm false).  Every other strategy, and under malsd_batch `allow_cuda_graphs`, `ngram_lm_*` /
-    `boosting_tree*`, `preserve_alignments` and any key this search does not know, is refused by name."""
+    max_symbols_per_step 10, score_norm false) and, with `beam.ngram_lm_arpa` (an ARPA text file or an NGramLM), `ngram_lm_alpha`
+    and `ngram_lm_token_offset`, `fusion_models=[(NGramLM, alpha)]` (`vocabulary`: the labels in id order; None: the section is
+    only checked).  `blank_lm_score_mode` / `pruning_mode` are accepted as `no_score` / `late` only.  Every other strategy, and
+    under malsd_batch `allow_cuda_graphs`, `ngram_lm_model`, a weight without `ngram_lm_arpa`, `boosting_tree*`,
+    `preserve_alignments` and any key this search does not know, is refused by name."""
     dcfg = dict(decoding_cfg or {})
     strategy = dcfg.get("strategy", "greedy_batch")
     if strategy in ("greedy", "greedy_batch"):
@@ -504,10 +531,26 @@ def transducer_beam_from_config(decoding_cfg, what: str = "transducer"):
             continue
         if (key.startswith("ngram_lm") or key.startswith("boosting_tree")) and not value:
             continue
+        if key in _BEAM_LM_KEYS and beam.get("ngram_lm_arpa") is not None:
+            continue
+        if key in _BEAM_LM_MODES:
+            if value is None or value == _BEAM_LM_MODES[key]:
+                continue
+            raise NotImplementedError(f"{what} decoding: strategy 'malsd_batch' with `beam.{key}` = {value!r} (implemented: "
+                                      f"'{_BEAM_LM_MODES[key]}')")
         raise NotImplementedError(f"{what} decoding: strategy 'malsd_batch' with `beam.{key}`")
-    return dict(beam_size=int(beam.get("beam_size", 4)), return_best_hypothesis=bool(beam.get("return_best_hypothesis", True)),
-                max_symbols_per_step=beam.get("max_symbols_per_step", 10), score_norm=bool(beam.get("score_norm", False)),
-                preserve_alignments=False)
+    out = dict(beam_size=int(beam.get("beam_size", 4)), return_best_hypothesis=bool(beam.get("return_best_hypothesis", True)),
+               max_symbols_per_step=beam.get("max_symbols_per_step", 10), score_norm=bool(beam.get("score_norm", False)),
+               preserve_alignments=False)
+    if beam.get("ngram_lm_arpa"):
+        from .ctc_decoding import _ngram_lm_from_config
+        alpha = float(beam.get("ngram_lm_alpha") or 0.0)
+        if alpha < 0:
+            raise ValueError(f"{what} decoding: `beam.ngram_lm_alpha` must be >= 0; got {alpha}")
+        lm = _ngram_lm_from_config(beam, vocabulary, what, sec="beam")
+        if lm is not None:
+            out["fusion_models"] = [(lm, alpha)]
+    return out
 
 
 def transducer_fusion_from_config(greedy, vocabulary=None, text_to_ids=None, what: str = "transducer"):
@@ -531,7 +574,8 @@ def transducer_fusion_from_config(greedy, vocabulary=None, text_to_ids=None, wha
 class RNNTDecoding:
     """`strategy: greedy_batch` of AbstractRNNTDecoding (rnnt_decoding.py:216-330) for a character / word-piece vocabulary;
     blank id = len(vocabulary) (rnnt_decoding.py:1170).  `fusion_models` (None: the search without models): what
-    `transducer_fusion_from_config` reads from `decoding.greedy`."""
+    `transducer_fusion_from_config` reads from `decoding.greedy`; under `strategy: malsd_batch` they stay refused, and the beam's
+    n-gram model is `beam["fusion_models"]`, what `transducer_beam_from_config` reads from `decoding.beam`."""
 
     def __init__(self, decoder, joint, vocabulary: Optional[Sequence[str]] = None, max_symbols: Optional[int] = 10,
                  tokenizer=None, model_type: str = "rnnt", durations: Optional[Sequence[int]] = None, confidence_cfg=None,
@@ -554,7 +598,7 @@ class RNNTDecoding:
                                                              big_blank_durations, max_symbols_per_step=max_symbols,
                                                              confidence_cfg=self.confidence_cfg, fusion_models=fusion_models)
         elif beam is not None:   # strategy malsd_batch: the keyword arguments `transducer_beam_from_config` read
-            if fusion_models:
+            if fusion_models:   # (the greedy section's; the beam's own model travels in `beam`: `beam.ngram_lm_arpa`)
                 raise NotImplementedError("strategy 'malsd_batch' with fusion models (`ngram_lm_*` / `boosting_tree`)")
             beam = dict(beam, confidence_cfg=self.confidence_cfg)
             self.decoding = (BeamBatchedTDTInfer(decoder, joint, self.blank_id, durations, **beam) if model_type == "tdt"

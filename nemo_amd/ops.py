@@ -1181,6 +1181,31 @@ def transducer_beam_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_i
     the rule): the arguments of rnnt_greedy_decode (`durations` given: TDT, w_out / b_out with V1 + len(durations) rows), one LSTM
     layer, beam_size in 1..16.  -> (tokens i32 [B, beam, max_out] -1 padded, frame indices likewise, lengths i32 [B, beam], score
     f32 [B, beam] best first and -inf in the empty ranks, n_hyp i32 [B])"""
+    return _beam_search("transducer_beam_decode", enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred,
+                        w_out, ld_out, b_out, blank, max_symbols, beam_size, durations, max_out, None)
+
+
+def transducer_beam_decode_fused(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                                 b_out, blank, max_symbols, beam_size, models, durations=None, max_out=None):
+    """transducer_beam_decode with shallow fusion of one n-gram model (mi355x_transducer_beam_decode_fused, whose rule
+    include/mi355x_asr.h states): `models` = [(NGramLM, alpha)] over the V1 - 1 labels, blank = V1 - 1.  Every label candidate gains
+    alpha * ln p(label | the hypothesis' context); blanks gain nothing; `score` is the one sum.  alpha = 0 gives the bits of
+    transducer_beam_decode.  A BoostingTree and a second model are refused by name.  -> transducer_beam_decode's tuple"""
+    what = "transducer_beam_decode_fused"
+    from .modules.boosting_tree import BoostingTree
+    models = _transducer_fusion_check(what, models, emb.shape[0])
+    if any(isinstance(m, BoostingTree) for m, _ in models):
+        raise NotImplementedError(f"{what}: a BoostingTree (the beam search fuses one n-gram model; trees are fused by the greedy "
+                                  "search and the CTC beam search)")
+    if len(models) != 1:
+        raise NotImplementedError(f"{what}: {len(models)} models (the beam search fuses one n-gram model)")
+    return _beam_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out,
+                        b_out, blank, max_symbols, beam_size, durations, max_out, models)
+
+
+def _beam_search(what, enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_ih, b_hh, w_pred, ld_pred, b_pred, w_out, ld_out, b_out,
+                 blank, max_symbols, beam_size, durations, max_out, models):
+    """the launch behind transducer_beam_decode (`models` None) and transducer_beam_decode_fused (`models` checked by it)"""
     B, T, J = enc_proj.shape
     V1, H = emb.shape
     W = int(beam_size)
@@ -1192,7 +1217,7 @@ def transducer_beam_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_i
     score = torch.empty(B, W, dtype=torch.float32, device=dev)
     nbytes = lib.mi355x_transducer_beam_workspace_bytes(B, T, H, J, W, max_out)
     if nbytes < 0:
-        raise ValueError(f"transducer_beam_decode: beam_size in 1..16 and positive sizes; got beam_size = {W}, B, T, H, J, max_out = "
+        raise ValueError(f"{what}: beam_size in 1..16 and positive sizes; got beam_size = {W}, B, T, H, J, max_out = "
                          f"{(B, T, H, J, max_out)}")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     d = TransducerBeamDesc(
@@ -1205,7 +1230,11 @@ def transducer_beam_decode(enc_proj, enc_len, emb, w_ih, ld_ih, w_hh, ld_hh, b_i
     if durations is not None:
         d.D, dur = _tdt_durations(durations)
         d.durations = C.addressof(dur)
-    check(lib.mi355x_transducer_beam_decode(C.byref(d), _stream()), "transducer_beam_decode")
+    if models is None:
+        check(lib.mi355x_transducer_beam_decode(C.byref(d), _stream()), what)
+    else:
+        arr, tables = _ctc_beam_fusion_array(models, enc_proj)   # (`tables` live to the end of the call: the launch is enqueued)
+        check(lib.mi355x_transducer_beam_decode_fused(C.byref(d), C.addressof(arr), len(arr), _stream()), what)
     return tokens, times, out_len, score, n_hyp
 
 
